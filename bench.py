@@ -13,9 +13,13 @@ Workload at N=1: BASELINE.json configs[2] -- 128x128 sensor, 500 000 stored view
 single-GPU configuration), synthetic views (navsim_amd.synth, generated on the device).  With N>1 every rank holds
 its own 500 000-view shard of an N*500 000-view library -- at N=8 that is configs[3], 4 M views -- and the per-step
 exchange is one RCCL collective (navsim_amd/sharded.py).  configs[1] (64x64, 50 000 views, 16 headings), the agent
-loop, the ensemble share of configs[4] and the ssd_f32 metric are timed after the headline as secondary blocks.
+loop, the ensemble share of configs[4] and the ssd_f32 metric are timed after the headline as secondary blocks with --full.
 
-    python bench.py --gpus N --steps K --warmup W
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything else: the second
+pass on resident patches (`scoring_only`), the known-answer step, the roofline (kernel events, read-ceiling probe), the
+exchange timing, the secondary blocks and the CPU baseline.  --dump-outputs DIR writes what the last timed step returned.
+
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -369,6 +373,17 @@ def ssd_u8_block(device_index, F, h, w, A, steps):
                          "bytes_basis": "streamed library bytes (1 B/px x passes of 32 headings) = the algorithmic bytes of a uint8 library"}}
 
 
+DUMP_KEYS = ("best_idex", "best_view", "step_familiarity", "angle_familiarity")
+
+
+def dump_outputs(dirname, res):
+    """What the step hands its caller, every rank's path alike: the decision (heading, view, its familiarity) and every
+    heading's maximum, as DIR/<name>.npy in float64 (view indices are exact in it)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name in DUMP_KEYS:
+        np.save(os.path.join(dirname, name + ".npy"), np.atleast_1d(np.asarray(res[name], dtype=np.float64)))
+
+
 def workload_name(w, h, F, A, cw, world):
     named = ""
     if w == h:
@@ -564,25 +579,31 @@ def main():
     ap.add_argument("--chem-weight", type=float, default=0.25,
                     help="0 < cw < 1 keeps all three reference bytes per pixel (H,S,V) algorithmically live")
     ap.add_argument("--full-range-s", action="store_true", help="headline library with saturation 0..127 instead of {0, 127}: the "
-                    "mixed layout (value bit planes + saturation bytes); the default run times it as the `full_range_s` block")
+                    "mixed layout (value bit planes + saturation bytes); a --full run times it as the `full_range_s` block")
     ap.add_argument("--seed", type=int, default=20261004)
-    ap.add_argument("--cpu-views", type=int, default=8000, help="views in the CPU-baseline sample (0 = skip); the "
+    ap.add_argument("--cpu-views", type=int, default=8000, help="--full: views in the CPU-baseline sample (0 = skip); the "
                     "default is ~15 s of one host core at the headline shape")
-    ap.add_argument("--agent-steps", type=int, default=2000, help="steps of the full agent loop timed at N=1 (0 = skip)")
-    ap.add_argument("--event-every", type=int, default=1, help="bracket every n-th timed step's scoring kernel with "
+    ap.add_argument("--agent-steps", type=int, default=2000, help="--full: steps of the agent loop timed at N=1 (0 = skip)")
+    ap.add_argument("--event-every", type=int, default=1, help="--full: bracket every n-th timed step's scoring kernel with "
                     "HIP events (roofline.kernel_ms); an event pair costs ~5 us of stream time")
-    ap.add_argument("--batch-agents", type=int, default=32, help="agents of the ensemble block (configs[4] share of one "
+    ap.add_argument("--batch-agents", type=int, default=32, help="--full: agents of the ensemble block (configs[4] share of one "
                     "GPU; 0 = skip)")
-    ap.add_argument("--secondary", type=int, default=1, help="1: also time configs[1] (64x64, 50 000 views, 16 headings) "
+    ap.add_argument("--secondary", type=int, default=1, help="--full, 1: also time configs[1] (64x64, 50 000 views, 16 headings) "
                     "at N=1; 0 = skip")
     ap.add_argument("--exchange", choices=["rccl", "mailbox"], default="rccl", help="per-step exchange between ranks: one RCCL "
                     "collective (default), or the single-node mailbox in host-shared memory (no collective kernel)")
-    ap.add_argument("--skip-known-answer", action="store_true", help="experiments with deliberately broken kernels only")
+    ap.add_argument("--skip-known-answer", action="store_true", help="--full: experiments with deliberately broken kernels only")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed even with one rank "
                     "(exercises the RCCL exchange path on a single GPU)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo only to "
                     "rehearse the exchange on a box with fewer GPUs than ranks)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: "
+                    "scoring_only, the known-answer step, roofline, exchange timing, the secondary blocks, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one returned as "
+                    "DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # Libraries (RCCL's version banner, HIP warnings) write to fd 1; keep stdout for the ONE JSON line.
     json_fd = os.dup(1)
@@ -650,61 +671,69 @@ def main():
 
     for i in range(args.warmup):
         one_step(args.seed + 1 + i)
-    # HIP events around the scoring kernel (on the engine's own stream) of the timed steps
-    eng.profile_kernel(True, every=args.event_every)
+    # HIP events around the scoring kernel (on the engine's own stream) of the timed steps: the roofline's kernel time
+    if args.full:
+        eng.profile_kernel(True, every=args.event_every)
     fence()
     t0 = time.perf_counter()
     for i in range(args.steps):
         res = one_step(args.seed + 1000 + i)
     fence()
     dt = time.perf_counter() - t0
-    kern_ms_total, kern_n = eng.profile_read()
-    eng.profile_kernel(False)
-    # second figure: the same K steps on the patches now resident (no preparation kernels)
-    fence()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        one_step()
-    fence()
-    dt_resident = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
 
-    # Known-answer step, outside the timed region: heading a* looks at a view stored on the LAST rank, so the global
-    # decision has to come through the exchange (a stale or mis-ordered record gives the previous answer instead).
-    from navsim_amd import synth
-    a_star, f_star = A // 2, (world - 1) * F + (12345 % F)
-    probe = synth.synth_patches(args.seed, A, h, w, full_range_s=args.full_range_s)
-    probe[a_star] = synth.synth_views(args.seed, 1, h, w, first_view=f_star, full_range_s=args.full_range_s)[0]
-    eng.upload_patches(probe)
-    chk = one_step()
-    ok = args.skip_known_answer or ((int(chk["best_idex"]), int(chk["best_view"])) == (a_star, f_star) and
-                                    float(chk["step_familiarity"]) == float(h * w))
-    if not ok:
-        sys.stderr.write("rank %d: known-answer step FAILED\n" % rank)
-    if use_dist:                                                 # fail together: nobody is left waiting in a collective
-        flag = torch.tensor([1 if ok else 0], dtype=torch.int32, device="cuda" if args.backend == "nccl" else "cpu")
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        all_ok = bool(flag.item())
-    else:
-        all_ok = ok
-    if not all_ok:
-        raise SystemExit("rank %d: known-answer step failed: got heading %d view %d familiarity %r, expected %d %d %r"
-                         % (rank, chk["best_idex"], chk["best_view"], chk["step_familiarity"], a_star, f_star, float(h * w)))
-
+    dt_resident = None
     rccl_ranks, exchange_us = None, None
-    if exchange is not None and hasattr(exchange, "rccl_ranks"):
-        try:
-            rccl_ranks = exchange.rccl_ranks()                      # ncclCommCount of the communicator the per-step collective uses
-            exchange_us = exchange.exchange_only_us(50)             # every rank takes part: a collective
-        except Exception as e:                                      # noqa: BLE001
-            sys.stderr.write("rank %d: exchange facts unavailable: %r\n" % (rank, e))
+    if args.full:
+        kern_ms_total, kern_n = eng.profile_read()
+        eng.profile_kernel(False)
+        # second figure: the same K steps on the patches now resident (no preparation kernels)
+        fence()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            one_step()
+        fence()
+        dt_resident = time.perf_counter() - t0
+
+        # Known-answer step, outside the timed region: heading a* looks at a view stored on the LAST rank, so the global
+        # decision has to come through the exchange (a stale or mis-ordered record gives the previous answer instead).
+        from navsim_amd import synth
+        a_star, f_star = A // 2, (world - 1) * F + (12345 % F)
+        probe = synth.synth_patches(args.seed, A, h, w, full_range_s=args.full_range_s)
+        probe[a_star] = synth.synth_views(args.seed, 1, h, w, first_view=f_star, full_range_s=args.full_range_s)[0]
+        eng.upload_patches(probe)
+        chk = one_step()
+        ok = args.skip_known_answer or ((int(chk["best_idex"]), int(chk["best_view"])) == (a_star, f_star) and
+                                        float(chk["step_familiarity"]) == float(h * w))
+        if not ok:
+            sys.stderr.write("rank %d: known-answer step FAILED\n" % rank)
+        if use_dist:                                             # fail together: nobody is left waiting in a collective
+            flag = torch.tensor([1 if ok else 0], dtype=torch.int32, device="cuda" if args.backend == "nccl" else "cpu")
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            all_ok = bool(flag.item())
+        else:
+            all_ok = ok
+        if not all_ok:
+            raise SystemExit("rank %d: known-answer step failed: got heading %d view %d familiarity %r, expected %d %d %r"
+                             % (rank, chk["best_idex"], chk["best_view"], chk["step_familiarity"], a_star, f_star, float(h * w)))
+
+        if exchange is not None and hasattr(exchange, "rccl_ranks"):
+            try:
+                rccl_ranks = exchange.rccl_ranks()                  # ncclCommCount of the communicator the per-step collective uses
+                exchange_us = exchange.exchange_only_us(50)         # every rank takes part: a collective
+            except Exception as e:                                  # noqa: BLE001
+                sys.stderr.write("rank %d: exchange facts unavailable: %r\n" % (rank, e))
     if use_dist:
-        t = torch.tensor([dt, dt_resident], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
+        times = [dt] if dt_resident is None else [dt, dt_resident]
+        t = torch.tensor(times, dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt, dt_resident = float(t[0].item()), float(t[1].item())
+        dt = float(t[0].item())
+        if dt_resident is not None:
+            dt_resident = float(t[1].item())
 
     if rank == 0:
         comparisons = float(world) * F * A * args.steps
-        kern_ms = kern_ms_total / max(kern_n, 1)
         shape = eng.workgroup_shape(A)
         workload = workload_name(w, h, F, A, cw, world) + (", saturation 0..127 (mixed layout)" if args.full_range_s else "")
         out = {
@@ -744,9 +773,6 @@ def main():
                      if args.backend == "nccl" else args.backend)),
             },
             "nav_steps_per_s": args.steps / dt,
-            "scoring_only": {"value": comparisons / dt_resident, "ms_per_step": dt_resident / args.steps * 1e3,
-                             "what": "the same K steps on resident patches (no k_patch_prep): the figure "
-                                     "rounds 1-2 reported as the headline"},
             "layout": {
                 "chosen": ("thermometer bit planes on the matrix cores" if shape == 6 else "byte planes, v_sad_u8"),
                 "why": ("every stored byte plane takes few values (%d + %d planes per pixel = %.3g B/px instead of the "
@@ -758,10 +784,15 @@ def main():
                                        "lossless re-coding of this library's few levels, a compression ratio and not a bandwidth",
             },
             "best_heading": int(res["best_idex"]),
-            "known_answer_step": "SKIPPED" if args.skip_known_answer else "ok on every rank (heading %d, view %d of %d, through the exchange)" % (a_star, f_star, world * F),
-            "roofline": roofline_block(eng, info, shape, kern_ms, kern_n, F, h, w, A, cw, workload),
         }
-        extras = world == 1 and not args.force_dist
+        if args.full:
+            out["scoring_only"] = {"value": comparisons / dt_resident, "ms_per_step": dt_resident / args.steps * 1e3,
+                                   "what": "the same K steps on resident patches (no k_patch_prep): the figure "
+                                           "rounds 1-2 reported as the headline"}
+            out["known_answer_step"] = "SKIPPED" if args.skip_known_answer else "ok on every rank (heading %d, view %d of %d, through the exchange)" % (a_star, f_star, world * F)
+            kern_ms = kern_ms_total / max(kern_n, 1)
+            out["roofline"] = roofline_block(eng, info, shape, kern_ms, kern_n, F, h, w, A, cw, workload)
+        extras = args.full and world == 1 and not args.force_dist
         eng.clear_library()                                      # make room for the secondary blocks
         if extras and args.secondary:
             try:
@@ -815,46 +846,47 @@ def main():
                 out["ensemble"] = ensemble_comparisons_per_s(64, 64, 16, cw, args.seed, args.batch_agents, 100000, 5)
             except Exception as e:                               # noqa: BLE001 - an extra block must not cost the JSON line
                 out["ensemble"] = {"error": repr(e)}
-        if world == 1 and args.cpu_views > 0:
+        if args.full and world == 1 and args.cpu_views > 0:
             out["cpu_baseline"] = cpu_baseline(h, w, A, cw, args.seed, min(args.cpu_views, F))
         else:
             out["cpu_baseline"] = None
-        # The figures of the secondary blocks as scalars INSIDE `roofline` (the driver's record keeps config / roofline /
-        # cpu_baseline whole and only lists other keys): every number DESIGN.md section 4 quotes can be read from here.
-        def g(block, *path):
-            v = out.get(block)
-            for k in path:
-                v = v.get(k) if isinstance(v, dict) else None
-            return v
-        def us(x):
-            return None if x is None else x * 1e3
-        out["roofline"]["secondary"] = {
-            "c2_step_ms": out["ms_per_step"], "c2_kernel_ms": g("roofline", "kernel_ms"), "c2_scoring_only_ms": g("scoring_only", "ms_per_step"),
-            "c1_step_us": us(g("configs1", "ms_per_step")), "c1_scoring_only_step_us": us(g("configs1", "scoring_only", "ms_per_step")),
-            "c1_kernel_us": us(g("configs1", "roofline", "kernel_ms")), "c1_frac": g("configs1", "roofline", "frac"),
-            "c1_view_comparisons_per_s": g("configs1", "value"),
-            "full_s_ms": g("full_range_s", "ms_per_step"), "full_s_kernel_ms": g("full_range_s", "roofline", "kernel_ms"),
-            "full_s_frac": g("full_range_s", "roofline", "frac"), "full_s_valu_frac": g("full_range_s", "roofline", "valu", "frac"),
-            "byte_path_ms": g("byte_path", "ms_per_step"), "byte_path_kernel_ms": g("byte_path", "roofline", "kernel_ms"),
-            "byte_path_frac": g("byte_path", "roofline", "frac"), "byte_path_valu_frac": g("byte_path", "roofline", "valu", "frac"),
-            "generic_hue_step_us": us(g("generic_hue", "ms_per_step")), "generic_hue_kernel_us": us(g("generic_hue", "roofline", "kernel_ms")),
-            "generic_hue_frac": g("generic_hue", "roofline", "frac"), "generic_hue_valu_frac": g("generic_hue", "roofline", "valu", "frac"),
-            "ssd_f32_kernel_us": us(g("ssd_f32", "roofline", "kernel_ms")), "ssd_f32_frac": g("ssd_f32", "roofline", "frac"),
-            "ssd_f32_step_us": us(g("ssd_f32", "ms_per_step")), "ssd_f32_direct_kernel_us": us(g("ssd_f32", "direct_form", "kernel_ms")),
-            "ssd_f32_c2_kernel_ms": g("ssd_f32_configs2", "roofline", "kernel_ms"), "ssd_f32_c2_frac": g("ssd_f32_configs2", "roofline", "frac"),
-            "ssd_f32_c2_step_ms": g("ssd_f32_configs2", "ms_per_step"), "ssd_f32_c2_direct_kernel_ms": g("ssd_f32_configs2", "direct_form", "kernel_ms"),
-            "ssd_f32_c2_mfma_frac": g("ssd_f32_configs2", "roofline", "mfma", "frac"),
-            "ssd_u8_kernel_us": us(g("ssd_u8", "roofline", "kernel_ms")), "ssd_u8_frac": g("ssd_u8", "roofline", "frac"),
-            "ssd_u8_step_us": us(g("ssd_u8", "ms_per_step")),
-            "ens_ms": g("ensemble", "ms_per_ensemble_step"), "ens_uploaded_ms": g("ensemble", "uploaded", "ms_per_ensemble_step"),
-            "ens_mfma_frac": g("ensemble", "mfma_frac_of_peak"), "ens_mfma_form": g("ensemble", "mfma_form"),
-            "ens_view_comparisons_per_s": g("ensemble", "view_comparisons_per_s"),
-            "agent_steps_per_s": g("agent", "nav_steps_per_s"), "agent_steps_per_s_fake": g("agent", "nav_steps_per_s_fake"),
-            "agent_median_step_us": g("agent", "median_step_us_and_steps_over_4x_median", "not_fake", "median_step_us"),
-            "agent_ensemble_of_32_steps_per_s": g("agent", "ensemble_of_32_nav_steps_per_s"),
-            "agent_ensemble_of_32_steps_per_s_with_metrics": g("agent", "ensemble_of_32_nav_steps_per_s_with_metrics"),
-            "cpu_one_core_cmp_per_s": g("cpu_baseline", "value"), "cpu_16_threads_cmp_per_s": g("cpu_baseline", "multicore", "value"),
-        }
+        if args.full:
+            # The figures of the secondary blocks as scalars INSIDE `roofline` (a record that keeps config / roofline /
+            # cpu_baseline whole and only lists other keys): every number DESIGN.md section 4 quotes can be read from here.
+            def g(block, *path):
+                v = out.get(block)
+                for k in path:
+                    v = v.get(k) if isinstance(v, dict) else None
+                return v
+            def us(x):
+                return None if x is None else x * 1e3
+            out["roofline"]["secondary"] = {
+                "c2_step_ms": out["ms_per_step"], "c2_kernel_ms": g("roofline", "kernel_ms"), "c2_scoring_only_ms": g("scoring_only", "ms_per_step"),
+                "c1_step_us": us(g("configs1", "ms_per_step")), "c1_scoring_only_step_us": us(g("configs1", "scoring_only", "ms_per_step")),
+                "c1_kernel_us": us(g("configs1", "roofline", "kernel_ms")), "c1_frac": g("configs1", "roofline", "frac"),
+                "c1_view_comparisons_per_s": g("configs1", "value"),
+                "full_s_ms": g("full_range_s", "ms_per_step"), "full_s_kernel_ms": g("full_range_s", "roofline", "kernel_ms"),
+                "full_s_frac": g("full_range_s", "roofline", "frac"), "full_s_valu_frac": g("full_range_s", "roofline", "valu", "frac"),
+                "byte_path_ms": g("byte_path", "ms_per_step"), "byte_path_kernel_ms": g("byte_path", "roofline", "kernel_ms"),
+                "byte_path_frac": g("byte_path", "roofline", "frac"), "byte_path_valu_frac": g("byte_path", "roofline", "valu", "frac"),
+                "generic_hue_step_us": us(g("generic_hue", "ms_per_step")), "generic_hue_kernel_us": us(g("generic_hue", "roofline", "kernel_ms")),
+                "generic_hue_frac": g("generic_hue", "roofline", "frac"), "generic_hue_valu_frac": g("generic_hue", "roofline", "valu", "frac"),
+                "ssd_f32_kernel_us": us(g("ssd_f32", "roofline", "kernel_ms")), "ssd_f32_frac": g("ssd_f32", "roofline", "frac"),
+                "ssd_f32_step_us": us(g("ssd_f32", "ms_per_step")), "ssd_f32_direct_kernel_us": us(g("ssd_f32", "direct_form", "kernel_ms")),
+                "ssd_f32_c2_kernel_ms": g("ssd_f32_configs2", "roofline", "kernel_ms"), "ssd_f32_c2_frac": g("ssd_f32_configs2", "roofline", "frac"),
+                "ssd_f32_c2_step_ms": g("ssd_f32_configs2", "ms_per_step"), "ssd_f32_c2_direct_kernel_ms": g("ssd_f32_configs2", "direct_form", "kernel_ms"),
+                "ssd_f32_c2_mfma_frac": g("ssd_f32_configs2", "roofline", "mfma", "frac"),
+                "ssd_u8_kernel_us": us(g("ssd_u8", "roofline", "kernel_ms")), "ssd_u8_frac": g("ssd_u8", "roofline", "frac"),
+                "ssd_u8_step_us": us(g("ssd_u8", "ms_per_step")),
+                "ens_ms": g("ensemble", "ms_per_ensemble_step"), "ens_uploaded_ms": g("ensemble", "uploaded", "ms_per_ensemble_step"),
+                "ens_mfma_frac": g("ensemble", "mfma_frac_of_peak"), "ens_mfma_form": g("ensemble", "mfma_form"),
+                "ens_view_comparisons_per_s": g("ensemble", "view_comparisons_per_s"),
+                "agent_steps_per_s": g("agent", "nav_steps_per_s"), "agent_steps_per_s_fake": g("agent", "nav_steps_per_s_fake"),
+                "agent_median_step_us": g("agent", "median_step_us_and_steps_over_4x_median", "not_fake", "median_step_us"),
+                "agent_ensemble_of_32_steps_per_s": g("agent", "ensemble_of_32_nav_steps_per_s"),
+                "agent_ensemble_of_32_steps_per_s_with_metrics": g("agent", "ensemble_of_32_nav_steps_per_s_with_metrics"),
+                "cpu_one_core_cmp_per_s": g("cpu_baseline", "value"), "cpu_16_threads_cmp_per_s": g("cpu_baseline", "multicore", "value"),
+            }
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if exchange is not None:
         exchange.close()

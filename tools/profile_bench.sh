@@ -21,8 +21,8 @@ if [ -n "$PROFILE_CMD" ]; then
   LONG="$ROOT/$PROFILE_CMD"
   SHORT="$ROOT/$PROFILE_CMD"
 else
-  LONG="$ROOT/bench.py --steps $PROFILE_STEPS --warmup 20 --cpu-views 0 --batch-agents 0 --secondary 0 --agent-steps 0 $BENCH_ARGS"
-  SHORT="$ROOT/bench.py --steps 20 --warmup 5 --cpu-views 0 --batch-agents 0 --secondary 0 --agent-steps 0 $BENCH_ARGS"
+  LONG="$ROOT/bench.py --full --steps $PROFILE_STEPS --warmup 20 --cpu-views 0 --batch-agents 0 --secondary 0 --agent-steps 0 $BENCH_ARGS"
+  SHORT="$ROOT/bench.py --full --steps 20 --warmup 5 --cpu-views 0 --batch-agents 0 --secondary 0 --agent-steps 0 $BENCH_ARGS"
 fi
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $LONG > $OUT/bench_under_trace.json 2> $OUT/trace.err
 if [ -z "$PROFILE_CMD" ]; then

@@ -3,7 +3,7 @@ OUT=${GRAFT_REPO_ROOT}/gpurun_out/ens_trace
 rm -rf $OUT; mkdir -p $OUT
 ROOT=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $ROOT/bench.py --steps 3 --warmup 1 --views 50000 --sensor 64 --headings 16 --cpu-views 0 --secondary 0 --agent-steps 0 > /dev/null 2> $OUT/err.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -- python3 $ROOT/bench.py --full --steps 3 --warmup 1 --views 50000 --sensor 64 --headings 16 --cpu-views 0 --secondary 0 --agent-steps 0 > /dev/null 2> $OUT/err.log
 python3 - <<PY
 import csv, glob, os
 t = max(glob.glob("$OUT/**/*_kernel_trace.csv", recursive=True), key=os.path.getsize)

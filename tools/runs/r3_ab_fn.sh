@@ -1,13 +1,16 @@
 # run <name> <bench args...>: one bench.py run (headline only), one line of result; env in front of the call
-mkdir -p gpurun_out/ab
+ROOT=${ROOT:-$(pwd)}
+OUT=${OUT:-$ROOT/results}
+mkdir -p "$OUT"
+mkdir -p $OUT/ab
 run() {
   name=$1; shift
-  timeout -k 10 240 python bench.py "$@" --cpu-views 0 --batch-agents 0 --secondary 0 --agent-steps 0 > gpurun_out/ab/$name.json 2> gpurun_out/ab/$name.err || echo "$name FAILED"
-  python - "$name" <<'PY'
+  timeout -k 10 240 python bench.py --full "$@" --cpu-views 0 --batch-agents 0 --secondary 0 --agent-steps 0 > $OUT/ab/$name.json 2> $OUT/ab/$name.err || echo "$name FAILED"
+  python - "$name" <<PY
 import json,sys
 n=sys.argv[1]
 try:
-    d=json.loads(open('gpurun_out/ab/%s.json'%n).read().strip().splitlines()[-1])
+    d=json.loads(open('$OUT/ab/%s.json'%n).read().strip().splitlines()[-1])
     print("%-22s step %8.1f us  scoring_only %8.1f us  kernel %8.1f us  frac %.3f" % (n, d['ms_per_step']*1e3, d['scoring_only']['ms_per_step']*1e3, d['roofline']['kernel_ms']*1e3, d['roofline']['frac']))
 except Exception as e:
     print(n, "no result", e)

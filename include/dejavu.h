@@ -103,6 +103,8 @@ typedef struct dv_lib_info {
                                    value bit planes, a v_sad_u8 pass the saturation BYTE planes (bit_planes_hs is 0 and a step
                                    streams bit_tile_bytes + the saturation planes' share of tile_bytes) */
     int32_t reserved0;
+    double weight_lo, weight_hi; /* chem_weights the layout serves for a weighted batch (dv_step_batch_weighted): [0, 1] when both
+                                   sums are stored, [0, 0] without saturation planes, [1, 1] without the value plane */
 } dv_lib_info;
 
 /* ---- lifetime ---------------------------------------------------------- */
@@ -142,6 +144,14 @@ int dv_generate_library_ex(dv_ctx *ctx, uint64_t seed, int64_t n_views, int h, i
                            int full_range_s);
 int dv_clear_library(dv_ctx *ctx);
 int dv_get_library_info(const dv_ctx *ctx, dv_lib_info *out);
+/*
+ * The chem_weights later ingests (dv_set_library, dv_set_library_from_poses, dv_generate_library[_ex]) lay the library out for:
+ * saturation planes are stored iff hi > 0, the value plane iff lo < 1, so that a weighted batch may give every agent a weight in
+ * [lo, hi].  The ingest's own chem_weight must lie in the range (else the ingest fails with DV_ERR_INVALID); it stays the weight of
+ * every unweighted step.  lo > hi (the default) restores the ingest's own weight alone.  dv_append_library* keep the layout
+ * they find.
+ */
+int dv_set_weight_range(dv_ctx *ctx, double lo, double hi);
 /*
  * Host arithmetic of the bit-plane layout (no context, no GPU): the thermometer planes of one stored byte plane from
  * the 256-bit presence map of its values (bit v of presence[v / 32] = value v occurs).  One plane per gap between
@@ -187,6 +197,15 @@ int dv_sense_step(dv_ctx *ctx, double x, double y, const double *angles, int n_h
  */
 int dv_sense_step_batch(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
                         uint32_t flags, dv_step_result *results);
+/*
+ * dv_sense_step_batch with a chem_weight per agent: agent i is scored and decided under chem_weights[i] (the experiment grid's
+ * chem_weight variable, scripts/run_experiment.py), all agents in the same library passes.  chem_weights == NULL is exactly
+ * dv_sense_step_batch.  Refused (DV_ERR_INVALID) when a weight lies outside [0, 1], and (DV_ERR_STATE) when a weight needs a sum
+ * the resident layout does not store (dv_lib_info.weight_lo / weight_hi; lay the library out with dv_set_weight_range first);
+ * dv_last_error names the agent.
+ */
+int dv_sense_step_batch_weighted(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
+                                 const double *chem_weights, uint32_t flags, dv_step_result *results);
 /*
  * The device work AND the device-side book-keeping of one agent step in ONE call (the fast path of
  * navsim_amd.NavBySceneFamiliarity.step_forward; a 60 us step does not want three trips through a binding):
@@ -275,6 +294,9 @@ int dv_step(dv_ctx *ctx, const uint8_t *patches, int n_headings, uint32_t flags,
  */
 int dv_step_batch(dv_ctx *ctx, const uint8_t *patches, int n_agents, int n_headings, uint32_t flags,
                   dv_step_result *results);
+/* dv_step_batch with a chem_weight per agent; the rules of dv_sense_step_batch_weighted. */
+int dv_step_batch_weighted(dv_ctx *ctx, const uint8_t *patches, int n_agents, int n_headings, const double *chem_weights,
+                           uint32_t flags, dv_step_result *results);
 /* Re-run the exact resolver on the candidates of the last step (sharded runs, cross-rank ties). */
 int dv_resolve(dv_ctx *ctx, dv_step_result *result);
 

@@ -234,6 +234,12 @@ struct dv_ctx {
     int spin_wait = 1;                        // poll the mapped result record instead of blocking on the stream (DEJAVU_SPIN)
     bool last_want_scene = false;
     double delta = 0.0;
+    // per-agent chem_weight (dv_set_weight_range, dv_step_batch_weighted / dv_sense_step_batch_weighted)
+    double wr_lo = 1.0, wr_hi = 0.0;          // weight range later ingests lay the library out for (lo > hi: the ingest's own weight)
+    AgentW* d_wts = nullptr;                  // [1 + kExtraSets][kMaxHeadings]: the weights of the agents of each set's resident pass
+    AgentW* h_wts = nullptr;                  // pinned: the weights of every agent of the call in progress
+    int h_wts_cap = 0;
+    bool wts_on = false;                      // the call in progress is weighted (run_batch): the kernels read d_wts
 
     // sensor model (landscape resident in HBM)
     unsigned char* d_land = nullptr;
@@ -397,6 +403,8 @@ extern "C" void dv_destroy(dv_ctx* c) {
     if (c->aux_stream) { (void)hipStreamSynchronize(c->aux_stream); (void)hipStreamDestroy(c->aux_stream); }
     if (c->batch_stream) { (void)hipStreamSynchronize(c->batch_stream); (void)hipStreamDestroy(c->batch_stream); }
     if (c->batch_stream3) { (void)hipStreamSynchronize(c->batch_stream3); (void)hipStreamDestroy(c->batch_stream3); }
+    if (c->d_wts) (void)hipFree(c->d_wts);
+    if (c->h_wts) (void)hipHostFree(c->h_wts);
     if (c->ev_a) (void)hipEventDestroy(c->ev_a);
     if (c->ev_b) (void)hipEventDestroy(c->ev_b);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -691,8 +699,11 @@ static int enqueue_bit_prep(dv_ctx* c, bool force = false) {             // (the
 // ------------------------------------------------------------------ library
 // metric 1 / 2 (ssd_f32 / ssd_u8): the common per-step buffers only (scores, state, candidates, records); the HSV tiles, the
 // byte-path operands and partial sums and the k_finish / k_fold summaries are not allocated (their ingests add their own).
+// [lay_lo, lay_hi]: the chem_weights the layout must serve (negative: cw alone).  The saturation planes are stored iff the range
+// reaches above 0, the value plane iff it reaches below 1; cw, the weight of every unweighted step, lies in the range.
 static int alloc_library(dv_ctx* c, int64_t F, int h, int w, double cw, int64_t first,
-                         int n_hues, const unsigned char* hues, int generic, int max_s = 255, int metric = 0) {
+                         int n_hues, const unsigned char* hues, int generic, int max_s = 255, int metric = 0,
+                         double lay_lo = -1.0, double lay_hi = -1.0) {
     free_library(c);
     c->metric = metric;
     LibCfg& g = c->cfg;
@@ -705,13 +716,15 @@ static int alloc_library(dv_ctx* c, int64_t F, int h, int w, double cw, int64_t 
     g.cw = cw;
     g.whs = 0.5 * cw;
     g.wv = 1 - cw;
-    g.generic = (cw > 0.0 && generic) ? 1 : 0;
+    const bool hs = (lay_hi >= 0.0 ? lay_hi : cw) > 0.0;
+    g.has_hs = hs ? 1 : 0;
+    g.generic = (hs && generic) ? 1 : 0;
     // two hues and no saturation above 127: one signed plane instead of two one-hot planes (plane_byte)
-    g.signed_s = (cw > 0.0 && !g.generic && n_hues == 2 && max_s <= 127 && c->allow_signed) ? 1 : 0;
-    g.nhs = cw > 0.0 ? (g.generic ? 2 : (g.signed_s ? 1 : n_hues)) : 0;
-    g.hasv = cw < 1.0 ? 1 : 0;
+    g.signed_s = (hs && !g.generic && n_hues == 2 && max_s <= 127 && c->allow_signed) ? 1 : 0;
+    g.nhs = hs ? (g.generic ? 2 : (g.signed_s ? 1 : n_hues)) : 0;
+    g.hasv = (lay_lo >= 0.0 ? lay_lo : cw) < 1.0 ? 1 : 0;
     g.npl = g.nhs + g.hasv;
-    for (int k = 0; k < kMaxHues; ++k) g.hues[k] = (!g.generic && cw > 0.0 && k < n_hues) ? hues[k] : 0;
+    for (int k = 0; k < kMaxHues; ++k) g.hues[k] = (!g.generic && hs && k < n_hues) ? hues[k] : 0;
     c->h = h;
     c->w = w;
     // cw == 1 with an all-zero-saturation library stores nothing; keep one (zero) plane so that the
@@ -778,13 +791,34 @@ static int check_lib_args(dv_ctx* c, int64_t F, int h, int w, double cw) {
     if (!(cw >= 0.0 && cw <= 1.0)) return fail(c, DV_ERR_INVALID, "chem_weight %g outside [0, 1]", cw);
     if ((int64_t)h * w > (1 << 22)) return fail(c, DV_ERR_INVALID, "sensor of %d x %d pixels is too large", h, w);
     if (F >= (1ll << 40)) return fail(c, DV_ERR_INVALID, "too many views");
+    if (c->wr_lo <= c->wr_hi && !(cw >= c->wr_lo && cw <= c->wr_hi))
+        return fail(c, DV_ERR_INVALID, "chem_weight %g outside the weight range [%g, %g] the library is to be laid out for (dv_set_weight_range)",
+                    cw, c->wr_lo, c->wr_hi);
+    return DV_OK;
+}
+
+// The weight range an ingest of weight cw lays the library out for (check_lib_args has checked that cw lies in it).
+static void ingest_range(const dv_ctx* c, double cw, double* lo, double* hi) {
+    if (c->wr_lo <= c->wr_hi) { *lo = c->wr_lo; *hi = c->wr_hi; }
+    else { *lo = cw; *hi = cw; }
+}
+
+extern "C" int dv_set_weight_range(dv_ctx* c, double lo, double hi) {
+    if (!c) return DV_ERR_INVALID;
+    if (lo > hi) { c->wr_lo = 1.0; c->wr_hi = 0.0; return DV_OK; }          // back to the ingest's own weight alone
+    if (!(lo >= 0.0 && hi <= 1.0))
+        return fail(c, DV_ERR_INVALID, "dv_set_weight_range: [%g, %g] is not a range within [0, 1]", lo, hi);
+    c->wr_lo = lo;
+    c->wr_hi = hi;
     return DV_OK;
 }
 
 // Library ingest from a raw uint8[F][h*w][3] buffer already on the device: hue scan, layout choice, re-tile.
 static int ingest_raw(dv_ctx* c, const unsigned char* d_raw, int64_t F, int h, int w, double cw, int64_t first) {
     unsigned bitmap[9] = {0};
-    if (cw > 0.0) {
+    double lo, hi;
+    ingest_range(c, cw, &lo, &hi);
+    if (hi > 0.0) {
         unsigned* d_bitmap = nullptr;
         hipError_t e = hipMalloc(&d_bitmap, sizeof bitmap);
         if (e == hipSuccess) e = hipMemsetAsync(d_bitmap, 0, sizeof bitmap, c->stream);
@@ -803,7 +837,7 @@ static int ingest_raw(dv_ctx* c, const unsigned char* d_raw, int64_t F, int h, i
         if (bitmap[v >> 5] & (1u << (v & 31))) hues[n_hues++] = (unsigned char)v;
     const int generic = n_hues > kMaxHues;
 
-    int rc = alloc_library(c, F, h, w, cw, first, n_hues, hues, generic, (int)bitmap[8]);
+    int rc = alloc_library(c, F, h, w, cw, first, n_hues, hues, generic, (int)bitmap[8], 0, lo, hi);
     if (rc) { free_library(c); return rc; }
     const long long total = (c->cfg.Fpad / 64) * (long long)c->cfg.npl * c->cfg.Q * 64;
     hipLaunchKernelGGL(k_retile, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, d_raw, c->d_tiles, c->cfg);
@@ -825,7 +859,7 @@ static int ensure_sense_buffer(dv_ctx* c, size_t bytes);
 // saturation range: views that do not fit it cannot be appended (DV_ERR_STATE; re-ingest the whole library).
 static int append_raw(dv_ctx* c, const unsigned char* d_raw, int64_t n) {
     const LibCfg old = c->cfg;
-    if (old.cw > 0.0 && !old.generic) {
+    if (old.has_hs && !old.generic) {
         unsigned bitmap[9] = {0};
         unsigned* d_bitmap = nullptr;
         hipError_t e = hipMalloc(&d_bitmap, sizeof bitmap);
@@ -856,8 +890,8 @@ static int append_raw(dv_ctx* c, const unsigned char* d_raw, int64_t n) {
     int tuned[4];
     for (int i = 0; i < 4; ++i) tuned[i] = c->tuned_shape[i];
     const int nk = old.signed_s ? 2 : old.nhs;
-    int rc = alloc_library(c, old.F + n, c->h, c->w, old.cw, old.first, (old.cw > 0.0 && !old.generic) ? nk : 0, old.hues,
-                           old.generic, old.signed_s ? 127 : 255);
+    int rc = alloc_library(c, old.F + n, c->h, c->w, old.cw, old.first, (old.has_hs && !old.generic) ? nk : 0, old.hues,
+                           old.generic, old.signed_s ? 127 : 255, 0, old.hasv ? 0.0 : 1.0, old.has_hs ? 1.0 : 0.0);
     if (rc) { (void)hipFree(old_tiles); free_library(c); return rc; }
     for (int i = 0; i < 4; ++i) c->tuned_shape[i] = tuned[i];
     const LibCfg& g = c->cfg;
@@ -1617,22 +1651,73 @@ static int run_batch(dv_ctx* c, int n_agents, int A, uint32_t flags, dv_step_res
     return rc;
 }
 
+// Per-agent chem_weight of a batched call (chem_weights[n_agents], or null: the library's weight for every agent).  Checks each
+// weight against [0, 1] and against the sums the resident layout stores, and leaves them as AgentW in the pinned staging array
+// (a call's passes copy their agents' entries up beside their patches or poses: upload_weights).  c->wts_on says whether the
+// kernels read them.
+static int stage_weights(dv_ctx* c, const double* w, int n_agents, const char* what) {
+    c->wts_on = false;
+    if (!w) return DV_OK;
+    if (c->metric != 0) return fail(c, DV_ERR_STATE, "%s: per-agent chem_weight needs a sads_hsv library", what);
+    const LibCfg& g = c->cfg;
+    for (int i = 0; i < n_agents; ++i) {
+        if (!(w[i] >= 0.0 && w[i] <= 1.0)) return fail(c, DV_ERR_INVALID, "%s: agent %d: chem_weight %g outside [0, 1]", what, i, w[i]);
+        if (w[i] > 0.0 && !g.has_hs)
+            return fail(c, DV_ERR_STATE, "%s: agent %d: chem_weight %g needs the hue/saturation sum, which the resident layout does not "
+                        "store (library ingested for chem_weight %g alone: dv_set_weight_range before the ingest)", what, i, w[i], g.cw);
+        if (w[i] < 1.0 && !g.hasv)
+            return fail(c, DV_ERR_STATE, "%s: agent %d: chem_weight %g needs the value sum, which the resident layout does not store "
+                        "(library ingested for chem_weight %g alone: dv_set_weight_range before the ingest)", what, i, w[i], g.cw);
+    }
+    if (!c->d_wts) HIP_TRY(c, hipMalloc(&c->d_wts, (size_t)(1 + dv_ctx::kExtraSets) * kMaxHeadings * sizeof(AgentW)));
+    if (c->h_wts_cap < n_agents) {
+        if (c->h_wts) { (void)hipHostFree(c->h_wts); c->h_wts = nullptr; c->h_wts_cap = 0; }
+        HIP_TRY(c, hipHostMalloc(&c->h_wts, (size_t)n_agents * sizeof(AgentW)));
+        c->h_wts_cap = n_agents;
+    }
+    for (int i = 0; i < n_agents; ++i) c->h_wts[i] = AgentW{w[i], 0.5 * w[i], 1 - w[i], 0.0};     // as alloc_library computes g.whs, g.wv
+    c->wts_on = true;
+    return DV_OK;
+}
+// Agents [first, first + n) of a weighted call become the resident pass: their weights go to the current set's slots, on the pass's
+// stream (a call's earlier copies out of h_wts are complete before the next call writes it: run_batch waits for every pass).
+static int upload_weights(dv_ctx* c, int first, int n) {
+    if (!c->wts_on) return DV_OK;
+    if (hipMemcpyAsync(c->d_wts + (size_t)c->cur_set * kMaxHeadings, c->h_wts + first, (size_t)n * sizeof(AgentW), hipMemcpyHostToDevice,
+                       c->stream) != hipSuccess)
+        return fail(c, DV_ERR_HIP, "weight upload failed: %s", hipGetErrorString(hipGetLastError()));
+    return DV_OK;
+}
+struct WeightsOff {                                 // a weighted call ends unweighted, whichever way it returns
+    dv_ctx* c;
+    ~WeightsOff() { c->wts_on = false; }
+};
+
 // Ensemble form of dv_sense_step: n_agents agents, each at its own position with its own A headings, sensed and
 // scored against the one resident library, 64/A agents per library pass; nothing but poses goes up.
-extern "C" int dv_sense_step_batch(dv_ctx* c, const double* x, const double* y, const double* angles, int n_agents, int A,
-                                   uint32_t flags, dv_step_result* results) {
+extern "C" int dv_sense_step_batch_weighted(dv_ctx* c, const double* x, const double* y, const double* angles, int n_agents, int A,
+                                            const double* chem_weights, uint32_t flags, dv_step_result* results) {
     int rc = check_sense_args(c, A);
     if (rc) return rc;
     if (!x || !y || !angles || !results || n_agents < 1) return fail(c, DV_ERR_INVALID, "dv_sense_step_batch: bad arguments");
     HIP_TRY(c, hipSetDevice(c->device));
+    WeightsOff off{c};
+    rc = stage_weights(c, chem_weights, n_agents, "dv_sense_step_batch_weighted");
+    if (rc) return rc;
     return run_batch(c, n_agents, A, flags, results, [&](int first, int n) {
         PoseSet poses;
         for (int ag = 0; ag < n; ++ag)
             for (int a = 0; a < A; ++a)
                 poses.p[ag * A + a] = make_pose(x[first + ag], y[first + ag], angles[(size_t)(first + ag) * A + a]);
         for (int a = n * A; a < kMaxHeadings; ++a) poses.p[a] = Pose{0., 0., 1., 0.};
-        return sense_prep_launch(c, poses, n, A);
+        const int r2 = upload_weights(c, first, n);
+        return r2 ? r2 : sense_prep_launch(c, poses, n, A);
     }, false);
+}
+
+extern "C" int dv_sense_step_batch(dv_ctx* c, const double* x, const double* y, const double* angles, int n_agents, int A,
+                                   uint32_t flags, dv_step_result* results) {
+    return dv_sense_step_batch_weighted(c, x, y, angles, n_agents, A, nullptr, flags, results);
 }
 
 // One full agent step's device work in one call: sense the heading patches at (x, y), score them, decide.
@@ -1783,7 +1868,9 @@ extern "C" int dv_generate_library_ex(dv_ctx* c, uint64_t seed, int64_t F, int h
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const unsigned char hues[2] = {0, 127};   // synth.hsv_from_words: H = bit * 127, S > 0 in both
-    rc = alloc_library(c, F, h, w, cw, first, 2, hues, 0, 127);     // synth: S is 0 or 127
+    double lo, hi;
+    ingest_range(c, cw, &lo, &hi);
+    rc = alloc_library(c, F, h, w, cw, first, 2, hues, 0, 127, 0, lo, hi);     // synth: S is 0 or 127
     if (rc) { free_library(c); return rc; }
     c->cfg.synth_full_s = full_range_s ? 1 : 0;
     const long long total = (c->cfg.Fpad / 64) * (long long)c->cfg.npl * c->cfg.Q * 64;
@@ -1846,7 +1933,9 @@ extern "C" int dv_get_library_info(const dv_ctx* c, dv_lib_info* o) {
     o->delta = c->delta;
     for (int k = 0; k < kMaxHues; ++k) o->hues[k] = c->cfg.hues[k];
     o->n_hues = 0;
-    if (c->cfg.cw > 0.0 && !c->cfg.generic) o->n_hues = c->cfg.signed_s ? 2 : c->cfg.nhs;
+    if (c->cfg.has_hs && !c->cfg.generic) o->n_hues = c->cfg.signed_s ? 2 : c->cfg.nhs;
+    o->weight_lo = c->cfg.hasv ? 0.0 : 1.0;                 // the chem_weights a weighted step may give an agent on this layout
+    o->weight_hi = c->cfg.has_hs ? 1.0 : 0.0;
     o->has_bit_planes = c->bits_ok ? 1 : 0;
     o->fp4_form = (c->bits_ok && c->fp4_ok) ? 1 : 0;
     o->bit_planes_hs = c->bits_ok ? c->bcfg.T[0] : 0;
@@ -2045,8 +2134,14 @@ static void launch_generic_apad(dv_ctx* c) {
     else launch_generic<HAS_HS, HASV, 32, 64>(c);
 }
 
+// The weights of the resident pass's agents (weighted calls), or null: the library's own weight for every agent.
+static const AgentW* wts_ptr(const dv_ctx* c) {
+    return c->wts_on ? c->d_wts + (size_t)c->cur_set * kMaxHeadings : nullptr;
+}
+
 static FuseArgs fuse_args(const dv_ctx* c) {
     FuseArgs fz{};
+    fz.wts = wts_ptr(c);
     fz.hsconst = c->d_acc[c->acc_parity].bhs;
     fz.vconst = c->d_acc[c->acc_parity].bv;
     fz.bsum = c->d_bsum;
@@ -2290,7 +2385,8 @@ static int launch_int_scoring(dv_ctx* c, hipEvent_t after_tiles, int* n_partial,
     if (!with_combine) return DV_OK;                     // the step ends in k_finish, which does the combining itself
     *n_partial = (int)((g.Fpad + 1023) / 1024);
     hipLaunchKernelGGL(k_combine, dim3((unsigned)*n_partial, (unsigned)c->A), dim3(256), 0, c->stream, c->d_part, c->int_hsconst,
-                       c->int_vconst, c->d_fam, c->d_pmax, c->d_state, c->cfg, c->nchunk, c->APAD, has_hs_sum, has_v_sum, c->n_agents);
+                       c->int_vconst, c->d_fam, c->d_pmax, c->d_state, c->cfg, c->nchunk, c->APAD, has_hs_sum, has_v_sum, c->n_agents, wts_ptr(c),
+                       c->A_agent);
     HIP_TRY(c, hipGetLastError());
     return DV_OK;
 }
@@ -2485,7 +2581,7 @@ static int launch_scoring(dv_ctx* c, bool with_combine = true) {
     }
     if (c->exact) {
         hipLaunchKernelGGL(k_exact_all, dim3((unsigned)(g.Fpad / 64), (unsigned)((c->A + 3) / 4)), dim3(64, 4), 0, c->stream,
-                           c->d_tiles, c->d_raw_patches, c->d_fam, c->d_pmax, c->d_state, c->cfg, c->A, c->n_agents);
+                           c->d_tiles, c->d_raw_patches, c->d_fam, c->d_pmax, c->d_state, c->cfg, c->A, c->n_agents, wts_ptr(c));
         HIP_TRY(c, hipGetLastError());
         n_partial = (int)(g.Fpad / 64);
     } else {
@@ -2563,7 +2659,7 @@ static void launch_finish(dv_ctx* c, int want_scene, int force) {
     hipLaunchKernelGGL(k_finish<NT>, dim3(nb, (unsigned)c->n_agents), dim3(256), 0, c->stream,
                        c->d_part, c->int_hsconst, c->int_vconst, c->nchunk, c->APAD, c->int_has_hs, c->int_has_v, c->d_state, c->d_bsum, c->d_ctmp,
                        c->d_cand, c->d_scene, outp, recp, c->cfg, c->A_agent, c->delta, want_scene, force,
-                       c->seq, serr, step_fenced(c), (int)vb, separate);
+                       c->seq, serr, step_fenced(c), (int)vb, separate, wts_ptr(c));
     if (separate) launch_fold(c, (int)nb, outp, recp, force, c->seq, serr);
 }
 
@@ -2637,7 +2733,7 @@ static int enqueue_resolve(dv_ctx* c, int agent = 0) {
     else
     hipLaunchKernelGGL(k_resolve, dim3(256), dim3(64), 0, c->stream, c->d_tiles,
                        c->d_raw_patches + (size_t)agent * c->A_agent * c->cfg.P * 3, c->d_state + agent, c->d_cand + co,
-                       c->d_cand_exact + co, c->cfg);
+                       c->d_cand_exact + co, c->cfg, c->wts_on ? wts_ptr(c) + agent : nullptr);
     HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(k_decide, dim3(1), dim3(64), 0, c->stream, c->d_state + agent, c->d_cand + co, c->d_cand_exact + co,
                        c->d_result + agent, c->d_record + (size_t)agent * (3 + 4 * kMaxHeadings), c->cfg, c->A_agent, c->delta,
@@ -2759,13 +2855,18 @@ extern "C" int dv_step(dv_ctx* c, const uint8_t* patches, int A, uint32_t flags,
 // Batched agents (ensemble runs): N agents x A headings each against the same library.  Agents are grouped into
 // passes of at most DV_MAX_HEADINGS headings; one pass = one scoring launch set, one k_tail with an agent per
 // blockIdx.y.  Each agent's decision obeys the same rules as dv_step.
-extern "C" int dv_step_batch(dv_ctx* c, const uint8_t* patches, int n_agents, int A, uint32_t flags, dv_step_result* results) {
+extern "C" int dv_step_batch_weighted(dv_ctx* c, const uint8_t* patches, int n_agents, int A, const double* chem_weights, uint32_t flags,
+                                      dv_step_result* results) {
     int rc = check_step_args(c, A);
     if (rc) return rc;
     if (!patches || !results || n_agents < 1) return fail(c, DV_ERR_INVALID, "dv_step_batch: bad arguments");
     HIP_TRY(c, hipSetDevice(c->device));
+    WeightsOff off{c};
+    rc = stage_weights(c, chem_weights, n_agents, "dv_step_batch_weighted");
+    if (rc) return rc;
     const size_t agent_bytes = (size_t)A * c->cfg.P * 3;
     return run_batch(c, n_agents, A, flags, results, [&](int first, int n) {
+        if (upload_weights(c, first, n)) return (int)DV_ERR_HIP;
         if (hipMemcpyAsync(c->d_raw_patches, patches + (size_t)first * agent_bytes, (size_t)n * agent_bytes, hipMemcpyHostToDevice,
                            c->stream) != hipSuccess)
             return fail(c, DV_ERR_HIP, "dv_step_batch: patch upload failed: %s", hipGetErrorString(hipGetLastError()));
@@ -2775,6 +2876,10 @@ extern "C" int dv_step_batch(dv_ctx* c, const uint8_t* patches, int n_agents, in
         c->A_agent = A;
         return (int)DV_OK;
     }, true);
+}
+
+extern "C" int dv_step_batch(dv_ctx* c, const uint8_t* patches, int n_agents, int A, uint32_t flags, dv_step_result* results) {
+    return dv_step_batch_weighted(c, patches, n_agents, A, nullptr, flags, results);
 }
 
 // Steps of any number of headings: passes of at most kMaxHeadings, merged by the rule of NavBySceneFamiliarity.py:313-315.

@@ -62,10 +62,17 @@ struct LibCfg {
     int generic;        // H and S kept as planes (more than kMaxHues hues)
     int signed_s;       // two hues and every library S <= 127: ONE saturation plane holding 128 + (S of hue0) - (S of hue1)
     int synth_full_s;   // the synthetic generators (dv_generate_library_ex, dv_generate_patches) draw S from 0..127 instead of {0, 127}
+    int has_hs;         // the layout serves the hue/saturation term (a weight range reaching above 0): planes and per-heading constants
     unsigned char hues[kMaxHues];
-    double cw;          // chem_weight
+    double cw;          // chem_weight of the ingest (the weight of every unweighted step)
     double whs;         // 0.5 * cw          (util.pyx:59,68)
     double wv;          // 1 - cw            (util.pyx:69)
+};
+
+// Per-agent weights of a weighted batch pass (dv_step_batch_weighted): one entry per agent of the pass, computed on the host in
+// double exactly as alloc_library computes the library's own.  A null pointer means every agent scores under LibCfg's weights.
+struct AgentW {
+    double cw, whs, wv, pad;
 };
 
 typedef int v4i_t __attribute__((ext_vector_type(4)));
@@ -149,7 +156,7 @@ __device__ __forceinline__ void px_ints(const LibCfg& c, const unsigned* lib, un
                                         int& hs, int& dv) {
     hs = 0;
     dv = 0;
-    if (c.cw > 0.0) {
+    if (c.has_hs) {
         if (c.generic) {
             const int lh = (int)lib[0], ls = (int)lib[1];
             hs = ((int)H == lh) ? abs((int)S - ls) : (int)S + ls;
@@ -605,7 +612,7 @@ k_sad_generic(const uint4* __restrict__ tiles, const unsigned* __restrict__ prep
 __global__ void __launch_bounds__(256)
 k_combine(const unsigned* __restrict__ part, const int* __restrict__ hsconst, const int* __restrict__ vconst,
           double* __restrict__ fam, unsigned long long* __restrict__ blockmax, StepState* __restrict__ st, LibCfg c, int nchunk,
-          int APAD, int has_hs_sum, int has_v_sum, int n_agents) {
+          int APAD, int has_hs_sum, int has_v_sum, int n_agents, const AgentW* __restrict__ wts, int A_agent) {
     __shared__ unsigned long long wmax[4];
     // four consecutive views per thread: one 16-byte load per (chunk, sum) row
     const long long f0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
@@ -630,11 +637,13 @@ k_combine(const unsigned* __restrict__ part, const int* __restrict__ hsconst, co
                 sv[0] += (int)q.x; sv[1] += (int)q.y; sv[2] += (int)q.z; sv[3] += (int)q.w;
             }
         }
+        double whs = c.whs, wv = c.wv;
+        if (wts) { whs = wts[a / A_agent].whs; wv = wts[a / A_agent].wv; }       // (uniform over the block)
         double val[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            double acc = c.whs * (double)shs[i];
-            if (has_v_sum) acc = acc + c.wv * (double)sv[i];
+            double acc = whs * (double)shs[i];
+            if (has_v_sum) acc = acc + wv * (double)sv[i];
             val[i] = (double)c.P - acc / 255.;
             if (f0 + i < c.F) {
                 const unsigned long long k = ordered_key(val[i]);
@@ -752,11 +761,13 @@ k_post(const double* __restrict__ rec, double* __restrict__ entry, int n, unsign
 __global__ void __launch_bounds__(256)
 k_exact_all(const uint4* __restrict__ tiles, const unsigned char* __restrict__ raw_patches,
             double* __restrict__ fam, unsigned long long* __restrict__ groupmax, StepState* __restrict__ st, LibCfg c,
-            int A, int n_agents) {
+            int A, int n_agents, const AgentW* __restrict__ wts) {
     const int lane = threadIdx.x;
     if (blockIdx.x == 0 && blockIdx.y == 0) reset_step_state(st, threadIdx.y * 64 + threadIdx.x, n_agents);
     const int a = blockIdx.y * 4 + threadIdx.y;
     if (a >= A) return;
+    double cw = c.cw, wv = c.wv;
+    if (wts) { cw = wts[a / (A / n_agents)].cw; wv = wts[a / (A / n_agents)].wv; }    // (uniform over the wave)
     const long long g = blockIdx.x;
     const long long f = g * 64 + lane;
     const uint4* base = tiles + g * c.gstride + lane;
@@ -775,7 +786,7 @@ k_exact_all(const uint4* __restrict__ tiles, const unsigned char* __restrict__ r
             }
             int hs, dv;
             px_ints(c, lib, pa[px * 3], pa[px * 3 + 1], pa[px * 3 + 2], hs, dv);
-            diff += px_term(hs, dv, c.cw, c.wv);
+            diff += px_term(hs, dv, cw, wv);
         }
     }
     const double val = (double)c.P - diff;
@@ -1258,7 +1269,8 @@ k_finish(const unsigned* __restrict__ part, const int* __restrict__ hsconst, con
          int APAD, int has_hs_sum, int has_v_sum, StepState* __restrict__ st, unsigned long long* __restrict__ bsum,
          unsigned long long* __restrict__ ctmp, unsigned long long* __restrict__ cand, double* __restrict__ scene,
          StepResultDev* __restrict__ out, double* __restrict__ rec, LibCfg c, int A, double delta, int want_scene, int force,
-         int seq, const unsigned long long* __restrict__ sense_err, int fenced, int vb, int separate_fold) {
+         int seq, const unsigned long long* __restrict__ sense_err, int fenced, int vb, int separate_fold,
+         const AgentW* __restrict__ wts) {
     __shared__ unsigned long long s_bmax[kMaxHeadings];
     __shared__ unsigned long long s_bview[kMaxHeadings];
     __shared__ unsigned long long s_keys[16 * 16 * 17];          // 34 KB: key transposes of phase 2
@@ -1319,8 +1331,8 @@ k_finish(const unsigned* __restrict__ part, const int* __restrict__ hsconst, con
                 // the chunk sums are int32 and may wrap on the way (bit-plane path: negative chunks); their total fits
                 const long long shs = (long long)acc_sum(hsconst, a_base + t * 16 + k) + (long long)(int)shs_u[k];
                 const long long sv = (long long)(vconst ? acc_sum(vconst, a_base + t * 16 + k) : 0) + (long long)(int)sv_u[k];
-                double acc = c.whs * (double)shs;
-                if (has_v_sum) acc = acc + c.wv * (double)sv;
+                double acc = (wts ? wts[agent].whs : c.whs) * (double)shs;
+                if (has_v_sum) acc = acc + (wts ? wts[agent].wv : c.wv) * (double)sv;
                 val[k] = (double)c.P - acc / 255.;
             }
         }
@@ -1486,8 +1498,9 @@ k_fold_reduce(const unsigned long long* __restrict__ bsum, unsigned long long* _
 __global__ void __launch_bounds__(64)
 k_resolve(const uint4* __restrict__ tiles, const unsigned char* __restrict__ raw_patches,
           const StepState* __restrict__ st, const unsigned long long* __restrict__ cand,
-          double* __restrict__ cand_exact, LibCfg c) {
+          double* __restrict__ cand_exact, LibCfg c, const AgentW* __restrict__ w) {
     __shared__ double terms[1024];
+    const double cw = w ? w->cw : c.cw, wv = w ? w->wv : c.wv;     // `w`: this agent's weights in a weighted pass
     const unsigned long long n_all = st->ncand;
     if (n_all > (unsigned long long)kCandCap) return;       // overflow: host redoes the step in exact mode
     const int n = (int)n_all;
@@ -1515,7 +1528,7 @@ k_resolve(const uint4* __restrict__ tiles, const unsigned char* __restrict__ raw
                         }
                         int hs, dv;
                         px_ints(c, lib, pa[px * 3], pa[px * 3 + 1], pa[px * 3 + 2], hs, dv);
-                        t = px_term(hs, dv, c.cw, c.wv);
+                        t = px_term(hs, dv, cw, wv);
                     }
                     terms[lane * 16 + i] = t;
                 }
@@ -2721,7 +2734,7 @@ k_patch_prep(const unsigned char* __restrict__ land, const PoseSet poses, int A,
     bool off = false;
     s_raw[tid * 3] = (unsigned char)H; s_raw[tid * 3 + 1] = (unsigned char)S; s_raw[tid * 3 + 2] = (unsigned char)V;
     if (px < c.P) {
-        if (!c.generic && c.cw > 0.0) {
+        if (!c.generic && c.has_hs) {
             const int nk = c.signed_s ? 2 : c.nhs;
             bool in_set = false;
             for (int k = 0; k < nk; ++k) in_set |= (H == c.hues[k]);
@@ -3033,6 +3046,7 @@ struct FuseArgs {
     unsigned long long* bsum;       // [agents][nb][2][A_agent] workgroup summaries
     unsigned long long* ctmp;       // [agents][kTmpCap][2] shared extra-candidate lists
     StepState* st;                  // [agents]
+    const AgentW* wts;              // [agents] per-agent weights of a weighted pass, or null: LibCfg's
     int A_real;                     // resident headings
     int A_agent;                    // headings per agent
     int nb;                         // summaries per agent (one per workgroup)
@@ -3092,6 +3106,9 @@ fused_finish(HsOf hs_of, VOf v_of, const long long (&gidx)[TILES], const bool (&
     const int ac = valid ? a : fz.A_real - 1;
     // the lane's two per-heading constants: loaded here, or once per kernel by the caller (`consts`: one L2 round trip less per item)
     const int hsc = consts ? consts[0] : acc_sum(fz.hsconst, ac), vc = consts ? consts[1] : (fz.vconst ? acc_sum(fz.vconst, ac) : 0);
+    // the lane's weights: its agent's in a weighted pass (a lane holds one heading, so one agent), else the library's
+    double whs = c.whs, wv = c.wv;
+    if (fz.wts) { const AgentW* w = fz.wts + ac / fz.A_agent; whs = w->whs; wv = w->wv; }
     // score >= best - delta  =>  sc <= sc_best + 255 delta up to roundings of a few ulp of P: loose by far more
     const double margin = 256. * fz.delta + 256. * (double)c.P * 8.9e-16;
     const double kInf = __longlong_as_double(0x7ff0000000000000ll);
@@ -3107,8 +3124,8 @@ fused_finish(HsOf hs_of, VOf v_of, const long long (&gidx)[TILES], const bool (&
     auto sc_of = [&](int t, int r) -> double {
         const int shs = hsc + (has_hs_sum ? hs_of(t, r) : 0);
         const int sv = vc + (c.hasv ? v_of(t, r) : 0);
-        double sc = c.whs * (double)shs;
-        if (c.hasv) sc = sc + c.wv * (double)sv;
+        double sc = whs * (double)shs;
+        if (c.hasv) sc = sc + wv * (double)sv;
         return ((r & 3) + 8 * (r >> 2) + 4 * half) < nreal[t] ? sc : kInf;
     };
     // One pass for the smallest; `near`: some other entry came within the margin of the smallest so far (a superset of
@@ -3122,7 +3139,7 @@ fused_finish(HsOf hs_of, VOf v_of, const long long (&gidx)[TILES], const bool (&
     // (tools/exp/stamps.py -DDEJAVU_EXP_FIN: the fp64 walk was 3.4-3.9 us of the finishing's 4.6-5.2.)
     bool walked = false;
     if constexpr (FAST) {
-        const float whs32 = (float)c.whs, wv32 = (float)c.wv;
+        const float whs32 = (float)whs, wv32 = (float)wv;
         const float kInfF = __int_as_float(0x7f800000);
         const float margin32 = (float)margin * 1.01f + 1e-30f;
         float m32 = kInfF, s32 = kInfF;
@@ -3147,8 +3164,8 @@ fused_finish(HsOf hs_of, VOf v_of, const long long (&gidx)[TILES], const bool (&
         const bool unclear = m32 != kInfF && s32 <= m32 * 1.000002f + margin32;
         if (!__any(unclear)) {
             if (m32 != kInfF) {
-                double sc = c.whs * (double)m_shs;
-                if (c.hasv) sc = sc + c.wv * (double)m_sv;
+                double sc = whs * (double)m_shs;
+                if (c.hasv) sc = sc + wv * (double)m_sv;
                 bs = sc;
                 bi = mi;
             }

@@ -83,6 +83,8 @@ class LibInfo(ctypes.Structure):
         ("code_tile_bytes", ctypes.c_int64),
         ("mixed_layout", ctypes.c_int32),
         ("reserved0", ctypes.c_int32),
+        ("weight_lo", ctypes.c_double),
+        ("weight_hi", ctypes.c_double),
     ]
 
 
@@ -121,6 +123,7 @@ PROTOTYPES = {
     "dv_append_library_from_poses": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int64, _u8p]),
     "dv_clear_library": (ctypes.c_int, [_ctx_p]),
     "dv_get_library_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(LibInfo)]),
+    "dv_set_weight_range": (ctypes.c_int, [_ctx_p, ctypes.c_double, ctypes.c_double]),
     "dv_read_planes": (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_int64, _u8p]),
     "dv_bitplane_plan": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32), ctypes.c_int, _u8p, _u8p,
                                         ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
@@ -133,6 +136,8 @@ PROTOTYPES = {
                                      ctypes.POINTER(StepResult), _f64p]),
     "dv_sense_step_batch": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, ctypes.c_uint32,
                                            ctypes.POINTER(StepResult)]),
+    "dv_sense_step_batch_weighted": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _f64p, ctypes.c_uint32,
+                                                    ctypes.POINTER(StepResult)]),
     "dv_agent_step": (ctypes.c_int, [_ctx_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, _f64p, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_double, ctypes.c_double, ctypes.c_double, _f64p, ctypes.POINTER(ctypes.c_int32), _f64p,
                                      ctypes.POINTER(ctypes.c_int32)]),
@@ -156,6 +161,8 @@ PROTOTYPES = {
     "dv_step": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(StepResult), _f64p]),
     "dv_step_batch": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, ctypes.c_uint32,
                                      ctypes.POINTER(StepResult)]),
+    "dv_step_batch_weighted": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, _f64p, ctypes.c_uint32,
+                                              ctypes.POINTER(StepResult)]),
     "dv_resolve": (ctypes.c_int, [_ctx_p, ctypes.POINTER(StepResult)]),
     "dv_step_wide": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(WideResult), _f64p, _i64p, _f64p]),
     "dv_sense_step_wide": (ctypes.c_int, [_ctx_p, ctypes.c_double, ctypes.c_double, _f64p, ctypes.c_int, ctypes.c_uint32,

@@ -125,6 +125,8 @@ class NavBySceneFamiliarity(object):
     default) the lean device step is kept and the minimum of the last step is worked out when `scene_familiarity` is read.
     """
 
+    chem_weight = None              # a NavEnsemble member's own weight (NavEnsemble.from_agent(chem_weights=...)); None: the model's
+
     def __init__(self,
                  landscape,
                  sensor_dimensions,
@@ -523,6 +525,10 @@ class NavBySceneFamiliarity(object):
 
     # ---- the step (:279-329) -------------------------------------------------------------------
     def step_forward(self, fake=False):
+        if self.chem_weight is not None and self.chem_weight != getattr(self.familiarity_model, "chem_weight", None):
+            # (a step of its own runs the library's weight: only its ensemble's batches score it under its own)
+            raise ValueError("this ensemble member scores under chem_weight %r, the library under %r: step it with its NavEnsemble"
+                             % (self.chem_weight, getattr(self.familiarity_model, "chem_weight", None)))
         position = self.position
         self.angle_familiarity[:] = np.nan
         assert len(self.familiar_scenes) == len(self._scene_fam)

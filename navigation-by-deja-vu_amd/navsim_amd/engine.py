@@ -6,6 +6,17 @@ import numpy as np
 from . import _native as N
 
 
+def agent_weights(chem_weights, n):
+    """chem_weights of a weighted batch as float64[n] (None stays None: the unweighted call).  The range [0, 1] and the layout are
+    the library's to check (dv_step_batch_weighted names the agent it refuses)."""
+    if chem_weights is None:
+        return None
+    w = np.ascontiguousarray(chem_weights, dtype=np.float64).reshape(-1)
+    if w.shape[0] != n:
+        raise ValueError("chem_weights holds %d weights for %d agents" % (w.shape[0], n))
+    return w
+
+
 class BatchResults(object):
     """The records of an ensemble step (dv_step_batch / dv_sense_step_batch), one per agent.  A sequence of the per-agent result
     dictionaries step() returns -- made when asked for -- and, for callers that only move agents, the same numbers as arrays over
@@ -136,6 +147,12 @@ class FamiliarityEngine(object):
         self.n_views += len(x)
         return out
 
+    def set_weight_range(self, lo, hi):
+        """Lay later ingests (set_library, set_library_from_poses, generate_library) out for every chem_weight in [lo, hi], so that a
+        weighted batch (step_batch / sense_step_batch with chem_weights) may score each agent under its own weight.  The ingest's own
+        chem_weight must lie in the range.  lo > hi restores the default: the ingest's weight alone."""
+        self._check(self._lib.dv_set_weight_range(self._ctx, float(lo), float(hi)), "dv_set_weight_range")
+
     def clear_library(self):
         self._check(self._lib.dv_clear_library(self._ctx), "dv_clear_library")
         self.n_views, self.shape = 0, None
@@ -149,7 +166,8 @@ class FamiliarityEngine(object):
                     chem_weight=info.chem_weight, delta=info.delta, hues=[int(x) for x in info.hues][:info.n_hues],
                     signed_saturation=bool(info.signed_saturation), has_bit_planes=bool(info.has_bit_planes),
                     bit_planes_hs=info.bit_planes_hs, bit_planes_v=info.bit_planes_v, bit_tile_bytes=info.bit_tile_bytes,
-                    fp4_form=bool(info.fp4_form), code_tile_bytes=info.code_tile_bytes, mixed_layout=bool(info.mixed_layout))
+                    fp4_form=bool(info.fp4_form), code_tile_bytes=info.code_tile_bytes, mixed_layout=bool(info.mixed_layout),
+                    weight_range=(info.weight_lo, info.weight_hi))
 
     def read_planes(self, v0, n):
         info = self.library_info()
@@ -311,18 +329,24 @@ class FamiliarityEngine(object):
         self._begun = bool(begun.value)
         return st[6].value, self._begun, (st[8].value if st[10].value else None)
 
-    def sense_step_batch(self, x, y, angles, force_resolve=False):
-        """Ensemble step on the device: agent i at (x[i], y[i]) looking along angles[i][0..A) -> BatchResults (a sequence of result dicts)."""
+    def sense_step_batch(self, x, y, angles, force_resolve=False, chem_weights=None):
+        """Ensemble step on the device: agent i at (x[i], y[i]) looking along angles[i][0..A) -> BatchResults (a sequence of result dicts).
+        chem_weights[N] (optional): agent i is scored under chem_weights[i] (the library's layout must serve it: set_weight_range)."""
         x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
         y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
         angles = np.ascontiguousarray(angles, dtype=np.float64)
         if angles.ndim != 2 or len(x) != len(y) or angles.shape[0] != len(x):
             raise ValueError("x[N], y[N] and angles[N, A] expected")
         n, A = angles.shape
+        w = agent_weights(chem_weights, n)
         res = (N.StepResult * n)()
-        self._check_sense(self._lib.dv_sense_step_batch(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A,
-                                                        N.DV_STEP_FORCE_RESOLVE if force_resolve else 0, res),
-                          "dv_sense_step_batch")
+        flags = N.DV_STEP_FORCE_RESOLVE if force_resolve else 0
+        if w is None:
+            self._check_sense(self._lib.dv_sense_step_batch(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, flags, res),
+                              "dv_sense_step_batch")
+        else:
+            self._check_sense(self._lib.dv_sense_step_batch_weighted(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A,
+                                                                     N.f64ptr(w), flags, res), "dv_sense_step_batch_weighted")
         return BatchResults(res, n, A)
 
     def set_library_from_poses(self, x, y, angle, chem_weight=0.0, first_view=0, want_views=True):
@@ -406,16 +430,22 @@ class FamiliarityEngine(object):
                     angle_view=view, flags=res.flags, n_passes=res.n_passes, n_contending=res.n_contending,
                     scene_familiarity=scene)
 
-    def step_batch(self, patches, force_resolve=False):
-        """Ensemble step: patches uint8[N, A, h, w, 3] -> BatchResults, a sequence of N result dicts (one library pass per 64/A agents)."""
+    def step_batch(self, patches, force_resolve=False, chem_weights=None):
+        """Ensemble step: patches uint8[N, A, h, w, 3] -> BatchResults, a sequence of N result dicts (one library pass per 64/A agents).
+        chem_weights[N] (optional): agent i is scored under chem_weights[i] (the library's layout must serve it: set_weight_range)."""
         patches = N.as_u8(patches, "patches")
         if patches.ndim != 5:
             raise ValueError("patches must be uint8[N,A,h,w,3]")
         n, A = patches.shape[0], patches.shape[1]
         self._patch_shape_ok(patches, (n, A))
+        w = agent_weights(chem_weights, n)
         res = (N.StepResult * n)()
-        self._check(self._lib.dv_step_batch(self._ctx, N.u8ptr(patches), n, A,
-                                            N.DV_STEP_FORCE_RESOLVE if force_resolve else 0, res), "dv_step_batch")
+        flags = N.DV_STEP_FORCE_RESOLVE if force_resolve else 0
+        if w is None:
+            self._check(self._lib.dv_step_batch(self._ctx, N.u8ptr(patches), n, A, flags, res), "dv_step_batch")
+        else:
+            self._check(self._lib.dv_step_batch_weighted(self._ctx, N.u8ptr(patches), n, A, N.f64ptr(w), flags, res),
+                        "dv_step_batch_weighted")
         return BatchResults(res, n, A)
 
     # -- ssd_f32 metric --------------------------------------------------------------------------

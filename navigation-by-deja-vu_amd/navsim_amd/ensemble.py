@@ -5,6 +5,10 @@ and the device work of 64/A of them shares each pass over the library (dv_sense_
 Every agent is a full navsim_amd.NavBySceneFamiliarity (own pose, error metrics, stop conditions); only the sensing
 and scoring of a step are batched.  An agent that stops (end of path, out of bounds, too far) keeps its final state
 and no longer takes part.
+
+Members may score under chem_weights of their own (the experiment grid's chem_weight variable, scripts/run_experiment.py:61,218):
+a trial's training views do not depend on the weight, so one library serves every weight its layout stores the sums for
+(FamiliarityEngine.set_weight_range), and the members of all weights share the library passes (dv_sense_step_batch_weighted).
 """
 import numpy as np
 
@@ -22,6 +26,10 @@ class NavEnsemble(object):
             raise ValueError("construct the agents with track_scene_familiarity=False: a batched pass keeps no per-view minimum")
         self.agents = list(agents)
         self.engine = eng
+        # per-member weights (a member's own `chem_weight`; None: the library's): sent with every batch when any member has one
+        lib_w = getattr(agents[0].familiarity_model, "chem_weight", None)
+        own = [getattr(a, "chem_weight", None) for a in agents]
+        self._weights = None if all(w is None for w in own) else np.array([lib_w if w is None else w for w in own], dtype=np.float64)
         self.stop_status = [0] * len(agents)                      # the reference's codes: 0 running / 1 / -1 / -2
         # update_error (:252-276) of all members in ONE device call per ensemble step: every member gets a coverage array of its own on
         # the device (dv_path_slots) and hands its position in; 32 members x a NumPy pass over 50 000 training points each were
@@ -70,14 +78,36 @@ class NavEnsemble(object):
                 self._too_far[id(a)] = e
 
     @classmethod
-    def from_agent(cls, agent, poses):
+    def from_agent(cls, agent, poses, chem_weights=None):
         """`agent`: trained, with the GPU sensor model; poses: iterable of ((x, y), angle), one agent each
-        (the first pose goes to `agent` itself, the others to clones on the same engine and library)."""
+        (the first pose goes to `agent` itself, the others to clones on the same engine and library).
+        chem_weights (optional, one per pose): member i scores under chem_weights[i], kept as its `chem_weight`.  When the resident
+        library's layout does not store the sums those weights need, it is ingested once more from agent.familiar_scenes, laid out
+        for the range of weights (the agent's own weight stays the library's: that of its unweighted steps)."""
         poses = list(poses)
+        weights = None
+        if chem_weights is not None:
+            weights = [float(w) for w in chem_weights]
+            if len(weights) != len(poses):
+                raise ValueError("chem_weights holds %d weights for %d poses" % (len(weights), len(poses)))
+            if not all(0.0 <= w <= 1.0 for w in weights):
+                raise ValueError("chem_weights must lie in [0, 1], got %r" % (weights,))
+            lib_w = float(agent.familiarity_model.chem_weight)
+            eng = agent._engine
+            if eng is None or agent.training_path is None:
+                raise ValueError("clone a trained agent whose sensor model runs on the GPU")
+            lo, hi = eng.library_info()["weight_range"]
+            if not all(lo <= w <= hi for w in weights):
+                eng.set_weight_range(min(weights + [lib_w]), max(weights + [lib_w]))
+                try:
+                    eng.set_library(agent.familiar_scenes, lib_w)
+                finally:
+                    eng.set_weight_range(1.0, 0.0)              # later ingests: their own weight alone, as before
         agents = [agent] + [agent.clone_for_ensemble() for _ in poses[1:]]
-        for a, (pos, ang) in zip(agents, poses):
+        for i, (a, (pos, ang)) in enumerate(zip(agents, poses)):
             a.position = (float(pos[0]), float(pos[1]))
             a.angle = float(ang)
+            a.chem_weight = None if weights is None else weights[i]
         return cls(agents)
 
     @property
@@ -131,7 +161,7 @@ class NavEnsemble(object):
                 angs = np.stack(angs)
         if idx:
             stops = {}
-            results = self.engine.sense_step_batch(xs, ys, angs)
+            results = self.engine.sense_step_batch(xs, ys, angs, chem_weights=None if self._weights is None else self._weights[idx])
             # the records as arrays when the engine offers them (engine.BatchResults): no dictionary per agent and step
             lean = hasattr(results, "angle_familiarity")
             flags = results.flags.tolist() if lean else [r["flags"] for r in results]

@@ -212,6 +212,7 @@ struct dv_ctx {
     bool defer_fold = false;                  // enqueue_step: a fused pass leaves its fold to the caller (run_batch launches them last)
     int deferred_force = 0, deferred_seq = 0; // ... with these arguments
     int lc22_env = 1;                         // DEJAVU_LC22=0: passes of 64 headings keep one view group per consumer (sad_lc_fp4 with two heading tiles; A/B)
+    int lreg_env = 1;                         // DEJAVU_LIBREG=0: single-pass fp4 steps of 32 headings keep the library rows in the LDS ring (sad_lc_fp4; A/B)
     int chain_order_env = -1;                 // DEJAVU_CHAIN_ORDER (A/B): how a chain of ensemble passes is laid out on its stream, see run_batch
     int chains_env = 2;                       // DEJAVU_CHAINS=1: ensemble passes one after the other on one stream, as in round 3 (A/B)
     StepResultDev* h_result = nullptr;        // pinned, mapped: the kernels write the result record into it
@@ -372,6 +373,7 @@ extern "C" int dv_create(dv_ctx** out, int device_id) {
     env_int("DEJAVU_CHAINS", c->chains_env, 1, 3);
     env_int("DEJAVU_CHAIN_ORDER", c->chain_order_env, -1, 2);
     env_int("DEJAVU_LC22", c->lc22_env, 0, 1);
+    env_int("DEJAVU_LIBREG", c->lreg_env, 0, 1);
     env_int("DEJAVU_NT", c->nt_env, 0, 1);
     env_int("DEJAVU_TEST_FAIL_ALLOC", c->fail_alloc_env, 0, 64);
     *out = c;
@@ -2174,7 +2176,7 @@ static void launch_mfma_dual_f(dv_ctx* c, int nchunk, int has_hs) {
     const size_t lds4 = (size_t)fp4_ring_bytes(SK4, TILES, RD4);
     size_t lds = lds8 > lds4 ? lds8 : lds4;
     if constexpr (SKL > 0) {
-        constexpr int lcb = lc_ring_bytes<SKL, RDL>();
+        constexpr int lcb = SKL == kLregStage ? lreg_ring_bytes<SKL, RDL>() : lc_ring_bytes<SKL, RDL>();
         static_assert(lcb + kFuseScratchBytes + (HT - 1) * 512 <= 160 * 1024, "LDS");
         if ((size_t)lcb > lds) lds = (size_t)lcb;
     }
@@ -2225,6 +2227,20 @@ static bool lc22_fits(const dv_ctx* c) {
         if (seg == 0 && c->bcfg.wacc[0][0] && w && c->bcfg.wacc[0][0] != w) return false;
     }
     return (long long)c->bcfg.NK[0] * 256 <= 32767;
+}
+// sad_lc_fp4_lreg (library rows in the consumers' registers, bit positions 1, 2, 3 sharing an accumulator) fits this library: per
+// segment the positions 1, 2, 3 that stand for something have one width, and the saturation K-steps are whole stages of eight.
+static bool lreg_fits(const dv_ctx* c) {
+    if (!c->lreg_env || !c->fp4_ok || c->bcfg.vcode || c->mixed) return false;
+    for (int seg = 0; seg < 2; ++seg) {
+        int w = 0;
+        for (int bit = 1; bit < 4; ++bit) {
+            const int wb = c->bcfg.wacc[seg][bit];
+            if (wb && w && wb != w) return false;
+            if (wb) w = wb;
+        }
+    }
+    return c->bcfg.NK[0] % kLregStage == 0;
 }
 // How a matrix-core pass over the resident library is cut for `apad` resident headings (what launch_mfma launches; run_batch asks
 // beforehand whether its passes will finish their scores themselves: one chunk).
@@ -2313,6 +2329,7 @@ static void launch_mfma(dv_ctx* c, int has_hs) {
     else if (two_tiles && c->bcfg.vcode) launch_mfma_dual<4, 2, 2, 4, 1, 4, 3, true, 2>(c, nchunk, has_hs);
     else if (two_tiles) launch_mfma_dual<4, 2, 2, 4, 1, 4, 3, false, 2>(c, nchunk, has_hs);
     else if (use_lc && c->bcfg.vcode) launch_mfma_dual<4, 2, 2, 4, 1, 4, 3, true>(c, nchunk, has_hs);
+    else if (use_lc && lc == 1 && nchunk == 1 && lreg_fits(c)) launch_mfma_dual<4, 2, 2, 4, 1, kLregStage, 3>(c, nchunk, has_hs);
     else if (use_lc && lc == 2) launch_mfma_dual<4, 2, 2, 4, 1, 2, 5>(c, nchunk, has_hs);
     else if (use_lc) launch_mfma_dual<4, 2, 2, 4, 1, 4, 3>(c, nchunk, has_hs);
     else if (tiles == 2) launch_mfma_dual<1, 3, 2, 3, 2>(c, nchunk, has_hs);

@@ -4236,6 +4236,274 @@ sad_lc_fp4(const uint4* __restrict__ ftiles, const uint4* __restrict__ coef4, in
     DV_STAMP(5);
 }
 
+// ------------------------------------------------------------------ fp4 body with the library rows in registers
+// sad_lc_fp4 sends every library row through LDS although exactly one consumer wave reads it: per K-step 8 of the 12 KB of
+// LDS-DMA and 8 of the 24 KB of ds_read_b128, and LDS bandwidth is what holds those consumers at ~1.05 us per stage of four
+// K-steps where their MFMAs need ~0.6.  Here a consumer loads its two view groups' library rows itself (global_load_dwordx4,
+// non-temporal: 16 B per lane and row, the lane's own operand dwords) into a ring of registers one stage (SK K-steps) deep:
+// the row of K-step k is loaded right behind the MFMAs of K-step k - SK into the registers those just read, so SK K-steps x 2
+// rows x 1 KB = 16 KB per consumer, 64 KB per CU, are always on their way.  The loads are compiler-visible: its waitcnt
+// bookkeeping counts them (vmcnt), and across items the cursor walks on into the next item's first stage, so the stream does
+// not drain while the consumers finish an item.  The loaders move the coefficient rows only (4 per K-step, shared by all four
+// consumers) with the ring protocol of sad_lc_fp4: one barrier per stage.
+// The register ring (64 registers) fits beside the accumulators because the bit positions of one width share one (as in
+// sad_lc22_fp4): every position's library bit is moved to the 1.0 bit of its nibble, position 0 accumulates in one block,
+// positions 1, 2, 3 -- whose widths must agree per segment (the host checks, lreg_fits) -- in the other.  The counts are
+// integers (|count| < 2^24), so the sums are bit for bit sad_lc_fp4's.  HT = 1, thermometer rows; the saturation / value
+// boundary NK[0] must be a whole number of stages (the host checks).
+constexpr int kLregStage = 8;                                           // SKL of k_sad_mfma_dual that selects this body
+template <int SK, int RD>
+constexpr int lreg_ring_bytes() { return RD * SK * 4 * 1024; }
+
+template <int SK, int RD, bool FUSE>
+__device__ __forceinline__ void
+sad_lc_fp4_lreg(const uint4* __restrict__ btiles, const uint4* __restrict__ coef4, int* __restrict__ part, const LibCfg& c, const BitCfg& b,
+                int apad_total, int a_off, int has_hs_sum, const FuseArgs& fz, int n_gq) {
+    extern __shared__ uint4 lds_ring[];
+    constexpr int TL = 2;                                               // view groups per consumer
+    constexpr int NW = 8, NC = 4;
+    constexpr int KCOEF = 4;                                            // coefficient rows per K-step
+    constexpr int SLOTB = SK * KCOEF * 1024;
+    constexpr int PER = SK;                                             // LDS-DMA instructions per loader wave and stage
+    constexpr int RING = RD * SLOTB;
+    static_assert(PER * (RD - 1) < 64 && SK % 2 == 0 && RD >= 3, "ring shape");
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const bool loader = wave >= NC;
+    const long long G32 = c.Fpad / 32, GQ = n_gq;
+    const int NKT = b.NK[0] + b.NK[1];
+    const int nst = (NKT + SK - 1) / SK;
+    const int NK0 = b.NK[0];
+    const long long gbytes = (long long)b.GS * 1024;                    // between view groups
+    const unsigned lds_base = (unsigned)(unsigned long long)(lds_ptr_t)lds_ring;
+    unsigned long long* scratch0 = reinterpret_cast<unsigned long long*>(reinterpret_cast<unsigned char*>(lds_ring) + RING);
+    const unsigned char* lib_bytes = reinterpret_cast<const unsigned char*>(btiles);
+    DV_STAMP(0);
+    if constexpr (FUSE) fused_block_begin(scratch0, true);
+    const long long n_mine = GQ > (long long)blockIdx.x ? (GQ - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;       // items of this workgroup
+
+    if (loader) {
+        // ---- loaders: coefficient row of bit position lw of every K-step of the stage (li, lst) into ring slot lslot
+        const int lw = wave - NC;
+        long long li = 0;
+        int lst = 0, lslot = 0;
+        auto issue_stage = [&]() {
+            const unsigned slot = lds_base + (unsigned)lslot * (unsigned)SLOTB;
+            const int kb = lst * SK;
+            const uint4* hot = coef4 + lw * 64 + lane;                  // re-read where there is nothing to fetch (hot in L2)
+#pragma unroll
+            for (int kk = 0; kk < SK; ++kk) {
+                int k = kb + kk;
+                k = k < NKT ? k : NKT - 1;
+                const unsigned dst = __builtin_amdgcn_readfirstlane(slot + (unsigned)((kk * KCOEF + lw) * 1024));
+                lds_dma_16(li < n_mine ? coef4 + ((long long)k * 4 + lw) * 64 + lane : hot, dst);
+            }
+            lslot = lslot + 1 == RD ? 0 : lslot + 1;
+            if (++lst == nst) { lst = 0; ++li; }
+        };
+#pragma unroll
+        for (int r = 0; r < RD - 1; ++r) issue_stage();
+        for (long long j = 0; j < n_mine; ++j) {
+            for (int st = 0; st < nst; ++st) {
+                wait_vmcnt_le<PER * (RD - 2)>();                        // this wave's rows of stage (j, st) have landed ...
+                __builtin_amdgcn_s_barrier();                           // ... everybody's have; nobody still reads the slot before it
+                issue_stage();                                          // (may belong to the next item: its pipeline fill)
+            }
+            if constexpr (FUSE) fused_finish_idle();                    // the barriers of the consumers' finishing
+        }
+        wait_vmcnt_le<0>();                                             // the re-reads past the last item
+    } else {
+        // ---- consumers
+        int cslot = 0;                                                  // ring slot of the current stage
+        int hconst[2] = {0, 0};                                         // this lane's heading constants (fused_finish)
+        if (FUSE) {
+            const int a = a_off + (lane & 31), ac = a < fz.A_real ? a : fz.A_real - 1;
+            hconst[0] = acc_sum(fz.hsconst, ac);
+            hconst[1] = fz.vconst ? acc_sum(fz.vconst, ac) : 0;
+        }
+        // widths of the two accumulator classes, per segment: position 0 | positions 1, 2, 3 (equal where they stand for something)
+        auto w_of = [&](int seg, int cls) -> int {
+            if (cls == 0) return b.wacc[seg][0];
+            const int w1 = b.wacc[seg][1], w2 = b.wacc[seg][2], w3 = b.wacc[seg][3];
+            return w1 ? w1 : (w2 ? w2 : w3);
+        };
+        // library cursor: the stage (lj, lkb / SK) whose rows the ring receives next; item lj's view groups at cp[t]
+        long long lj = 0;
+        int lkb = 0;
+        const unsigned char* cp[TL] = {lib_bytes, lib_bytes};
+        auto cursor_item = [&]() {
+            const long long item = blockIdx.x + (lj < n_mine ? lj : 0) * gridDim.x;     // (past the last item: re-reads of the first)
+            const long long g0 = (item * G32) / GQ, g1 = ((item + 1) * G32) / GQ;
+#pragma unroll
+            for (int t = 0; t < TL; ++t) {
+                const long long g = g0 + wave * TL + t;
+                cp[t] = lib_bytes + (g < g1 ? g : g0) * gbytes + lane * 16;
+            }
+        };
+        v4u_t xr[SK][TL];                                               // the register ring: K-step kk of a stage in xr[kk]
+        auto load_row = [&](int kk) {
+            int k = lkb + kk;
+            k = k < NKT ? k : NKT - 1;
+#pragma unroll
+            for (int t = 0; t < TL; ++t) xr[kk][t] = __builtin_nontemporal_load(reinterpret_cast<const v4u_t*>(cp[t] + (long long)k * 1024));
+        };
+        auto cursor_next = [&]() {                                      // behind a stage's loads
+            lkb += SK;
+            if (lkb >= nst * SK) { lkb = 0; ++lj; cursor_item(); }
+        };
+        if (n_mine > 0) {                                               // (the host launches no workgroup without items)
+            cursor_item();
+#pragma unroll
+            for (int kk = 0; kk < SK; ++kk) load_row(kk);
+            cursor_next();
+        }
+        for (long long j = 0; j < n_mine; ++j) {
+            const long long item = blockIdx.x + j * gridDim.x;
+            const long long g0 = (item * G32) / GQ, g1 = ((item + 1) * G32) / GQ;
+            long long gidx[TL];
+            bool live[TL];
+#pragma unroll
+            for (int t = 0; t < TL; ++t) {
+                const long long g = g0 + wave * TL + t;
+                live[t] = g < g1;
+                gidx[t] = live[t] ? g : g0;
+            }
+            int tot_hs[TL][16], tot_v[TL][16];
+#pragma unroll
+            for (int t = 0; t < TL; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { tot_hs[t][r] = 0; tot_v[t][r] = 0; }
+            // unfused passes store a segment's sums as soon as its accumulators are flushed (as sad_lc_fp4's store_sums)
+            auto store_sums = [&](const int (&tot)[TL][16], int seg) {
+                const int rows = (apad_total - a_off) < 32 ? (apad_total - a_off) : 32;
+#pragma unroll
+                for (int t = 0; t < TL; ++t) {
+                    if (!live[t]) continue;
+                    const int type_row = seg ? has_hs_sum : 0;
+                    int* dst = part + ((long long)type_row * apad_total + a_off) * c.Fpad + gidx[t] * 32 + (lane & 31);
+                    int half = lane >> 5;                               // opaque, as in sad_lc_fp4
+                    asm volatile("" : "+v"(half));
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int m = (r & 3) + 8 * (r >> 2) + 4 * half;
+                        if (m < rows) dst[(long long)m * c.Fpad] = tot[t][r];
+                    }
+                }
+            };
+            {
+                v16f_t acc[TL][2];
+                auto clear = [&]() {
+#pragma unroll
+                    for (int t = 0; t < TL; ++t)
+#pragma unroll
+                        for (int cl = 0; cl < 2; ++cl)
+#pragma unroll
+                            for (int r = 0; r < 16; ++r) acc[t][cl][r] = 0.f;
+                };
+                auto flush = [&](int (&dst)[TL][16], int seg) {
+                    const int w0 = w_of(seg, 0), w1 = w_of(seg, 1);
+#pragma unroll
+                    for (int t = 0; t < TL; ++t)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) dst[t][r] = __mul24(w0, (int)acc[t][0][r]) + __mul24(w1, (int)acc[t][1][r]);
+                };
+                clear();
+                v4u_t a[2][4];                                          // the four coefficient rows of K-step kk in a[kk & 1]
+                auto fetch = [&](int slot_i, auto kc) {
+                    constexpr int kk = decltype(kc)::value;
+                    const unsigned sad = lds_base + (unsigned)slot_i * (unsigned)SLOTB + (unsigned)lane * 16u;
+                    static_for<4>([&](auto sc) { constexpr int s_ = decltype(sc)::value; lds_read16<(kk * KCOEF + s_) * 1024>(a[kk & 1][s_], sad); });
+                };
+                __builtin_amdgcn_s_barrier();                           // stage (j, 0) is in LDS
+                if (j == 0) DV_STAMP(1);
+                fetch(cslot, IntC<0>{});
+                auto run_stages = [&](int s0, int s1) {
+                    for (int st = s0; st < s1; ++st) {
+                        const int kb = st * SK;
+                        const int nslot = cslot + 1 == RD ? 0 : cslot + 1;
+                        static_for<SK>([&](auto kc) {
+                            constexpr int kk = decltype(kc)::value;
+                            if constexpr (kk + 1 < SK) {
+                                fetch(cslot, IntC<kk + 1>{});           // one K-step ahead
+                                lds_wait<4>();                          // all but the newest K-step's reads have landed
+                            } else {
+                                lds_wait<0>();                          // everything this wave will use of the slot is in registers
+                                if (st + 1 < nst) {
+                                    __builtin_amdgcn_s_barrier();       // stage st + 1 is in LDS; the loaders may refill slot st - 1 ... and,
+                                    fetch(nslot, IntC<0>{});            //   one barrier later, this one
+                                }
+                            }
+#pragma unroll
+                            for (int s = 0; s < 4; ++s) lds_tie(a[kk & 1][s]);
+                            // every position's bit to the 1.0 bit of its nibble (E2M1 0010): positions 0 / 2 / 3 by a shift
+                            const unsigned m = kb + kk < NKT ? 0x22222222u : 0u;
+                            unsigned bo[TL][4][4];
+                            // (pinned to this K-step: the compiler hoisted masks of K-step 6 into K-step 1, and its vmcnt wait for
+                            // them drained the ring there -- every use of xr[kk] now waits behind this volatile no-op, in order)
+#pragma unroll
+                            for (int t = 0; t < TL; ++t) lds_tie(xr[kk][t]);
+#pragma unroll
+                            for (int t = 0; t < TL; ++t) {
+                                const unsigned x[4] = {xr[kk][t].x, xr[kk][t].y, xr[kk][t].z, xr[kk][t].w};
+#pragma unroll
+                                for (int d = 0; d < 4; ++d) {
+                                    bo[t][0][d] = (x[d] << 1) & m;
+                                    bo[t][1][d] = x[d] & m;
+                                    bo[t][2][d] = (x[d] >> 1) & m;
+                                    bo[t][3][d] = (x[d] >> 2) & m;
+                                }
+                            }
+                            load_row(kk);                               // K-step kk of the cursor's stage into the registers just read
+#pragma unroll
+                            for (int s = 0; s < 4; ++s) {
+                                const v4u_t& av = a[kk & 1][s];
+                                const v8i_t ao = v8i_t{(int)av.x, (int)av.y, (int)av.z, (int)av.w, 0, 0, 0, 0};
+#pragma unroll
+                                for (int t = 0; t < TL; ++t) {
+                                    const v8i_t bv = v8i_t{(int)bo[t][s][0], (int)bo[t][s][1], (int)bo[t][s][2], (int)bo[t][s][3], 0, 0, 0, 0};
+                                    if constexpr (FUSE) acc[t][s ? 1 : 0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bv, ao, acc[t][s ? 1 : 0], 4, 4, 0, 0, 0, 0);   // views x headings
+                                    else acc[t][s ? 1 : 0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ao, bv, acc[t][s ? 1 : 0], 4, 4, 0, 0, 0, 0);
+                                }
+                            }
+                        });
+                        cursor_next();
+                        cslot = nslot;
+                    }
+                };
+                // saturation stages (when the library has that segment), then the value stages; the accumulators change hands at the boundary
+                const int nst0 = has_hs_sum ? (NK0 / SK < nst ? NK0 / SK : nst) : 0;       // (NK0 is a whole number of stages: the host checks)
+                const int hs_end = (has_hs_sum && !(c.hasv && b.NK[1] > 0)) ? nst : nst0;
+                run_stages(0, hs_end);
+                if (hs_end > 0 && hs_end < nst) {
+                    flush(tot_hs, 0);
+                    if constexpr (!FUSE) store_sums(tot_hs, 0);
+                    clear();
+                }
+                run_stages(hs_end, nst);
+                if (hs_end < nst) flush(tot_v, 1);                      // what the accumulators hold at the end: the value segment's sums,
+                else flush(tot_hs, 0);                                  // unless there are no value K-steps
+                if constexpr (!FUSE) {
+                    // (a sum without K-steps is stored as the zeros it was initialised to)
+                    if (has_hs_sum && !(hs_end > 0 && hs_end < nst)) store_sums(tot_hs, 0);
+                    if (c.hasv) store_sums(tot_v, 1);
+                }
+            }
+            if (j == 0) DV_STAMP(2);
+            if constexpr (FUSE) {
+                if (j == 0) DV_STAMP(3);
+                auto of_hs = [&](int t, int r) -> int { return tot_hs[t][r]; };
+                auto of_v = [&](int t, int r) -> int { return tot_v[t][r]; };
+                fused_finish<TL, NW, true>(of_hs, of_v, gidx, live, scratch0, c, fz, a_off, has_hs_sum, j, lane, wave, (int)(j & 1), NC, hconst);
+                if (j == 0) DV_STAMP(4);
+            }
+        }
+    }
+    if constexpr (FUSE) {
+        if (a_off < fz.A_real) fused_block_end(scratch0, fz, c, a_off);
+    }
+    DV_STAMP(5);
+}
+
 // ------------------------------------------------------------------ loader / consumer body, two view groups x two heading tiles
 // sad_lc_fp4 with two heading tiles (HT = 2: the ensemble passes of 64 headings) gives a consumer ONE view group: per K-step it reads
 // eight coefficient rows and one library row from LDS for eight MFMAs, and the CU's LDS moves 4 x 9 KB of reads + 12 KB of LDS-DMA =
@@ -4586,7 +4854,12 @@ k_sad_mfma_dual(const uint4* __restrict__ btiles, const uint4* __restrict__ ftil
     if constexpr (SKL > 0) {
         static_assert(TILES == 1, "the loader / consumer body cuts the library into ranges of 8 / HT view groups; the other bodies must agree");
         if (fp4 && nchunk == 1) {
-            sad_lc_fp4<SKL, RDL, FUSE, LCODE, HT>(ftiles, coef4, part, c, b, apad_total, a_off, has_hs_sum, fz, n_gq);     // LCODE == (b.vcode != 0)
+            if constexpr (SKL == kLregStage) {                          // the library rows in the consumers' registers (thermometer rows)
+                static_assert(HT == 1 && !LCODE, "sad_lc_fp4_lreg: one heading tile, thermometer rows");
+                sad_lc_fp4_lreg<SKL, RDL, FUSE>(btiles, coef4, part, c, b, apad_total, a_off, has_hs_sum, fz, n_gq);
+            } else {
+                sad_lc_fp4<SKL, RDL, FUSE, LCODE, HT>(ftiles, coef4, part, c, b, apad_total, a_off, has_hs_sum, fz, n_gq);     // LCODE == (b.vcode != 0)
+            }
             return;
         }
     }

@@ -207,6 +207,18 @@ int dv_sense_step_batch(dv_ctx *ctx, const double *x, const double *y, const dou
 int dv_sense_step_batch_weighted(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
                                  const double *chem_weights, uint32_t flags, dv_step_result *results);
 /*
+ * dv_sense_step_batch_weighted that also returns every agent's scene_familiarity (NavBySceneFamiliarity.py:283-303 for each trial):
+ * scene_fam = double[n_agents][F], non-NULL; scene_fam[i][f] = minimum over agent i's OWN n_headings headings of view f's familiarity
+ * under chem_weights[i] (NULL: the library's weight) -- the values dv_sense_step(x[i], y[i], angles[i], ..., scene_fam) returns for
+ * that pose on a library of that weight, bit for bit.  results as from dv_sense_step_batch_weighted (the same records).  An agent
+ * with DV_RES_SENSE_ERROR gets a row of +inf (the reference has reset the array to inf before it senses, :287).  Argument errors as
+ * for dv_sense_step_batch_weighted.  The passes keep their sums in HBM and run one after the other (as a single-agent step with
+ * scene_fam does), so this is the call for reading the minimum, not for stepping; its row buffers are allocated at the first call
+ * and grow only when a later call's passes hold more agents or views.  sads_hsv libraries only (DV_ERR_STATE otherwise).
+ */
+int dv_sense_step_batch_scene(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
+                              const double *chem_weights, uint32_t flags, dv_step_result *results, double *scene_fam);
+/*
  * The device work AND the device-side book-keeping of one agent step in ONE call (the fast path of
  * navsim_amd.NavBySceneFamiliarity.step_forward; a 60 us step does not want three trips through a binding):
  *   1. when an error-metric answer is outstanding (dv_path_error_enqueue of an earlier step), it is collected:
@@ -297,6 +309,9 @@ int dv_step_batch(dv_ctx *ctx, const uint8_t *patches, int n_agents, int n_headi
 /* dv_step_batch with a chem_weight per agent; the rules of dv_sense_step_batch_weighted. */
 int dv_step_batch_weighted(dv_ctx *ctx, const uint8_t *patches, int n_agents, int n_headings, const double *chem_weights,
                            uint32_t flags, dv_step_result *results);
+/* dv_step_batch_weighted that also returns scene_fam = double[n_agents][F]; the rules of dv_sense_step_batch_scene. */
+int dv_step_batch_scene(dv_ctx *ctx, const uint8_t *patches, int n_agents, int n_headings, const double *chem_weights,
+                        uint32_t flags, dv_step_result *results, double *scene_fam);
 /* Re-run the exact resolver on the candidates of the last step (sharded runs, cross-rank ties). */
 int dv_resolve(dv_ctx *ctx, dv_step_result *result);
 

@@ -220,6 +220,12 @@ struct dv_ctx {
     double* d_record = nullptr;               // [3 + 4*64] packed record of the last step, for device-side exchange
     unsigned long long* d_keys = nullptr;     // [64 + 4*64] packed keys of the last step (all-reduce(max) exchange)
     double* h_scene = nullptr;                // pinned staging for scene_fam
+    // per-agent scene_fam of a batched pass (dv_step_batch_scene / dv_sense_step_batch_scene): one row of F doubles per agent of
+    // the resident pass, allocated at the first such call and grown only when a later call's passes hold more agents or views
+    double* d_scene_b = nullptr;              // [scene_b_cap] = [agents of a pass][F]
+    double* h_scene_b = nullptr;              // pinned staging, same size
+    size_t scene_b_cap = 0;                   // doubles
+    bool scene_batch = false;                 // the call in progress wants the rows (run_batch_scene): k_finish / k_tail write them
     int A = 0, APAD = 0;                      // resident patches (all agents of the pass)
     int n_agents = 1, A_agent = 0;            // agents in the resident pass and headings per agent
     bool step_pending = false;
@@ -316,6 +322,9 @@ static void free_library(dv_ctx* c) {
     F(c->d_state); F(c->d_cand); F(c->d_cand_exact);
     if (c->h_result) { (void)hipHostFree(c->h_result); c->h_result = nullptr; c->d_result = nullptr; }
     if (c->h_scene) { (void)hipHostFree(c->h_scene); c->h_scene = nullptr; }
+    F(c->d_scene_b);
+    if (c->h_scene_b) { (void)hipHostFree(c->h_scene_b); c->h_scene_b = nullptr; }
+    c->scene_b_cap = 0;
     c->have_lib = false;
     for (int i = 0; i < 4; ++i) c->tuned_shape[i] = 0;
     c->A = 0;
@@ -2660,7 +2669,7 @@ static void launch_fold(dv_ctx* c, int nb, StepResultDev* outp, double* recp, in
 }
 
 template <int NT>
-static void launch_finish(dv_ctx* c, int want_scene, int force) {
+static void launch_finish(dv_ctx* c, int want_scene, double* scene, int force) {
     const LibCfg& g = c->cfg;
     // Large libraries (more than 256 blocks of 256 views): the blocks only leave their summaries and k_fold, a 1024-thread
     // kernel behind them, folds and decides -- the serial walk of thousands of summaries by one 256-thread last block cost
@@ -2675,7 +2684,7 @@ static void launch_finish(dv_ctx* c, int want_scene, int force) {
     ++c->seq;
     hipLaunchKernelGGL(k_finish<NT>, dim3(nb, (unsigned)c->n_agents), dim3(256), 0, c->stream,
                        c->d_part, c->int_hsconst, c->int_vconst, c->nchunk, c->APAD, c->int_has_hs, c->int_has_v, c->d_state, c->d_bsum, c->d_ctmp,
-                       c->d_cand, c->d_scene, outp, recp, c->cfg, c->A_agent, c->delta, want_scene, force,
+                       c->d_cand, scene, outp, recp, c->cfg, c->A_agent, c->delta, want_scene, force,
                        c->seq, serr, step_fenced(c), (int)vb, separate, wts_ptr(c));
     if (separate) launch_fold(c, (int)nb, outp, recp, force, c->seq, serr);
 }
@@ -2684,7 +2693,10 @@ static int enqueue_step(dv_ctx* c, uint32_t flags, bool want_scene) {
     const LibCfg& g = c->cfg;
     c->agent_pending = 0;                                               // (dv_agent_step_begin sets it behind its own enqueue)
     const int force = (flags & DV_STEP_FORCE_RESOLVE) ? 1 : 0;
-    const int scene_on = (want_scene && c->n_agents == 1) ? 1 : 0;
+    // the per-view minimum over an agent's own headings: one row per agent of the pass.  A batched pass has rows to write to only
+    // inside dv_step_batch_scene / dv_sense_step_batch_scene (d_scene holds one row)
+    const int scene_on = (want_scene && (c->n_agents == 1 || c->scene_batch)) ? 1 : 0;
+    double* const scene_dst = c->scene_batch ? c->d_scene_b : c->d_scene;
     // integer path: the scoring kernel's partial sums go straight to k_finish (combine + reductions + decision in one
     // launch); the exact mode and ssd_f32 produce fam[] first and end in k_tail
     // Where it pays (measured, DEJAVU_FINISH=0/1/2): up to 16 headings per agent and libraries from ~32 k views.
@@ -2720,19 +2732,21 @@ static int enqueue_step(dv_ctx* c, uint32_t flags, bool want_scene) {
         launch_fold(c, c->fused_nb, c->d_result + c->result_slot, c->d_record + (size_t)c->result_slot * (3 + 4 * kMaxHeadings), force, ++c->seq,
                     sense_err_ptr(c));
     } else if (fused) {
-        if (c->A_agent <= 16) launch_finish<1>(c, scene_on, force);
-        else launch_finish<2>(c, scene_on, force);
+        if (c->A_agent <= 16) launch_finish<1>(c, scene_on, scene_dst, force);
+        else launch_finish<2>(c, scene_on, scene_dst, force);
     } else {
         // (one view per thread: with 64 blocks walking the views block-stride -- fewer arrival tickets on the one word -- k_tail took
         // 18.5 us instead of 14.9 at 50 000 views x 16 headings: its time is the scores' read, not the tickets)
         hipLaunchKernelGGL(k_tail, dim3((unsigned)((g.F + 255) / 256), (unsigned)c->n_agents), dim3(256), 0, c->stream, c->d_fam,
-                           c->d_pmax, c->n_partial, c->d_state, c->d_cand, c->d_scene, c->d_result + c->result_slot,
+                           c->d_pmax, c->n_partial, c->d_state, c->d_cand, scene_dst, c->d_result + c->result_slot,
                            c->d_record + (size_t)c->result_slot * (3 + 4 * kMaxHeadings), c->cfg,
                            c->A_agent, c->delta, scene_on, (c->exact || c->metric == 2) ? 1 : 0, force, ++c->seq,
                            sense_err_ptr(c), c->metric == 1 ? 3e-6 : 0.0, step_fenced(c));
     }
     HIP_TRY(c, hipGetLastError());
-    if (want_scene)
+    if (want_scene && c->scene_batch)
+        HIP_TRY(c, hipMemcpyAsync(c->h_scene_b, c->d_scene_b, (size_t)c->n_agents * g.F * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    else if (want_scene)
         HIP_TRY(c, hipMemcpyAsync(c->h_scene, c->d_scene, (size_t)g.F * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     c->step_pending = true;
     c->last_want_scene = want_scene;
@@ -2821,11 +2835,20 @@ static int finish_pass(dv_ctx* c) {
         std::vector<long long> n_first(c->n_agents);
         std::vector<unsigned> had(c->n_agents);
         for (int ag = 0; ag < c->n_agents; ++ag) { n_first[ag] = c->h_result[ag].n_candidates; had[ag] = c->h_result[ag].flags; }
+        // per-agent scene_fam rows: the redo writes every agent's row from exact scores, but an agent that did not overflow keeps
+        // the row of the pass it was decided in (what a step of that agent alone returns)
+        const bool keep_rows = c->scene_batch && c->last_want_scene && !was_exact;
+        std::vector<double> kept;
+        if (keep_rows) kept.assign(c->h_scene_b, c->h_scene_b + (size_t)c->n_agents * c->cfg.F);
         c->exact = 1;
         int rc = enqueue_step(c, 0, c->last_want_scene);
         c->exact = was_exact;
         if (rc) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (keep_rows)
+            for (int ag = 0; ag < c->n_agents; ++ag)
+                if (!(had[ag] & DV_RES_OVERFLOW))
+                    memcpy(c->h_scene_b + (size_t)ag * c->cfg.F, kept.data() + (size_t)ag * c->cfg.F, (size_t)c->cfg.F * sizeof(double));
         for (int ag = 0; ag < c->n_agents; ++ag)
             if (had[ag] & DV_RES_OVERFLOW) { c->h_result[ag].flags |= DV_RES_OVERFLOW; c->h_result[ag].n_candidates = n_first[ag]; }
     }
@@ -2897,6 +2920,95 @@ extern "C" int dv_step_batch_weighted(dv_ctx* c, const uint8_t* patches, int n_a
 
 extern "C" int dv_step_batch(dv_ctx* c, const uint8_t* patches, int n_agents, int A, uint32_t flags, dv_step_result* results) {
     return dv_step_batch_weighted(c, patches, n_agents, A, nullptr, flags, results);
+}
+
+// Batched passes that also keep scene_fam per agent: scene_fam[i][f] = minimum over agent i's OWN A headings of view f's
+// familiarity, under agent i's weight.  The finishing kernels already own one agent per blockIdx.y -- its headings
+// [slot * A, (slot + 1) * A), its weights -- so the segmented minimum is the one a single-agent step forms, written to row `slot`
+// of d_scene_b.  Like the single-agent want_scene step the passes take the unfused route (sums through HBM, k_finish or k_combine +
+// k_tail behind the scoring kernel) and run one after the other on the context's stream: each pass's rows are copied out before
+// the next pass overwrites them.  finish_pass handles resolver and overflow per pass.
+template <class Stage>
+static int run_batch_scene(dv_ctx* c, int n_agents, int A, uint32_t flags, dv_step_result* results, double* scene_fam, Stage stage) {
+    const LibCfg& g = c->cfg;
+    const int per_pass = kMaxHeadings / A;
+    const size_t need = (size_t)(n_agents < per_pass ? n_agents : per_pass) * (size_t)g.F;
+    if (c->scene_b_cap < need) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (c->d_scene_b) { (void)hipFree(c->d_scene_b); c->d_scene_b = nullptr; }
+        if (c->h_scene_b) { (void)hipHostFree(c->h_scene_b); c->h_scene_b = nullptr; }
+        c->scene_b_cap = 0;
+        HIP_TRY(c, hipMalloc(&c->d_scene_b, need * sizeof(double)));
+        HIP_TRY(c, hipHostMalloc(&c->h_scene_b, need * sizeof(double)));
+        c->scene_b_cap = need;
+    }
+    struct Off { dv_ctx* c; ~Off() { c->scene_batch = false; } } off{c};
+    c->scene_batch = true;
+    const double inf = std::numeric_limits<double>::infinity();
+    for (int first = 0; first < n_agents; first += per_pass) {
+        const int n = (n_agents - first < per_pass) ? n_agents - first : per_pass;
+        int rc = stage(first, n);
+        if (rc) return rc;
+        c->result_slot = 0;
+        rc = enqueue_step(c, flags, true);
+        if (rc) return rc;
+        rc = finish_pass(c);
+        if (rc) return rc;
+        for (int ag = 0; ag < n; ++ag) {
+            copy_result(c, ag, &results[first + ag]);
+            double* row = scene_fam + (size_t)(first + ag) * (size_t)g.F;
+            if (c->h_result[ag].flags & kResSenseError)       // the reference has reset the array to inf before it senses
+                for (int64_t f = 0; f < g.F; ++f) row[f] = inf;
+            else
+                memcpy(row, c->h_scene_b + (size_t)ag * (size_t)g.F, (size_t)g.F * sizeof(double));
+        }
+    }
+    return DV_OK;
+}
+
+extern "C" int dv_step_batch_scene(dv_ctx* c, const uint8_t* patches, int n_agents, int A, const double* chem_weights, uint32_t flags,
+                                   dv_step_result* results, double* scene_fam) {
+    int rc = check_step_args(c, A);
+    if (rc) return rc;
+    if (!patches || !results || !scene_fam || n_agents < 1) return fail(c, DV_ERR_INVALID, "dv_step_batch_scene: bad arguments");
+    if (c->metric != 0) return fail(c, DV_ERR_STATE, "dv_step_batch_scene needs a sads_hsv library");
+    HIP_TRY(c, hipSetDevice(c->device));
+    WeightsOff off{c};
+    rc = stage_weights(c, chem_weights, n_agents, "dv_step_batch_scene");
+    if (rc) return rc;
+    const size_t agent_bytes = (size_t)A * c->cfg.P * 3;
+    return run_batch_scene(c, n_agents, A, flags, results, scene_fam, [&](int first, int n) {
+        if (upload_weights(c, first, n)) return (int)DV_ERR_HIP;
+        if (hipMemcpyAsync(c->d_raw_patches, patches + (size_t)first * agent_bytes, (size_t)n * agent_bytes, hipMemcpyHostToDevice,
+                           c->stream) != hipSuccess)
+            return fail(c, DV_ERR_HIP, "dv_step_batch_scene: patch upload failed: %s", hipGetErrorString(hipGetLastError()));
+        const int rc2 = prep_patches(c, n * A);
+        if (rc2) return rc2;
+        c->n_agents = n;
+        c->A_agent = A;
+        return (int)DV_OK;
+    });
+}
+
+extern "C" int dv_sense_step_batch_scene(dv_ctx* c, const double* x, const double* y, const double* angles, int n_agents, int A,
+                                         const double* chem_weights, uint32_t flags, dv_step_result* results, double* scene_fam) {
+    int rc = check_sense_args(c, A);
+    if (rc) return rc;
+    if (!x || !y || !angles || !results || !scene_fam || n_agents < 1) return fail(c, DV_ERR_INVALID, "dv_sense_step_batch_scene: bad arguments");
+    if (c->metric != 0) return fail(c, DV_ERR_STATE, "dv_sense_step_batch_scene needs a sads_hsv library");
+    HIP_TRY(c, hipSetDevice(c->device));
+    WeightsOff off{c};
+    rc = stage_weights(c, chem_weights, n_agents, "dv_sense_step_batch_scene");
+    if (rc) return rc;
+    return run_batch_scene(c, n_agents, A, flags, results, scene_fam, [&](int first, int n) {
+        PoseSet poses;
+        for (int ag = 0; ag < n; ++ag)
+            for (int a = 0; a < A; ++a)
+                poses.p[ag * A + a] = make_pose(x[first + ag], y[first + ag], angles[(size_t)(first + ag) * A + a]);
+        for (int a = n * A; a < kMaxHeadings; ++a) poses.p[a] = Pose{0., 0., 1., 0.};
+        const int r2 = upload_weights(c, first, n);
+        return r2 ? r2 : sense_prep_launch(c, poses, n, A);
+    });
 }
 
 // Steps of any number of headings: passes of at most kMaxHeadings, merged by the rule of NavBySceneFamiliarity.py:313-315.

@@ -970,7 +970,8 @@ __device__ __forceinline__ void emit_record(const StepResultDev* r, double* __re
 //  3. the block that finishes last decides (argmax over headings) unless more than one candidate
 //     needs exact re-scoring, in which case it flags the result and the host runs k_resolve + k_decide.
 // blockIdx.y = agent of a batched pass: agent g owns headings [g*A, (g+1)*A) and its own state, candidate list,
-// result record and packed record.
+// result record and packed record -- and, with want_scene, row g of scene[agents][F]: the minimum of step 2 runs over the
+// agent's own headings, so a batched pass leaves every agent the scene_fam a step of its own would (dv_step_batch_scene).
 __global__ void __launch_bounds__(256)
 k_tail(const double* __restrict__ fam, const unsigned long long* __restrict__ pmax, int n_partial,
        StepState* __restrict__ st, unsigned long long* __restrict__ cand, double* __restrict__ scene,
@@ -1039,7 +1040,7 @@ k_tail(const double* __restrict__ fam, const unsigned long long* __restrict__ pm
                 }
             }
         }
-        if (want_scene) scene[f] = smin;
+        if (want_scene) scene[(long long)agent * c.F + f] = smin;        // row of this agent of the pass: double[n_agents][F]
     }
 
     // Arrival ticket.  Everything the last block reads from the others (aview[], ncand) was written with device-scope
@@ -1115,6 +1116,7 @@ k_tail(const double* __restrict__ fam, const unsigned long long* __restrict__ pm
 //     candidate list from the representatives and the shared list, dropping what falls short -- the same set
 //     k_tail lists.  It then decides and writes the record as k_tail does, and clears the counters for the next step.
 // Cross-block data travels through device-scope atomic stores/loads (no fences, see k_tail).
+// want_scene: the thread's minimum over the headings of ITS agent (blockIdx.y) goes to row blockIdx.y of scene[agents][F], as in k_tail.
 constexpr int kTmpCap = 4096;       // entries of the shared extra-candidate list per agent
 
 // The part of k_finish after every block has left its summary: fold the summaries into per-heading maxima and first
@@ -1379,7 +1381,7 @@ k_finish(const unsigned* __restrict__ part, const int* __restrict__ hsconst, con
             }
         }
     }
-    if (inb && want_scene) scene[f] = smin;
+    if (inb && want_scene) scene[(long long)agent * c.F + f] = smin;     // row of this agent of the pass: double[n_agents][F]
     __syncthreads();
     if (tid < A && s_bmax[tid] != 0) {
         // This set's representative of heading tid against the block's so far: larger key, then smaller view, wins.  The

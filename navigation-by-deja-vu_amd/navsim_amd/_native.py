@@ -138,6 +138,8 @@ PROTOTYPES = {
                                            ctypes.POINTER(StepResult)]),
     "dv_sense_step_batch_weighted": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _f64p, ctypes.c_uint32,
                                                     ctypes.POINTER(StepResult)]),
+    "dv_sense_step_batch_scene": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _f64p, ctypes.c_uint32,
+                                                 ctypes.POINTER(StepResult), _f64p]),
     "dv_agent_step": (ctypes.c_int, [_ctx_p, ctypes.c_double, ctypes.c_double, ctypes.c_double, _f64p, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_double, ctypes.c_double, ctypes.c_double, _f64p, ctypes.POINTER(ctypes.c_int32), _f64p,
                                      ctypes.POINTER(ctypes.c_int32)]),
@@ -163,6 +165,8 @@ PROTOTYPES = {
                                      ctypes.POINTER(StepResult)]),
     "dv_step_batch_weighted": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, _f64p, ctypes.c_uint32,
                                               ctypes.POINTER(StepResult)]),
+    "dv_step_batch_scene": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, _f64p, ctypes.c_uint32,
+                                           ctypes.POINTER(StepResult), _f64p]),
     "dv_resolve": (ctypes.c_int, [_ctx_p, ctypes.POINTER(StepResult)]),
     "dv_step_wide": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(WideResult), _f64p, _i64p, _f64p]),
     "dv_sense_step_wide": (ctypes.c_int, [_ctx_p, ctypes.c_double, ctypes.c_double, _f64p, ctypes.c_int, ctypes.c_uint32,

@@ -504,7 +504,8 @@ class NavBySceneFamiliarity(object):
 
     # ---- scene_familiarity: kept every step, or worked out when it is read ----------------------
     _scene_fam = None
-    _scene_stale = None
+    _scene_stale = None            # what the last step left to work out: (x, y, angle) of a step of its own, or an ensemble's note
+    _scene_owner = None            # the NavEnsemble that took the last step and works its members' rows out together (else None)
 
     @property
     def scene_familiarity(self):
@@ -512,7 +513,11 @@ class NavBySceneFamiliarity(object):
         (`lazy_scene`, the default) a step only notes its pose; the first read senses that pose again and takes the minimum then --
         the same patches, the same numbers, paid by whoever reads them."""
         st = self._scene_stale
-        if st is not None:
+        if st is not None and self._scene_owner is not None:
+            # the step was an ensemble's (NavEnsemble._note_scene): the ensemble works out what all its members have left to work
+            # out, in library passes they share
+            self._scene_owner._read_scene()
+        elif st is not None:
             self._scene_stale = None
             res = self._engine.sense_step(st[0], st[1], (st[2] + self.angle_offsets) % (2 * np.pi), want_scene=True)
             self._scene_fam[:] = res["scene_familiarity"]
@@ -521,6 +526,7 @@ class NavBySceneFamiliarity(object):
     @scene_familiarity.setter
     def scene_familiarity(self, value):
         self._scene_stale = None
+        self._scene_owner = None
         self._scene_fam = value
 
     # ---- the step (:279-329) -------------------------------------------------------------------
@@ -540,6 +546,7 @@ class NavBySceneFamiliarity(object):
         cand = None
         scene_stale = None
         self._scene_stale = None               # (whatever was left to work out belonged to the step before)
+        self._scene_owner = None
         begun_next = None                      # (the next step was begun by the call that ended this one, an error answer it collected)
         if engine is not None and str(getattr(func, "metric", "")).startswith("ssd"):
             self._step_ssd(func, engine, position)

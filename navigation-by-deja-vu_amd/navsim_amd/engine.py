@@ -21,11 +21,14 @@ class BatchResults(object):
     """The records of an ensemble step (dv_step_batch / dv_sense_step_batch), one per agent.  A sequence of the per-agent result
     dictionaries step() returns -- made when asked for -- and, for callers that only move agents, the same numbers as arrays over
     the records' own memory: best_idex[n], best_view[n], step_familiarity[n], flags[n], n_candidates[n], angle_familiarity[n, A],
-    angle_view[n, A].  (32 dictionaries per ensemble step cost the host 60-80 us beside a 0.8 ms device step.)"""
+    angle_view[n, A].  (32 dictionaries per ensemble step cost the host 60-80 us beside a 0.8 ms device step.)
+    scene_familiarity: float64[n, F] after sense_step_batch_scene / step_batch_scene (row i: the per-view minimum over agent i's own
+    headings), else None."""
     _DTYPE = np.dtype(N.StepResult)
 
-    def __init__(self, raw, n, A):
+    def __init__(self, raw, n, A, scene=None):
         self._raw, self.n, self.A = raw, n, A
+        self.scene_familiarity = scene
         rec = np.frombuffer(raw, dtype=self._DTYPE, count=n)
         self.records = rec
         self.best_idex, self.best_view, self.step_familiarity = rec["best_heading"], rec["best_view"], rec["best_fam"]
@@ -349,6 +352,27 @@ class FamiliarityEngine(object):
                                                                      N.f64ptr(w), flags, res), "dv_sense_step_batch_weighted")
         return BatchResults(res, n, A)
 
+    def sense_step_batch_scene(self, x, y, angles, force_resolve=False, chem_weights=None):
+        """sense_step_batch that also keeps every agent's per-view minimum (dv_sense_step_batch_scene): the same records, and
+        BatchResults.scene_familiarity = float64[N, F], row i the minimum over agent i's OWN headings under its own weight -- what
+        sense_step(x[i], y[i], angles[i], want_scene=True) returns, bit for bit; a row of +inf for an agent whose footprint left
+        the landscape (flags & DV_RES_SENSE_ERROR).  The passes go through HBM one after the other: a call for reading the minimum
+        of a step already taken (NavEnsemble.scene_familiarity), not for stepping."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        angles = np.ascontiguousarray(angles, dtype=np.float64)
+        if angles.ndim != 2 or len(x) != len(y) or angles.shape[0] != len(x):
+            raise ValueError("x[N], y[N] and angles[N, A] expected")
+        n, A = angles.shape
+        w = agent_weights(chem_weights, n)
+        res = (N.StepResult * n)()
+        scene = np.empty((n, int(self.n_views)), dtype=np.float64)
+        self._check_sense(self._lib.dv_sense_step_batch_scene(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A,
+                                                              None if w is None else N.f64ptr(w),
+                                                              N.DV_STEP_FORCE_RESOLVE if force_resolve else 0, res, N.f64ptr(scene)),
+                          "dv_sense_step_batch_scene")
+        return BatchResults(res, n, A, scene)
+
     def set_library_from_poses(self, x, y, angle, chem_weight=0.0, first_view=0, want_views=True):
         """train_from_path on the device: sense the poses and ingest them as the library; returns familiar_scenes."""
         x, y, angle = self._pose_arrays(x, y, angle)
@@ -447,6 +471,22 @@ class FamiliarityEngine(object):
             self._check(self._lib.dv_step_batch_weighted(self._ctx, N.u8ptr(patches), n, A, N.f64ptr(w), flags, res),
                         "dv_step_batch_weighted")
         return BatchResults(res, n, A)
+
+    def step_batch_scene(self, patches, force_resolve=False, chem_weights=None):
+        """step_batch that also keeps every agent's per-view minimum (dv_step_batch_scene): BatchResults.scene_familiarity =
+        float64[N, F], row i what step(patches[i], want_scene=True) returns under agent i's weight."""
+        patches = N.as_u8(patches, "patches")
+        if patches.ndim != 5:
+            raise ValueError("patches must be uint8[N,A,h,w,3]")
+        n, A = patches.shape[0], patches.shape[1]
+        self._patch_shape_ok(patches, (n, A))
+        w = agent_weights(chem_weights, n)
+        res = (N.StepResult * n)()
+        scene = np.empty((n, int(self.n_views)), dtype=np.float64)
+        self._check(self._lib.dv_step_batch_scene(self._ctx, N.u8ptr(patches), n, A, None if w is None else N.f64ptr(w),
+                                                  N.DV_STEP_FORCE_RESOLVE if force_resolve else 0, res, N.f64ptr(scene)),
+                    "dv_step_batch_scene")
+        return BatchResults(res, n, A, scene)
 
     # -- ssd_f32 metric --------------------------------------------------------------------------
     @staticmethod

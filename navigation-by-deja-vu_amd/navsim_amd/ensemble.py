@@ -9,6 +9,12 @@ and no longer takes part.
 Members may score under chem_weights of their own (the experiment grid's chem_weight variable, scripts/run_experiment.py:61,218):
 a trial's training views do not depend on the weight, so one library serves every weight its layout stores the sums for
 (FamiliarityEngine.set_weight_range), and the members of all weights share the library passes (dv_sense_step_batch_weighted).
+
+Members may track scene_familiarity (the constructor's default, the reference's agent).  The ensemble's step is the same either way:
+it only remembers, per tracking member, the pose, candidate headings and weight of the step it last took.  When a member's
+`scene_familiarity` -- or NavEnsemble.scene_familiarity() for all members -- is read, those poses are sensed once more and the
+per-view minimum over each member's OWN headings comes back from shared library passes (dv_sense_step_batch_scene), as the
+single agent works its minimum out when it is read.
 """
 import numpy as np
 
@@ -22,7 +28,7 @@ class NavEnsemble(object):
         eng = agents[0]._engine
         if eng is None or any(a._engine is not eng for a in agents):
             raise ValueError("the agents of an ensemble share one engine (NavEnsemble.from_agent)")
-        if any(a.track_scene_familiarity for a in agents):
+        if any(a.track_scene_familiarity for a in agents) and not hasattr(eng, "sense_step_batch_scene"):
             raise ValueError("construct the agents with track_scene_familiarity=False: a batched pass keeps no per-view minimum")
         self.agents = list(agents)
         self.engine = eng
@@ -110,6 +116,44 @@ class NavEnsemble(object):
             a.chem_weight = None if weights is None else weights[i]
         return cls(agents)
 
+    # ---- scene_familiarity of tracking members: worked out when it is read -------------------------------------
+    def _note_scene(self, agent, x, y, headings, weight):
+        """`agent` has just been scored at (x, y) along `headings` under `weight`: what its scene_familiarity is made from when read."""
+        agent._scene_stale = (x, y, headings, weight)
+        agent._scene_owner = self
+        agent._scene_is_inf = False
+
+    def _scene_inf(self, agent):
+        """`agent` stopped before it was scored: the reference had reset the array to +inf before it sensed (:287)."""
+        if agent.track_scene_familiarity:
+            agent._scene_stale = None                         # (whatever was left to work out belonged to the step before)
+            agent._scene_owner = None
+            agent._scene_fam[:] = np.inf
+            agent._scene_is_inf = True
+
+    def _read_scene(self):
+        """The per-view minima every member's last step left to work out, all members in shared library passes."""
+        todo = [a for a in self.agents if a._scene_stale is not None and a._scene_owner is self]
+        if not todo:
+            return
+        st = [a._scene_stale for a in todo]
+        weights = None if all(t[3] is None for t in st) else [t[3] for t in st]
+        res = self.engine.sense_step_batch_scene([t[0] for t in st], [t[1] for t in st], np.stack([t[2] for t in st]), chem_weights=weights)
+        for a, row in zip(todo, res.scene_familiarity):
+            a._scene_stale = None
+            a._scene_owner = None
+            a._scene_fam[:] = row
+
+    def scene_familiarity(self):
+        """float64[n_members, F]: every member's scene_familiarity after its last step (members that never stepped: zeros, as after
+        train_from_path; stopped before sensing: inf; stopped members keep the row of their last step).  The device work is done once
+        per step (the members keep their rows); the array handed out is the caller's own copy, stacked from the members' rows as they
+        are now -- also of a member that has stepped on its own since."""
+        if any(not a.track_scene_familiarity for a in self.agents):
+            raise ValueError("construct the agents with track_scene_familiarity=True (the default) to read scene_familiarity")
+        self._read_scene()
+        return np.stack([a.scene_familiarity for a in self.agents])
+
     @property
     def active(self):
         return [i for i, s in enumerate(self.stop_status) if s == 0 and self.agents[i].stopped_with_exception is None]
@@ -141,6 +185,7 @@ class NavEnsemble(object):
             out = (px <= b[0]) | (py <= b[0]) | (px >= b[1]) | (py >= b[2])        # the bounds test of :153-158, before anything is sensed
             for k in np.nonzero(out)[0].tolist():
                 self.agents[act[k]].angle_familiarity[:] = np.nan
+                self._scene_inf(self.agents[act[k]])
                 self._stop(act[k], OutOfLandscapeBoundsException())
             keep = np.nonzero(~out)[0]
             idx = [act[k] for k in keep.tolist()]
@@ -154,6 +199,7 @@ class NavEnsemble(object):
                 try:
                     x, y, a = self.agents[i].headings_to_test()
                 except StopNavigationException as e:              # out of the landscape before anything is sensed
+                    self._scene_inf(self.agents[i])
                     self._stop(i, e)
                     continue
                 idx.append(i); xs.append(x); ys.append(y); angs.append(a)
@@ -172,8 +218,11 @@ class NavEnsemble(object):
                     # IndexError, the other trials go on
                     if cands is not None:
                         self.agents[i].angle_familiarity[:] = np.nan      # (headings_to_test's reset, :285)
+                    self._scene_inf(self.agents[i])
                     self._stop(i, IndexError("sensor footprint reaches past the end of the landscape (index out of bounds)"))
                     continue
+                if self.agents[i].track_scene_familiarity:
+                    self._note_scene(self.agents[i], xs[k], ys[k], angs[k], None if self._weights is None else self._weights[i])
                 try:
                     if lean:
                         self.agents[i].apply_step_arrays(results.angle_familiarity[k], best[k], fake,

@@ -491,6 +491,40 @@ int dv_group_step(dv_group *g, const uint8_t *patches, int n_headings, uint32_t 
 int dv_group_sense_step(dv_group *g, double x, double y, const double *angles, int n_headings, uint32_t flags,
                         dv_step_result *result, double *scene_fam);
 
+/* ---- landscape generator: the 2-D heat equation ---------------------------- */
+/*
+ * diffuse of the reference (navsim/util.pyx:189-235): the explicit five-point scheme under periodic boundaries on a square
+ * float64 field, `nstep` full sweeps, every cell
+ *     new = m + multiplier * ((((m[i+1,j] + m[i-1,j]) - 4*m[i,j]) + m[i,j+1]) + m[i,j-1])
+ * with multiplier = c * (delta_t / (delta_s * delta_s)), delta_s = 1 / (n + 1), delta_t = delta_t_factor * (delta_s^2 / (2c)),
+ * each operation rounded on its own (no fused multiply-add), so the field carries the reference's bits after every step.
+ * The field lives in two device buffers of the context, on its device and stream, beside (and independent of) a resident
+ * library, landscape, patches and training path.  The reference's sanity checks (sum, maximum, minimum, NaN) are the
+ * caller's: navsim_amd/generate_landscapes.py runs them in NumPy as the reference does.
+ *   begin     uploads float64[n, n] and fixes the multiplier; DV_ERR_INVALID for n < 1, c == 0 or a NULL field.  A field
+ *             already there is replaced.
+ *   advance   nstep >= 0 more steps, enqueued.  DV_DIFFUSE_PLAIN: one launch per step between the two buffers.
+ *             DV_DIFFUSE_BLOCKED: a workgroup advances a tile plus its halo `steps_per_launch` steps in LDS per launch (the
+ *             rest of nstep in a shorter launch).  DV_DIFFUSE_AUTO: whichever was measured faster.  All give the same bits.
+ *   read      the current field into float64[n, n]; waits for the stream.
+ *   end       frees the buffers.
+ *   configure window side (64 or 96) and steps per launch (1..44, cut to what the window allows) of the blocked form for later
+ *             advances, for A/B; 0 keeps a value.  Defaults: DEJAVU_DIFFUSE_S / DEJAVU_DIFFUSE_T at dv_create, else 64 and 8.
+ *   info      tile side and steps per launch of the blocked form, and the steps advanced since begin (0 without a field);
+ *             any pointer may be NULL.
+ * advance / read without a field: DV_ERR_STATE.  The last declaration is the one-shot call made of the others.
+ */
+#define DV_DIFFUSE_AUTO    0u
+#define DV_DIFFUSE_PLAIN   1u
+#define DV_DIFFUSE_BLOCKED 2u
+int dv_diffuse_begin(dv_ctx *ctx, const double *init, int n, double c, double delta_t_factor);
+int dv_diffuse_advance(dv_ctx *ctx, int64_t nstep, uint32_t flags);
+int dv_diffuse_read(dv_ctx *ctx, double *out);
+int dv_diffuse_end(dv_ctx *ctx);
+int dv_diffuse_configure(dv_ctx *ctx, int window, int steps_per_launch);
+int dv_diffuse_info(dv_ctx *ctx, int *tile, int *steps_per_launch, int *steps_done);
+int dv_diffuse(dv_ctx *ctx, const double *init, int n, int64_t nstep, double c, double delta_t_factor, uint32_t flags, double *out);
+
 /* ---- measurement ------------------------------------------------------- */
 /* hipEvent pair on the context's stream around whatever is enqueued between the two calls. */
 int dv_timer_start(dv_ctx *ctx);

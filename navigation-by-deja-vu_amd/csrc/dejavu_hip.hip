@@ -275,6 +275,15 @@ struct dv_ctx {
     int agent_pending = 0;                    // headings of the agent step begun and not yet ended (dv_agent_step_begin / _end)
     bool err_on_main = false;                 // the last metric computation rode on the step's own stream (dv_agent_step)
 
+    // heat-equation field of the landscape generator (dejavu_diffuse.inl): independent of everything above
+    double* d_diff[2] = {nullptr, nullptr};   // [n][n] each; d_diff[diff_cur] is the current field
+    int diff_n = 0, diff_cur = 0;
+    int64_t diff_done = 0;                    // steps advanced since dv_diffuse_begin
+    double diff_mult = 0.0;
+    int diff_auto_env = 2;                    // DEJAVU_DIFFUSE_AUTO: the form DV_DIFFUSE_AUTO takes (1 plain, 2 blocked: the default, by measurement)
+    int diff_S = 0, diff_T = 0;               // window side (64 or 96) and steps per launch of the blocked form; 0 = default (dv_diffuse_configure, DEJAVU_DIFFUSE_S / _T)
+    bool diff_lds_opted = false;              // the 96 window's 144 KB of LDS were asked for on this context
+
     // measurement
     hipEvent_t t0 = nullptr, t1 = nullptr;
     int profile = 0;                          // dv_profile_kernel: bracket every profile-th scoring launch with events
@@ -302,6 +311,7 @@ static int fail(dv_ctx* c, int code, const char* fmt, ...) {
     } while (0)
 
 static void use_set(dv_ctx* c, int which);
+static void diffuse_free(dv_ctx* c);
 static void free_library(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
     use_set(c, 0);
@@ -385,6 +395,10 @@ extern "C" int dv_create(dv_ctx** out, int device_id) {
     env_int("DEJAVU_LIBREG", c->lreg_env, 0, 1);
     env_int("DEJAVU_NT", c->nt_env, 0, 1);
     env_int("DEJAVU_TEST_FAIL_ALLOC", c->fail_alloc_env, 0, 64);
+    env_int("DEJAVU_DIFFUSE_AUTO", c->diff_auto_env, 1, 2);
+    env_int("DEJAVU_DIFFUSE_S", c->diff_S, 64, 64);
+    env_int("DEJAVU_DIFFUSE_S", c->diff_S, 96, 96);
+    env_int("DEJAVU_DIFFUSE_T", c->diff_T, 1, 44);
     *out = c;
     return DV_OK;
 }
@@ -394,6 +408,7 @@ extern "C" void dv_destroy(dv_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     free_library(c);
+    diffuse_free(c);
     if (c->d_land) (void)hipFree(c->d_land);
     if (c->d_lut) (void)hipFree(c->d_lut);
     if (c->d_poses) (void)hipFree(c->d_poses);
@@ -3473,4 +3488,5 @@ extern "C" int dv_stream_read_gbps(dv_ctx* c, int64_t n_bytes, int iters, double
     return DV_OK;
 }
 
+#include "dejavu_diffuse.inl"   // dv_diffuse_*: the landscape generator's heat equation (kernels and host side)
 #include "dejavu_group.inl"     // dv_group_*: one process, several devices -- host logic above the C ABI

@@ -16,10 +16,13 @@ from ._native import EngineError
 from . import synth
 from .experiment import run_experiment, run_ensemble, chop_path_to_len
 from .ensemble import NavEnsemble
+from . import generate_landscapes
+from .generate_landscapes import diffuse, diffuse_series
 
 __all__ = [
     "NavBySceneFamiliarity", "StopNavigationException", "ReachedEndOfTrainingPathException",
     "NavigatingFailedException", "TooFarFromTrainingPathException", "OutOfLandscapeBoundsException",
     "sads_familiarity", "hip_sads_familiarity", "ssd_familiarity", "FamiliarityEngine", "FamiliarityGroup", "EngineError",
     "fill_sensor_from", "downscale_chem", "synth", "run_experiment", "run_ensemble", "chop_path_to_len", "NavEnsemble",
+    "generate_landscapes", "diffuse", "diffuse_series",
 ]

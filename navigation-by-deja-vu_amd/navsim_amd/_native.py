@@ -20,6 +20,9 @@ DV_RES_RESOLVED = 1
 DV_RES_EXACT_ALL = 2
 DV_RES_OVERFLOW = 4
 DV_RES_SENSE_ERROR = 16
+DV_DIFFUSE_AUTO = 0
+DV_DIFFUSE_PLAIN = 1
+DV_DIFFUSE_BLOCKED = 2
 
 ERROR_NAMES = {-1: "DV_ERR_INVALID", -2: "DV_ERR_HIP", -3: "DV_ERR_STATE", -4: "DV_ERR_OOM", -5: "DV_ERR_INDEX"}
 
@@ -212,6 +215,13 @@ PROTOTYPES = {
     "dv_group_step": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(StepResult), _f64p]),
     "dv_group_sense_step": (ctypes.c_int, [_ctx_p, ctypes.c_double, ctypes.c_double, _f64p, ctypes.c_int, ctypes.c_uint32,
                                            ctypes.POINTER(StepResult), _f64p]),
+    "dv_diffuse_begin": (ctypes.c_int, [_ctx_p, _f64p, ctypes.c_int, ctypes.c_double, ctypes.c_double]),
+    "dv_diffuse_advance": (ctypes.c_int, [_ctx_p, ctypes.c_int64, ctypes.c_uint32]),
+    "dv_diffuse_read": (ctypes.c_int, [_ctx_p, _f64p]),
+    "dv_diffuse_end": (ctypes.c_int, [_ctx_p]),
+    "dv_diffuse_configure": (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int]),
+    "dv_diffuse_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "dv_diffuse": (ctypes.c_int, [_ctx_p, _f64p, ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_uint32, _f64p]),
     "dv_synchronize": (ctypes.c_int, [_ctx_p]),
     "dv_timer_start": (ctypes.c_int, [_ctx_p]),
     "dv_timer_stop": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_float)]),

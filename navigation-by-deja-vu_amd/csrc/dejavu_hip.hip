@@ -787,7 +787,7 @@ static int alloc_library(dv_ctx* c, int64_t F, int h, int w, double cw, int64_t 
     HIP_TRY(c, hipMalloc(&c->d_scene, (size_t)g.Fpad * sizeof(double)));
     // per-agent state of a batched pass: up to kMaxHeadings agents (one heading each)
     HIP_TRY(c, hipMalloc(&c->d_state, kMaxHeadings * sizeof(StepState)));
-    // summaries per agent: one per 256 views (k_finish) or one per workgroup of a fused scoring pass (at most 256: launch_mfma_dual_f)
+    // summaries per agent: one per 256 views (k_finish) or one per workgroup of a fused scoring pass (at most 256: launch_body)
     if (metric == 0) {
         HIP_TRY(c, hipMalloc(&c->d_bsum, (size_t)std::max<long long>((g.F + 255) / 256, 256) * 2 * kMaxHeadings * sizeof(unsigned long long)));
         HIP_TRY(c, hipMalloc(&c->d_bsum2, (size_t)kFoldSlices * 2 * kMaxHeadings * sizeof(unsigned long long)));
@@ -1909,10 +1909,9 @@ extern "C" int dv_generate_library_ex(dv_ctx* c, uint64_t seed, int64_t F, int h
     return DV_OK;
 }
 
-extern "C" int dv_patches_on_level(dv_ctx* c) {
-    if (!c) return DV_ERR_INVALID;
-    if (!c->have_lib || !c->bits_ok || !c->fp4_ok) return fail(c, DV_ERR_STATE, "this library has no fp4 form");
-    if (!c->coef_ready) return fail(c, DV_ERR_STATE, "no coefficient image of the resident patches yet");
+// The form word of the resident patches, read back behind everything queued: 1 = they sit on the library's levels (fp4 form),
+// 0 = not, negative = error.
+static int read_on_level(dv_ctx* c) {
     HIP_TRY(c, hipSetDevice(c->device));
     unsigned word = 0;
     HIP_TRY(c, hipMemcpyAsync(&word, offlevel_word(c), sizeof word, hipMemcpyDeviceToHost, c->stream));
@@ -1920,17 +1919,19 @@ extern "C" int dv_patches_on_level(dv_ctx* c) {
     return word == 0 ? 1 : 0;
 }
 
+extern "C" int dv_patches_on_level(dv_ctx* c) {
+    if (!c) return DV_ERR_INVALID;
+    if (!c->have_lib || !c->bits_ok || !c->fp4_ok) return fail(c, DV_ERR_STATE, "this library has no fp4 form");
+    if (!c->coef_ready) return fail(c, DV_ERR_STATE, "no coefficient image of the resident patches yet");
+    return read_on_level(c);
+}
+
 extern "C" int dv_scoring_form(dv_ctx* c) {
     if (!c) return DV_ERR_INVALID;
-    int form = c->last_form;
-    if (form & DV_FORM_FP4) {                              // the dual kernel ran: which image it took is on the device
-        HIP_TRY(c, hipSetDevice(c->device));
-        unsigned word = 0;
-        HIP_TRY(c, hipMemcpyAsync(&word, offlevel_word(c), sizeof word, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (word != 0) form &= ~DV_FORM_FP4;
-    }
-    return form;
+    if (!(c->last_form & DV_FORM_FP4)) return c->last_form;
+    const int on_level = read_on_level(c);                 // the dual kernel ran: which image it took is on the device
+    if (on_level < 0) return on_level;
+    return on_level ? c->last_form : c->last_form & ~DV_FORM_FP4;
 }
 
 extern "C" int dv_clear_library(dv_ctx* c) {
@@ -2179,6 +2180,66 @@ static FuseArgs fuse_args(const dv_ctx* c) {
     return fz;
 }
 
+// The bodies a matrix-core pass can be launched with.  mfma_plan names one; nothing else chooses.
+//   Ring, Ring2, RingA, RingB: every wave loads and multiplies (sad_ring_fp4 / sad_ring_i8) -- one view group per wave, two, and the
+//     two ring shapes of DEJAVU_RING (A/B);
+//   Lc, LcShort, LcCode, LcReg: loader and consumer waves (sad_lc_fp4) -- stages of 4 K-steps and a ring of 3, stages of 2 and a ring
+//     of 5 (DEJAVU_LC=2), 3-bit code rows (DEJAVU_VCODE=1), the library rows in the consumers' registers (sad_lc_fp4_lreg);
+//   Lc2Tiles, Lc2TilesCode: sad_lc_fp4 with two heading tiles per view group (64 resident headings in one pass);
+//   Lc22: k_sad_lc22, two view groups x two heading tiles per consumer (fused finishing only).
+// Every fp4 body has the int8 ring body <SK8, TILES, RD8> beside it for off-level patches, and the loader / consumer bodies the fp4
+// ring body <SK4, TILES, RD4> for chunked passes.
+enum class Body { Ring, Ring2, RingA, RingB, Lc, LcShort, LcCode, LcReg, Lc2Tiles, Lc2TilesCode, Lc22, Count };
+
+// <int8 stage, ring | fp4 stage, ring (ring body) | view groups per wave | fp4 stage, ring (loader / consumer body; stage 0: none),
+// code rows, heading tiles per view group>: the template arguments of k_sad_mfma_dual (k_sad_lc22: SKL, RDL; it has no fp4 ring
+// body).  Measured in round 2 (other ring shapes: DESIGN.md section 4): int8 500 000 views x 128x128 x 32 headings <1, 3> 1.29 ms,
+// 50 000 views x 64x64 x 16 headings <4, 2> 46.7 us; fp4 <2, 3> 0.95 ms and <2, 4> 34.5 us.
+struct BodyShape { int SK8, RD8, SK4, RD4, TILES, SKL, RDL; bool LCODE; int HT; };
+constexpr BodyShape kBodyShapes[] = {
+    /* Ring         */ {4, 2, 2, 4, 1, 0, 3, false, 1},
+    /* Ring2        */ {1, 3, 2, 3, 2, 0, 3, false, 1},
+    /* RingA        */ {4, 2, 2, 6, 1, 0, 3, false, 1},
+    /* RingB        */ {4, 2, 4, 3, 1, 0, 3, false, 1},
+    /* Lc           */ {4, 2, 2, 4, 1, 4, 3, false, 1},
+    /* LcShort      */ {4, 2, 2, 4, 1, 2, 5, false, 1},
+    /* LcCode       */ {4, 2, 2, 4, 1, 4, 3, true, 1},
+    /* LcReg        */ {4, 2, 2, 4, 1, kLregStage, 3, false, 1},
+    /* Lc2Tiles     */ {4, 2, 2, 4, 1, 4, 3, false, 2},
+    /* Lc2TilesCode */ {4, 2, 2, 4, 1, 4, 3, true, 2},
+    /* Lc22         */ {4, 2, 0, 0, 1, 2, 3, false, 2},
+};
+static_assert(sizeof kBodyShapes / sizeof kBodyShapes[0] == (size_t)Body::Count, "one shape per body");
+constexpr BodyShape body_shape(Body b) { return kBodyShapes[(int)b]; }
+
+// The kernel of a body.  (k_sad_lc22 has the fused form only.)
+template <Body B, bool FUSE>
+constexpr auto body_kernel() {
+    constexpr BodyShape s = body_shape(B);
+    if constexpr (B == Body::Lc22) return &k_sad_lc22<s.SKL, s.RDL>;
+    else return &k_sad_mfma_dual<s.SK8, s.RD8, s.SK4, s.RD4, s.TILES, FUSE, s.SKL, s.RDL, s.LCODE, s.HT>;
+}
+
+// View groups of 32 per work item of a body: 8 waves x TILES groups, shared among the heading tiles (Lc22: two groups for each of its
+// four consumers).
+constexpr int body_view_groups(Body b) { return b == Body::Lc22 ? 8 : 8 * body_shape(b).TILES / body_shape(b).HT; }
+
+// Dynamic LDS of a body's kernel: the largest of its bodies' rings -- [RD][coefficient rows SK * 8 | library rows 8 waves x SK x TILES]
+// of 1 KB for the int8 one (sad_ring_i8) -- then the fused finishing's scratch (a second heading tile adds its 64 running-summary
+// words).
+template <Body B, bool FUSE>
+constexpr int body_lds_bytes() {
+    constexpr BodyShape s = body_shape(B);
+    int ring = s.RD8 * (s.SK8 * 8 + 8 * s.SK8 * s.TILES) * 1024;
+    if (fp4_ring_bytes(s.SK4, s.TILES, s.RD4) > ring) ring = fp4_ring_bytes(s.SK4, s.TILES, s.RD4);
+    int lc = 0;
+    if constexpr (B == Body::Lc22) lc = lc22_ring_bytes<s.SKL, s.RDL>() + kLc22ParkBytes;
+    else if constexpr (s.SKL == kLregStage) lc = lreg_ring_bytes<s.SKL, s.RDL>();
+    else if constexpr (s.SKL > 0) lc = lc_ring_bytes<s.SKL, s.RDL>();
+    if (lc > ring) ring = lc;
+    return ring + (FUSE ? kFuseScratchBytes + (s.HT - 1) * 512 : 0);
+}
+
 // View-group ranges (items per chunk) the library is cut into for a workgroup of 8 waves x TILES groups: as few as hold it,
 // ceil(G32 / VW), of equal size to within one group -- 500 000 views x 128x128: 7.63 ranges of 8 per workgroup, so 94 of the 256
 // workgroups sit out the eighth round.  Two finer cuts were measured and are SLOWER, because a range takes its consumers' time per
@@ -2191,175 +2252,148 @@ static long long item_groups(long long G32, int VW) {
     return (G32 + VW - 1) / VW;
 }
 
-// Both forms in one launch (k_sad_mfma_dual): the fp4 form when this prep's patches sit on the library's levels (the
-// device decides, offlevel_word); libraries without an fp4 form point that word at a constant 1 and pass no fp4 image.
-template <int SK8, int RD8, int SK4, int RD4, int TILES, bool FUSE, int SKL, int RDL, bool LCODE, int HT>
-static void launch_mfma_dual_f(dv_ctx* c, int nchunk, int has_hs) {
-    static bool attr_set = false;
-    const size_t lds8 = (size_t)RD8 * (SK8 * 8 + 8 * SK8 * TILES) * 1024;
-    const size_t lds4 = (size_t)fp4_ring_bytes(SK4, TILES, RD4);
-    size_t lds = lds8 > lds4 ? lds8 : lds4;
-    if constexpr (SKL > 0) {
-        constexpr int lcb = SKL == kLregStage ? lreg_ring_bytes<SKL, RDL>() : lc_ring_bytes<SKL, RDL>();
-        static_assert(lcb + kFuseScratchBytes + (HT - 1) * 512 <= 160 * 1024, "LDS");
-        if ((size_t)lcb > lds) lds = (size_t)lcb;
-    }
-    lds += FUSE ? (size_t)kFuseScratchBytes + (HT - 1) * 512 : 0;     // (a second heading tile adds its 64 running-summary words)
-    static_assert(fp4_ring_bytes(SK4, TILES, RD4) + kFuseScratchBytes <= 160 * 1024, "LDS");
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)k_sad_mfma_dual<SK8, RD8, SK4, RD4, TILES, FUSE, SKL, RDL, LCODE, HT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    const long long G32 = c->cfg.Fpad / 32;
-    const long long n_gq = item_groups(G32, 8 * TILES / HT);
+// One body's launch.  Both forms in one launch: the fp4 form when this prep's patches sit on the library's levels (the device
+// decides, offlevel_word); libraries without an fp4 form point that word at a constant 1 and pass no fp4 image.  FUSE: the kernel
+// finishes its scores itself (one chunk, and a step that may end in k_fold).
+template <Body B, bool FUSE>
+static void launch_body(dv_ctx* c, int nchunk, int has_hs) {
+    constexpr BodyShape s = body_shape(B);
+    constexpr int lds = body_lds_bytes<B, FUSE>();
+    static_assert(body_lds_bytes<B, true>() <= 160 * 1024, "LDS");
+    constexpr auto kernel = body_kernel<B, FUSE>();
+    static const hipError_t attr_set = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)attr_set;
+    const long long n_gq = item_groups(c->cfg.Fpad / 32, body_view_groups(B));
     const long long items = n_gq * nchunk;
     const unsigned grid = (unsigned)(items < 256 ? items : 256);          // one 8-wave workgroup per CU, grid-stride
     const int nkt = c->bcfg.NK[0] + c->bcfg.NK[1];
     FuseArgs fz{};
     if (FUSE) { fz = fuse_args(c); fz.nb = (int)grid; }
-    for (int a_off = 0; a_off < c->APAD; a_off += 32 * HT)
-        hipLaunchKernelGGL((k_sad_mfma_dual<SK8, RD8, SK4, RD4, TILES, FUSE, SKL, RDL, LCODE, HT>), dim3(grid), dim3(512), lds, c->stream, c->d_btiles,
-                           c->bcfg.vcode ? c->d_ctiles : c->d_btiles, c->d_coef + (size_t)(a_off / 32) * nkt * 512,
-                           c->fp4_ok ? c->d_coef4 + (size_t)(a_off / 32) * nkt * 256 : nullptr, offlevel_word(c), reinterpret_cast<int*>(c->d_part),
-                           c->cfg, c->bcfg, nchunk, c->APAD, a_off, has_hs, fz, (int)n_gq);
+    for (int a_off = 0; a_off < c->APAD; a_off += 32 * s.HT) {
+        const uint4* coef = c->d_coef + (size_t)(a_off / 32) * nkt * 512;
+        const uint4* coef4 = c->fp4_ok ? c->d_coef4 + (size_t)(a_off / 32) * nkt * 256 : nullptr;
+        if constexpr (B == Body::Lc22) {
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), lds, c->stream, c->d_btiles, coef, coef4, offlevel_word(c), c->cfg, c->bcfg,
+                               c->APAD, a_off, has_hs, fz, (int)n_gq);
+        } else {
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), lds, c->stream, c->d_btiles, c->bcfg.vcode ? c->d_ctiles : c->d_btiles, coef,
+                               coef4, offlevel_word(c), reinterpret_cast<int*>(c->d_part), c->cfg, c->bcfg, nchunk, c->APAD, a_off, has_hs,
+                               fz, (int)n_gq);
+        }
+    }
     if (FUSE) { c->epilogue_fused = true; c->fused_nb = (int)grid; }     // one summary per workgroup
 }
 
-template <int SK8, int RD8, int SK4, int RD4, int TILES, int SKL = 0, int RDL = 3, bool LCODE = false, int HT = 1>
-static void launch_mfma_dual(dv_ctx* c, int nchunk, int has_hs) {
-    // One chunk and a step that may end in k_fold: the kernel finishes its scores itself.
-    if (c->fuse_request && nchunk == 1 && c->fuse_env) launch_mfma_dual_f<SK8, RD8, SK4, RD4, TILES, true, SKL, RDL, LCODE, HT>(c, nchunk, has_hs);
-    else launch_mfma_dual_f<SK8, RD8, SK4, RD4, TILES, false, SKL, RDL, LCODE, HT>(c, nchunk, has_hs);
+// Bit positions 1, 2, 3 that stand for something have one width per segment, so that they can share an accumulator (sad_lc22_fp4,
+// sad_lc_fp4_lreg), in a library those bodies can take at all.  `with_bit0`: position 0 of the saturation segment has that width too.
+static bool shared_accumulator_fits(const dv_ctx* c, bool with_bit0) {
+    if (!c->fp4_ok || c->bcfg.vcode || c->mixed) return false;
+    for (int seg = 0; seg < 2; ++seg) {
+        int w = 0;
+        for (int bit = 1; bit < 4; ++bit) {
+            const int wb = c->bcfg.wacc[seg][bit];
+            if (wb && w && wb != w) return false;
+            if (wb) w = wb;
+        }
+        if (with_bit0 && seg == 0 && c->bcfg.wacc[0][0] && w && c->bcfg.wacc[0][0] != w) return false;
+    }
+    return true;
+}
+// k_sad_lc22 fits this library: the saturation segment has one width altogether and its counts fit the int16 they wait in.
+static bool lc22_fits(const dv_ctx* c) {
+    return shared_accumulator_fits(c, true) && (long long)c->bcfg.NK[0] * 256 <= 32767;
+}
+// sad_lc_fp4_lreg fits this library: the saturation K-steps are whole stages of eight.
+static bool lreg_fits(const dv_ctx* c) {
+    return shared_accumulator_fits(c, false) && c->bcfg.NK[0] % kLregStage == 0;
 }
 
-// Work items of k_sad_mfma_dual = (chunk of K-steps, range of at most 8*TILES view groups of 32).  Two view groups per wave
-// halve the coefficient traffic (every A operand serves both) once the library is large enough to keep every CU busy that
-// way; very small libraries also cut the K-steps into chunks so that there are about as many items as CUs.
-struct MfmaPlan { bool use_lc, two_tiles, lc22; int tiles, nchunk; };
-// k_sad_lc22 (two view groups x two heading tiles per consumer, bit positions of one width sharing an accumulator) fits this library:
-// per segment the positions 1, 2, 3 that stand for something have one width, the saturation segment has one width altogether and
-// its counts fit the int16 they wait in (sad_lc22_fp4).
-static bool lc22_fits(const dv_ctx* c) {
-    if (!c->lc22_env || !c->fp4_ok || c->bcfg.vcode || c->mixed) return false;
-    for (int seg = 0; seg < 2; ++seg) {
-        int w = 0;
-        for (int bit = 1; bit < 4; ++bit) {
-            const int wb = c->bcfg.wacc[seg][bit];
-            if (wb && w && wb != w) return false;
-            if (wb) w = wb;
-        }
-        if (seg == 0 && c->bcfg.wacc[0][0] && w && c->bcfg.wacc[0][0] != w) return false;
-    }
-    return (long long)c->bcfg.NK[0] * 256 <= 32767;
-}
-// sad_lc_fp4_lreg (library rows in the consumers' registers, bit positions 1, 2, 3 sharing an accumulator) fits this library: per
-// segment the positions 1, 2, 3 that stand for something have one width, and the saturation K-steps are whole stages of eight.
-static bool lreg_fits(const dv_ctx* c) {
-    if (!c->lreg_env || !c->fp4_ok || c->bcfg.vcode || c->mixed) return false;
-    for (int seg = 0; seg < 2; ++seg) {
-        int w = 0;
-        for (int bit = 1; bit < 4; ++bit) {
-            const int wb = c->bcfg.wacc[seg][bit];
-            if (wb && w && wb != w) return false;
-            if (wb) w = wb;
-        }
-    }
-    return c->bcfg.NK[0] % kLregStage == 0;
-}
-// How a matrix-core pass over the resident library is cut for `apad` resident headings (what launch_mfma launches; run_batch asks
-// beforehand whether its passes will finish their scores themselves: one chunk).
+// A matrix-core pass over the resident library for `apad` resident headings: the body, the chunks its K-steps are cut into, and
+// whether the kernel finishes its scores itself.  Work items = (chunk of K-steps, range of at most body_view_groups view groups of
+// 32).  launch_mfma launches exactly this; run_batch asks it beforehand whether its passes will fuse (batch_pass_fuses).
+struct MfmaPlan { Body body; int nchunk; bool fuses; };
 static MfmaPlan mfma_plan(dv_ctx* c, int apad, bool fuse_request) {
-    MfmaPlan p{};
     const long long G32 = c->cfg.Fpad / 32;
-    // two view groups per wave once there are about 1.25 such items per CU (200 000 views x 128x128 x 32 headings, 391 items:
-    // 0.432 ms with two, 0.474 ms with one; 500 000 views: two)
+    const bool may_fuse = fuse_request && c->fuse_env && !c->mfma_chunk_env;         // (and one chunk: decided below)
     // DEJAVU_LC (A/B): 0 = every wave loads and multiplies (sad_ring_fp4); 1 = loader and consumer waves, stage of 4 K-steps, ring of 3
     // (sad_lc_fp4; ranges of 8 view groups whatever the library's size); 2 = the same with stages of 2 K-steps, ring of 5
-    p.use_lc = c->lc_env != 0 && c->fp4_ok && !c->mfma_tiles_env;
-    p.tiles = c->mfma_tiles_env ? c->mfma_tiles_env : (p.use_lc ? 1 : (G32 >= 16ll * 320 ? 2 : 1));
-    // (never by default a variant the compiler could only build with scratch: its fused form keeps a few item-level pointers
-    // there in this build -- tests/test_host_logic.py:test_shipped_scoring_kernels_use_no_scratch lists what is guarded)
-    if (p.tiles == 2 && !c->mfma_tiles_env) {
-        static const bool spills[2] = {kernel_uses_scratch((const void*)k_sad_mfma_dual<1, 3, 2, 3, 2, false, 0, 3, false, 1>),
-                                       kernel_uses_scratch((const void*)k_sad_mfma_dual<1, 3, 2, 3, 2, true, 0, 3, false, 1>)};
-        const bool will_fuse = fuse_request && c->fuse_env && !c->mfma_chunk_env && item_groups(G32, 16) >= 160;
-        if (spills[will_fuse ? 1 : 0]) p.tiles = 1;
+    const bool use_lc = c->lc_env != 0 && c->fp4_ok && !c->mfma_tiles_env;
+    Body body;
+    if (use_lc) {
+        // DEJAVU_HT=1 (A/B): 64 resident headings as two passes over the library instead of two heading tiles per view group in one
+        const bool two_tiles = apad == 64 && c->ht_env == 2;
+        if (two_tiles && may_fuse && c->lc22_env && lc22_fits(c) && item_groups(G32, 8) >= 160) body = Body::Lc22;
+        else if (two_tiles) body = c->bcfg.vcode ? Body::Lc2TilesCode : Body::Lc2Tiles;
+        else if (c->bcfg.vcode) body = Body::LcCode;
+        else body = c->lc_env == 2 ? Body::LcShort : Body::Lc;                      // (Lc: LcReg instead where it fits, below)
+    } else {
+        // Two view groups per wave halve the coefficient traffic (every A operand serves both) once there are about 1.25 such items
+        // per CU (200 000 views x 128x128 x 32 headings, 391 items: 0.432 ms with two, 0.474 ms with one; 500 000 views: two)
+        const int tiles = c->mfma_tiles_env ? c->mfma_tiles_env : (G32 >= 16ll * 320 ? 2 : 1);
+        body = tiles == 2 ? Body::Ring2 : (c->ring_env == 1 ? Body::RingA : (c->ring_env == 2 ? Body::RingB : Body::Ring));
+        // (never by default a variant the compiler could only build with scratch: its fused form keeps a few item-level pointers
+        // there in this build -- tests/test_host_logic.py:test_shipped_scoring_kernels_use_no_scratch lists what is guarded)
+        if (body == Body::Ring2 && !c->mfma_tiles_env) {
+            static const bool spills[2] = {kernel_uses_scratch((const void*)body_kernel<Body::Ring2, false>()),
+                                           kernel_uses_scratch((const void*)body_kernel<Body::Ring2, true>())};
+            const bool will_fuse = may_fuse && item_groups(G32, body_view_groups(Body::Ring2)) >= 160;
+            if (spills[will_fuse ? 1 : 0]) body = c->ring_env == 1 ? Body::RingA : (c->ring_env == 2 ? Body::RingB : Body::Ring);
+        }
     }
-    // DEJAVU_HT=1 (A/B): 64 resident headings as two passes over the library instead of two heading tiles per view group in one
-    p.two_tiles = p.use_lc && apad == 64 && c->ht_env == 2;
-    p.lc22 = p.two_tiles && fuse_request && c->fuse_env && !c->mfma_chunk_env && lc22_fits(c) && item_groups(G32, 8) >= 160;
-    const long long GQ = item_groups(G32, p.lc22 ? 8 : (p.two_tiles ? 4 : 8 * p.tiles));
+    const long long GQ = item_groups(G32, body_view_groups(body));
     int nchunk = 1;
     if (c->mfma_chunk_env) {
         nchunk = c->mfma_chunk_env;
     } else if (GQ < 160) {
-        // Fewer view groups than ~60 % of the CUs: cut the K-steps too.  (More chunks mean partial sums through HBM, k_finish
-        // behind the kernel and more pipeline fills: only where CUs would otherwise have nothing at all.)
+        // Fewer view groups than ~60 % of the CUs: very small libraries also cut the K-steps, so that there are about as many items
+        // as CUs.  (More chunks mean partial sums through HBM, k_finish behind the kernel and more pipeline fills: only where CUs
+        // would otherwise have nothing at all.)
         nchunk = (int)((256 + GQ - 1) / GQ);
     }
     const int nk_min = c->bcfg.NK[1] > 0 ? (c->bcfg.NK[0] > 0 && c->bcfg.NK[0] < c->bcfg.NK[1] ? c->bcfg.NK[0] : c->bcfg.NK[1]) : c->bcfg.NK[0];
     while (nchunk > 1 && nk_min / nchunk < 4) --nchunk;                  // keep a few K-steps per chunk
     if (nchunk > c->nchunk_cap) nchunk = c->nchunk_cap;
     if (nchunk < 1 || c->mixed) nchunk = 1;                              // (mixed layout: the byte pass shares the one-chunk rows of the partial sums)
-    p.nchunk = nchunk;
-    if (nchunk != 1) p.lc22 = false;
-    return p;
-}
-
-template <int SKL, int RDL>
-static void launch_lc22(dv_ctx* c, int has_hs) {
-    static bool attr_set = false;
-    size_t lds = (size_t)lc22_ring_bytes<SKL, RDL>() + kLc22ParkBytes;
-    const size_t lds8 = (size_t)2 * (4 * 8 + 8 * 4) * 1024;             // the int8 ring body's (off-level patches): <4, 1, 2>
-    if (lds8 > lds) lds = lds8;
-    lds += (size_t)kFuseScratchBytes + 512;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)k_sad_lc22<SKL, RDL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    const long long G32 = c->cfg.Fpad / 32;
-    const long long n_gq = item_groups(G32, 8);
-    const unsigned grid = (unsigned)(n_gq < 256 ? n_gq : 256);          // one 8-wave workgroup per CU, grid-stride
-    const int nkt = c->bcfg.NK[0] + c->bcfg.NK[1];
-    FuseArgs fz = fuse_args(c);
-    fz.nb = (int)grid;
-    for (int a_off = 0; a_off < c->APAD; a_off += 64)
-        hipLaunchKernelGGL((k_sad_lc22<SKL, RDL>), dim3(grid), dim3(512), lds, c->stream, c->d_btiles, c->d_coef + (size_t)(a_off / 32) * nkt * 512,
-                           c->d_coef4 + (size_t)(a_off / 32) * nkt * 256, offlevel_word(c), c->cfg, c->bcfg, c->APAD, a_off, has_hs, fz, (int)n_gq);
-    c->epilogue_fused = true;
-    c->fused_nb = (int)grid;
+    // (Lc22 was chosen with may_fuse and >= 160 ranges, lc22_fits excludes the mixed layout: one chunk, fused)
+    if (body == Body::Lc && nchunk == 1 && c->lreg_env && lreg_fits(c)) body = Body::LcReg;
+    return {body, nchunk, fuse_request && c->fuse_env && nchunk == 1};
 }
 
 // An ensemble pass of `apad` resident headings would finish its scores inside the scoring kernel (fused epilogue: nothing shared is
 // written, so passes may run beside each other).  The shape must be known already (timed or forced): an untimed class says no.
 static bool batch_pass_fuses(dv_ctx* c, int apad) {
-    if (c->metric != 0 || c->exact || c->cfg.generic || !c->bits_ok || c->mixed || !c->fuse_env) return false;
+    if (c->metric != 0 || c->exact || c->cfg.generic || !c->bits_ok || c->mixed) return false;
     const int cls = apad_class(apad);
     const int shape = c->shape_env ? c->shape_env : c->tuned_shape[cls];
     if (shape != 6) return false;
-    return mfma_plan(c, apad, true).nchunk == 1;
+    return mfma_plan(c, apad, true).fuses;
+}
+
+template <Body B>
+static void launch_planned(dv_ctx* c, const MfmaPlan& p, int has_hs) {
+    if constexpr (B != Body::Lc22) {
+        if (!p.fuses) return launch_body<B, false>(c, p.nchunk, has_hs);
+    }
+    launch_body<B, true>(c, p.nchunk, has_hs);
 }
 
 static void launch_mfma(dv_ctx* c, int has_hs) {
-    const MfmaPlan plan = mfma_plan(c, c->APAD, c->fuse_request);
-    const bool use_lc = plan.use_lc, two_tiles = plan.two_tiles;
-    const int tiles = plan.tiles, nchunk = plan.nchunk, lc = c->lc_env;
-    c->nchunk = nchunk;
-    // <int8 stage, ring | fp4 stage, ring (thermometer rows) | fp4 stage, ring (code rows), view groups per wave>.  Measured in
-    // round 2 (other ring shapes: DESIGN.md section 4): int8 500 000 views x 128x128 x 32 headings <1, 3> 1.29 ms, 50 000 views
-    // x 64x64 x 16 headings <4, 2> 46.7 us; fp4 <2, 3> 0.95 ms and <2, 4> 34.5 us.
-    const int ring = c->ring_env;                                                                   // A/B of ring shapes
-    if (plan.lc22) launch_lc22<2, 3>(c, has_hs);
-    else if (two_tiles && c->bcfg.vcode) launch_mfma_dual<4, 2, 2, 4, 1, 4, 3, true, 2>(c, nchunk, has_hs);
-    else if (two_tiles) launch_mfma_dual<4, 2, 2, 4, 1, 4, 3, false, 2>(c, nchunk, has_hs);
-    else if (use_lc && c->bcfg.vcode) launch_mfma_dual<4, 2, 2, 4, 1, 4, 3, true>(c, nchunk, has_hs);
-    else if (use_lc && lc == 1 && nchunk == 1 && lreg_fits(c)) launch_mfma_dual<4, 2, 2, 4, 1, kLregStage, 3>(c, nchunk, has_hs);
-    else if (use_lc && lc == 2) launch_mfma_dual<4, 2, 2, 4, 1, 2, 5>(c, nchunk, has_hs);
-    else if (use_lc) launch_mfma_dual<4, 2, 2, 4, 1, 4, 3>(c, nchunk, has_hs);
-    else if (tiles == 2) launch_mfma_dual<1, 3, 2, 3, 2>(c, nchunk, has_hs);
-    else if (ring == 1) launch_mfma_dual<4, 2, 2, 6, 1>(c, nchunk, has_hs);
-    else if (ring == 2) launch_mfma_dual<4, 2, 4, 3, 1>(c, nchunk, has_hs);
-    else launch_mfma_dual<4, 2, 2, 4, 1>(c, nchunk, has_hs);
+    const MfmaPlan p = mfma_plan(c, c->APAD, c->fuse_request);
+    c->nchunk = p.nchunk;
+    switch (p.body) {
+        case Body::Ring: return launch_planned<Body::Ring>(c, p, has_hs);
+        case Body::Ring2: return launch_planned<Body::Ring2>(c, p, has_hs);
+        case Body::RingA: return launch_planned<Body::RingA>(c, p, has_hs);
+        case Body::RingB: return launch_planned<Body::RingB>(c, p, has_hs);
+        case Body::Lc: return launch_planned<Body::Lc>(c, p, has_hs);
+        case Body::LcShort: return launch_planned<Body::LcShort>(c, p, has_hs);
+        case Body::LcCode: return launch_planned<Body::LcCode>(c, p, has_hs);
+        case Body::LcReg: return launch_planned<Body::LcReg>(c, p, has_hs);
+        case Body::Lc2Tiles: return launch_planned<Body::Lc2Tiles>(c, p, has_hs);
+        case Body::Lc2TilesCode: return launch_planned<Body::Lc2TilesCode>(c, p, has_hs);
+        case Body::Lc22: return launch_planned<Body::Lc22>(c, p, has_hs);
+        case Body::Count: break;
+    }
 }
 
 // The integer path of one scoring pass: k_sad_tiles / k_sad_generic, then k_combine.  `after_tiles` (optional) is

@@ -65,25 +65,23 @@ _MODE_ENV = {
 _MODE_KEYS = ("DEJAVU_FINISH", "DEJAVU_SHAPE", "DEJAVU_BITS", "DEJAVU_FENCED", "DEJAVU_FUSE", "DEJAVU_FP4")
 
 
-class engine_mode(object):
-    """Context manager: the environment of one engine mode while an engine is created."""
+def engine_with(env, device=0, **kwargs):
+    """An engine created under `env` (the context reads its knobs when it is created; a value of None: that variable unset); the
+    environment is put back."""
+    import os
 
-    def __init__(self, mode):
-        self.env = _MODE_ENV[mode]
-
-    def __enter__(self):
-        import os
-        self.before = {k: os.environ.get(k) for k in _MODE_KEYS}
-        for k in _MODE_KEYS:
+    import navsim_amd
+    before = {k: os.environ.pop(k, None) for k in env}
+    os.environ.update({k: v for k, v in env.items() if v is not None})
+    try:
+        return navsim_amd.FamiliarityEngine(device, **kwargs)
+    finally:
+        for k, v in before.items():
             os.environ.pop(k, None)
-        os.environ.update(self.env)
-        return self
-
-    def __exit__(self, *exc):
-        import os
-        for k, v in self.before.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
+            if v is not None:
                 os.environ[k] = v
-        return False
+
+
+def engine_mode(mode, device=0):
+    """An engine created under one engine mode: its variables set, every other mode variable unset."""
+    return engine_with({**dict.fromkeys(_MODE_KEYS), **_MODE_ENV[mode]}, device)

@@ -27,8 +27,7 @@ def rec(r, i):
 def eng(request):
     """Every test runs under each form of the scoring path (tests/helpers.py:ENGINE_MODES): both step endings, the
     bit-plane matrix-core kernel, and the product default."""
-    with engine_mode(request.param):
-        e = navsim_amd.FamiliarityEngine(device=0)
+    e = engine_mode(request.param)
     e.mode = request.param
     yield e
     e.close()
@@ -137,8 +136,7 @@ def test_weighted_rows_equal_a_library_of_that_weight(eng, F):
     patches[3, 7] = lib[F // 3]
     patches[6, ..., 2] = synth.random_hsv(seed + 9, patches[6].shape[:-1])
     weights = [(0.0, 0.25, 0.5, 1.0)[i % 4] for i in range(n)]
-    with engine_mode(eng.mode):
-        single = navsim_amd.FamiliarityEngine(device=0)
+    single = engine_mode(eng.mode)
     try:
         eng.set_weight_range(0.0, 1.0)
         eng.set_library(lib, 0.25)

@@ -3,7 +3,6 @@ NavEnsemble.from_agent(chem_weights=...).
 
 The reference runs chem_weight as a variable of its experiment grid (scripts/run_experiment.py:61,218); a trial's training views
 do not depend on it, so one library laid out for a range of weights serves every member of an ensemble under its own weight."""
-import os
 
 import numpy as np
 import pytest
@@ -11,28 +10,13 @@ import pytest
 import navsim_amd
 from navsim_amd import synth
 from oracle import oracle
-from tests.helpers import sha
+from tests.helpers import engine_with, sha
 from tests.test_host_logic import _run_trajectory
 
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-9
 WEIGHTS = (0.0, 0.25, 0.3, 0.5, 1.0)
-
-
-def _engine(env=None):
-    """An engine created under `env` (the context reads its knobs when it is created); the environment is put back."""
-    env = env or {}
-    before = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return navsim_amd.FamiliarityEngine(0)
-    finally:
-        for k, v in before.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 # ------------------------------------------------------------------ 1. the reference's trajectories of two weights from ONE ensemble
@@ -108,7 +92,7 @@ def _check_weighted(lib, cases, weights, modes, lib_cw=0.25, info_check=None):
     want = {name: [oracle.step(lib, p[ag], weights[ag], want_scene=False) for ag in range(len(p))] for name, p in cases}
     for mode in modes:
         env, exact, force = MODES[mode]
-        eng = _engine(env)
+        eng = engine_with(env)
         try:
             eng.set_weight_range(0.0, 1.0)
             eng.set_library(lib, lib_cw)
@@ -179,7 +163,7 @@ def test_weighted_records_equal_uniform_records_at_each_weight():
     def rec(r, ag):
         return tuple(np.asarray(r.records[ag][k]).tobytes() for k in keys)
 
-    eng = _engine()
+    eng = engine_with({})
     try:
         eng.set_weight_range(0.0, 1.0)
         eng.set_library(lib, 0.25)
@@ -206,7 +190,7 @@ def test_weighted_calls_refuse_what_the_layout_cannot_serve():
     lib = synth.synth_views(3, F, h, w)
     patches = synth.synth_patches(4, n_agents * A, h, w).reshape(n_agents, A, h, w, 3)
     patches[1, 2] = lib[321]
-    eng = _engine()
+    eng = engine_with({})
     try:
         eng.set_library(lib, 0.0)                                    # cw 0 alone: no saturation planes
         assert eng.library_info()["weight_range"] == (0.0, 0.0)

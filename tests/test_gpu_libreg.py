@@ -5,7 +5,6 @@ Ragged view counts (a partial last item of 8 view groups and a partial last view
 after one and after four stages, and a library whose value widths differ on bit positions 1..3 (the host then keeps the
 LDS body) are covered; the oracle checks the winners.
 """
-import os
 
 import numpy as np
 import pytest
@@ -13,21 +12,9 @@ import pytest
 import navsim_amd
 from navsim_amd import synth
 from oracle import oracle
+from tests.helpers import engine_with
 
 pytestmark = pytest.mark.gpu
-
-
-def _engine(env):
-    before = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return navsim_amd.FamiliarityEngine(0)
-    finally:
-        for k, v in before.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _uneven_v(views):
@@ -56,8 +43,8 @@ def test_register_body_gives_the_lds_bodys_sums(F, h, w, force_chunk, uneven):
     base = {"DEJAVU_SHAPE": "6", "DEJAVU_BITS": "2"}
     if force_chunk:
         base["DEJAVU_MFMA_CHUNK"] = "1"
-    e_new = _engine(base)
-    e_old = _engine(dict(base, DEJAVU_LIBREG="0"))
+    e_new = engine_with(base)
+    e_old = engine_with(dict(base, DEJAVU_LIBREG="0"))
     try:
         for e in (e_new, e_old):
             e.set_library(lib, cw)

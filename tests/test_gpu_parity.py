@@ -10,7 +10,7 @@ import pytest
 import navsim_amd
 from navsim_amd import synth
 from oracle import oracle
-from tests.helpers import ENGINE_MODES, engine_mode, kernel_case_inputs, step_case_inputs
+from tests.helpers import ENGINE_MODES, engine_mode, engine_with, kernel_case_inputs, step_case_inputs
 from tests.test_host_logic import check_trajectory
 
 pytestmark = pytest.mark.gpu
@@ -22,8 +22,7 @@ RTOL = 1e-9
 def eng(request):
     """Every test runs under each form of the scoring path (tests/helpers.py:ENGINE_MODES): both step endings, the
     bit-plane matrix-core kernel, and the product default."""
-    with engine_mode(request.param):
-        e = navsim_amd.FamiliarityEngine(device=0)
+    e = engine_mode(request.param)
     e.mode = request.param
     yield e
     e.close()
@@ -706,32 +705,27 @@ def test_every_workgroup_shape_gives_identical_results(A):
     """The scoring kernel's forms (1 single-wave, 2 four waves + LDS sums, 3/4 heading ways, 5 packed accumulators;
     csrc/dejavu_hip.hip:launch_tiles_apad; 6 the bit-plane matrix-core kernel k_sad_mfma_dual) are normally chosen by timing; forced one by one they must produce the same
     integer sums, hence bit-identical scores and the reference's decision."""
-    import os
     F, h, w, cw = 1500, 20, 24, 0.25
     lib = synth.synth_views(91, F, h, w)
     pats = synth.synth_patches(91, A, h, w)
     pats[A // 2] = synth.near_match_patch(lib[777], 5)
     want = oracle.step(lib, pats, cw)
     fams = {}
-    try:
-        for shape in (1, 2, 3, 4, 5, 6, 0):
-            os.environ["DEJAVU_SHAPE"] = str(shape)
-            e = navsim_amd.FamiliarityEngine(0)
-            try:
-                e.set_library(lib, cw)
-                info = e.library_info()
-                assert info["n_planes"] == 2 and info["signed_saturation"] == 1      # both sums live: shape 5 is valid
-                assert info["has_bit_planes"] and (info["bit_planes_hs"], info["bit_planes_v"]) == (2, 4)   # shape 6 is
-                r = e.step(pats, want_scene=False)
-                assert (r["best_idex"], r["best_view"]) == (want["best_idex"], want["best_view"]), shape
-                fams[shape] = np.array(r["angle_familiarity"])
-                buf = np.empty(F)
-                e.score(pats[0], buf)
-                fams[(shape, "score")] = buf
-            finally:
-                e.close()
-    finally:
-        os.environ.pop("DEJAVU_SHAPE", None)
+    for shape in (1, 2, 3, 4, 5, 6, 0):
+        e = engine_with({"DEJAVU_SHAPE": str(shape)})
+        try:
+            e.set_library(lib, cw)
+            info = e.library_info()
+            assert info["n_planes"] == 2 and info["signed_saturation"] == 1      # both sums live: shape 5 is valid
+            assert info["has_bit_planes"] and (info["bit_planes_hs"], info["bit_planes_v"]) == (2, 4)   # shape 6 is
+            r = e.step(pats, want_scene=False)
+            assert (r["best_idex"], r["best_view"]) == (want["best_idex"], want["best_view"]), shape
+            fams[shape] = np.array(r["angle_familiarity"])
+            buf = np.empty(F)
+            e.score(pats[0], buf)
+            fams[(shape, "score")] = buf
+        finally:
+            e.close()
     for shape in (2, 3, 4, 5, 6, 0):
         np.testing.assert_array_equal(fams[shape], fams[1])
         np.testing.assert_array_equal(fams[(shape, "score")], fams[(1, "score")])
@@ -1011,7 +1005,6 @@ def test_ssd_f32_full_size_properties():
     """ssd_f32 on BASELINE configs[1]'s shape (64x64, 50 000 views; 16 and 32 headings = one and two passes): planted
     near-copies win at their headings, the planted pairs' SSDs equal the reference's `ssds` on the upcast data to 1e-6,
     scaling every input by 2 scales every SSD by exactly 4, and both workgroup shapes agree on the decision."""
-    import os
     F, h, w = 50000, 64, 64
     rng = np.random.default_rng(2)
     lib = rng.random((F, h, w), dtype=np.float32)
@@ -1021,11 +1014,7 @@ def test_ssd_f32_full_size_properties():
         patches[2] = lib[49999] + rng.normal(0, 0.02, (h, w)).astype(np.float32)
         seen = {}
         for shape in ("0", "2"):                    # default (single wave, prefetch) and four waves + LDS fold
-            os.environ["DEJAVU_SHAPE"] = shape
-            try:
-                eng = navsim_amd.FamiliarityEngine(0)
-            finally:
-                os.environ.pop("DEJAVU_SHAPE", None)
+            eng = engine_with({"DEJAVU_SHAPE": shape})
             try:
                 eng.set_library_f32(lib)
                 r = eng.step_f32(patches)
@@ -1139,7 +1128,6 @@ def test_fenced_and_unfenced_arrival_tickets_decide_alike(finish):
     acquire pair of the memory model around the arrival ticket is optional on the single-agent integer path
     (DEJAVU_FENCED, csrc/dejavu_hip.hip:step_fenced).  Both forms must give the reference's decision, per-heading maxima
     and per-view minima on a library whose best view is duplicated in far-apart blocks and seen by several headings."""
-    import os
     F, h, w, A, cw = 90000, 4, 4, 16, 0.25
     lib = synth.synth_views(23, F, h, w)
     star = lib[41000].copy()
@@ -1151,12 +1139,7 @@ def test_fenced_and_unfenced_arrival_tickets_decide_alike(finish):
     want = oracle.step(lib, pats, cw)
     seen = {}
     for fenced in ("0", "1"):
-        os.environ["DEJAVU_FENCED"], os.environ["DEJAVU_FINISH"] = fenced, finish
-        try:
-            e = navsim_amd.FamiliarityEngine(0)
-        finally:
-            os.environ.pop("DEJAVU_FENCED", None)
-            os.environ.pop("DEJAVU_FINISH", None)
+        e = engine_with({"DEJAVU_FENCED": fenced, "DEJAVU_FINISH": finish})
         try:
             e.set_library(lib, cw)
             for _ in range(20):
@@ -1177,15 +1160,9 @@ def test_matrix_core_kernel_forms_under_repetition(fp4, tiles):
     with ragged view-group ranges (waves without a group of their own in most items), every decision, per-heading
     maximum and per-view minimum against the oracle (the integer sums are exact, so the scores must agree to the last
     bit from step to step)."""
-    import os
     F, h, w, A, cw = 9000 + 37, 20, 12, 13, 0.25
     lib = synth.synth_views(61, F, h, w)
-    os.environ.update(DEJAVU_SHAPE="6", DEJAVU_BITS="2", DEJAVU_FP4=fp4, DEJAVU_MFMA_TILES=tiles)
-    try:
-        e = navsim_amd.FamiliarityEngine(0)
-    finally:
-        for k in ("DEJAVU_SHAPE", "DEJAVU_BITS", "DEJAVU_FP4", "DEJAVU_MFMA_TILES"):
-            os.environ.pop(k, None)
+    e = engine_with(dict(DEJAVU_SHAPE="6", DEJAVU_BITS="2", DEJAVU_FP4=fp4, DEJAVU_MFMA_TILES=tiles))
     try:
         e.set_library(lib, cw)
         assert e.library_info()["has_bit_planes"]
@@ -1211,7 +1188,6 @@ def test_ties_inside_one_finishing_block_of_several_view_sets():
     heading; a set's representative that loses to a later set's must still reach the candidate list.  The best view is
     duplicated in two sets of the same block (and far away), seen by two headings: the decision, every per-heading
     maximum and the candidate count must be the oracle's / the two-kernel ending's."""
-    import os
     F, h, w, A, cw = 300000, 4, 4, 20, 0.25                     # 300 000 views -> 3 view sets per block
     lib = synth.synth_views(29, F, h, w)
     star = lib[100000].copy()
@@ -1225,11 +1201,7 @@ def test_ties_inside_one_finishing_block_of_several_view_sets():
     assert (want["best_idex"], want["best_view"]) == (7, min(dup))
     seen = {}
     for finish in ("2", "0"):
-        os.environ["DEJAVU_FINISH"] = finish
-        try:
-            e = navsim_amd.FamiliarityEngine(0)
-        finally:
-            os.environ.pop("DEJAVU_FINISH", None)
+        e = engine_with({"DEJAVU_FINISH": finish})
         try:
             e.set_library(lib, cw)
             r = e.step(pats, want_scene=True)
@@ -1243,18 +1215,8 @@ def test_ties_inside_one_finishing_block_of_several_view_sets():
     assert seen["2"] == seen["0"] >= 2 * len(dup)
 
 
-def _engine_with(env):
-    import os
-    keys = ("DEJAVU_SHAPE", "DEJAVU_BITS", "DEJAVU_FP4", "DEJAVU_FUSE", "DEJAVU_MFMA_TILES", "DEJAVU_VCODE")
-    before = {k: os.environ.pop(k, None) for k in keys}
-    os.environ.update(env)
-    try:
-        return navsim_amd.FamiliarityEngine(0)
-    finally:
-        for k in keys:
-            os.environ.pop(k, None)
-            if before[k] is not None:
-                os.environ[k] = before[k]
+# The matrix-core knobs the tests below set; an engine of theirs is created with the others of these unset.
+_MFMA_UNSET = dict.fromkeys(("DEJAVU_SHAPE", "DEJAVU_BITS", "DEJAVU_FP4", "DEJAVU_FUSE", "DEJAVU_MFMA_TILES", "DEJAVU_VCODE"))
 
 
 @pytest.mark.parametrize("F,h,w,A,cw,tiles", [(5000, 32, 32, 32, 0.5, "0"), (3001, 20, 24, 7, 0.3, "2"), (9037, 16, 16, 64, 0.5, "0"),
@@ -1271,8 +1233,8 @@ def test_fp4_form_gives_the_int8_forms_sums(F, h, w, A, cw, tiles):
     seen = {}
     for fp4 in ("1", "code", "0"):                    # "code": the value plane as 3-bit level codes (DEJAVU_VCODE=1, k_bitpack_code)
         for fuse in ("1", "0"):
-            e = _engine_with(dict(DEJAVU_SHAPE="6", DEJAVU_BITS="2", DEJAVU_FP4="0" if fp4 == "0" else "1", DEJAVU_FUSE=fuse,
-                                  DEJAVU_MFMA_TILES=tiles, DEJAVU_VCODE="1" if fp4 == "code" else "0"))
+            e = engine_with(dict(DEJAVU_SHAPE="6", DEJAVU_BITS="2", DEJAVU_FP4="0" if fp4 == "0" else "1", DEJAVU_FUSE=fuse,
+                                 DEJAVU_MFMA_TILES=tiles, DEJAVU_VCODE="1" if fp4 == "code" else "0"))
             try:
                 e.set_library(lib, cw)
                 info = e.library_info()
@@ -1305,7 +1267,7 @@ def test_off_level_patches_take_the_int8_form_in_the_same_launch():
     step against the oracle, and the flag follows the patches."""
     F, h, w, A, cw = 6000 + 5, 24, 16, 12, 0.4
     lib = synth.synth_views(23, F, h, w)
-    e = _engine_with(dict(DEJAVU_SHAPE="6", DEJAVU_BITS="2"))
+    e = engine_with(dict(_MFMA_UNSET, DEJAVU_SHAPE="6", DEJAVU_BITS="2"))
     try:
         e.set_library(lib, cw)
         assert e.library_info()["fp4_form"]
@@ -1338,7 +1300,7 @@ def test_fp4_form_needs_one_gap_width_per_nibble_bit():
         lib[..., 2] = np.array(levels, np.uint8)[rng.integers(0, len(levels), (F, h, w))]
         pat = np.zeros((3, h, w, 3), np.uint8)
         pat[..., 2] = np.array(levels, np.uint8)[rng.integers(0, len(levels), (3, h, w))]
-        e = _engine_with(dict(DEJAVU_SHAPE="6", DEJAVU_BITS="2"))
+        e = engine_with(dict(_MFMA_UNSET, DEJAVU_SHAPE="6", DEJAVU_BITS="2"))
         try:
             e.set_library(lib, 0.0)
             info = e.library_info()

@@ -20,8 +20,7 @@ pytestmark = pytest.mark.gpu
 def eng(request):
     """Every test runs under each form of the scoring path (tests/helpers.py:ENGINE_MODES): both step endings, the
     bit-plane matrix-core kernel, and the product default."""
-    with engine_mode(request.param):
-        e = navsim_amd.FamiliarityEngine(device=0)
+    e = engine_mode(request.param)
     e.mode = request.param
     yield e
     e.close()

@@ -4,7 +4,6 @@ ingests and the kernel knobs a context reads at creation.  Everything calls libd
 the oracle (oracle/) is the checker only; nothing reads /root/reference.
 """
 import ctypes
-import os
 
 import numpy as np
 import pytest
@@ -13,26 +12,11 @@ import navsim_amd
 from navsim_amd import synth
 from navsim_amd import _native as N
 from oracle import oracle
-from tests.helpers import ENGINE_MODES, engine_mode
+from tests.helpers import ENGINE_MODES, engine_mode, engine_with
 
 pytestmark = pytest.mark.gpu
 
 RTOL = 1e-9
-
-
-def _engine(env=None):
-    """An engine created under `env` (the context reads its knobs when it is created); the environment is put back."""
-    env = env or {}
-    before = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return navsim_amd.FamiliarityEngine(0)
-    finally:
-        for k, v in before.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 # ------------------------------------------------------------------ dense check at the size the headline is quoted on
@@ -106,8 +90,7 @@ def test_dense_oracle_at_config_two():
 # ------------------------------------------------------------------ more than 64 headings
 @pytest.fixture(scope="module", params=ENGINE_MODES)
 def eng(request):
-    with engine_mode(request.param):
-        e = navsim_amd.FamiliarityEngine(device=0)
+    e = engine_mode(request.param)
     e.mode = request.param
     yield e
     e.close()
@@ -163,7 +146,7 @@ def test_wide_step_on_the_tie_stress_fixture(manifest):
     pats = np.ascontiguousarray(patches[order])
     want = oracle.step(lib, pats, case["chem_weight"])
     for env in ({}, {"DEJAVU_SHAPE": "6", "DEJAVU_BITS": "2"}):
-        e = _engine(env)
+        e = engine_with(env)
         try:
             e.set_library(lib, case["chem_weight"])
             got = e.step(pats, want_scene=False)
@@ -333,7 +316,7 @@ def test_allocation_failure_leaves_no_library(metric, n_allocs):
         views = rng.random((200, 10, 12), dtype=np.float32)
         pats = rng.random((4, 10, 12), dtype=np.float32)
     for k in range(1, n_allocs + 1):
-        e = _engine({"DEJAVU_TEST_FAIL_ALLOC": str(k)})
+        e = engine_with({"DEJAVU_TEST_FAIL_ALLOC": str(k)})
         try:
             with pytest.raises(navsim_amd.EngineError, match="DV_ERR_OOM"):
                 (e.set_library_u8 if metric == "u8" else e.set_library_f32)(views)
@@ -346,7 +329,7 @@ def test_allocation_failure_leaves_no_library(metric, n_allocs):
             assert e._lib.dv_get_library_info(e._ctx, ctypes.byref(N.LibInfo())) == -3
         finally:
             e.close()
-    e = _engine({"DEJAVU_TEST_FAIL_ALLOC": str(n_allocs + 1)})      # past the ingest's allocations: nothing fails
+    e = engine_with({"DEJAVU_TEST_FAIL_ALLOC": str(n_allocs + 1)})      # past the ingest's allocations: nothing fails
     try:
         (e.set_library_u8 if metric == "u8" else e.set_library_f32)(views)
         r = (e.step_u8 if metric == "u8" else e.step_f32)(pats)
@@ -385,8 +368,8 @@ def test_body_knobs_are_read_per_context(env):
     full = env.get("DEJAVU_MIXED") is not None
     lib = synth.synth_views(71, F, h, w, full_range_s=full)
     base = {"DEJAVU_SHAPE": "6", "DEJAVU_BITS": "2", "DEJAVU_MFMA_CHUNK": "1"}     # one K chunk: the loader / consumer body even at this size
-    e_def = _engine(base)
-    e_knob = _engine(dict(base, **env))
+    e_def = engine_with(base)
+    e_knob = engine_with(dict(base, **env))
     try:
         for e in (e_def, e_knob):
             e.set_library(lib, cw)
@@ -416,7 +399,7 @@ def test_fenced_ticket_is_the_default_on_long_passes():
     seen = {}
     for name, env in (("default bytes", {"DEJAVU_BITS": "0", "DEJAVU_FINISH": "2"}),
                       ("unfenced bytes", {"DEJAVU_BITS": "0", "DEJAVU_FINISH": "2", "DEJAVU_FENCED": "0"})):
-        e = _engine(env)
+        e = engine_with(env)
         try:
             e.generate_library(31, F, h, w, cw)
             pats = synth.synth_patches(31, A, h, w)
@@ -512,7 +495,7 @@ def test_ssd_f32_on_the_matrix_cores_reports_the_references_doubles(F, h, w, A):
     for a in range(A):
         d = l64 - patches[a].astype(np.float64)
         want[a] = (d * d).reshape(F, -1).sum(axis=1)                  # near the oracle's value: used to find the few pairs it scores
-    e_new, e_old = _engine({}), _engine({"DEJAVU_SSD_MFMA": "0"})
+    e_new, e_old = engine_with({}), engine_with({"DEJAVU_SSD_MFMA": "0"})
     try:
         for e in (e_new, e_old):
             e.set_library_f32(lib)
@@ -557,7 +540,7 @@ def test_ssd_f32_selection_bound_under_cancellation(A, scale, noise):
     patches = (base[None] + (noise * scale) * rng.standard_normal((A, h, w))).astype(np.float32)
     patches[3] = lib[777]                                              # an exact match among the near-duplicates
     l64 = lib.astype(np.float64)
-    e = _engine({})
+    e = engine_with({})
     try:
         e.set_library_f32(lib)
         r = e.step_f32(patches)
@@ -689,7 +672,7 @@ def test_passes_of_64_headings_with_shared_accumulators_match_the_oracle(cw):
     off[4, 3] = lib[777]
     got = {}
     for knob in ("1", "0"):
-        eng = _engine({"DEJAVU_LC22": knob})
+        eng = engine_with({"DEJAVU_LC22": knob})
         try:
             eng.set_library(lib, cw)
             for name, patches in (("on", on), ("off", off)):
@@ -713,7 +696,7 @@ def test_passes_of_64_headings_with_shared_accumulators_match_the_oracle(cw):
         assert (got["1", "on"][2]["best_idex"], got["1", "on"][2]["best_view"]) == (5, 123)      # the first of the two duplicates
     # the reference's default n_test_angles = 60 (NavBySceneFamiliarity.py:62) is ONE pass of 64 resident headings: a single agent's
     # step takes the same kernel
-    eng = _engine()
+    eng = engine_with({})
     try:
         eng.set_library(lib, cw)
         p60 = on.reshape(-1, h, w, 3)[:60].copy()
@@ -749,7 +732,7 @@ def test_two_group_body_equals_one_group_body(h, w, n_agents, A, F, cw, levels):
     patches[n_agents // 2, A // 2] = lib[F - 7]
     recs = {}
     for knob in ("1", "0"):
-        eng = _engine({"DEJAVU_LC22": knob})
+        eng = engine_with({"DEJAVU_LC22": knob})
         try:
             eng.set_library(lib, cw)
             eng.step_batch(patches)
@@ -760,7 +743,7 @@ def test_two_group_body_equals_one_group_body(h, w, n_agents, A, F, cw, levels):
     assert recs["1"] == recs["0"]
     assert recs["1"][n_agents // 2][:2] == (A // 2, F - 7)
     want = oracle.step(lib[F - 300:], patches[0], cw, want_scene=False)      # and a slice of the oracle for good measure
-    got = _engine()
+    got = engine_with({})
     try:
         got.set_library(lib[F - 300:], cw)
         r0 = got.step(patches[0], want_scene=False)
@@ -781,7 +764,7 @@ def test_ensemble_chain_knobs_leave_the_records_alone(env):
     patches[17, 9] = synth.near_match_patch(lib[12345], 4, fraction=0.02)
     recs = []
     for e in ({}, env):
-        eng = _engine(e)
+        eng = engine_with(e)
         try:
             eng.set_library(lib, 0.25)
             eng.step_batch(patches)

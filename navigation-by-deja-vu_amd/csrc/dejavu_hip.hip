@@ -166,13 +166,17 @@ struct dv_ctx {
     bool fp4_ok = false;                      // this library's planes qualify (build_bit_planes)
     int fp4_env = 1;                          // DEJAVU_FP4=0: never
     uint4* d_coef4 = nullptr;                 // [pass][K-step][4][64] E2M1 sign images (k_patch_prep)
-    uint4* d_ctiles = nullptr;                // [Fpad/32][GSC][64] code tiles (k_bitpack_code), when bcfg.vcode
+    uint4* d_ctiles = nullptr;                // [Fpad/32][GSC][64] code tiles (k_bitpack_code), when they were built
     size_t ctile_bytes = 0;
-    // DEJAVU_VCODE=1: the fp4 form reads five-level value planes as 3-bit codes (k_bitpack_code: a third copy of the library, 5
-    // bits per pixel).  Off by default: at 500 000 views x 128x128 it moves 5.16 GB instead of 6.18 GB per pass in the SAME
-    // 0.94 ms -- with the library stream out of the way the loop is bound by its LDS operand traffic and the matrix pipe
-    // (tools/exp/fp4_ladder.hip), so the copy would cost 5 GB and buy nothing yet.
-    int vcode_env = 0;
+    // Five-level value planes as 3-bit codes (k_bitpack_code: a third copy of the library, 5 bits per pixel).  Which body reads them
+    // is a property of the launch (launch_body), not of the library.  DEJAVU_VCODE unset (-1): the tiles are built where the
+    // library's single-pass step of <= 32 headings takes the register-ring body, and only that body (LcRegCode) reads them;
+    // 0: never built; 1 (experiment): built whenever five levels allow, and the LDS-ring bodies LcCode / Lc2TilesCode read them
+    // (`code_all`: at 500 000 views x 128x128 those move 5.16 GB instead of 6.18 GB per pass in the SAME 0.94 ms -- bound by
+    // their LDS operand traffic, tools/exp/fp4_ladder.hip -- and Lc22 / LcReg are not taken).
+    int vcode_env = -1;
+    bool code_all = false;                    // DEJAVU_VCODE=1 and the tiles exist
+    bool last_codes = false;                  // the last matrix-core pass was launched with a body that reads code rows
     int last_form = 0;                        // DV_FORM_* of the last integer scoring pass (fp4 bit: the fp4 image existed)
     int fuse_env = 1;                         // DEJAVU_FUSE=0: one-chunk matrix-core passes leave their sums to k_finish instead of finishing them
     int lc_env = 1;                           // DEJAVU_LC: 0 every wave loads and multiplies, 1 loader / consumer waves (stages of 4, ring of 3), 2 (stages of 2, ring of 5)
@@ -325,7 +329,7 @@ static void free_library(dv_ctx* c) {
     F(c->d_part); F(c->d_pmax); F(c->d_record); F(c->d_keys); F(c->d_bsum); F(c->d_bsum2); F(c->d_ctmp);
     F(c->d_ftiles); F(c->d_fraw); F(c->d_fprep); F(c->d_fpart); F(c->d_fprep4); F(c->d_fvnorm); F(c->d_fpnorm); F(c->d_flower); F(c->d_fprepb);
     F(c->d_u8tiles); F(c->d_u8raw); F(c->d_u8prep); F(c->d_u8part); F(c->d_vnorm); F(c->d_pnorm);
-    F(c->d_btiles); F(c->d_coef); F(c->d_coef4); F(c->d_ctiles); c->ctile_bytes = 0;
+    F(c->d_btiles); F(c->d_coef); F(c->d_coef4); F(c->d_ctiles); c->ctile_bytes = 0; c->code_all = false;
     c->pbits = PrepBits{};
     c->bits_ok = false; c->coef_ready = false; c->btile_bytes = 0;
     c->metric = 0;
@@ -570,6 +574,7 @@ static long long group_stride(const dv_ctx* c, long long kb) {
 // ------------------------------------------------------------------ bit planes (MFMA scoring path)
 // Builds the bit-plane copy of the resident byte tiles when the library's values allow it.  Never fails the ingest:
 // a library that does not qualify simply keeps the byte path.
+static bool plan_reads_codes(dv_ctx* c);
 static int build_bit_planes(dv_ctx* c) {
     const LibCfg& g = c->cfg;
     c->bits_ok = false;
@@ -629,7 +634,7 @@ static int build_bit_planes(dv_ctx* c) {
     // and the V K-steps in whole stages of four too: the code tiles store a stage's code dwords together (k_bitpack_code)
     b.NK[1] = (b.NK[1] + 3) / 4 * 4;
     // Five value levels (four planes of the one value byte plane): the fp4 form may read them as 3-bit codes (k_bitpack_code)
-    const bool five_levels = c->fp4_env != 0 && c->vcode_env != 0 && g.hasv && b.T[1] == 4 && !mixed;
+    const bool five_levels = c->fp4_env != 0 && c->vcode_env != 0 && g.hasv && b.T[1] == 4 && !mixed;   // (unset: see below)
     const int nkt = b.NK[0] + b.NK[1];
     b.GS = nkt | 1;
     // fp4 form of the kernel.  A gap wider than 127 was split for the int8 coefficients into planes that carry the same bits
@@ -678,30 +683,33 @@ static int build_bit_planes(dv_ctx* c) {
     }
     c->pbits = pb;
     c->mixed = mixed;
-    b.vcode = 0;
+    b.vcode = 0;                                                        // (set per launch: launch_body)
     b.GSC = b.GS;
-    if (c->fp4_ok && five_levels) {
+    b.nt = c->nt_env >= 0 ? c->nt_env : 1;
+    c->bcfg = b;
+    // DEJAVU_VCODE unset: only where this library's single-pass step of <= 32 headings would read them (LcRegCode)
+    if (c->fp4_ok && five_levels && (c->vcode_env == 1 || plan_reads_codes(c))) {
         const long long units = 4ll * b.NK[0] + 3ll * b.NK[1];          // 256-byte units of a view group: 1-KB HS rows, 768-B V rows
         long long kib = (units + 3) / 4;
         if (kib % 2 == 0) ++kib;                                        // an odd number of KiB apart, like the bit tiles
         b.GSC = (int)(kib * 4);
         if (hipMalloc(&c->d_ctiles, (size_t)G32 * b.GSC * 256) == hipSuccess) {
-            b.vcode = 1;
+            c->code_all = c->vcode_env == 1;
             c->ctile_bytes = (size_t)G32 * units * 256;
         } else {
             (void)hipGetLastError();                                    // no room for the third copy: the fp4 form reads the bit tiles
+            c->d_ctiles = nullptr;
             b.GSC = b.GS;
         }
     }
     // library rows: non-temporal (used once per step).  DEJAVU_NT=0 streams them with the default policy instead -- measured equal on
     // 50 000 views x 64x64 (158 MB of bit tiles, which would fit the 256 MiB Infinity Cache between two steps): kernel 38.9-40.5 us
     // either way (tools/runs/r4_c1.sh), so that kernel is not waiting for its stream
-    b.nt = c->nt_env >= 0 ? c->nt_env : 1;
     c->bcfg = b;
     const long long total_t = G32 * nkt * 64;
     hipLaunchKernelGGL(k_bitpack, dim3((unsigned)((total_t + 255) / 256)), dim3(256), 0, c->stream, c->d_tiles, c->d_btiles, c->cfg, b);
     HIP_TRY(c, hipGetLastError());
-    if (b.vcode) {
+    if (c->d_ctiles) {
         hipLaunchKernelGGL(k_bitpack_code, dim3((unsigned)((total_t + 255) / 256)), dim3(256), 0, c->stream, c->d_btiles,
                            reinterpret_cast<unsigned*>(c->d_ctiles), c->cfg, b);
         HIP_TRY(c, hipGetLastError());
@@ -1931,7 +1939,7 @@ extern "C" int dv_scoring_form(dv_ctx* c) {
     if (!(c->last_form & DV_FORM_FP4)) return c->last_form;
     const int on_level = read_on_level(c);                 // the dual kernel ran: which image it took is on the device
     if (on_level < 0) return on_level;
-    return on_level ? c->last_form : c->last_form & ~DV_FORM_FP4;
+    return on_level ? c->last_form : c->last_form & ~(DV_FORM_FP4 | DV_FORM_CODES);    // (the int8 form reads the bit tiles)
 }
 
 extern "C" int dv_clear_library(dv_ctx* c) {
@@ -1968,7 +1976,7 @@ extern "C" int dv_get_library_info(const dv_ctx* c, dv_lib_info* o) {
     o->bit_planes_hs = c->bits_ok ? c->bcfg.T[0] : 0;
     o->bit_planes_v = c->bits_ok ? c->bcfg.T[1] : 0;
     o->bit_tile_bytes = c->bits_ok ? (int64_t)c->btile_bytes : 0;
-    o->code_tile_bytes = (c->bits_ok && c->bcfg.vcode) ? (int64_t)c->ctile_bytes : 0;
+    o->code_tile_bytes = (c->bits_ok && c->d_ctiles) ? (int64_t)c->ctile_bytes : 0;
     o->mixed_layout = (c->bits_ok && c->mixed) ? 1 : 0;
     return DV_OK;
 }
@@ -2183,13 +2191,14 @@ static FuseArgs fuse_args(const dv_ctx* c) {
 // The bodies a matrix-core pass can be launched with.  mfma_plan names one; nothing else chooses.
 //   Ring, Ring2, RingA, RingB: every wave loads and multiplies (sad_ring_fp4 / sad_ring_i8) -- one view group per wave, two, and the
 //     two ring shapes of DEJAVU_RING (A/B);
-//   Lc, LcShort, LcCode, LcReg: loader and consumer waves (sad_lc_fp4) -- stages of 4 K-steps and a ring of 3, stages of 2 and a ring
-//     of 5 (DEJAVU_LC=2), 3-bit code rows (DEJAVU_VCODE=1), the library rows in the consumers' registers (sad_lc_fp4_lreg);
+//   Lc, LcShort, LcCode, LcReg, LcRegCode: loader and consumer waves (sad_lc_fp4) -- stages of 4 K-steps and a ring of 3, stages of 2
+//     and a ring of 5 (DEJAVU_LC=2), 3-bit code rows (DEJAVU_VCODE=1), the library rows in the consumers' registers
+//     (sad_lc_fp4_lreg), and those with the value rows as 3-bit codes (where the code tiles were built);
 //   Lc2Tiles, Lc2TilesCode: sad_lc_fp4 with two heading tiles per view group (64 resident headings in one pass);
 //   Lc22: k_sad_lc22, two view groups x two heading tiles per consumer (fused finishing only).
 // Every fp4 body has the int8 ring body <SK8, TILES, RD8> beside it for off-level patches, and the loader / consumer bodies the fp4
 // ring body <SK4, TILES, RD4> for chunked passes.
-enum class Body { Ring, Ring2, RingA, RingB, Lc, LcShort, LcCode, LcReg, Lc2Tiles, Lc2TilesCode, Lc22, Count };
+enum class Body { Ring, Ring2, RingA, RingB, Lc, LcShort, LcCode, LcReg, LcRegCode, Lc2Tiles, Lc2TilesCode, Lc22, Count };
 
 // <int8 stage, ring | fp4 stage, ring (ring body) | view groups per wave | fp4 stage, ring (loader / consumer body; stage 0: none),
 // code rows, heading tiles per view group>: the template arguments of k_sad_mfma_dual (k_sad_lc22: SKL, RDL; it has no fp4 ring
@@ -2205,6 +2214,7 @@ constexpr BodyShape kBodyShapes[] = {
     /* LcShort      */ {4, 2, 2, 4, 1, 2, 5, false, 1},
     /* LcCode       */ {4, 2, 2, 4, 1, 4, 3, true, 1},
     /* LcReg        */ {4, 2, 2, 4, 1, kLregStage, 3, false, 1},
+    /* LcRegCode    */ {4, 2, 2, 4, 1, kLregStage, 3, true, 1},
     /* Lc2Tiles     */ {4, 2, 2, 4, 1, 4, 3, false, 2},
     /* Lc2TilesCode */ {4, 2, 2, 4, 1, 4, 3, true, 2},
     /* Lc22         */ {4, 2, 0, 0, 1, 2, 3, false, 2},
@@ -2269,6 +2279,12 @@ static void launch_body(dv_ctx* c, int nchunk, int has_hs) {
     const int nkt = c->bcfg.NK[0] + c->bcfg.NK[1];
     FuseArgs fz{};
     if (FUSE) { fz = fuse_args(c); fz.nb = (int)grid; }
+    // what this body's loader / consumer form reads: the code tiles (LCODE bodies; mfma_plan names one only where they exist) or the
+    // bit tiles, as everything else in the launch does
+    BitCfg bcfg = c->bcfg;
+    bcfg.vcode = s.LCODE ? 1 : 0;
+    const uint4* ftiles = s.LCODE ? c->d_ctiles : c->d_btiles;
+    c->last_codes = s.LCODE && nchunk == 1;
     for (int a_off = 0; a_off < c->APAD; a_off += 32 * s.HT) {
         const uint4* coef = c->d_coef + (size_t)(a_off / 32) * nkt * 512;
         const uint4* coef4 = c->fp4_ok ? c->d_coef4 + (size_t)(a_off / 32) * nkt * 256 : nullptr;
@@ -2276,8 +2292,8 @@ static void launch_body(dv_ctx* c, int nchunk, int has_hs) {
             hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), lds, c->stream, c->d_btiles, coef, coef4, offlevel_word(c), c->cfg, c->bcfg,
                                c->APAD, a_off, has_hs, fz, (int)n_gq);
         } else {
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), lds, c->stream, c->d_btiles, c->bcfg.vcode ? c->d_ctiles : c->d_btiles, coef,
-                               coef4, offlevel_word(c), reinterpret_cast<int*>(c->d_part), c->cfg, c->bcfg, nchunk, c->APAD, a_off, has_hs,
+            hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), lds, c->stream, c->d_btiles, ftiles, coef,
+                               coef4, offlevel_word(c), reinterpret_cast<int*>(c->d_part), c->cfg, bcfg, nchunk, c->APAD, a_off, has_hs,
                                fz, (int)n_gq);
         }
     }
@@ -2287,7 +2303,7 @@ static void launch_body(dv_ctx* c, int nchunk, int has_hs) {
 // Bit positions 1, 2, 3 that stand for something have one width per segment, so that they can share an accumulator (sad_lc22_fp4,
 // sad_lc_fp4_lreg), in a library those bodies can take at all.  `with_bit0`: position 0 of the saturation segment has that width too.
 static bool shared_accumulator_fits(const dv_ctx* c, bool with_bit0) {
-    if (!c->fp4_ok || c->bcfg.vcode || c->mixed) return false;
+    if (!c->fp4_ok || c->code_all || c->mixed) return false;
     for (int seg = 0; seg < 2; ++seg) {
         int w = 0;
         for (int bit = 1; bit < 4; ++bit) {
@@ -2307,12 +2323,16 @@ static bool lc22_fits(const dv_ctx* c) {
 static bool lreg_fits(const dv_ctx* c) {
     return shared_accumulator_fits(c, false) && c->bcfg.NK[0] % kLregStage == 0;
 }
+// ... and with the value rows as codes: value K-steps, in whole stages of eight (two code stages of four, k_bitpack_code).
+static bool lreg_code_fits(const dv_ctx* c) {
+    return lreg_fits(c) && c->cfg.hasv && c->bcfg.T[1] == 4 && c->bcfg.NK[1] > 0 && c->bcfg.NK[1] % kLregStage == 0;
+}
 
 // A matrix-core pass over the resident library for `apad` resident headings: the body, the chunks its K-steps are cut into, and
 // whether the kernel finishes its scores itself.  Work items = (chunk of K-steps, range of at most body_view_groups view groups of
 // 32).  launch_mfma launches exactly this; run_batch asks it beforehand whether its passes will fuse (batch_pass_fuses).
 struct MfmaPlan { Body body; int nchunk; bool fuses; };
-static MfmaPlan mfma_plan(dv_ctx* c, int apad, bool fuse_request) {
+static MfmaPlan mfma_plan(dv_ctx* c, int apad, bool fuse_request, bool assume_code_tiles) {
     const long long G32 = c->cfg.Fpad / 32;
     const bool may_fuse = fuse_request && c->fuse_env && !c->mfma_chunk_env;         // (and one chunk: decided below)
     // DEJAVU_LC (A/B): 0 = every wave loads and multiplies (sad_ring_fp4); 1 = loader and consumer waves, stage of 4 K-steps, ring of 3
@@ -2323,8 +2343,8 @@ static MfmaPlan mfma_plan(dv_ctx* c, int apad, bool fuse_request) {
         // DEJAVU_HT=1 (A/B): 64 resident headings as two passes over the library instead of two heading tiles per view group in one
         const bool two_tiles = apad == 64 && c->ht_env == 2;
         if (two_tiles && may_fuse && c->lc22_env && lc22_fits(c) && item_groups(G32, 8) >= 160) body = Body::Lc22;
-        else if (two_tiles) body = c->bcfg.vcode ? Body::Lc2TilesCode : Body::Lc2Tiles;
-        else if (c->bcfg.vcode) body = Body::LcCode;
+        else if (two_tiles) body = c->code_all ? Body::Lc2TilesCode : Body::Lc2Tiles;
+        else if (c->code_all) body = Body::LcCode;
         else body = c->lc_env == 2 ? Body::LcShort : Body::Lc;                      // (Lc: LcReg instead where it fits, below)
     } else {
         // Two view groups per wave halve the coefficient traffic (every A operand serves both) once there are about 1.25 such items
@@ -2356,7 +2376,13 @@ static MfmaPlan mfma_plan(dv_ctx* c, int apad, bool fuse_request) {
     if (nchunk < 1 || c->mixed) nchunk = 1;                              // (mixed layout: the byte pass shares the one-chunk rows of the partial sums)
     // (Lc22 was chosen with may_fuse and >= 160 ranges, lc22_fits excludes the mixed layout: one chunk, fused)
     if (body == Body::Lc && nchunk == 1 && c->lreg_env && lreg_fits(c)) body = Body::LcReg;
+    if (body == Body::LcReg && (c->d_ctiles || assume_code_tiles) && lreg_code_fits(c)) body = Body::LcRegCode;
     return {body, nchunk, fuse_request && c->fuse_env && nchunk == 1};
+}
+
+// build_bit_planes, before it builds the code tiles by default: this library's single-pass step of <= 32 headings would read them.
+static bool plan_reads_codes(dv_ctx* c) {
+    return mfma_plan(c, 32, true, true).body == Body::LcRegCode;
 }
 
 // An ensemble pass of `apad` resident headings would finish its scores inside the scoring kernel (fused epilogue: nothing shared is
@@ -2366,7 +2392,7 @@ static bool batch_pass_fuses(dv_ctx* c, int apad) {
     const int cls = apad_class(apad);
     const int shape = c->shape_env ? c->shape_env : c->tuned_shape[cls];
     if (shape != 6) return false;
-    return mfma_plan(c, apad, true).fuses;
+    return mfma_plan(c, apad, true, false).fuses;
 }
 
 template <Body B>
@@ -2378,7 +2404,7 @@ static void launch_planned(dv_ctx* c, const MfmaPlan& p, int has_hs) {
 }
 
 static void launch_mfma(dv_ctx* c, int has_hs) {
-    const MfmaPlan p = mfma_plan(c, c->APAD, c->fuse_request);
+    const MfmaPlan p = mfma_plan(c, c->APAD, c->fuse_request, false);
     c->nchunk = p.nchunk;
     switch (p.body) {
         case Body::Ring: return launch_planned<Body::Ring>(c, p, has_hs);
@@ -2389,6 +2415,7 @@ static void launch_mfma(dv_ctx* c, int has_hs) {
         case Body::LcShort: return launch_planned<Body::LcShort>(c, p, has_hs);
         case Body::LcCode: return launch_planned<Body::LcCode>(c, p, has_hs);
         case Body::LcReg: return launch_planned<Body::LcReg>(c, p, has_hs);
+        case Body::LcRegCode: return launch_planned<Body::LcRegCode>(c, p, has_hs);
         case Body::Lc2Tiles: return launch_planned<Body::Lc2Tiles>(c, p, has_hs);
         case Body::Lc2TilesCode: return launch_planned<Body::Lc2TilesCode>(c, p, has_hs);
         case Body::Lc22: return launch_planned<Body::Lc22>(c, p, has_hs);
@@ -2431,7 +2458,8 @@ static int launch_int_scoring(dv_ctx* c, hipEvent_t after_tiles, int* n_partial,
             c->nchunk = 1;
         } else
         launch_mfma(c, has_hs_sum);
-        c->last_form = DV_FORM_MATRIX_CORES | (c->fp4_ok ? DV_FORM_FP4 : 0) | (c->epilogue_fused ? DV_FORM_FUSED_FINISH : 0);
+        c->last_form = DV_FORM_MATRIX_CORES | (c->fp4_ok ? DV_FORM_FP4 : 0) | (c->epilogue_fused ? DV_FORM_FUSED_FINISH : 0) |
+                       (c->fp4_ok && c->last_codes ? DV_FORM_CODES : 0);
         c->int_hsconst = c->mixed ? c->d_acc[c->acc_parity].hs : c->d_acc[c->acc_parity].bhs;
         c->int_vconst = c->d_acc[c->acc_parity].bv;
     } else if (g.generic) {

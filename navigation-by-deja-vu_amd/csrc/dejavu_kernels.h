@@ -2873,7 +2873,7 @@ struct BitCfg {
     int T[2];               // planes of the HS segment and of the V segment
     int NK[2];              // K-steps (256 K-elements) of each segment
     int GS;                 // 1-KB rows between consecutive view groups in btiles (>= NK[0] + NK[1], odd)
-    int vcode;              // 1: the fp4 form reads the V segment as 3-bit level codes (ctiles, see k_bitpack_code)
+    int vcode;              // 1: this launch's loader / consumer body reads the V segment as 3-bit level codes (ctiles, see k_bitpack_code)
     int GSC;                // 256-byte units between view groups in ctiles (>= 4 NK[0] + 3 NK[1])
     int nt;                 // 1: the library rows are streamed with the non-temporal policy (used once per step and larger than the
                             // Infinity Cache); 0: default policy -- a library that fits the 256 MiB cache is re-read from it step after step
@@ -4251,13 +4251,26 @@ sad_lc_fp4(const uint4* __restrict__ ftiles, const uint4* __restrict__ coef4, in
 // The register ring (64 registers) fits beside the accumulators because the bit positions of one width share one (as in
 // sad_lc22_fp4): every position's library bit is moved to the 1.0 bit of its nibble, position 0 accumulates in one block,
 // positions 1, 2, 3 -- whose widths must agree per segment (the host checks, lreg_fits) -- in the other.  The counts are
-// integers (|count| < 2^24), so the sums are bit for bit sad_lc_fp4's.  HT = 1, thermometer rows; the saturation / value
-// boundary NK[0] must be a whole number of stages (the host checks).
+// integers (|count| < 2^24), so the sums are bit for bit sad_lc_fp4's.  HT = 1; the saturation / value boundary NK[0] must be a
+// whole number of stages (the host checks).
+// CODE: `btiles` are the code tiles (k_bitpack_code) and a value stage is six 1-KB chunks of 3-bit-code dwords per view group
+// instead of eight rows, decoded per K-step in registers (48 KB per CU on their way in the value segment).  The stage loop is
+// peeled so that every loop has one fixed pair (kind of the stage consumed, kind of the stage the ring receives), the library
+// loads are inline assembly the compiler's waitcnt bookkeeping does not see, and every K-step waits for its pieces with a
+// counted s_waitcnt (run_code below); the value K-steps must be whole stages too (the host checks, lreg_code_fits).
 constexpr int kLregStage = 8;                                           // SKL of k_sad_mfma_dual that selects this body
 template <int SK, int RD>
 constexpr int lreg_ring_bytes() { return RD * SK * 4 * 1024; }
 
-template <int SK, int RD, bool FUSE>
+// a consumer's library load with the wait counted by hand (CODE): 64 lanes x 16 B at `base` (uniform) + `voff`, non-temporal.  The
+// compiler's waitcnt bookkeeping does not see it: a counted wait_vmcnt_le and lds_tie on `d` stand in front of every use.
+template <int OFF>
+__device__ __forceinline__ void lib_load16_nt(v4u_t& d, unsigned voff, unsigned long long base) {
+    static_assert(OFF >= 0 && OFF < 4096, "immediate offset");
+    asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3 nt" : "+v"(d) : "v"(voff), "s"(base), "n"(OFF) : "memory");
+}
+
+template <int SK, int RD, bool FUSE, bool CODE>
 __device__ __forceinline__ void
 sad_lc_fp4_lreg(const uint4* __restrict__ btiles, const uint4* __restrict__ coef4, int* __restrict__ part, const LibCfg& c, const BitCfg& b,
                 int apad_total, int a_off, int has_hs_sum, const FuseArgs& fz, int n_gq) {
@@ -4276,7 +4289,7 @@ sad_lc_fp4_lreg(const uint4* __restrict__ btiles, const uint4* __restrict__ coef
     const int NKT = b.NK[0] + b.NK[1];
     const int nst = (NKT + SK - 1) / SK;
     const int NK0 = b.NK[0];
-    const long long gbytes = (long long)b.GS * 1024;                    // between view groups
+    const long long gbytes = CODE ? (long long)b.GSC * 256 : (long long)b.GS * 1024;        // between view groups
     const unsigned lds_base = (unsigned)(unsigned long long)(lds_ptr_t)lds_ring;
     unsigned long long* scratch0 = reinterpret_cast<unsigned long long*>(reinterpret_cast<unsigned char*>(lds_ring) + RING);
     const unsigned char* lib_bytes = reinterpret_cast<const unsigned char*>(btiles);
@@ -4353,11 +4366,51 @@ sad_lc_fp4_lreg(const uint4* __restrict__ btiles, const uint4* __restrict__ coef
             lkb += SK;
             if (lkb >= nst * SK) { lkb = 0; ++lj; cursor_item(); }
         };
-        if (n_mine > 0) {                                               // (the host launches no workgroup without items)
-            cursor_item();
+        // CODE: the cursor's stage is a saturation stage (eight 1-KB rows per view group) or a value stage (six 1-KB chunks of code
+        // dwords: two half stages of four K-steps, k_bitpack_code); piece e of either goes to xr[e].  The addresses are uniform
+        // (cbase[t]: the cursor item's view group) plus the lane's 16 bytes.
+        const int n_sat = has_hs_sum ? NK0 / SK : 0;                    // saturation stages of an item (CODE: value stages follow)
+        const unsigned voff = (unsigned)lane * 16u;
+        unsigned long long cbase[TL] = {0, 0}, cstage[TL] = {0, 0};     // the cursor item's view groups; the cursor's stage in them
+        auto cursor_stage_code = [&]() {
+            // a value stage starts NK[0] KB + 768 B per value K-step into the group (a group is far smaller than 4 GB)
+            const int vk = lkb - n_sat * SK;
+            const unsigned off = (unsigned)lkb * 1024u - (unsigned)(vk > 0 ? vk : 0) * 256u;
 #pragma unroll
-            for (int kk = 0; kk < SK; ++kk) load_row(kk);
-            cursor_next();
+            for (int t = 0; t < TL; ++t) cstage[t] = cbase[t] + off;
+        };
+        auto cursor_item_code = [&]() {
+            const long long item = blockIdx.x + (lj < n_mine ? lj : 0) * gridDim.x;     // (past the last item: re-reads of the first)
+            const long long g0 = (item * G32) / GQ, g1 = ((item + 1) * G32) / GQ;
+#pragma unroll
+            for (int t = 0; t < TL; ++t) {
+                const long long g = g0 + wave * TL + t;
+                cbase[t] = (unsigned long long)(lib_bytes + (g < g1 ? g : g0) * gbytes);
+            }
+            cursor_stage_code();
+        };
+        auto load_piece = [&](auto ec) {
+            constexpr int e = decltype(ec)::value;
+#pragma unroll
+            for (int t = 0; t < TL; ++t) lib_load16_nt<(e & 3) * 1024>(xr[e][t], voff, cstage[t] + (e >> 2) * 4096u);
+        };
+        auto cursor_next_code = [&]() {                                 // behind a stage's loads
+            lkb += SK;
+            if (lkb >= nst * SK) { lkb = 0; ++lj; cursor_item_code(); }
+            else cursor_stage_code();
+        };
+        if (n_mine > 0) {                                               // (the host launches no workgroup without items)
+            if constexpr (CODE) {
+                cursor_item_code();
+                static_for<6>([&](auto ec) { load_piece(ec); });
+                if (n_sat > 0) { load_piece(IntC<6>{}); load_piece(IntC<7>{}); }
+                cursor_next_code();
+            } else {
+                cursor_item();
+#pragma unroll
+                for (int kk = 0; kk < SK; ++kk) load_row(kk);
+                cursor_next();
+            }
         }
         for (long long j = 0; j < n_mine; ++j) {
             const long long item = blockIdx.x + j * gridDim.x;
@@ -4472,9 +4525,115 @@ sad_lc_fp4_lreg(const uint4* __restrict__ btiles, const uint4* __restrict__ coef
                         cslot = nslot;
                     }
                 };
+                // CODE: stages [s0, s1) of kind CK (0: saturation rows, 1: value codes) while the cursor's stage, the one the ring
+                // receives, is of kind LK -- one fixed pair per loop, so the loads outstanding at every K-step are a constant and
+                // every wait is counted.  A stage is entered with exactly its own pieces outstanding, in order (8 rows / 6 chunks
+                // per view group); a piece goes out right behind the K-step that read its registers last:
+                //   saturation stage: row kk dies in K-step kk (a value stage behind it: chunks 0..5 behind K-steps 0..5);
+                //   value stage: chunk 0 of a half stage dies in its K-step 1, chunk 1 in 2, chunk 2 in 3 -- pieces 0..5 behind
+                //   K-steps 1, 2, 3, 5, 6, 7 (a saturation stage behind it: its rows 6, 7 behind K-step 7 too, xr[6], xr[7] are idle).
+                // Younger than the newest piece K-step kk reads = the stage's later pieces + what went out before kk.
+                auto run_code = [&](int s0, int s1, auto ckc, auto lkc) {
+                    constexpr int CK = decltype(ckc)::value, LK = decltype(lkc)::value;
+                    for (int st = s0; st < s1; ++st) {
+                        const int nslot = cslot + 1 == RD ? 0 : cslot + 1;
+                        static_for<SK>([&](auto kc) {
+                            constexpr int kk = decltype(kc)::value;
+                            if constexpr (kk + 1 < SK) {
+                                fetch(cslot, IntC<kk + 1>{});           // one K-step ahead
+                                lds_wait<4>();                          // all but the newest K-step's reads have landed
+                            } else {
+                                lds_wait<0>();                          // everything this wave will use of the slot is in registers
+                                if (st + 1 < nst) {
+                                    __builtin_amdgcn_s_barrier();       // stage st + 1 is in LDS; the loaders may refill slot st - 1 ... and,
+                                    fetch(nslot, IntC<0>{});            //   one barrier later, this one
+                                }
+                            }
+#pragma unroll
+                            for (int s = 0; s < 4; ++s) lds_tie(a[kk & 1][s]);
+                            constexpr unsigned m = 0x22222222u;         // (whole stages: no K-step without K-elements)
+                            constexpr int h3 = 3 * (kk / 4), q = kk % 4;
+                            constexpr int newest = CK ? h3 + (q < 2 ? q : 2) : kk;
+                            constexpr int sent = CK ? kk - (kk + 3) / 4 : (LK == 0 || kk < 6 ? kk : 6);
+                            wait_vmcnt_le<TL * ((CK ? 6 : 8) - 1 - newest + sent)>();
+                            unsigned bo[TL][4][4];
+                            if constexpr (CK == 0) {
+#pragma unroll
+                                for (int t = 0; t < TL; ++t) lds_tie(xr[kk][t]);
+#pragma unroll
+                                for (int t = 0; t < TL; ++t) {
+                                    const unsigned x[4] = {xr[kk][t].x, xr[kk][t].y, xr[kk][t].z, xr[kk][t].w};
+#pragma unroll
+                                    for (int d = 0; d < 4; ++d) {
+                                        bo[t][0][d] = (x[d] << 1) & m;
+                                        bo[t][1][d] = x[d] & m;
+                                        bo[t][2][d] = (x[d] >> 1) & m;
+                                        bo[t][3][d] = (x[d] >> 2) & m;
+                                    }
+                                }
+                                if constexpr (LK == 0 || kk < 6) load_piece(kc);
+                            } else {
+                                // the K-step's three code dwords are dwords 3 q .. 3 q + 2 of the half stage's twelve (chunks h3 .. h3 + 2)
+#pragma unroll
+                                for (int t = 0; t < TL; ++t) {
+                                    if constexpr (q < 2) lds_tie(xr[h3][t]);
+                                    if constexpr (q == 1 || q == 2) lds_tie(xr[h3 + 1][t]);
+                                    if constexpr (q >= 2) lds_tie(xr[h3 + 2][t]);
+                                }
+#pragma unroll
+                                for (int t = 0; t < TL; ++t) {
+                                    unsigned x[4];
+                                    if constexpr (q == 0) { x[0] = xr[h3][t].x; x[1] = xr[h3][t].y; x[2] = xr[h3][t].z; }
+                                    else if constexpr (q == 1) { x[0] = xr[h3][t].w; x[1] = xr[h3 + 1][t].x; x[2] = xr[h3 + 1][t].y; }
+                                    else if constexpr (q == 2) { x[0] = xr[h3 + 1][t].z; x[1] = xr[h3 + 1][t].w; x[2] = xr[h3 + 2][t].x; }
+                                    else { x[0] = xr[h3 + 2][t].y; x[1] = xr[h3 + 2][t].z; x[2] = xr[h3 + 2][t].w; }
+                                    // the fourth dword's pixels: bit 3 of the three code dwords' nibbles
+                                    x[3] = ((x[0] >> 3) & 0x11111111u) | ((x[1] >> 2) & 0x22222222u) | ((x[2] >> 1) & 0x44444444u);
+                                    // code b2 b1 b0 -> thermometer bit of every position on the 1.0 bit: t1 = b0 | b1, t2 = b1, t3 = b2, t4 = b0 & b2
+#pragma unroll
+                                    for (int d = 0; d < 4; ++d) {
+                                        bo[t][0][d] = ((x[d] << 1) | x[d]) & m;
+                                        bo[t][1][d] = x[d] & m;
+                                        bo[t][2][d] = (x[d] >> 1) & m;
+                                        bo[t][3][d] = (x[d] << 1) & (x[d] >> 1) & m;
+                                    }
+                                }
+                                if constexpr (q > 0) load_piece(IntC<kk - 1 - kk / 4>{});
+                                if constexpr (LK == 0 && kk == SK - 1) { load_piece(IntC<6>{}); load_piece(IntC<7>{}); }
+                            }
+#pragma unroll
+                            for (int s = 0; s < 4; ++s) {
+                                const v4u_t& av = a[kk & 1][s];
+                                const v8i_t ao = v8i_t{(int)av.x, (int)av.y, (int)av.z, (int)av.w, 0, 0, 0, 0};
+#pragma unroll
+                                for (int t = 0; t < TL; ++t) {
+                                    const v8i_t bv = v8i_t{(int)bo[t][s][0], (int)bo[t][s][1], (int)bo[t][s][2], (int)bo[t][s][3], 0, 0, 0, 0};
+                                    if constexpr (FUSE) acc[t][s ? 1 : 0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bv, ao, acc[t][s ? 1 : 0], 4, 4, 0, 0, 0, 0);   // views x headings
+                                    else acc[t][s ? 1 : 0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ao, bv, acc[t][s ? 1 : 0], 4, 4, 0, 0, 0, 0);
+                                }
+                            }
+                        });
+                        cursor_next_code();
+                        cslot = nslot;
+                    }
+                };
                 // saturation stages (when the library has that segment), then the value stages; the accumulators change hands at the boundary
                 const int nst0 = has_hs_sum ? (NK0 / SK < nst ? NK0 / SK : nst) : 0;       // (NK0 is a whole number of stages: the host checks)
                 const int hs_end = (has_hs_sum && !(c.hasv && b.NK[1] > 0)) ? nst : nst0;
+                if constexpr (CODE) {
+                    // (the host checks: value K-steps in whole stages, at least one; hs_end == n_sat < nst)
+                    if (hs_end > 0) {
+                        run_code(0, hs_end - 1, IntC<0>{}, IntC<0>{});
+                        run_code(hs_end - 1, hs_end, IntC<0>{}, IntC<1>{});
+                        flush(tot_hs, 0);
+                        // (unfused: these stores are younger than every load the next waits are for -- the counts hold, a little early)
+                        if constexpr (!FUSE) store_sums(tot_hs, 0);
+                        clear();
+                    }
+                    // the last value stage's cursor is in the next item's first stage: saturation, or value like the stages before it
+                    run_code(hs_end, hs_end > 0 ? nst - 1 : nst, IntC<1>{}, IntC<1>{});
+                    if (hs_end > 0) run_code(nst - 1, nst, IntC<1>{}, IntC<0>{});
+                } else {
                 run_stages(0, hs_end);
                 if (hs_end > 0 && hs_end < nst) {
                     flush(tot_hs, 0);
@@ -4482,6 +4641,7 @@ sad_lc_fp4_lreg(const uint4* __restrict__ btiles, const uint4* __restrict__ coef
                     clear();
                 }
                 run_stages(hs_end, nst);
+                }
                 if (hs_end < nst) flush(tot_v, 1);                      // what the accumulators hold at the end: the value segment's sums,
                 else flush(tot_hs, 0);                                  // unless there are no value K-steps
                 if constexpr (!FUSE) {
@@ -4499,6 +4659,7 @@ sad_lc_fp4_lreg(const uint4* __restrict__ btiles, const uint4* __restrict__ coef
                 if (j == 0) DV_STAMP(4);
             }
         }
+        if constexpr (CODE) wait_vmcnt_le<0>();                         // the re-reads past the last item
     }
     if constexpr (FUSE) {
         if (a_off < fz.A_real) fused_block_end(scratch0, fz, c, a_off);
@@ -4856,9 +5017,9 @@ k_sad_mfma_dual(const uint4* __restrict__ btiles, const uint4* __restrict__ ftil
     if constexpr (SKL > 0) {
         static_assert(TILES == 1, "the loader / consumer body cuts the library into ranges of 8 / HT view groups; the other bodies must agree");
         if (fp4 && nchunk == 1) {
-            if constexpr (SKL == kLregStage) {                          // the library rows in the consumers' registers (thermometer rows)
-                static_assert(HT == 1 && !LCODE, "sad_lc_fp4_lreg: one heading tile, thermometer rows");
-                sad_lc_fp4_lreg<SKL, RDL, FUSE>(btiles, coef4, part, c, b, apad_total, a_off, has_hs_sum, fz, n_gq);
+            if constexpr (SKL == kLregStage) {                          // the library rows in the consumers' registers (LCODE: value rows as codes)
+                static_assert(HT == 1, "sad_lc_fp4_lreg: one heading tile");
+                sad_lc_fp4_lreg<SKL, RDL, FUSE, LCODE>(LCODE ? ftiles : btiles, coef4, part, c, b, apad_total, a_off, has_hs_sum, fz, n_gq);
             } else {
                 sad_lc_fp4<SKL, RDL, FUSE, LCODE, HT>(ftiles, coef4, part, c, b, apad_total, a_off, has_hs_sum, fz, n_gq);     // LCODE == (b.vcode != 0)
             }

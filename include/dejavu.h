@@ -525,6 +525,48 @@ int dv_diffuse_configure(dv_ctx *ctx, int window, int steps_per_launch);
 int dv_diffuse_info(dv_ctx *ctx, int *tile, int *steps_per_launch, int *steps_done);
 int dv_diffuse(dv_ctx *ctx, const double *init, int n, int64_t nstep, double c, double delta_t_factor, uint32_t flags, double *out);
 
+/* ---- Infomax familiarity model -------------------------------------------- */
+/*
+ * A second familiarity model behind the reference's plug-in seam (navsim/util.pyx:10-25): the Infomax network of Baddeley, Graham,
+ * Husbands & Philippides (2012).  One layer of weights W, float64[M, N], N = h * w sensor pixels, M = n_hidden, trained in one pass
+ * over the route's views; memory and the cost of a step do not grow with the route.  With p the view's compared plane (uint8[h, w],
+ * C order) and x = p/255 - mean(p/255) in float64, a training view does
+ *     h = W x;  y = tanh(h);  u = h^T W;  W <- W + (learning_rate / N) * (W - (y + h) u^T)
+ * and a scored view has unfamiliarity d(x) = sum_i |(W x)_i|; the calls report familiarity = -d (so the reference's np.max /
+ * np.argmax pick the least novel heading; the largest possible value is 0).  Everything is float64 on the device, no reduction
+ * uses floating-point atomics and each has a fixed order: the same calls on the same bytes give the same bits.  The model lives
+ * beside, and independent of, a resident library, landscape, patches and diffuse field.
+ *   begin            allocates W and copies w0 (float64[n_hidden * h * w], row-major; the caller draws it).  A model already there
+ *                    is replaced.  DV_ERR_INVALID: channel outside {0, 1, 2}, learning_rate <= 0, n_hidden < 1, h or w < 1, NULL w0.
+ *                    DV_ERR_OOM when W does not fit.
+ *   train_u8         trains on uint8[n, h, w] planes in order; calling it again continues the chain (train(a) then train(b) gives
+ *                    the bits of train(a + b)).
+ *   train_from_poses senses the n poses as dv_set_library_from_poses does and trains on their `channel` plane with no host round
+ *                    trip; out_views (may be NULL) receives uint8[n, h, w, 3].  DV_ERR_INDEX as dv_sense; DV_ERR_INVALID when the
+ *                    sensor's shape is not the model's.
+ *                    Both: after training, one reduction checks that W is finite; if not (a too-large learning rate makes the rule
+ *                    diverge) the call returns DV_ERR_STATE, dv_last_error names the learning rate, and training and scoring keep
+ *                    returning DV_ERR_STATE until begin or set_weights brings finite weights.
+ *   score_u8         familiarity[a] = -d of each of uint8[n, h, w] planes, any n >= 1 (64 per pass over W).
+ *   sense_step       one agent step: senses the n_headings patches at (x, y), scores their `channel` plane and takes the first
+ *                    maximum of angle_fam (np.argmax).  Any n_headings >= 1.  DV_ERR_INDEX like dv_sense_step.
+ *   read_weights / set_weights   copy float64[n_hidden * h * w] out and in: what a user saves and restores.
+ *   info             n_hidden, n_pixels, views trained since begin, whether W is finite (0 without a model), bytes of W; any
+ *                    pointer may be NULL.
+ *   end              frees the model; dv_destroy frees it too.
+ * Every call but begin, info and end returns DV_ERR_STATE without a model.
+ */
+int dv_infomax_begin(dv_ctx *ctx, int h, int w, int channel, int n_hidden, double learning_rate, const double *w0);
+int dv_infomax_train_u8(dv_ctx *ctx, const uint8_t *planes, int64_t n);
+int dv_infomax_train_from_poses(dv_ctx *ctx, const double *x, const double *y, const double *angle, int64_t n, uint8_t *out_views);
+int dv_infomax_score_u8(dv_ctx *ctx, const uint8_t *planes, int n, double *familiarity);
+int dv_infomax_sense_step(dv_ctx *ctx, double x, double y, const double *angles, int n_headings, double *angle_fam,
+                          int32_t *best_heading);
+int dv_infomax_read_weights(dv_ctx *ctx, double *out);
+int dv_infomax_set_weights(dv_ctx *ctx, const double *weights);
+int dv_infomax_info(dv_ctx *ctx, int *n_hidden, int *n_pixels, int64_t *views_trained, int *finite, int64_t *bytes);
+int dv_infomax_end(dv_ctx *ctx);
+
 /* ---- measurement ------------------------------------------------------- */
 /* hipEvent pair on the context's stream around whatever is enqueued between the two calls. */
 int dv_timer_start(dv_ctx *ctx);

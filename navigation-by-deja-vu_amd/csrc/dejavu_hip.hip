@@ -288,6 +288,22 @@ struct dv_ctx {
     int diff_S = 0, diff_T = 0;               // window side (64 or 96) and steps per launch of the blocked form; 0 = default (dv_diffuse_configure, DEJAVU_DIFFUSE_S / _T)
     bool diff_lds_opted = false;              // the 96 window's 144 KB of LDS were asked for on this context
 
+    // Infomax familiarity model (dejavu_infomax.inl): one layer of weights, independent of the library above
+    double* im_W = nullptr;                   // [M][N]
+    double* im_h[2] = {nullptr, nullptr};     // [M] each: h of the current view and of the next
+    double* im_u = nullptr;                   // [N]
+    double* im_upart = nullptr;               // [row blocks][N]
+    double* im_xs = nullptr;                  // [im_xs_cap][N]: the x vectors of the training views being chained
+    size_t im_xs_cap = 0;
+    double* im_sx = nullptr;                  // [64][N]: the x vectors of the headings being scored
+    double* im_dpart = nullptr;               // [row tiles][64]
+    double* im_d = nullptr;                   // [64]
+    int* im_flag = nullptr;                   // k_im_finite's answer
+    int im_M = 0, im_N = 0, im_hh = 0, im_ww = 0, im_channel = 2;
+    double im_eta = 0.0;
+    int64_t im_views = 0;                     // views trained on since dv_infomax_begin
+    bool im_finite = true;
+
     // measurement
     hipEvent_t t0 = nullptr, t1 = nullptr;
     int profile = 0;                          // dv_profile_kernel: bracket every profile-th scoring launch with events
@@ -316,6 +332,7 @@ static int fail(dv_ctx* c, int code, const char* fmt, ...) {
 
 static void use_set(dv_ctx* c, int which);
 static void diffuse_free(dv_ctx* c);
+static void infomax_free(dv_ctx* c);
 static void free_library(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
     use_set(c, 0);
@@ -413,6 +430,7 @@ extern "C" void dv_destroy(dv_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     free_library(c);
     diffuse_free(c);
+    infomax_free(c);
     if (c->d_land) (void)hipFree(c->d_land);
     if (c->d_lut) (void)hipFree(c->d_lut);
     if (c->d_poses) (void)hipFree(c->d_poses);
@@ -3551,4 +3569,5 @@ extern "C" int dv_stream_read_gbps(dv_ctx* c, int64_t n_bytes, int iters, double
 }
 
 #include "dejavu_diffuse.inl"   // dv_diffuse_*: the landscape generator's heat equation (kernels and host side)
+#include "dejavu_infomax.inl"   // dv_infomax_*: the Infomax familiarity model (kernels and host side)
 #include "dejavu_group.inl"     // dv_group_*: one process, several devices -- host logic above the C ABI

@@ -1,0 +1,486 @@
+// The Infomax familiarity model on the device (include/dejavu.h: dv_infomax_*).  One layer of weights W, double[M][N], trained once
+// over the route's views (Baddeley, Graham, Husbands & Philippides 2012); a view's unfamiliarity is d(x) = sum_i |(W x)_i|.  Per
+// training view, with x = p/255 - mean(p/255) of the view's compared plane:
+//
+//     h = W x;   y = tanh(h);   u = h^T W;   W <- W + (eta/N) * (W - (y + h) u^T)
+//
+// Everything is double and every reduction has a fixed order (no floating-point atomics), so two runs give the same bits.
+// The grid-wide dependencies (u needs all of h, the update needs all of u) are kernel boundaries on the context's stream:
+//
+//   k_im_prep     one workgroup per view: plane bytes -> x (the mean's sum: 256 strided partial sums, then a fixed tree in LDS)
+//   k_im_gemv     h = W x, one wave per row (a lane's strided partial sum, then the xor butterfly): the first h of a chain only
+//   k_im_upart    pass A: partial u over blocks of kImRowsPerBlock rows, a thread per column, rows in order
+//   k_im_ureduce  u_j = the partials of column j, row blocks in order (N threads: a launch of its own, since every workgroup of the
+//                 update needs all of u and re-summing the partials there would cost more than the launch)
+//   k_im_update   pass B: one wave per row updates the row and, in the same sweep, dots the UPDATED row with the NEXT view's x --
+//                 the next h.  Same loop, same operations and same order as k_im_gemv on the stored row, so a chain cut in two
+//                 (dv_infomax_train_u8 called twice) carries the bits of the uncut one.  W: read twice, written once per view.
+//   k_im_score    H = W X for up to 64 headings and d's partial sums in one pass over W on the f64 matrix cores
+//                 (v_mfma_f64_16x16x4_f64): a workgroup of 8 waves owns 16 rows of W, the waves take the 16-column chunks of those rows
+//                 round-robin, their accumulators are added in wave order through LDS, then |.| is summed over the 16 rows in order
+//   k_im_dfinish  d_a = the row tiles' partial sums (one wave per heading: strided partial sums, then the butterfly)
+//   k_im_finite   is every weight finite? (a too-large learning rate makes the rule diverge)
+//
+// A heading's column of H does not depend on how many headings ride with it (an MFMA result element is its own dot product), which
+// is what lets the agent's fused step and a plug-in call on one patch agree bit for bit.
+namespace dv {
+
+__device__ __forceinline__ double im_wave_sum(double v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// src: view v's compared plane is src[v * view_stride + offset + j * px_stride], j < N
+__global__ __launch_bounds__(256) void k_im_prep(const unsigned char* __restrict__ src, long long view_stride, int px_stride, int offset, int N,
+                                                 double* __restrict__ x) {
+    __shared__ double red[256];
+    const int tid = (int)threadIdx.x;
+    const unsigned char* p = src + (size_t)blockIdx.x * (size_t)view_stride + offset;
+    double* xo = x + (size_t)blockIdx.x * (size_t)N;
+    double s = 0.0;
+    for (int j = tid; j < N; j += 256) s += (double)p[(size_t)j * px_stride] / 255.0;
+    red[tid] = s;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (tid < st) red[tid] += red[tid + st];
+        __syncthreads();
+    }
+    const double mean = red[0] / (double)N;
+    for (int j = tid; j < N; j += 256) xo[j] = (double)p[(size_t)j * px_stride] / 255.0 - mean;
+}
+
+__global__ __launch_bounds__(256) void k_im_gemv(const double* __restrict__ W, const double* __restrict__ x, int M, int N, double* __restrict__ h) {
+    const int lane = (int)threadIdx.x & 63;
+    const int row = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+    if (row >= M) return;                                   // (whole waves leave: no workgroup barrier below)
+    const double* w = W + (size_t)row * (size_t)N;
+    double acc = 0.0;
+    for (int j = lane; j < N; j += 64) acc = __builtin_fma(w[j], x[j], acc);
+    acc = im_wave_sum(acc);
+    if (lane == 0) h[row] = acc;
+}
+
+static constexpr int kImRowsPerBlock = 64;
+
+__global__ __launch_bounds__(256) void k_im_upart(const double* __restrict__ W, const double* __restrict__ h, int M, int N, double* __restrict__ upart) {
+    const int j = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (j >= N) return;
+    const int i0 = (int)blockIdx.y * kImRowsPerBlock;
+    const int i1 = i0 + kImRowsPerBlock < M ? i0 + kImRowsPerBlock : M;
+    const double* w = W + (size_t)i0 * (size_t)N + j;
+    double acc = 0.0;
+#pragma unroll 8
+    for (int i = i0; i < i1; ++i, w += N) acc = __builtin_fma(h[i], *w, acc);
+    upart[(size_t)blockIdx.y * (size_t)N + j] = acc;
+}
+
+__global__ __launch_bounds__(256) void k_im_ureduce(const double* __restrict__ upart, int n_blocks, int N, double* __restrict__ u) {
+    const int j = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (j >= N) return;
+    double acc = 0.0;
+    for (int b = 0; b < n_blocks; ++b) acc += upart[(size_t)b * (size_t)N + j];
+    u[j] = acc;
+}
+
+// x_next == nullptr: the chain ends here (h_next is not written)
+__global__ __launch_bounds__(256) void k_im_update(double* __restrict__ W, const double* __restrict__ h, const double* __restrict__ u, int M, int N,
+                                                   double rate, const double* __restrict__ x_next, double* __restrict__ h_next) {
+#pragma clang fp contract(off)
+    const int lane = (int)threadIdx.x & 63;
+    const int row = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+    if (row >= M) return;
+    double* w = W + (size_t)row * (size_t)N;
+    const double hi = h[row];
+    const double yh = tanh(hi) + hi;
+    double acc = 0.0;
+    if (x_next) {
+        for (int j = lane; j < N; j += 64) {
+            const double wo = w[j];
+            const double wn = wo + rate * (wo - yh * u[j]);
+            w[j] = wn;
+            acc = __builtin_fma(wn, x_next[j], acc);
+        }
+        acc = im_wave_sum(acc);
+        if (lane == 0) h_next[row] = acc;
+    } else {
+        for (int j = lane; j < N; j += 64) {
+            const double wo = w[j];
+            w[j] = wo + rate * (wo - yh * u[j]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_im_finite(const double* __restrict__ W, long long n, int* __restrict__ flag) {
+    bool bad = false;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) bad |= !isfinite(W[i]);
+    if (bad) *flag = 1;                                     // (every writer stores the same word)
+}
+
+typedef double im_d4 __attribute__((ext_vector_type(4)));
+
+// The 4 doubles base[k .. k+3] of one row (zeros where ok is false or past n).  VEC: n % 4 == 0 and k % 4 == 0, so the four are there
+// together and 32-byte aligned.
+template <bool VEC>
+__device__ __forceinline__ im_d4 im_load4(const double* __restrict__ base, int k, int n, bool ok) {
+    im_d4 v = {0.0, 0.0, 0.0, 0.0};
+    if (VEC) {
+        if (ok && k < n) v = *reinterpret_cast<const im_d4*>(base + k);
+    } else if (ok) {
+        if (k < n) v.x = base[k];
+        if (k + 1 < n) v.y = base[k + 1];
+        if (k + 2 < n) v.z = base[k + 2];
+        if (k + 3 < n) v.w = base[k + 3];
+    }
+    return v;
+}
+
+static constexpr int kImScoreWaves = 8;
+static constexpr int kImHeadings = 64;                       // headings of one pass over W
+
+// HT: 16-heading tiles computed (the call's headings, rounded up).  X: [A][N], heading-major.  dpart: [row tiles][kImHeadings].
+// Lane l = (r = l & 15, g = l >> 4) feeds row r of the workgroup's 16 rows of W as the MFMA's A operand and heading r of each tile as
+// its B operand, element k = chunk * 16 + g * 4 + j in MFMA j of 4; accumulator register q of tile t is H[row g + 4 q][heading 16 t + r].
+template <int HT, bool VEC>
+__global__ __launch_bounds__(kImScoreWaves * 64) void k_im_score(const double* __restrict__ W, const double* __restrict__ X, int M, int N, int A,
+                                                                 double* __restrict__ dpart) {
+    __shared__ double sred[16][HT * 16];
+    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, g = lane >> 4;
+    const int row = (int)blockIdx.x * 16 + r;
+    const bool row_ok = row < M;
+    const double* wrow = W + (size_t)(row_ok ? row : 0) * (size_t)N;
+    const double* xrow[HT];
+    bool x_ok[HT];
+    im_d4 acc[HT];
+#pragma unroll
+    for (int t = 0; t < HT; ++t) {
+        const int a = t * 16 + r;
+        x_ok[t] = a < A;
+        xrow[t] = X + (size_t)(x_ok[t] ? a : 0) * (size_t)N;
+        acc[t] = im_d4{0.0, 0.0, 0.0, 0.0};
+    }
+    const int n_chunks = (N + 15) / 16;
+    // two of the wave's chunks per trip (chunk c and c + 8: loaded together, used in that order; a chunk past the end loads zeros)
+    for (int c = wave; c < n_chunks; c += 2 * kImScoreWaves) {   // (wave-uniform bounds: every lane runs every MFMA)
+        const int k0 = c * 16 + g * 4, k1 = k0 + 16 * kImScoreWaves;
+        const im_d4 wv0 = im_load4<VEC>(wrow, k0, N, row_ok);
+        const im_d4 wv1 = im_load4<VEC>(wrow, k1, N, row_ok);
+        im_d4 xv0[HT], xv1[HT];
+#pragma unroll
+        for (int t = 0; t < HT; ++t) {
+            xv0[t] = im_load4<VEC>(xrow[t], k0, N, x_ok[t]);
+            xv1[t] = im_load4<VEC>(xrow[t], k1, N, x_ok[t]);
+        }
+#pragma unroll
+        for (int t = 0; t < HT; ++t) {
+            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wv0.x, xv0[t].x, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wv0.y, xv0[t].y, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wv0.z, xv0[t].z, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wv0.w, xv0[t].w, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wv1.x, xv1[t].x, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wv1.y, xv1[t].y, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wv1.z, xv1[t].z, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(wv1.w, xv1[t].w, acc[t], 0, 0, 0);
+        }
+    }
+    // the waves' shares of the sum over k, added in wave order
+    for (int w = 0; w < kImScoreWaves; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int t = 0; t < HT; ++t) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    double* s = &sred[g + 4 * q][t * 16 + r];
+                    *s = w == 0 ? acc[t][q] : *s + acc[t][q];
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (tid < HT * 16) {
+        double s = 0.0;
+        for (int rr = 0; rr < 16; ++rr) s += fabs(sred[rr][tid]);         // (rows past M hold zeros)
+        dpart[(size_t)blockIdx.x * kImHeadings + tid] = s;
+    }
+}
+
+// one wave per heading
+__global__ __launch_bounds__(64) void k_im_dfinish(const double* __restrict__ dpart, int n_tiles, double* __restrict__ d) {
+    const int lane = (int)threadIdx.x;
+    double s = 0.0;
+    for (int t = lane; t < n_tiles; t += 64) s += dpart[(size_t)t * kImHeadings + blockIdx.x];
+    s = im_wave_sum(s);
+    if (lane == 0) d[blockIdx.x] = s;
+}
+
+}  // namespace dv
+
+static constexpr long long kImMaxPixels = 1 << 20;            // N of a view
+static constexpr size_t kImStageBytes = 64u << 20;            // x vectors and uploaded planes are staged in slabs of at most this
+
+static void infomax_free(dv_ctx* c) {
+    auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
+    F(c->im_W); F(c->im_h[0]); F(c->im_h[1]); F(c->im_u); F(c->im_upart); F(c->im_xs); F(c->im_sx); F(c->im_dpart); F(c->im_d); F(c->im_flag);
+    c->im_M = c->im_N = c->im_hh = c->im_ww = 0;
+    c->im_xs_cap = 0;
+    c->im_views = 0;
+    c->im_finite = true;
+}
+
+static int infomax_need(dv_ctx* c, const char* who) {
+    if (!c->im_W) return fail(c, DV_ERR_STATE, "%s: no Infomax model (dv_infomax_begin first)", who);
+    return DV_OK;
+}
+
+// Sets im_finite from the weights as they stand (synchronises the stream).
+static int infomax_check_finite(dv_ctx* c) {
+    const long long n = (long long)c->im_M * c->im_N;
+    HIP_TRY(c, hipMemsetAsync(c->im_flag, 0, sizeof(int), c->stream));
+    const long long blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(k_im_finite, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, c->stream, c->im_W, n, c->im_flag);
+    HIP_TRY(c, hipGetLastError());
+    int bad = 0;
+    HIP_TRY(c, hipMemcpyAsync(&bad, c->im_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->im_finite = bad == 0;
+    return DV_OK;
+}
+
+static int infomax_not_finite(dv_ctx* c, const char* who) {
+    return fail(c, DV_ERR_STATE, "%s: the weights are not finite (learning_rate %g is too large for these views: the rule diverged)", who,
+                c->im_eta);
+}
+
+// Enqueue the training chain over n views resident on the device (layout as k_im_prep's src).
+static int infomax_train_device(dv_ctx* c, const unsigned char* d_src, long long view_stride, int px_stride, int offset, int64_t n) {
+    const int M = c->im_M, N = c->im_N;
+    if (!c->im_xs) {
+        size_t cap = kImStageBytes / ((size_t)N * sizeof(double));
+        if (cap < 1) cap = 1;
+        HIP_TRY(c, hipMalloc((void**)&c->im_xs, cap * (size_t)N * sizeof(double)));
+        c->im_xs_cap = cap;
+    }
+    const double rate = c->im_eta / (double)N;
+    const unsigned row_blocks = (unsigned)((M + 3) / 4), col_blocks = (unsigned)((N + 255) / 256);
+    const int n_rb = (M + kImRowsPerBlock - 1) / kImRowsPerBlock;
+    int cur = 0;
+    for (int64_t b0 = 0; b0 < n; b0 += (int64_t)c->im_xs_cap) {
+        const int64_t nb = n - b0 < (int64_t)c->im_xs_cap ? n - b0 : (int64_t)c->im_xs_cap;
+        hipLaunchKernelGGL(k_im_prep, dim3((unsigned)nb), dim3(256), 0, c->stream, d_src + (size_t)b0 * (size_t)view_stride, view_stride, px_stride,
+                           offset, N, c->im_xs);
+        HIP_TRY(c, hipGetLastError());
+        hipLaunchKernelGGL(k_im_gemv, dim3(row_blocks), dim3(256), 0, c->stream, c->im_W, c->im_xs, M, N, c->im_h[cur]);
+        HIP_TRY(c, hipGetLastError());
+        for (int64_t v = 0; v < nb; ++v) {
+            hipLaunchKernelGGL(k_im_upart, dim3(col_blocks, (unsigned)n_rb), dim3(256), 0, c->stream, c->im_W, c->im_h[cur], M, N, c->im_upart);
+            hipLaunchKernelGGL(k_im_ureduce, dim3(col_blocks), dim3(256), 0, c->stream, c->im_upart, n_rb, N, c->im_u);
+            const double* x_next = v + 1 < nb ? c->im_xs + (size_t)(v + 1) * (size_t)N : nullptr;
+            hipLaunchKernelGGL(k_im_update, dim3(row_blocks), dim3(256), 0, c->stream, c->im_W, c->im_h[cur], c->im_u, M, N, rate, x_next,
+                               c->im_h[cur ^ 1]);
+            HIP_TRY(c, hipGetLastError());
+            cur ^= 1;
+        }
+    }
+    c->im_views += n;
+    return DV_OK;
+}
+
+template <int HT>
+static void infomax_launch_score(dv_ctx* c, int n) {
+    const unsigned tiles = (unsigned)((c->im_M + 15) / 16);
+    if (c->im_N % 4 == 0)
+        hipLaunchKernelGGL((k_im_score<HT, true>), dim3(tiles), dim3(kImScoreWaves * 64), 0, c->stream, c->im_W, c->im_sx, c->im_M, c->im_N, n, c->im_dpart);
+    else
+        hipLaunchKernelGGL((k_im_score<HT, false>), dim3(tiles), dim3(kImScoreWaves * 64), 0, c->stream, c->im_W, c->im_sx, c->im_M, c->im_N, n, c->im_dpart);
+}
+
+// Enqueue: x of the n <= 64 views at d_src, d of each, and the copy of the n values to `out` (the caller synchronises).
+static int infomax_score_device(dv_ctx* c, const unsigned char* d_src, long long view_stride, int px_stride, int offset, int n, double* out) {
+    hipLaunchKernelGGL(k_im_prep, dim3((unsigned)n), dim3(256), 0, c->stream, d_src, view_stride, px_stride, offset, c->im_N, c->im_sx);
+    HIP_TRY(c, hipGetLastError());
+    if (n <= 16) infomax_launch_score<1>(c, n);
+    else if (n <= 32) infomax_launch_score<2>(c, n);
+    else infomax_launch_score<4>(c, n);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(k_im_dfinish, dim3((unsigned)n), dim3(64), 0, c->stream, c->im_dpart, (c->im_M + 15) / 16, c->im_d);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(out, c->im_d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return DV_OK;
+}
+
+extern "C" int dv_infomax_end(dv_ctx* c) {
+    if (!c) return DV_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    infomax_free(c);
+    return DV_OK;
+}
+
+extern "C" int dv_infomax_begin(dv_ctx* c, int h, int w, int channel, int n_hidden, double learning_rate, const double* w0) {
+    if (!c) return DV_ERR_INVALID;
+    if (!w0) return fail(c, DV_ERR_INVALID, "dv_infomax_begin: the initial weights are NULL");
+    if (h < 1 || w < 1 || (long long)h * w > kImMaxPixels) return fail(c, DV_ERR_INVALID, "dv_infomax_begin: views of %d x %d (1..%lld pixels)", h, w, kImMaxPixels);
+    if (channel < 0 || channel > 2) return fail(c, DV_ERR_INVALID, "dv_infomax_begin: channel %d outside [0, 2]", channel);
+    if (n_hidden < 1 || n_hidden > kImMaxPixels) return fail(c, DV_ERR_INVALID, "dv_infomax_begin: n_hidden %d outside [1, %lld]", n_hidden, kImMaxPixels);
+    if (!(learning_rate > 0.0) || !std::isfinite(learning_rate)) return fail(c, DV_ERR_INVALID, "dv_infomax_begin: learning_rate %g must be positive", learning_rate);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    infomax_free(c);
+    const int M = n_hidden, N = h * w;
+    const size_t wbytes = (size_t)M * (size_t)N * sizeof(double);
+    const size_t n_rb = (size_t)((M + kImRowsPerBlock - 1) / kImRowsPerBlock), tiles = (size_t)((M + 15) / 16);
+    hipError_t e = hipMalloc((void**)&c->im_W, wbytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&c->im_h[0], (size_t)M * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->im_h[1], (size_t)M * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->im_u, (size_t)N * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->im_upart, n_rb * (size_t)N * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->im_sx, (size_t)kImHeadings * (size_t)N * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->im_dpart, tiles * kImHeadings * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->im_d, kImHeadings * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->im_flag, sizeof(int));
+    if (e == hipSuccess) e = hipMemcpyAsync(c->im_W, w0, wbytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);           // `w0` is borrowed for this call only
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        infomax_free(c);
+        return fail(c, e == hipErrorOutOfMemory ? DV_ERR_OOM : DV_ERR_HIP, "dv_infomax_begin: %d x %d weights (%zu bytes): %s", M, N, wbytes,
+                    hipGetErrorString(e));
+    }
+    c->im_M = M; c->im_N = N; c->im_hh = h; c->im_ww = w; c->im_channel = channel; c->im_eta = learning_rate;
+    return infomax_check_finite(c);
+}
+
+extern "C" int dv_infomax_train_u8(dv_ctx* c, const uint8_t* planes, int64_t n) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = infomax_need(c, "dv_infomax_train_u8");
+    if (rc) return rc;
+    if (!planes || n < 0) return fail(c, DV_ERR_INVALID, "dv_infomax_train_u8: planes is NULL or n < 0");
+    if (!c->im_finite) return infomax_not_finite(c, "dv_infomax_train_u8");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t N = (size_t)c->im_N;
+    size_t slab = kImStageBytes / N;
+    if (slab < 1) slab = 1;
+    if ((int64_t)slab > n) slab = (size_t)n;
+    if (n > 0) { rc = ensure_sense_buffer(c, slab * N); if (rc) return rc; }
+    for (int64_t v0 = 0; v0 < n; v0 += (int64_t)slab) {
+        const int64_t ns = n - v0 < (int64_t)slab ? n - v0 : (int64_t)slab;
+        HIP_TRY(c, hipMemcpyAsync(c->d_sense, planes + (size_t)v0 * N, (size_t)ns * N, hipMemcpyHostToDevice, c->stream));
+        rc = infomax_train_device(c, c->d_sense, (long long)N, 1, 0, ns);
+        if (rc) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));          // the slab is reused, `planes` is borrowed
+    }
+    rc = infomax_check_finite(c);
+    if (rc) return rc;
+    return c->im_finite ? DV_OK : infomax_not_finite(c, "dv_infomax_train_u8");
+}
+
+extern "C" int dv_infomax_train_from_poses(dv_ctx* c, const double* x, const double* y, const double* angle, int64_t n, uint8_t* out_views) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = infomax_need(c, "dv_infomax_train_from_poses");
+    if (rc) return rc;
+    if (!x || !y || !angle || n < 1 || n > 0x7fffffff) return fail(c, DV_ERR_INVALID, "dv_infomax_train_from_poses: bad arguments");
+    if (!c->have_sensor) return fail(c, DV_ERR_STATE, "sensor not configured");
+    if (c->sensor.sh != c->im_hh || c->sensor.sw != c->im_ww)
+        return fail(c, DV_ERR_INVALID, "dv_infomax_train_from_poses: the sensor is %dx%d but the model takes %dx%d views", c->sensor.sw, c->sensor.sh,
+                    c->im_ww, c->im_hh);
+    if (!c->im_finite) return infomax_not_finite(c, "dv_infomax_train_from_poses");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)n * (size_t)c->im_N * 3;
+    rc = ensure_sense_buffer(c, bytes);
+    if (rc) return rc;
+    rc = enqueue_sense(c, x, y, angle, n, c->d_sense);
+    if (rc) return rc;
+    if (out_views) HIP_TRY(c, hipMemcpyAsync(out_views, c->d_sense, bytes, hipMemcpyDeviceToHost, c->stream));
+    rc = check_sense_error(c);
+    if (rc) return rc;
+    rc = infomax_train_device(c, c->d_sense, 3ll * c->im_N, 3, c->im_channel, n);
+    if (rc) return rc;
+    rc = infomax_check_finite(c);
+    if (rc) return rc;
+    return c->im_finite ? DV_OK : infomax_not_finite(c, "dv_infomax_train_from_poses");
+}
+
+extern "C" int dv_infomax_score_u8(dv_ctx* c, const uint8_t* planes, int n, double* familiarity) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = infomax_need(c, "dv_infomax_score_u8");
+    if (rc) return rc;
+    if (!planes || !familiarity || n < 1) return fail(c, DV_ERR_INVALID, "dv_infomax_score_u8: NULL argument or n < 1");
+    if (!c->im_finite) return infomax_not_finite(c, "dv_infomax_score_u8");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t N = (size_t)c->im_N;
+    rc = ensure_sense_buffer(c, (size_t)kImHeadings * N * 3);                // (the size dv_infomax_sense_step asks for: one allocation for both)
+    if (rc) return rc;
+    for (int a0 = 0; a0 < n; a0 += kImHeadings) {                            // headings are independent: 64 per pass over W
+        const int na = n - a0 < kImHeadings ? n - a0 : kImHeadings;
+        HIP_TRY(c, hipMemcpyAsync(c->d_sense, planes + (size_t)a0 * N, (size_t)na * N, hipMemcpyHostToDevice, c->stream));
+        rc = infomax_score_device(c, c->d_sense, (long long)N, 1, 0, na, familiarity + a0);
+        if (rc) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    for (int a = 0; a < n; ++a) familiarity[a] = -familiarity[a];
+    return DV_OK;
+}
+
+extern "C" int dv_infomax_sense_step(dv_ctx* c, double x, double y, const double* angles, int n, double* angle_fam, int32_t* best_heading) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = infomax_need(c, "dv_infomax_sense_step");
+    if (rc) return rc;
+    if (!angles || !angle_fam || !best_heading || n < 1) return fail(c, DV_ERR_INVALID, "dv_infomax_sense_step: NULL argument or n_headings < 1");
+    if (!c->have_sensor) return fail(c, DV_ERR_STATE, "sensor not configured");
+    if (c->sensor.sh != c->im_hh || c->sensor.sw != c->im_ww)
+        return fail(c, DV_ERR_INVALID, "dv_infomax_sense_step: the sensor is %dx%d but the model takes %dx%d views", c->sensor.sw, c->sensor.sh,
+                    c->im_ww, c->im_hh);
+    if (!c->im_finite) return infomax_not_finite(c, "dv_infomax_sense_step");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t N = (size_t)c->im_N;
+    rc = ensure_sense_buffer(c, (size_t)kImHeadings * N * 3);
+    if (rc) return rc;
+    double xs[kImHeadings], ys[kImHeadings];
+    for (int a = 0; a < kImHeadings; ++a) { xs[a] = x; ys[a] = y; }
+    for (int a0 = 0; a0 < n; a0 += kImHeadings) {
+        const int na = n - a0 < kImHeadings ? n - a0 : kImHeadings;
+        rc = enqueue_sense(c, xs, ys, angles + a0, na, c->d_sense);
+        if (rc) return rc;
+        rc = infomax_score_device(c, c->d_sense, 3ll * (long long)N, 3, c->im_channel, na, angle_fam + a0);
+        if (rc) return rc;
+        rc = check_sense_error(c);                                           // (synchronises)
+        if (rc) return rc;
+    }
+    int best = 0;
+    for (int a = 0; a < n; ++a) {
+        angle_fam[a] = -angle_fam[a];
+        if (angle_fam[a] > angle_fam[best]) best = a;                        // first maximum, as np.argmax
+    }
+    *best_heading = best;
+    return DV_OK;
+}
+
+extern "C" int dv_infomax_read_weights(dv_ctx* c, double* out) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = infomax_need(c, "dv_infomax_read_weights");
+    if (rc) return rc;
+    if (!out) return fail(c, DV_ERR_INVALID, "dv_infomax_read_weights: out is NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(out, c->im_W, (size_t)c->im_M * (size_t)c->im_N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DV_OK;
+}
+
+extern "C" int dv_infomax_set_weights(dv_ctx* c, const double* weights) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = infomax_need(c, "dv_infomax_set_weights");
+    if (rc) return rc;
+    if (!weights) return fail(c, DV_ERR_INVALID, "dv_infomax_set_weights: weights is NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(c->im_W, weights, (size_t)c->im_M * (size_t)c->im_N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    return infomax_check_finite(c);
+}
+
+extern "C" int dv_infomax_info(dv_ctx* c, int* n_hidden, int* n_pixels, int64_t* views_trained, int* finite, int64_t* bytes) {
+    if (!c) return DV_ERR_INVALID;
+    if (n_hidden) *n_hidden = c->im_M;
+    if (n_pixels) *n_pixels = c->im_N;
+    if (views_trained) *views_trained = c->im_views;
+    if (finite) *finite = c->im_W && c->im_finite ? 1 : 0;
+    if (bytes) *bytes = (int64_t)c->im_M * c->im_N * (int64_t)sizeof(double);
+    return DV_OK;
+}

@@ -222,6 +222,17 @@ PROTOTYPES = {
     "dv_diffuse_configure": (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int]),
     "dv_diffuse_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "dv_diffuse": (ctypes.c_int, [_ctx_p, _f64p, ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_double, ctypes.c_uint32, _f64p]),
+    "dv_infomax_begin": (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, _f64p]),
+    "dv_infomax_train_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int64]),
+    "dv_infomax_train_from_poses": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int64, _u8p]),
+    "dv_infomax_score_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, _f64p]),
+    "dv_infomax_sense_step": (ctypes.c_int, [_ctx_p, ctypes.c_double, ctypes.c_double, _f64p, ctypes.c_int, _f64p,
+                                             ctypes.POINTER(ctypes.c_int32)]),
+    "dv_infomax_read_weights": (ctypes.c_int, [_ctx_p, _f64p]),
+    "dv_infomax_set_weights": (ctypes.c_int, [_ctx_p, _f64p]),
+    "dv_infomax_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _i64p,
+                                       ctypes.POINTER(ctypes.c_int), _i64p]),
+    "dv_infomax_end": (ctypes.c_int, [_ctx_p]),
     "dv_synchronize": (ctypes.c_int, [_ctx_p]),
     "dv_timer_start": (ctypes.c_int, [_ctx_p]),
     "dv_timer_stop": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_float)]),

@@ -246,7 +246,11 @@ class NavBySceneFamiliarity(object):
             for pt in points:
                 self._check_bounds(pt)
             # sensed and ingested on the device; familiar_scenes comes back for the API
-            if getattr(self.familiarity_model, "metric", "sads_hsv") == "ssd":
+            if getattr(self.familiarity_model, "metric", "sads_hsv") == "infomax":
+                # no library: a fresh weight matrix, trained on the views where they are sensed
+                self.familiarity_model.begin(self._engine, self.sensor_dimensions[1], self.sensor_dimensions[0])
+                self.familiar_scenes[...] = self._engine.infomax_train_from_poses(points[:, 0], points[:, 1], view_headings)
+            elif getattr(self.familiarity_model, "metric", "sads_hsv") == "ssd":
                 self.familiar_scenes[...] = self._engine.set_library_u8_from_poses(
                     points[:, 0], points[:, 1], view_headings, self.familiarity_model.channel)
             else:
@@ -290,7 +294,16 @@ class NavBySceneFamiliarity(object):
         view_headings = headings[np.minimum(np.arange(n), n - 2)]
         engine = getattr(self._familiarity_func, "engine", None)
         ssd = str(getattr(self._familiarity_func, "metric", "")).startswith("ssd")
-        if self._engine is not None and engine is self._engine and not ssd:
+        infomax = getattr(self._familiarity_func, "metric", "") == "infomax"
+        if infomax and self._engine is not None and engine is self._engine:
+            # the Infomax model keeps training on the same weights: the new views follow the old ones in the chain
+            for pt in points:
+                self._check_bounds(pt)
+            new_views = self._engine.infomax_train_from_poses(points[:, 0], points[:, 1], view_headings)
+        elif infomax:
+            new_views = np.stack([self.get_sensor_mat(points[i], view_headings[i]) for i in range(n)])
+            engine.infomax_train_u8(np.ascontiguousarray(new_views[..., self._familiarity_func.channel]))
+        elif self._engine is not None and engine is self._engine and not ssd:
             for pt in points:
                 self._check_bounds(pt)
             new_views = self._engine.append_library_from_poses(points[:, 0], points[:, 1], view_headings)
@@ -323,6 +336,8 @@ class NavBySceneFamiliarity(object):
         if func is not None and hasattr(func, "engine"):
             if func.engine is getattr(self, "_engine", None):
                 func.engine.clear_library()          # keep the landscape and the sensor configuration
+                if getattr(func, "metric", "") == "infomax":
+                    func.engine.infomax_end()
             else:
                 func.engine.close()
         if getattr(self, "_metrics_on_device", False) and getattr(self, "_engine", None) is not None:
@@ -551,6 +566,9 @@ class NavBySceneFamiliarity(object):
         if engine is not None and str(getattr(func, "metric", "")).startswith("ssd"):
             self._step_ssd(func, engine, position)
             best_idex = self.last_scored_idex
+        elif engine is not None and getattr(func, "metric", "") == "infomax":
+            self._step_infomax(func, engine, position)
+            best_idex = self.last_scored_idex
         elif engine is not None:
             # one fused device step for all headings: kernel + min-merge + max + argmax (:289-315)
             try:
@@ -681,6 +699,34 @@ class NavBySceneFamiliarity(object):
             self._scene_fam[:] = np.inf
             self._scene_is_inf = True
         self.last_scored_idex = res["best_idex"]
+
+    def _step_infomax(self, func, engine, position):
+        """The heading loop (:289-315) with the Infomax plug-in (util.infomax_familiarity): ONE device call -- sense, score W x for all
+        headings in one pass over the weights, first maximum -- when the sensor model runs on the GPU; with a foreign engine or the host
+        sensor model the patches are sensed here and scored in one call.  familiarity = -sum|W x|.  The model has no per-view score:
+        scene_familiarity is the least familiarity over the headings at every view (what the reference's loop leaves when the plug-in
+        fills its buffer with the one value)."""
+        angles = (self.angle + self.angle_offsets) % (2 * np.pi)
+        try:
+            if engine is self._engine:
+                self._check_bounds(position)
+                best, _ = engine.infomax_sense_step(position[0], position[1], angles, self.angle_familiarity)
+            else:
+                patches = np.stack([self.get_sensor_mat(position, a) for a in angles])
+                planes = np.ascontiguousarray(patches[..., func.channel] if patches.ndim == 4 else patches)
+                engine.infomax_score_u8(planes, self.angle_familiarity)
+                best = int(np.argmax(self.angle_familiarity))
+        except Exception:
+            self._scene_fam[:] = np.inf
+            self._scene_is_inf = True
+            raise
+        if self.track_scene_familiarity:
+            self._scene_fam[:] = np.min(self.angle_familiarity)
+            self._scene_is_inf = False
+        elif not self._scene_is_inf:
+            self._scene_fam[:] = np.inf
+            self._scene_is_inf = True
+        self.last_scored_idex = best
 
     def _move(self, best_idex, fake=False, defer_error=False, begin_next=False, cand=None, begun_next=None):
         """The part of a step after the heading is chosen (:316-329): turn, advance, book-keeping, stop conditions.

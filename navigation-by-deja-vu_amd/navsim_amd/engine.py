@@ -758,3 +758,85 @@ class FamiliarityEngine(object):
         self._check(self._lib.dv_stream_read_gbps(self._ctx, int(n_bytes), int(iters), ctypes.byref(g)),
                     "dv_stream_read_gbps")
         return float(g.value)
+
+    # -- Infomax familiarity model: one layer of weights instead of a library (include/dejavu.h: dv_infomax_*) ----------------
+    def infomax_begin(self, h, w, weights, channel=2, learning_rate=0.01):
+        """weights: float64[n_hidden, h*w], the initial W (drawn by the caller: util.infomax_initial_weights).  Copied to the GPU."""
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+        if weights.ndim != 2 or weights.shape[1] != int(h) * int(w):
+            raise ValueError("weights must be float64[n_hidden, %d], got shape %r" % (int(h) * int(w), weights.shape))
+        self._check(self._lib.dv_infomax_begin(self._ctx, int(h), int(w), int(channel), weights.shape[0], float(learning_rate),
+                                               N.f64ptr(weights)), "dv_infomax_begin")
+        self.infomax_shape = (int(h), int(w))
+        self.infomax_hidden = weights.shape[0]
+
+    def _infomax_planes(self, planes, what):
+        planes = N.as_u8(planes, what)
+        shape = getattr(self, "infomax_shape", None)
+        if planes.ndim == 2:
+            planes = planes[None]
+        if shape is None:
+            return planes if planes.ndim == 3 else planes.reshape(1, 1, -1)      # (no model: the library answers DV_ERR_STATE)
+        if planes.ndim != 3 or tuple(planes.shape[1:]) != shape:
+            raise ValueError("%s must be uint8[n,%d,%d], got shape %r" % ((what,) + shape + (planes.shape,)))
+        return planes
+
+    def infomax_train_u8(self, planes):
+        """One more pass of the learning rule over uint8[n,h,w] planes, in order, on the same W."""
+        planes = self._infomax_planes(planes, "planes")
+        self._check(self._lib.dv_infomax_train_u8(self._ctx, N.u8ptr(planes), planes.shape[0]), "dv_infomax_train_u8")
+
+    def infomax_train_from_poses(self, x, y, angle, want_views=True):
+        """train_from_path for the Infomax plug-in on the device: sense the poses, train on their compared plane; returns
+        familiar_scenes (uint8[n,h,w,3]) when want_views."""
+        x, y, angle = self._pose_arrays(x, y, angle)
+        h, w = self.sensor_shape
+        views = np.empty((len(x), h, w, 3), dtype=np.uint8) if want_views else None
+        self._check_sense(self._lib.dv_infomax_train_from_poses(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), len(x),
+                                                                N.u8ptr(views) if want_views else None),
+                          "dv_infomax_train_from_poses")
+        return views
+
+    def infomax_score_u8(self, planes, out=None):
+        """familiarity = -sum|W x| of each of uint8[n,h,w] planes (or one uint8[h,w]) -> float64[n]."""
+        planes = self._infomax_planes(planes, "planes")
+        if out is None:
+            out = np.empty(planes.shape[0], dtype=np.float64)
+        self._check(self._lib.dv_infomax_score_u8(self._ctx, N.u8ptr(planes), planes.shape[0], N.f64ptr(out)), "dv_infomax_score_u8")
+        return out
+
+    def infomax_sense_step(self, x, y, angles, out_fam=None):
+        """One agent step: sense the heading patches at (x, y), score them, first maximum -> (best_idex, angle_familiarity)."""
+        angles = np.ascontiguousarray(angles, dtype=np.float64).reshape(-1)
+        if out_fam is None:
+            out_fam = np.empty(len(angles), dtype=np.float64)
+        assert out_fam.dtype == np.float64 and out_fam.flags.c_contiguous and out_fam.size == len(angles)
+        best = ctypes.c_int32(-1)
+        self._check_sense(self._lib.dv_infomax_sense_step(self._ctx, float(x), float(y), N.f64ptr(angles), len(angles), N.f64ptr(out_fam),
+                                                          ctypes.byref(best)), "dv_infomax_sense_step")
+        return int(best.value), out_fam
+
+    def infomax_info(self):
+        m, n, fin = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        views, nbytes = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self._lib.dv_infomax_info(self._ctx, ctypes.byref(m), ctypes.byref(n), ctypes.byref(views), ctypes.byref(fin),
+                                              ctypes.byref(nbytes)), "dv_infomax_info")
+        return dict(n_hidden=m.value, n_pixels=n.value, views_trained=views.value, finite=bool(fin.value), bytes=nbytes.value)
+
+    def infomax_read_weights(self):
+        """float64[n_hidden, h*w]: what a user saves (np.save) and hands to infomax_set_weights or infomax_begin later."""
+        info = self.infomax_info()
+        out = np.empty((info["n_hidden"], info["n_pixels"]), dtype=np.float64)
+        self._check(self._lib.dv_infomax_read_weights(self._ctx, N.f64ptr(out)), "dv_infomax_read_weights")
+        return out
+
+    def infomax_set_weights(self, weights):
+        info = self.infomax_info()
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+        if info["n_hidden"] and weights.shape != (info["n_hidden"], info["n_pixels"]):
+            raise ValueError("weights must be float64[%d,%d], got shape %r" % (info["n_hidden"], info["n_pixels"], weights.shape))
+        self._check(self._lib.dv_infomax_set_weights(self._ctx, N.f64ptr(weights)), "dv_infomax_set_weights")
+
+    def infomax_end(self):
+        self._check(self._lib.dv_infomax_end(self._ctx), "dv_infomax_end")
+        self.infomax_shape = None

@@ -19,12 +19,15 @@ single agent works its minimum out when it is read.
 import numpy as np
 
 from .agent import StopNavigationException, OutOfLandscapeBoundsException
+from .util import reject_infomax
 
 
 class NavEnsemble(object):
     def __init__(self, agents):
         if not agents:
             raise ValueError("no agents")
+        for a in agents:
+            reject_infomax(a, "NavEnsemble")
         eng = agents[0]._engine
         if eng is None or any(a._engine is not eng for a in agents):
             raise ValueError("the agents of an ensemble share one engine (NavEnsemble.from_agent)")
@@ -90,6 +93,7 @@ class NavEnsemble(object):
         chem_weights (optional, one per pose): member i scores under chem_weights[i], kept as its `chem_weight`.  When the resident
         library's layout does not store the sums those weights need, it is ingested once more from agent.familiar_scenes, laid out
         for the range of weights (the agent's own weight stays the library's: that of its unweighted steps)."""
+        reject_infomax(agent, "NavEnsemble")
         poses = list(poses)
         weights = None
         if chem_weights is not None:

@@ -291,6 +291,8 @@ def sharded_sads_familiarity(chem_weight, gather, rank, world_size, engine_facto
     use_gpu_sensor=False, track_scene_familiarity=False: the per-view minimum stays sharded).  Calling `func`
     itself (one heading, all views) is not offered: the per-view scores live on different ranks.
     """
+    from .util import reject_infomax
+    reject_infomax(chem_weight, "sharded_sads_familiarity")
     def model(scenes):
         assert 0 <= chem_weight <= 1
         if engine_factory is not None:
@@ -790,6 +792,9 @@ def device_sharded_sads_familiarity(chem_weight, rank, world_size, device, gathe
     """Plug-in for navsim_amd.NavBySceneFamiliarity with library AND sensor model on the GPUs, sharded over the ranks
     of an initialised torch.distributed (nccl) group: `NavBySceneFamiliarity(..., familiarity_model=this,
     track_scene_familiarity=False)` on every rank."""
+    from .util import reject_infomax
+    reject_infomax(chem_weight, "device_sharded_sads_familiarity")
+
     def model(scenes):
         raise NotImplementedError("this model builds its library on the device from the training path "
                                   "(NavBySceneFamiliarity with use_gpu_sensor=True)")

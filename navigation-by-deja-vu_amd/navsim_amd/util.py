@@ -55,6 +55,7 @@ def sads_familiarity(chem_weight=0.0, device=0, exact=False, devices=None):
 
 
 def _group_sads_familiarity(chem_weight, devices):
+    reject_infomax(chem_weight, "FamiliarityGroup")
     def sads_familiarity_internal(scenes):
         assert 0 <= chem_weight <= 1
         from .group import FamiliarityGroup
@@ -138,3 +139,101 @@ def ssd_familiarity(channel=2, device=0):
     ssd_familiarity_internal.metric = "ssd"
     ssd_familiarity_internal.channel = channel
     return ssd_familiarity_internal
+
+
+def reject_infomax(model, what):
+    """The batched and multi-device forms score a library; the Infomax model has none.  Raises ValueError for an Infomax model (the
+    factory's product, its bound func, or an agent that carries one)."""
+    for obj in (model, getattr(model, "familiarity_model", None), getattr(model, "_familiarity_func", None)):
+        if getattr(obj, "metric", None) == "infomax":
+            raise ValueError("%s does not take an Infomax model: it batches or shards a view library, and infomax_familiarity keeps "
+                             "none (step each agent on its own engine)" % what)
+
+
+def infomax_initial_weights(n_hidden, n_pixels, seed=0):
+    """The Infomax model's initial W, float64[n_hidden, n_pixels], drawn on the host: standard normal from
+    np.random.default_rng(seed), then every row has its mean subtracted and is divided by its standard deviation (ddof=0)."""
+    w = np.random.default_rng(seed).standard_normal((int(n_hidden), int(n_pixels)))
+    w -= w.mean(axis=1, keepdims=True)
+    w /= w.std(axis=1, keepdims=True)
+    return w
+
+
+def infomax_familiarity(channel=2, learning_rate=0.01, seed=0, n_hidden=None, device=0, devices=None):
+    """The Infomax network of Baddeley, Graham, Husbands & Philippides (2012) as a familiarity plug-in of the reference's shape
+    (util.pyx:10-25): a fixed-size memory -- one layer of weights W, float64[n_hidden, h*w], trained in one pass over the route's
+    views -- where sads_familiarity and ssd_familiarity keep every view.
+
+    stage 1  infomax_familiarity(channel, learning_rate, seed, n_hidden)   the compared channel of HSV scenes (0 H, 1 S, 2 V), the
+                                                       rule's learning rate, the seed of the initial W and its number of rows
+                                                       (None: as many as the view has pixels)
+    stage 2  model(scenes) -> func                     trains on uint8[F,h,w,3] / uint8[F,h,w], in order, on the device
+    func(scene, fambuf: float64[F])                    writes the ONE value -d(scene) = -sum|W x| into EVERY entry of fambuf: np.max
+                                                       of it is the heading's familiarity, so the reference's loop
+                                                       (NavBySceneFamiliarity.py:301-315) works unchanged -- and the agent's
+                                                       scene_familiarity is therefore constant over the views (the least familiarity
+                                                       over the headings): the model keeps no per-view memory
+    func.max_familiarity = 0.0
+
+    With x = p/255 - mean(p/255) of the view's plane, a training view does h = W x; y = tanh(h); u = h^T W;
+    W <- W + (learning_rate / N) (W - (y + h) u^T).  A learning rate too large for the views makes the rule diverge: training then
+    raises EngineError.  Extras carried by `func`: func.engine (engine.infomax_read_weights() / infomax_set_weights() save and restore
+    the model), func.metric ("infomax"), func.channel.
+    """
+    if devices is not None:
+        raise ValueError("infomax_familiarity runs on one device (device=...): FamiliarityGroup cuts a view library over several, and "
+                         "this model keeps none")
+    if channel not in (0, 1, 2):
+        raise ValueError("channel must be 0 (H), 1 (S) or 2 (V), got %r" % (channel,))
+    if not (isinstance(learning_rate, (int, float, np.floating, np.integer)) and learning_rate > 0 and np.isfinite(learning_rate)):
+        raise ValueError("learning_rate must be a positive number, got %r" % (learning_rate,))
+    if n_hidden is not None and not (isinstance(n_hidden, (int, np.integer)) and n_hidden >= 1):
+        raise ValueError("n_hidden must be a positive integer or None, got %r" % (n_hidden,))
+
+    def plane(a, lead):
+        a = np.asarray(a)
+        if a.ndim == lead + 3:
+            a = a[..., channel]
+        if a.ndim != lead + 2:
+            raise ValueError("scene array has shape %r" % (a.shape,))
+        return np.ascontiguousarray(a)
+
+    def begin(engine, h, w):
+        """A fresh model of h x w views on `engine` (the agent calls this before it trains from poses)."""
+        n = int(h) * int(w)
+        engine.infomax_begin(h, w, infomax_initial_weights(n if n_hidden is None else n_hidden, n, seed), channel, learning_rate)
+
+    def bind(engine, scenes=None):
+        def func(scene, fambuf):
+            if not (isinstance(fambuf, np.ndarray) and fambuf.dtype == np.float64):
+                raise ValueError("Buffer dtype mismatch for fambuf, expected 'double'")
+            fambuf[...] = engine.infomax_score_u8(plane(scene, 0))[0]
+
+        func.max_familiarity = 0.0
+        func.engine = engine
+        func.metric = "infomax"
+        func.channel = channel
+        return func
+
+    def infomax_familiarity_internal(scenes):
+        scenes = np.asarray(scenes)
+        if scenes.dtype != np.uint8:
+            raise ValueError("Buffer dtype mismatch, expected 'uint8_t' but got '%s'" % scenes.dtype)
+        planes = plane(scenes, 1)
+        engine = FamiliarityEngine(device=device)
+        try:
+            begin(engine, planes.shape[1], planes.shape[2])
+            engine.infomax_train_u8(planes)
+        except Exception:
+            engine.close()
+            raise
+        return bind(engine)
+
+    # hooks for navsim_amd.NavBySceneFamiliarity (landscape, sensor model and training on the GPU: see sads_familiarity)
+    infomax_familiarity_internal.make_engine = lambda: FamiliarityEngine(device=device)
+    infomax_familiarity_internal.from_engine = bind
+    infomax_familiarity_internal.begin = begin
+    infomax_familiarity_internal.metric = "infomax"
+    infomax_familiarity_internal.channel = channel
+    infomax_familiarity_internal.learning_rate = learning_rate
+    return infomax_familiarity_internal

@@ -1,0 +1,143 @@
+#!/usr/bin/env python3
+"""Times the Infomax familiarity model (navsim_amd.infomax_familiarity; include/dejavu.h: dv_infomax_*) on GPU 0 and writes
+profiles/infomax_time.json.
+
+    python tools/infomax_time.py [--sides 32,64] [--views 400] [--calls 200] [--reps 5] [--out profiles/infomax_time.json]
+
+Per sensor side s (views of s x s, N = M = s*s): microseconds per training view (a dv_infomax_train_u8 call over --views views, the
+upload and the x preparation included, divided by the views) and per scoring call (dv_infomax_score_u8: upload, x preparation, the
+pass over W and the read-back) for 16 and for 60 headings, each the median of --reps timed windows after a warm-up of the same
+shape, from a hipEvent pair on the context's stream (dv_timer_start / dv_timer_stop) with the spread (min, max) beside it.  Beside
+each figure its byte floor -- 3*8*M*N bytes per training view (W read twice, written once), 8*M*N per scoring call -- over the box's
+own stream probe (dv_stream_read_gbps), and the fraction of that floor reached.  The same quantities for the NumPy restatement of
+the model (tests/helpers_infomax.py) on the host's CPU, wall clock.
+
+Every GPU measurement runs in a child process of its own under a time limit, and nothing more is started on the GPU after one
+that failed."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "navigation-by-deja-vu_amd"))
+sys.path.insert(0, ROOT)
+
+HEADINGS = (16, 60)                                               # 60: the reference's default n_test_angles
+
+
+def views_of(side, n, seed=1):
+    from tests import helpers_infomax as H
+    return H.route_views(seed, n, side, side)
+
+
+def spread(samples):
+    return dict(median=round(float(np.median(samples)), 3), min=round(float(min(samples)), 3), max=round(float(max(samples)), 3))
+
+
+def gpu_child(side, n_views, n_calls, reps, eta):
+    """One size on the GPU -> one JSON line on stdout."""
+    from navsim_amd import FamiliarityEngine
+    from navsim_amd.util import infomax_initial_weights
+    N = side * side
+    eng = FamiliarityEngine(device=0)
+    out = dict(side=side, N=N, M=N, weight_bytes=8 * N * N)
+    out["stream_probe_gbps"] = round(eng.stream_read_gbps(1 << 30, 10), 1)
+    views = views_of(side, n_views)
+    W0 = infomax_initial_weights(N, N, 0)
+
+    def train_once():
+        eng.infomax_begin(side, side, W0, 2, eta)
+        eng.timer_start()
+        eng.infomax_train_u8(views)
+        return eng.timer_stop() * 1e3 / n_views               # us per view
+
+    train_once()                                                  # warm-up (code load, clocks, the staging buffers)
+    out["train_us_per_view"] = spread([train_once() for _ in range(reps)])
+    out["views_per_window"] = n_views
+    assert eng.infomax_info()["finite"]
+    for A in HEADINGS:
+        patches = views_of(side, A, seed=2)
+        fam = np.empty(A)
+
+        def score_window():
+            eng.timer_start()
+            for _ in range(n_calls):
+                eng.infomax_score_u8(patches, fam)
+            return eng.timer_stop() * 1e3 / n_calls           # us per call
+        score_window()
+        out["score_us_per_call_A%d" % A] = spread([score_window() for _ in range(reps)])
+    out["calls_per_window"] = n_calls
+    eng.close()
+    print(json.dumps(out))
+
+
+def cpu_row(side, n_views, n_calls, eta):
+    """The NumPy restatement on this host: wall clock."""
+    from tests import helpers_infomax as H
+    N = side * side
+    views = views_of(side, n_views)
+    W0 = H.initial_weights(N, N, 0)
+    t0 = time.perf_counter()
+    W = H.train(W0, views, eta=eta)
+    t1 = time.perf_counter()
+    row = dict(train_us_per_view=round((t1 - t0) * 1e6 / n_views, 1), views=n_views)
+    for A in HEADINGS:
+        patches = views_of(side, A, seed=2)
+        t0 = time.perf_counter()
+        for _ in range(n_calls):
+            H.familiarity(W, patches)
+        row["score_us_per_call_A%d" % A] = round((time.perf_counter() - t0) * 1e6 / n_calls, 1)
+    return row
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sides", default="32,64")
+    ap.add_argument("--views", type=int, default=400)
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--learning-rate", type=float, default=0.001,
+                    help="the rule must stay finite on the tool's 5-level noise views: 0.01 overflows at 64x64 (the time does not depend on it)")
+    ap.add_argument("--limit", type=int, default=240, help="seconds allowed to each GPU child")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "infomax_time.json"))
+    ap.add_argument("--child", type=int, default=0, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:
+        gpu_child(args.child, args.views, args.calls, args.reps, args.learning_rate)
+        return 0
+    result = dict(tool="tools/infomax_time.py", timer="hipEvent pair (dv_timer_start/stop), median of %d windows after a warm-up" % args.reps,
+                  learning_rate=args.learning_rate, sizes=[])
+    for side in [int(x) for x in args.sides.split(",")]:
+        cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child", str(side), "--views", str(args.views),
+               "--calls", str(args.calls), "--reps", str(args.reps), "--learning-rate", str(args.learning_rate)]
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, universal_newlines=True)
+        if p.returncode != 0:
+            print("GPU measurement of side %d ended with status %d: nothing more is run" % (side, p.returncode), file=sys.stderr)
+            return p.returncode
+        row = json.loads(p.stdout.strip().splitlines()[-1])
+        gbps = row["stream_probe_gbps"]
+        M = N = row["N"]
+        floors = dict(train=3 * 8 * M * N, score=8 * M * N)
+        row["train_floor_bytes_per_view"] = floors["train"]
+        row["score_floor_bytes_per_call"] = floors["score"]
+        for key, kind in [("train_us_per_view", "train")] + [("score_us_per_call_A%d" % A, "score") for A in HEADINGS]:
+            floor_us = floors[kind] / (gbps * 1e3)
+            row[key]["floor_us_at_probe"] = round(floor_us, 3)
+            row[key]["fraction_of_probe"] = round(floor_us / row[key]["median"], 4)
+        row["numpy_cpu"] = cpu_row(side, min(args.views, 40), min(args.calls, 10), args.learning_rate)
+        result["sizes"].append(row)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print(json.dumps(result))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -550,6 +550,19 @@ int dv_diffuse(dv_ctx *ctx, const double *init, int n, int64_t nstep, double c, 
  *   score_u8         familiarity[a] = -d of each of uint8[n, h, w] planes, any n >= 1 (64 per pass over W).
  *   sense_step       one agent step: senses the n_headings patches at (x, y), scores their `channel` plane and takes the first
  *                    maximum of angle_fam (np.argmax).  Any n_headings >= 1.  DV_ERR_INDEX like dv_sense_step.
+ *   dv_batch_infomax_step_u8 / dv_batch_infomax_sense_step   an ensemble's step.  (The dv_infomax_ prefix is kept to the single
+ *                    model's nine calls; the ensemble's two are named apart from it.)  n_agents members of n_headings headings
+ *                    each share the one W, their n_agents * n_headings patches being columns of one H = W X (member i owns
+ *                    columns [i * n_headings, (i + 1) * n_headings)).  batch_infomax_step_u8 scores uploaded planes
+ *                    uint8[n_agents][n_headings][h][w]; batch_infomax_sense_step senses member i at (x[i], y[i]) along
+ *                    angles[i][0 .. n_headings).  angle_fam[n_agents][n_headings] and best_heading[n_agents] (each member's first
+ *                    maximum, np.argmax) come back from ONE enqueue and ONE wait, whatever n_agents is; the sums, the negation
+ *                    and the maxima are taken on the device.  Any n_agents >= 1 and n_headings >= 1 (also > 64).  A column's
+ *                    value has the bits score_u8 / sense_step give the same patch.  batch_infomax_sense_step does not fail for
+ *                    a footprint that leaves the landscape: flags[i] (uint32[n_agents]) carries DV_RES_SENSE_ERROR for such a
+ *                    member, its best_heading is -1 and its row of angle_fam unspecified; the other members' results are
+ *                    untouched (as dv_sense_step_batch).  State, sensor-shape and non-finite-weight errors as sense_step;
+ *                    DV_ERR_INVALID for a NULL pointer, n_agents < 1 or n_headings < 1.
  *   read_weights / set_weights   copy float64[n_hidden * h * w] out and in: what a user saves and restores.
  *   info             n_hidden, n_pixels, views trained since begin, whether W is finite (0 without a model), bytes of W; any
  *                    pointer may be NULL.
@@ -562,6 +575,9 @@ int dv_infomax_train_from_poses(dv_ctx *ctx, const double *x, const double *y, c
 int dv_infomax_score_u8(dv_ctx *ctx, const uint8_t *planes, int n, double *familiarity);
 int dv_infomax_sense_step(dv_ctx *ctx, double x, double y, const double *angles, int n_headings, double *angle_fam,
                           int32_t *best_heading);
+int dv_batch_infomax_step_u8(dv_ctx *ctx, const uint8_t *planes, int n_agents, int n_headings, double *angle_fam, int32_t *best_heading);
+int dv_batch_infomax_sense_step(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
+                                double *angle_fam, int32_t *best_heading, uint32_t *flags);
 int dv_infomax_read_weights(dv_ctx *ctx, double *out);
 int dv_infomax_set_weights(dv_ctx *ctx, const double *weights);
 int dv_infomax_info(dv_ctx *ctx, int *n_hidden, int *n_pixels, int64_t *views_trained, int *finite, int64_t *bytes);

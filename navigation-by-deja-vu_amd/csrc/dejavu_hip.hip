@@ -299,6 +299,13 @@ struct dv_ctx {
     double* im_dpart = nullptr;               // [row tiles][64]
     double* im_d = nullptr;                   // [64]
     int* im_flag = nullptr;                   // k_im_finite's answer
+    // the batch calls' buffers (dv_batch_infomax_step_u8 / dv_batch_infomax_sense_step): made at first use, grown when a call is larger
+    double* im_bx = nullptr;                  // [slab columns][N]
+    double* im_bdpart = nullptr;              // [row tiles][columns padded to 64]
+    unsigned char* im_bout = nullptr;         // angle_fam[C] doubles, best[n_agents] int32, flags[n_agents] uint32: one copy to the host
+    int* im_perr = nullptr;                   // [C]: k_sense_each's word per pose
+    size_t im_bx_cap = 0, im_bdpart_cap = 0, im_bout_cap = 0, im_perr_cap = 0;   // bytes
+    std::vector<unsigned char> im_hout;       // where that copy lands
     int im_M = 0, im_N = 0, im_hh = 0, im_ww = 0, im_channel = 2;
     double im_eta = 0.0;
     int64_t im_views = 0;                     // views trained on since dv_infomax_begin

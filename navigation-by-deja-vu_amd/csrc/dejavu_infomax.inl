@@ -19,6 +19,10 @@
 //                 (v_mfma_f64_16x16x4_f64): a workgroup of 8 waves owns 16 rows of W, the waves take the 16-column chunks of those rows
 //                 round-robin, their accumulators are added in wave order through LDS, then |.| is summed over the 16 rows in order
 //   k_im_dfinish  d_a = the row tiles' partial sums (one wave per heading: strided partial sums, then the butterfly)
+//   k_im_score_cols  an ensemble's step (dv_infomax_*_batch): k_im_score's body over a grid of row tiles x blocks of 64 columns, the
+//                 members' headings being one flat list of columns (member i owns [i A, (i + 1) A)); dpart is [row tiles][C padded to 64]
+//   k_im_decide   one workgroup per member: each of its columns summed as k_im_dfinish sums it and negated, then the member's first
+//                 maximum and, from k_sense_each's word per pose, its DV_RES_SENSE_ERROR flag
 //   k_im_finite   is every weight finite? (a too-large learning rate makes the rule diverge)
 //
 // A heading's column of H does not depend on how many headings ride with it (an MFMA result element is its own dot product), which
@@ -140,12 +144,12 @@ static constexpr int kImHeadings = 64;                       // headings of one 
 // HT: 16-heading tiles computed (the call's headings, rounded up).  X: [A][N], heading-major.  dpart: [row tiles][kImHeadings].
 // Lane l = (r = l & 15, g = l >> 4) feeds row r of the workgroup's 16 rows of W as the MFMA's A operand and heading r of each tile as
 // its B operand, element k = chunk * 16 + g * 4 + j in MFMA j of 4; accumulator register q of tile t is H[row g + 4 q][heading 16 t + r].
+// sred: [16][HT * 16] doubles of LDS; dout: where the tile's HT * 16 partial sums go.
 template <int HT, bool VEC>
-__global__ __launch_bounds__(kImScoreWaves * 64) void k_im_score(const double* __restrict__ W, const double* __restrict__ X, int M, int N, int A,
-                                                                 double* __restrict__ dpart) {
-    __shared__ double sred[16][HT * 16];
+__device__ __forceinline__ void im_score_tile(const double* __restrict__ W, const double* __restrict__ X, int M, int N, int A, int tile,
+                                              double* __restrict__ sred, double* __restrict__ dout) {
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 15, g = lane >> 4;
-    const int row = (int)blockIdx.x * 16 + r;
+    const int row = tile * 16 + r;
     const bool row_ok = row < M;
     const double* wrow = W + (size_t)(row_ok ? row : 0) * (size_t)N;
     const double* xrow[HT];
@@ -189,7 +193,7 @@ __global__ __launch_bounds__(kImScoreWaves * 64) void k_im_score(const double* _
             for (int t = 0; t < HT; ++t) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    double* s = &sred[g + 4 * q][t * 16 + r];
+                    double* s = &sred[(g + 4 * q) * (HT * 16) + t * 16 + r];
                     *s = w == 0 ? acc[t][q] : *s + acc[t][q];
                 }
             }
@@ -198,9 +202,32 @@ __global__ __launch_bounds__(kImScoreWaves * 64) void k_im_score(const double* _
     }
     if (tid < HT * 16) {
         double s = 0.0;
-        for (int rr = 0; rr < 16; ++rr) s += fabs(sred[rr][tid]);         // (rows past M hold zeros)
-        dpart[(size_t)blockIdx.x * kImHeadings + tid] = s;
+        for (int rr = 0; rr < 16; ++rr) s += fabs(sred[rr * (HT * 16) + tid]);   // (rows past M hold zeros)
+        dout[tid] = s;
     }
+}
+
+template <int HT, bool VEC>
+__global__ __launch_bounds__(kImScoreWaves * 64) void k_im_score(const double* __restrict__ W, const double* __restrict__ X, int M, int N, int A,
+                                                                 double* __restrict__ dpart) {
+    __shared__ double sred[16 * HT * 16];
+    im_score_tile<HT, VEC>(W, X, M, N, A, (int)blockIdx.x, sred, dpart + (size_t)blockIdx.x * kImHeadings);
+}
+
+// C columns (X: [C][N]) in blocks of kImHeadings: workgroup (x, y) takes row tile x of column block y with the body above, so a column
+// has the sums k_im_score gives it however many ride with it.  dpart: [row tiles][cpad], cpad = the call's columns padded to 64; the
+// last block computes only the 16-column tiles it needs.
+template <bool VEC>
+__global__ __launch_bounds__(kImScoreWaves * 64) void k_im_score_cols(const double* __restrict__ W, const double* __restrict__ X, int M, int N, int C,
+                                                                      long long cpad, double* __restrict__ dpart) {
+    __shared__ double sred[16 * kImHeadings];
+    const int c0 = (int)blockIdx.y * kImHeadings;
+    const int nc = C - c0 < kImHeadings ? C - c0 : kImHeadings;          // (uniform over the workgroup)
+    const double* Xb = X + (size_t)c0 * (size_t)N;
+    double* dout = dpart + (size_t)blockIdx.x * (size_t)cpad + c0;
+    if (nc <= 16) im_score_tile<1, VEC>(W, Xb, M, N, nc, (int)blockIdx.x, sred, dout);
+    else if (nc <= 32) im_score_tile<2, VEC>(W, Xb, M, N, nc, (int)blockIdx.x, sred, dout);
+    else im_score_tile<4, VEC>(W, Xb, M, N, nc, (int)blockIdx.x, sred, dout);
 }
 
 // one wave per heading
@@ -212,6 +239,42 @@ __global__ __launch_bounds__(64) void k_im_dfinish(const double* __restrict__ dp
     if (lane == 0) d[blockIdx.x] = s;
 }
 
+// One workgroup of 4 waves per member i of A columns.  fam[i][a] = -(column i A + a summed over the row tiles in k_im_dfinish's order);
+// best[i] = the first maximum of the row; perr (nullptr: the patches were uploaded) holds k_sense_each's word per column: a member
+// with one set gets best -1 and kResSenseError, its row is whatever its stale patches scored.
+__global__ __launch_bounds__(256) void k_im_decide(const double* __restrict__ dpart, int n_tiles, long long cpad, int A, const int* __restrict__ perr,
+                                                   double* __restrict__ fam, int* __restrict__ best, unsigned* __restrict__ flags) {
+    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+    const size_t col0 = (size_t)blockIdx.x * (size_t)A;
+    double* row = fam + col0;
+    for (int a = wave; a < A; a += 4) {
+        double s = 0.0;
+        for (int t = lane; t < n_tiles; t += 64) s += dpart[(size_t)t * (size_t)cpad + col0 + a];
+        s = im_wave_sum(s);
+        if (lane == 0) row[a] = -s;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    // a lane's first maximum over its columns in rising order, then the lanes' maxima: the larger value, the lower column of equals
+    double bv = 0.0;
+    int bi = -1, bad = 0;
+    for (int a = lane; a < A; a += 64) {
+        const double v = row[a];
+        if (bi < 0 || v > bv) { bv = v; bi = a; }
+        if (perr) bad |= perr[col0 + a];
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_xor(bv, off);
+        const int oi = __shfl_xor(bi, off);
+        bad |= __shfl_xor(bad, off);
+        if (oi >= 0 && (bi < 0 || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+    }
+    if (lane == 0) {
+        best[blockIdx.x] = bad ? -1 : bi;
+        flags[blockIdx.x] = bad ? kResSenseError : 0u;
+    }
+}
+
 }  // namespace dv
 
 static constexpr long long kImMaxPixels = 1 << 20;            // N of a view
@@ -220,6 +283,8 @@ static constexpr size_t kImStageBytes = 64u << 20;            // x vectors and u
 static void infomax_free(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
     F(c->im_W); F(c->im_h[0]); F(c->im_h[1]); F(c->im_u); F(c->im_upart); F(c->im_xs); F(c->im_sx); F(c->im_dpart); F(c->im_d); F(c->im_flag);
+    F(c->im_bx); F(c->im_bdpart); F(c->im_bout); F(c->im_perr);
+    c->im_bx_cap = c->im_bdpart_cap = c->im_bout_cap = c->im_perr_cap = 0;
     c->im_M = c->im_N = c->im_hh = c->im_ww = 0;
     c->im_xs_cap = 0;
     c->im_views = 0;
@@ -452,6 +517,122 @@ extern "C" int dv_infomax_sense_step(dv_ctx* c, double x, double y, const double
     }
     *best_heading = best;
     return DV_OK;
+}
+
+// ---- ensembles: every member's headings in one enqueue and one wait ----------------------------------------------------------
+static constexpr long long kImSlabColsMax = 1 << 20;          // columns of one scoring launch (its grid's y extent: 16384 blocks)
+
+// Device buffers of the batch calls: allocated at first use, grown only when a call needs more.
+template <class T>
+static int infomax_grow(dv_ctx* c, T*& p, size_t& cap, size_t bytes) {
+    if (bytes <= cap) return DV_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    HIP_TRY(c, hipMalloc((void**)&p, bytes));
+    cap = bytes;
+    return DV_OK;
+}
+
+// planes != nullptr: uploaded uint8[n_agents][A][h][w]; else the poses (x[i], y[i], angles[i][a]) are sensed.  The unfused pair (sense,
+// then k_im_prep over the slab's patches in one launch) keeps x's bits by construction.  Columns go through X in slabs of at most
+// kImStageBytes, back to back on the stream; the host waits once, for the one copy of the packed results.
+static int infomax_batch(dv_ctx* c, const char* who, const uint8_t* planes, const double* x, const double* y, const double* angles, int n_agents,
+                         int A, double* angle_fam, int32_t* best_heading, uint32_t* flags) {
+    const long long C = (long long)n_agents * A;
+    if (C > 0x7fffffffll - kImHeadings) return fail(c, DV_ERR_INVALID, "%s: %d agents x %d headings are too many columns", who, n_agents, A);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t N = (size_t)c->im_N;
+    const int M = c->im_M, tiles = (M + 15) / 16;
+    const long long cpad = (C + kImHeadings - 1) / kImHeadings * kImHeadings;
+    long long slab = (long long)(kImStageBytes / (N * sizeof(double))) / kImHeadings * kImHeadings;
+    if (slab < kImHeadings) slab = kImHeadings;
+    if (slab > kImSlabColsMax) slab = kImSlabColsMax;
+    if (slab > cpad) slab = cpad;
+    const size_t fam_bytes = (size_t)C * sizeof(double), out_bytes = fam_bytes + (size_t)n_agents * 8;
+    int rc = infomax_grow(c, c->im_bx, c->im_bx_cap, (size_t)slab * N * sizeof(double));
+    if (!rc) rc = infomax_grow(c, c->im_bdpart, c->im_bdpart_cap, (size_t)tiles * (size_t)cpad * sizeof(double));
+    if (!rc) rc = infomax_grow(c, c->im_bout, c->im_bout_cap, out_bytes);
+    if (!rc && !planes) rc = infomax_grow(c, c->im_perr, c->im_perr_cap, (size_t)C * sizeof(int));
+    if (!rc) rc = ensure_sense_buffer(c, (size_t)slab * N * (planes ? 1 : 3));
+    if (rc) return rc;
+    if (!planes) {
+        if ((size_t)C > c->poses_cap) {
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            if (c->d_poses) (void)hipFree(c->d_poses);
+            c->d_poses = nullptr;
+            c->poses_cap = 0;
+            HIP_TRY(c, hipMalloc(&c->d_poses, (size_t)C * sizeof(Pose)));
+            c->poses_cap = (size_t)C;
+        }
+        c->h_poses.resize((size_t)C);
+        for (int i = 0; i < n_agents; ++i)
+            for (int a = 0; a < A; ++a) c->h_poses[(size_t)i * A + a] = make_pose(x[i], y[i], angles[(size_t)i * A + a]);
+        HIP_TRY(c, hipMemsetAsync(c->im_perr, 0, (size_t)C * sizeof(int), c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_poses, c->h_poses.data(), (size_t)C * sizeof(Pose), hipMemcpyHostToDevice, c->stream));
+    }
+    for (long long c0 = 0; c0 < C; c0 += slab) {
+        const long long nc = C - c0 < slab ? C - c0 : slab;
+        if (planes) {
+            HIP_TRY(c, hipMemcpyAsync(c->d_sense, planes + (size_t)c0 * N, (size_t)nc * N, hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(k_im_prep, dim3((unsigned)nc), dim3(256), 0, c->stream, c->d_sense, (long long)N, 1, 0, c->im_N, c->im_bx);
+        } else {
+            const long long total = nc * (long long)N;
+            hipLaunchKernelGGL(k_sense_each, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, c->d_land, c->d_poses + c0, (int)nc,
+                               c->sensor, c->d_lut, c->d_sense, c->im_perr + c0);
+            HIP_TRY(c, hipGetLastError());
+            hipLaunchKernelGGL(k_im_prep, dim3((unsigned)nc), dim3(256), 0, c->stream, c->d_sense, 3ll * (long long)N, 3, c->im_channel, c->im_N,
+                               c->im_bx);
+        }
+        HIP_TRY(c, hipGetLastError());
+        const dim3 grid((unsigned)tiles, (unsigned)((nc + kImHeadings - 1) / kImHeadings));
+        if (N % 4 == 0)
+            hipLaunchKernelGGL((k_im_score_cols<true>), grid, dim3(kImScoreWaves * 64), 0, c->stream, c->im_W, c->im_bx, M, c->im_N, (int)nc, cpad,
+                               c->im_bdpart + c0);
+        else
+            hipLaunchKernelGGL((k_im_score_cols<false>), grid, dim3(kImScoreWaves * 64), 0, c->stream, c->im_W, c->im_bx, M, c->im_N, (int)nc, cpad,
+                               c->im_bdpart + c0);
+        HIP_TRY(c, hipGetLastError());
+    }
+    double* d_fam = reinterpret_cast<double*>(c->im_bout);
+    int* d_best = reinterpret_cast<int*>(c->im_bout + fam_bytes);
+    unsigned* d_flags = reinterpret_cast<unsigned*>(c->im_bout + fam_bytes + (size_t)n_agents * 4);
+    hipLaunchKernelGGL(k_im_decide, dim3((unsigned)n_agents), dim3(256), 0, c->stream, c->im_bdpart, tiles, cpad, A, planes ? nullptr : c->im_perr,
+                       d_fam, d_best, d_flags);
+    HIP_TRY(c, hipGetLastError());
+    c->im_hout.resize(out_bytes);
+    HIP_TRY(c, hipMemcpyAsync(c->im_hout.data(), c->im_bout, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    std::memcpy(angle_fam, c->im_hout.data(), fam_bytes);
+    std::memcpy(best_heading, c->im_hout.data() + fam_bytes, (size_t)n_agents * 4);
+    if (flags) std::memcpy(flags, c->im_hout.data() + fam_bytes + (size_t)n_agents * 4, (size_t)n_agents * 4);
+    return DV_OK;
+}
+
+extern "C" int dv_batch_infomax_step_u8(dv_ctx* c, const uint8_t* planes, int n_agents, int n_headings, double* angle_fam, int32_t* best_heading) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = infomax_need(c, "dv_batch_infomax_step_u8");
+    if (rc) return rc;
+    if (!planes || !angle_fam || !best_heading || n_agents < 1 || n_headings < 1)
+        return fail(c, DV_ERR_INVALID, "dv_batch_infomax_step_u8: NULL argument, n_agents < 1 or n_headings < 1");
+    if (!c->im_finite) return infomax_not_finite(c, "dv_batch_infomax_step_u8");
+    return infomax_batch(c, "dv_batch_infomax_step_u8", planes, nullptr, nullptr, nullptr, n_agents, n_headings, angle_fam, best_heading, nullptr);
+}
+
+extern "C" int dv_batch_infomax_sense_step(dv_ctx* c, const double* x, const double* y, const double* angles, int n_agents, int n_headings,
+                                           double* angle_fam, int32_t* best_heading, uint32_t* flags) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = infomax_need(c, "dv_batch_infomax_sense_step");
+    if (rc) return rc;
+    if (!x || !y || !angles || !angle_fam || !best_heading || !flags || n_agents < 1 || n_headings < 1)
+        return fail(c, DV_ERR_INVALID, "dv_batch_infomax_sense_step: NULL argument, n_agents < 1 or n_headings < 1");
+    if (!c->have_sensor) return fail(c, DV_ERR_STATE, "sensor not configured");
+    if (c->sensor.sh != c->im_hh || c->sensor.sw != c->im_ww)
+        return fail(c, DV_ERR_INVALID, "dv_batch_infomax_sense_step: the sensor is %dx%d but the model takes %dx%d views", c->sensor.sw, c->sensor.sh,
+                    c->im_ww, c->im_hh);
+    if (!c->im_finite) return infomax_not_finite(c, "dv_batch_infomax_sense_step");
+    return infomax_batch(c, "dv_batch_infomax_sense_step", nullptr, x, y, angles, n_agents, n_headings, angle_fam, best_heading, flags);
 }
 
 extern "C" int dv_infomax_read_weights(dv_ctx* c, double* out) {

@@ -2451,15 +2451,18 @@ __device__ __forceinline__ bool sense_fetch(const unsigned char* __restrict__ la
     return true;
 }
 
-// One thread per sensor pixel of every pose.  out: uint8[n][sh][sw][3].
-__global__ void k_sense(const unsigned char* __restrict__ land, const Pose* __restrict__ poses, int n, SensorCfg g,
-                        const unsigned char* __restrict__ lut, unsigned char* __restrict__ out, int* __restrict__ err) {
+// One thread per sensor pixel of every pose.  out: uint8[n][sh][sw][3].  EACH: err is int[n], a word per pose (an ensemble must know
+// whose footprint left the landscape); else one word for all poses.
+template <bool EACH>
+__device__ __forceinline__ void sense_thread(const unsigned char* __restrict__ land, const Pose* __restrict__ poses, int n, const SensorCfg& g,
+                                             const unsigned char* __restrict__ lut, unsigned char* __restrict__ out, int* __restrict__ err) {
     const long long total = (long long)n * g.sh * g.sw;
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= total) return;
     const int bj = (int)(t % g.sw);
     const int bi = (int)((t / g.sw) % g.sh);
-    const Pose p = poses[t / ((long long)g.sw * g.sh)];
+    const long long pose = t / ((long long)g.sw * g.sh);
+    const Pose p = poses[pose];
     const int nblk = g.pw * g.ph;
     unsigned oh = 0, os = 0, ov = 0;
     bool ok = true;
@@ -2489,12 +2492,27 @@ __global__ void k_sense(const unsigned char* __restrict__ land, const Pose* __re
             ov = (unsigned)(long long)round((double)vsum / (double)nblk);
         }
     }
-    if (!ok) { atomicOr(err, 1); return; }
+    if (!ok) {
+        if (EACH) err[pose] = 1;                                // (every writer stores the same word)
+        else atomicOr(err, 1);
+        return;
+    }
     oh = lut[oh]; os = lut[256 + os]; ov = lut[512 + ov];
     const int mid = g.sw / 2;
     if (bj >= mid - g.mask_n && bj < mid + g.mask_n) { oh = 0; os = 0; ov = 0; }
     unsigned char* o = out + t * 3;
     o[0] = (unsigned char)oh; o[1] = (unsigned char)os; o[2] = (unsigned char)ov;
+}
+
+__global__ void k_sense(const unsigned char* __restrict__ land, const Pose* __restrict__ poses, int n, SensorCfg g,
+                        const unsigned char* __restrict__ lut, unsigned char* __restrict__ out, int* __restrict__ err) {
+    sense_thread<false>(land, poses, n, g, lut, out, err);
+}
+
+// k_sense with the error recorded per pose: err is int[n], zeroed by the caller.
+__global__ void k_sense_each(const unsigned char* __restrict__ land, const Pose* __restrict__ poses, int n, SensorCfg g,
+                             const unsigned char* __restrict__ lut, unsigned char* __restrict__ out, int* __restrict__ err) {
+    sense_thread<true>(land, poses, n, g, lut, out, err);
 }
 
 // One sensor pixel of one pose (k_patch_prep senses the headings' patches with it, four pixels per thread).

@@ -108,6 +108,8 @@ _ctx_p = ctypes.c_void_p
 _u8p = ctypes.POINTER(ctypes.c_uint8)
 _f64p = ctypes.POINTER(ctypes.c_double)
 _i64p = ctypes.POINTER(ctypes.c_int64)
+_i32p = ctypes.POINTER(ctypes.c_int32)
+_u32p = ctypes.POINTER(ctypes.c_uint32)
 
 # name -> (restype, argtypes); every symbol include/dejavu.h declares
 PROTOTYPES = {
@@ -228,6 +230,8 @@ PROTOTYPES = {
     "dv_infomax_score_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, _f64p]),
     "dv_infomax_sense_step": (ctypes.c_int, [_ctx_p, ctypes.c_double, ctypes.c_double, _f64p, ctypes.c_int, _f64p,
                                              ctypes.POINTER(ctypes.c_int32)]),
+    "dv_batch_infomax_step_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, _f64p, _i32p]),
+    "dv_batch_infomax_sense_step": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _f64p, _i32p, _u32p]),
     "dv_infomax_read_weights": (ctypes.c_int, [_ctx_p, _f64p]),
     "dv_infomax_set_weights": (ctypes.c_int, [_ctx_p, _f64p]),
     "dv_infomax_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _i64p,

@@ -51,6 +51,19 @@ class BatchResults(object):
         return (self[i] for i in range(self.n))
 
 
+class InfomaxBatchResults(object):
+    """An ensemble step of the Infomax model (dv_batch_infomax_step_u8 / dv_batch_infomax_sense_step), in BatchResults' shape for
+    callers that move agents: angle_familiarity[n, A] (float64), best_idex[n] (int32; -1 for a member whose footprint left the
+    landscape) and flags[n] (uint32; DV_RES_SENSE_ERROR = 16 for such a member, whose row is unspecified)."""
+
+    def __init__(self, angle_familiarity, best_idex, flags):
+        self.n, self.A = angle_familiarity.shape
+        self.angle_familiarity, self.best_idex, self.flags = angle_familiarity, best_idex, flags
+
+    def __len__(self):
+        return self.n
+
+
 class FamiliarityEngine(object):
     """Scores sensor patches against a stored-view library resident in HBM.
 
@@ -815,6 +828,37 @@ class FamiliarityEngine(object):
         self._check_sense(self._lib.dv_infomax_sense_step(self._ctx, float(x), float(y), N.f64ptr(angles), len(angles), N.f64ptr(out_fam),
                                                           ctypes.byref(best)), "dv_infomax_sense_step")
         return int(best.value), out_fam
+
+    def infomax_step_batch_u8(self, planes):
+        """An ensemble's step on uploaded patches: uint8[n, A, h, w] planes, member i's A headings in row i -> InfomaxBatchResults (every
+        member's familiarities and first maximum from one device call; the flags are 0)."""
+        planes = N.as_u8(planes, "planes")
+        if planes.ndim != 4:
+            raise ValueError("planes must be uint8[n,A,h,w], got shape %r" % (planes.shape,))
+        n, A = planes.shape[:2]
+        flat = self._infomax_planes(planes.reshape((n * A,) + planes.shape[2:]), "planes") if n * A else planes
+        fam = np.empty((n, A), dtype=np.float64)
+        best = np.full(n, -1, dtype=np.int32)
+        self._check(self._lib.dv_batch_infomax_step_u8(self._ctx, N.u8ptr(flat), n, A, N.f64ptr(fam), best.ctypes.data_as(N._i32p)),
+                    "dv_batch_infomax_step_u8")
+        return InfomaxBatchResults(fam, best, np.zeros(n, dtype=np.uint32))
+
+    def infomax_sense_step_batch(self, x, y, angles):
+        """An ensemble's step: member i at (x[i], y[i]) looking along angles[i][0..A) -> InfomaxBatchResults.  One enqueue and one wait
+        for all members; a member whose footprint leaves the landscape is flagged (flags & 16, best_idex -1), the others are scored."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        angles = np.ascontiguousarray(angles, dtype=np.float64)
+        if angles.ndim != 2 or len(x) != len(y) or angles.shape[0] != len(x):
+            raise ValueError("x[N], y[N] and angles[N, A] expected")
+        n, A = angles.shape
+        fam = np.empty((n, A), dtype=np.float64)
+        best = np.full(n, -1, dtype=np.int32)
+        flags = np.zeros(n, dtype=np.uint32)
+        self._check(self._lib.dv_batch_infomax_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, N.f64ptr(fam),
+                                                          best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)),
+                    "dv_batch_infomax_sense_step")
+        return InfomaxBatchResults(fam, best, flags)
 
     def infomax_info(self):
         m, n, fin = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)

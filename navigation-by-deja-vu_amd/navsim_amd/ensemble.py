@@ -27,7 +27,7 @@ class NavEnsemble(object):
         if not agents:
             raise ValueError("no agents")
         for a in agents:
-            reject_infomax(a, "NavEnsemble")
+            self._check_member(a)
         eng = agents[0]._engine
         if eng is None or any(a._engine is not eng for a in agents):
             raise ValueError("the agents of an ensemble share one engine (NavEnsemble.from_agent)")
@@ -62,6 +62,15 @@ class NavEnsemble(object):
                 a._metric_slot, a._ens = j, self
                 a._metrics_on_device = False
 
+    @classmethod
+    def _check_member(cls, agent):
+        """Raises ValueError for an agent this kind of ensemble cannot step."""
+        reject_infomax(agent, "NavEnsemble")
+
+    def _device_step(self, idx, xs, ys, angs):
+        """The one device call of an ensemble step: members `idx` at (xs, ys) looking along angs[k] -> engine.BatchResults."""
+        return self.engine.sense_step_batch(xs, ys, angs, chem_weights=None if self._weights is None else self._weights[idx])
+
     def _want_error(self, agent):
         self._pending.append((agent, agent.position[0], agent.position[1]))
 
@@ -93,7 +102,7 @@ class NavEnsemble(object):
         chem_weights (optional, one per pose): member i scores under chem_weights[i], kept as its `chem_weight`.  When the resident
         library's layout does not store the sums those weights need, it is ingested once more from agent.familiar_scenes, laid out
         for the range of weights (the agent's own weight stays the library's: that of its unweighted steps)."""
-        reject_infomax(agent, "NavEnsemble")
+        cls._check_member(agent)
         poses = list(poses)
         weights = None
         if chem_weights is not None:
@@ -211,7 +220,7 @@ class NavEnsemble(object):
                 angs = np.stack(angs)
         if idx:
             stops = {}
-            results = self.engine.sense_step_batch(xs, ys, angs, chem_weights=None if self._weights is None else self._weights[idx])
+            results = self._device_step(idx, xs, ys, angs)
             # the records as arrays when the engine offers them (engine.BatchResults): no dictionary per agent and step
             lean = hasattr(results, "angle_familiarity")
             flags = results.flags.tolist() if lean else [r["flags"] for r in results]
@@ -256,3 +265,41 @@ class NavEnsemble(object):
                 if self.stop_status[i] == 0:
                     done[i] += 1
         return done
+
+
+class InfomaxEnsemble(NavEnsemble):
+    """NavEnsemble for agents of the Infomax model (util.infomax_familiarity): the trials of the reference's grid that share one trained
+    route and differ in start_offset.  One W serves every member; a step senses every running member's headings, scores them as columns
+    of one H = W X and takes each member's first maximum in ONE device call (dv_batch_infomax_sense_step), with the bits a lone agent's
+    step_forward gives at the same pose.  The model keeps no per-view score: a tracking member's scene_familiarity is its least
+    familiarity over the headings at every view, filled after each step (as the lone agent's); +inf for a member stopped before it
+    sensed.  Members' error metrics run on the device as NavEnsemble's do.  Members with weights of their own are not offered: there is
+    no chem_weights argument."""
+
+    @classmethod
+    def _check_member(cls, agent):
+        func = getattr(agent, "_familiarity_func", None)
+        if getattr(getattr(agent, "familiarity_model", None), "metric", None) != "infomax":
+            raise ValueError("InfomaxEnsemble takes agents of the Infomax model (familiarity_model=infomax_familiarity(...)); "
+                             "NavEnsemble steps the library-based models")
+        if getattr(agent, "_engine", None) is None:
+            raise ValueError("InfomaxEnsemble needs agents whose sensor model runs on the GPU (use_gpu_sensor=True)")
+        if agent.training_path is None or func is None or getattr(func, "engine", None) is not agent._engine:
+            raise ValueError("InfomaxEnsemble needs trained agents (train_from_path first)")
+
+    @classmethod
+    def from_agent(cls, agent, poses):
+        """`agent`: a trained Infomax agent with the GPU sensor model; poses: iterable of ((x, y), angle), one member each (the first
+        goes to `agent` itself, the others to clones on the same engine and weights)."""
+        return super(InfomaxEnsemble, cls).from_agent(agent, poses)
+
+    def _device_step(self, idx, xs, ys, angs):
+        results = self.engine.infomax_sense_step_batch(xs, ys, angs)
+        self._rows = {id(self.agents[i]): results.angle_familiarity[k] for k, i in enumerate(idx)}
+        return results
+
+    def _note_scene(self, agent, x, y, headings, weight):
+        agent._scene_stale = None
+        agent._scene_owner = None
+        agent._scene_fam[:] = np.min(self._rows[id(agent)])
+        agent._scene_is_inf = False

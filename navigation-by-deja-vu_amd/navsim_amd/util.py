@@ -147,7 +147,7 @@ def reject_infomax(model, what):
     for obj in (model, getattr(model, "familiarity_model", None), getattr(model, "_familiarity_func", None)):
         if getattr(obj, "metric", None) == "infomax":
             raise ValueError("%s does not take an Infomax model: it batches or shards a view library, and infomax_familiarity keeps "
-                             "none (step each agent on its own engine)" % what)
+                             "none (step each agent on its own engine, or use navsim_amd.InfomaxEnsemble)" % what)
 
 
 def infomax_initial_weights(n_hidden, n_pixels, seed=0):

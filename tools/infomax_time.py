@@ -12,6 +12,12 @@ each figure its byte floor -- 3*8*M*N bytes per training view (W read twice, wri
 own stream probe (dv_stream_read_gbps), and the fraction of that floor reached.  The same quantities for the NumPy restatement of
 the model (tests/helpers_infomax.py) on the host's CPU, wall clock.
 
+Ensemble block (--blocks ensemble): per side, 32 members x 16 headings and 8 members x 60 headings at poses spread over a synthetic
+landscape -- microseconds per ensemble step of dv_batch_infomax_sense_step (one call for all members), and of the same poses as a
+loop of dv_infomax_sense_step calls (one per member), the two taken in the same child process in alternating windows; median and
+spread of --reps windows each, and the byte floor 8*M*N of one pass over W at the stream probe beside them.  (The matrix-time floor
+from an fp64 MFMA rate probe is not part of the tool yet.)
+
 Every GPU measurement runs in a child process of its own under a time limit, and nothing more is started on the GPU after one
 that failed."""
 import argparse
@@ -76,6 +82,53 @@ def gpu_child(side, n_views, n_calls, reps, eta):
     print(json.dumps(out))
 
 
+ENSEMBLES = ((32, 16), (8, 60))                                   # (members, headings)
+
+
+def ensemble_child(side, n_calls, reps, eta):
+    """The ensemble block of one size on the GPU -> one JSON line on stdout."""
+    from navsim_amd import NavBySceneFamiliarity, infomax_familiarity, synth
+    from navsim_amd.util import infomax_initial_weights
+    N = side * side
+    land = synth.synth_landscape(3, 600, 4)
+    out = dict(side=side, N=N, M=N, weight_bytes=8 * N * N, calls_per_window=n_calls, layouts=[])
+    for n, A in ENSEMBLES:
+        agent = NavBySceneFamiliarity(land, (side, side), 1.0, n_test_angles=A, familiarity_model=infomax_familiarity(learning_rate=eta))
+        eng = agent._engine                                       # (landscape and sensor attached; the weights are the initial ones)
+        if "stream_probe_gbps" not in out:
+            out["stream_probe_gbps"] = round(eng.stream_read_gbps(1 << 30, 10), 1)
+        eng.infomax_begin(side, side, infomax_initial_weights(N, N, 0), 2, eta)
+        rng = np.random.default_rng(n * 100 + A)
+        xs, ys = rng.uniform(150, 450, n), rng.uniform(150, 450, n)
+        angs = (rng.uniform(0, 2 * np.pi, n)[:, None] + agent.angle_offsets[None, :]) % (2 * np.pi)
+        fam = np.empty(A)
+
+        def batched():
+            eng.timer_start()
+            for _ in range(n_calls):
+                res = eng.infomax_sense_step_batch(xs, ys, angs)
+            return eng.timer_stop() * 1e3 / n_calls, res          # us per ensemble step
+
+        def looped():
+            eng.timer_start()
+            for _ in range(n_calls):
+                for i in range(n):
+                    eng.infomax_sense_step(xs[i], ys[i], angs[i], fam)
+            return eng.timer_stop() * 1e3 / n_calls
+
+        _, res = batched()                                        # warm-up of both (code load, clocks, the buffers)
+        looped()
+        assert not res.flags.any()
+        tb, tl = [], []
+        for _ in range(reps):                                     # alternating windows
+            tb.append(batched()[0])
+            tl.append(looped())
+        out["layouts"].append(dict(members=n, headings=A, batched_us_per_step=spread(tb), loop_us_per_step=spread(tl),
+                                   loop_over_batched=round(float(np.median(tl) / np.median(tb)), 3)))
+        eng.close()
+    print(json.dumps(out))
+
+
 def cpu_row(side, n_views, n_calls, eta):
     """The NumPy restatement on this host: wall clock."""
     from tests import helpers_infomax as H
@@ -105,14 +158,31 @@ def main():
                     help="the rule must stay finite on the tool's 5-level noise views: 0.01 overflows at 64x64 (the time does not depend on it)")
     ap.add_argument("--limit", type=int, default=240, help="seconds allowed to each GPU child")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "infomax_time.json"))
+    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and score_u8), ensemble")
+    ap.add_argument("--ensemble-calls", type=int, default=30, help="ensemble steps per timed window")
     ap.add_argument("--child", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--ensemble-child", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
         gpu_child(args.child, args.views, args.calls, args.reps, args.learning_rate)
         return 0
+    if args.ensemble_child:
+        ensemble_child(args.ensemble_child, args.ensemble_calls, args.reps, args.learning_rate)
+        return 0
+    blocks = args.blocks.split(",")
     result = dict(tool="tools/infomax_time.py", timer="hipEvent pair (dv_timer_start/stop), median of %d windows after a warm-up" % args.reps,
-                  learning_rate=args.learning_rate, sizes=[])
-    for side in [int(x) for x in args.sides.split(",")]:
+                  learning_rate=args.learning_rate, blocks=blocks, sizes=[], ensembles=[])
+    for side in [int(x) for x in args.sides.split(",")] if "ensemble" in blocks else []:
+        cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--ensemble-child", str(side),
+               "--ensemble-calls", str(args.ensemble_calls), "--reps", str(args.reps), "--learning-rate", str(args.learning_rate)]
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, universal_newlines=True)
+        if p.returncode != 0:
+            print("GPU measurement of the ensembles of side %d ended with status %d: nothing more is run" % (side, p.returncode), file=sys.stderr)
+            return p.returncode
+        row = json.loads(p.stdout.strip().splitlines()[-1])
+        row["byte_floor_us_at_probe"] = round(8 * row["M"] * row["N"] / (row["stream_probe_gbps"] * 1e3), 3)
+        result["ensembles"].append(row)
+    for side in [int(x) for x in args.sides.split(",")] if "single" in blocks else []:
         cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child", str(side), "--views", str(args.views),
                "--calls", str(args.calls), "--reps", str(args.reps), "--learning-rate", str(args.learning_rate)]
         p = subprocess.run(cmd, stdout=subprocess.PIPE, universal_newlines=True)

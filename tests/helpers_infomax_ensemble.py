@@ -16,7 +16,8 @@ import numpy as np
 
 from tests import helpers_infomax as H
 
-KEYS = ("20x13", "40x1", "5x3_f2", "16x16_a16")
+# the last two: more than 64 row tiles, so k_im_decide's sum over a column's tiles takes a second trip (as k_im_dfinish's does)
+KEYS = ("20x13", "40x1", "5x3_f2", "16x16_a16", "7x5_m1043", "32x32_m1040")
 # (n_agents, A): a single member; one heading per member; 65 columns, member 4 straddles a column block; 180 columns, ragged last
 # block; a member wider than a block
 LAYOUTS = ((1, 16), (7, 1), (5, 13), (3, 60), (2, 65))
@@ -38,7 +39,13 @@ def ensemble_data(key, n, A):
             fam_views = H.familiarity(d["W"], d["views"])
             top = int(np.argmax(fam_views))
             pool = H.route_views(SEED + 1 + d["seed"] * 100 + n * 7 + A, 40 * A, d["h"], d["w"])
-            below = pool[H.familiarity(d["W"], pool) < fam_views[top] * (1 + 1e-3)][:A]           # (familiarities are negative)
+            # the first A such windows (familiarities are negative), the pool scored no further than they take
+            below = np.empty((0, d["h"], d["w"]), dtype=np.uint8)
+            for p0 in range(0, len(pool), A):
+                part = pool[p0:p0 + A]
+                below = np.concatenate([below, part[H.familiarity(d["W"], part) < fam_views[top] * (1 + 1e-3)]])[:A]
+                if len(below) == A:
+                    break
             assert len(below) == A
             planes[i] = below
             planes[i, 2] = planes[i, 7] = d["views"][top]

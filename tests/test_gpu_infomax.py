@@ -3,7 +3,9 @@ restatement gives against itself (H.TOL); device against device, bit for bit.
 
 Shapes (H.CASES): (5,3) with one and two views -- the first-h launch and the fused hand-over of the next h; (40,1) with 24 rows, the
 shape of the reference's scripts/test.py; (16,16) with 130 views and 16 / 65 patches -- the steady state and the 64-heading chunk;
-(20,13) with 70 rows -- ragged in every tile."""
+(20,13) with 70 rows -- ragged in every tile; (7,5) with 1043 rows, (33,31) with 20 and (32,32) with 1040 -- the smallest at which
+the strided loops of the kernels take a further trip (66 and 65 row tiles for 64 lanes, 17 row blocks, 4 column blocks of 256, 64
+chunks of scalar loads); 8197 views of (32,32) -- the chain that crosses the staging slab of the training."""
 import ctypes
 
 import numpy as np
@@ -28,7 +30,7 @@ def begin(e, d, weights=None, eta=H.ETA):
     e.infomax_begin(d["h"], d["w"], d["W0"] if weights is None else weights, 2, eta)
 
 
-@pytest.mark.parametrize("key", ["5x3_f1", "5x3_f2", "40x1", "16x16_a16", "20x13"])
+@pytest.mark.parametrize("key", ["5x3_f1", "5x3_f2", "40x1", "16x16_a16", "20x13", "7x5_m1043", "33x31", "32x32_m1040"])
 def test_weights_after_training(eng, key):
     d = H.case_data(key)
     begin(eng, d)
@@ -62,7 +64,26 @@ def test_scores_on_the_restatements_weights(eng, key):
     assert np.array_equal(H.bits(alone), H.bits(fam[:3]))
 
 
-@pytest.mark.parametrize("key,cut", [("5x3_f2", 1), ("16x16_a16", 50), ("20x13", 32)])
+@pytest.mark.parametrize("key", H.MEAN_KEYS)
+def test_weights_whose_rows_do_not_sum_to_zero_see_the_views_mean(eng, key):
+    """From W0 + 1/N: under every other W of these tests the rows sum to zero and W x does not depend on the mean k_im_prep takes off
+    a view (tests/helpers_infomax.py: MEAN_KEYS); here a mean that misses one pixel moves the scores by 6e-6 and more."""
+    d = H.offset_case_data(key)
+    begin(eng, d)
+    eng.infomax_train_u8(d["views"])
+    W = eng.infomax_read_weights()
+    err = np.max(np.abs(W - d["W"])) / np.max(np.abs(d["W"]))
+    print("infomax weights %s from W0 + 1/N: relative error %.3e (bound %.1e)" % (key, err, H.TOL))
+    assert err <= H.TOL
+    eng.infomax_set_weights(d["W"])
+    fam = eng.infomax_score_u8(d["patches"])
+    err = np.max(np.abs(fam - d["fam"])) / np.max(np.abs(d["fam"]))
+    print("infomax scores %s from W0 + 1/N: relative error %.3e (bound %.1e)" % (key, err, H.TOL))
+    assert err <= H.TOL
+    assert H.best_margin(d["fam"]) > H.TOL and int(np.argmax(fam)) == int(np.argmax(d["fam"]))
+
+
+@pytest.mark.parametrize("key,cut", [("5x3_f2", 1), ("16x16_a16", 50), ("20x13", 32), ("7x5_m1043", 2), ("32x32_m1040", 5)])
 def test_continued_training_is_the_uncut_chain(eng, key, cut):
     d = H.case_data(key)
     begin(eng, d)
@@ -73,6 +94,29 @@ def test_continued_training_is_the_uncut_chain(eng, key, cut):
     eng.infomax_train_u8(d["views"][cut:])
     assert eng.infomax_info()["views_trained"] == d["F"]
     assert np.array_equal(H.bits(eng.infomax_read_weights()), H.bits(whole))
+
+
+def test_chain_across_the_staging_slab_is_the_uncut_chain(eng):
+    """8197 views of 32x32: the x vectors are staged 8192 at a time, so the training ends one slab without a next view and starts the
+    next with a first h of its own.  Cut anywhere -- inside the first slab, or exactly where the slabs meet -- it carries the same
+    bits, and they are the restatement's weights within the bound that chain's own rounding gives (H.TOL_LONG_CHAIN)."""
+    d = H.long_chain_data()
+    assert d["F"] == 8192 + 5 and (64 << 20) // (8 * d["N"]) == 8192
+    got = []
+    for cut in (None, 100, 8192):
+        begin(eng, d)
+        if cut is None:
+            eng.infomax_train_u8(d["views"])
+        else:
+            eng.infomax_train_u8(d["views"][:cut])
+            eng.infomax_train_u8(d["views"][cut:])
+        assert eng.infomax_info()["views_trained"] == 8197, cut
+        got.append(eng.infomax_read_weights())
+    assert np.array_equal(H.bits(got[1]), H.bits(got[0]))
+    assert np.array_equal(H.bits(got[2]), H.bits(got[0]))
+    err = np.max(np.abs(got[0] - d["W"])) / np.max(np.abs(d["W"]))
+    print("infomax weights, 8197-view chain: relative error %.3e (bound %.1e)" % (err, H.TOL_LONG_CHAIN))
+    assert err <= H.TOL_LONG_CHAIN
 
 
 def test_set_weights_round_trip_and_a_second_engine(eng):
@@ -168,6 +212,78 @@ def test_agent_fused_step_is_the_generic_plug_in_path():
     finally:
         agents[2]._familiarity_func.inner.engine.close()
         for a in agents[:2]:
+            a.clear_training()
+
+
+# ---- behind the agent, at a shape past one trip of the loops: 32x32 views, 1040 rows (65 row tiles) ----------------------------------
+def sensed_agent(seed=H.SENSED["seed"]):
+    a = H.sensed_agent(infomax_familiarity(learning_rate=H.SENSED["eta"], seed=seed, n_hidden=H.SENSED["M"]), True)
+    a.train_from_path(H.sensed_route())
+    return a
+
+
+def test_sensed_training_at_1040_rows_gives_the_restatements_weights():
+    s = H.sensed_data()
+    agent = sensed_agent()
+    try:
+        assert agent.familiar_scenes.tobytes() == s["scenes"].tobytes()              # the host sensor model's views
+        W = agent._engine.infomax_read_weights()
+        assert agent._engine.infomax_info()["views_trained"] == s["n_poses"]
+    finally:
+        agent.clear_training()
+    # s["W"]: H.train(H.initial_weights(1040, 1024, seed), familiar_scenes[..., 2], eta=0.001), computed once for both test modules
+    want = s["W"]
+    assert W.shape == want.shape == (1040, 1024)
+    err = np.max(np.abs(W - want)) / np.max(np.abs(want))
+    print("infomax weights, sensed 32x32 x 1040: relative error %.3e (bound %.1e)" % (err, H.TOL))
+    assert err <= H.TOL                                    # (this chain passes the 1000 x rule under TOL: tests/test_infomax_host.py)
+
+
+def test_sense_step_batch_at_1040_rows_is_five_single_steps():
+    path = H.sensed_route()
+    agent = sensed_agent()
+    try:
+        e = agent._engine
+        rng = np.random.default_rng(9)
+        xs = np.array([path[k][0] + rng.uniform(-1, 1) for k in (3, 11, 20, 29, 38)])
+        ys = np.array([path[k][1] + rng.uniform(-1, 1) for k in (3, 11, 20, 29, 38)])
+        angs = np.stack([(a + agent.angle_offsets) % (2 * np.pi) for a in (0.9, 0.2, 5.9, 1.4, 3.0)])
+        assert angs.shape == (5, 9)
+        single = [e.infomax_sense_step(xs[i], ys[i], angs[i]) for i in range(5)]
+        res = e.infomax_sense_step_batch(xs, ys, angs)
+        assert not res.flags.any()
+        for i, (best, fam) in enumerate(single):
+            assert np.all(fam < 0) and len(np.unique(fam)) > 1, i
+            assert np.array_equal(H.bits(res.angle_familiarity[i]), H.bits(fam)), i
+            assert res.best_idex[i] == best == int(np.argmax(fam)), i
+    finally:
+        agent.clear_training()
+
+
+def test_infomax_ensemble_at_1040_rows_equals_lone_agents():
+    path = H.sensed_route()
+    poses = []
+    for k, (dx, dy, da) in zip((3, 14, 27), ((0.7, -0.4, 0.1), (-0.5, 0.6, -0.2), (0.3, 0.9, 0.15))):
+        step = path[k + 1] - path[k]
+        poses.append(((float(path[k][0] + dx), float(path[k][1] + dy)), float((np.arctan2(step[1], step[0]) + da) % (2 * np.pi))))
+    ens = navsim_amd.InfomaxEnsemble.from_agent(sensed_agent(), poses)
+    alone = []
+    try:
+        for pos, ang in poses:
+            a = sensed_agent()
+            a.position, a.angle = pos, ang
+            alone.append(a)
+        for t in range(5):
+            ens.step_forward(fake=False)
+            for a in alone:
+                a.step_forward(fake=False)
+            for i, (m, a) in enumerate(zip(ens.agents, alone)):
+                assert m.position == a.position and m.angle == a.angle, (t, i)
+                assert np.array_equal(H.bits(m.angle_familiarity), H.bits(a.angle_familiarity)), (t, i)
+        assert not any(ens.stop_status) and len(ens.active) == 3
+    finally:
+        ens.agents[0].clear_training()
+        for a in alone:
             a.clear_training()
 
 

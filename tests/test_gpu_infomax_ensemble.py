@@ -2,7 +2,8 @@
 restatement (tests/helpers_infomax.py) within its own tolerance; InfomaxEnsemble against agents stepping alone.
 
 Shapes: the small cases of tests/helpers_infomax.py -- (20,13) with 70 rows (vector loads, a ragged row tile), (40,1) with 24 rows,
-(5,3) (the scalar-load path), (16,16) -- under member layouts that put a single member, one heading per member, a member across a
+(5,3) (the scalar-load path), (16,16), and (7,5) with 1043 rows and (32,32) with 1040 (more than 64 row tiles: k_im_decide's sum over
+a column's tiles takes a second trip, compared with k_im_dfinish's on the same wrapped loop) -- under member layouts that put a single member, one heading per member, a member across a
 block of 64 columns, a ragged last block and a member wider than a block through the column grid (tests/helpers_infomax_ensemble.py)."""
 
 import numpy as np

@@ -94,13 +94,53 @@ def test_initial_weights_are_the_restatements():
     assert np.allclose(W.mean(axis=1), 0, atol=1e-15) and np.allclose(W.std(axis=1), 1, atol=1e-15)
 
 
-@pytest.mark.parametrize("key", ["5x3_f1", "5x3_f2", "40x1", "16x16_a65", "20x13"])
+@pytest.mark.parametrize("key", ["5x3_f1", "5x3_f2", "40x1", "16x16_a65", "20x13", "7x5_m1043", "33x31", "32x32_m1040"])
 def test_restatement_against_itself_gives_the_gpu_tolerance(key):
     """float64 against longdouble and against a permuted summation order, at every GPU test shape: 1000 x the largest is the bound."""
     disc = H.discrepancies(key)
     print("infomax restatement %s: W/d vs longdouble %.2e %.2e, vs permuted order %.2e %.2e" % ((key,) + disc))
     assert 1000 * max(disc) <= H.TOL
     assert H.TOL <= 1e-11                                   # ... and the bound stays beside the 1e-12 score contract
+
+
+@pytest.mark.parametrize("key", H.MEAN_KEYS)
+def test_offset_weights_see_the_mean_and_keep_the_gpu_tolerance(key):
+    """The cases whose rows of W sum to 1: the 1000 x rule holds under TOL as for the others, and -- what they are for -- a mean that
+    misses one pixel moves their scores by far more than TOL, while the scores under the zero-sum weights of the plain case do not move."""
+    d, plain = H.offset_case_data(key), H.case_data(key)
+    assert d["N"] > 256 and np.isfinite(d["W"]).all() and np.abs(d["W"]).max() < 10
+    disc = H.offset_discrepancies(key)
+    print("infomax restatement %s from W0 + 1/N: W/d vs longdouble %.2e %.2e, vs permuted order %.2e %.2e" % ((key,) + disc))
+    assert 1000 * max(disc) <= H.TOL
+    assert np.abs(plain["W"].sum(axis=1)).max() < 1e-12 and np.abs(d["W"].sum(axis=1)).min() > 0.5
+    moved = np.max(np.abs(H.familiarity_with_mean_off(d["W"], d["patches"], 1.0 / d["N"]) - d["fam"])) / np.max(np.abs(d["fam"]))
+    blind = np.max(np.abs(H.familiarity_with_mean_off(plain["W"], plain["patches"], 1.0 / d["N"]) - plain["fam"])) / np.max(np.abs(plain["fam"]))
+    print("    a mean one pixel short moves d by %.2e (zero-sum rows: %.2e)" % (moved, blind))
+    assert moved > 1000 * H.TOL and blind < H.TOL
+    assert H.best_margin(d["fam"]) > 1000 * H.TOL
+
+
+def test_long_chain_has_a_bound_of_its_own_by_the_same_rule():
+    """8197 views of 32x32 (the chain that crosses the training's staging slab): 1000 x its largest self-discrepancy is above TOL, and
+    TOL_LONG_CHAIN is that figure rounded up to one digit.  Its cap is its own, not TOL's: within a factor of ten of the figure measured
+    here, whichever NumPy measures it."""
+    d = H.long_chain_data()
+    assert d["F"] > (64 << 20) // (8 * d["N"]) and np.isfinite(d["W"]).all()
+    disc = H.chain_discrepancy(d["W0"], d["views"], d["W"], H.ETA)
+    print("infomax restatement, long chain: W vs longdouble / permuted order %.2e (max|W| %.3g)" % (disc, np.abs(d["W"]).max()))
+    assert 1000 * disc > H.TOL                              # (why it is no member of CASES)
+    assert 1000 * disc <= H.TOL_LONG_CHAIN <= 10000 * disc
+
+
+def test_sensed_chain_is_held_to_the_gpu_tolerance():
+    """The 45 sensed 32x32 views of the agent test at 1040 rows (host sensor model, a plug-in without an engine): the chain passes the
+    1000 x rule under TOL, so the device's weights after train_from_path are held to TOL."""
+    s = H.sensed_data()
+    assert s["views"].shape == (45, 32, 32) and s["W"].shape == (1040, 1024) and np.isfinite(s["W"]).all()
+    assert len(np.unique(s["views"])) > 1
+    disc = H.chain_discrepancy(s["W0"], s["views"], s["W"], s["eta"])
+    print("infomax restatement, sensed chain: W vs longdouble / permuted order %.2e (max|W| %.3g)" % (disc, np.abs(s["W"]).max()))
+    assert 1000 * disc <= H.TOL
 
 
 def test_restatement_separates_trained_from_novel_views():

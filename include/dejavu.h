@@ -583,6 +583,50 @@ int dv_infomax_set_weights(dv_ctx *ctx, const double *weights);
 int dv_infomax_info(dv_ctx *ctx, int *n_hidden, int *n_pixels, int64_t *views_trained, int *finite, int64_t *bytes);
 int dv_infomax_end(dv_ctx *ctx);
 
+/* ---- mushroom-body familiarity model --------------------------------------- */
+/*
+ * A third familiarity model behind the same plug-in seam: the mushroom-body circuit of Ardin, Peng, Mangan, Lagogiannis & Webb
+ * (2016).  The view's compared plane p (uint8[h, w] flattened in C order, N = h * w pixels) excites n_kc Kenyon cells through a fixed
+ * sparse fan-in, conn int32[n_kc, fan_in] (drawn by the caller; a repeated pixel in a row counts twice):
+ *     a_k = sum_j p[conn[k, j]]                                   an integer, at most 255 * fan_in
+ *     fired = the n_active cells that come first in the order (larger a first, then lower k): np.argsort(-a, kind="stable")[:n_active]
+ *     training on a view: wt[fired] = 0 (wt uint8[n_kc], all 1 after begin);   a scored view: d = sum of wt over its fired cells
+ * and the calls report familiarity = (double)(-d): 0.0 for a trained view (the largest possible value), -n_active at most novel.
+ * Integers from pixel to score: every figure is exact, whatever the order of the work.  Training ORs the fired sets, so it has no
+ * order and is idempotent: train(a) then train(b) is train(a + b) is train(b + a).  The memory is n_kc bytes however long the route.
+ * The model lives beside, and independent of, a resident library, landscape, patches, diffuse field and Infomax model.
+ *   begin            allocates the model and copies conn.  A model already there is replaced.  DV_ERR_INVALID: NULL conn, a conn entry
+ *                    outside [0, h * w), channel outside {0, 1, 2}, h or w < 1, h * w > 65536, n_kc < 1, fan_in outside [1, 16],
+ *                    n_active outside [1, n_kc].
+ *   train_u8         trains on uint8[n, h, w] planes: every view of a call in one launch (8192 views, or 64 MiB of planes, at a time).
+ *   train_from_poses senses the n poses as dv_set_library_from_poses does and trains on their `channel` plane with no host round
+ *                    trip; out_views (may be NULL) receives uint8[n, h, w, 3].  DV_ERR_INDEX as dv_sense, and then nothing was
+ *                    trained; DV_ERR_INVALID when the sensor's shape is not the model's.
+ *   score_u8         familiarity[a] = -d of each of uint8[n, h, w] planes, any n >= 1, one launch.
+ *   activity_u8      which cells each of uint8[n, h, w] planes excites: fired uint8[n][n_kc] (1 where the cell fires) and threshold
+ *                    int32[n], the least a of a firing cell; either may be NULL.
+ *   sense_step       one agent step: senses the n_headings patches at (x, y), scores their `channel` plane in one launch and takes
+ *                    the first maximum of angle_fam (np.argmax: integer scores tie).  Any n_headings >= 1.  DV_ERR_INDEX like
+ *                    dv_sense_step.
+ *   read_weights / set_weights   copy uint8[n_kc] out and in: what a user saves and restores.  DV_ERR_INVALID for a value other
+ *                    than 0 or 1.
+ *   info             n_kc, n_pixels, fan_in, n_active, views trained since begin, n_depressed (the number of zero weights: how full
+ *                    the memory is), bytes of the weights; zeros without a model; any pointer may be NULL.
+ *   end              frees the model; dv_destroy frees it too.
+ * Every call but begin, info and end returns DV_ERR_STATE without a model.
+ */
+int dv_mb_begin(dv_ctx *ctx, int h, int w, int channel, int n_kc, int fan_in, int n_active, const int32_t *conn);
+int dv_mb_train_u8(dv_ctx *ctx, const uint8_t *planes, int64_t n);
+int dv_mb_train_from_poses(dv_ctx *ctx, const double *x, const double *y, const double *angle, int64_t n, uint8_t *out_views);
+int dv_mb_score_u8(dv_ctx *ctx, const uint8_t *planes, int n, double *familiarity);
+int dv_mb_activity_u8(dv_ctx *ctx, const uint8_t *planes, int n, uint8_t *fired, int32_t *threshold);
+int dv_mb_sense_step(dv_ctx *ctx, double x, double y, const double *angles, int n_headings, double *angle_fam, int32_t *best_heading);
+int dv_mb_read_weights(dv_ctx *ctx, uint8_t *out);
+int dv_mb_set_weights(dv_ctx *ctx, const uint8_t *weights);
+int dv_mb_info(dv_ctx *ctx, int *n_kc, int *n_pixels, int *fan_in, int *n_active, int64_t *views_trained, int64_t *n_depressed,
+               int64_t *bytes);
+int dv_mb_end(dv_ctx *ctx);
+
 /* ---- measurement ------------------------------------------------------- */
 /* hipEvent pair on the context's stream around whatever is enqueued between the two calls. */
 int dv_timer_start(dv_ctx *ctx);

@@ -310,6 +310,18 @@ struct dv_ctx {
     double im_eta = 0.0;
     int64_t im_views = 0;                     // views trained on since dv_infomax_begin
     bool im_finite = true;
+    // mushroom-body familiarity model (dejavu_mushroom.inl): fixed fan-in, one byte of weight per Kenyon cell; independent of the above
+    unsigned short* mb_conn = nullptr;        // [fan_in][K]: input j of every cell
+    unsigned char* mb_wt = nullptr;           // [K]: 1, or 0 once depressed
+    int* mb_d = nullptr;                      // novelty (or threshold) per view of a launch
+    unsigned char* mb_out = nullptr;          // a step's angle_fam[n] doubles and best heading: one copy to the host
+    unsigned char* mb_fired = nullptr;        // [slab][K]: dv_mb_activity_u8's masks
+    long long* mb_zeros = nullptr;            // k_mb_count's answer
+    size_t mb_d_cap = 0, mb_out_cap = 0, mb_fired_cap = 0;   // bytes
+    std::vector<unsigned char> mb_hout;       // where a step's copy lands
+    std::vector<double> mb_xy;                // a step's pose, once per heading
+    int mb_K = 0, mb_N = 0, mb_c = 0, mb_active = 0, mb_hh = 0, mb_ww = 0, mb_channel = 2;
+    int64_t mb_views = 0;                     // views trained on since dv_mb_begin
 
     // measurement
     hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -340,6 +352,7 @@ static int fail(dv_ctx* c, int code, const char* fmt, ...) {
 static void use_set(dv_ctx* c, int which);
 static void diffuse_free(dv_ctx* c);
 static void infomax_free(dv_ctx* c);
+static void mb_free(dv_ctx* c);
 static void free_library(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
     use_set(c, 0);
@@ -438,6 +451,7 @@ extern "C" void dv_destroy(dv_ctx* c) {
     free_library(c);
     diffuse_free(c);
     infomax_free(c);
+    mb_free(c);
     if (c->d_land) (void)hipFree(c->d_land);
     if (c->d_lut) (void)hipFree(c->d_lut);
     if (c->d_poses) (void)hipFree(c->d_poses);
@@ -3577,4 +3591,5 @@ extern "C" int dv_stream_read_gbps(dv_ctx* c, int64_t n_bytes, int iters, double
 
 #include "dejavu_diffuse.inl"   // dv_diffuse_*: the landscape generator's heat equation (kernels and host side)
 #include "dejavu_infomax.inl"   // dv_infomax_*: the Infomax familiarity model (kernels and host side)
+#include "dejavu_mushroom.inl"  // dv_mb_*: the mushroom-body familiarity model (kernels and host side)
 #include "dejavu_group.inl"     // dv_group_*: one process, several devices -- host logic above the C ABI

@@ -1,0 +1,442 @@
+// The mushroom-body familiarity model on the device (include/dejavu.h: dv_mb_*): the circuit of Ardin, Peng, Mangan, Lagogiannis &
+// Webb (2016).  A view's compared plane p (uint8, N = h * w pixels, C order) excites K Kenyon cells through a fixed random fan-in of c
+// pixels each, a_k = sum_j p[conn[k][j]]; the n_active cells that come first in the order (larger a first, then lower k) fire; training
+// on a view clears the one-byte output weight of every cell that fired, and a view's novelty d is the number of its firing cells whose
+// weight is still 1.  Integers from pixel to score: there is nothing to round and no order of summation to fix.
+//
+//   k_mb<MODE>   one workgroup of 4 waves per view.  The plane is staged in LDS once.  Wave w owns the contiguous cells
+//                [w * span, (w + 1) * span), span a multiple of 64, and walks them 64 at a time with lane = cell, so the connectivity
+//                (uint16 [c][K]: row j holds input j of every cell) is read in consecutive words and a wave's ballot sees its cells in
+//                index order.
+//                pass 1     a_k from c byte gathers; one LDS atomic into the WAVE's histogram over the 255 c + 1 possible sums
+//                threshold  a suffix scan over the bins of the four histograms added: t with count(a > t) < n_active <= count(a >= t),
+//                           the quota q = n_active - count(a > t), and from the waves' own bins at t the rank at which each wave's
+//                           cells with a == t begin -- the per-wave histograms are what spares a counting pass between the two
+//                pass 2     a_k again; a cell fires when a_k > t, or a_k == t and its rank among the equals (the wave's start, the
+//                           equals of its earlier trips, the ballot's lower lanes) is below q: exactly the first q in index order
+//                MODE kMbTrain stores 0 to wt[k] of a firing cell (plain byte stores: every writer of a byte stores the same value,
+//                whichever view's workgroup it is, so a whole route is one launch); kMbScore adds wt[k] over the firing cells;
+//                kMbMask writes the fired mask and t.
+//   k_mb_decide  fam[a] = (double)(-d[a]) and the first maximum over the headings (np.argmax), one workgroup
+//   k_mb_count   the number of zero weights, one workgroup
+namespace dv {
+
+static constexpr int kMbTrain = 0, kMbScore = 1, kMbMask = 2;
+static constexpr int kMbWaves = 4;
+static constexpr int kMbMaxFanIn = 16;
+
+__device__ __forceinline__ int mb_activity(const unsigned char* __restrict__ plane, const unsigned short* __restrict__ conn, int K, int c, int k) {
+    // All kMbMaxFanIn index loads are issued together and then all the gathers: one global and one LDS latency per cell instead of c of
+    // each.  No branch on c, which would serialise them: a row past c - 1 reads row c - 1 again (the line just fetched) and adds nothing.
+    unsigned short idx[kMbMaxFanIn];
+#pragma unroll
+    for (int j = 0; j < kMbMaxFanIn; ++j) idx[j] = conn[(size_t)(j < c ? j : c - 1) * (size_t)K + k];
+    int a = 0;
+#pragma unroll
+    for (int j = 0; j < kMbMaxFanIn; ++j) {
+        const int v = (int)plane[idx[j]];
+        a += j < c ? v : 0;
+    }
+    return a;
+}
+
+// src: view v's compared plane is src[v * view_stride + offset + j * px_stride], j < N (as k_im_prep).  Dynamic LDS:
+// [N rounded up to 4] plane bytes, [kMbWaves][nb] histogram words (nb = 255 c + 1), then 16 words of hand-over.
+// d: [views] (kMbScore); fired: [views][K], thr: [views] (kMbMask; either may be nullptr).
+template <int MODE>
+__global__ __launch_bounds__(kMbWaves * 64) void k_mb(const unsigned char* __restrict__ src, long long view_stride, int px_stride, int offset, int N,
+                                                      const unsigned short* __restrict__ conn, int K, int c, int n_active,
+                                                      unsigned char* __restrict__ wt, int* __restrict__ d, unsigned char* __restrict__ fired,
+                                                      int* __restrict__ thr) {
+    extern __shared__ unsigned mb_lds[];
+    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int nb = 255 * c + 1;
+    unsigned char* plane = reinterpret_cast<unsigned char*>(mb_lds);
+    unsigned* hist = mb_lds + ((N + 3) >> 2);                // [kMbWaves][nb]
+    unsigned* hand = hist + kMbWaves * nb;                   // [0..3] the waves' totals, [4] t, [5] q, [6..9] the waves' starting ranks
+    const unsigned char* p = src + (size_t)blockIdx.x * (size_t)view_stride + offset;
+    for (int j = tid; j < N; j += kMbWaves * 64) plane[j] = p[(size_t)j * px_stride];
+    for (int b = tid; b < kMbWaves * nb; b += kMbWaves * 64) hist[b] = 0u;
+    __syncthreads();
+
+    const int span = (((K + kMbWaves - 1) / kMbWaves) + 63) & ~63;
+    const int k0 = wave * span;
+    const int k1 = k0 + span < K ? k0 + span : K;            // (k0 >= K: the wave has no cells)
+    unsigned* myhist = hist + wave * nb;
+    for (int base = k0; base < k1; base += 64) {
+        const int k = base + lane;
+        const int a = mb_activity(plane, conn, K, c, k < k1 ? k : k1 - 1);   // (a lane past the end: a cell again, not counted)
+        if (k < k1) atomicAdd(&myhist[a], 1u);
+    }
+    __syncthreads();
+
+    // thread tid owns the bins [lo, hi); `above` = the cells in the bins of the threads after it
+    const int bpt = (nb + kMbWaves * 64 - 1) / (kMbWaves * 64);
+    const int lo = tid * bpt < nb ? tid * bpt : nb;
+    const int hi = lo + bpt < nb ? lo + bpt : nb;
+    unsigned mine = 0;
+    for (int b = lo; b < hi; ++b) mine += hist[b] + hist[nb + b] + hist[2 * nb + b] + hist[3 * nb + b];
+    unsigned suf = mine;                                      // inclusive suffix sum over the wave's lanes
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned u = __shfl_down(suf, off);
+        if (lane + off < 64) suf += u;
+    }
+    if (lane == 0) hand[wave] = suf;
+    __syncthreads();
+    unsigned above = suf - mine;
+    for (int w = wave + 1; w < kMbWaves; ++w) above += hand[w];
+    for (int b = hi - 1; b >= lo; --b) {
+        const unsigned h0 = hist[b], h1 = hist[nb + b], h2 = hist[2 * nb + b], h3 = hist[3 * nb + b];
+        const unsigned cnt = h0 + h1 + h2 + h3;
+        if (above < (unsigned)n_active && (unsigned)n_active <= above + cnt) {   // (one bin of one thread: 1 <= n_active <= K)
+            hand[4] = (unsigned)b;
+            hand[5] = (unsigned)n_active - above;
+            hand[6] = 0u; hand[7] = h0; hand[8] = h0 + h1; hand[9] = h0 + h1 + h2;
+        }
+        above += cnt;
+    }
+    __syncthreads();
+    const int t = (int)hand[4];
+    const unsigned q = hand[5];
+    unsigned rank0 = hand[6 + wave];                          // equals before this trip's cells
+    int acc = 0;
+    for (int base = k0; base < k1; base += 64) {
+        const int k = base + lane;
+        const bool in = k < k1;
+        const int ak = mb_activity(plane, conn, K, c, in ? k : k1 - 1);
+        const int a = in ? ak : -1;
+        const bool eq = a == t;
+        const unsigned long long m = __ballot(eq);
+        const unsigned rank = rank0 + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
+        const bool fire = a > t || (eq && rank < q);
+        rank0 += (unsigned)__popcll(m);
+        if (MODE == kMbTrain) {
+            if (fire) wt[k] = 0;
+        } else if (MODE == kMbScore) {
+            if (fire) acc += (int)wt[k];
+        } else if (in && fired) {
+            fired[(size_t)blockIdx.x * (size_t)K + k] = fire ? 1 : 0;
+        }
+    }
+    if (MODE == kMbScore) {
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+        if (lane == 0) hand[10 + wave] = (unsigned)acc;
+        __syncthreads();
+        if (tid == 0) d[blockIdx.x] = (int)(hand[10] + hand[11] + hand[12] + hand[13]);
+    }
+    if (MODE == kMbMask && thr && tid == 0) thr[blockIdx.x] = t;
+}
+
+// fam[a] = (double)(-d[a]); *best = the first maximum (the larger value, the lower heading of equals)
+__global__ __launch_bounds__(256) void k_mb_decide(const int* __restrict__ d, int n, double* __restrict__ fam, int* __restrict__ best) {
+    __shared__ int sv[256], si[256];
+    const int tid = (int)threadIdx.x;
+    int bv = 0, bi = -1;
+    for (int a = tid; a < n; a += 256) {                      // headings in rising order: a later equal does not replace
+        const int v = -d[a];
+        fam[a] = (double)v;
+        if (bi < 0 || v > bv) { bv = v; bi = a; }
+    }
+    sv[tid] = bv; si[tid] = bi;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (tid < st) {
+            const int ov = sv[tid + st], oi = si[tid + st];
+            if (oi >= 0 && (si[tid] < 0 || ov > sv[tid] || (ov == sv[tid] && oi < si[tid]))) { sv[tid] = ov; si[tid] = oi; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) *best = si[0];
+}
+
+__global__ __launch_bounds__(256) void k_mb_count(const unsigned char* __restrict__ wt, int K, long long* __restrict__ zeros) {
+    __shared__ int red[256];
+    const int tid = (int)threadIdx.x;
+    int s = 0;
+    for (int k = tid; k < K; k += 256) s += wt[k] == 0 ? 1 : 0;
+    red[tid] = s;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (tid < st) red[tid] += red[tid + st];
+        __syncthreads();
+    }
+    if (tid == 0) *zeros = (long long)red[0];
+}
+
+}  // namespace dv
+
+static constexpr int kMbMaxPixels = 65536;                   // N of a view: a pixel index is a uint16 on the device
+static constexpr int kMbMaxCells = 1 << 24;
+static constexpr int kMbSlabViews = 8192;                    // views of one launch (one workgroup each) ...
+static constexpr size_t kMbStageBytes = 64u << 20;           // ... and the bytes of uploaded planes, or of fired masks, it may stage
+
+static void mb_free(dv_ctx* c) {
+    auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
+    F(c->mb_conn); F(c->mb_wt); F(c->mb_d); F(c->mb_out); F(c->mb_fired); F(c->mb_zeros);
+    c->mb_d_cap = c->mb_out_cap = c->mb_fired_cap = 0;
+    c->mb_K = c->mb_N = c->mb_c = c->mb_active = c->mb_hh = c->mb_ww = 0;
+    c->mb_views = 0;
+}
+
+static int mb_need(dv_ctx* c, const char* who) {
+    if (!c->mb_wt) return fail(c, DV_ERR_STATE, "%s: no mushroom-body model (dv_mb_begin first)", who);
+    return DV_OK;
+}
+
+static size_t mb_lds_bytes(const dv_ctx* c) {
+    return (size_t)((c->mb_N + 3) & ~3) + (size_t)kMbWaves * (size_t)(255 * c->mb_c + 1) * 4u + 16u * 4u;
+}
+
+// Views of one launch when each brings `bytes_per_view` of staged bytes.
+static int64_t mb_slab(size_t bytes_per_view) {
+    int64_t s = (int64_t)(kMbStageBytes / (bytes_per_view ? bytes_per_view : 1));
+    if (s > kMbSlabViews) s = kMbSlabViews;
+    return s < 1 ? 1 : s;
+}
+
+// Enqueue one launch over n <= kMbSlabViews views resident on the device (layout as k_mb's src).
+template <int MODE>
+static int mb_launch(dv_ctx* c, const unsigned char* d_src, long long view_stride, int px_stride, int offset, int n, int* d, unsigned char* fired,
+                     int* thr) {
+    hipLaunchKernelGGL((k_mb<MODE>), dim3((unsigned)n), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, d_src, view_stride, px_stride, offset, c->mb_N,
+                       c->mb_conn, c->mb_K, c->mb_c, c->mb_active, c->mb_wt, d, fired, thr);
+    HIP_TRY(c, hipGetLastError());
+    return DV_OK;
+}
+
+static int mb_sensor_fits(dv_ctx* c, const char* who) {
+    if (!c->have_sensor) return fail(c, DV_ERR_STATE, "sensor not configured");
+    if (c->sensor.sh != c->mb_hh || c->sensor.sw != c->mb_ww)
+        return fail(c, DV_ERR_INVALID, "%s: the sensor is %dx%d but the model takes %dx%d views", who, c->sensor.sw, c->sensor.sh, c->mb_ww, c->mb_hh);
+    return DV_OK;
+}
+
+extern "C" int dv_mb_end(dv_ctx* c) {
+    if (!c) return DV_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    mb_free(c);
+    return DV_OK;
+}
+
+extern "C" int dv_mb_begin(dv_ctx* c, int h, int w, int channel, int n_kc, int fan_in, int n_active, const int32_t* conn) {
+    if (!c) return DV_ERR_INVALID;
+    if (!conn) return fail(c, DV_ERR_INVALID, "dv_mb_begin: the connectivity is NULL");
+    if (h < 1 || w < 1 || (long long)h * w > kMbMaxPixels) return fail(c, DV_ERR_INVALID, "dv_mb_begin: views of %d x %d (1..%d pixels)", h, w, kMbMaxPixels);
+    if (channel < 0 || channel > 2) return fail(c, DV_ERR_INVALID, "dv_mb_begin: channel %d outside [0, 2]", channel);
+    if (n_kc < 1 || n_kc > kMbMaxCells) return fail(c, DV_ERR_INVALID, "dv_mb_begin: n_kc %d outside [1, %d]", n_kc, kMbMaxCells);
+    if (fan_in < 1 || fan_in > dv::kMbMaxFanIn) return fail(c, DV_ERR_INVALID, "dv_mb_begin: fan_in %d outside [1, %d]", fan_in, dv::kMbMaxFanIn);
+    if (n_active < 1 || n_active > n_kc) return fail(c, DV_ERR_INVALID, "dv_mb_begin: n_active %d outside [1, n_kc = %d]", n_active, n_kc);
+    const int N = h * w;
+    const size_t K = (size_t)n_kc, cc = (size_t)fan_in;
+    // the device's layout: uint16 [fan_in][n_kc], so that a wave's lanes read consecutive cells
+    std::vector<unsigned short> ct(K * cc);
+    for (size_t k = 0; k < K; ++k)
+        for (size_t j = 0; j < cc; ++j) {
+            const int32_t v = conn[k * cc + j];
+            if (v < 0 || v >= N) return fail(c, DV_ERR_INVALID, "dv_mb_begin: conn[%zu][%zu] = %d outside [0, %d)", k, j, (int)v, N);
+            ct[j * K + k] = (unsigned short)v;
+        }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    mb_free(c);
+    c->mb_K = n_kc; c->mb_N = N; c->mb_c = fan_in; c->mb_active = n_active; c->mb_hh = h; c->mb_ww = w; c->mb_channel = channel;
+    const int lds = (int)mb_lds_bytes(c);                    // at most 65536 + 4 * 4081 * 4 + 64 = 130896 of the workgroup's 160 KB
+    hipError_t e = hipMalloc((void**)&c->mb_conn, ct.size() * sizeof(unsigned short));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->mb_wt, K);
+    if (e == hipSuccess) e = hipMalloc((void**)&c->mb_zeros, sizeof(long long));
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb<kMbTrain>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb<kMbScore>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb<kMbMask>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->mb_conn, ct.data(), ct.size() * sizeof(unsigned short), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->mb_wt, 1, K, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);           // `ct` is this call's
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        mb_free(c);
+        return fail(c, e == hipErrorOutOfMemory ? DV_ERR_OOM : DV_ERR_HIP, "dv_mb_begin: %d cells x %d inputs: %s", n_kc, fan_in, hipGetErrorString(e));
+    }
+    return DV_OK;
+}
+
+extern "C" int dv_mb_train_u8(dv_ctx* c, const uint8_t* planes, int64_t n) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = mb_need(c, "dv_mb_train_u8");
+    if (rc) return rc;
+    if (!planes || n < 0) return fail(c, DV_ERR_INVALID, "dv_mb_train_u8: planes is NULL or n < 0");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t N = (size_t)c->mb_N;
+    int64_t slab = mb_slab(N);
+    if (slab > n) slab = n;
+    if (n > 0) { rc = ensure_sense_buffer(c, (size_t)slab * N); if (rc) return rc; }
+    for (int64_t v0 = 0; v0 < n; v0 += slab) {
+        const int64_t ns = n - v0 < slab ? n - v0 : slab;
+        HIP_TRY(c, hipMemcpyAsync(c->d_sense, planes + (size_t)v0 * N, (size_t)ns * N, hipMemcpyHostToDevice, c->stream));
+        rc = mb_launch<kMbTrain>(c, c->d_sense, (long long)N, 1, 0, (int)ns, nullptr, nullptr, nullptr);
+        if (rc) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));          // the slab is reused, `planes` is borrowed
+    }
+    c->mb_views += n;
+    return DV_OK;
+}
+
+extern "C" int dv_mb_train_from_poses(dv_ctx* c, const double* x, const double* y, const double* angle, int64_t n, uint8_t* out_views) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = mb_need(c, "dv_mb_train_from_poses");
+    if (rc) return rc;
+    if (!x || !y || !angle || n < 1 || n > 0x7fffffff) return fail(c, DV_ERR_INVALID, "dv_mb_train_from_poses: bad arguments");
+    rc = mb_sensor_fits(c, "dv_mb_train_from_poses");
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)n * (size_t)c->mb_N * 3;
+    rc = ensure_sense_buffer(c, bytes);
+    if (rc) return rc;
+    rc = enqueue_sense(c, x, y, angle, n, c->d_sense);
+    if (rc) return rc;
+    if (out_views) HIP_TRY(c, hipMemcpyAsync(out_views, c->d_sense, bytes, hipMemcpyDeviceToHost, c->stream));
+    rc = check_sense_error(c);                                // (synchronises: nothing is trained from a footprint off the landscape)
+    if (rc) return rc;
+    const long long stride = 3ll * c->mb_N;
+    for (int64_t v0 = 0; v0 < n; v0 += kMbSlabViews) {
+        const int64_t ns = n - v0 < kMbSlabViews ? n - v0 : kMbSlabViews;
+        rc = mb_launch<kMbTrain>(c, c->d_sense + (size_t)v0 * (size_t)stride, stride, 3, c->mb_channel, (int)ns, nullptr, nullptr, nullptr);
+        if (rc) return rc;
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->mb_views += n;
+    return DV_OK;
+}
+
+extern "C" int dv_mb_score_u8(dv_ctx* c, const uint8_t* planes, int n, double* familiarity) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = mb_need(c, "dv_mb_score_u8");
+    if (rc) return rc;
+    if (!planes || !familiarity || n < 1) return fail(c, DV_ERR_INVALID, "dv_mb_score_u8: NULL argument or n < 1");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t N = (size_t)c->mb_N;
+    int64_t slab = mb_slab(N);
+    if (slab > n) slab = n;
+    rc = ensure_sense_buffer(c, (size_t)slab * N);
+    if (!rc) rc = infomax_grow(c, c->mb_d, c->mb_d_cap, (size_t)slab * sizeof(int));
+    if (rc) return rc;
+    std::vector<int> dh((size_t)slab);
+    for (int64_t v0 = 0; v0 < n; v0 += slab) {
+        const int64_t ns = n - v0 < slab ? n - v0 : slab;
+        HIP_TRY(c, hipMemcpyAsync(c->d_sense, planes + (size_t)v0 * N, (size_t)ns * N, hipMemcpyHostToDevice, c->stream));
+        rc = mb_launch<kMbScore>(c, c->d_sense, (long long)N, 1, 0, (int)ns, c->mb_d, nullptr, nullptr);
+        if (rc) return rc;
+        HIP_TRY(c, hipMemcpyAsync(dh.data(), c->mb_d, (size_t)ns * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (int64_t a = 0; a < ns; ++a) familiarity[v0 + a] = (double)(-dh[(size_t)a]);   // (the integer is negated: a trained view gives +0.0)
+    }
+    return DV_OK;
+}
+
+extern "C" int dv_mb_activity_u8(dv_ctx* c, const uint8_t* planes, int n, uint8_t* fired, int32_t* threshold) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = mb_need(c, "dv_mb_activity_u8");
+    if (rc) return rc;
+    if (!planes || n < 1) return fail(c, DV_ERR_INVALID, "dv_mb_activity_u8: planes is NULL or n < 1");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t N = (size_t)c->mb_N, K = (size_t)c->mb_K;
+    int64_t slab = mb_slab(N > K ? N : K);
+    if (slab > n) slab = n;
+    rc = ensure_sense_buffer(c, (size_t)slab * N);
+    if (!rc) rc = infomax_grow(c, c->mb_d, c->mb_d_cap, (size_t)slab * sizeof(int));
+    if (!rc && fired) rc = infomax_grow(c, c->mb_fired, c->mb_fired_cap, (size_t)slab * K);
+    if (rc) return rc;
+    for (int64_t v0 = 0; v0 < n; v0 += slab) {
+        const int64_t ns = n - v0 < slab ? n - v0 : slab;
+        HIP_TRY(c, hipMemcpyAsync(c->d_sense, planes + (size_t)v0 * N, (size_t)ns * N, hipMemcpyHostToDevice, c->stream));
+        rc = mb_launch<kMbMask>(c, c->d_sense, (long long)N, 1, 0, (int)ns, nullptr, fired ? c->mb_fired : nullptr, c->mb_d);
+        if (rc) return rc;
+        if (fired) HIP_TRY(c, hipMemcpyAsync(fired + (size_t)v0 * K, c->mb_fired, (size_t)ns * K, hipMemcpyDeviceToHost, c->stream));
+        if (threshold) HIP_TRY(c, hipMemcpyAsync(threshold + v0, c->mb_d, (size_t)ns * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return DV_OK;
+}
+
+extern "C" int dv_mb_sense_step(dv_ctx* c, double x, double y, const double* angles, int n, double* angle_fam, int32_t* best_heading) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = mb_need(c, "dv_mb_sense_step");
+    if (rc) return rc;
+    if (!angles || !angle_fam || !best_heading || n < 1) return fail(c, DV_ERR_INVALID, "dv_mb_sense_step: NULL argument or n_headings < 1");
+    rc = mb_sensor_fits(c, "dv_mb_sense_step");
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t fam_bytes = (size_t)n * sizeof(double), out_bytes = fam_bytes + sizeof(int);
+    rc = ensure_sense_buffer(c, (size_t)n * (size_t)c->mb_N * 3);
+    if (!rc) rc = infomax_grow(c, c->mb_d, c->mb_d_cap, (size_t)n * sizeof(int));
+    if (!rc) rc = infomax_grow(c, c->mb_out, c->mb_out_cap, out_bytes);
+    if (rc) return rc;
+    c->mb_xy.assign((size_t)n, x);
+    c->mb_xy.resize(2 * (size_t)n, y);
+    rc = enqueue_sense(c, c->mb_xy.data(), c->mb_xy.data() + n, angles, n, c->d_sense);
+    if (rc) return rc;
+    const long long stride = 3ll * c->mb_N;
+    for (int v0 = 0; v0 < n; v0 += kMbSlabViews) {            // every heading in one launch (a launch's grid: kMbSlabViews workgroups)
+        const int ns = n - v0 < kMbSlabViews ? n - v0 : kMbSlabViews;
+        rc = mb_launch<kMbScore>(c, c->d_sense + (size_t)v0 * (size_t)stride, stride, 3, c->mb_channel, ns, c->mb_d + v0, nullptr, nullptr);
+        if (rc) return rc;
+    }
+    double* d_fam = reinterpret_cast<double*>(c->mb_out);
+    int* d_best = reinterpret_cast<int*>(c->mb_out + fam_bytes);
+    hipLaunchKernelGGL(k_mb_decide, dim3(1), dim3(256), 0, c->stream, c->mb_d, n, d_fam, d_best);
+    HIP_TRY(c, hipGetLastError());
+    c->mb_hout.resize(out_bytes);
+    HIP_TRY(c, hipMemcpyAsync(c->mb_hout.data(), c->mb_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    rc = check_sense_error(c);                                // (synchronises)
+    if (rc) return rc;
+    std::memcpy(angle_fam, c->mb_hout.data(), fam_bytes);
+    std::memcpy(best_heading, c->mb_hout.data() + fam_bytes, sizeof(int));
+    return DV_OK;
+}
+
+extern "C" int dv_mb_read_weights(dv_ctx* c, uint8_t* out) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = mb_need(c, "dv_mb_read_weights");
+    if (rc) return rc;
+    if (!out) return fail(c, DV_ERR_INVALID, "dv_mb_read_weights: out is NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(out, c->mb_wt, (size_t)c->mb_K, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DV_OK;
+}
+
+extern "C" int dv_mb_set_weights(dv_ctx* c, const uint8_t* weights) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = mb_need(c, "dv_mb_set_weights");
+    if (rc) return rc;
+    if (!weights) return fail(c, DV_ERR_INVALID, "dv_mb_set_weights: weights is NULL");
+    for (int k = 0; k < c->mb_K; ++k)
+        if (weights[k] > 1) return fail(c, DV_ERR_INVALID, "dv_mb_set_weights: weights[%d] = %d is neither 0 nor 1", k, (int)weights[k]);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(c->mb_wt, weights, (size_t)c->mb_K, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));              // `weights` is borrowed for this call only
+    return DV_OK;
+}
+
+extern "C" int dv_mb_info(dv_ctx* c, int* n_kc, int* n_pixels, int* fan_in, int* n_active, int64_t* views_trained, int64_t* n_depressed,
+                          int64_t* bytes) {
+    if (!c) return DV_ERR_INVALID;
+    if (n_kc) *n_kc = c->mb_K;
+    if (n_pixels) *n_pixels = c->mb_N;
+    if (fan_in) *fan_in = c->mb_c;
+    if (n_active) *n_active = c->mb_active;
+    if (views_trained) *views_trained = c->mb_views;
+    if (bytes) *bytes = (int64_t)c->mb_K;
+    if (n_depressed) {
+        *n_depressed = 0;
+        if (c->mb_wt) {
+            long long z = 0;
+            HIP_TRY(c, hipSetDevice(c->device));
+            hipLaunchKernelGGL(k_mb_count, dim3(1), dim3(256), 0, c->stream, c->mb_wt, c->mb_K, c->mb_zeros);
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipMemcpyAsync(&z, c->mb_zeros, sizeof z, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            *n_depressed = (int64_t)z;
+        }
+    }
+    return DV_OK;
+}

@@ -237,6 +237,17 @@ PROTOTYPES = {
     "dv_infomax_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _i64p,
                                        ctypes.POINTER(ctypes.c_int), _i64p]),
     "dv_infomax_end": (ctypes.c_int, [_ctx_p]),
+    "dv_mb_begin": (ctypes.c_int, [_ctx_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p]),
+    "dv_mb_train_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int64]),
+    "dv_mb_train_from_poses": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int64, _u8p]),
+    "dv_mb_score_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, _f64p]),
+    "dv_mb_activity_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, _u8p, _i32p]),
+    "dv_mb_sense_step": (ctypes.c_int, [_ctx_p, ctypes.c_double, ctypes.c_double, _f64p, ctypes.c_int, _f64p, _i32p]),
+    "dv_mb_read_weights": (ctypes.c_int, [_ctx_p, _u8p]),
+    "dv_mb_set_weights": (ctypes.c_int, [_ctx_p, _u8p]),
+    "dv_mb_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                  ctypes.POINTER(ctypes.c_int), _i64p, _i64p, _i64p]),
+    "dv_mb_end": (ctypes.c_int, [_ctx_p]),
     "dv_synchronize": (ctypes.c_int, [_ctx_p]),
     "dv_timer_start": (ctypes.c_int, [_ctx_p]),
     "dv_timer_stop": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_float)]),

@@ -250,6 +250,10 @@ class NavBySceneFamiliarity(object):
                 # no library: a fresh weight matrix, trained on the views where they are sensed
                 self.familiarity_model.begin(self._engine, self.sensor_dimensions[1], self.sensor_dimensions[0])
                 self.familiar_scenes[...] = self._engine.infomax_train_from_poses(points[:, 0], points[:, 1], view_headings)
+            elif getattr(self.familiarity_model, "metric", "sads_hsv") == "mushroom":
+                # no library either: fresh Kenyon-cell weights, depressed by the views where they are sensed
+                self.familiarity_model.begin(self._engine, self.sensor_dimensions[1], self.sensor_dimensions[0])
+                self.familiar_scenes[...] = self._engine.mb_train_from_poses(points[:, 0], points[:, 1], view_headings)
             elif getattr(self.familiarity_model, "metric", "sads_hsv") == "ssd":
                 self.familiar_scenes[...] = self._engine.set_library_u8_from_poses(
                     points[:, 0], points[:, 1], view_headings, self.familiarity_model.channel)
@@ -295,6 +299,7 @@ class NavBySceneFamiliarity(object):
         engine = getattr(self._familiarity_func, "engine", None)
         ssd = str(getattr(self._familiarity_func, "metric", "")).startswith("ssd")
         infomax = getattr(self._familiarity_func, "metric", "") == "infomax"
+        mushroom = getattr(self._familiarity_func, "metric", "") == "mushroom"
         if infomax and self._engine is not None and engine is self._engine:
             # the Infomax model keeps training on the same weights: the new views follow the old ones in the chain
             for pt in points:
@@ -303,6 +308,14 @@ class NavBySceneFamiliarity(object):
         elif infomax:
             new_views = np.stack([self.get_sensor_mat(points[i], view_headings[i]) for i in range(n)])
             engine.infomax_train_u8(np.ascontiguousarray(new_views[..., self._familiarity_func.channel]))
+        elif mushroom and self._engine is not None and engine is self._engine:
+            # the mushroom-body model keeps depressing the same weights: training has no order
+            for pt in points:
+                self._check_bounds(pt)
+            new_views = self._engine.mb_train_from_poses(points[:, 0], points[:, 1], view_headings)
+        elif mushroom:
+            new_views = np.stack([self.get_sensor_mat(points[i], view_headings[i]) for i in range(n)])
+            engine.mb_train_u8(np.ascontiguousarray(new_views[..., self._familiarity_func.channel]))
         elif self._engine is not None and engine is self._engine and not ssd:
             for pt in points:
                 self._check_bounds(pt)
@@ -338,6 +351,8 @@ class NavBySceneFamiliarity(object):
                 func.engine.clear_library()          # keep the landscape and the sensor configuration
                 if getattr(func, "metric", "") == "infomax":
                     func.engine.infomax_end()
+                if getattr(func, "metric", "") == "mushroom":
+                    func.engine.mb_end()
             else:
                 func.engine.close()
         if getattr(self, "_metrics_on_device", False) and getattr(self, "_engine", None) is not None:
@@ -569,6 +584,9 @@ class NavBySceneFamiliarity(object):
         elif engine is not None and getattr(func, "metric", "") == "infomax":
             self._step_infomax(func, engine, position)
             best_idex = self.last_scored_idex
+        elif engine is not None and getattr(func, "metric", "") == "mushroom":
+            self._step_mushroom(func, engine, position)
+            best_idex = self.last_scored_idex
         elif engine is not None:
             # one fused device step for all headings: kernel + min-merge + max + argmax (:289-315)
             try:
@@ -706,15 +724,26 @@ class NavBySceneFamiliarity(object):
         sensor model the patches are sensed here and scored in one call.  familiarity = -sum|W x|.  The model has no per-view score:
         scene_familiarity is the least familiarity over the headings at every view (what the reference's loop leaves when the plug-in
         fills its buffer with the one value)."""
+        self._step_one_value(func, engine, position, engine.infomax_sense_step, engine.infomax_score_u8)
+
+    def _step_mushroom(self, func, engine, position):
+        """The heading loop (:289-315) with the mushroom-body plug-in (util.mushroom_familiarity): ONE device call -- sense, every
+        heading's Kenyon cells selected and their intact weights counted in one launch, first maximum -- when the sensor model runs on
+        the GPU; otherwise the patches are sensed here and scored in one call.  familiarity = -d, an integer: headings tie, and the
+        first maximum decides as np.argmax does.  scene_familiarity as for the Infomax model."""
+        self._step_one_value(func, engine, position, engine.mb_sense_step, engine.mb_score_u8)
+
+    def _step_one_value(self, func, engine, position, sense_step, score_u8):
+        """A step of a model without per-view memory (Infomax, mushroom body) through its engine's sense_step / score_u8 pair."""
         angles = (self.angle + self.angle_offsets) % (2 * np.pi)
         try:
             if engine is self._engine:
                 self._check_bounds(position)
-                best, _ = engine.infomax_sense_step(position[0], position[1], angles, self.angle_familiarity)
+                best, _ = sense_step(position[0], position[1], angles, self.angle_familiarity)
             else:
                 patches = np.stack([self.get_sensor_mat(position, a) for a in angles])
                 planes = np.ascontiguousarray(patches[..., func.channel] if patches.ndim == 4 else patches)
-                engine.infomax_score_u8(planes, self.angle_familiarity)
+                score_u8(planes, self.angle_familiarity)
                 best = int(np.argmax(self.angle_familiarity))
         except Exception:
             self._scene_fam[:] = np.inf

@@ -884,3 +884,94 @@ class FamiliarityEngine(object):
     def infomax_end(self):
         self._check(self._lib.dv_infomax_end(self._ctx), "dv_infomax_end")
         self.infomax_shape = None
+
+    # -- mushroom-body familiarity model: a fixed fan-in and one byte of weight per Kenyon cell (include/dejavu.h: dv_mb_*) --------
+    def mb_begin(self, h, w, conn, n_active, channel=2):
+        """conn: int32[n_kc, fan_in], the pixels each Kenyon cell listens to (drawn by the caller: util.mushroom_connectivity).
+        Copied to the GPU; the weights start at 1."""
+        conn = np.ascontiguousarray(conn, dtype=np.int32)
+        if conn.ndim != 2:
+            raise ValueError("conn must be int32[n_kc, fan_in], got shape %r" % (conn.shape,))
+        self._check(self._lib.dv_mb_begin(self._ctx, int(h), int(w), int(channel), conn.shape[0], conn.shape[1], int(n_active),
+                                          conn.ctypes.data_as(N._i32p)), "dv_mb_begin")
+        self.mb_shape = (int(h), int(w))
+
+    def _mb_planes(self, planes, what):
+        planes = N.as_u8(planes, what)
+        shape = getattr(self, "mb_shape", None)
+        if planes.ndim == 2:
+            planes = planes[None]
+        if shape is None:
+            return planes if planes.ndim == 3 else planes.reshape(1, 1, -1)      # (no model: the library answers DV_ERR_STATE)
+        if planes.ndim != 3 or tuple(planes.shape[1:]) != shape:
+            raise ValueError("%s must be uint8[n,%d,%d], got shape %r" % ((what,) + shape + (planes.shape,)))
+        return planes
+
+    def mb_train_u8(self, planes):
+        """Depress the cells that fire for each of uint8[n,h,w] planes: one launch for all of them, in no order."""
+        planes = self._mb_planes(planes, "planes")
+        self._check(self._lib.dv_mb_train_u8(self._ctx, N.u8ptr(planes), planes.shape[0]), "dv_mb_train_u8")
+
+    def mb_train_from_poses(self, x, y, angle, want_views=True):
+        """train_from_path for the mushroom-body plug-in on the device: sense the poses, train on their compared plane; returns
+        familiar_scenes (uint8[n,h,w,3]) when want_views."""
+        x, y, angle = self._pose_arrays(x, y, angle)
+        h, w = self.sensor_shape
+        views = np.empty((len(x), h, w, 3), dtype=np.uint8) if want_views else None
+        self._check_sense(self._lib.dv_mb_train_from_poses(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), len(x),
+                                                           N.u8ptr(views) if want_views else None), "dv_mb_train_from_poses")
+        return views
+
+    def mb_score_u8(self, planes, out=None):
+        """familiarity = -(firing cells whose weight is intact) of each of uint8[n,h,w] planes (or one uint8[h,w]) -> float64[n]."""
+        planes = self._mb_planes(planes, "planes")
+        if out is None:
+            out = np.empty(planes.shape[0], dtype=np.float64)
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.size == planes.shape[0]
+        self._check(self._lib.dv_mb_score_u8(self._ctx, N.u8ptr(planes), planes.shape[0], N.f64ptr(out)), "dv_mb_score_u8")
+        return out
+
+    def mb_activity_u8(self, planes):
+        """Which cells each of uint8[n,h,w] planes excites -> (fired uint8[n, n_kc], threshold int32[n]: the least activity that fires)."""
+        planes = self._mb_planes(planes, "planes")
+        fired = np.empty((planes.shape[0], self.mb_info()["n_kc"]), dtype=np.uint8)
+        thr = np.empty(planes.shape[0], dtype=np.int32)
+        self._check(self._lib.dv_mb_activity_u8(self._ctx, N.u8ptr(planes), planes.shape[0], N.u8ptr(fired), thr.ctypes.data_as(N._i32p)),
+                    "dv_mb_activity_u8")
+        return fired, thr
+
+    def mb_sense_step(self, x, y, angles, out_fam=None):
+        """One agent step: sense the heading patches at (x, y), score them, first maximum -> (best_idex, angle_familiarity)."""
+        angles = np.ascontiguousarray(angles, dtype=np.float64).reshape(-1)
+        if out_fam is None:
+            out_fam = np.empty(len(angles), dtype=np.float64)
+        assert out_fam.dtype == np.float64 and out_fam.flags.c_contiguous and out_fam.size == len(angles)
+        best = ctypes.c_int32(-1)
+        self._check_sense(self._lib.dv_mb_sense_step(self._ctx, float(x), float(y), N.f64ptr(angles), len(angles), N.f64ptr(out_fam),
+                                                     ctypes.byref(best)), "dv_mb_sense_step")
+        return int(best.value), out_fam
+
+    def mb_info(self):
+        k, n, c, act = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        views, zeros, nbytes = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self._lib.dv_mb_info(self._ctx, ctypes.byref(k), ctypes.byref(n), ctypes.byref(c), ctypes.byref(act), ctypes.byref(views),
+                                         ctypes.byref(zeros), ctypes.byref(nbytes)), "dv_mb_info")
+        return dict(n_kc=k.value, n_pixels=n.value, fan_in=c.value, n_active=act.value, views_trained=views.value,
+                    n_depressed=zeros.value, bytes=nbytes.value)
+
+    def mb_read_weights(self):
+        """uint8[n_kc], 1 or 0: what a user saves (np.save) and hands to mb_set_weights later."""
+        out = np.empty(max(self.mb_info()["n_kc"], 1), dtype=np.uint8)
+        self._check(self._lib.dv_mb_read_weights(self._ctx, N.u8ptr(out)), "dv_mb_read_weights")
+        return out
+
+    def mb_set_weights(self, weights):
+        n_kc = self.mb_info()["n_kc"]
+        weights = N.as_u8(weights, "weights")
+        if n_kc and weights.shape != (n_kc,):
+            raise ValueError("weights must be uint8[%d], got shape %r" % (n_kc, weights.shape))
+        self._check(self._lib.dv_mb_set_weights(self._ctx, N.u8ptr(weights)), "dv_mb_set_weights")
+
+    def mb_end(self):
+        self._check(self._lib.dv_mb_end(self._ctx), "dv_mb_end")
+        self.mb_shape = None

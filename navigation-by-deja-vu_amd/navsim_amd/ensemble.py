@@ -19,7 +19,7 @@ single agent works its minimum out when it is read.
 import numpy as np
 
 from .agent import StopNavigationException, OutOfLandscapeBoundsException
-from .util import reject_infomax
+from .util import reject_infomax, reject_mushroom
 
 
 class NavEnsemble(object):
@@ -279,6 +279,7 @@ class InfomaxEnsemble(NavEnsemble):
     @classmethod
     def _check_member(cls, agent):
         func = getattr(agent, "_familiarity_func", None)
+        reject_mushroom(agent, "InfomaxEnsemble")
         if getattr(getattr(agent, "familiarity_model", None), "metric", None) != "infomax":
             raise ValueError("InfomaxEnsemble takes agents of the Infomax model (familiarity_model=infomax_familiarity(...)); "
                              "NavEnsemble steps the library-based models")

@@ -148,6 +148,15 @@ def reject_infomax(model, what):
         if getattr(obj, "metric", None) == "infomax":
             raise ValueError("%s does not take an Infomax model: it batches or shards a view library, and infomax_familiarity keeps "
                              "none (step each agent on its own engine, or use navsim_amd.InfomaxEnsemble)" % what)
+    reject_mushroom(model, what)
+
+
+def reject_mushroom(model, what):
+    """The same refusal for the mushroom-body model (mushroom_familiarity): it keeps no library either, and its ensembles are not built."""
+    for obj in (model, getattr(model, "familiarity_model", None), getattr(model, "_familiarity_func", None)):
+        if getattr(obj, "metric", None) == "mushroom":
+            raise ValueError("%s does not take a mushroom-body model: it batches or shards a view library (or one Infomax weight "
+                             "matrix), and mushroom_familiarity keeps neither (step each agent on its own engine)" % what)
 
 
 def infomax_initial_weights(n_hidden, n_pixels, seed=0):
@@ -237,3 +246,92 @@ def infomax_familiarity(channel=2, learning_rate=0.01, seed=0, n_hidden=None, de
     infomax_familiarity_internal.channel = channel
     infomax_familiarity_internal.learning_rate = learning_rate
     return infomax_familiarity_internal
+
+
+def mushroom_connectivity(n_kc, n_pixels, fan_in, seed=0):
+    """The mushroom-body model's fan-in, int32[n_kc, fan_in], drawn on the host: the pixels each Kenyon cell listens to, from
+    np.random.default_rng(seed).integers(0, n_pixels, (n_kc, fan_in)).  A pixel repeated in a row counts twice."""
+    return np.random.default_rng(seed).integers(0, int(n_pixels), (int(n_kc), int(fan_in))).astype(np.int32)
+
+
+def mushroom_familiarity(channel=2, n_kc=20000, fan_in=10, sparsity=0.01, seed=0, device=0, devices=None):
+    """The mushroom-body circuit of Ardin, Peng, Mangan, Lagogiannis & Webb (2016) as a familiarity plug-in of the reference's shape
+    (util.pyx:10-25): a memory of fixed size and finite capacity -- one byte of output weight per Kenyon cell -- where sads_familiarity
+    and ssd_familiarity keep every view and infomax_familiarity a float64 matrix.
+
+    stage 1  mushroom_familiarity(channel, n_kc, fan_in, sparsity, seed)   the compared channel of HSV scenes (0 H, 1 S, 2 V), the number
+                                                       of Kenyon cells, the pixels each listens to (1..16), the fraction of cells that
+                                                       fire for a view (n_active = max(1, round(sparsity * n_kc))) and the seed of the
+                                                       fan-in (mushroom_connectivity)
+    stage 2  model(scenes) -> func                     trains on uint8[F,h,w,3] / uint8[F,h,w] on the device, all views in one launch
+    func(scene, fambuf: float64[F])                    writes the ONE value -d(scene) into EVERY entry of fambuf, as infomax_familiarity
+                                                       does: the model keeps no per-view memory
+    func.max_familiarity = 0.0
+
+    A cell's activity is the sum of its pixels; the n_active most excited fire (larger sum first, then lower index: the sensor's planes
+    have five levels, so the tie rule decides at every view); training clears the weight of every cell that fired, and d is the number
+    of a view's firing cells whose weight is intact: 0 for a trained view, n_active at most.  Integer from pixel to score, so exact.
+    Extras carried by `func`: func.engine (engine.mb_read_weights() / mb_set_weights() save and restore the model,
+    engine.mb_info()["n_depressed"] tells how full it is), func.metric ("mushroom"), func.channel.
+    """
+    if devices is not None:
+        raise ValueError("mushroom_familiarity runs on one device (device=...): FamiliarityGroup cuts a view library over several, and "
+                         "this model keeps none")
+    if channel not in (0, 1, 2):
+        raise ValueError("channel must be 0 (H), 1 (S) or 2 (V), got %r" % (channel,))
+    if not (isinstance(n_kc, (int, np.integer)) and not isinstance(n_kc, bool) and n_kc >= 1):
+        raise ValueError("n_kc must be a positive integer, got %r" % (n_kc,))
+    if not (isinstance(fan_in, (int, np.integer)) and not isinstance(fan_in, bool) and 1 <= fan_in <= 16):
+        raise ValueError("fan_in must be an integer in [1, 16], got %r" % (fan_in,))
+    if not (isinstance(sparsity, (int, float, np.floating, np.integer)) and not isinstance(sparsity, bool) and 0 < sparsity <= 1):
+        raise ValueError("sparsity must be a number in (0, 1], got %r" % (sparsity,))
+    n_active = max(1, int(round(sparsity * n_kc)))
+
+    def plane(a, lead):
+        a = np.asarray(a)
+        if a.ndim == lead + 3:
+            a = a[..., channel]
+        if a.ndim != lead + 2:
+            raise ValueError("scene array has shape %r" % (a.shape,))
+        return np.ascontiguousarray(a)
+
+    def begin(engine, h, w):
+        """A fresh model of h x w views on `engine` (the agent calls this before it trains from poses)."""
+        engine.mb_begin(h, w, mushroom_connectivity(n_kc, int(h) * int(w), fan_in, seed), n_active, channel)
+
+    def bind(engine, scenes=None):
+        def func(scene, fambuf):
+            if not (isinstance(fambuf, np.ndarray) and fambuf.dtype == np.float64):
+                raise ValueError("Buffer dtype mismatch for fambuf, expected 'double'")
+            fambuf[...] = engine.mb_score_u8(plane(scene, 0))[0]
+
+        func.max_familiarity = 0.0
+        func.engine = engine
+        func.metric = "mushroom"
+        func.channel = channel
+        return func
+
+    def mushroom_familiarity_internal(scenes):
+        scenes = np.asarray(scenes)
+        if scenes.dtype != np.uint8:
+            raise ValueError("Buffer dtype mismatch, expected 'uint8_t' but got '%s'" % scenes.dtype)
+        planes = plane(scenes, 1)
+        engine = FamiliarityEngine(device=device)
+        try:
+            begin(engine, planes.shape[1], planes.shape[2])
+            engine.mb_train_u8(planes)
+        except Exception:
+            engine.close()
+            raise
+        return bind(engine)
+
+    # hooks for navsim_amd.NavBySceneFamiliarity (landscape, sensor model and training on the GPU: see sads_familiarity)
+    mushroom_familiarity_internal.make_engine = lambda: FamiliarityEngine(device=device)
+    mushroom_familiarity_internal.from_engine = bind
+    mushroom_familiarity_internal.begin = begin
+    mushroom_familiarity_internal.metric = "mushroom"
+    mushroom_familiarity_internal.channel = channel
+    mushroom_familiarity_internal.n_kc = n_kc
+    mushroom_familiarity_internal.fan_in = fan_in
+    mushroom_familiarity_internal.n_active = n_active
+    return mushroom_familiarity_internal

@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""Times the mushroom-body familiarity model (navsim_amd.mushroom_familiarity; include/dejavu.h: dv_mb_*) on GPU 0 and writes
+profiles/mushroom_time.json.
+
+    python tools/mushroom_time.py [--sides 32,64] [--views 1000] [--calls 200] [--reps 5] [--out profiles/mushroom_time.json]
+
+Per sensor side s (views of s x s) with K = 20000 Kenyon cells, fan-in 10 and 200 firing cells: microseconds per agent step
+(dv_mb_sense_step: sensing, one scoring launch over all headings, the decision and the read-back) for 16 and for 60 headings, and
+microseconds to train --views sensed views (dv_mb_train_from_poses without the views' read-back: sensing and one training launch),
+each the median of --reps timed windows after a warm-up of the same shape, from a hipEvent pair on the context's stream
+(dv_timer_start / dv_timer_stop) with the spread (min, max) beside it.  For context, from the same child process: the Infomax
+model's step (dv_infomax_sense_step, N x N weights) at the same shapes; and from this host's CPU, wall clock: the NumPy statement
+of the model (tests/helpers_mushroom.py) scoring the same number of patches.
+
+Every GPU measurement runs in a child process of its own under a time limit, and nothing more is started on the GPU after one
+that failed."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "navigation-by-deja-vu_amd"))
+sys.path.insert(0, ROOT)
+
+HEADINGS = (16, 60)                                               # 60: the reference's default n_test_angles
+K, FAN_IN, N_ACTIVE = 20000, 10, 200
+
+
+def spread(samples):
+    return dict(median=round(float(np.median(samples)), 3), min=round(float(min(samples)), 3), max=round(float(max(samples)), 3))
+
+
+def gpu_child(side, n_views, n_calls, reps):
+    """One size on the GPU -> one JSON line on stdout."""
+    from navsim_amd import NavBySceneFamiliarity, mushroom_familiarity, synth
+    from navsim_amd.util import infomax_initial_weights, mushroom_connectivity
+    N = side * side
+    land = synth.synth_landscape(3, 600, 4)
+    agent = NavBySceneFamiliarity(land, (side, side), 1.0, n_test_angles=HEADINGS[-1], familiarity_model=mushroom_familiarity())
+    eng = agent._engine                                           # (landscape and sensor attached)
+    out = dict(side=side, N=N, n_kc=K, fan_in=FAN_IN, n_active=N_ACTIVE, calls_per_window=n_calls, views_per_window=n_views)
+    conn = mushroom_connectivity(K, N, FAN_IN, 0)
+    rng = np.random.default_rng(side)
+    xs, ys, angs = rng.uniform(150, 450, n_views), rng.uniform(150, 450, n_views), rng.uniform(0, 2 * np.pi, n_views)
+
+    def train_window():
+        eng.mb_begin(side, side, conn, N_ACTIVE, 2)
+        eng.timer_start()
+        eng.mb_train_from_poses(xs, ys, angs, want_views=False)
+        return eng.timer_stop() * 1e3                             # us per n_views views
+
+    train_window()                                                # warm-up (code load, clocks, the buffers)
+    out["train_us_per_%d_views" % n_views] = spread([train_window() for _ in range(reps)])
+    info = eng.mb_info()
+    out["n_depressed_after_training"] = info["n_depressed"]
+    assert info["views_trained"] == n_views and 0 < info["n_depressed"] <= K
+
+    def step_windows(step, A):
+        angles = (0.3 + np.linspace(-np.pi / 2, np.pi / 2, A)) % (2 * np.pi)
+        fam = np.empty(A)
+
+        def window():
+            eng.timer_start()
+            for _ in range(n_calls):
+                step(300.0, 300.0, angles, fam)
+            return eng.timer_stop() * 1e3 / n_calls               # us per step
+        window()
+        return spread([window() for _ in range(reps)])
+
+    for A in HEADINGS:
+        out["mb_sense_step_us_A%d" % A] = step_windows(eng.mb_sense_step, A)
+    eng.mb_end()
+    eng.infomax_begin(side, side, infomax_initial_weights(N, N, 0), 2, 0.001)
+    for A in HEADINGS:
+        out["infomax_sense_step_us_A%d" % A] = step_windows(eng.infomax_sense_step, A)
+    eng.close()
+    print(json.dumps(out))
+
+
+def cpu_row(side, n_calls):
+    """The NumPy statement on this host: wall clock, microseconds per call that scores A patches."""
+    from tests import helpers_mushroom as H
+    N = side * side
+    conn = H.connectivity(K, N, FAN_IN, 0)
+    wt = H.train(np.ones(K, np.uint8), H.route_views(1, 8, side, side), conn, N_ACTIVE)
+    row = {}
+    for A in HEADINGS:
+        patches = H.route_views(2, A, side, side)
+        t0 = time.perf_counter()
+        for _ in range(n_calls):
+            H.familiarity(wt, patches, conn, N_ACTIVE)
+        row["score_us_per_call_A%d" % A] = round((time.perf_counter() - t0) * 1e6 / n_calls, 1)
+    return row
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sides", default="32,64")
+    ap.add_argument("--views", type=int, default=1000)
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--limit", type=int, default=240, help="seconds allowed to each GPU child")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mushroom_time.json"))
+    ap.add_argument("--child", type=int, default=0, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:
+        gpu_child(args.child, args.views, args.calls, args.reps)
+        return 0
+    result = dict(tool="tools/mushroom_time.py", timer="hipEvent pair (dv_timer_start/stop), median of %d windows after a warm-up" % args.reps,
+                  sizes=[])
+    for side in [int(x) for x in args.sides.split(",")]:
+        cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child", str(side), "--views", str(args.views),
+               "--calls", str(args.calls), "--reps", str(args.reps)]
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, universal_newlines=True)
+        if p.returncode != 0:
+            print("GPU measurement of side %d ended with status %d: nothing more is run" % (side, p.returncode), file=sys.stderr)
+            return p.returncode
+        row = json.loads(p.stdout.strip().splitlines()[-1])
+        row["numpy_cpu"] = cpu_row(side, 3)
+        result["sizes"].append(row)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print(json.dumps(result))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -183,9 +183,10 @@ static int mb_need(dv_ctx* c, const char* who) {
     return DV_OK;
 }
 
-static size_t mb_lds_bytes(const dv_ctx* c) {
-    return (size_t)((c->mb_N + 3) & ~3) + (size_t)kMbWaves * (size_t)(255 * c->mb_c + 1) * 4u + 16u * 4u;
+static size_t mb_lds_bytes(int N, int fan_in) {
+    return (size_t)((N + 3) & ~3) + (size_t)kMbWaves * (size_t)(255 * fan_in + 1) * 4u + 16u * 4u;
 }
+static size_t mb_lds_bytes(const dv_ctx* c) { return mb_lds_bytes(c->mb_N, c->mb_c); }
 
 // Views of one launch when each brings `bytes_per_view` of staged bytes.
 static int64_t mb_slab(size_t bytes_per_view) {
@@ -241,7 +242,11 @@ extern "C" int dv_mb_begin(dv_ctx* c, int h, int w, int channel, int n_kc, int f
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     mb_free(c);
     c->mb_K = n_kc; c->mb_N = N; c->mb_c = fan_in; c->mb_active = n_active; c->mb_hh = h; c->mb_ww = w; c->mb_channel = channel;
-    const int lds = (int)mb_lds_bytes(c);                    // at most 65536 + 4 * 4081 * 4 + 64 = 130896 of the workgroup's 160 KB
+    // The cap on dynamic LDS belongs to the FUNCTION, not to this context: set to this model's own bytes, the begin of a small model in
+    // one context would lower it under the launches of a larger model in another.  So it is the most any model can ask for, whatever
+    // this one needs: 65536 + 4 * 4081 * 4 + 64 = 130896 of the workgroup's 160 KB.  A cap, not an allocation: a launch still takes
+    // mb_lds_bytes(c) of its own model.
+    const int lds = (int)mb_lds_bytes(kMbMaxPixels, dv::kMbMaxFanIn);
     hipError_t e = hipMalloc((void**)&c->mb_conn, ct.size() * sizeof(unsigned short));
     if (e == hipSuccess) e = hipMalloc((void**)&c->mb_wt, K);
     if (e == hipSuccess) e = hipMalloc((void**)&c->mb_zeros, sizeof(long long));

@@ -3,8 +3,15 @@ so every comparison is exact -- np.array_equal, floats through their uint64 view
 
 Shapes (H.CASES): K below one wave with c close to N; one winner taken from the tie bin; ragged K with more than 64 headings; the
 default K = 20000 (many trips per wave) with N % 4 != 0; the widest histogram (c = 16: 4081 bins) with odd N; the largest plane that
-fits in LDS (128 x 128) with K = 8 * 256 + 1; n_active = K; c = 1 with a tie bin far wider than the quota; constant and two-level
-planes, where every cell ties and exactly the first n_active must fire across every wave's span."""
+fits in LDS (128 x 128) with K = 8 * 256 + 1; n_active = K; c = 1 with a tie bin far wider than the quota; 256 x 256, the widest plane
+the model takes: pixel indices with the top bit of their uint16 set and the largest LDS request (130896 B), checked for content;
+constant and two-level planes, where every cell ties and exactly the first n_active must fire across every wave's span -- also under
+quotas that run past wave 0's first trip, past its span and into the third wave (H.LONG_QUOTA).
+
+Beyond one launch and one trip: calls whose views cross the view bound of a launch (kMbSlabViews) and the byte bound (kMbStageBytes) --
+training and scoring of planes, the activity call's per-slab copies, training from poses, the agent's step -- always two distinct views
+repeated, so that the NumPy side stays two rows; k_mb_decide over more than 256 headings, with ties planted between its first and
+second trip; two engines whose models need different amounts of LDS, used in turn."""
 import ctypes
 
 import numpy as np
@@ -76,6 +83,21 @@ def test_constant_and_two_level_planes(eng, key):
     assert np.array_equal(H.bits(eng.mb_score_u8(k["planes"])), H.bits(k["fam"]))
 
 
+@pytest.mark.parametrize("n_active", H.LONG_QUOTA["n_active"])
+def test_a_quota_that_runs_past_the_first_cells(eng, n_active):
+    """Every cell ties and the quota is not used up inside wave 0's first trip: the wave's starting rank, the equals of its earlier
+    trips and the ballot's lower lanes all decide (masks and fresh scores only: one such view would clear most of the weights)."""
+    q = H.quota_data(n_active)
+    eng.mb_begin(q["h"], q["w"], q["conn"], n_active, 2)
+    mask, thr = eng.mb_activity_u8(q["planes"])
+    assert np.array_equal(thr, q["thr"]), (thr, q["thr"])
+    assert np.array_equal(mask, q["mask"]), [np.flatnonzero(m != w)[:8].tolist() for m, w in zip(mask, q["mask"])]
+    for row in (0, 1):                                                   # all 0, all 255: the cells 0 .. n_active-1 and no others
+        assert mask[row, :n_active].all() and not mask[row, n_active:].any()
+    assert thr[0] == 0 and thr[1] == 255 * q["c"]
+    assert np.array_equal(H.bits(eng.mb_score_u8(q["planes"])), H.bits(np.full(3, -float(n_active))))
+
+
 # ---- 2. weights ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("key", list(H.CASES))
 def test_weights_after_training(eng, key):
@@ -135,6 +157,58 @@ def test_training_across_the_slab():
         e.close()
 
 
+def test_training_and_scoring_across_the_byte_bound(eng):
+    """128x128 planes: 64 MiB of them, not kMbSlabViews, end a launch.  `slab` copies of one view, then ONE other view."""
+    views_bound, stage = H.slab_views()
+    t = H.slab_train_data()
+    slab = stage // t["N"]
+    assert slab < views_bound and (slab + 1) * t["N"] > stage            # it is the bytes that end the slab
+    views = np.ascontiguousarray(np.concatenate([np.repeat(t["two"][:1], slab, axis=0), t["two"][1:]]))
+    assert not np.array_equal(t["both"], t["first"])                     # (the last view matters)
+    eng.mb_begin(t["h"], t["w"], t["conn"], t["n_active"], 2)
+    eng.mb_train_u8(views)
+    assert np.array_equal(eng.mb_read_weights(), t["both"])
+    assert eng.mb_info()["views_trained"] == slab + 1 and eng.mb_info()["n_depressed"] == int((t["both"] == 0).sum())
+    fam = eng.mb_score_u8(views)
+    assert fam.shape == (slab + 1,) and not H.bits(fam).any()            # every view trained: +0.0
+    eng.mb_set_weights(t["first"])
+    fam = eng.mb_score_u8(views)
+    last = H.familiarity(t["first"], t["two"][1:], t["conn"], t["n_active"])
+    assert last[0] < 0 and not H.bits(fam[:slab]).any() and H.bits(fam[slab:])[0] == H.bits(last)[0], (fam[slab - 2:], last)
+
+
+def test_activity_across_the_byte_bound_and_its_optional_outputs(eng):
+    """K = 20000: the fired masks (20000 bytes a view) end a launch of the activity call.  Copies of patch 0, then patch 1: the masks
+    and thresholds of the second launch must land behind those of the first.  Then fired = NULL and threshold = NULL, one at a time."""
+    views_bound, stage = H.slab_views()
+    d = H.case_data(H.SLAB_ACTIVITY["key"])
+    slab = stage // d["K"]
+    assert slab < views_bound and slab < stage // d["N"]
+    begin(eng, d)
+    planes = np.ascontiguousarray(np.concatenate([np.repeat(d["patches"][:1], slab, axis=0), d["patches"][1:2]]))
+    mask, thr = eng.mb_activity_u8(planes)
+    assert mask.shape == (slab + 1, d["K"]) and thr.shape == (slab + 1,)
+    assert not np.array_equal(d["mask"][0], d["mask"][1]) and d["thr"][0] != d["thr"][1]
+    assert np.array_equal(thr[:slab], np.full(slab, d["thr"][0], np.int32)) and thr[slab] == d["thr"][1], (thr[:2], thr[slab - 2:])
+    assert np.array_equal(mask[slab], d["mask"][1])
+    assert np.array_equal(mask[slab - 1], d["mask"][0]) and np.array_equal(mask[0], d["mask"][0])
+    assert (mask[:slab] == d["mask"][0]).all()
+    # either output may be NULL
+    three = np.ascontiguousarray(d["patches"][:3])
+    full_mask, full_thr = eng.mb_activity_u8(three)
+    assert np.array_equal(full_mask, d["mask"][:3]) and np.array_equal(full_thr, d["thr"][:3])
+    only_thr = np.full(3, -7, dtype=np.int32)
+    assert eng._lib.dv_mb_activity_u8(eng._ctx, N.u8ptr(three), 3, None, only_thr.ctypes.data_as(N._i32p)) == 0
+    assert np.array_equal(only_thr, full_thr)
+    only_mask = np.full((3, d["K"]), 7, dtype=np.uint8)
+    assert eng._lib.dv_mb_activity_u8(eng._ctx, N.u8ptr(three), 3, N.u8ptr(only_mask), None) == 0
+    assert np.array_equal(only_mask, full_mask)
+    assert eng._lib.dv_mb_activity_u8(eng._ctx, N.u8ptr(three), 3, None, None) == 0
+    # the engine goes on working
+    eng.mb_set_weights(d["wt"])
+    assert np.array_equal(H.bits(eng.mb_score_u8(d["patches"])), H.bits(d["fam"]))
+
+
 # ---- 5. weights round trip -------------------------------------------------------------------------------------------------------
 def test_set_weights_round_trip_and_a_second_engine(eng):
     d = H.case_data("16x16_k1043")
@@ -158,14 +232,39 @@ def test_set_weights_round_trip_and_a_second_engine(eng):
         other.close()
 
 
+def check_model(e, d):
+    """The engine's model is `d`'s, trained: its weights, the scores and the activity of its patches are the restatement's."""
+    assert np.array_equal(e.mb_read_weights(), d["wt"])
+    assert np.array_equal(H.bits(e.mb_score_u8(d["patches"])), H.bits(d["fam"]))
+    mask, thr = e.mb_activity_u8(d["patches"])
+    assert np.array_equal(thr, d["thr"]) and np.array_equal(mask, d["mask"])
+
+
+@pytest.mark.parametrize("key", ["33x31_k4100_c16", "256x256_k1043_c16"])
+def test_two_engines_with_models_of_different_lds_size(key):
+    """The cap on a kernel's dynamic LDS belongs to the function, not to an engine: the begin of a small model in one engine must not
+    lower it under the launches of a model of more than 64 KB in another."""
+    big, small = H.case_data(key), H.case_data("5x3_k37")
+    a, b = navsim_amd.FamiliarityEngine(device=0), navsim_amd.FamiliarityEngine(device=0)
+    try:
+        begin(a, big)
+        a.mb_train_u8(big["views"])
+        begin(b, small)
+        b.mb_train_u8(small["views"])
+        check_model(b, small)
+        check_model(a, big)
+        check_model(b, small)
+        assert np.array_equal(H.bits(a.mb_score_u8(big["views"])), H.bits(np.zeros(big["F"])))
+    finally:
+        a.close()
+        b.close()
+
+
 # ---- 6, 7. poses ---------------------------------------------------------------------------------------------------------------------
 POSE_MODEL = dict(n_kc=4100, fan_in=10, sparsity=0.01, seed=41)
 
 
-def pose_headings(path):
-    steps = path[1:] - path[:-1]
-    headings = np.arctan2(steps[:, 1], steps[:, 0])
-    return headings[np.minimum(np.arange(len(path)), len(path) - 2)]
+pose_headings = H.route_headings
 
 
 @pytest.fixture(scope="module")
@@ -221,6 +320,95 @@ def test_sense_step_is_score_on_the_sensed_planes(sensed, n_headings):
     # every heading the same view: all scores tie and the first wins
     best, fam = e.mb_sense_step(x, y, np.full(n_headings, 0.4))
     assert best == 0 and len(np.unique(fam)) == 1
+
+
+def v_planes(e, x, y, angles):
+    angles = np.asarray(angles, dtype=np.float64)
+    return np.ascontiguousarray(e.sense(np.full(len(angles), x), np.full(len(angles), y), angles)[..., 2])
+
+
+def test_training_from_poses_across_the_view_bound(sensed):
+    """kMbSlabViews copies of one pose and then ONE other pose: the second launch of dv_mb_train_from_poses reads behind the first's
+    views and brings cells that the first did not depress."""
+    e = sensed[0]._engine
+    slab, _ = H.slab_views()
+    m = H.SLAB_POSES
+    conn = H.connectivity(m["K"], 1024, m["c"], m["seed"])
+    ones = np.ones(m["K"], np.uint8)
+    path = HI.sensed_route()
+    p = path[list(m["poses"])]
+    ang = pose_headings(path)[list(m["poses"])]
+    two = np.ascontiguousarray(e.sense(p[:, 0], p[:, 1], ang)[..., 2])
+    assert np.array_equal(two, H.host_sensed_planes(p[:, 0], p[:, 1], ang))
+    want = H.train(ones, two, conn, m["n_active"])
+    assert not np.array_equal(want, H.train(ones, two[:1], conn, m["n_active"]))        # (the last pose matters)
+    e.mb_begin(32, 32, conn, m["n_active"], 2)
+    rep = np.r_[np.zeros(slab, dtype=np.int64), 1]
+    assert e.mb_train_from_poses(p[rep, 0], p[rep, 1], ang[rep], want_views=False) is None
+    assert np.array_equal(e.mb_read_weights(), want)
+    assert e.mb_info()["views_trained"] == slab + 1 and e.mb_info()["n_depressed"] == int((want == 0).sum())
+
+
+def test_sense_step_across_the_view_bound(sensed):
+    """kMbSlabViews copies of one heading and then ONE other: the second scoring launch writes its d behind the first's."""
+    e = sensed[0]._engine
+    slab, _ = H.slab_views()
+    m = H.SLAB_POSES
+    conn = H.connectivity(m["K"], 1024, m["c"], m["seed"])
+    ones = np.ones(m["K"], np.uint8)
+    x, y = H.step_xy()
+    two = v_planes(e, x, y, m["angles"])
+    assert np.array_equal(two, H.host_sensed_planes(x, y, m["angles"]))
+    rep = np.r_[np.zeros(slab, dtype=np.int64), 1]
+    angles = np.asarray(m["angles"])[rep]
+    e.mb_begin(32, 32, conn, m["n_active"], 2)
+    # trained on the LAST heading's view alone: it wins, at index kMbSlabViews
+    wt = H.train(ones, two[1:], conn, m["n_active"])
+    e.mb_set_weights(wt)
+    best, fam = e.mb_sense_step(x, y, angles)
+    want = H.familiarity(wt, two, conn, m["n_active"])[rep]
+    assert fam.shape == (slab + 1,) and np.array_equal(H.bits(fam), H.bits(want)), (fam[:2], fam[slab - 2:], want[[0, -1]])
+    assert H.bits(fam[-1:])[0] == 0 and fam[0] < 0 and len(np.unique(fam[:-1])) == 1
+    assert best == slab
+    # trained on the FIRST heading's view alone: heading 0 wins over its 8191 equals
+    wt = H.train(ones, two[:1], conn, m["n_active"])
+    e.mb_set_weights(wt)
+    best, fam = e.mb_sense_step(x, y, angles)
+    want = H.familiarity(wt, two, conn, m["n_active"])[rep]
+    assert np.array_equal(H.bits(fam), H.bits(want)), (fam[:2], fam[slab - 2:], want[[0, -1]])
+    assert best == 0 and fam[-1] < 0
+
+
+def test_decide_beyond_its_first_trip(sensed):
+    """k_mb_decide strides 256 threads over the headings: 300 of them, then ties planted between a first-trip and a second-trip
+    heading, inside one thread across trips, and a single maximum in the second trip."""
+    agent, model = sensed
+    e = agent._engine
+    path = HI.sensed_route()
+    model.begin(e, 32, 32)
+    e.mb_train_from_poses(path[:, 0], path[:, 1], pose_headings(path), want_views=False)
+    wt = e.mb_read_weights()
+    conn = H.connectivity(4100, 1024, 10, POSE_MODEL["seed"])
+    x, y = H.step_xy()
+
+    def step(angles):
+        best, fam = e.mb_sense_step(x, y, angles)
+        want = H.familiarity(wt, v_planes(e, x, y, angles), conn, 41)
+        assert np.array_equal(H.bits(fam), H.bits(want)), np.flatnonzero(fam != want)[:8]
+        assert best == int(np.argmax(want)), (best, int(np.argmax(want)))
+        return best, want
+
+    angles = H.circle_angles(300)
+    assert len(np.unique(angles)) == 300
+    _, want = step(angles)
+    assert want.max() > want.min() and np.all(want <= 0)
+    b, m = angles[int(np.argmax(want))], angles[int(np.argmin(want))]
+    for planted, winner in (((200, 257), 200), ((257,), 257), ((1, 257), 1), ((299, 257), 257)):
+        arranged = np.where(want == want.max(), m, angles)
+        arranged[list(planted)] = b
+        best, got = step(arranged)
+        assert np.flatnonzero(got == got.max()).tolist() == sorted(planted) and got.max() == want.max(), planted
+        assert best == winner, (planted, best)
 
 
 # ---- 8, 9. behind the agent ----------------------------------------------------------------------------------------------------------

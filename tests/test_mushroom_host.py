@@ -1,5 +1,8 @@
 """Mushroom-body familiarity model, host side: the C ABI's surface, the factory's argument checks, the refusals of the batched and
-sharded forms, and the properties of the NumPy restatement the GPU tests compare against (tests/helpers_mushroom.py)."""
+sharded forms, and the properties of the NumPy restatement the GPU tests compare against (tests/helpers_mushroom.py) -- among them
+what the inputs of the GPU tests must distinguish, so that a later change of a seed or a shape cannot hollow one out: the widest case
+under 15-bit indices, the waves and trips that the long quotas choose their equals from, the two views of every slab test, and the
+poses and headings of the sensed ones (taken here with the host sensor model, which is byte-equal to the device's)."""
 import os
 import re
 
@@ -170,6 +173,82 @@ def test_constant_planes_fire_the_first_cells(key):
     assert k["planes"].shape == (3, d["h"], d["w"]) and k["mask"].sum(axis=1).tolist() == [d["n_active"]] * 3
     assert k["thr"][0] == 0 and k["thr"][1] == 255 * d["c"] and 0 <= k["thr"][2] <= 255 * d["c"]
     assert len(np.unique(H.activity(k["planes"][2:], d["conn"]))) > 2           # the two-level plane spreads the cells
+
+
+def test_the_widest_case_needs_all_sixteen_index_bits():
+    d = H.case_data("256x256_k1043_c16")
+    assert d["N"] == 65536 and d["conn"].max() >= 65000 and 0.45 < float((d["conn"] >= 32768).mean()) < 0.55
+    low_mask, low_thr = H.fired_mask(d["patches"], d["conn"] & 0x7fff, d["n_active"])
+    print("mushroom 256x256: thresholds %r, with 15-bit indices %r" % (d["thr"].tolist(), low_thr.tolist()))
+    assert (low_mask != d["mask"]).any(axis=1).all()                          # (case_data asserts it too)
+    ties = H.tie_counts(d["patches"], d["conn"], d["n_active"])
+    assert sum(at > d["n_active"] - ab for ab, at in ties) >= 2               # the tie rule decides on more than one patch
+    assert d["d"].max() > 0 and d["d"][-1] == 0
+
+
+@pytest.mark.parametrize("n_active", H.LONG_QUOTA["n_active"])
+def test_long_quotas_choose_equals_beyond_the_first_wave(n_active):
+    q = H.quota_data(n_active)
+    span = H.wave_span(q["K"])
+    assert span == 320 and q["K"] > 3 * span                                  # four waves, the last one ragged
+    assert q["mask"].sum(axis=1).tolist() == [n_active] * 3
+    for plane in q["planes"][:2]:                                             # constant: every cell an equal, the first n_active chosen
+        assert np.array_equal(H.chosen_equals(plane, q["conn"], n_active), np.arange(n_active))
+    chosen = H.chosen_equals(q["planes"][2], q["conn"], n_active)
+    waves, trips = sorted(set((chosen // span).tolist())), sorted(set(((chosen % span) // 64).tolist()))
+    print("mushroom long quota %d: halves plane, threshold %d, %d chosen equals in waves %r, trips %r"
+          % (n_active, q["thr"][2], len(chosen), waves, trips))
+    assert len(chosen) >= 1
+    if n_active in (320, 321, 1000):
+        assert waves == [0, 1, 2] and trips == [0, 1, 2, 3, 4]
+    if n_active == 1042:
+        assert waves == [2] and len(chosen) == 1
+    assert n_active > 64                                                      # the constant planes' quota leaves wave 0's first trip
+    # more equals than places: the rank decides
+    a = H.activity(q["planes"][2:], q["conn"])[0]
+    assert int((a == q["thr"][2]).sum()) > len(chosen)
+
+
+def test_slab_inputs_are_two_views_that_differ():
+    views, stage = H.slab_views()
+    t = H.slab_train_data()
+    slab = stage // t["N"]
+    assert 1 < slab < views and (slab + 1) * t["N"] > stage                   # the bytes end a slab of 128x128 planes
+    assert not np.array_equal(t["both"], t["first"])                          # the view behind the edge brings cells
+    assert 0 < (t["both"] == 0).sum() <= t["K"] // 2
+    fam = H.familiarity(t["first"], t["two"], t["conn"], t["n_active"])
+    assert H.bits(fam[:1])[0] == 0 and fam[1] < 0
+    d = H.case_data(H.SLAB_ACTIVITY["key"])
+    assert 1 < stage // d["K"] < views and stage // d["K"] < stage // d["N"]  # the fired masks end a slab of the activity call
+    assert not np.array_equal(d["mask"][0], d["mask"][1]) and d["thr"][0] != d["thr"][1]
+    assert len({d["mask"][i].tobytes() for i in range(3)}) == 3               # (the three patches of the optional-output calls)
+
+
+def test_slab_poses_and_headings_distinguish():
+    from tests import helpers_infomax as HI
+    m = H.SLAB_POSES
+    conn = H.connectivity(m["K"], 1024, m["c"], m["seed"])
+    ones = np.ones(m["K"], np.uint8)
+    path = H.sensed_route()
+    i0, i1 = m["poses"]
+    head = H.route_headings(path)
+    two = H.host_sensed_planes(path[[i0, i1], 0], path[[i0, i1], 1], head[[i0, i1]])
+    assert np.array_equal(two, HI.sensed_data()["views"][[i0, i1]])            # (the agent's own training views)
+    assert not np.array_equal(H.train(ones, two, conn, m["n_active"]), H.train(ones, two[:1], conn, m["n_active"]))
+    x, y = H.step_xy()
+    planes = H.host_sensed_planes(x, y, m["angles"])
+    for trained in (0, 1):
+        fam = H.familiarity(H.train(ones, planes[trained:trained + 1], conn, m["n_active"]), planes, conn, m["n_active"])
+        assert H.bits(fam[trained:trained + 1])[0] == 0 and fam[1 - trained] < 0
+    # the 300 headings of the decide test, under the route's weights: a best and a worst to plant
+    angles = H.circle_angles(300)
+    assert len(np.unique(angles)) == 300
+    conn = H.connectivity(4100, 1024, 10, 41)
+    wt = H.train(np.ones(4100, np.uint8), HI.sensed_data()["views"], conn, 41)
+    want = H.familiarity(wt, H.host_sensed_planes(x, y, angles), conn, 41)
+    print("mushroom decide: 300 headings score %g .. %g, %d values, first maximum at %d"
+          % (want.min(), want.max(), len(np.unique(want)), int(np.argmax(want))))
+    assert want.max() > want.min()
 
 
 def test_slab_size_is_read_from_the_kernel_file():

@@ -608,6 +608,21 @@ int dv_infomax_end(dv_ctx *ctx);
  *   sense_step       one agent step: senses the n_headings patches at (x, y), scores their `channel` plane in one launch and takes
  *                    the first maximum of angle_fam (np.argmax: integer scores tie).  Any n_headings >= 1.  DV_ERR_INDEX like
  *                    dv_sense_step.
+ *   dv_batch_mb_step_u8 / dv_batch_mb_sense_step   an ensemble's step.  (The dv_mb_ prefix is kept to the single model's ten calls; the
+ *                    ensemble's two are named apart from it, as the Infomax model's are.)  n_agents members of n_headings headings
+ *                    each share the one model (conn, wt); member i owns columns [i * n_headings, (i + 1) * n_headings).
+ *                    batch_mb_step_u8 scores uploaded planes uint8[n_agents][n_headings][h][w]; batch_mb_sense_step senses member i
+ *                    at (x[i], y[i]) along angles[i][0 .. n_headings): every column's workgroup fills its plane from the landscape
+ *                    itself, so no view is written to device memory.  angle_fam[n_agents][n_headings] ((double)(-d), +0.0 for a
+ *                    trained view) and best_heading[n_agents] (each member's first maximum, np.argmax: integer scores tie) come
+ *                    back from ONE enqueue and ONE wait, whatever n_agents is.  Any n_agents >= 1 and n_headings >= 1 (also > 64
+ *                    and > 256); more than 8192 columns (or 64 MiB of uploaded planes) run as launches back to back on the stream.
+ *                    A column's value has the bits score_u8 / sense_step give the same patch.  batch_mb_sense_step does not fail
+ *                    for a footprint that leaves the landscape: flags[i] (uint32[n_agents]) carries DV_RES_SENSE_ERROR for such a
+ *                    member, its best_heading is -1 and its row of angle_fam unspecified; the other members' results are
+ *                    untouched.  DV_ERR_STATE without a model or (batch_mb_sense_step) without a sensor; DV_ERR_INVALID for a NULL
+ *                    pointer, n_agents < 1, n_headings < 1, a sensor whose shape is not the model's, or n_agents * n_headings
+ *                    that does not fit an int.
  *   read_weights / set_weights   copy uint8[n_kc] out and in: what a user saves and restores.  DV_ERR_INVALID for a value other
  *                    than 0 or 1.
  *   info             n_kc, n_pixels, fan_in, n_active, views trained since begin, n_depressed (the number of zero weights: how full
@@ -621,6 +636,9 @@ int dv_mb_train_from_poses(dv_ctx *ctx, const double *x, const double *y, const 
 int dv_mb_score_u8(dv_ctx *ctx, const uint8_t *planes, int n, double *familiarity);
 int dv_mb_activity_u8(dv_ctx *ctx, const uint8_t *planes, int n, uint8_t *fired, int32_t *threshold);
 int dv_mb_sense_step(dv_ctx *ctx, double x, double y, const double *angles, int n_headings, double *angle_fam, int32_t *best_heading);
+int dv_batch_mb_step_u8(dv_ctx *ctx, const uint8_t *planes, int n_agents, int n_headings, double *angle_fam, int32_t *best_heading);
+int dv_batch_mb_sense_step(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
+                           double *angle_fam, int32_t *best_heading, uint32_t *flags);
 int dv_mb_read_weights(dv_ctx *ctx, uint8_t *out);
 int dv_mb_set_weights(dv_ctx *ctx, const uint8_t *weights);
 int dv_mb_info(dv_ctx *ctx, int *n_kc, int *n_pixels, int *fan_in, int *n_active, int64_t *views_trained, int64_t *n_depressed,

@@ -319,6 +319,12 @@ struct dv_ctx {
     long long* mb_zeros = nullptr;            // k_mb_count's answer
     size_t mb_d_cap = 0, mb_out_cap = 0, mb_fired_cap = 0;   // bytes
     std::vector<unsigned char> mb_hout;       // where a step's copy lands
+    // the batch calls' buffers (dv_batch_mb_step_u8 / dv_batch_mb_sense_step): made at first use, grown when a call is larger
+    int* mb_bd = nullptr;                     // [C]: novelty per column
+    int* mb_berr = nullptr;                   // [C]: did the column's footprint leave the landscape (k_mb_pose's word per workgroup)
+    unsigned char* mb_bout = nullptr;         // angle_fam[C] doubles, best[n_agents] int32, flags[n_agents] uint32: one copy to the host
+    size_t mb_bd_cap = 0, mb_berr_cap = 0, mb_bout_cap = 0;  // bytes
+    std::vector<unsigned char> mb_bhout;      // where that copy lands
     std::vector<double> mb_xy;                // a step's pose, once per heading
     int mb_K = 0, mb_N = 0, mb_c = 0, mb_active = 0, mb_hh = 0, mb_ww = 0, mb_channel = 2;
     int64_t mb_views = 0;                     // views trained on since dv_mb_begin

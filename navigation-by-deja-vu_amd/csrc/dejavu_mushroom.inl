@@ -17,7 +17,11 @@
 //                MODE kMbTrain stores 0 to wt[k] of a firing cell (plain byte stores: every writer of a byte stores the same value,
 //                whichever view's workgroup it is, so a whole route is one launch); kMbScore adds wt[k] over the firing cells;
 //                kMbMask writes the fired mask and t.
+//   k_mb_pose    kMbScore from a pose instead of staged bytes (an ensemble's step, dv_batch_mb_sense_step): the workgroup fills its LDS
+//                plane with the compared channel of the sensor model's pixels (sense_pixel) at its column's pose, so no view goes
+//                through HBM, and records in a word of its own whether a pixel left the landscape.  The body after the plane is k_mb's.
 //   k_mb_decide  fam[a] = (double)(-d[a]) and the first maximum over the headings (np.argmax), one workgroup
+//   k_mb_decide_batch  the same per member of an ensemble, one workgroup each, with the member's DV_RES_SENSE_ERROR flag
 //   k_mb_count   the number of zero weights, one workgroup
 namespace dv {
 
@@ -40,22 +44,20 @@ __device__ __forceinline__ int mb_activity(const unsigned char* __restrict__ pla
     return a;
 }
 
-// src: view v's compared plane is src[v * view_stride + offset + j * px_stride], j < N (as k_im_prep).  Dynamic LDS:
-// [N rounded up to 4] plane bytes, [kMbWaves][nb] histogram words (nb = 255 c + 1), then 16 words of hand-over.
+// One view of a launch, whatever its source: `fill(plane, tid)` puts the view's N bytes into the LDS plane (no barrier needed after
+// it), then histogram, threshold, rank arithmetic and pass 2.  lds: the workgroup's dynamic LDS, [N rounded up to 4] plane bytes,
+// [kMbWaves][nb] histogram words (nb = 255 c + 1), then 16 words of hand-over.
 // d: [views] (kMbScore); fired: [views][K], thr: [views] (kMbMask; either may be nullptr).
-template <int MODE>
-__global__ __launch_bounds__(kMbWaves * 64) void k_mb(const unsigned char* __restrict__ src, long long view_stride, int px_stride, int offset, int N,
-                                                      const unsigned short* __restrict__ conn, int K, int c, int n_active,
-                                                      unsigned char* __restrict__ wt, int* __restrict__ d, unsigned char* __restrict__ fired,
-                                                      int* __restrict__ thr) {
-    extern __shared__ unsigned mb_lds[];
+template <int MODE, class Fill>
+__device__ __forceinline__ void mb_view(unsigned* lds, Fill fill, int view, int N, const unsigned short* __restrict__ conn, int K, int c, int n_active,
+                                        unsigned char* __restrict__ wt, int* __restrict__ d, unsigned char* __restrict__ fired,
+                                        int* __restrict__ thr) {
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int nb = 255 * c + 1;
-    unsigned char* plane = reinterpret_cast<unsigned char*>(mb_lds);
-    unsigned* hist = mb_lds + ((N + 3) >> 2);                // [kMbWaves][nb]
+    unsigned char* plane = reinterpret_cast<unsigned char*>(lds);
+    unsigned* hist = lds + ((N + 3) >> 2);                   // [kMbWaves][nb]
     unsigned* hand = hist + kMbWaves * nb;                   // [0..3] the waves' totals, [4] t, [5] q, [6..9] the waves' starting ranks
-    const unsigned char* p = src + (size_t)blockIdx.x * (size_t)view_stride + offset;
-    for (int j = tid; j < N; j += kMbWaves * 64) plane[j] = p[(size_t)j * px_stride];
+    fill(plane, tid);
     for (int b = tid; b < kMbWaves * nb; b += kMbWaves * 64) hist[b] = 0u;
     __syncthreads();
 
@@ -115,16 +117,51 @@ __global__ __launch_bounds__(kMbWaves * 64) void k_mb(const unsigned char* __res
         } else if (MODE == kMbScore) {
             if (fire) acc += (int)wt[k];
         } else if (in && fired) {
-            fired[(size_t)blockIdx.x * (size_t)K + k] = fire ? 1 : 0;
+            fired[(size_t)view * (size_t)K + k] = fire ? 1 : 0;
         }
     }
     if (MODE == kMbScore) {
         for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
         if (lane == 0) hand[10 + wave] = (unsigned)acc;
         __syncthreads();
-        if (tid == 0) d[blockIdx.x] = (int)(hand[10] + hand[11] + hand[12] + hand[13]);
+        if (tid == 0) d[view] = (int)(hand[10] + hand[11] + hand[12] + hand[13]);
     }
-    if (MODE == kMbMask && thr && tid == 0) thr[blockIdx.x] = t;
+    if (MODE == kMbMask && thr && tid == 0) thr[view] = t;
+}
+
+// src: view v's compared plane is src[v * view_stride + offset + j * px_stride], j < N (as k_im_prep).
+template <int MODE>
+__global__ __launch_bounds__(kMbWaves * 64) void k_mb(const unsigned char* __restrict__ src, long long view_stride, int px_stride, int offset, int N,
+                                                      const unsigned short* __restrict__ conn, int K, int c, int n_active,
+                                                      unsigned char* __restrict__ wt, int* __restrict__ d, unsigned char* __restrict__ fired,
+                                                      int* __restrict__ thr) {
+    extern __shared__ unsigned mb_lds[];
+    mb_view<MODE>(mb_lds, [&](unsigned char* plane, int tid) {
+        const unsigned char* p = src + (size_t)blockIdx.x * (size_t)view_stride + offset;
+        for (int j = tid; j < N; j += kMbWaves * 64) plane[j] = p[(size_t)j * px_stride];
+    }, (int)blockIdx.x, N, conn, K, c, n_active, wt, d, fired, thr);
+}
+
+// kMbScore with the sensor model as the source: workgroup v senses channel `channel` of the g.sh x g.sw pixels at poses[v] into its LDS
+// plane.  A pixel off the landscape contributes 0 and the selection runs all the same (every thread reaches every barrier); err[v] is
+// written by this workgroup alone, 1 when any of its pixels was off, so the caller clears nothing beforehand.
+__global__ __launch_bounds__(kMbWaves * 64) void k_mb_pose(const unsigned char* __restrict__ land, const Pose* __restrict__ poses, SensorCfg g,
+                                                           const unsigned char* __restrict__ lut, int channel,
+                                                           const unsigned short* __restrict__ conn, int K, int c, int n_active,
+                                                           unsigned char* __restrict__ wt, int* __restrict__ d, int* __restrict__ err) {
+    extern __shared__ unsigned mb_lds[];
+    const int N = g.sh * g.sw;
+    mb_view<kMbScore>(mb_lds, [&](unsigned char* plane, int tid) {
+        const Pose p = poses[blockIdx.x];
+        int off = 0;
+        for (int j = tid; j < N; j += kMbWaves * 64) {
+            unsigned H, S, V;
+            if (!sense_pixel(land, g, p, lut, j / g.sw, j % g.sw, H, S, V)) { off = 1; H = S = V = 0; }
+            plane[j] = (unsigned char)(channel == 0 ? H : channel == 1 ? S : V);
+        }
+        off = __syncthreads_or(off);
+        if (tid == 0) err[blockIdx.x] = off;
+    }, (int)blockIdx.x, N, conn, K, c, n_active, wt, d, nullptr, nullptr);
 }
 
 // fam[a] = (double)(-d[a]); *best = the first maximum (the larger value, the lower heading of equals)
@@ -147,6 +184,37 @@ __global__ __launch_bounds__(256) void k_mb_decide(const int* __restrict__ d, in
         __syncthreads();
     }
     if (tid == 0) *best = si[0];
+}
+
+// One workgroup per member i of A columns: fam[i][a] = (double)(-d[i A + a]); best[i] = the member's first maximum (the larger value,
+// the lower heading of equals, whichever thread held it).  perr (nullptr: the planes were uploaded) holds k_mb_pose's word per column:
+// a member with one set gets best -1 and kResSenseError.
+__global__ __launch_bounds__(256) void k_mb_decide_batch(const int* __restrict__ d, const int* __restrict__ perr, int A, double* __restrict__ fam,
+                                                         int* __restrict__ best, unsigned* __restrict__ flags) {
+    __shared__ int sv[256], si[256], sb[256];
+    const int tid = (int)threadIdx.x;
+    const size_t col0 = (size_t)blockIdx.x * (size_t)A;
+    int bv = 0, bi = -1, bad = 0;
+    for (int a = tid; a < A; a += 256) {                      // headings in rising order: a later equal does not replace
+        const int v = -d[col0 + a];
+        fam[col0 + a] = (double)v;
+        if (bi < 0 || v > bv) { bv = v; bi = a; }
+        if (perr) bad |= perr[col0 + a];
+    }
+    sv[tid] = bv; si[tid] = bi; sb[tid] = bad;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+        if (tid < st) {
+            const int ov = sv[tid + st], oi = si[tid + st];
+            if (oi >= 0 && (si[tid] < 0 || ov > sv[tid] || (ov == sv[tid] && oi < si[tid]))) { sv[tid] = ov; si[tid] = oi; }
+            sb[tid] |= sb[tid + st];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        best[blockIdx.x] = sb[0] ? -1 : si[0];
+        flags[blockIdx.x] = sb[0] ? kResSenseError : 0u;
+    }
 }
 
 __global__ __launch_bounds__(256) void k_mb_count(const unsigned char* __restrict__ wt, int K, long long* __restrict__ zeros) {
@@ -172,8 +240,8 @@ static constexpr size_t kMbStageBytes = 64u << 20;           // ... and the byte
 
 static void mb_free(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-    F(c->mb_conn); F(c->mb_wt); F(c->mb_d); F(c->mb_out); F(c->mb_fired); F(c->mb_zeros);
-    c->mb_d_cap = c->mb_out_cap = c->mb_fired_cap = 0;
+    F(c->mb_conn); F(c->mb_wt); F(c->mb_d); F(c->mb_out); F(c->mb_fired); F(c->mb_zeros); F(c->mb_bd); F(c->mb_berr); F(c->mb_bout);
+    c->mb_d_cap = c->mb_out_cap = c->mb_fired_cap = c->mb_bd_cap = c->mb_berr_cap = c->mb_bout_cap = 0;
     c->mb_K = c->mb_N = c->mb_c = c->mb_active = c->mb_hh = c->mb_ww = 0;
     c->mb_views = 0;
 }
@@ -253,6 +321,7 @@ extern "C" int dv_mb_begin(dv_ctx* c, int h, int w, int channel, int n_kc, int f
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb<kMbTrain>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb<kMbScore>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb<kMbMask>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_pose, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = hipMemcpyAsync(c->mb_conn, ct.data(), ct.size() * sizeof(unsigned short), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->mb_wt, 1, K, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);           // `ct` is this call's
@@ -396,6 +465,86 @@ extern "C" int dv_mb_sense_step(dv_ctx* c, double x, double y, const double* ang
     std::memcpy(angle_fam, c->mb_hout.data(), fam_bytes);
     std::memcpy(best_heading, c->mb_hout.data() + fam_bytes, sizeof(int));
     return DV_OK;
+}
+
+// ---- ensembles: every member's headings in one enqueue and one wait ----------------------------------------------------------
+// planes != nullptr: uploaded uint8[n_agents][A][h][w], scored by k_mb<kMbScore> in launches of mb_slab(N) columns (the view bound and
+// the byte bound of dv_mb_score_u8); else the poses (x[i], y[i], angles[i][a]) go to k_mb_pose, kMbSlabViews columns a launch.  The
+// launches follow one another on the stream; the host waits once, for the one copy of the packed results.
+static int mb_batch(dv_ctx* c, const char* who, const uint8_t* planes, const double* x, const double* y, const double* angles, int n_agents, int A,
+                    double* angle_fam, int32_t* best_heading, uint32_t* flags) {
+    const long long C = (long long)n_agents * A;
+    if (C > 0x7fffffffll) return fail(c, DV_ERR_INVALID, "%s: %d agents x %d headings are too many columns", who, n_agents, A);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t N = (size_t)c->mb_N;
+    const size_t fam_bytes = (size_t)C * sizeof(double), out_bytes = fam_bytes + (size_t)n_agents * 8;
+    long long slab = planes ? (long long)mb_slab(N) : (long long)kMbSlabViews;
+    if (slab > C) slab = C;
+    int rc = infomax_grow(c, c->mb_bd, c->mb_bd_cap, (size_t)C * sizeof(int));
+    if (!rc) rc = infomax_grow(c, c->mb_bout, c->mb_bout_cap, out_bytes);
+    if (!rc && !planes) rc = infomax_grow(c, c->mb_berr, c->mb_berr_cap, (size_t)C * sizeof(int));
+    if (!rc && planes) rc = ensure_sense_buffer(c, (size_t)slab * N);
+    if (rc) return rc;
+    if (!planes) {
+        if ((size_t)C > c->poses_cap) {
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            if (c->d_poses) (void)hipFree(c->d_poses);
+            c->d_poses = nullptr;
+            c->poses_cap = 0;
+            HIP_TRY(c, hipMalloc(&c->d_poses, (size_t)C * sizeof(Pose)));
+            c->poses_cap = (size_t)C;
+        }
+        c->h_poses.resize((size_t)C);
+        for (int i = 0; i < n_agents; ++i)
+            for (int a = 0; a < A; ++a) c->h_poses[(size_t)i * A + a] = make_pose(x[i], y[i], angles[(size_t)i * A + a]);
+        HIP_TRY(c, hipMemcpyAsync(c->d_poses, c->h_poses.data(), (size_t)C * sizeof(Pose), hipMemcpyHostToDevice, c->stream));
+    }
+    for (long long c0 = 0; c0 < C; c0 += slab) {
+        const int nc = (int)(C - c0 < slab ? C - c0 : slab);
+        if (planes) {
+            HIP_TRY(c, hipMemcpyAsync(c->d_sense, planes + (size_t)c0 * N, (size_t)nc * N, hipMemcpyHostToDevice, c->stream));
+            rc = mb_launch<kMbScore>(c, c->d_sense, (long long)N, 1, 0, nc, c->mb_bd + c0, nullptr, nullptr);
+            if (rc) return rc;
+        } else {
+            hipLaunchKernelGGL(k_mb_pose, dim3((unsigned)nc), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, c->d_land, c->d_poses + c0, c->sensor,
+                               c->d_lut, c->mb_channel, c->mb_conn, c->mb_K, c->mb_c, c->mb_active, c->mb_wt, c->mb_bd + c0, c->mb_berr + c0);
+            HIP_TRY(c, hipGetLastError());
+        }
+    }
+    double* d_fam = reinterpret_cast<double*>(c->mb_bout);
+    int* d_best = reinterpret_cast<int*>(c->mb_bout + fam_bytes);
+    unsigned* d_flags = reinterpret_cast<unsigned*>(c->mb_bout + fam_bytes + (size_t)n_agents * 4);
+    hipLaunchKernelGGL(k_mb_decide_batch, dim3((unsigned)n_agents), dim3(256), 0, c->stream, c->mb_bd, planes ? nullptr : c->mb_berr, A, d_fam, d_best,
+                       d_flags);
+    HIP_TRY(c, hipGetLastError());
+    c->mb_bhout.resize(out_bytes);
+    HIP_TRY(c, hipMemcpyAsync(c->mb_bhout.data(), c->mb_bout, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    std::memcpy(angle_fam, c->mb_bhout.data(), fam_bytes);
+    std::memcpy(best_heading, c->mb_bhout.data() + fam_bytes, (size_t)n_agents * 4);
+    if (flags) std::memcpy(flags, c->mb_bhout.data() + fam_bytes + (size_t)n_agents * 4, (size_t)n_agents * 4);
+    return DV_OK;
+}
+
+extern "C" int dv_batch_mb_step_u8(dv_ctx* c, const uint8_t* planes, int n_agents, int n_headings, double* angle_fam, int32_t* best_heading) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = mb_need(c, "dv_batch_mb_step_u8");
+    if (rc) return rc;
+    if (!planes || !angle_fam || !best_heading || n_agents < 1 || n_headings < 1)
+        return fail(c, DV_ERR_INVALID, "dv_batch_mb_step_u8: NULL argument, n_agents < 1 or n_headings < 1");
+    return mb_batch(c, "dv_batch_mb_step_u8", planes, nullptr, nullptr, nullptr, n_agents, n_headings, angle_fam, best_heading, nullptr);
+}
+
+extern "C" int dv_batch_mb_sense_step(dv_ctx* c, const double* x, const double* y, const double* angles, int n_agents, int n_headings,
+                                      double* angle_fam, int32_t* best_heading, uint32_t* flags) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = mb_need(c, "dv_batch_mb_sense_step");
+    if (rc) return rc;
+    if (!x || !y || !angles || !angle_fam || !best_heading || !flags || n_agents < 1 || n_headings < 1)
+        return fail(c, DV_ERR_INVALID, "dv_batch_mb_sense_step: NULL argument, n_agents < 1 or n_headings < 1");
+    rc = mb_sensor_fits(c, "dv_batch_mb_sense_step");
+    if (rc) return rc;
+    return mb_batch(c, "dv_batch_mb_sense_step", nullptr, x, y, angles, n_agents, n_headings, angle_fam, best_heading, flags);
 }
 
 extern "C" int dv_mb_read_weights(dv_ctx* c, uint8_t* out) {

@@ -243,6 +243,8 @@ PROTOTYPES = {
     "dv_mb_score_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, _f64p]),
     "dv_mb_activity_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, _u8p, _i32p]),
     "dv_mb_sense_step": (ctypes.c_int, [_ctx_p, ctypes.c_double, ctypes.c_double, _f64p, ctypes.c_int, _f64p, _i32p]),
+    "dv_batch_mb_step_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, _f64p, _i32p]),
+    "dv_batch_mb_sense_step": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _f64p, _i32p, _u32p]),
     "dv_mb_read_weights": (ctypes.c_int, [_ctx_p, _u8p]),
     "dv_mb_set_weights": (ctypes.c_int, [_ctx_p, _u8p]),
     "dv_mb_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),

@@ -52,7 +52,8 @@ class BatchResults(object):
 
 
 class InfomaxBatchResults(object):
-    """An ensemble step of the Infomax model (dv_batch_infomax_step_u8 / dv_batch_infomax_sense_step), in BatchResults' shape for
+    """An ensemble step of the Infomax model (dv_batch_infomax_step_u8 / dv_batch_infomax_sense_step) or of the mushroom-body model
+    (dv_batch_mb_step_u8 / dv_batch_mb_sense_step), in BatchResults' shape for
     callers that move agents: angle_familiarity[n, A] (float64), best_idex[n] (int32; -1 for a member whose footprint left the
     landscape) and flags[n] (uint32; DV_RES_SENSE_ERROR = 16 for such a member, whose row is unspecified)."""
 
@@ -950,6 +951,37 @@ class FamiliarityEngine(object):
         self._check_sense(self._lib.dv_mb_sense_step(self._ctx, float(x), float(y), N.f64ptr(angles), len(angles), N.f64ptr(out_fam),
                                                      ctypes.byref(best)), "dv_mb_sense_step")
         return int(best.value), out_fam
+
+    def mb_step_batch_u8(self, planes):
+        """An ensemble's step on uploaded patches: uint8[n, A, h, w] planes, member i's A headings in row i -> InfomaxBatchResults (every
+        member's familiarities and first maximum from one device call; the flags are 0)."""
+        planes = N.as_u8(planes, "planes")
+        if planes.ndim != 4 or planes.shape[0] < 1 or planes.shape[1] < 1:
+            raise ValueError("planes must be uint8[n,A,h,w] with n, A >= 1, got shape %r" % (planes.shape,))
+        n, A = planes.shape[:2]
+        flat = self._mb_planes(planes.reshape((n * A,) + planes.shape[2:]), "planes")
+        fam = np.empty((n, A), dtype=np.float64)
+        best = np.full(n, -1, dtype=np.int32)
+        self._check(self._lib.dv_batch_mb_step_u8(self._ctx, N.u8ptr(flat), n, A, N.f64ptr(fam), best.ctypes.data_as(N._i32p)),
+                    "dv_batch_mb_step_u8")
+        return InfomaxBatchResults(fam, best, np.zeros(n, dtype=np.uint32))
+
+    def mb_sense_step_batch(self, x, y, angles):
+        """An ensemble's step: member i at (x[i], y[i]) looking along angles[i][0..A) -> InfomaxBatchResults.  One enqueue and one wait
+        for all members; a member whose footprint leaves the landscape is flagged (flags & 16, best_idex -1), the others are scored."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        angles = np.ascontiguousarray(angles, dtype=np.float64)
+        if angles.ndim != 2 or len(x) != len(y) or angles.shape[0] != len(x) or angles.shape[0] < 1 or angles.shape[1] < 1:
+            raise ValueError("x[N], y[N] and angles[N, A] expected (N, A >= 1), got shapes %r, %r and %r" % (x.shape, y.shape, angles.shape))
+        n, A = angles.shape
+        fam = np.empty((n, A), dtype=np.float64)
+        best = np.full(n, -1, dtype=np.int32)
+        flags = np.zeros(n, dtype=np.uint32)
+        self._check(self._lib.dv_batch_mb_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, N.f64ptr(fam),
+                                                     best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)),
+                    "dv_batch_mb_sense_step")
+        return InfomaxBatchResults(fam, best, flags)
 
     def mb_info(self):
         k, n, c, act = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)

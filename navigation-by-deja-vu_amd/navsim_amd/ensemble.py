@@ -267,35 +267,39 @@ class NavEnsemble(object):
         return done
 
 
-class InfomaxEnsemble(NavEnsemble):
-    """NavEnsemble for agents of the Infomax model (util.infomax_familiarity): the trials of the reference's grid that share one trained
-    route and differ in start_offset.  One W serves every member; a step senses every running member's headings, scores them as columns
-    of one H = W X and takes each member's first maximum in ONE device call (dv_batch_infomax_sense_step), with the bits a lone agent's
-    step_forward gives at the same pose.  The model keeps no per-view score: a tracking member's scene_familiarity is its least
-    familiarity over the headings at every view, filled after each step (as the lone agent's); +inf for a member stopped before it
-    sensed.  Members' error metrics run on the device as NavEnsemble's do.  Members with weights of their own are not offered: there is
-    no chem_weights argument."""
+class _OneValueEnsemble(NavEnsemble):
+    """What InfomaxEnsemble and MushroomEnsemble share: one model without per-view memory serves every member, and a step is ONE device
+    call on the members' engine (`_batch_call`).  The model keeps no per-view score: a tracking member's scene_familiarity is its least
+    familiarity over the headings at every view, filled after each step (as the lone agent's _step_one_value fills it); +inf for a
+    member stopped before it sensed.  Members' error metrics run on the device as NavEnsemble's do.  Members with weights of their own
+    are not offered: there is no chem_weights argument."""
+    _metric = None               # familiarity_model.metric of the agents taken
+    _takes = None                # "agents of the ... model (familiarity_model=...(...))", for the refusal
+    _batch_call = None           # the engine's batched sense step
+
+    @classmethod
+    def _reject_others(cls, agent):
+        """The refusals of util.py for the other model without a library."""
 
     @classmethod
     def _check_member(cls, agent):
         func = getattr(agent, "_familiarity_func", None)
-        reject_mushroom(agent, "InfomaxEnsemble")
-        if getattr(getattr(agent, "familiarity_model", None), "metric", None) != "infomax":
-            raise ValueError("InfomaxEnsemble takes agents of the Infomax model (familiarity_model=infomax_familiarity(...)); "
-                             "NavEnsemble steps the library-based models")
+        cls._reject_others(agent)
+        if getattr(getattr(agent, "familiarity_model", None), "metric", None) != cls._metric:
+            raise ValueError("%s takes %s; NavEnsemble steps the library-based models" % (cls.__name__, cls._takes))
         if getattr(agent, "_engine", None) is None:
-            raise ValueError("InfomaxEnsemble needs agents whose sensor model runs on the GPU (use_gpu_sensor=True)")
+            raise ValueError("%s needs agents whose sensor model runs on the GPU (use_gpu_sensor=True)" % cls.__name__)
         if agent.training_path is None or func is None or getattr(func, "engine", None) is not agent._engine:
-            raise ValueError("InfomaxEnsemble needs trained agents (train_from_path first)")
+            raise ValueError("%s needs trained agents (train_from_path first)" % cls.__name__)
 
     @classmethod
     def from_agent(cls, agent, poses):
-        """`agent`: a trained Infomax agent with the GPU sensor model; poses: iterable of ((x, y), angle), one member each (the first
-        goes to `agent` itself, the others to clones on the same engine and weights)."""
-        return super(InfomaxEnsemble, cls).from_agent(agent, poses)
+        """`agent`: a trained agent of the ensemble's model with the GPU sensor model; poses: iterable of ((x, y), angle), one member
+        each (the first goes to `agent` itself, the others to clones on the same engine and model)."""
+        return super(_OneValueEnsemble, cls).from_agent(agent, poses)
 
     def _device_step(self, idx, xs, ys, angs):
-        results = self.engine.infomax_sense_step_batch(xs, ys, angs)
+        results = getattr(self.engine, self._batch_call)(xs, ys, angs)
         self._rows = {id(self.agents[i]): results.angle_familiarity[k] for k, i in enumerate(idx)}
         return results
 
@@ -304,3 +308,33 @@ class InfomaxEnsemble(NavEnsemble):
         agent._scene_owner = None
         agent._scene_fam[:] = np.min(self._rows[id(agent)])
         agent._scene_is_inf = False
+
+
+class InfomaxEnsemble(_OneValueEnsemble):
+    """NavEnsemble for agents of the Infomax model (util.infomax_familiarity): the trials of the reference's grid that share one trained
+    route and differ in start_offset.  One W serves every member; a step senses every running member's headings, scores them as columns
+    of one H = W X and takes each member's first maximum in ONE device call (dv_batch_infomax_sense_step), with the bits a lone agent's
+    step_forward gives at the same pose."""
+    _metric = "infomax"
+    _takes = "agents of the Infomax model (familiarity_model=infomax_familiarity(...))"
+    _batch_call = "infomax_sense_step_batch"
+
+    @classmethod
+    def _reject_others(cls, agent):
+        reject_mushroom(agent, "InfomaxEnsemble")
+
+
+class MushroomEnsemble(_OneValueEnsemble):
+    """NavEnsemble for agents of the mushroom-body model (util.mushroom_familiarity), the twin of InfomaxEnsemble.  One connectivity and
+    one byte of weight per Kenyon cell serve every member; a step scores every running member's headings, one workgroup each, straight
+    from the landscape, and takes each member's first maximum in ONE device call (dv_batch_mb_sense_step), with the bits a lone agent's
+    step_forward gives at the same pose."""
+    _metric = "mushroom"
+    _takes = "agents of the mushroom-body model (familiarity_model=mushroom_familiarity(...))"
+    _batch_call = "mb_sense_step_batch"
+
+    @classmethod
+    def _reject_others(cls, agent):
+        for obj in (agent, getattr(agent, "familiarity_model", None), getattr(agent, "_familiarity_func", None)):
+            if getattr(obj, "metric", None) == "infomax":
+                raise ValueError("MushroomEnsemble does not take an Infomax model: navsim_amd.InfomaxEnsemble steps that one")

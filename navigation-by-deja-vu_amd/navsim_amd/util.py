@@ -152,11 +152,13 @@ def reject_infomax(model, what):
 
 
 def reject_mushroom(model, what):
-    """The same refusal for the mushroom-body model (mushroom_familiarity): it keeps no library either, and its ensembles are not built."""
+    """The same refusal for the mushroom-body model (mushroom_familiarity): it keeps no library either; navsim_amd.MushroomEnsemble is
+    the one batched form that takes it."""
     for obj in (model, getattr(model, "familiarity_model", None), getattr(model, "_familiarity_func", None)):
         if getattr(obj, "metric", None) == "mushroom":
             raise ValueError("%s does not take a mushroom-body model: it batches or shards a view library (or one Infomax weight "
-                             "matrix), and mushroom_familiarity keeps neither (step each agent on its own engine)" % what)
+                             "matrix), and mushroom_familiarity keeps neither (step each agent on its own engine, or use "
+                             "navsim_amd.MushroomEnsemble)" % what)
 
 
 def infomax_initial_weights(n_hidden, n_pixels, seed=0):

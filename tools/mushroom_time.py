@@ -2,7 +2,8 @@
 """Times the mushroom-body familiarity model (navsim_amd.mushroom_familiarity; include/dejavu.h: dv_mb_*) on GPU 0 and writes
 profiles/mushroom_time.json.
 
-    python tools/mushroom_time.py [--sides 32,64] [--views 1000] [--calls 200] [--reps 5] [--out profiles/mushroom_time.json]
+    python tools/mushroom_time.py [--sides 32,64] [--views 1000] [--calls 200] [--reps 5] [--blocks single,ensemble]
+                                  [--out profiles/mushroom_time.json]
 
 Per sensor side s (views of s x s) with K = 20000 Kenyon cells, fan-in 10 and 200 firing cells: microseconds per agent step
 (dv_mb_sense_step: sensing, one scoring launch over all headings, the decision and the read-back) for 16 and for 60 headings, and
@@ -11,6 +12,11 @@ each the median of --reps timed windows after a warm-up of the same shape, from 
 (dv_timer_start / dv_timer_stop) with the spread (min, max) beside it.  For context, from the same child process: the Infomax
 model's step (dv_infomax_sense_step, N x N weights) at the same shapes; and from this host's CPU, wall clock: the NumPy statement
 of the model (tests/helpers_mushroom.py) scoring the same number of patches.
+
+Ensemble block (--blocks ensemble): per side, 32 members x 16 headings and 8 members x 60 headings at poses spread over the synthetic
+landscape -- microseconds per ensemble step of dv_batch_mb_sense_step (one call for all members), and of the same poses as a loop of
+dv_mb_sense_step calls, one per member, from the same child process in alternating windows of --ensemble-calls steps; their ratio is
+loop_over_batched.  A block that is not measured keeps the rows it has in the output file.
 
 Every GPU measurement runs in a child process of its own under a time limit, and nothing more is started on the GPU after one
 that failed."""
@@ -28,6 +34,7 @@ sys.path.insert(0, os.path.join(ROOT, "navigation-by-deja-vu_amd"))
 sys.path.insert(0, ROOT)
 
 HEADINGS = (16, 60)                                               # 60: the reference's default n_test_angles
+ENSEMBLES = ((32, 16), (8, 60))                                   # (members, headings)
 K, FAN_IN, N_ACTIVE = 20000, 10, 200
 
 
@@ -82,6 +89,50 @@ def gpu_child(side, n_views, n_calls, reps):
     print(json.dumps(out))
 
 
+def ensemble_child(side, n_calls, reps):
+    """The ensemble block of one size on the GPU -> one JSON line on stdout."""
+    from navsim_amd import NavBySceneFamiliarity, mushroom_familiarity, synth
+    from navsim_amd.util import mushroom_connectivity
+    N = side * side
+    land = synth.synth_landscape(3, 600, 4)
+    out = dict(side=side, N=N, n_kc=K, fan_in=FAN_IN, n_active=N_ACTIVE, calls_per_window=n_calls, layouts=[])
+    conn = mushroom_connectivity(K, N, FAN_IN, 0)
+    for n, A in ENSEMBLES:
+        agent = NavBySceneFamiliarity(land, (side, side), 1.0, n_test_angles=A, familiarity_model=mushroom_familiarity())
+        eng = agent._engine                                       # (landscape and sensor attached)
+        eng.mb_begin(side, side, conn, N_ACTIVE, 2)
+        rng = np.random.default_rng(n * 100 + A)
+        xs, ys = rng.uniform(150, 450, n), rng.uniform(150, 450, n)
+        angs = (rng.uniform(0, 2 * np.pi, n)[:, None] + agent.angle_offsets[None, :]) % (2 * np.pi)
+        eng.mb_train_from_poses(xs, ys, angs[:, A // 2].copy(), want_views=False)   # (some weights at 0, as on a trained route)
+        fam = np.empty(A)
+
+        def batched():
+            eng.timer_start()
+            for _ in range(n_calls):
+                res = eng.mb_sense_step_batch(xs, ys, angs)
+            return eng.timer_stop() * 1e3 / n_calls, res          # us per ensemble step
+
+        def looped():
+            eng.timer_start()
+            for _ in range(n_calls):
+                for i in range(n):
+                    eng.mb_sense_step(xs[i], ys[i], angs[i], fam)
+            return eng.timer_stop() * 1e3 / n_calls
+
+        _, res = batched()                                        # warm-up of both (code load, clocks, the buffers)
+        looped()
+        assert not res.flags.any() and res.angle_familiarity.max() == 0.0 and res.angle_familiarity.min() < 0
+        tb, tl = [], []
+        for _ in range(reps):                                     # alternating windows
+            tb.append(batched()[0])
+            tl.append(looped())
+        out["layouts"].append(dict(members=n, headings=A, batched_us_per_step=spread(tb), loop_us_per_step=spread(tl),
+                                   loop_over_batched=round(float(np.median(tl) / np.median(tb)), 3)))
+        eng.close()
+    print(json.dumps(out))
+
+
 def cpu_row(side, n_calls):
     """The NumPy statement on this host: wall clock, microseconds per call that scores A patches."""
     from tests import helpers_mushroom as H
@@ -106,14 +157,35 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--limit", type=int, default=240, help="seconds allowed to each GPU child")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mushroom_time.json"))
+    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and the agent step), ensemble")
+    ap.add_argument("--ensemble-calls", type=int, default=30, help="ensemble steps per timed window")
     ap.add_argument("--child", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--ensemble-child", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
         gpu_child(args.child, args.views, args.calls, args.reps)
         return 0
+    if args.ensemble_child:
+        ensemble_child(args.ensemble_child, args.ensemble_calls, args.reps)
+        return 0
+    blocks = args.blocks.split(",")
     result = dict(tool="tools/mushroom_time.py", timer="hipEvent pair (dv_timer_start/stop), median of %d windows after a warm-up" % args.reps,
-                  sizes=[])
-    for side in [int(x) for x in args.sides.split(",")]:
+                  sizes=[], ensembles=[])
+    if os.path.exists(args.out):                                  # a block that is not measured keeps its rows
+        with open(args.out) as f:
+            kept = json.load(f)
+        for block, key in (("single", "sizes"), ("ensemble", "ensembles")):
+            if block not in blocks:
+                result[key] = kept.get(key, [])
+    for side in [int(x) for x in args.sides.split(",")] if "ensemble" in blocks else []:
+        cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--ensemble-child", str(side),
+               "--ensemble-calls", str(args.ensemble_calls), "--reps", str(args.reps)]
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, universal_newlines=True)
+        if p.returncode != 0:
+            print("GPU measurement of the ensembles of side %d ended with status %d: nothing more is run" % (side, p.returncode), file=sys.stderr)
+            return p.returncode
+        result["ensembles"].append(json.loads(p.stdout.strip().splitlines()[-1]))
+    for side in [int(x) for x in args.sides.split(",")] if "single" in blocks else []:
         cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child", str(side), "--views", str(args.views),
                "--calls", str(args.calls), "--reps", str(args.reps)]
         p = subprocess.run(cmd, stdout=subprocess.PIPE, universal_newlines=True)

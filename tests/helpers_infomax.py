@@ -49,6 +49,19 @@ Two chains outside CASES, measured the same way (weights only):
 Along 8197 views the rounding of the chain accumulates: 1000 x 6.75e-15 is above TOL, so that chain has a bound of its own by the
 same rule, TOL_LONG_CHAIN = 7e-12 (1000 x its largest discrepancy, rounded up to one digit; no cap shared with TOL).  The sensed
 chain passes the rule under TOL itself.  tests/test_infomax_host.py measures both again.
+
+The sensed chains under the sensor's options (tests/helpers_sensed_models.py: 45 sensed views at 1e-3, 20 rows, 70 for odd; scores of
+5 x 13 + 13 sensed headings on the trained weights), the larger of the two discrepancies each (vs longdouble, vs permuted order):
+
+    configuration (w x h), channel     W         d
+    px    16x8    H / S / V            6.3e-16 / 8.9e-16 / 5.7e-16     3.6e-16 / 2.3e-16 / 2.6e-16
+    odd   19x17   H / S / V            8.8e-16 / 8.3e-16 / 8.6e-16     3.2e-16 / 4.1e-16 / 3.3e-16
+    tall  6x23    H / S / V            8.6e-16 / 7.6e-16 / 6.4e-16     4.0e-16 / 3.1e-16 / 2.7e-16
+    wide  34x10   H / V                7.3e-16 / 7.4e-16               4.5e-16 / 5.9e-16
+    sq    32x32   V (flag tests)       6.6e-16                         4.9e-16
+
+and the scores of the flag layouts (5 x 9 and 3 x 70 headings at the landscape's edge) 3.7e-16 .. 5.5e-16.  The largest is 8.9e-16:
+all pass the rule under TOL.  tests/test_sensed_models_host.py measures them again.
 """
 import functools
 

@@ -83,6 +83,14 @@ extern "C" int dv_range_pop(void) {
 
 static thread_local std::string g_create_error;
 
+// A one-value model's results of one call, packed so that ONE copy brings them to the host:
+// angle_fam[C] doubles | best[n_agents] int32 | flags[n_agents] uint32 (packed_device, packed_fetch, packed_unpack below).
+struct PackedResults {
+    unsigned char* dev = nullptr;
+    size_t cap = 0;                           // bytes
+    std::vector<unsigned char> host;          // where the copy lands
+};
+
 struct dv_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -302,10 +310,9 @@ struct dv_ctx {
     // the batch calls' buffers (dv_batch_infomax_step_u8 / dv_batch_infomax_sense_step): made at first use, grown when a call is larger
     double* im_bx = nullptr;                  // [slab columns][N]
     double* im_bdpart = nullptr;              // [row tiles][columns padded to 64]
-    unsigned char* im_bout = nullptr;         // angle_fam[C] doubles, best[n_agents] int32, flags[n_agents] uint32: one copy to the host
+    PackedResults im_res;                     // of the batch calls
     int* im_perr = nullptr;                   // [C]: k_sense_each's word per pose
-    size_t im_bx_cap = 0, im_bdpart_cap = 0, im_bout_cap = 0, im_perr_cap = 0;   // bytes
-    std::vector<unsigned char> im_hout;       // where that copy lands
+    size_t im_bx_cap = 0, im_bdpart_cap = 0, im_perr_cap = 0;   // bytes
     int im_M = 0, im_N = 0, im_hh = 0, im_ww = 0, im_channel = 2;
     double im_eta = 0.0;
     int64_t im_views = 0;                     // views trained on since dv_infomax_begin
@@ -314,17 +321,14 @@ struct dv_ctx {
     unsigned short* mb_conn = nullptr;        // [fan_in][K]: input j of every cell
     unsigned char* mb_wt = nullptr;           // [K]: 1, or 0 once depressed
     int* mb_d = nullptr;                      // novelty (or threshold) per view of a launch
-    unsigned char* mb_out = nullptr;          // a step's angle_fam[n] doubles and best heading: one copy to the host
     unsigned char* mb_fired = nullptr;        // [slab][K]: dv_mb_activity_u8's masks
     long long* mb_zeros = nullptr;            // k_mb_count's answer
-    size_t mb_d_cap = 0, mb_out_cap = 0, mb_fired_cap = 0;   // bytes
-    std::vector<unsigned char> mb_hout;       // where a step's copy lands
+    size_t mb_d_cap = 0, mb_fired_cap = 0;    // bytes
+    PackedResults mb_res;                     // of a step (one member) and of the batch calls alike
     // the batch calls' buffers (dv_batch_mb_step_u8 / dv_batch_mb_sense_step): made at first use, grown when a call is larger
     int* mb_bd = nullptr;                     // [C]: novelty per column
     int* mb_berr = nullptr;                   // [C]: did the column's footprint leave the landscape (k_mb_pose's word per workgroup)
-    unsigned char* mb_bout = nullptr;         // angle_fam[C] doubles, best[n_agents] int32, flags[n_agents] uint32: one copy to the host
-    size_t mb_bd_cap = 0, mb_berr_cap = 0, mb_bout_cap = 0;  // bytes
-    std::vector<unsigned char> mb_bhout;      // where that copy lands
+    size_t mb_bd_cap = 0, mb_berr_cap = 0;    // bytes
     std::vector<double> mb_xy;                // a step's pose, once per heading
     int mb_K = 0, mb_N = 0, mb_c = 0, mb_active = 0, mb_hh = 0, mb_ww = 0, mb_channel = 2;
     int64_t mb_views = 0;                     // views trained on since dv_mb_begin
@@ -1396,6 +1400,11 @@ extern "C" int dv_configure_sensor(dv_ctx* c, int sw, int sh, int pw, int ph, co
     return DV_OK;
 }
 
+static inline Pose make_pose(double x, double y, double angle) {   // cos/sin from the host's libm, as the reference's come
+    const double rot = -(0.5 * M_PI - angle);
+    return Pose{x, y, std::cos(rot), std::sin(rot)};
+}
+
 // Enqueue k_sense for n poses into `d_out` (uint8[n][sh][sw][3]).  Rotation cos/sin come from the host's libm,
 // like the reference's cimported cos/sin (util.pyx:143-145).
 static int enqueue_sense(dv_ctx* c, const double* x, const double* y, const double* angle, long long n, unsigned char* d_out) {
@@ -1407,10 +1416,7 @@ static int enqueue_sense(dv_ctx* c, const double* x, const double* y, const doub
         c->poses_cap = (size_t)n;
     }
     c->h_poses.resize((size_t)n);
-    for (long long i = 0; i < n; ++i) {
-        const double rot = -(0.5 * M_PI - angle[i]);
-        c->h_poses[(size_t)i] = Pose{x[i], y[i], std::cos(rot), std::sin(rot)};
-    }
+    for (long long i = 0; i < n; ++i) c->h_poses[(size_t)i] = make_pose(x[i], y[i], angle[i]);
     HIP_TRY(c, hipMemsetAsync(c->d_sense_err, 0, sizeof(unsigned long long), c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->d_poses, c->h_poses.data(), (size_t)n * sizeof(Pose), hipMemcpyHostToDevice, c->stream));
     const long long total = n * c->sensor.sh * c->sensor.sw;
@@ -1437,6 +1443,72 @@ static int ensure_sense_buffer(dv_ctx* c, size_t bytes) {
         c->sense_cap = bytes;
     }
     return DV_OK;
+}
+
+// ---- what the one-value models (dejavu_infomax.inl, dejavu_mushroom.inl) share on the host ----------------------------------------
+// A device buffer made at first use and grown only when a call needs more; the stream is drained before the old one is freed.
+template <class T>
+static int grow_buffer(dv_ctx* c, T*& p, size_t& cap, size_t bytes) {
+    if (bytes <= cap) return DV_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    HIP_TRY(c, hipMalloc((void**)&p, bytes));
+    cap = bytes;
+    return DV_OK;
+}
+
+// Is the sensor model there, and are its views the hh x ww ones the model of `who` was begun with?
+static int sensor_fits(dv_ctx* c, const char* who, int hh, int ww) {
+    if (!c->have_sensor) return fail(c, DV_ERR_STATE, "sensor not configured");
+    if (c->sensor.sh != hh || c->sensor.sw != ww)
+        return fail(c, DV_ERR_INVALID, "%s: the sensor is %dx%d but the model takes %dx%d views", who, c->sensor.sw, c->sensor.sh, ww, hh);
+    return DV_OK;
+}
+
+// Enqueue the upload of an ensemble's poses to d_poses, member-major: pose i A + a is member i at (x[i], y[i]) looking along angles[i][a].
+static int upload_member_poses(dv_ctx* c, const double* x, const double* y, const double* angles, int n_agents, int A) {
+    const size_t C = (size_t)n_agents * (size_t)A;
+    if (C > c->poses_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (c->d_poses) (void)hipFree(c->d_poses);
+        c->d_poses = nullptr;
+        c->poses_cap = 0;
+        HIP_TRY(c, hipMalloc(&c->d_poses, C * sizeof(Pose)));
+        c->poses_cap = C;
+    }
+    c->h_poses.resize(C);
+    for (int i = 0; i < n_agents; ++i)
+        for (int a = 0; a < A; ++a) c->h_poses[(size_t)i * A + a] = make_pose(x[i], y[i], angles[(size_t)i * A + a]);
+    HIP_TRY(c, hipMemcpyAsync(c->d_poses, c->h_poses.data(), C * sizeof(Pose), hipMemcpyHostToDevice, c->stream));
+    return DV_OK;
+}
+
+// PackedResults for C columns of n_agents members: the device pointers of its three parts (the buffer grown to hold them) ...
+static int packed_device(dv_ctx* c, PackedResults& r, long long C, int n_agents, double*& fam, int*& best, unsigned*& flags) {
+    const size_t fam_bytes = (size_t)C * sizeof(double);
+    int rc = grow_buffer(c, r.dev, r.cap, fam_bytes + (size_t)n_agents * 8);
+    if (rc) return rc;
+    fam = reinterpret_cast<double*>(r.dev);
+    best = reinterpret_cast<int*>(r.dev + fam_bytes);
+    flags = reinterpret_cast<unsigned*>(r.dev + fam_bytes + (size_t)n_agents * 4);
+    return DV_OK;
+}
+
+// ... the one copy to the host, enqueued (the caller synchronises) ...
+static int packed_fetch(dv_ctx* c, PackedResults& r, long long C, int n_agents) {
+    r.host.resize((size_t)C * sizeof(double) + (size_t)n_agents * 8);
+    HIP_TRY(c, hipMemcpyAsync(r.host.data(), r.dev, r.host.size(), hipMemcpyDeviceToHost, c->stream));
+    return DV_OK;
+}
+
+// ... and, once it has landed, its parts in the caller's arrays (flags may be nullptr).
+static void packed_unpack(const PackedResults& r, long long C, int n_agents, double* angle_fam, int32_t* best_heading, uint32_t* flags) {
+    const size_t fam_bytes = (size_t)C * sizeof(double), word_bytes = (size_t)n_agents * 4;
+    std::memcpy(angle_fam, r.host.data(), fam_bytes);
+    std::memcpy(best_heading, r.host.data() + fam_bytes, word_bytes);
+    if (flags) std::memcpy(flags, r.host.data() + fam_bytes + word_bytes, word_bytes);
 }
 
 extern "C" int dv_sense(dv_ctx* c, const double* x, const double* y, const double* angle, int n, uint8_t* out) {
@@ -1517,11 +1589,6 @@ static int check_sense_args(dv_ctx* c, int A) {
     if (c->sensor.sw != c->w || c->sensor.sh != c->h)
         return fail(c, DV_ERR_STATE, "sensor is %dx%d but the library holds %dx%d views", c->sensor.sw, c->sensor.sh, c->w, c->h);
     return DV_OK;
-}
-
-static inline Pose make_pose(double x, double y, double angle) {   // cos/sin from the host's libm, as the reference's come
-    const double rot = -(0.5 * M_PI - angle);
-    return Pose{x, y, std::cos(rot), std::sin(rot)};
 }
 
 extern "C" int dv_sense_patches(dv_ctx* c, double x, double y, const double* angles, int A) {

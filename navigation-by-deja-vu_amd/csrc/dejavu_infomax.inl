@@ -283,8 +283,8 @@ static constexpr size_t kImStageBytes = 64u << 20;            // x vectors and u
 static void infomax_free(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
     F(c->im_W); F(c->im_h[0]); F(c->im_h[1]); F(c->im_u); F(c->im_upart); F(c->im_xs); F(c->im_sx); F(c->im_dpart); F(c->im_d); F(c->im_flag);
-    F(c->im_bx); F(c->im_bdpart); F(c->im_bout); F(c->im_perr);
-    c->im_bx_cap = c->im_bdpart_cap = c->im_bout_cap = c->im_perr_cap = 0;
+    F(c->im_bx); F(c->im_bdpart); F(c->im_res.dev); F(c->im_perr);
+    c->im_bx_cap = c->im_bdpart_cap = c->im_res.cap = c->im_perr_cap = 0;
     c->im_M = c->im_N = c->im_hh = c->im_ww = 0;
     c->im_xs_cap = 0;
     c->im_views = 0;
@@ -443,10 +443,8 @@ extern "C" int dv_infomax_train_from_poses(dv_ctx* c, const double* x, const dou
     int rc = infomax_need(c, "dv_infomax_train_from_poses");
     if (rc) return rc;
     if (!x || !y || !angle || n < 1 || n > 0x7fffffff) return fail(c, DV_ERR_INVALID, "dv_infomax_train_from_poses: bad arguments");
-    if (!c->have_sensor) return fail(c, DV_ERR_STATE, "sensor not configured");
-    if (c->sensor.sh != c->im_hh || c->sensor.sw != c->im_ww)
-        return fail(c, DV_ERR_INVALID, "dv_infomax_train_from_poses: the sensor is %dx%d but the model takes %dx%d views", c->sensor.sw, c->sensor.sh,
-                    c->im_ww, c->im_hh);
+    rc = sensor_fits(c, "dv_infomax_train_from_poses", c->im_hh, c->im_ww);
+    if (rc) return rc;
     if (!c->im_finite) return infomax_not_finite(c, "dv_infomax_train_from_poses");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)n * (size_t)c->im_N * 3;
@@ -490,10 +488,8 @@ extern "C" int dv_infomax_sense_step(dv_ctx* c, double x, double y, const double
     int rc = infomax_need(c, "dv_infomax_sense_step");
     if (rc) return rc;
     if (!angles || !angle_fam || !best_heading || n < 1) return fail(c, DV_ERR_INVALID, "dv_infomax_sense_step: NULL argument or n_headings < 1");
-    if (!c->have_sensor) return fail(c, DV_ERR_STATE, "sensor not configured");
-    if (c->sensor.sh != c->im_hh || c->sensor.sw != c->im_ww)
-        return fail(c, DV_ERR_INVALID, "dv_infomax_sense_step: the sensor is %dx%d but the model takes %dx%d views", c->sensor.sw, c->sensor.sh,
-                    c->im_ww, c->im_hh);
+    rc = sensor_fits(c, "dv_infomax_sense_step", c->im_hh, c->im_ww);
+    if (rc) return rc;
     if (!c->im_finite) return infomax_not_finite(c, "dv_infomax_sense_step");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t N = (size_t)c->im_N;
@@ -522,19 +518,6 @@ extern "C" int dv_infomax_sense_step(dv_ctx* c, double x, double y, const double
 // ---- ensembles: every member's headings in one enqueue and one wait ----------------------------------------------------------
 static constexpr long long kImSlabColsMax = 1 << 20;          // columns of one scoring launch (its grid's y extent: 16384 blocks)
 
-// Device buffers of the batch calls: allocated at first use, grown only when a call needs more.
-template <class T>
-static int infomax_grow(dv_ctx* c, T*& p, size_t& cap, size_t bytes) {
-    if (bytes <= cap) return DV_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    HIP_TRY(c, hipMalloc((void**)&p, bytes));
-    cap = bytes;
-    return DV_OK;
-}
-
 // planes != nullptr: uploaded uint8[n_agents][A][h][w]; else the poses (x[i], y[i], angles[i][a]) are sensed.  The unfused pair (sense,
 // then k_im_prep over the slab's patches in one launch) keeps x's bits by construction.  Columns go through X in slabs of at most
 // kImStageBytes, back to back on the stream; the host waits once, for the one copy of the packed results.
@@ -550,27 +533,17 @@ static int infomax_batch(dv_ctx* c, const char* who, const uint8_t* planes, cons
     if (slab < kImHeadings) slab = kImHeadings;
     if (slab > kImSlabColsMax) slab = kImSlabColsMax;
     if (slab > cpad) slab = cpad;
-    const size_t fam_bytes = (size_t)C * sizeof(double), out_bytes = fam_bytes + (size_t)n_agents * 8;
-    int rc = infomax_grow(c, c->im_bx, c->im_bx_cap, (size_t)slab * N * sizeof(double));
-    if (!rc) rc = infomax_grow(c, c->im_bdpart, c->im_bdpart_cap, (size_t)tiles * (size_t)cpad * sizeof(double));
-    if (!rc) rc = infomax_grow(c, c->im_bout, c->im_bout_cap, out_bytes);
-    if (!rc && !planes) rc = infomax_grow(c, c->im_perr, c->im_perr_cap, (size_t)C * sizeof(int));
+    double* d_fam = nullptr; int* d_best = nullptr; unsigned* d_flags = nullptr;   // the packed results' parts on the device
+    int rc = grow_buffer(c, c->im_bx, c->im_bx_cap, (size_t)slab * N * sizeof(double));
+    if (!rc) rc = grow_buffer(c, c->im_bdpart, c->im_bdpart_cap, (size_t)tiles * (size_t)cpad * sizeof(double));
+    if (!rc) rc = packed_device(c, c->im_res, C, n_agents, d_fam, d_best, d_flags);
+    if (!rc && !planes) rc = grow_buffer(c, c->im_perr, c->im_perr_cap, (size_t)C * sizeof(int));
     if (!rc) rc = ensure_sense_buffer(c, (size_t)slab * N * (planes ? 1 : 3));
     if (rc) return rc;
     if (!planes) {
-        if ((size_t)C > c->poses_cap) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            if (c->d_poses) (void)hipFree(c->d_poses);
-            c->d_poses = nullptr;
-            c->poses_cap = 0;
-            HIP_TRY(c, hipMalloc(&c->d_poses, (size_t)C * sizeof(Pose)));
-            c->poses_cap = (size_t)C;
-        }
-        c->h_poses.resize((size_t)C);
-        for (int i = 0; i < n_agents; ++i)
-            for (int a = 0; a < A; ++a) c->h_poses[(size_t)i * A + a] = make_pose(x[i], y[i], angles[(size_t)i * A + a]);
+        rc = upload_member_poses(c, x, y, angles, n_agents, A);
+        if (rc) return rc;
         HIP_TRY(c, hipMemsetAsync(c->im_perr, 0, (size_t)C * sizeof(int), c->stream));
-        HIP_TRY(c, hipMemcpyAsync(c->d_poses, c->h_poses.data(), (size_t)C * sizeof(Pose), hipMemcpyHostToDevice, c->stream));
     }
     for (long long c0 = 0; c0 < C; c0 += slab) {
         const long long nc = C - c0 < slab ? C - c0 : slab;
@@ -595,18 +568,13 @@ static int infomax_batch(dv_ctx* c, const char* who, const uint8_t* planes, cons
                                c->im_bdpart + c0);
         HIP_TRY(c, hipGetLastError());
     }
-    double* d_fam = reinterpret_cast<double*>(c->im_bout);
-    int* d_best = reinterpret_cast<int*>(c->im_bout + fam_bytes);
-    unsigned* d_flags = reinterpret_cast<unsigned*>(c->im_bout + fam_bytes + (size_t)n_agents * 4);
     hipLaunchKernelGGL(k_im_decide, dim3((unsigned)n_agents), dim3(256), 0, c->stream, c->im_bdpart, tiles, cpad, A, planes ? nullptr : c->im_perr,
                        d_fam, d_best, d_flags);
     HIP_TRY(c, hipGetLastError());
-    c->im_hout.resize(out_bytes);
-    HIP_TRY(c, hipMemcpyAsync(c->im_hout.data(), c->im_bout, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    rc = packed_fetch(c, c->im_res, C, n_agents);
+    if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    std::memcpy(angle_fam, c->im_hout.data(), fam_bytes);
-    std::memcpy(best_heading, c->im_hout.data() + fam_bytes, (size_t)n_agents * 4);
-    if (flags) std::memcpy(flags, c->im_hout.data() + fam_bytes + (size_t)n_agents * 4, (size_t)n_agents * 4);
+    packed_unpack(c->im_res, C, n_agents, angle_fam, best_heading, flags);
     return DV_OK;
 }
 
@@ -627,10 +595,8 @@ extern "C" int dv_batch_infomax_sense_step(dv_ctx* c, const double* x, const dou
     if (rc) return rc;
     if (!x || !y || !angles || !angle_fam || !best_heading || !flags || n_agents < 1 || n_headings < 1)
         return fail(c, DV_ERR_INVALID, "dv_batch_infomax_sense_step: NULL argument, n_agents < 1 or n_headings < 1");
-    if (!c->have_sensor) return fail(c, DV_ERR_STATE, "sensor not configured");
-    if (c->sensor.sh != c->im_hh || c->sensor.sw != c->im_ww)
-        return fail(c, DV_ERR_INVALID, "dv_batch_infomax_sense_step: the sensor is %dx%d but the model takes %dx%d views", c->sensor.sw, c->sensor.sh,
-                    c->im_ww, c->im_hh);
+    rc = sensor_fits(c, "dv_batch_infomax_sense_step", c->im_hh, c->im_ww);
+    if (rc) return rc;
     if (!c->im_finite) return infomax_not_finite(c, "dv_batch_infomax_sense_step");
     return infomax_batch(c, "dv_batch_infomax_sense_step", nullptr, x, y, angles, n_agents, n_headings, angle_fam, best_heading, flags);
 }

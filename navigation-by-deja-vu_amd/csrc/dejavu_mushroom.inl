@@ -20,8 +20,8 @@
 //   k_mb_pose    kMbScore from a pose instead of staged bytes (an ensemble's step, dv_batch_mb_sense_step): the workgroup fills its LDS
 //                plane with the compared channel of the sensor model's pixels (sense_pixel) at its column's pose, so no view goes
 //                through HBM, and records in a word of its own whether a pixel left the landscape.  The body after the plane is k_mb's.
-//   k_mb_decide  fam[a] = (double)(-d[a]) and the first maximum over the headings (np.argmax), one workgroup
-//   k_mb_decide_batch  the same per member of an ensemble, one workgroup each, with the member's DV_RES_SENSE_ERROR flag
+//   k_mb_decide_batch  fam[a] = (double)(-d[a]) and the first maximum over a member's headings (np.argmax), one workgroup per member
+//                (an agent's own step is an ensemble of one), with the member's DV_RES_SENSE_ERROR flag
 //   k_mb_count   the number of zero weights, one workgroup
 namespace dv {
 
@@ -164,28 +164,6 @@ __global__ __launch_bounds__(kMbWaves * 64) void k_mb_pose(const unsigned char* 
     }, (int)blockIdx.x, N, conn, K, c, n_active, wt, d, nullptr, nullptr);
 }
 
-// fam[a] = (double)(-d[a]); *best = the first maximum (the larger value, the lower heading of equals)
-__global__ __launch_bounds__(256) void k_mb_decide(const int* __restrict__ d, int n, double* __restrict__ fam, int* __restrict__ best) {
-    __shared__ int sv[256], si[256];
-    const int tid = (int)threadIdx.x;
-    int bv = 0, bi = -1;
-    for (int a = tid; a < n; a += 256) {                      // headings in rising order: a later equal does not replace
-        const int v = -d[a];
-        fam[a] = (double)v;
-        if (bi < 0 || v > bv) { bv = v; bi = a; }
-    }
-    sv[tid] = bv; si[tid] = bi;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) {
-            const int ov = sv[tid + st], oi = si[tid + st];
-            if (oi >= 0 && (si[tid] < 0 || ov > sv[tid] || (ov == sv[tid] && oi < si[tid]))) { sv[tid] = ov; si[tid] = oi; }
-        }
-        __syncthreads();
-    }
-    if (tid == 0) *best = si[0];
-}
-
 // One workgroup per member i of A columns: fam[i][a] = (double)(-d[i A + a]); best[i] = the member's first maximum (the larger value,
 // the lower heading of equals, whichever thread held it).  perr (nullptr: the planes were uploaded) holds k_mb_pose's word per column:
 // a member with one set gets best -1 and kResSenseError.
@@ -240,8 +218,8 @@ static constexpr size_t kMbStageBytes = 64u << 20;           // ... and the byte
 
 static void mb_free(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-    F(c->mb_conn); F(c->mb_wt); F(c->mb_d); F(c->mb_out); F(c->mb_fired); F(c->mb_zeros); F(c->mb_bd); F(c->mb_berr); F(c->mb_bout);
-    c->mb_d_cap = c->mb_out_cap = c->mb_fired_cap = c->mb_bd_cap = c->mb_berr_cap = c->mb_bout_cap = 0;
+    F(c->mb_conn); F(c->mb_wt); F(c->mb_d); F(c->mb_fired); F(c->mb_zeros); F(c->mb_bd); F(c->mb_berr); F(c->mb_res.dev);
+    c->mb_d_cap = c->mb_fired_cap = c->mb_bd_cap = c->mb_berr_cap = c->mb_res.cap = 0;
     c->mb_K = c->mb_N = c->mb_c = c->mb_active = c->mb_hh = c->mb_ww = 0;
     c->mb_views = 0;
 }
@@ -270,13 +248,6 @@ static int mb_launch(dv_ctx* c, const unsigned char* d_src, long long view_strid
     hipLaunchKernelGGL((k_mb<MODE>), dim3((unsigned)n), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, d_src, view_stride, px_stride, offset, c->mb_N,
                        c->mb_conn, c->mb_K, c->mb_c, c->mb_active, c->mb_wt, d, fired, thr);
     HIP_TRY(c, hipGetLastError());
-    return DV_OK;
-}
-
-static int mb_sensor_fits(dv_ctx* c, const char* who) {
-    if (!c->have_sensor) return fail(c, DV_ERR_STATE, "sensor not configured");
-    if (c->sensor.sh != c->mb_hh || c->sensor.sw != c->mb_ww)
-        return fail(c, DV_ERR_INVALID, "%s: the sensor is %dx%d but the model takes %dx%d views", who, c->sensor.sw, c->sensor.sh, c->mb_ww, c->mb_hh);
     return DV_OK;
 }
 
@@ -359,7 +330,7 @@ extern "C" int dv_mb_train_from_poses(dv_ctx* c, const double* x, const double* 
     int rc = mb_need(c, "dv_mb_train_from_poses");
     if (rc) return rc;
     if (!x || !y || !angle || n < 1 || n > 0x7fffffff) return fail(c, DV_ERR_INVALID, "dv_mb_train_from_poses: bad arguments");
-    rc = mb_sensor_fits(c, "dv_mb_train_from_poses");
+    rc = sensor_fits(c, "dv_mb_train_from_poses", c->mb_hh, c->mb_ww);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)n * (size_t)c->mb_N * 3;
@@ -391,7 +362,7 @@ extern "C" int dv_mb_score_u8(dv_ctx* c, const uint8_t* planes, int n, double* f
     int64_t slab = mb_slab(N);
     if (slab > n) slab = n;
     rc = ensure_sense_buffer(c, (size_t)slab * N);
-    if (!rc) rc = infomax_grow(c, c->mb_d, c->mb_d_cap, (size_t)slab * sizeof(int));
+    if (!rc) rc = grow_buffer(c, c->mb_d, c->mb_d_cap, (size_t)slab * sizeof(int));
     if (rc) return rc;
     std::vector<int> dh((size_t)slab);
     for (int64_t v0 = 0; v0 < n; v0 += slab) {
@@ -416,8 +387,8 @@ extern "C" int dv_mb_activity_u8(dv_ctx* c, const uint8_t* planes, int n, uint8_
     int64_t slab = mb_slab(N > K ? N : K);
     if (slab > n) slab = n;
     rc = ensure_sense_buffer(c, (size_t)slab * N);
-    if (!rc) rc = infomax_grow(c, c->mb_d, c->mb_d_cap, (size_t)slab * sizeof(int));
-    if (!rc && fired) rc = infomax_grow(c, c->mb_fired, c->mb_fired_cap, (size_t)slab * K);
+    if (!rc) rc = grow_buffer(c, c->mb_d, c->mb_d_cap, (size_t)slab * sizeof(int));
+    if (!rc && fired) rc = grow_buffer(c, c->mb_fired, c->mb_fired_cap, (size_t)slab * K);
     if (rc) return rc;
     for (int64_t v0 = 0; v0 < n; v0 += slab) {
         const int64_t ns = n - v0 < slab ? n - v0 : slab;
@@ -436,13 +407,13 @@ extern "C" int dv_mb_sense_step(dv_ctx* c, double x, double y, const double* ang
     int rc = mb_need(c, "dv_mb_sense_step");
     if (rc) return rc;
     if (!angles || !angle_fam || !best_heading || n < 1) return fail(c, DV_ERR_INVALID, "dv_mb_sense_step: NULL argument or n_headings < 1");
-    rc = mb_sensor_fits(c, "dv_mb_sense_step");
+    rc = sensor_fits(c, "dv_mb_sense_step", c->mb_hh, c->mb_ww);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t fam_bytes = (size_t)n * sizeof(double), out_bytes = fam_bytes + sizeof(int);
+    double* d_fam = nullptr; int* d_best = nullptr; unsigned* d_flags = nullptr;   // the packed results' parts on the device
     rc = ensure_sense_buffer(c, (size_t)n * (size_t)c->mb_N * 3);
-    if (!rc) rc = infomax_grow(c, c->mb_d, c->mb_d_cap, (size_t)n * sizeof(int));
-    if (!rc) rc = infomax_grow(c, c->mb_out, c->mb_out_cap, out_bytes);
+    if (!rc) rc = grow_buffer(c, c->mb_d, c->mb_d_cap, (size_t)n * sizeof(int));
+    if (!rc) rc = packed_device(c, c->mb_res, n, 1, d_fam, d_best, d_flags);
     if (rc) return rc;
     c->mb_xy.assign((size_t)n, x);
     c->mb_xy.resize(2 * (size_t)n, y);
@@ -454,16 +425,13 @@ extern "C" int dv_mb_sense_step(dv_ctx* c, double x, double y, const double* ang
         rc = mb_launch<kMbScore>(c, c->d_sense + (size_t)v0 * (size_t)stride, stride, 3, c->mb_channel, ns, c->mb_d + v0, nullptr, nullptr);
         if (rc) return rc;
     }
-    double* d_fam = reinterpret_cast<double*>(c->mb_out);
-    int* d_best = reinterpret_cast<int*>(c->mb_out + fam_bytes);
-    hipLaunchKernelGGL(k_mb_decide, dim3(1), dim3(256), 0, c->stream, c->mb_d, n, d_fam, d_best);
+    // an ensemble of one whose patches are in d_sense: no word per pose (k_sense's one flag is read below), so the member's flag is 0
+    hipLaunchKernelGGL(k_mb_decide_batch, dim3(1), dim3(256), 0, c->stream, c->mb_d, (const int*)nullptr, n, d_fam, d_best, d_flags);
     HIP_TRY(c, hipGetLastError());
-    c->mb_hout.resize(out_bytes);
-    HIP_TRY(c, hipMemcpyAsync(c->mb_hout.data(), c->mb_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    rc = check_sense_error(c);                                // (synchronises)
+    rc = packed_fetch(c, c->mb_res, n, 1);
+    if (!rc) rc = check_sense_error(c);                       // (synchronises; a footprint off the landscape: DV_ERR_INDEX)
     if (rc) return rc;
-    std::memcpy(angle_fam, c->mb_hout.data(), fam_bytes);
-    std::memcpy(best_heading, c->mb_hout.data() + fam_bytes, sizeof(int));
+    packed_unpack(c->mb_res, n, 1, angle_fam, best_heading, nullptr);
     return DV_OK;
 }
 
@@ -477,27 +445,17 @@ static int mb_batch(dv_ctx* c, const char* who, const uint8_t* planes, const dou
     if (C > 0x7fffffffll) return fail(c, DV_ERR_INVALID, "%s: %d agents x %d headings are too many columns", who, n_agents, A);
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t N = (size_t)c->mb_N;
-    const size_t fam_bytes = (size_t)C * sizeof(double), out_bytes = fam_bytes + (size_t)n_agents * 8;
     long long slab = planes ? (long long)mb_slab(N) : (long long)kMbSlabViews;
     if (slab > C) slab = C;
-    int rc = infomax_grow(c, c->mb_bd, c->mb_bd_cap, (size_t)C * sizeof(int));
-    if (!rc) rc = infomax_grow(c, c->mb_bout, c->mb_bout_cap, out_bytes);
-    if (!rc && !planes) rc = infomax_grow(c, c->mb_berr, c->mb_berr_cap, (size_t)C * sizeof(int));
+    double* d_fam = nullptr; int* d_best = nullptr; unsigned* d_flags = nullptr;   // the packed results' parts on the device
+    int rc = grow_buffer(c, c->mb_bd, c->mb_bd_cap, (size_t)C * sizeof(int));
+    if (!rc) rc = packed_device(c, c->mb_res, C, n_agents, d_fam, d_best, d_flags);
+    if (!rc && !planes) rc = grow_buffer(c, c->mb_berr, c->mb_berr_cap, (size_t)C * sizeof(int));
     if (!rc && planes) rc = ensure_sense_buffer(c, (size_t)slab * N);
     if (rc) return rc;
     if (!planes) {
-        if ((size_t)C > c->poses_cap) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            if (c->d_poses) (void)hipFree(c->d_poses);
-            c->d_poses = nullptr;
-            c->poses_cap = 0;
-            HIP_TRY(c, hipMalloc(&c->d_poses, (size_t)C * sizeof(Pose)));
-            c->poses_cap = (size_t)C;
-        }
-        c->h_poses.resize((size_t)C);
-        for (int i = 0; i < n_agents; ++i)
-            for (int a = 0; a < A; ++a) c->h_poses[(size_t)i * A + a] = make_pose(x[i], y[i], angles[(size_t)i * A + a]);
-        HIP_TRY(c, hipMemcpyAsync(c->d_poses, c->h_poses.data(), (size_t)C * sizeof(Pose), hipMemcpyHostToDevice, c->stream));
+        rc = upload_member_poses(c, x, y, angles, n_agents, A);
+        if (rc) return rc;
     }
     for (long long c0 = 0; c0 < C; c0 += slab) {
         const int nc = (int)(C - c0 < slab ? C - c0 : slab);
@@ -511,18 +469,13 @@ static int mb_batch(dv_ctx* c, const char* who, const uint8_t* planes, const dou
             HIP_TRY(c, hipGetLastError());
         }
     }
-    double* d_fam = reinterpret_cast<double*>(c->mb_bout);
-    int* d_best = reinterpret_cast<int*>(c->mb_bout + fam_bytes);
-    unsigned* d_flags = reinterpret_cast<unsigned*>(c->mb_bout + fam_bytes + (size_t)n_agents * 4);
     hipLaunchKernelGGL(k_mb_decide_batch, dim3((unsigned)n_agents), dim3(256), 0, c->stream, c->mb_bd, planes ? nullptr : c->mb_berr, A, d_fam, d_best,
                        d_flags);
     HIP_TRY(c, hipGetLastError());
-    c->mb_bhout.resize(out_bytes);
-    HIP_TRY(c, hipMemcpyAsync(c->mb_bhout.data(), c->mb_bout, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    rc = packed_fetch(c, c->mb_res, C, n_agents);
+    if (rc) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    std::memcpy(angle_fam, c->mb_bhout.data(), fam_bytes);
-    std::memcpy(best_heading, c->mb_bhout.data() + fam_bytes, (size_t)n_agents * 4);
-    if (flags) std::memcpy(flags, c->mb_bhout.data() + fam_bytes + (size_t)n_agents * 4, (size_t)n_agents * 4);
+    packed_unpack(c->mb_res, C, n_agents, angle_fam, best_heading, flags);
     return DV_OK;
 }
 
@@ -542,7 +495,7 @@ extern "C" int dv_batch_mb_sense_step(dv_ctx* c, const double* x, const double* 
     if (rc) return rc;
     if (!x || !y || !angles || !angle_fam || !best_heading || !flags || n_agents < 1 || n_headings < 1)
         return fail(c, DV_ERR_INVALID, "dv_batch_mb_sense_step: NULL argument, n_agents < 1 or n_headings < 1");
-    rc = mb_sensor_fits(c, "dv_batch_mb_sense_step");
+    rc = sensor_fits(c, "dv_batch_mb_sense_step", c->mb_hh, c->mb_ww);
     if (rc) return rc;
     return mb_batch(c, "dv_batch_mb_sense_step", nullptr, x, y, angles, n_agents, n_headings, angle_fam, best_heading, flags);
 }

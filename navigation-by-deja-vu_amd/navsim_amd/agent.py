@@ -14,6 +14,7 @@ import os
 
 import numpy as np
 
+from .engine import ONE_VALUE_METRICS
 from .util import sads_familiarity
 
 
@@ -246,14 +247,12 @@ class NavBySceneFamiliarity(object):
             for pt in points:
                 self._check_bounds(pt)
             # sensed and ingested on the device; familiar_scenes comes back for the API
-            if getattr(self.familiarity_model, "metric", "sads_hsv") == "infomax":
-                # no library: a fresh weight matrix, trained on the views where they are sensed
+            if getattr(self.familiarity_model, "metric", "sads_hsv") in ONE_VALUE_METRICS:
+                # no library: a fresh model (Infomax: a weight matrix; mushroom body: Kenyon-cell weights), trained on the views where
+                # they are sensed
                 self.familiarity_model.begin(self._engine, self.sensor_dimensions[1], self.sensor_dimensions[0])
-                self.familiar_scenes[...] = self._engine.infomax_train_from_poses(points[:, 0], points[:, 1], view_headings)
-            elif getattr(self.familiarity_model, "metric", "sads_hsv") == "mushroom":
-                # no library either: fresh Kenyon-cell weights, depressed by the views where they are sensed
-                self.familiarity_model.begin(self._engine, self.sensor_dimensions[1], self.sensor_dimensions[0])
-                self.familiar_scenes[...] = self._engine.mb_train_from_poses(points[:, 0], points[:, 1], view_headings)
+                model = self._engine.one_value(self.familiarity_model.metric)
+                self.familiar_scenes[...] = model.train_from_poses(points[:, 0], points[:, 1], view_headings)
             elif getattr(self.familiarity_model, "metric", "sads_hsv") == "ssd":
                 self.familiar_scenes[...] = self._engine.set_library_u8_from_poses(
                     points[:, 0], points[:, 1], view_headings, self.familiarity_model.channel)
@@ -298,24 +297,16 @@ class NavBySceneFamiliarity(object):
         view_headings = headings[np.minimum(np.arange(n), n - 2)]
         engine = getattr(self._familiarity_func, "engine", None)
         ssd = str(getattr(self._familiarity_func, "metric", "")).startswith("ssd")
-        infomax = getattr(self._familiarity_func, "metric", "") == "infomax"
-        mushroom = getattr(self._familiarity_func, "metric", "") == "mushroom"
-        if infomax and self._engine is not None and engine is self._engine:
-            # the Infomax model keeps training on the same weights: the new views follow the old ones in the chain
+        one_value = getattr(self._familiarity_func, "metric", "") in ONE_VALUE_METRICS
+        if one_value and self._engine is not None and engine is self._engine:
+            # the model keeps training on the same weights (Infomax: the new views follow the old ones in the chain; mushroom body: the
+            # same weights are depressed further, in no order)
             for pt in points:
                 self._check_bounds(pt)
-            new_views = self._engine.infomax_train_from_poses(points[:, 0], points[:, 1], view_headings)
-        elif infomax:
+            new_views = engine.one_value(self._familiarity_func.metric).train_from_poses(points[:, 0], points[:, 1], view_headings)
+        elif one_value:
             new_views = np.stack([self.get_sensor_mat(points[i], view_headings[i]) for i in range(n)])
-            engine.infomax_train_u8(np.ascontiguousarray(new_views[..., self._familiarity_func.channel]))
-        elif mushroom and self._engine is not None and engine is self._engine:
-            # the mushroom-body model keeps depressing the same weights: training has no order
-            for pt in points:
-                self._check_bounds(pt)
-            new_views = self._engine.mb_train_from_poses(points[:, 0], points[:, 1], view_headings)
-        elif mushroom:
-            new_views = np.stack([self.get_sensor_mat(points[i], view_headings[i]) for i in range(n)])
-            engine.mb_train_u8(np.ascontiguousarray(new_views[..., self._familiarity_func.channel]))
+            engine.one_value(self._familiarity_func.metric).train_u8(np.ascontiguousarray(new_views[..., self._familiarity_func.channel]))
         elif self._engine is not None and engine is self._engine and not ssd:
             for pt in points:
                 self._check_bounds(pt)
@@ -349,10 +340,8 @@ class NavBySceneFamiliarity(object):
         if func is not None and hasattr(func, "engine"):
             if func.engine is getattr(self, "_engine", None):
                 func.engine.clear_library()          # keep the landscape and the sensor configuration
-                if getattr(func, "metric", "") == "infomax":
-                    func.engine.infomax_end()
-                if getattr(func, "metric", "") == "mushroom":
-                    func.engine.mb_end()
+                if getattr(func, "metric", "") in ONE_VALUE_METRICS:
+                    func.engine.one_value(func.metric).end()
             else:
                 func.engine.close()
         if getattr(self, "_metrics_on_device", False) and getattr(self, "_engine", None) is not None:
@@ -581,11 +570,8 @@ class NavBySceneFamiliarity(object):
         if engine is not None and str(getattr(func, "metric", "")).startswith("ssd"):
             self._step_ssd(func, engine, position)
             best_idex = self.last_scored_idex
-        elif engine is not None and getattr(func, "metric", "") == "infomax":
-            self._step_infomax(func, engine, position)
-            best_idex = self.last_scored_idex
-        elif engine is not None and getattr(func, "metric", "") == "mushroom":
-            self._step_mushroom(func, engine, position)
+        elif engine is not None and getattr(func, "metric", "") in ONE_VALUE_METRICS:
+            self._step_one_value(func, engine, position)
             best_idex = self.last_scored_idex
         elif engine is not None:
             # one fused device step for all headings: kernel + min-merge + max + argmax (:289-315)
@@ -718,32 +704,24 @@ class NavBySceneFamiliarity(object):
             self._scene_is_inf = True
         self.last_scored_idex = res["best_idex"]
 
-    def _step_infomax(self, func, engine, position):
-        """The heading loop (:289-315) with the Infomax plug-in (util.infomax_familiarity): ONE device call -- sense, score W x for all
-        headings in one pass over the weights, first maximum -- when the sensor model runs on the GPU; with a foreign engine or the host
-        sensor model the patches are sensed here and scored in one call.  familiarity = -sum|W x|.  The model has no per-view score:
+    def _step_one_value(self, func, engine, position):
+        """The heading loop (:289-315) with a plug-in without per-view memory (util.infomax_familiarity, util.mushroom_familiarity): ONE
+        device call -- sense, score all headings (Infomax: W x in one pass over the weights; mushroom body: every heading's Kenyon cells
+        selected and their intact weights counted in one launch), first maximum -- when the sensor model runs on the GPU; with a foreign
+        engine or the host sensor model the patches are sensed here and scored in one call.  familiarity = -sum|W x| (Infomax) or -d
+        (mushroom body: an integer, so headings tie, and the first maximum decides as np.argmax does).  The model has no per-view score:
         scene_familiarity is the least familiarity over the headings at every view (what the reference's loop leaves when the plug-in
         fills its buffer with the one value)."""
-        self._step_one_value(func, engine, position, engine.infomax_sense_step, engine.infomax_score_u8)
-
-    def _step_mushroom(self, func, engine, position):
-        """The heading loop (:289-315) with the mushroom-body plug-in (util.mushroom_familiarity): ONE device call -- sense, every
-        heading's Kenyon cells selected and their intact weights counted in one launch, first maximum -- when the sensor model runs on
-        the GPU; otherwise the patches are sensed here and scored in one call.  familiarity = -d, an integer: headings tie, and the
-        first maximum decides as np.argmax does.  scene_familiarity as for the Infomax model."""
-        self._step_one_value(func, engine, position, engine.mb_sense_step, engine.mb_score_u8)
-
-    def _step_one_value(self, func, engine, position, sense_step, score_u8):
-        """A step of a model without per-view memory (Infomax, mushroom body) through its engine's sense_step / score_u8 pair."""
+        model = engine.one_value(func.metric)
         angles = (self.angle + self.angle_offsets) % (2 * np.pi)
         try:
             if engine is self._engine:
                 self._check_bounds(position)
-                best, _ = sense_step(position[0], position[1], angles, self.angle_familiarity)
+                best, _ = model.sense_step(position[0], position[1], angles, self.angle_familiarity)
             else:
                 patches = np.stack([self.get_sensor_mat(position, a) for a in angles])
                 planes = np.ascontiguousarray(patches[..., func.channel] if patches.ndim == 4 else patches)
-                score_u8(planes, self.angle_familiarity)
+                model.score_u8(planes, self.angle_familiarity)
                 best = int(np.argmax(self.angle_familiarity))
         except Exception:
             self._scene_fam[:] = np.inf

@@ -1,5 +1,6 @@
 """FamiliarityEngine -- Python face of one dv_ctx (one GPU, one stored-view library shard)."""
 import ctypes
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -51,7 +52,7 @@ class BatchResults(object):
         return (self[i] for i in range(self.n))
 
 
-class InfomaxBatchResults(object):
+class OneValueBatchResults(object):
     """An ensemble step of the Infomax model (dv_batch_infomax_step_u8 / dv_batch_infomax_sense_step) or of the mushroom-body model
     (dv_batch_mb_step_u8 / dv_batch_mb_sense_step), in BatchResults' shape for
     callers that move agents: angle_familiarity[n, A] (float64), best_idex[n] (int32; -1 for a member whose footprint left the
@@ -63,6 +64,20 @@ class InfomaxBatchResults(object):
 
     def __len__(self):
         return self.n
+
+
+InfomaxBatchResults = OneValueBatchResults     # the name it had while Infomax was the only such model
+
+# The one-value models -- no library, ONE value per heading: metric -> (prefix of the single calls' symbols, of the batch calls', the
+# engine attribute that holds the model's (h, w)).
+_ONE_VALUE = {"infomax": ("dv_infomax_", "dv_batch_infomax_", "infomax_shape"),
+              "mushroom": ("dv_mb_", "dv_batch_mb_", "mb_shape")}
+ONE_VALUE_METRICS = tuple(_ONE_VALUE)
+
+
+def one_value_prefix(metric):
+    """"infomax_" / "mb_": what the names of the engine's methods for the one-value model `metric` begin with."""
+    return _ONE_VALUE[metric][0][3:]
 
 
 class FamiliarityEngine(object):
@@ -773,6 +788,89 @@ class FamiliarityEngine(object):
                     "dv_stream_read_gbps")
         return float(g.value)
 
+    # -- the one-value models (Infomax, mushroom body): one implementation per operation, the model's symbols from _ONE_VALUE ----
+    @staticmethod
+    def _model_planes(shape, planes, what):
+        """`planes` as uint8[n,h,w] of a model begun with shape (h, w); one uint8[h,w] counts as n = 1."""
+        planes = N.as_u8(planes, what)
+        if planes.ndim == 2:
+            planes = planes[None]
+        if shape is None:
+            return planes if planes.ndim == 3 else planes.reshape(1, 1, -1)      # (no model: the library answers DV_ERR_STATE)
+        if planes.ndim != 3 or tuple(planes.shape[1:]) != shape:
+            raise ValueError("%s must be uint8[n,%d,%d], got shape %r" % ((what,) + shape + (planes.shape,)))
+        return planes
+
+    def _ov_planes(self, metric, planes):
+        return self._model_planes(getattr(self, _ONE_VALUE[metric][2], None), planes, "planes")
+
+    def one_value(self, metric):
+        """The bound train_u8, train_from_poses, score_u8, sense_step and end of the one-value model `metric` ("infomax" or
+        "mushroom": ONE_VALUE_METRICS), so that a caller needs no branch per model."""
+        prefix = one_value_prefix(metric)
+        return SimpleNamespace(**{op: getattr(self, prefix + op) for op in ("train_u8", "train_from_poses", "score_u8", "sense_step", "end")})
+
+    def _ov_train_u8(self, metric, planes):
+        name = _ONE_VALUE[metric][0] + "train_u8"
+        planes = self._ov_planes(metric, planes)
+        self._check(getattr(self._lib, name)(self._ctx, N.u8ptr(planes), planes.shape[0]), name)
+
+    def _ov_train_from_poses(self, metric, x, y, angle, want_views):
+        name = _ONE_VALUE[metric][0] + "train_from_poses"
+        x, y, angle = self._pose_arrays(x, y, angle)
+        h, w = self.sensor_shape
+        views = np.empty((len(x), h, w, 3), dtype=np.uint8) if want_views else None
+        self._check_sense(getattr(self._lib, name)(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), len(x),
+                                                   N.u8ptr(views) if want_views else None), name)
+        return views
+
+    def _ov_score_u8(self, metric, planes, out):
+        name = _ONE_VALUE[metric][0] + "score_u8"
+        planes = self._ov_planes(metric, planes)
+        if out is None:
+            out = np.empty(planes.shape[0], dtype=np.float64)
+        assert out.dtype == np.float64 and out.flags.c_contiguous and out.size == planes.shape[0]
+        self._check(getattr(self._lib, name)(self._ctx, N.u8ptr(planes), planes.shape[0], N.f64ptr(out)), name)
+        return out
+
+    def _ov_sense_step(self, metric, x, y, angles, out_fam):
+        name = _ONE_VALUE[metric][0] + "sense_step"
+        angles = np.ascontiguousarray(angles, dtype=np.float64).reshape(-1)
+        if out_fam is None:
+            out_fam = np.empty(len(angles), dtype=np.float64)
+        assert out_fam.dtype == np.float64 and out_fam.flags.c_contiguous and out_fam.size == len(angles)
+        best = ctypes.c_int32(-1)
+        self._check_sense(getattr(self._lib, name)(self._ctx, float(x), float(y), N.f64ptr(angles), len(angles), N.f64ptr(out_fam),
+                                                   ctypes.byref(best)), name)
+        return int(best.value), out_fam
+
+    def _ov_step_batch_u8(self, metric, planes):
+        name = _ONE_VALUE[metric][1] + "step_u8"
+        planes = N.as_u8(planes, "planes")
+        if planes.ndim != 4 or planes.shape[0] < 1 or planes.shape[1] < 1:
+            raise ValueError("planes must be uint8[n,A,h,w] with n, A >= 1, got shape %r" % (planes.shape,))
+        n, A = planes.shape[:2]
+        flat = self._ov_planes(metric, planes.reshape((n * A,) + planes.shape[2:]))
+        fam = np.empty((n, A), dtype=np.float64)
+        best = np.full(n, -1, dtype=np.int32)
+        self._check(getattr(self._lib, name)(self._ctx, N.u8ptr(flat), n, A, N.f64ptr(fam), best.ctypes.data_as(N._i32p)), name)
+        return OneValueBatchResults(fam, best, np.zeros(n, dtype=np.uint32))
+
+    def _ov_sense_step_batch(self, metric, x, y, angles):
+        name = _ONE_VALUE[metric][1] + "sense_step"
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        angles = np.ascontiguousarray(angles, dtype=np.float64)
+        if angles.ndim != 2 or len(x) != len(y) or angles.shape[0] != len(x) or angles.shape[0] < 1 or angles.shape[1] < 1:
+            raise ValueError("x[N], y[N] and angles[N, A] expected (N, A >= 1), got shapes %r, %r and %r" % (x.shape, y.shape, angles.shape))
+        n, A = angles.shape
+        fam = np.empty((n, A), dtype=np.float64)
+        best = np.full(n, -1, dtype=np.int32)
+        flags = np.zeros(n, dtype=np.uint32)
+        self._check(getattr(self._lib, name)(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, N.f64ptr(fam),
+                                             best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)), name)
+        return OneValueBatchResults(fam, best, flags)
+
     # -- Infomax familiarity model: one layer of weights instead of a library (include/dejavu.h: dv_infomax_*) ----------------
     def infomax_begin(self, h, w, weights, channel=2, learning_rate=0.01):
         """weights: float64[n_hidden, h*w], the initial W (drawn by the caller: util.infomax_initial_weights).  Copied to the GPU."""
@@ -784,82 +882,32 @@ class FamiliarityEngine(object):
         self.infomax_shape = (int(h), int(w))
         self.infomax_hidden = weights.shape[0]
 
-    def _infomax_planes(self, planes, what):
-        planes = N.as_u8(planes, what)
-        shape = getattr(self, "infomax_shape", None)
-        if planes.ndim == 2:
-            planes = planes[None]
-        if shape is None:
-            return planes if planes.ndim == 3 else planes.reshape(1, 1, -1)      # (no model: the library answers DV_ERR_STATE)
-        if planes.ndim != 3 or tuple(planes.shape[1:]) != shape:
-            raise ValueError("%s must be uint8[n,%d,%d], got shape %r" % ((what,) + shape + (planes.shape,)))
-        return planes
-
     def infomax_train_u8(self, planes):
         """One more pass of the learning rule over uint8[n,h,w] planes, in order, on the same W."""
-        planes = self._infomax_planes(planes, "planes")
-        self._check(self._lib.dv_infomax_train_u8(self._ctx, N.u8ptr(planes), planes.shape[0]), "dv_infomax_train_u8")
+        self._ov_train_u8("infomax", planes)
 
     def infomax_train_from_poses(self, x, y, angle, want_views=True):
         """train_from_path for the Infomax plug-in on the device: sense the poses, train on their compared plane; returns
         familiar_scenes (uint8[n,h,w,3]) when want_views."""
-        x, y, angle = self._pose_arrays(x, y, angle)
-        h, w = self.sensor_shape
-        views = np.empty((len(x), h, w, 3), dtype=np.uint8) if want_views else None
-        self._check_sense(self._lib.dv_infomax_train_from_poses(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), len(x),
-                                                                N.u8ptr(views) if want_views else None),
-                          "dv_infomax_train_from_poses")
-        return views
+        return self._ov_train_from_poses("infomax", x, y, angle, want_views)
 
     def infomax_score_u8(self, planes, out=None):
         """familiarity = -sum|W x| of each of uint8[n,h,w] planes (or one uint8[h,w]) -> float64[n]."""
-        planes = self._infomax_planes(planes, "planes")
-        if out is None:
-            out = np.empty(planes.shape[0], dtype=np.float64)
-        self._check(self._lib.dv_infomax_score_u8(self._ctx, N.u8ptr(planes), planes.shape[0], N.f64ptr(out)), "dv_infomax_score_u8")
-        return out
+        return self._ov_score_u8("infomax", planes, out)
 
     def infomax_sense_step(self, x, y, angles, out_fam=None):
         """One agent step: sense the heading patches at (x, y), score them, first maximum -> (best_idex, angle_familiarity)."""
-        angles = np.ascontiguousarray(angles, dtype=np.float64).reshape(-1)
-        if out_fam is None:
-            out_fam = np.empty(len(angles), dtype=np.float64)
-        assert out_fam.dtype == np.float64 and out_fam.flags.c_contiguous and out_fam.size == len(angles)
-        best = ctypes.c_int32(-1)
-        self._check_sense(self._lib.dv_infomax_sense_step(self._ctx, float(x), float(y), N.f64ptr(angles), len(angles), N.f64ptr(out_fam),
-                                                          ctypes.byref(best)), "dv_infomax_sense_step")
-        return int(best.value), out_fam
+        return self._ov_sense_step("infomax", x, y, angles, out_fam)
 
     def infomax_step_batch_u8(self, planes):
         """An ensemble's step on uploaded patches: uint8[n, A, h, w] planes, member i's A headings in row i -> InfomaxBatchResults (every
         member's familiarities and first maximum from one device call; the flags are 0)."""
-        planes = N.as_u8(planes, "planes")
-        if planes.ndim != 4:
-            raise ValueError("planes must be uint8[n,A,h,w], got shape %r" % (planes.shape,))
-        n, A = planes.shape[:2]
-        flat = self._infomax_planes(planes.reshape((n * A,) + planes.shape[2:]), "planes") if n * A else planes
-        fam = np.empty((n, A), dtype=np.float64)
-        best = np.full(n, -1, dtype=np.int32)
-        self._check(self._lib.dv_batch_infomax_step_u8(self._ctx, N.u8ptr(flat), n, A, N.f64ptr(fam), best.ctypes.data_as(N._i32p)),
-                    "dv_batch_infomax_step_u8")
-        return InfomaxBatchResults(fam, best, np.zeros(n, dtype=np.uint32))
+        return self._ov_step_batch_u8("infomax", planes)
 
     def infomax_sense_step_batch(self, x, y, angles):
         """An ensemble's step: member i at (x[i], y[i]) looking along angles[i][0..A) -> InfomaxBatchResults.  One enqueue and one wait
         for all members; a member whose footprint leaves the landscape is flagged (flags & 16, best_idex -1), the others are scored."""
-        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
-        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
-        angles = np.ascontiguousarray(angles, dtype=np.float64)
-        if angles.ndim != 2 or len(x) != len(y) or angles.shape[0] != len(x):
-            raise ValueError("x[N], y[N] and angles[N, A] expected")
-        n, A = angles.shape
-        fam = np.empty((n, A), dtype=np.float64)
-        best = np.full(n, -1, dtype=np.int32)
-        flags = np.zeros(n, dtype=np.uint32)
-        self._check(self._lib.dv_batch_infomax_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, N.f64ptr(fam),
-                                                          best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)),
-                    "dv_batch_infomax_sense_step")
-        return InfomaxBatchResults(fam, best, flags)
+        return self._ov_sense_step_batch("infomax", x, y, angles)
 
     def infomax_info(self):
         m, n, fin = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
@@ -897,44 +945,22 @@ class FamiliarityEngine(object):
                                           conn.ctypes.data_as(N._i32p)), "dv_mb_begin")
         self.mb_shape = (int(h), int(w))
 
-    def _mb_planes(self, planes, what):
-        planes = N.as_u8(planes, what)
-        shape = getattr(self, "mb_shape", None)
-        if planes.ndim == 2:
-            planes = planes[None]
-        if shape is None:
-            return planes if planes.ndim == 3 else planes.reshape(1, 1, -1)      # (no model: the library answers DV_ERR_STATE)
-        if planes.ndim != 3 or tuple(planes.shape[1:]) != shape:
-            raise ValueError("%s must be uint8[n,%d,%d], got shape %r" % ((what,) + shape + (planes.shape,)))
-        return planes
-
     def mb_train_u8(self, planes):
         """Depress the cells that fire for each of uint8[n,h,w] planes: one launch for all of them, in no order."""
-        planes = self._mb_planes(planes, "planes")
-        self._check(self._lib.dv_mb_train_u8(self._ctx, N.u8ptr(planes), planes.shape[0]), "dv_mb_train_u8")
+        self._ov_train_u8("mushroom", planes)
 
     def mb_train_from_poses(self, x, y, angle, want_views=True):
         """train_from_path for the mushroom-body plug-in on the device: sense the poses, train on their compared plane; returns
         familiar_scenes (uint8[n,h,w,3]) when want_views."""
-        x, y, angle = self._pose_arrays(x, y, angle)
-        h, w = self.sensor_shape
-        views = np.empty((len(x), h, w, 3), dtype=np.uint8) if want_views else None
-        self._check_sense(self._lib.dv_mb_train_from_poses(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), len(x),
-                                                           N.u8ptr(views) if want_views else None), "dv_mb_train_from_poses")
-        return views
+        return self._ov_train_from_poses("mushroom", x, y, angle, want_views)
 
     def mb_score_u8(self, planes, out=None):
         """familiarity = -(firing cells whose weight is intact) of each of uint8[n,h,w] planes (or one uint8[h,w]) -> float64[n]."""
-        planes = self._mb_planes(planes, "planes")
-        if out is None:
-            out = np.empty(planes.shape[0], dtype=np.float64)
-        assert out.dtype == np.float64 and out.flags.c_contiguous and out.size == planes.shape[0]
-        self._check(self._lib.dv_mb_score_u8(self._ctx, N.u8ptr(planes), planes.shape[0], N.f64ptr(out)), "dv_mb_score_u8")
-        return out
+        return self._ov_score_u8("mushroom", planes, out)
 
     def mb_activity_u8(self, planes):
         """Which cells each of uint8[n,h,w] planes excites -> (fired uint8[n, n_kc], threshold int32[n]: the least activity that fires)."""
-        planes = self._mb_planes(planes, "planes")
+        planes = self._ov_planes("mushroom", planes)
         fired = np.empty((planes.shape[0], self.mb_info()["n_kc"]), dtype=np.uint8)
         thr = np.empty(planes.shape[0], dtype=np.int32)
         self._check(self._lib.dv_mb_activity_u8(self._ctx, N.u8ptr(planes), planes.shape[0], N.u8ptr(fired), thr.ctypes.data_as(N._i32p)),
@@ -943,45 +969,17 @@ class FamiliarityEngine(object):
 
     def mb_sense_step(self, x, y, angles, out_fam=None):
         """One agent step: sense the heading patches at (x, y), score them, first maximum -> (best_idex, angle_familiarity)."""
-        angles = np.ascontiguousarray(angles, dtype=np.float64).reshape(-1)
-        if out_fam is None:
-            out_fam = np.empty(len(angles), dtype=np.float64)
-        assert out_fam.dtype == np.float64 and out_fam.flags.c_contiguous and out_fam.size == len(angles)
-        best = ctypes.c_int32(-1)
-        self._check_sense(self._lib.dv_mb_sense_step(self._ctx, float(x), float(y), N.f64ptr(angles), len(angles), N.f64ptr(out_fam),
-                                                     ctypes.byref(best)), "dv_mb_sense_step")
-        return int(best.value), out_fam
+        return self._ov_sense_step("mushroom", x, y, angles, out_fam)
 
     def mb_step_batch_u8(self, planes):
         """An ensemble's step on uploaded patches: uint8[n, A, h, w] planes, member i's A headings in row i -> InfomaxBatchResults (every
         member's familiarities and first maximum from one device call; the flags are 0)."""
-        planes = N.as_u8(planes, "planes")
-        if planes.ndim != 4 or planes.shape[0] < 1 or planes.shape[1] < 1:
-            raise ValueError("planes must be uint8[n,A,h,w] with n, A >= 1, got shape %r" % (planes.shape,))
-        n, A = planes.shape[:2]
-        flat = self._mb_planes(planes.reshape((n * A,) + planes.shape[2:]), "planes")
-        fam = np.empty((n, A), dtype=np.float64)
-        best = np.full(n, -1, dtype=np.int32)
-        self._check(self._lib.dv_batch_mb_step_u8(self._ctx, N.u8ptr(flat), n, A, N.f64ptr(fam), best.ctypes.data_as(N._i32p)),
-                    "dv_batch_mb_step_u8")
-        return InfomaxBatchResults(fam, best, np.zeros(n, dtype=np.uint32))
+        return self._ov_step_batch_u8("mushroom", planes)
 
     def mb_sense_step_batch(self, x, y, angles):
         """An ensemble's step: member i at (x[i], y[i]) looking along angles[i][0..A) -> InfomaxBatchResults.  One enqueue and one wait
         for all members; a member whose footprint leaves the landscape is flagged (flags & 16, best_idex -1), the others are scored."""
-        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
-        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
-        angles = np.ascontiguousarray(angles, dtype=np.float64)
-        if angles.ndim != 2 or len(x) != len(y) or angles.shape[0] != len(x) or angles.shape[0] < 1 or angles.shape[1] < 1:
-            raise ValueError("x[N], y[N] and angles[N, A] expected (N, A >= 1), got shapes %r, %r and %r" % (x.shape, y.shape, angles.shape))
-        n, A = angles.shape
-        fam = np.empty((n, A), dtype=np.float64)
-        best = np.full(n, -1, dtype=np.int32)
-        flags = np.zeros(n, dtype=np.uint32)
-        self._check(self._lib.dv_batch_mb_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, N.f64ptr(fam),
-                                                     best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)),
-                    "dv_batch_mb_sense_step")
-        return InfomaxBatchResults(fam, best, flags)
+        return self._ov_sense_step_batch("mushroom", x, y, angles)
 
     def mb_info(self):
         k, n, c, act = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)

@@ -4,7 +4,7 @@ Reference: navsim/util.pyx:10-25 (`sads_familiarity(chem_weight)` -> `internal(s
 """
 import numpy as np
 
-from .engine import FamiliarityEngine
+from .engine import FamiliarityEngine, one_value_prefix
 
 
 def sads_familiarity(chem_weight=0.0, device=0, exact=False, devices=None):
@@ -161,6 +161,59 @@ def reject_mushroom(model, what):
                              "navsim_amd.MushroomEnsemble)" % what)
 
 
+def _one_value_familiarity(metric, channel, device, begin, **extras):
+    """Stage 2 of a model that keeps no library (infomax_familiarity, mushroom_familiarity): `begin(engine, h, w)` makes a fresh model
+    of h x w views; the engine's <prefix>_train_u8 / <prefix>_score_u8 are the ones of `metric`.  `extras` become attributes of the product."""
+    prefix = one_value_prefix(metric)
+
+    def plane(a, lead):
+        a = np.asarray(a)
+        if a.ndim == lead + 3:
+            a = a[..., channel]
+        if a.ndim != lead + 2:
+            raise ValueError("scene array has shape %r" % (a.shape,))
+        return np.ascontiguousarray(a)
+
+    def bind(engine, scenes=None):
+        score_u8 = getattr(engine, prefix + "score_u8")
+
+        def func(scene, fambuf):
+            if not (isinstance(fambuf, np.ndarray) and fambuf.dtype == np.float64):
+                raise ValueError("Buffer dtype mismatch for fambuf, expected 'double'")
+            fambuf[...] = score_u8(plane(scene, 0))[0]
+
+        func.max_familiarity = 0.0
+        func.engine = engine
+        func.metric = metric
+        func.channel = channel
+        return func
+
+    def internal(scenes):
+        scenes = np.asarray(scenes)
+        if scenes.dtype != np.uint8:
+            raise ValueError("Buffer dtype mismatch, expected 'uint8_t' but got '%s'" % scenes.dtype)
+        planes = plane(scenes, 1)
+        engine = FamiliarityEngine(device=device)
+        try:
+            begin(engine, planes.shape[1], planes.shape[2])
+            getattr(engine, prefix + "train_u8")(planes)
+        except Exception:
+            engine.close()
+            raise
+        return bind(engine)
+
+    # hooks for navsim_amd.NavBySceneFamiliarity (landscape, sensor model and training on the GPU: see sads_familiarity)
+    internal.__name__ = internal.__qualname__ = "%s_familiarity_internal" % metric
+    internal.make_engine = lambda: FamiliarityEngine(device=device)
+    internal.from_engine = bind
+    internal.begin = begin
+    internal.metric = metric
+    internal.channel = channel
+    for name, value in extras.items():
+        setattr(internal, name, value)
+    return internal
+
+
 def infomax_initial_weights(n_hidden, n_pixels, seed=0):
     """The Infomax model's initial W, float64[n_hidden, n_pixels], drawn on the host: standard normal from
     np.random.default_rng(seed), then every row has its mean subtracted and is divided by its standard deviation (ddof=0)."""
@@ -201,53 +254,12 @@ def infomax_familiarity(channel=2, learning_rate=0.01, seed=0, n_hidden=None, de
     if n_hidden is not None and not (isinstance(n_hidden, (int, np.integer)) and n_hidden >= 1):
         raise ValueError("n_hidden must be a positive integer or None, got %r" % (n_hidden,))
 
-    def plane(a, lead):
-        a = np.asarray(a)
-        if a.ndim == lead + 3:
-            a = a[..., channel]
-        if a.ndim != lead + 2:
-            raise ValueError("scene array has shape %r" % (a.shape,))
-        return np.ascontiguousarray(a)
-
     def begin(engine, h, w):
         """A fresh model of h x w views on `engine` (the agent calls this before it trains from poses)."""
         n = int(h) * int(w)
         engine.infomax_begin(h, w, infomax_initial_weights(n if n_hidden is None else n_hidden, n, seed), channel, learning_rate)
 
-    def bind(engine, scenes=None):
-        def func(scene, fambuf):
-            if not (isinstance(fambuf, np.ndarray) and fambuf.dtype == np.float64):
-                raise ValueError("Buffer dtype mismatch for fambuf, expected 'double'")
-            fambuf[...] = engine.infomax_score_u8(plane(scene, 0))[0]
-
-        func.max_familiarity = 0.0
-        func.engine = engine
-        func.metric = "infomax"
-        func.channel = channel
-        return func
-
-    def infomax_familiarity_internal(scenes):
-        scenes = np.asarray(scenes)
-        if scenes.dtype != np.uint8:
-            raise ValueError("Buffer dtype mismatch, expected 'uint8_t' but got '%s'" % scenes.dtype)
-        planes = plane(scenes, 1)
-        engine = FamiliarityEngine(device=device)
-        try:
-            begin(engine, planes.shape[1], planes.shape[2])
-            engine.infomax_train_u8(planes)
-        except Exception:
-            engine.close()
-            raise
-        return bind(engine)
-
-    # hooks for navsim_amd.NavBySceneFamiliarity (landscape, sensor model and training on the GPU: see sads_familiarity)
-    infomax_familiarity_internal.make_engine = lambda: FamiliarityEngine(device=device)
-    infomax_familiarity_internal.from_engine = bind
-    infomax_familiarity_internal.begin = begin
-    infomax_familiarity_internal.metric = "infomax"
-    infomax_familiarity_internal.channel = channel
-    infomax_familiarity_internal.learning_rate = learning_rate
-    return infomax_familiarity_internal
+    return _one_value_familiarity("infomax", channel, device, begin, learning_rate=learning_rate)
 
 
 def mushroom_connectivity(n_kc, n_pixels, fan_in, seed=0):
@@ -289,51 +301,8 @@ def mushroom_familiarity(channel=2, n_kc=20000, fan_in=10, sparsity=0.01, seed=0
         raise ValueError("sparsity must be a number in (0, 1], got %r" % (sparsity,))
     n_active = max(1, int(round(sparsity * n_kc)))
 
-    def plane(a, lead):
-        a = np.asarray(a)
-        if a.ndim == lead + 3:
-            a = a[..., channel]
-        if a.ndim != lead + 2:
-            raise ValueError("scene array has shape %r" % (a.shape,))
-        return np.ascontiguousarray(a)
-
     def begin(engine, h, w):
         """A fresh model of h x w views on `engine` (the agent calls this before it trains from poses)."""
         engine.mb_begin(h, w, mushroom_connectivity(n_kc, int(h) * int(w), fan_in, seed), n_active, channel)
 
-    def bind(engine, scenes=None):
-        def func(scene, fambuf):
-            if not (isinstance(fambuf, np.ndarray) and fambuf.dtype == np.float64):
-                raise ValueError("Buffer dtype mismatch for fambuf, expected 'double'")
-            fambuf[...] = engine.mb_score_u8(plane(scene, 0))[0]
-
-        func.max_familiarity = 0.0
-        func.engine = engine
-        func.metric = "mushroom"
-        func.channel = channel
-        return func
-
-    def mushroom_familiarity_internal(scenes):
-        scenes = np.asarray(scenes)
-        if scenes.dtype != np.uint8:
-            raise ValueError("Buffer dtype mismatch, expected 'uint8_t' but got '%s'" % scenes.dtype)
-        planes = plane(scenes, 1)
-        engine = FamiliarityEngine(device=device)
-        try:
-            begin(engine, planes.shape[1], planes.shape[2])
-            engine.mb_train_u8(planes)
-        except Exception:
-            engine.close()
-            raise
-        return bind(engine)
-
-    # hooks for navsim_amd.NavBySceneFamiliarity (landscape, sensor model and training on the GPU: see sads_familiarity)
-    mushroom_familiarity_internal.make_engine = lambda: FamiliarityEngine(device=device)
-    mushroom_familiarity_internal.from_engine = bind
-    mushroom_familiarity_internal.begin = begin
-    mushroom_familiarity_internal.metric = "mushroom"
-    mushroom_familiarity_internal.channel = channel
-    mushroom_familiarity_internal.n_kc = n_kc
-    mushroom_familiarity_internal.fan_in = fan_in
-    mushroom_familiarity_internal.n_active = n_active
-    return mushroom_familiarity_internal
+    return _one_value_familiarity("mushroom", channel, device, begin, n_kc=n_kc, fan_in=fan_in, n_active=n_active)

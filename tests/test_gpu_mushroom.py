@@ -380,7 +380,7 @@ def test_sense_step_across_the_view_bound(sensed):
 
 
 def test_decide_beyond_its_first_trip(sensed):
-    """k_mb_decide strides 256 threads over the headings: 300 of them, then ties planted between a first-trip and a second-trip
+    """k_mb_decide_batch (the step is an ensemble of one) strides 256 threads over the headings: 300 of them, then ties planted between a first-trip and a second-trip
     heading, inside one thread across trips, and a single maximum in the second trip."""
     agent, model = sensed
     e = agent._engine

@@ -1,5 +1,6 @@
 """Ensembles of Infomax agents, host side (no GPU): who InfomaxEnsemble and NavEnsemble refuse, the C ABI's two batch calls in the
-binding, and the margins of the patch sets the GPU tests use (tests/helpers_infomax_ensemble.py) under the NumPy restatement."""
+binding, the engine methods' shape checks (made before any device call), the symbols the two one-value models' shared engine code
+reaches, and the margins of the patch sets the GPU tests use (tests/helpers_infomax_ensemble.py) under the NumPy restatement."""
 import ctypes
 from types import SimpleNamespace
 
@@ -82,6 +83,74 @@ def test_batch_calls_are_bound_and_exported():
         assert callable(getattr(navsim_amd.FamiliarityEngine, name)), name
     # the single-agent calls are as they were
     assert len(N.PROTOTYPES["dv_infomax_sense_step"][1]) == 7 and len(N.PROTOTYPES["dv_infomax_score_u8"][1]) == 4
+
+
+class _NoDevice(object):
+    """Stands where the library does: any call through it is a test failure."""
+    def __getattr__(self, name):
+        raise AssertionError("%s reached the library" % name)
+
+
+def _engine_without_a_device(lib, shape):
+    e = navsim_amd.FamiliarityEngine.__new__(navsim_amd.FamiliarityEngine)
+    e._lib, e._ctx_raw, e._begun, e.infomax_shape, e.mb_shape, e.sensor_shape = lib, None, False, shape, shape, shape
+    return e
+
+
+def test_shape_checks_come_before_any_device_call():
+    """The Infomax twin of the mushroom-body test of this name (tests/test_mushroom_ensemble_host.py): the same bad inputs."""
+    e = _engine_without_a_device(_NoDevice(), (3, 5))
+    for planes in (np.zeros((2, 3, 5), np.uint8), np.zeros((2, 4, 5, 3), np.uint8), np.zeros((0, 4, 3, 5), np.uint8),
+                   np.zeros((2, 0, 3, 5), np.uint8), np.zeros((2, 4, 3, 5, 1), np.uint8)):
+        with pytest.raises(ValueError, match="planes must be uint8"):
+            e.infomax_step_batch_u8(planes)
+    with pytest.raises((ValueError, TypeError)):
+        e.infomax_step_batch_u8(np.zeros((2, 4, 3, 5), np.float32))
+    for x, y, ang in ((np.ones(2), np.ones(3), np.zeros((2, 4))), (np.ones(2), np.ones(2), np.zeros((3, 4))),
+                      (np.ones(2), np.ones(2), np.zeros(8)), (np.ones(2), np.ones(2), np.zeros((2, 0))),
+                      (np.ones(0), np.ones(0), np.zeros((0, 4))), (np.ones(2), np.ones(2), np.zeros((2, 2, 2)))):
+        with pytest.raises(ValueError, match=r"x\[N\], y\[N\] and angles\[N, A\] expected"):
+            e.infomax_sense_step_batch(x, y, ang)
+    # shapes that agree do reach the library
+    with pytest.raises(AssertionError, match="dv_batch_infomax_step_u8 reached the library"):
+        e.infomax_step_batch_u8(np.zeros((2, 4, 3, 5), np.uint8))
+    with pytest.raises(AssertionError, match="dv_batch_infomax_sense_step reached the library"):
+        e.infomax_sense_step_batch(np.ones(2), np.ones(2), np.zeros((2, 4)))
+
+
+class _Recorder(object):
+    """Stands where the library does: every call succeeds and is noted as (symbol, number of arguments)."""
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        def call(*args):
+            self.calls.append((name, len(args)))
+            return 0
+        return call
+
+
+@pytest.mark.parametrize("prefix,single,batch", [("infomax", "dv_infomax", "dv_batch_infomax"), ("mb", "dv_mb", "dv_batch_mb")])
+def test_each_shared_operation_reaches_its_own_models_symbol(prefix, single, batch):
+    """The two one-value models share one implementation per engine operation, driven by a table of symbol prefixes: every public
+    method must still reach the symbol its name promises, with as many arguments as the binding declares for that symbol."""
+    h, w, n, A = 3, 5, 2, 4
+    lib = _Recorder()
+    e = _engine_without_a_device(lib, (h, w))
+    views, xy = np.zeros((n, h, w), np.uint8), np.ones(n)
+    for method, args, symbol in (("train_u8", (views,), single + "_train_u8"),
+                                 ("train_from_poses", (xy, xy, xy), single + "_train_from_poses"),
+                                 ("score_u8", (views,), single + "_score_u8"),
+                                 ("sense_step", (1.0, 1.0, np.zeros(A)), single + "_sense_step"),
+                                 ("step_batch_u8", (np.zeros((n, A, h, w), np.uint8),), batch + "_step_u8"),
+                                 ("sense_step_batch", (xy, xy, np.zeros((n, A))), batch + "_sense_step")):
+        del lib.calls[:]
+        getattr(e, prefix + "_" + method)(*args)
+        assert lib.calls == [(symbol, len(N.PROTOTYPES[symbol][1]))], (method, lib.calls)
+    # ... and the accessor hands out the same model's methods
+    model = e.one_value({"infomax": "infomax", "mb": "mushroom"}[prefix])
+    for op in ("train_u8", "train_from_poses", "score_u8", "sense_step", "end"):
+        assert getattr(model, op) == getattr(e, prefix + "_" + op), op
 
 
 @pytest.mark.parametrize("n,A", HE.LAYOUTS)

@@ -645,6 +645,39 @@ int dv_mb_info(dv_ctx *ctx, int *n_kc, int *n_pixels, int *fan_in, int *n_active
                int64_t *bytes);
 int dv_mb_end(dv_ctx *ctx);
 
+/* ---- mushroom-body memory banks ---------------------------------------------- */
+/*
+ * Several memories behind ONE connectivity: the weights are uint8[n_banks][n_kc], bank b at offset b * n_kc.  A bank is a route's
+ * memory: the trials of a grid that differ in their training route share the model's connectivity, selection and launches, and each
+ * trains and scores through the n_kc bytes of its own bank.  n_banks is 1 after dv_mb_begin; the dv_mb_ and dv_batch_mb_ calls act on
+ * bank 0 and touch no other.  A bank table is int32, one entry per view (training) or per member (a step); every entry is checked
+ * against [0, n_banks) before anything of the call reaches the device: DV_ERR_INVALID names the first entry out of range, and nothing
+ * was trained, scored or uploaded.
+ *   set              n_banks >= 1 memories, all weights 1, all view counts 0 (whatever was trained before is dropped).  DV_ERR_OOM
+ *                    leaves the model as it was.  dv_mb_begin and dv_mb_end return to one bank.
+ *   train_u8 / train_from_poses   as their dv_mb_ twins, with view v depressing bank bank_of_view[v]: the views of all banks share the
+ *                    launches (training has no order, and a view writes inside its own bank only).  DV_ERR_INDEX: nothing was trained
+ *                    in any bank.
+ *   step_u8 / sense_step   as dv_batch_mb_step_u8 / dv_batch_mb_sense_step, with member i scored under bank bank_of_member[i]: one
+ *                    enqueue and one wait.
+ *   read_weights / set_weights   copy uint8[n_kc] of one bank out and in; DV_ERR_INVALID for a bank outside [0, n_banks) or a value
+ *                    other than 0 or 1.
+ *   info             n_banks, and per bank the views trained and the zero weights: views_trained and n_depressed are the caller's
+ *                    arrays of n_banks entries (ask for n_banks first); any pointer may be NULL.  One bank without a model.
+ * Every call but info returns DV_ERR_STATE without a model.
+ */
+int dv_mbank_set(dv_ctx *ctx, int n_banks);
+int dv_mbank_train_u8(dv_ctx *ctx, const uint8_t *planes, int64_t n, const int32_t *bank_of_view);
+int dv_mbank_train_from_poses(dv_ctx *ctx, const double *x, const double *y, const double *angle, int64_t n, const int32_t *bank_of_view,
+                              uint8_t *out_views);
+int dv_mbank_step_u8(dv_ctx *ctx, const uint8_t *planes, int n_agents, int n_headings, const int32_t *bank_of_member, double *angle_fam,
+                     int32_t *best_heading);
+int dv_mbank_sense_step(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
+                        const int32_t *bank_of_member, double *angle_fam, int32_t *best_heading, uint32_t *flags);
+int dv_mbank_read_weights(dv_ctx *ctx, int bank, uint8_t *out);
+int dv_mbank_set_weights(dv_ctx *ctx, int bank, const uint8_t *weights);
+int dv_mbank_info(dv_ctx *ctx, int *n_banks, int64_t *views_trained, int64_t *n_depressed);
+
 /* ---- measurement ------------------------------------------------------- */
 /* hipEvent pair on the context's stream around whatever is enqueued between the two calls. */
 int dv_timer_start(dv_ctx *ctx);

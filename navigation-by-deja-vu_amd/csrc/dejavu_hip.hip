@@ -319,10 +319,10 @@ struct dv_ctx {
     bool im_finite = true;
     // mushroom-body familiarity model (dejavu_mushroom.inl): fixed fan-in, one byte of weight per Kenyon cell; independent of the above
     unsigned short* mb_conn = nullptr;        // [fan_in][K]: input j of every cell
-    unsigned char* mb_wt = nullptr;           // [K]: 1, or 0 once depressed
+    unsigned char* mb_wt = nullptr;           // [mb_banks][K]: 1, or 0 once depressed (bank 0 is the dv_mb_* calls' memory)
     int* mb_d = nullptr;                      // novelty (or threshold) per view of a launch
     unsigned char* mb_fired = nullptr;        // [slab][K]: dv_mb_activity_u8's masks
-    long long* mb_zeros = nullptr;            // k_mb_count's answer
+    long long* mb_zeros = nullptr;            // [mb_banks]: k_mb_count's answers
     size_t mb_d_cap = 0, mb_fired_cap = 0;    // bytes
     PackedResults mb_res;                     // of a step (one member) and of the batch calls alike
     // the batch calls' buffers (dv_batch_mb_step_u8 / dv_batch_mb_sense_step): made at first use, grown when a call is larger
@@ -331,7 +331,11 @@ struct dv_ctx {
     size_t mb_bd_cap = 0, mb_berr_cap = 0;    // bytes
     std::vector<double> mb_xy;                // a step's pose, once per heading
     int mb_K = 0, mb_N = 0, mb_c = 0, mb_active = 0, mb_hh = 0, mb_ww = 0, mb_channel = 2;
-    int64_t mb_views = 0;                     // views trained on since dv_mb_begin
+    int mb_banks = 1;                         // memories that share the connectivity (dv_mbank_set; 1 after dv_mb_begin)
+    std::vector<int64_t> mb_views = std::vector<int64_t>(1, 0);   // [mb_banks]: views trained on since dv_mb_begin / dv_mbank_set
+    int* mb_bank_of = nullptr;                // a banked call's table on the device: the bank of every view, or of every member
+    size_t mb_bank_of_cap = 0;                // bytes
+    std::vector<int32_t> mb_bank_host;        // what mb_bank_of holds (empty: nothing known), so that an unchanged table is not sent again
 
     // measurement
     hipEvent_t t0 = nullptr, t1 = nullptr;

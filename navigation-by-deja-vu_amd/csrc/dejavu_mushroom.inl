@@ -22,7 +22,15 @@
 //                through HBM, and records in a word of its own whether a pixel left the landscape.  The body after the plane is k_mb's.
 //   k_mb_decide_batch  fam[a] = (double)(-d[a]) and the first maximum over a member's headings (np.argmax), one workgroup per member
 //                (an agent's own step is an ensemble of one), with the member's DV_RES_SENSE_ERROR flag
-//   k_mb_count   the number of zero weights, one workgroup
+//   k_mb_count   the number of zero weights of each memory bank, one workgroup per bank
+//
+// Memory banks (dv_mbank_*).  wt is uint8[n_banks][K], bank b at wt + b K with no padding; n_banks is 1 after dv_mb_begin, and every
+// dv_mb_* / dv_batch_mb_* call works on bank 0 through the kernels above.  k_mb_bank<kMbTrain>, k_mb_bank<kMbScore> and k_mb_pose_bank
+// are k_mb and k_mb_pose with one more word read per workgroup: the view's bank, bank_of[(col0 + blockIdx.x) / per] (per = 1 in
+// training: a bank per view; per = A in an ensemble's step: a bank per member), whose weights mb_view is handed instead of bank 0's.
+// The connectivity, the selection and the LDS plane are the same.  Training views of many banks in one launch is safe for the reason one
+// route is: every writer of a byte stores 0, and a workgroup writes inside its own bank only, so no order between views or banks
+// matters and nothing is atomic.  The host checks every entry of a bank table against [0, n_banks) before a call's first launch.
 namespace dv {
 
 static constexpr int kMbTrain = 0, kMbScore = 1, kMbMask = 2;
@@ -129,39 +137,77 @@ __device__ __forceinline__ void mb_view(unsigned* lds, Fill fill, int view, int 
     if (MODE == kMbMask && thr && tid == 0) thr[view] = t;
 }
 
-// src: view v's compared plane is src[v * view_stride + offset + j * px_stride], j < N (as k_im_prep).
+// The two sources of a view's plane.  Staged bytes: view v's compared plane is src[v * view_stride + offset + j * px_stride], j < N (as
+// k_im_prep).
+__device__ __forceinline__ void mb_fill_staged(unsigned char* plane, int tid, const unsigned char* __restrict__ src, long long view_stride,
+                                               int px_stride, int offset, int N) {
+    const unsigned char* p = src + (size_t)blockIdx.x * (size_t)view_stride + offset;
+    for (int j = tid; j < N; j += kMbWaves * 64) plane[j] = p[(size_t)j * px_stride];
+}
+
+// The sensor model: workgroup v senses channel `channel` of the g.sh x g.sw pixels at poses[v] into its LDS plane.  A pixel off the
+// landscape contributes 0 and the selection runs all the same (every thread reaches every barrier); err[v] is written by this workgroup
+// alone, 1 when any of its pixels was off, so the caller clears nothing beforehand.
+__device__ __forceinline__ void mb_fill_pose(unsigned char* plane, int tid, const unsigned char* __restrict__ land, const Pose* __restrict__ poses,
+                                             const SensorCfg& g, const unsigned char* __restrict__ lut, int channel, int N, int* __restrict__ err) {
+    const Pose p = poses[blockIdx.x];
+    int off = 0;
+    for (int j = tid; j < N; j += kMbWaves * 64) {
+        unsigned H, S, V;
+        if (!sense_pixel(land, g, p, lut, j / g.sw, j % g.sw, H, S, V)) { off = 1; H = S = V = 0; }
+        plane[j] = (unsigned char)(channel == 0 ? H : channel == 1 ? S : V);
+    }
+    off = __syncthreads_or(off);
+    if (tid == 0) err[blockIdx.x] = off;
+}
+
+// The weights of workgroup blockIdx.x's bank (the host has checked the table: 0 <= bank < n_banks).
+__device__ __forceinline__ unsigned char* mb_bank(unsigned char* __restrict__ wt, int K, const int* __restrict__ bank_of, unsigned col0, unsigned per) {
+    return wt + (size_t)bank_of[(col0 + blockIdx.x) / per] * (size_t)K;
+}
+
 template <int MODE>
 __global__ __launch_bounds__(kMbWaves * 64) void k_mb(const unsigned char* __restrict__ src, long long view_stride, int px_stride, int offset, int N,
                                                       const unsigned short* __restrict__ conn, int K, int c, int n_active,
                                                       unsigned char* __restrict__ wt, int* __restrict__ d, unsigned char* __restrict__ fired,
                                                       int* __restrict__ thr) {
     extern __shared__ unsigned mb_lds[];
-    mb_view<MODE>(mb_lds, [&](unsigned char* plane, int tid) {
-        const unsigned char* p = src + (size_t)blockIdx.x * (size_t)view_stride + offset;
-        for (int j = tid; j < N; j += kMbWaves * 64) plane[j] = p[(size_t)j * px_stride];
-    }, (int)blockIdx.x, N, conn, K, c, n_active, wt, d, fired, thr);
+    mb_view<MODE>(mb_lds, [&](unsigned char* plane, int tid) { mb_fill_staged(plane, tid, src, view_stride, px_stride, offset, N); },
+                  (int)blockIdx.x, N, conn, K, c, n_active, wt, d, fired, thr);
 }
 
-// kMbScore with the sensor model as the source: workgroup v senses channel `channel` of the g.sh x g.sw pixels at poses[v] into its LDS
-// plane.  A pixel off the landscape contributes 0 and the selection runs all the same (every thread reaches every barrier); err[v] is
-// written by this workgroup alone, 1 when any of its pixels was off, so the caller clears nothing beforehand.
+// kMbScore with the sensor model as the source.
 __global__ __launch_bounds__(kMbWaves * 64) void k_mb_pose(const unsigned char* __restrict__ land, const Pose* __restrict__ poses, SensorCfg g,
                                                            const unsigned char* __restrict__ lut, int channel,
                                                            const unsigned short* __restrict__ conn, int K, int c, int n_active,
                                                            unsigned char* __restrict__ wt, int* __restrict__ d, int* __restrict__ err) {
     extern __shared__ unsigned mb_lds[];
     const int N = g.sh * g.sw;
-    mb_view<kMbScore>(mb_lds, [&](unsigned char* plane, int tid) {
-        const Pose p = poses[blockIdx.x];
-        int off = 0;
-        for (int j = tid; j < N; j += kMbWaves * 64) {
-            unsigned H, S, V;
-            if (!sense_pixel(land, g, p, lut, j / g.sw, j % g.sw, H, S, V)) { off = 1; H = S = V = 0; }
-            plane[j] = (unsigned char)(channel == 0 ? H : channel == 1 ? S : V);
-        }
-        off = __syncthreads_or(off);
-        if (tid == 0) err[blockIdx.x] = off;
-    }, (int)blockIdx.x, N, conn, K, c, n_active, wt, d, nullptr, nullptr);
+    mb_view<kMbScore>(mb_lds, [&](unsigned char* plane, int tid) { mb_fill_pose(plane, tid, land, poses, g, lut, channel, N, err); },
+                      (int)blockIdx.x, N, conn, K, c, n_active, wt, d, nullptr, nullptr);
+}
+
+// The banked forms (MODE kMbTrain or kMbScore): `wt` is bank 0's; src, poses, d and err begin at this launch's first column, which is
+// column col0 of the call, and the bank table is the whole call's.
+template <int MODE>
+__global__ __launch_bounds__(kMbWaves * 64) void k_mb_bank(const unsigned char* __restrict__ src, long long view_stride, int px_stride, int offset,
+                                                           int N, const unsigned short* __restrict__ conn, int K, int c, int n_active,
+                                                           unsigned char* __restrict__ wt, int* __restrict__ d, const int* __restrict__ bank_of,
+                                                           unsigned col0, unsigned per) {
+    extern __shared__ unsigned mb_lds[];
+    mb_view<MODE>(mb_lds, [&](unsigned char* plane, int tid) { mb_fill_staged(plane, tid, src, view_stride, px_stride, offset, N); },
+                  (int)blockIdx.x, N, conn, K, c, n_active, mb_bank(wt, K, bank_of, col0, per), d, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(kMbWaves * 64) void k_mb_pose_bank(const unsigned char* __restrict__ land, const Pose* __restrict__ poses, SensorCfg g,
+                                                                const unsigned char* __restrict__ lut, int channel,
+                                                                const unsigned short* __restrict__ conn, int K, int c, int n_active,
+                                                                unsigned char* __restrict__ wt, int* __restrict__ d, int* __restrict__ err,
+                                                                const int* __restrict__ bank_of, unsigned col0, unsigned per) {
+    extern __shared__ unsigned mb_lds[];
+    const int N = g.sh * g.sw;
+    mb_view<kMbScore>(mb_lds, [&](unsigned char* plane, int tid) { mb_fill_pose(plane, tid, land, poses, g, lut, channel, N, err); },
+                      (int)blockIdx.x, N, conn, K, c, n_active, mb_bank(wt, K, bank_of, col0, per), d, nullptr, nullptr);
 }
 
 // One workgroup per member i of A columns: fam[i][a] = (double)(-d[i A + a]); best[i] = the member's first maximum (the larger value,
@@ -195,9 +241,11 @@ __global__ __launch_bounds__(256) void k_mb_decide_batch(const int* __restrict__
     }
 }
 
+// zeros[b] = the zero weights of bank b = blockIdx.x (wt: [banks][K]).
 __global__ __launch_bounds__(256) void k_mb_count(const unsigned char* __restrict__ wt, int K, long long* __restrict__ zeros) {
     __shared__ int red[256];
     const int tid = (int)threadIdx.x;
+    wt += (size_t)blockIdx.x * (size_t)K;
     int s = 0;
     for (int k = tid; k < K; k += 256) s += wt[k] == 0 ? 1 : 0;
     red[tid] = s;
@@ -206,7 +254,7 @@ __global__ __launch_bounds__(256) void k_mb_count(const unsigned char* __restric
         if (tid < st) red[tid] += red[tid + st];
         __syncthreads();
     }
-    if (tid == 0) *zeros = (long long)red[0];
+    if (tid == 0) zeros[blockIdx.x] = (long long)red[0];
 }
 
 }  // namespace dv
@@ -218,10 +266,12 @@ static constexpr size_t kMbStageBytes = 64u << 20;           // ... and the byte
 
 static void mb_free(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-    F(c->mb_conn); F(c->mb_wt); F(c->mb_d); F(c->mb_fired); F(c->mb_zeros); F(c->mb_bd); F(c->mb_berr); F(c->mb_res.dev);
-    c->mb_d_cap = c->mb_fired_cap = c->mb_bd_cap = c->mb_berr_cap = c->mb_res.cap = 0;
+    F(c->mb_conn); F(c->mb_wt); F(c->mb_d); F(c->mb_fired); F(c->mb_zeros); F(c->mb_bd); F(c->mb_berr); F(c->mb_bank_of); F(c->mb_res.dev);
+    c->mb_d_cap = c->mb_fired_cap = c->mb_bd_cap = c->mb_berr_cap = c->mb_bank_of_cap = c->mb_res.cap = 0;
     c->mb_K = c->mb_N = c->mb_c = c->mb_active = c->mb_hh = c->mb_ww = 0;
-    c->mb_views = 0;
+    c->mb_banks = 1;
+    c->mb_views.assign(1, 0);
+    c->mb_bank_host.clear();
 }
 
 static int mb_need(dv_ctx* c, const char* who) {
@@ -248,6 +298,45 @@ static int mb_launch(dv_ctx* c, const unsigned char* d_src, long long view_strid
     hipLaunchKernelGGL((k_mb<MODE>), dim3((unsigned)n), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, d_src, view_stride, px_stride, offset, c->mb_N,
                        c->mb_conn, c->mb_K, c->mb_c, c->mb_active, c->mb_wt, d, fired, thr);
     HIP_TRY(c, hipGetLastError());
+    return DV_OK;
+}
+
+// The banked launch: its view v works through bank d_bank_of[(col0 + v) / per].  Training hands the table in from the launch's own
+// first view on (col0 = 0, per = 1: a bank per view); an ensemble's step hands in the whole table, the launch's first column and A.
+template <int MODE>
+static int mb_launch_bank(dv_ctx* c, const unsigned char* d_src, long long view_stride, int px_stride, int offset, int n, int* d, const int* d_bank_of,
+                          long long col0, int per) {
+    hipLaunchKernelGGL((k_mb_bank<MODE>), dim3((unsigned)n), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, d_src, view_stride, px_stride, offset,
+                       c->mb_N, c->mb_conn, c->mb_K, c->mb_c, c->mb_active, c->mb_wt, d, d_bank_of, (unsigned)col0, (unsigned)per);
+    HIP_TRY(c, hipGetLastError());
+    return DV_OK;
+}
+
+// n views were trained: all into bank 0 (bank_of == nullptr), or view v into bank_of[v].
+static void mb_count_views(dv_ctx* c, int64_t n, const int32_t* bank_of) {
+    if (!bank_of) c->mb_views[0] += n;
+    else for (int64_t v = 0; v < n; ++v) c->mb_views[(size_t)bank_of[v]] += 1;
+}
+
+// A banked call's table, checked entry by entry before anything of the call reaches the device ...
+static int mbank_check(dv_ctx* c, const char* who, const char* what, const int32_t* bank_of, int64_t n) {
+    if (!bank_of) return fail(c, DV_ERR_INVALID, "%s: %s is NULL", who, what);
+    for (int64_t i = 0; i < n; ++i)
+        if (bank_of[i] < 0 || bank_of[i] >= c->mb_banks)
+            return fail(c, DV_ERR_INVALID, "%s: %s[%lld] = %d outside [0, n_banks = %d)", who, what, (long long)i, (int)bank_of[i], c->mb_banks);
+    return DV_OK;
+}
+
+// ... and then enqueued for the device (`bank_of` is borrowed: every caller waits for the stream before it returns).  The host keeps
+// what the device's table holds: an ensemble's banks change only when a member stops, so most steps find it there and upload nothing.
+static int mbank_upload(dv_ctx* c, const int32_t* bank_of, int64_t n) {
+    if (n < 1) return DV_OK;
+    if ((int64_t)c->mb_bank_host.size() == n && std::equal(bank_of, bank_of + n, c->mb_bank_host.begin())) return DV_OK;
+    c->mb_bank_host.clear();
+    int rc = grow_buffer(c, c->mb_bank_of, c->mb_bank_of_cap, (size_t)n * sizeof(int));
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->mb_bank_of, bank_of, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    c->mb_bank_host.assign(bank_of, bank_of + n);
     return DV_OK;
 }
 
@@ -293,6 +382,9 @@ extern "C" int dv_mb_begin(dv_ctx* c, int h, int w, int channel, int n_kc, int f
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb<kMbScore>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb<kMbMask>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_pose, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_bank<kMbTrain>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_bank<kMbScore>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_pose_bank, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = hipMemcpyAsync(c->mb_conn, ct.data(), ct.size() * sizeof(unsigned short), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->mb_wt, 1, K, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);           // `ct` is this call's
@@ -304,12 +396,14 @@ extern "C" int dv_mb_begin(dv_ctx* c, int h, int w, int channel, int n_kc, int f
     return DV_OK;
 }
 
-extern "C" int dv_mb_train_u8(dv_ctx* c, const uint8_t* planes, int64_t n) {
-    if (!c) return DV_ERR_INVALID;
-    int rc = mb_need(c, "dv_mb_train_u8");
+// Train on n uploaded planes; bank_of == nullptr: all into bank 0 (dv_mb_train_u8), else view v into bank bank_of[v].
+static int mb_train_u8(dv_ctx* c, const char* who, const uint8_t* planes, int64_t n, const int32_t* bank_of) {
+    int rc = mb_need(c, who);
     if (rc) return rc;
-    if (!planes || n < 0) return fail(c, DV_ERR_INVALID, "dv_mb_train_u8: planes is NULL or n < 0");
+    if (!planes || n < 0) return fail(c, DV_ERR_INVALID, "%s: planes is NULL or n < 0", who);
+    if (bank_of) { rc = mbank_check(c, who, "bank_of_view", bank_of, n); if (rc) return rc; }
     HIP_TRY(c, hipSetDevice(c->device));
+    if (bank_of) { rc = mbank_upload(c, bank_of, n); if (rc) return rc; }
     const size_t N = (size_t)c->mb_N;
     int64_t slab = mb_slab(N);
     if (slab > n) slab = n;
@@ -317,22 +411,31 @@ extern "C" int dv_mb_train_u8(dv_ctx* c, const uint8_t* planes, int64_t n) {
     for (int64_t v0 = 0; v0 < n; v0 += slab) {
         const int64_t ns = n - v0 < slab ? n - v0 : slab;
         HIP_TRY(c, hipMemcpyAsync(c->d_sense, planes + (size_t)v0 * N, (size_t)ns * N, hipMemcpyHostToDevice, c->stream));
-        rc = mb_launch<kMbTrain>(c, c->d_sense, (long long)N, 1, 0, (int)ns, nullptr, nullptr, nullptr);
+        rc = bank_of ? mb_launch_bank<kMbTrain>(c, c->d_sense, (long long)N, 1, 0, (int)ns, nullptr, c->mb_bank_of + v0, 0, 1)
+                     : mb_launch<kMbTrain>(c, c->d_sense, (long long)N, 1, 0, (int)ns, nullptr, nullptr, nullptr);
         if (rc) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->stream));          // the slab is reused, `planes` is borrowed
     }
-    c->mb_views += n;
+    mb_count_views(c, n, bank_of);
     return DV_OK;
 }
 
-extern "C" int dv_mb_train_from_poses(dv_ctx* c, const double* x, const double* y, const double* angle, int64_t n, uint8_t* out_views) {
+extern "C" int dv_mb_train_u8(dv_ctx* c, const uint8_t* planes, int64_t n) {
     if (!c) return DV_ERR_INVALID;
-    int rc = mb_need(c, "dv_mb_train_from_poses");
+    return mb_train_u8(c, "dv_mb_train_u8", planes, n, nullptr);
+}
+
+// Sense n poses and train on their compared plane; bank_of as mb_train_u8's.
+static int mb_train_from_poses(dv_ctx* c, const char* who, const double* x, const double* y, const double* angle, int64_t n, const int32_t* bank_of,
+                               uint8_t* out_views) {
+    int rc = mb_need(c, who);
     if (rc) return rc;
-    if (!x || !y || !angle || n < 1 || n > 0x7fffffff) return fail(c, DV_ERR_INVALID, "dv_mb_train_from_poses: bad arguments");
-    rc = sensor_fits(c, "dv_mb_train_from_poses", c->mb_hh, c->mb_ww);
+    if (!x || !y || !angle || n < 1 || n > 0x7fffffff) return fail(c, DV_ERR_INVALID, "%s: bad arguments", who);
+    rc = sensor_fits(c, who, c->mb_hh, c->mb_ww);
     if (rc) return rc;
+    if (bank_of) { rc = mbank_check(c, who, "bank_of_view", bank_of, n); if (rc) return rc; }
     HIP_TRY(c, hipSetDevice(c->device));
+    if (bank_of) { rc = mbank_upload(c, bank_of, n); if (rc) return rc; }
     const size_t bytes = (size_t)n * (size_t)c->mb_N * 3;
     rc = ensure_sense_buffer(c, bytes);
     if (rc) return rc;
@@ -344,12 +447,19 @@ extern "C" int dv_mb_train_from_poses(dv_ctx* c, const double* x, const double* 
     const long long stride = 3ll * c->mb_N;
     for (int64_t v0 = 0; v0 < n; v0 += kMbSlabViews) {
         const int64_t ns = n - v0 < kMbSlabViews ? n - v0 : kMbSlabViews;
-        rc = mb_launch<kMbTrain>(c, c->d_sense + (size_t)v0 * (size_t)stride, stride, 3, c->mb_channel, (int)ns, nullptr, nullptr, nullptr);
+        const unsigned char* src = c->d_sense + (size_t)v0 * (size_t)stride;
+        rc = bank_of ? mb_launch_bank<kMbTrain>(c, src, stride, 3, c->mb_channel, (int)ns, nullptr, c->mb_bank_of + v0, 0, 1)
+                     : mb_launch<kMbTrain>(c, src, stride, 3, c->mb_channel, (int)ns, nullptr, nullptr, nullptr);
         if (rc) return rc;
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->mb_views += n;
+    mb_count_views(c, n, bank_of);
     return DV_OK;
+}
+
+extern "C" int dv_mb_train_from_poses(dv_ctx* c, const double* x, const double* y, const double* angle, int64_t n, uint8_t* out_views) {
+    if (!c) return DV_ERR_INVALID;
+    return mb_train_from_poses(c, "dv_mb_train_from_poses", x, y, angle, n, nullptr, out_views);
 }
 
 extern "C" int dv_mb_score_u8(dv_ctx* c, const uint8_t* planes, int n, double* familiarity) {
@@ -439,10 +549,13 @@ extern "C" int dv_mb_sense_step(dv_ctx* c, double x, double y, const double* ang
 // planes != nullptr: uploaded uint8[n_agents][A][h][w], scored by k_mb<kMbScore> in launches of mb_slab(N) columns (the view bound and
 // the byte bound of dv_mb_score_u8); else the poses (x[i], y[i], angles[i][a]) go to k_mb_pose, kMbSlabViews columns a launch.  The
 // launches follow one another on the stream; the host waits once, for the one copy of the packed results.
+// bank_of == nullptr: every member scores under bank 0 (the dv_batch_mb_* calls); else member i under bank bank_of[i], through the
+// banked kernels -- the same enqueue, with the members' table uploaded ahead of the launches.
 static int mb_batch(dv_ctx* c, const char* who, const uint8_t* planes, const double* x, const double* y, const double* angles, int n_agents, int A,
-                    double* angle_fam, int32_t* best_heading, uint32_t* flags) {
+                    const int32_t* bank_of, double* angle_fam, int32_t* best_heading, uint32_t* flags) {
     const long long C = (long long)n_agents * A;
     if (C > 0x7fffffffll) return fail(c, DV_ERR_INVALID, "%s: %d agents x %d headings are too many columns", who, n_agents, A);
+    if (bank_of) { const int rb = mbank_check(c, who, "bank_of_member", bank_of, n_agents); if (rb) return rb; }
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t N = (size_t)c->mb_N;
     long long slab = planes ? (long long)mb_slab(N) : (long long)kMbSlabViews;
@@ -452,6 +565,7 @@ static int mb_batch(dv_ctx* c, const char* who, const uint8_t* planes, const dou
     if (!rc) rc = packed_device(c, c->mb_res, C, n_agents, d_fam, d_best, d_flags);
     if (!rc && !planes) rc = grow_buffer(c, c->mb_berr, c->mb_berr_cap, (size_t)C * sizeof(int));
     if (!rc && planes) rc = ensure_sense_buffer(c, (size_t)slab * N);
+    if (!rc && bank_of) rc = mbank_upload(c, bank_of, n_agents);
     if (rc) return rc;
     if (!planes) {
         rc = upload_member_poses(c, x, y, angles, n_agents, A);
@@ -461,8 +575,14 @@ static int mb_batch(dv_ctx* c, const char* who, const uint8_t* planes, const dou
         const int nc = (int)(C - c0 < slab ? C - c0 : slab);
         if (planes) {
             HIP_TRY(c, hipMemcpyAsync(c->d_sense, planes + (size_t)c0 * N, (size_t)nc * N, hipMemcpyHostToDevice, c->stream));
-            rc = mb_launch<kMbScore>(c, c->d_sense, (long long)N, 1, 0, nc, c->mb_bd + c0, nullptr, nullptr);
+            rc = bank_of ? mb_launch_bank<kMbScore>(c, c->d_sense, (long long)N, 1, 0, nc, c->mb_bd + c0, c->mb_bank_of, c0, A)
+                         : mb_launch<kMbScore>(c, c->d_sense, (long long)N, 1, 0, nc, c->mb_bd + c0, nullptr, nullptr);
             if (rc) return rc;
+        } else if (bank_of) {
+            hipLaunchKernelGGL(k_mb_pose_bank, dim3((unsigned)nc), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, c->d_land, c->d_poses + c0, c->sensor,
+                               c->d_lut, c->mb_channel, c->mb_conn, c->mb_K, c->mb_c, c->mb_active, c->mb_wt, c->mb_bd + c0, c->mb_berr + c0,
+                               (const int*)c->mb_bank_of, (unsigned)c0, (unsigned)A);
+            HIP_TRY(c, hipGetLastError());
         } else {
             hipLaunchKernelGGL(k_mb_pose, dim3((unsigned)nc), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, c->d_land, c->d_poses + c0, c->sensor,
                                c->d_lut, c->mb_channel, c->mb_conn, c->mb_K, c->mb_c, c->mb_active, c->mb_wt, c->mb_bd + c0, c->mb_berr + c0);
@@ -485,7 +605,7 @@ extern "C" int dv_batch_mb_step_u8(dv_ctx* c, const uint8_t* planes, int n_agent
     if (rc) return rc;
     if (!planes || !angle_fam || !best_heading || n_agents < 1 || n_headings < 1)
         return fail(c, DV_ERR_INVALID, "dv_batch_mb_step_u8: NULL argument, n_agents < 1 or n_headings < 1");
-    return mb_batch(c, "dv_batch_mb_step_u8", planes, nullptr, nullptr, nullptr, n_agents, n_headings, angle_fam, best_heading, nullptr);
+    return mb_batch(c, "dv_batch_mb_step_u8", planes, nullptr, nullptr, nullptr, n_agents, n_headings, nullptr, angle_fam, best_heading, nullptr);
 }
 
 extern "C" int dv_batch_mb_sense_step(dv_ctx* c, const double* x, const double* y, const double* angles, int n_agents, int n_headings,
@@ -497,7 +617,7 @@ extern "C" int dv_batch_mb_sense_step(dv_ctx* c, const double* x, const double* 
         return fail(c, DV_ERR_INVALID, "dv_batch_mb_sense_step: NULL argument, n_agents < 1 or n_headings < 1");
     rc = sensor_fits(c, "dv_batch_mb_sense_step", c->mb_hh, c->mb_ww);
     if (rc) return rc;
-    return mb_batch(c, "dv_batch_mb_sense_step", nullptr, x, y, angles, n_agents, n_headings, angle_fam, best_heading, flags);
+    return mb_batch(c, "dv_batch_mb_sense_step", nullptr, x, y, angles, n_agents, n_headings, nullptr, angle_fam, best_heading, flags);
 }
 
 extern "C" int dv_mb_read_weights(dv_ctx* c, uint8_t* out) {
@@ -531,7 +651,7 @@ extern "C" int dv_mb_info(dv_ctx* c, int* n_kc, int* n_pixels, int* fan_in, int*
     if (n_pixels) *n_pixels = c->mb_N;
     if (fan_in) *fan_in = c->mb_c;
     if (n_active) *n_active = c->mb_active;
-    if (views_trained) *views_trained = c->mb_views;
+    if (views_trained) *views_trained = c->mb_views[0];
     if (bytes) *bytes = (int64_t)c->mb_K;
     if (n_depressed) {
         *n_depressed = 0;
@@ -543,6 +663,125 @@ extern "C" int dv_mb_info(dv_ctx* c, int* n_kc, int* n_pixels, int* fan_in, int*
             HIP_TRY(c, hipMemcpyAsync(&z, c->mb_zeros, sizeof z, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             *n_depressed = (int64_t)z;
+        }
+    }
+    return DV_OK;
+}
+
+// ---- memory banks: n_banks memories behind the one connectivity (include/dejavu.h: dv_mbank_*) -------------------------------------
+extern "C" int dv_mbank_set(dv_ctx* c, int n_banks) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = mb_need(c, "dv_mbank_set");
+    if (rc) return rc;
+    if (n_banks < 1) return fail(c, DV_ERR_INVALID, "dv_mbank_set: n_banks %d < 1", n_banks);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)n_banks * (size_t)c->mb_K;
+    unsigned char* wt = nullptr;
+    long long* zeros = nullptr;
+    hipError_t e = hipMalloc((void**)&wt, bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&zeros, (size_t)n_banks * sizeof(long long));
+    if (e == hipSuccess) e = hipMemsetAsync(wt, 1, bytes, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);           // (nothing enqueued reads the old weights any more)
+    if (e != hipSuccess) {                                              // the model stays as it was
+        (void)hipGetLastError();
+        if (wt) (void)hipFree(wt);
+        if (zeros) (void)hipFree(zeros);
+        return fail(c, e == hipErrorOutOfMemory ? DV_ERR_OOM : DV_ERR_HIP, "dv_mbank_set: %d banks of %d cells: %s", n_banks, c->mb_K, hipGetErrorString(e));
+    }
+    (void)hipFree(c->mb_wt);
+    (void)hipFree(c->mb_zeros);
+    c->mb_wt = wt;
+    c->mb_zeros = zeros;
+    c->mb_banks = n_banks;
+    c->mb_views.assign((size_t)n_banks, 0);
+    return DV_OK;
+}
+
+extern "C" int dv_mbank_train_u8(dv_ctx* c, const uint8_t* planes, int64_t n, const int32_t* bank_of_view) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = mb_need(c, "dv_mbank_train_u8");
+    if (rc) return rc;
+    if (!bank_of_view) return fail(c, DV_ERR_INVALID, "dv_mbank_train_u8: bank_of_view is NULL");
+    return mb_train_u8(c, "dv_mbank_train_u8", planes, n, bank_of_view);
+}
+
+extern "C" int dv_mbank_train_from_poses(dv_ctx* c, const double* x, const double* y, const double* angle, int64_t n, const int32_t* bank_of_view,
+                                         uint8_t* out_views) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = mb_need(c, "dv_mbank_train_from_poses");
+    if (rc) return rc;
+    if (!bank_of_view) return fail(c, DV_ERR_INVALID, "dv_mbank_train_from_poses: bank_of_view is NULL");
+    return mb_train_from_poses(c, "dv_mbank_train_from_poses", x, y, angle, n, bank_of_view, out_views);
+}
+
+extern "C" int dv_mbank_step_u8(dv_ctx* c, const uint8_t* planes, int n_agents, int n_headings, const int32_t* bank_of_member, double* angle_fam,
+                                int32_t* best_heading) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = mb_need(c, "dv_mbank_step_u8");
+    if (rc) return rc;
+    if (!planes || !bank_of_member || !angle_fam || !best_heading || n_agents < 1 || n_headings < 1)
+        return fail(c, DV_ERR_INVALID, "dv_mbank_step_u8: NULL argument, n_agents < 1 or n_headings < 1");
+    return mb_batch(c, "dv_mbank_step_u8", planes, nullptr, nullptr, nullptr, n_agents, n_headings, bank_of_member, angle_fam, best_heading, nullptr);
+}
+
+extern "C" int dv_mbank_sense_step(dv_ctx* c, const double* x, const double* y, const double* angles, int n_agents, int n_headings,
+                                   const int32_t* bank_of_member, double* angle_fam, int32_t* best_heading, uint32_t* flags) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = mb_need(c, "dv_mbank_sense_step");
+    if (rc) return rc;
+    if (!x || !y || !angles || !bank_of_member || !angle_fam || !best_heading || !flags || n_agents < 1 || n_headings < 1)
+        return fail(c, DV_ERR_INVALID, "dv_mbank_sense_step: NULL argument, n_agents < 1 or n_headings < 1");
+    rc = sensor_fits(c, "dv_mbank_sense_step", c->mb_hh, c->mb_ww);
+    if (rc) return rc;
+    return mb_batch(c, "dv_mbank_sense_step", nullptr, x, y, angles, n_agents, n_headings, bank_of_member, angle_fam, best_heading, flags);
+}
+
+static int mbank_one(dv_ctx* c, const char* who, int bank) {
+    int rc = mb_need(c, who);
+    if (rc) return rc;
+    if (bank < 0 || bank >= c->mb_banks) return fail(c, DV_ERR_INVALID, "%s: bank %d outside [0, n_banks = %d)", who, bank, c->mb_banks);
+    return DV_OK;
+}
+
+extern "C" int dv_mbank_read_weights(dv_ctx* c, int bank, uint8_t* out) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = mbank_one(c, "dv_mbank_read_weights", bank);
+    if (rc) return rc;
+    if (!out) return fail(c, DV_ERR_INVALID, "dv_mbank_read_weights: out is NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(out, c->mb_wt + (size_t)bank * (size_t)c->mb_K, (size_t)c->mb_K, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DV_OK;
+}
+
+extern "C" int dv_mbank_set_weights(dv_ctx* c, int bank, const uint8_t* weights) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = mbank_one(c, "dv_mbank_set_weights", bank);
+    if (rc) return rc;
+    if (!weights) return fail(c, DV_ERR_INVALID, "dv_mbank_set_weights: weights is NULL");
+    for (int k = 0; k < c->mb_K; ++k)
+        if (weights[k] > 1) return fail(c, DV_ERR_INVALID, "dv_mbank_set_weights: weights[%d] = %d is neither 0 nor 1", k, (int)weights[k]);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(c->mb_wt + (size_t)bank * (size_t)c->mb_K, weights, (size_t)c->mb_K, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));              // `weights` is borrowed for this call only
+    return DV_OK;
+}
+
+extern "C" int dv_mbank_info(dv_ctx* c, int* n_banks, int64_t* views_trained, int64_t* n_depressed) {
+    if (!c) return DV_ERR_INVALID;
+    const size_t B = (size_t)c->mb_banks;
+    if (n_banks) *n_banks = c->mb_banks;
+    if (views_trained) for (size_t b = 0; b < B; ++b) views_trained[b] = c->mb_views[b];
+    if (n_depressed) {
+        for (size_t b = 0; b < B; ++b) n_depressed[b] = 0;
+        if (c->mb_wt) {
+            std::vector<long long> z(B);
+            HIP_TRY(c, hipSetDevice(c->device));
+            hipLaunchKernelGGL(k_mb_count, dim3((unsigned)B), dim3(256), 0, c->stream, c->mb_wt, c->mb_K, c->mb_zeros);
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipMemcpyAsync(z.data(), c->mb_zeros, B * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            for (size_t b = 0; b < B; ++b) n_depressed[b] = (int64_t)z[b];
         }
     }
     return DV_OK;

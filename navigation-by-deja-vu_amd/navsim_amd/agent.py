@@ -127,6 +127,7 @@ class NavBySceneFamiliarity(object):
     """
 
     chem_weight = None              # a NavEnsemble member's own weight (NavEnsemble.from_agent(chem_weights=...)); None: the model's
+    memory_bank = None              # a MushroomRouteEnsemble member's own memory of the shared mushroom-body model; None: the model's one
 
     def __init__(self,
                  landscape,
@@ -554,6 +555,10 @@ class NavBySceneFamiliarity(object):
             # (a step of its own runs the library's weight: only its ensemble's batches score it under its own)
             raise ValueError("this ensemble member scores under chem_weight %r, the library under %r: step it with its NavEnsemble"
                              % (self.chem_weight, getattr(self.familiarity_model, "chem_weight", None)))
+        if self.memory_bank is not None:
+            # (a step of its own scores under bank 0 of the model: only its ensemble's batches score it under its own bank)
+            raise ValueError("this ensemble member's route is kept in memory bank %d of a model it shares: step it with its "
+                             "MushroomRouteEnsemble" % self.memory_bank)
         position = self.position
         self.angle_familiarity[:] = np.nan
         assert len(self.familiar_scenes) == len(self._scene_fam)

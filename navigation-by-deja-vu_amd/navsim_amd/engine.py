@@ -944,6 +944,7 @@ class FamiliarityEngine(object):
         self._check(self._lib.dv_mb_begin(self._ctx, int(h), int(w), int(channel), conn.shape[0], conn.shape[1], int(n_active),
                                           conn.ctypes.data_as(N._i32p)), "dv_mb_begin")
         self.mb_shape = (int(h), int(w))
+        self.mb_banks = 1
 
     def mb_train_u8(self, planes):
         """Depress the cells that fire for each of uint8[n,h,w] planes: one launch for all of them, in no order."""
@@ -1005,3 +1006,109 @@ class FamiliarityEngine(object):
     def mb_end(self):
         self._check(self._lib.dv_mb_end(self._ctx), "dv_mb_end")
         self.mb_shape = None
+        self.mb_banks = 1
+
+    # -- memory banks of the mushroom-body model: several memories behind one connectivity (include/dejavu.h: dv_mbank_*) ---------
+    mb_banks = 1                 # memories of the model (mbank_set; 1 after mb_begin)
+
+    def _bank_table(self, table, n, what):
+        """`table` as int32[n] with every entry in [0, mb_banks), or ValueError naming `what`: checked before any library call."""
+        arr = np.asarray(table)
+        if arr.dtype.kind not in "iu":
+            raise ValueError("%s must hold integers (a bank per entry), got dtype %s" % (what, arr.dtype))
+        if arr.shape != (n,):
+            raise ValueError("%s must have shape (%d,), got %r" % (what, n, arr.shape))
+        if n and (arr.min() < 0 or arr.max() >= self.mb_banks):
+            bad = np.flatnonzero((arr < 0) | (arr >= self.mb_banks))
+            raise ValueError("%s[%d] = %d outside [0, n_banks = %d)" % (what, bad[0], arr[bad[0]], self.mb_banks))
+        return np.ascontiguousarray(arr, dtype=np.int32)
+
+    def _bank_index(self, bank):
+        if isinstance(bank, bool) or not isinstance(bank, (int, np.integer)) or not 0 <= bank < self.mb_banks:
+            raise ValueError("bank must be an integer in [0, n_banks = %d), got %r" % (self.mb_banks, bank))
+        return int(bank)
+
+    def mbank_set(self, n_banks):
+        """n_banks memories behind the model's connectivity, all weights 1 (what was trained is dropped).  The mb_* calls keep acting
+        on bank 0; mb_begin and mb_end return to one bank."""
+        if isinstance(n_banks, bool) or not isinstance(n_banks, (int, np.integer)) or n_banks < 1:
+            raise ValueError("n_banks must be an integer >= 1, got %r" % (n_banks,))
+        self._check(self._lib.dv_mbank_set(self._ctx, int(n_banks)), "dv_mbank_set")
+        self.mb_banks = int(n_banks)
+
+    def mbank_train_u8(self, planes, bank_of_view):
+        """mb_train_u8 with view v depressing bank bank_of_view[v]: the views of all banks in the same launches."""
+        planes = self._ov_planes("mushroom", planes)
+        banks = self._bank_table(bank_of_view, planes.shape[0], "bank_of_view")
+        self._check(self._lib.dv_mbank_train_u8(self._ctx, N.u8ptr(planes), planes.shape[0], banks.ctypes.data_as(N._i32p)), "dv_mbank_train_u8")
+
+    def mbank_train_from_poses(self, x, y, angle, bank_of_view, want_views=True):
+        """mb_train_from_poses with view v depressing bank bank_of_view[v] (the routes of a grid, trained in one call); returns the
+        views (uint8[n,h,w,3]) when want_views."""
+        x, y, angle = self._pose_arrays(x, y, angle)
+        banks = self._bank_table(bank_of_view, len(x), "bank_of_view")
+        h, w = self.sensor_shape
+        views = np.empty((len(x), h, w, 3), dtype=np.uint8) if want_views else None
+        self._check_sense(self._lib.dv_mbank_train_from_poses(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), len(x),
+                                                              banks.ctypes.data_as(N._i32p), N.u8ptr(views) if want_views else None),
+                          "dv_mbank_train_from_poses")
+        return views
+
+    def mbank_step_batch_u8(self, planes, bank_of_member):
+        """mb_step_batch_u8 with member i scored under bank bank_of_member[i] -> OneValueBatchResults."""
+        planes = N.as_u8(planes, "planes")
+        if planes.ndim != 4 or planes.shape[0] < 1 or planes.shape[1] < 1:
+            raise ValueError("planes must be uint8[n,A,h,w] with n, A >= 1, got shape %r" % (planes.shape,))
+        n, A = planes.shape[:2]
+        banks = self._bank_table(bank_of_member, n, "bank_of_member")
+        flat = self._ov_planes("mushroom", planes.reshape((n * A,) + planes.shape[2:]))
+        fam = np.empty((n, A), dtype=np.float64)
+        best = np.full(n, -1, dtype=np.int32)
+        self._check(self._lib.dv_mbank_step_u8(self._ctx, N.u8ptr(flat), n, A, banks.ctypes.data_as(N._i32p), N.f64ptr(fam),
+                                               best.ctypes.data_as(N._i32p)), "dv_mbank_step_u8")
+        return OneValueBatchResults(fam, best, np.zeros(n, dtype=np.uint32))
+
+    def mbank_sense_step_batch(self, x, y, angles, bank_of_member):
+        """mb_sense_step_batch with member i scored under bank bank_of_member[i] -> OneValueBatchResults: one enqueue and one wait."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        angles = np.ascontiguousarray(angles, dtype=np.float64)
+        if angles.ndim != 2 or len(x) != len(y) or angles.shape[0] != len(x) or angles.shape[0] < 1 or angles.shape[1] < 1:
+            raise ValueError("x[N], y[N] and angles[N, A] expected (N, A >= 1), got shapes %r, %r and %r" % (x.shape, y.shape, angles.shape))
+        n, A = angles.shape
+        banks = self._bank_table(bank_of_member, n, "bank_of_member")
+        fam = np.empty((n, A), dtype=np.float64)
+        best = np.full(n, -1, dtype=np.int32)
+        flags = np.zeros(n, dtype=np.uint32)
+        self._check(self._lib.dv_mbank_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, banks.ctypes.data_as(N._i32p),
+                                                  N.f64ptr(fam), best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)),
+                    "dv_mbank_sense_step")
+        return OneValueBatchResults(fam, best, flags)
+
+    def mbank_read_weights(self, bank=None):
+        """uint8[n_kc] of one bank; bank=None: all of them, uint8[n_banks, n_kc]."""
+        if bank is not None:
+            bank = self._bank_index(bank)
+        n_kc = max(self.mb_info()["n_kc"], 1)
+        out = np.empty((self.mb_banks if bank is None else 1, n_kc), dtype=np.uint8)
+        for row, b in enumerate(range(self.mb_banks) if bank is None else (bank,)):
+            self._check(self._lib.dv_mbank_read_weights(self._ctx, b, N.u8ptr(out[row])), "dv_mbank_read_weights")
+        return out if bank is None else out[0]
+
+    def mbank_set_weights(self, bank, weights):
+        bank = self._bank_index(bank)
+        n_kc = self.mb_info()["n_kc"]
+        weights = N.as_u8(weights, "weights")
+        if n_kc and weights.shape != (n_kc,):
+            raise ValueError("weights must be uint8[%d], got shape %r" % (n_kc, weights.shape))
+        self._check(self._lib.dv_mbank_set_weights(self._ctx, bank, N.u8ptr(weights)), "dv_mbank_set_weights")
+
+    def mbank_info(self):
+        """dict(n_banks, views_trained int64[n_banks], n_depressed int64[n_banks])."""
+        nb = ctypes.c_int(0)
+        self._check(self._lib.dv_mbank_info(self._ctx, ctypes.byref(nb), None, None), "dv_mbank_info")
+        views = np.zeros(max(nb.value, 1), dtype=np.int64)
+        zeros = np.zeros(max(nb.value, 1), dtype=np.int64)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        self._check(self._lib.dv_mbank_info(self._ctx, None, views.ctypes.data_as(i64p), zeros.ctypes.data_as(i64p)), "dv_mbank_info")
+        return dict(n_banks=nb.value, views_trained=views, n_depressed=zeros)

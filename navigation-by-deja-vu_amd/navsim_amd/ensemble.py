@@ -19,10 +19,12 @@ single agent works its minimum out when it is read.
 import numpy as np
 
 from .agent import StopNavigationException, OutOfLandscapeBoundsException
-from .util import reject_infomax, reject_mushroom
+from .util import reject_infomax, reject_mushroom, reject_banked
 
 
 class NavEnsemble(object):
+    _metrics_on_slots = True     # the members' error metrics run on the device's path slots (they hold ONE training path)
+
     def __init__(self, agents):
         if not agents:
             raise ValueError("no agents")
@@ -51,7 +53,7 @@ class NavEnsemble(object):
         self._stepping = False
         self._pending = []                                        # members whose position awaits its metrics
         self._too_far = {}
-        if agents[0].training_path is not None and hasattr(eng, "path_slots") and all(a.training_path is agents[0].training_path for a in agents):
+        if self._metrics_on_slots and agents[0].training_path is not None and hasattr(eng, "path_slots") and all(a.training_path is agents[0].training_path for a in agents):
             for a in self.agents:
                 if getattr(a, "_metrics_on_device", False):
                     a._collect_errors()                           # (answers still outstanding from steps it took on its own)
@@ -65,6 +67,7 @@ class NavEnsemble(object):
     @classmethod
     def _check_member(cls, agent):
         """Raises ValueError for an agent this kind of ensemble cannot step."""
+        reject_banked(agent, cls.__name__)
         reject_infomax(agent, "NavEnsemble")
 
     def _device_step(self, idx, xs, ys, angs):
@@ -167,10 +170,6 @@ class NavEnsemble(object):
         self._read_scene()
         return np.stack([a.scene_familiarity for a in self.agents])
 
-    @property
-    def active(self):
-        return [i for i, s in enumerate(self.stop_status) if s == 0 and self.agents[i].stopped_with_exception is None]
-
     SENSE_ERROR_STATUS = -3      # not one of the reference's codes: its trial would have died of an IndexError
 
     def _stop(self, i, exc):
@@ -253,17 +252,37 @@ class NavEnsemble(object):
                     self._stop(i, e)
         return self.active
 
+    _frames_left = None          # run() with a count per member: the steps each member may still take
+
+    @property
+    def active(self):
+        left = self._frames_left
+        return [i for i, s in enumerate(self.stop_status) if s == 0 and self.agents[i].stopped_with_exception is None and
+                (left is None or left[i] > 0)]
+
     def run(self, frames):
-        """Up to `frames` steps; returns the per-agent number of completed steps."""
+        """Up to `frames` steps -- an int, or one count per member; returns the per-agent number of completed steps.  A member that has
+        taken its count steps no more and keeps stop_status 0."""
+        if isinstance(frames, (int, np.integer)):
+            frames = [int(frames)] * len(self.agents)
+        else:
+            frames = [int(f) for f in frames]
+            if len(frames) != len(self.agents):
+                raise ValueError("frames holds %d counts for %d members" % (len(frames), len(self.agents)))
         done = [0] * len(self.agents)
-        for _ in range(frames):
-            before = self.active
-            if not before:
-                break
-            self.step_forward()
-            for i in before:
-                if self.stop_status[i] == 0:
-                    done[i] += 1
+        self._frames_left = list(frames)
+        try:
+            for _ in range(max(frames + [0])):
+                before = self.active
+                if not before:
+                    break
+                self.step_forward()
+                for i in before:
+                    self._frames_left[i] -= 1
+                    if self.stop_status[i] == 0:
+                        done[i] += 1
+        finally:
+            self._frames_left = None
         return done
 
 
@@ -282,8 +301,13 @@ class _OneValueEnsemble(NavEnsemble):
         """The refusals of util.py for the other model without a library."""
 
     @classmethod
+    def _reject_banked(cls, agent):
+        reject_banked(agent, cls.__name__)
+
+    @classmethod
     def _check_member(cls, agent):
         func = getattr(agent, "_familiarity_func", None)
+        cls._reject_banked(agent)
         cls._reject_others(agent)
         if getattr(getattr(agent, "familiarity_model", None), "metric", None) != cls._metric:
             raise ValueError("%s takes %s; NavEnsemble steps the library-based models" % (cls.__name__, cls._takes))
@@ -338,3 +362,103 @@ class MushroomEnsemble(_OneValueEnsemble):
         for obj in (agent, getattr(agent, "familiarity_model", None), getattr(agent, "_familiarity_func", None)):
             if getattr(obj, "metric", None) == "infomax":
                 raise ValueError("MushroomEnsemble does not take an Infomax model: navsim_amd.InfomaxEnsemble steps that one")
+
+
+class MushroomRouteEnsemble(_OneValueEnsemble):
+    """MushroomEnsemble for trials that differ in their TRAINING ROUTE as well (the reference's grid varies training_path_curve on one
+    landscape, scripts/run_experiment.py:57,208): the model's connectivity is shared, and every route has a memory bank of its own
+    (FamiliarityEngine.mbank_set: n_kc bytes a route).  All routes are trained in one device call, and a step scores every running
+    member's headings under its own route's bank in ONE device call (dv_mbank_sense_step), with the bits a lone agent trained on that
+    route alone gives at the same pose.  Made by from_routes.  Members' error metrics stay on the host (the device's path slots hold one
+    path); a member steps with its ensemble only."""
+    _metric = "mushroom"
+    _takes = MushroomEnsemble._takes
+    _batch_call = "mbank_sense_step_batch"
+    _metrics_on_slots = False
+    _reject_others = MushroomEnsemble._reject_others
+
+    def __init__(self, agents):
+        for a in agents:
+            if getattr(a, "memory_bank", None) is None:
+                raise ValueError("MushroomRouteEnsemble takes the members MushroomRouteEnsemble.from_routes makes (agents with a "
+                                 "memory_bank); MushroomEnsemble steps agents that share one trained route")
+        super(MushroomRouteEnsemble, self).__init__(agents)
+        self._banks = np.array([a.memory_bank for a in agents], dtype=np.int32)
+
+    @classmethod
+    def _reject_banked(cls, agent):
+        """(its own members are the banked ones)"""
+
+    @classmethod
+    def from_agent(cls, agent, poses):
+        raise ValueError("MushroomRouteEnsemble is made from routes (from_routes); MushroomEnsemble.from_agent clones a trained agent")
+
+    @classmethod
+    def from_routes(cls, agent, routes, starts):
+        """`agent`: an UNTRAINED agent of mushroom_familiarity(...) with the GPU sensor model; routes: R arrays float64[n_r, 2];
+        starts: iterable of (route_index, (x, y), angle), one member each (the first is `agent` itself, the others copies of it on the
+        same engine).  Every route is trained into its own bank, all in one call; member i gets the training_path, training_path_length
+        and familiar_scenes of routes[route_index_i], and that route's bank as its `memory_bank`."""
+        import copy
+        cls._reject_others(agent)
+        model = getattr(agent, "familiarity_model", None)
+        if getattr(model, "metric", None) != cls._metric:
+            raise ValueError("%s takes %s; NavEnsemble steps the library-based models" % (cls.__name__, cls._takes))
+        eng = getattr(agent, "_engine", None)
+        if eng is None:
+            raise ValueError("%s needs agents whose sensor model runs on the GPU (use_gpu_sensor=True)" % cls.__name__)
+        if agent.training_path is not None or getattr(agent, "memory_bank", None) is not None:
+            raise ValueError("%s.from_routes takes an UNTRAINED agent: it trains every route into a memory bank of its own" % cls.__name__)
+        routes = [np.asarray(r, dtype=np.float64) for r in routes]
+        if not routes or any(r.ndim != 2 or r.shape[1] != 2 or len(r) < 2 for r in routes):
+            raise ValueError("routes must be one or more arrays float64[n_r, 2] of at least two points each")
+        starts = [(r, (float(pos[0]), float(pos[1])), float(ang)) for r, pos, ang in starts]
+        if not starts:
+            raise ValueError("no starts: one (route_index, (x, y), angle) per member")
+        for i, (r, _, _) in enumerate(starts):
+            if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 0 <= r < len(routes):
+                raise ValueError("starts[%d]: route_index %r outside [0, %d)" % (i, r, len(routes)))
+        for route in routes:
+            for pt in route:
+                agent._check_bounds(pt)
+        # the views of a route look along ITS steps (train_from_path: towards the next point, the last heading once more)
+        headings = []
+        for route in routes:
+            steps = route[1:] - route[:-1]
+            h = np.arctan2(steps[:, 1], steps[:, 0])
+            headings.append(h[np.minimum(np.arange(len(route)), len(route) - 2)])
+        first = np.cumsum([0] + [len(r) for r in routes])
+        points = np.concatenate(routes)
+        bank_of_view = np.repeat(np.arange(len(routes), dtype=np.int32), [len(r) for r in routes])
+        model.begin(eng, agent.sensor_dimensions[1], agent.sensor_dimensions[0])
+        eng.mbank_set(len(routes))
+        views = eng.mbank_train_from_poses(points[:, 0], points[:, 1], np.concatenate(headings), bank_of_view)
+        func = model.from_engine(eng, views)
+        members = []
+        for k, (r, pos, ang) in enumerate(starts):
+            a = agent if k == 0 else copy.copy(agent)
+            route = routes[r]
+            a.training_path = route
+            a.training_path_length = np.sum(np.linalg.norm(route[1:] - route[:-1], axis=1))
+            a.familiar_scenes = views[first[r]:first[r + 1]]
+            a._familiarity_func = func
+            a.memory_bank = int(r)
+            a.angle_familiarity = np.full(agent.n_test_angles, np.nan)
+            a.scene_familiarity = np.zeros(len(route), dtype=np.float64)
+            a._scene_is_inf = False
+            a._metrics_on_device = False                         # (update_error's NumPy branch: the device's slots hold one path)
+            a._metric_slot, a._ens, a._spec = None, None, None
+            a.step_familiarity = np.inf
+            a.position, a.angle = pos, ang
+            a.reset_error()
+            members.append(a)
+        return cls(members)
+
+    def _device_step(self, idx, xs, ys, angs):
+        results = self.engine.mbank_sense_step_batch(xs, ys, angs, self._banks[idx])
+        self._rows = {id(self.agents[i]): results.angle_familiarity[k] for k, i in enumerate(idx)}
+        return results
+
+    def bank_info(self):
+        """Per bank (route): dict(n_banks, views_trained int64[R], n_depressed int64[R])."""
+        return self.engine.mbank_info()

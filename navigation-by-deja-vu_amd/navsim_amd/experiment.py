@@ -89,10 +89,11 @@ def run_experiment(nsf, frames=None):
 
 
 def run_ensemble(ens, frames=None):
-    """run_experiment for a navsim_amd.NavEnsemble: every agent gets the reference's result row (:251-258)."""
-    first = ens.agents[0]
+    """run_experiment for a navsim_amd.NavEnsemble: every agent gets the reference's result row (:251-258).  frames: an int, one count
+    per member, or None for every member's own FRAME_FACTOR * training_path_length / step_size."""
     if frames is None:
-        frames = int(FRAME_FACTOR * first.training_path_length / first.step_size)
+        # every member its own trial's count (members on one path: one value, as a lone run_experiment gives each)
+        frames = [int(FRAME_FACTOR * nsf.training_path_length / nsf.step_size) for nsf in ens.agents]
     done = ens.run(frames)
     rows = []
     for i, nsf in enumerate(ens.agents):

@@ -161,6 +161,14 @@ def reject_mushroom(model, what):
                              "navsim_amd.MushroomEnsemble)" % what)
 
 
+def reject_banked(agent, what):
+    """The refusal of every ensemble but navsim_amd.MushroomRouteEnsemble for one of ITS members: the member's route is kept in a memory
+    bank of its own (agent.memory_bank), and the other ensembles' steps score under the model's first bank."""
+    if getattr(agent, "memory_bank", None) is not None:
+        raise ValueError("%s does not take a member of a MushroomRouteEnsemble: its route is kept in memory bank %d of the shared model, "
+                         "and only that ensemble's step scores it there" % (what, agent.memory_bank))
+
+
 def _one_value_familiarity(metric, channel, device, begin, **extras):
     """Stage 2 of a model that keeps no library (infomax_familiarity, mushroom_familiarity): `begin(engine, h, w)` makes a fresh model
     of h x w views; the engine's <prefix>_train_u8 / <prefix>_score_u8 are the ones of `metric`.  `extras` become attributes of the product."""

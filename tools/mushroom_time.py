@@ -2,7 +2,7 @@
 """Times the mushroom-body familiarity model (navsim_amd.mushroom_familiarity; include/dejavu.h: dv_mb_*) on GPU 0 and writes
 profiles/mushroom_time.json.
 
-    python tools/mushroom_time.py [--sides 32,64] [--views 1000] [--calls 200] [--reps 5] [--blocks single,ensemble]
+    python tools/mushroom_time.py [--sides 32,64] [--views 1000] [--calls 200] [--reps 5] [--blocks single,ensemble[,banks]]
                                   [--out profiles/mushroom_time.json]
 
 Per sensor side s (views of s x s) with K = 20000 Kenyon cells, fan-in 10 and 200 firing cells: microseconds per agent step
@@ -16,7 +16,15 @@ of the model (tests/helpers_mushroom.py) scoring the same number of patches.
 Ensemble block (--blocks ensemble): per side, 32 members x 16 headings and 8 members x 60 headings at poses spread over the synthetic
 landscape -- microseconds per ensemble step of dv_batch_mb_sense_step (one call for all members), and of the same poses as a loop of
 dv_mb_sense_step calls, one per member, from the same child process in alternating windows of --ensemble-calls steps; their ratio is
-loop_over_batched.  A block that is not measured keeps the rows it has in the output file.
+loop_over_batched.
+
+Banks block (--blocks banks): per side, the same two layouts over 4 memory banks (dv_mbank_set; member i in bank i % 4) --
+microseconds per ensemble step of dv_mbank_sense_step and of dv_batch_mb_sense_step (every member under bank 0: the unbanked call, the
+yardstick) at the same poses, alternating windows in the same child process; their ratio is banked_over_unbanked.  And training: 4
+routes of --views views each in ONE dv_mbank_train_from_poses call on one engine, against four dv_mb_train_from_poses calls on four
+engines (the sum of the four engines' own timers).
+
+A block that is not measured keeps the rows it has in the output file.
 
 Every GPU measurement runs in a child process of its own under a time limit, and nothing more is started on the GPU after one
 that failed."""
@@ -133,6 +141,92 @@ def ensemble_child(side, n_calls, reps):
     print(json.dumps(out))
 
 
+N_BANKS = 4
+
+
+def banks_child(side, n_views, n_calls, reps):
+    """The banks block of one size on the GPU -> one JSON line on stdout."""
+    from navsim_amd import NavBySceneFamiliarity, mushroom_familiarity, synth
+    from navsim_amd.util import mushroom_connectivity
+    N = side * side
+    land = synth.synth_landscape(3, 600, 4)
+    out = dict(side=side, N=N, n_kc=K, fan_in=FAN_IN, n_active=N_ACTIVE, n_banks=N_BANKS, calls_per_window=n_calls,
+               views_per_route=n_views, layouts=[])
+    conn = mushroom_connectivity(K, N, FAN_IN, 0)
+    for n, A in ENSEMBLES:
+        agent = NavBySceneFamiliarity(land, (side, side), 1.0, n_test_angles=A, familiarity_model=mushroom_familiarity())
+        eng = agent._engine                                       # (landscape and sensor attached)
+        eng.mb_begin(side, side, conn, N_ACTIVE, 2)
+        eng.mbank_set(N_BANKS)
+        rng = np.random.default_rng(n * 100 + A)
+        xs, ys = rng.uniform(150, 450, n), rng.uniform(150, 450, n)
+        angs = (rng.uniform(0, 2 * np.pi, n)[:, None] + agent.angle_offsets[None, :]) % (2 * np.pi)
+        banks = (np.arange(n) % N_BANKS).astype(np.int32)
+        eng.mbank_train_from_poses(xs, ys, angs[:, A // 2].copy(), banks, want_views=False)   # (some weights at 0 in every bank)
+
+        def banked():
+            eng.timer_start()
+            for _ in range(n_calls):
+                res = eng.mbank_sense_step_batch(xs, ys, angs, banks)
+            return eng.timer_stop() * 1e3 / n_calls, res          # us per ensemble step
+
+        def unbanked():
+            eng.timer_start()
+            for _ in range(n_calls):
+                eng.mb_sense_step_batch(xs, ys, angs)
+            return eng.timer_stop() * 1e3 / n_calls
+
+        _, res = banked()                                         # warm-up of both (code load, clocks, the buffers)
+        unbanked()
+        assert not res.flags.any() and res.angle_familiarity.max() == 0.0 and res.angle_familiarity.min() < 0
+        tb, tu = [], []
+        for _ in range(reps):                                     # alternating windows
+            tb.append(banked()[0])
+            tu.append(unbanked())
+        out["layouts"].append(dict(members=n, headings=A, banked_us_per_step=spread(tb), unbanked_us_per_step=spread(tu),
+                                   banked_over_unbanked=round(float(np.median(tb) / np.median(tu)), 3)))
+        eng.close()
+    # training: N_BANKS routes in one banked call on one engine, against one call per route on an engine each
+    engines = [NavBySceneFamiliarity(land, (side, side), 1.0, n_test_angles=HEADINGS[0], familiarity_model=mushroom_familiarity())._engine
+               for _ in range(N_BANKS)]
+    rng = np.random.default_rng(side + 7)
+    total = N_BANKS * n_views
+    xs, ys, angs = rng.uniform(150, 450, total), rng.uniform(150, 450, total), rng.uniform(0, 2 * np.pi, total)
+    bank_of = np.repeat(np.arange(N_BANKS, dtype=np.int32), n_views)
+
+    def one_call():
+        eng = engines[0]
+        eng.mb_begin(side, side, conn, N_ACTIVE, 2)
+        eng.mbank_set(N_BANKS)
+        eng.timer_start()
+        eng.mbank_train_from_poses(xs, ys, angs, bank_of, want_views=False)
+        return eng.timer_stop() * 1e3
+
+    def call_per_route():
+        t = 0.0
+        for r, eng in enumerate(engines):
+            eng.mb_begin(side, side, conn, N_ACTIVE, 2)
+            sl = slice(r * n_views, (r + 1) * n_views)
+            eng.timer_start()
+            eng.mb_train_from_poses(xs[sl], ys[sl], angs[sl], want_views=False)
+            t += eng.timer_stop() * 1e3
+        return t
+
+    one_call()
+    zeros = engines[0].mbank_info()["n_depressed"].tolist()
+    call_per_route()
+    assert zeros == [e.mb_info()["n_depressed"] for e in engines] and all(0 < z <= K for z in zeros)
+    t1, t4 = [], []
+    for _ in range(reps):
+        t1.append(one_call())
+        t4.append(call_per_route())
+    out["train"] = dict(routes=N_BANKS, views_per_route=n_views, one_banked_call_us=spread(t1), call_per_route_us=spread(t4),
+                        per_route_over_banked=round(float(np.median(t4) / np.median(t1)), 3), n_depressed=zeros)
+    for e in engines:
+        e.close()
+    print(json.dumps(out))
+
+
 def cpu_row(side, n_calls):
     """The NumPy statement on this host: wall clock, microseconds per call that scores A patches."""
     from tests import helpers_mushroom as H
@@ -157,10 +251,11 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--limit", type=int, default=240, help="seconds allowed to each GPU child")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mushroom_time.json"))
-    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and the agent step), ensemble")
+    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and the agent step), ensemble, banks")
     ap.add_argument("--ensemble-calls", type=int, default=30, help="ensemble steps per timed window")
     ap.add_argument("--child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--ensemble-child", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--banks-child", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
         gpu_child(args.child, args.views, args.calls, args.reps)
@@ -168,13 +263,16 @@ def main():
     if args.ensemble_child:
         ensemble_child(args.ensemble_child, args.ensemble_calls, args.reps)
         return 0
+    if args.banks_child:
+        banks_child(args.banks_child, args.views, args.ensemble_calls, args.reps)
+        return 0
     blocks = args.blocks.split(",")
     result = dict(tool="tools/mushroom_time.py", timer="hipEvent pair (dv_timer_start/stop), median of %d windows after a warm-up" % args.reps,
-                  sizes=[], ensembles=[])
+                  sizes=[], ensembles=[], banks=[])
     if os.path.exists(args.out):                                  # a block that is not measured keeps its rows
         with open(args.out) as f:
             kept = json.load(f)
-        for block, key in (("single", "sizes"), ("ensemble", "ensembles")):
+        for block, key in (("single", "sizes"), ("ensemble", "ensembles"), ("banks", "banks")):
             if block not in blocks:
                 result[key] = kept.get(key, [])
     for side in [int(x) for x in args.sides.split(",")] if "ensemble" in blocks else []:
@@ -185,6 +283,14 @@ def main():
             print("GPU measurement of the ensembles of side %d ended with status %d: nothing more is run" % (side, p.returncode), file=sys.stderr)
             return p.returncode
         result["ensembles"].append(json.loads(p.stdout.strip().splitlines()[-1]))
+    for side in [int(x) for x in args.sides.split(",")] if "banks" in blocks else []:
+        cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--banks-child", str(side), "--views", str(args.views),
+               "--ensemble-calls", str(args.ensemble_calls), "--reps", str(args.reps)]
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, universal_newlines=True)
+        if p.returncode != 0:
+            print("GPU measurement of the banks of side %d ended with status %d: nothing more is run" % (side, p.returncode), file=sys.stderr)
+            return p.returncode
+        result["banks"].append(json.loads(p.stdout.strip().splitlines()[-1]))
     for side in [int(x) for x in args.sides.split(",")] if "single" in blocks else []:
         cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child", str(side), "--views", str(args.views),
                "--calls", str(args.calls), "--reps", str(args.reps)]

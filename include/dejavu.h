@@ -678,6 +678,47 @@ int dv_mbank_read_weights(dv_ctx *ctx, int bank, uint8_t *out);
 int dv_mbank_set_weights(dv_ctx *ctx, int bank, const uint8_t *weights);
 int dv_mbank_info(dv_ctx *ctx, int *n_banks, int64_t *views_trained, int64_t *n_depressed);
 
+/* ---- Infomax weight banks --------------------------------------------------- */
+/*
+ * Several Infomax models of one shape and one learning rate in ONE context: the weights are float64[n_banks][n_hidden][h * w], bank b
+ * at offset b * n_hidden * h * w.  A bank is a route's model: the trials of a grid that differ in their training route train in one
+ * call and step in one call, each through its own bank.  n_banks is 1 after dv_infomax_begin; the dv_infomax_ and dv_batch_infomax_
+ * calls act on bank 0 and touch no other.  A bank table is int32, one entry per view (training) or per member (a step); every entry is
+ * checked against [0, n_banks) before anything of the call reaches the device: DV_ERR_INVALID names the first entry out of range, and
+ * nothing was trained, scored or uploaded.  A table that names a bank whose weights are not finite: DV_ERR_STATE, likewise.
+ *   set              n_banks >= 1 banks (at most 65535), every one a copy of w0 (float64[n_hidden * h * w], required), all view counts
+ *                    0 (whatever was trained before is dropped).  DV_ERR_OOM leaves the model as it was.  dv_infomax_begin and
+ *                    dv_infomax_end return to one bank.
+ *   train_u8 / train_from_poses   as their dv_infomax_ twins, with view v trained into bank bank_of_view[v].  Every bank's views are
+ *                    taken in the order they have in the call, and the R chains advance in lockstep: step s of the call is every
+ *                    bank's s-th view, in the three launches one chain's step takes.  A bank's weights after the call have the bits
+ *                    dv_infomax_train_u8 gives on that bank's views alone from the same weights; a bank that gets no view keeps its
+ *                    bits.  n = 0 is legal for train_u8.  DV_ERR_INDEX (train_from_poses): nothing was trained in any bank.
+ *                    DV_ERR_STATE after the call: the message names the first bank of the call whose weights are no longer finite,
+ *                    and the learning rate; the other banks hold their own chains' weights and go on working.
+ *   step_u8 / sense_step   as dv_batch_infomax_step_u8 / dv_batch_infomax_sense_step, with member i scored under bank
+ *                    bank_of_member[i]: the members may come in any bank order, the results come in the caller's order, from one
+ *                    enqueue and one wait.  A column's value has the bits dv_infomax_score_u8 gives the same patch on a model that
+ *                    holds that bank's weights.  flags, the sensor-shape check and DV_RES_SENSE_ERROR per member as
+ *                    dv_batch_infomax_sense_step.
+ *   read_weights / set_weights   copy float64[n_hidden][h * w] of one bank out and in; DV_ERR_INVALID for a bank outside
+ *                    [0, n_banks).  set_weights with finite weights makes a bank that diverged usable again.
+ *   info             n_banks, and per bank the views trained and whether the weights are finite: views_trained and finite are the
+ *                    caller's arrays of n_banks entries (ask for n_banks first); any pointer may be NULL.  One bank without a model.
+ * Every call but info returns DV_ERR_STATE without a model.
+ */
+int dv_ibank_set(dv_ctx *ctx, int n_banks, const double *w0);
+int dv_ibank_train_u8(dv_ctx *ctx, const uint8_t *planes, int64_t n, const int32_t *bank_of_view);
+int dv_ibank_train_from_poses(dv_ctx *ctx, const double *x, const double *y, const double *angle, int64_t n, const int32_t *bank_of_view,
+                              uint8_t *out_views);
+int dv_ibank_step_u8(dv_ctx *ctx, const uint8_t *planes, int n_agents, int n_headings, const int32_t *bank_of_member, double *angle_fam,
+                     int32_t *best_heading);
+int dv_ibank_sense_step(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
+                        const int32_t *bank_of_member, double *angle_fam, int32_t *best_heading, uint32_t *flags);
+int dv_ibank_read_weights(dv_ctx *ctx, int bank, double *out);
+int dv_ibank_set_weights(dv_ctx *ctx, int bank, const double *weights);
+int dv_ibank_info(dv_ctx *ctx, int *n_banks, int64_t *views_trained, int32_t *finite);
+
 /* ---- measurement ------------------------------------------------------- */
 /* hipEvent pair on the context's stream around whatever is enqueued between the two calls. */
 int dv_timer_start(dv_ctx *ctx);

@@ -315,8 +315,19 @@ struct dv_ctx {
     size_t im_bx_cap = 0, im_bdpart_cap = 0, im_perr_cap = 0;   // bytes
     int im_M = 0, im_N = 0, im_hh = 0, im_ww = 0, im_channel = 2;
     double im_eta = 0.0;
-    int64_t im_views = 0;                     // views trained on since dv_infomax_begin
-    bool im_finite = true;
+    // weight banks (dv_ibank_*): im_W is [im_banks][M][N], bank b at b M N; bank 0 is the dv_infomax_* and dv_batch_infomax_* calls' model
+    int im_banks = 1;                         // 1 after dv_infomax_begin; dv_ibank_set
+    std::vector<int64_t> im_views = std::vector<int64_t>(1, 0);   // [im_banks]: views trained on since dv_infomax_begin / dv_ibank_set
+    std::vector<char> im_finite = std::vector<char>(1, 1);        // [im_banks]: are the bank's weights finite (im_flag: a word per bank)
+    double* im_kh[2] = {nullptr, nullptr};    // [im_banks][M] each: banked training's h
+    double* im_ku = nullptr;                  // [im_banks][N]
+    double* im_kupart = nullptr;              // [im_banks][row blocks][N]
+    int* im_ktab = nullptr;                   // a banked call's table on the device (training: chains; a step: column blocks and members)
+    size_t im_ktab_cap = 0;                   // bytes
+    std::vector<int> im_ktab_host;            // what im_ktab holds
+    bool im_ktab_step = false;                // im_ktab holds a step's table: an equal one is not sent again
+    std::vector<double> im_kpose;             // a banked step's poses in bank order: x, y, angles
+    std::vector<uint8_t> im_kplanes;          // ... or its uploaded planes
     // mushroom-body familiarity model (dejavu_mushroom.inl): fixed fan-in, one byte of weight per Kenyon cell; independent of the above
     unsigned short* mb_conn = nullptr;        // [fan_in][K]: input j of every cell
     unsigned char* mb_wt = nullptr;           // [mb_banks][K]: 1, or 0 once depressed (bank 0 is the dv_mb_* calls' memory)

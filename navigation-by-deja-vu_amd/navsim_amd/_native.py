@@ -258,6 +258,14 @@ PROTOTYPES = {
     "dv_mbank_read_weights": (ctypes.c_int, [_ctx_p, ctypes.c_int, _u8p]),
     "dv_mbank_set_weights": (ctypes.c_int, [_ctx_p, ctypes.c_int, _u8p]),
     "dv_mbank_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "dv_ibank_set": (ctypes.c_int, [_ctx_p, ctypes.c_int, _f64p]),
+    "dv_ibank_train_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int64, _i32p]),
+    "dv_ibank_train_from_poses": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int64, _i32p, _u8p]),
+    "dv_ibank_step_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, _i32p, _f64p, _i32p]),
+    "dv_ibank_sense_step": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _i32p, _f64p, _i32p, _u32p]),
+    "dv_ibank_read_weights": (ctypes.c_int, [_ctx_p, ctypes.c_int, _f64p]),
+    "dv_ibank_set_weights": (ctypes.c_int, [_ctx_p, ctypes.c_int, _f64p]),
+    "dv_ibank_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64), _i32p]),
     "dv_synchronize": (ctypes.c_int, [_ctx_p]),
     "dv_timer_start": (ctypes.c_int, [_ctx_p]),
     "dv_timer_stop": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_float)]),

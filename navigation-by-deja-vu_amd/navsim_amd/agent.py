@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 from .engine import ONE_VALUE_METRICS
-from .util import sads_familiarity
+from .util import sads_familiarity, route_ensemble_name
 
 
 # ---- stop conditions (names and codes of navsim/NavBySceneFamiliarity.py:22-49) ----------------
@@ -127,7 +127,7 @@ class NavBySceneFamiliarity(object):
     """
 
     chem_weight = None              # a NavEnsemble member's own weight (NavEnsemble.from_agent(chem_weights=...)); None: the model's
-    memory_bank = None              # a MushroomRouteEnsemble member's own memory of the shared mushroom-body model; None: the model's one
+    memory_bank = None              # a route ensemble's member: its own bank of the shared mushroom-body or Infomax model; None: the model's one
 
     def __init__(self,
                  landscape,
@@ -557,8 +557,8 @@ class NavBySceneFamiliarity(object):
                              % (self.chem_weight, getattr(self.familiarity_model, "chem_weight", None)))
         if self.memory_bank is not None:
             # (a step of its own scores under bank 0 of the model: only its ensemble's batches score it under its own bank)
-            raise ValueError("this ensemble member's route is kept in memory bank %d of a model it shares: step it with its "
-                             "MushroomRouteEnsemble" % self.memory_bank)
+            raise ValueError("this ensemble member's route is kept in memory bank %d of a model it shares: step it with its %s"
+                             % (self.memory_bank, route_ensemble_name(self)))
         position = self.position
         self.angle_familiarity[:] = np.nan
         assert len(self.familiar_scenes) == len(self._scene_fam)

@@ -881,6 +881,7 @@ class FamiliarityEngine(object):
                                                N.f64ptr(weights)), "dv_infomax_begin")
         self.infomax_shape = (int(h), int(w))
         self.infomax_hidden = weights.shape[0]
+        self.infomax_banks = 1
 
     def infomax_train_u8(self, planes):
         """One more pass of the learning rule over uint8[n,h,w] planes, in order, on the same W."""
@@ -933,6 +934,99 @@ class FamiliarityEngine(object):
     def infomax_end(self):
         self._check(self._lib.dv_infomax_end(self._ctx), "dv_infomax_end")
         self.infomax_shape = None
+        self.infomax_banks = 1
+
+    # -- weight banks of the Infomax model: several models of one shape in one context (include/dejavu.h: dv_ibank_*) ------------
+    infomax_banks = 1            # banks of the model (ibank_set; 1 after infomax_begin)
+
+    def _ibank_weights(self, weights, what):
+        info = self.infomax_info()
+        weights = np.ascontiguousarray(weights, dtype=np.float64)
+        if info["n_hidden"] and weights.shape != (info["n_hidden"], info["n_pixels"]):
+            raise ValueError("%s must be float64[%d,%d], got shape %r" % (what, info["n_hidden"], info["n_pixels"], weights.shape))
+        return weights
+
+    def ibank_set(self, n_banks, weights):
+        """n_banks banks, every one a copy of `weights` (float64[n_hidden, h*w]: the model's W0); what was trained is dropped.  The
+        infomax_* calls keep acting on bank 0; infomax_begin and infomax_end return to one bank."""
+        if isinstance(n_banks, bool) or not isinstance(n_banks, (int, np.integer)) or n_banks < 1:
+            raise ValueError("n_banks must be an integer >= 1, got %r" % (n_banks,))
+        weights = self._ibank_weights(weights, "weights")
+        self._check(self._lib.dv_ibank_set(self._ctx, int(n_banks), N.f64ptr(weights)), "dv_ibank_set")
+        self.infomax_banks = int(n_banks)
+
+    def ibank_train_u8(self, planes, bank_of_view):
+        """infomax_train_u8 with view v trained into bank bank_of_view[v]: every bank's views in their order, the banks' chains in
+        lockstep, three launches a step for all of them."""
+        planes = self._ov_planes("infomax", planes)
+        banks = self._bank_table(bank_of_view, planes.shape[0], "bank_of_view", self.infomax_banks)
+        self._check(self._lib.dv_ibank_train_u8(self._ctx, N.u8ptr(planes), planes.shape[0], banks.ctypes.data_as(N._i32p)), "dv_ibank_train_u8")
+
+    def ibank_train_from_poses(self, x, y, angle, bank_of_view, want_views=True):
+        """infomax_train_from_poses with view v trained into bank bank_of_view[v] (the routes of a grid, trained in one call); returns
+        the views (uint8[n,h,w,3]) when want_views."""
+        x, y, angle = self._pose_arrays(x, y, angle)
+        banks = self._bank_table(bank_of_view, len(x), "bank_of_view", self.infomax_banks)
+        h, w = self.sensor_shape
+        views = np.empty((len(x), h, w, 3), dtype=np.uint8) if want_views else None
+        self._check_sense(self._lib.dv_ibank_train_from_poses(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), len(x),
+                                                              banks.ctypes.data_as(N._i32p), N.u8ptr(views) if want_views else None),
+                          "dv_ibank_train_from_poses")
+        return views
+
+    def ibank_step_batch_u8(self, planes, bank_of_member):
+        """infomax_step_batch_u8 with member i scored under bank bank_of_member[i] -> OneValueBatchResults, in the caller's order."""
+        planes = N.as_u8(planes, "planes")
+        if planes.ndim != 4 or planes.shape[0] < 1 or planes.shape[1] < 1:
+            raise ValueError("planes must be uint8[n,A,h,w] with n, A >= 1, got shape %r" % (planes.shape,))
+        n, A = planes.shape[:2]
+        banks = self._bank_table(bank_of_member, n, "bank_of_member", self.infomax_banks)
+        flat = self._ov_planes("infomax", planes.reshape((n * A,) + planes.shape[2:]))
+        fam = np.empty((n, A), dtype=np.float64)
+        best = np.full(n, -1, dtype=np.int32)
+        self._check(self._lib.dv_ibank_step_u8(self._ctx, N.u8ptr(flat), n, A, banks.ctypes.data_as(N._i32p), N.f64ptr(fam),
+                                               best.ctypes.data_as(N._i32p)), "dv_ibank_step_u8")
+        return OneValueBatchResults(fam, best, np.zeros(n, dtype=np.uint32))
+
+    def ibank_sense_step_batch(self, x, y, angles, bank_of_member):
+        """infomax_sense_step_batch with member i scored under bank bank_of_member[i] -> OneValueBatchResults: one enqueue and one wait."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        angles = np.ascontiguousarray(angles, dtype=np.float64)
+        if angles.ndim != 2 or len(x) != len(y) or angles.shape[0] != len(x) or angles.shape[0] < 1 or angles.shape[1] < 1:
+            raise ValueError("x[N], y[N] and angles[N, A] expected (N, A >= 1), got shapes %r, %r and %r" % (x.shape, y.shape, angles.shape))
+        n, A = angles.shape
+        banks = self._bank_table(bank_of_member, n, "bank_of_member", self.infomax_banks)
+        fam = np.empty((n, A), dtype=np.float64)
+        best = np.full(n, -1, dtype=np.int32)
+        flags = np.zeros(n, dtype=np.uint32)
+        self._check(self._lib.dv_ibank_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, banks.ctypes.data_as(N._i32p),
+                                                  N.f64ptr(fam), best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)),
+                    "dv_ibank_sense_step")
+        return OneValueBatchResults(fam, best, flags)
+
+    def ibank_read_weights(self, bank):
+        """float64[n_hidden, h*w] of one bank."""
+        bank = self._bank_index(bank, self.infomax_banks)
+        info = self.infomax_info()
+        out = np.empty((max(info["n_hidden"], 1), max(info["n_pixels"], 1)), dtype=np.float64)
+        self._check(self._lib.dv_ibank_read_weights(self._ctx, bank, N.f64ptr(out)), "dv_ibank_read_weights")
+        return out
+
+    def ibank_set_weights(self, bank, weights):
+        bank = self._bank_index(bank, self.infomax_banks)
+        weights = self._ibank_weights(weights, "weights")
+        self._check(self._lib.dv_ibank_set_weights(self._ctx, bank, N.f64ptr(weights)), "dv_ibank_set_weights")
+
+    def ibank_info(self):
+        """dict(n_banks, views_trained int64[n_banks], finite bool[n_banks])."""
+        nb = ctypes.c_int(0)
+        self._check(self._lib.dv_ibank_info(self._ctx, ctypes.byref(nb), None, None), "dv_ibank_info")
+        views = np.zeros(max(nb.value, 1), dtype=np.int64)
+        finite = np.zeros(max(nb.value, 1), dtype=np.int32)
+        self._check(self._lib.dv_ibank_info(self._ctx, None, views.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                            finite.ctypes.data_as(N._i32p)), "dv_ibank_info")
+        return dict(n_banks=nb.value, views_trained=views, finite=finite.astype(bool))
 
     # -- mushroom-body familiarity model: a fixed fan-in and one byte of weight per Kenyon cell (include/dejavu.h: dv_mb_*) --------
     def mb_begin(self, h, w, conn, n_active, channel=2):
@@ -1011,21 +1105,26 @@ class FamiliarityEngine(object):
     # -- memory banks of the mushroom-body model: several memories behind one connectivity (include/dejavu.h: dv_mbank_*) ---------
     mb_banks = 1                 # memories of the model (mbank_set; 1 after mb_begin)
 
-    def _bank_table(self, table, n, what):
-        """`table` as int32[n] with every entry in [0, mb_banks), or ValueError naming `what`: checked before any library call."""
+    def _bank_table(self, table, n, what, n_banks=None):
+        """`table` as int32[n] with every entry in [0, n_banks) (default: mb_banks), or ValueError naming `what`: checked before any
+        library call."""
+        n_banks = self.mb_banks if n_banks is None else n_banks
         arr = np.asarray(table)
+        if arr.shape == (0,):
+            arr = arr.astype(np.int32)                           # (an empty list has no dtype to speak of)
         if arr.dtype.kind not in "iu":
             raise ValueError("%s must hold integers (a bank per entry), got dtype %s" % (what, arr.dtype))
         if arr.shape != (n,):
             raise ValueError("%s must have shape (%d,), got %r" % (what, n, arr.shape))
-        if n and (arr.min() < 0 or arr.max() >= self.mb_banks):
-            bad = np.flatnonzero((arr < 0) | (arr >= self.mb_banks))
-            raise ValueError("%s[%d] = %d outside [0, n_banks = %d)" % (what, bad[0], arr[bad[0]], self.mb_banks))
+        if n and (arr.min() < 0 or arr.max() >= n_banks):
+            bad = np.flatnonzero((arr < 0) | (arr >= n_banks))
+            raise ValueError("%s[%d] = %d outside [0, n_banks = %d)" % (what, bad[0], arr[bad[0]], n_banks))
         return np.ascontiguousarray(arr, dtype=np.int32)
 
-    def _bank_index(self, bank):
-        if isinstance(bank, bool) or not isinstance(bank, (int, np.integer)) or not 0 <= bank < self.mb_banks:
-            raise ValueError("bank must be an integer in [0, n_banks = %d), got %r" % (self.mb_banks, bank))
+    def _bank_index(self, bank, n_banks=None):
+        n_banks = self.mb_banks if n_banks is None else n_banks
+        if isinstance(bank, bool) or not isinstance(bank, (int, np.integer)) or not 0 <= bank < n_banks:
+            raise ValueError("bank must be an integer in [0, n_banks = %d), got %r" % (n_banks, bank))
         return int(bank)
 
     def mbank_set(self, n_banks):

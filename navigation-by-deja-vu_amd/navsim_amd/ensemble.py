@@ -364,25 +364,22 @@ class MushroomEnsemble(_OneValueEnsemble):
                 raise ValueError("MushroomEnsemble does not take an Infomax model: navsim_amd.InfomaxEnsemble steps that one")
 
 
-class MushroomRouteEnsemble(_OneValueEnsemble):
-    """MushroomEnsemble for trials that differ in their TRAINING ROUTE as well (the reference's grid varies training_path_curve on one
-    landscape, scripts/run_experiment.py:57,208): the model's connectivity is shared, and every route has a memory bank of its own
-    (FamiliarityEngine.mbank_set: n_kc bytes a route).  All routes are trained in one device call, and a step scores every running
-    member's headings under its own route's bank in ONE device call (dv_mbank_sense_step), with the bits a lone agent trained on that
-    route alone gives at the same pose.  Made by from_routes.  Members' error metrics stay on the host (the device's path slots hold one
-    path); a member steps with its ensemble only."""
-    _metric = "mushroom"
-    _takes = MushroomEnsemble._takes
-    _batch_call = "mbank_sense_step_batch"
+class _RouteEnsemble(_OneValueEnsemble):
+    """What MushroomRouteEnsemble and InfomaxRouteEnsemble share: trials that differ in their TRAINING ROUTE as well as in their start.
+    The engine's one model holds a bank per route; from_routes trains all routes in one device call (`_train_banks`), and a step scores
+    every running member under its own route's bank in ONE device call (`_batch_call`, which takes the members' banks).  Members' error
+    metrics stay on the host (the device's path slots hold one path); a member steps with its ensemble only."""
     _metrics_on_slots = False
-    _reject_others = MushroomEnsemble._reject_others
+    _one_route = None            # the name of the ensemble whose members share one trained route
+    _info_call = None            # the engine's per-bank info
 
     def __init__(self, agents):
+        name = type(self).__name__
         for a in agents:
             if getattr(a, "memory_bank", None) is None:
-                raise ValueError("MushroomRouteEnsemble takes the members MushroomRouteEnsemble.from_routes makes (agents with a "
-                                 "memory_bank); MushroomEnsemble steps agents that share one trained route")
-        super(MushroomRouteEnsemble, self).__init__(agents)
+                raise ValueError("%s takes the members %s.from_routes makes (agents with a memory_bank); %s steps agents that share one "
+                                 "trained route" % (name, name, self._one_route))
+        super(_RouteEnsemble, self).__init__(agents)
         self._banks = np.array([a.memory_bank for a in agents], dtype=np.int32)
 
     @classmethod
@@ -391,11 +388,16 @@ class MushroomRouteEnsemble(_OneValueEnsemble):
 
     @classmethod
     def from_agent(cls, agent, poses):
-        raise ValueError("MushroomRouteEnsemble is made from routes (from_routes); MushroomEnsemble.from_agent clones a trained agent")
+        raise ValueError("%s is made from routes (from_routes); %s.from_agent clones a trained agent" % (cls.__name__, cls._one_route))
+
+    @staticmethod
+    def _train_banks(eng, n_routes, x, y, headings, bank_of_view):
+        """One bank per route on the engine's fresh model, every view trained into its route's bank in one call -> the views."""
+        raise NotImplementedError
 
     @classmethod
     def from_routes(cls, agent, routes, starts):
-        """`agent`: an UNTRAINED agent of mushroom_familiarity(...) with the GPU sensor model; routes: R arrays float64[n_r, 2];
+        """`agent`: an UNTRAINED agent of the ensemble's model with the GPU sensor model; routes: R arrays float64[n_r, 2];
         starts: iterable of (route_index, (x, y), angle), one member each (the first is `agent` itself, the others copies of it on the
         same engine).  Every route is trained into its own bank, all in one call; member i gets the training_path, training_path_length
         and familiar_scenes of routes[route_index_i], and that route's bank as its `memory_bank`."""
@@ -408,7 +410,7 @@ class MushroomRouteEnsemble(_OneValueEnsemble):
         if eng is None:
             raise ValueError("%s needs agents whose sensor model runs on the GPU (use_gpu_sensor=True)" % cls.__name__)
         if agent.training_path is not None or getattr(agent, "memory_bank", None) is not None:
-            raise ValueError("%s.from_routes takes an UNTRAINED agent: it trains every route into a memory bank of its own" % cls.__name__)
+            raise ValueError("%s.from_routes takes an UNTRAINED agent: it trains every route into a bank of its own" % cls.__name__)
         routes = [np.asarray(r, dtype=np.float64) for r in routes]
         if not routes or any(r.ndim != 2 or r.shape[1] != 2 or len(r) < 2 for r in routes):
             raise ValueError("routes must be one or more arrays float64[n_r, 2] of at least two points each")
@@ -431,8 +433,7 @@ class MushroomRouteEnsemble(_OneValueEnsemble):
         points = np.concatenate(routes)
         bank_of_view = np.repeat(np.arange(len(routes), dtype=np.int32), [len(r) for r in routes])
         model.begin(eng, agent.sensor_dimensions[1], agent.sensor_dimensions[0])
-        eng.mbank_set(len(routes))
-        views = eng.mbank_train_from_poses(points[:, 0], points[:, 1], np.concatenate(headings), bank_of_view)
+        views = cls._train_banks(eng, len(routes), points[:, 0], points[:, 1], np.concatenate(headings), bank_of_view)
         func = model.from_engine(eng, views)
         members = []
         for k, (r, pos, ang) in enumerate(starts):
@@ -455,10 +456,48 @@ class MushroomRouteEnsemble(_OneValueEnsemble):
         return cls(members)
 
     def _device_step(self, idx, xs, ys, angs):
-        results = self.engine.mbank_sense_step_batch(xs, ys, angs, self._banks[idx])
+        results = getattr(self.engine, self._batch_call)(xs, ys, angs, self._banks[idx])
         self._rows = {id(self.agents[i]): results.angle_familiarity[k] for k, i in enumerate(idx)}
         return results
 
     def bank_info(self):
-        """Per bank (route): dict(n_banks, views_trained int64[R], n_depressed int64[R])."""
-        return self.engine.mbank_info()
+        """Per bank (route): the engine's dict of n_banks and arrays of R entries (views_trained, and the model's own figure)."""
+        return getattr(self.engine, self._info_call)()
+
+
+class MushroomRouteEnsemble(_RouteEnsemble):
+    """MushroomEnsemble for trials that differ in their TRAINING ROUTE as well (the reference's grid varies training_path_curve on one
+    landscape, scripts/run_experiment.py:57,208): the model's connectivity is shared, and every route has a memory bank of its own
+    (FamiliarityEngine.mbank_set: n_kc bytes a route).  All routes are trained in one device call, and a step scores every running
+    member's headings under its own route's bank in ONE device call (dv_mbank_sense_step), with the bits a lone agent trained on that
+    route alone gives at the same pose.  Made by from_routes (see _RouteEnsemble)."""
+    _metric = "mushroom"
+    _takes = MushroomEnsemble._takes
+    _batch_call = "mbank_sense_step_batch"
+    _info_call = "mbank_info"                # dict(n_banks, views_trained int64[R], n_depressed int64[R])
+    _one_route = "MushroomEnsemble"
+    _reject_others = MushroomEnsemble._reject_others
+
+    @staticmethod
+    def _train_banks(eng, n_routes, x, y, headings, bank_of_view):
+        eng.mbank_set(n_routes)
+        return eng.mbank_train_from_poses(x, y, headings, bank_of_view)
+
+
+class InfomaxRouteEnsemble(_RouteEnsemble):
+    """InfomaxEnsemble for trials that differ in their TRAINING ROUTE as well, the twin of MushroomRouteEnsemble: every route has a weight
+    bank of its own on the one engine (FamiliarityEngine.ibank_set: n_hidden x h*w doubles a route), every bank begins as the model's own
+    seeded W0, all routes are trained in one device call whose chains advance in lockstep (dv_ibank_train_from_poses), and a step scores
+    every running member's headings under its own route's W in ONE device call (dv_ibank_sense_step), with the bits a lone agent trained
+    on that route alone gives at the same pose.  Made by from_routes (see _RouteEnsemble)."""
+    _metric = "infomax"
+    _takes = InfomaxEnsemble._takes
+    _batch_call = "ibank_sense_step_batch"
+    _info_call = "ibank_info"                # dict(n_banks, views_trained int64[R], finite bool[R])
+    _one_route = "InfomaxEnsemble"
+    _reject_others = InfomaxEnsemble._reject_others
+
+    @staticmethod
+    def _train_banks(eng, n_routes, x, y, headings, bank_of_view):
+        eng.ibank_set(n_routes, eng.infomax_read_weights())          # (bank 0 holds the W0 the model's begin has just drawn)
+        return eng.ibank_train_from_poses(x, y, headings, bank_of_view)

@@ -161,12 +161,20 @@ def reject_mushroom(model, what):
                              "navsim_amd.MushroomEnsemble)" % what)
 
 
+def route_ensemble_name(agent):
+    """The ensemble that steps a banked member of `agent`'s model."""
+    for obj in (agent, getattr(agent, "familiarity_model", None), getattr(agent, "_familiarity_func", None)):
+        if getattr(obj, "metric", None) == "infomax":
+            return "InfomaxRouteEnsemble"
+    return "MushroomRouteEnsemble"
+
+
 def reject_banked(agent, what):
-    """The refusal of every ensemble but navsim_amd.MushroomRouteEnsemble for one of ITS members: the member's route is kept in a memory
-    bank of its own (agent.memory_bank), and the other ensembles' steps score under the model's first bank."""
+    """The refusal of every ensemble but the member's own route ensemble (navsim_amd.MushroomRouteEnsemble, InfomaxRouteEnsemble): the
+    member's route is kept in a bank of its own (agent.memory_bank), and the other ensembles' steps score under the model's first bank."""
     if getattr(agent, "memory_bank", None) is not None:
-        raise ValueError("%s does not take a member of a MushroomRouteEnsemble: its route is kept in memory bank %d of the shared model, "
-                         "and only that ensemble's step scores it there" % (what, agent.memory_bank))
+        raise ValueError("%s does not take a member of a %s: its route is kept in memory bank %d of the shared model, "
+                         "and only that ensemble's step scores it there" % (what, route_ensemble_name(agent), agent.memory_bank))
 
 
 def _one_value_familiarity(metric, channel, device, begin, **extras):

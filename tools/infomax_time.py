@@ -2,7 +2,8 @@
 """Times the Infomax familiarity model (navsim_amd.infomax_familiarity; include/dejavu.h: dv_infomax_*) on GPU 0 and writes
 profiles/infomax_time.json.
 
-    python tools/infomax_time.py [--sides 32,64] [--views 400] [--calls 200] [--reps 5] [--out profiles/infomax_time.json]
+    python tools/infomax_time.py [--sides 32,64] [--views 400] [--calls 200] [--reps 5] [--blocks single,ensemble[,banks]]
+                                 [--out profiles/infomax_time.json]
 
 Per sensor side s (views of s x s, N = M = s*s): microseconds per training view (a dv_infomax_train_u8 call over --views views, the
 upload and the x preparation included, divided by the views) and per scoring call (dv_infomax_score_u8: upload, x preparation, the
@@ -17,6 +18,13 @@ landscape -- microseconds per ensemble step of dv_batch_infomax_sense_step (one 
 loop of dv_infomax_sense_step calls (one per member), the two taken in the same child process in alternating windows; median and
 spread of --reps windows each, and the byte floor 8*M*N of one pass over W at the stream probe beside them.  (The matrix-time floor
 from an fp64 MFMA rate probe is not part of the tool yet.)
+
+Banks block (--blocks banks): per side, (a) training -- 4 routes of --route-views sensed views each (random poses on the synthetic
+landscape) in ONE dv_ibank_train_from_poses call on one engine of 4 banks, against four dv_infomax_train_from_poses calls on four
+engines (what there was before the banks), the two sides in alternating windows of one process, a window being one whole training;
+microseconds from the hipEvent pair of each call (summed over the four) and, beside it, the wall clock around the calls; and (b) the
+step -- the ensemble block's two layouts over 4 banks (dv_ibank_sense_step; member i in bank i % 4) against dv_batch_infomax_sense_step
+at the same poses on one W.  Medians and spreads of --reps windows.  A block that is not measured keeps the rows the file holds.
 
 Every GPU measurement runs in a child process of its own under a time limit, and nothing more is started on the GPU after one
 that failed."""
@@ -129,6 +137,106 @@ def ensemble_child(side, n_calls, reps, eta):
     print(json.dumps(out))
 
 
+N_BANKS = 4
+
+
+def banks_child(side, n_views, n_calls, reps, eta):
+    """The banks block of one size on the GPU -> one JSON line on stdout."""
+    from navsim_amd import NavBySceneFamiliarity, infomax_familiarity, synth
+    from navsim_amd.util import infomax_initial_weights
+    N = side * side
+    land = synth.synth_landscape(3, 600, 4)
+    W0 = infomax_initial_weights(N, N, 0)
+    out = dict(side=side, N=N, M=N, weight_bytes=8 * N * N, n_banks=N_BANKS, calls_per_window=n_calls, layouts=[])
+
+    def engine(A):
+        agent = NavBySceneFamiliarity(land, (side, side), 1.0, n_test_angles=A, familiarity_model=infomax_familiarity(learning_rate=eta))
+        return agent, agent._engine                              # (landscape and sensor attached)
+
+    # (a) training: N_BANKS routes in one banked call on one engine, against one call per route on an engine each
+    engines = [engine(HEADINGS[0])[1] for _ in range(N_BANKS)]
+    rng = np.random.default_rng(side + 7)
+    total = N_BANKS * n_views
+    xs, ys, angs = rng.uniform(150, 450, total), rng.uniform(150, 450, total), rng.uniform(0, 2 * np.pi, total)
+    bank_of = np.repeat(np.arange(N_BANKS, dtype=np.int32), n_views)
+
+    def one_call():
+        eng = engines[0]
+        eng.infomax_begin(side, side, W0, 2, eta)
+        eng.ibank_set(N_BANKS, W0)
+        w0 = time.perf_counter()
+        eng.timer_start()
+        eng.ibank_train_from_poses(xs, ys, angs, bank_of, want_views=False)
+        return eng.timer_stop() * 1e3, (time.perf_counter() - w0) * 1e6
+
+    def call_per_route():
+        t = wall = 0.0
+        for r, eng in enumerate(engines):
+            eng.infomax_begin(side, side, W0, 2, eta)
+            sl = slice(r * n_views, (r + 1) * n_views)
+            w0 = time.perf_counter()
+            eng.timer_start()
+            eng.infomax_train_from_poses(xs[sl], ys[sl], angs[sl], want_views=False)
+            t += eng.timer_stop() * 1e3
+            wall += (time.perf_counter() - w0) * 1e6
+        return t, wall
+
+    one_call()                                                    # warm-up of both (code load, clocks, the buffers)
+    banked_w = [engines[0].ibank_read_weights(r) for r in range(N_BANKS)]
+    call_per_route()
+    assert all(np.array_equal(banked_w[r], engines[r].infomax_read_weights()) for r in range(N_BANKS))      # the same bits
+    assert all(np.isfinite(w).all() for w in banked_w)
+    t1, t4, w1, w4 = [], [], [], []
+    for _ in range(reps):                                         # alternating windows
+        a, b = one_call()
+        t1.append(a)
+        w1.append(b)
+        a, b = call_per_route()
+        t4.append(a)
+        w4.append(b)
+    out["train"] = dict(routes=N_BANKS, views_per_route=n_views, one_banked_call_us=spread(t1), call_per_route_us=spread(t4),
+                        per_route_over_banked=round(float(np.median(t4) / np.median(t1)), 3),
+                        one_banked_call_wall_us=spread(w1), call_per_route_wall_us=spread(w4),
+                        per_route_over_banked_wall=round(float(np.median(w4) / np.median(w1)), 3),
+                        banked_below_call_per_route=bool(np.median(t1) < np.median(t4)),
+                        kernel_launches=dict(one_banked_call=3 * n_views + 4, call_per_route=N_BANKS * (3 * n_views + 4)))
+    for e in engines:
+        e.close()
+    # (b) the step: the ensemble block's layouts over N_BANKS banks against the same poses on one W
+    for n, A in ENSEMBLES:
+        agent, eng = engine(A)
+        eng.infomax_begin(side, side, W0, 2, eta)
+        eng.ibank_set(N_BANKS, W0)
+        rng = np.random.default_rng(n * 100 + A)
+        xs, ys = rng.uniform(150, 450, n), rng.uniform(150, 450, n)
+        angs = (rng.uniform(0, 2 * np.pi, n)[:, None] + agent.angle_offsets[None, :]) % (2 * np.pi)
+        banks = (np.arange(n) % N_BANKS).astype(np.int32)
+
+        def banked():
+            eng.timer_start()
+            for _ in range(n_calls):
+                res = eng.ibank_sense_step_batch(xs, ys, angs, banks)
+            return eng.timer_stop() * 1e3 / n_calls, res          # us per ensemble step
+
+        def unbanked():
+            eng.timer_start()
+            for _ in range(n_calls):
+                res = eng.infomax_sense_step_batch(xs, ys, angs)
+            return eng.timer_stop() * 1e3 / n_calls, res
+
+        _, res = banked()
+        _, one = unbanked()
+        assert not res.flags.any() and np.array_equal(res.angle_familiarity, one.angle_familiarity)       # (every bank holds W0)
+        tb, tu = [], []
+        for _ in range(reps):                                     # alternating windows
+            tb.append(banked()[0])
+            tu.append(unbanked()[0])
+        out["layouts"].append(dict(members=n, headings=A, banked_us_per_step=spread(tb), unbanked_us_per_step=spread(tu),
+                                   banked_over_unbanked=round(float(np.median(tb) / np.median(tu)), 3)))
+        eng.close()
+    print(json.dumps(out))
+
+
 def cpu_row(side, n_views, n_calls, eta):
     """The NumPy restatement on this host: wall clock."""
     from tests import helpers_infomax as H
@@ -158,7 +266,9 @@ def main():
                     help="the rule must stay finite on the tool's 5-level noise views: 0.01 overflows at 64x64 (the time does not depend on it)")
     ap.add_argument("--limit", type=int, default=240, help="seconds allowed to each GPU child")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "infomax_time.json"))
-    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and score_u8), ensemble")
+    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and score_u8), ensemble, banks")
+    ap.add_argument("--route-views", type=int, default=200, help="sensed views of each of the banks block's 4 routes")
+    ap.add_argument("--banks-child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--ensemble-calls", type=int, default=30, help="ensemble steps per timed window")
     ap.add_argument("--child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--ensemble-child", type=int, default=0, help=argparse.SUPPRESS)
@@ -169,9 +279,27 @@ def main():
     if args.ensemble_child:
         ensemble_child(args.ensemble_child, args.ensemble_calls, args.reps, args.learning_rate)
         return 0
+    if args.banks_child:
+        banks_child(args.banks_child, args.route_views, args.ensemble_calls, args.reps, args.learning_rate)
+        return 0
     blocks = args.blocks.split(",")
     result = dict(tool="tools/infomax_time.py", timer="hipEvent pair (dv_timer_start/stop), median of %d windows after a warm-up" % args.reps,
-                  learning_rate=args.learning_rate, blocks=blocks, sizes=[], ensembles=[])
+                  learning_rate=args.learning_rate, blocks=blocks, sizes=[], ensembles=[], banks=[])
+    if os.path.exists(args.out):                                  # a block that is not measured keeps its rows
+        with open(args.out) as f:
+            kept = json.load(f)
+        for block, key in (("single", "sizes"), ("ensemble", "ensembles"), ("banks", "banks")):
+            if block not in blocks:
+                result[key] = kept.get(key, [])
+    for side in [int(x) for x in args.sides.split(",")] if "banks" in blocks else []:
+        cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--banks-child", str(side),
+               "--route-views", str(args.route_views), "--ensemble-calls", str(args.ensemble_calls), "--reps", str(args.reps),
+               "--learning-rate", str(args.learning_rate)]
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, universal_newlines=True)
+        if p.returncode != 0:
+            print("GPU measurement of the banks of side %d ended with status %d: nothing more is run" % (side, p.returncode), file=sys.stderr)
+            return p.returncode
+        result["banks"].append(json.loads(p.stdout.strip().splitlines()[-1]))
     for side in [int(x) for x in args.sides.split(",")] if "ensemble" in blocks else []:
         cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--ensemble-child", str(side),
                "--ensemble-calls", str(args.ensemble_calls), "--reps", str(args.reps), "--learning-rate", str(args.learning_rate)]

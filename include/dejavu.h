@@ -289,6 +289,34 @@ int dv_path_slots(dv_ctx *ctx, int n_slots);
 int dv_path_error_batch(dv_ctx *ctx, const int32_t *slots, const double *x, const double *y, int n, double reach, double *nearest);
 int dv_path_coverage_slot(dv_ctx *ctx, int slot, uint8_t *out, int64_t n);
 int dv_path_reset_slot(dv_ctx *ctx, int slot);
+/*
+ * The same metrics for an ensemble whose trials have training routes of their OWN (the reference's grid varies training_path_curve,
+ * scripts/run_experiment.py:57,208).  These calls have buffers of their own: they leave the calls above and their results alone, and
+ * the calls above leave them alone.
+ *   dv_path_routes_set       xy = double[first[n_routes]][2], all routes' points, one route after the other; first = int64[n_routes + 1],
+ *                            rising from first[0] = 0 (every route has at least one point).  NULL or n_routes = 0 detaches.  Drops the
+ *                            slots and their marks.
+ *   dv_path_routes_slots     slot j gets coverage marks of its own for route route_of_slot[j]: exactly that route's length in bytes,
+ *                            cleared; the arrays lie back to back without padding.  n_slots = 0 frees them.
+ *   dv_path_routes_error     update_error for n entries at once: entry i is slot slots[i] standing at (x[i], y[i]) with its OWN
+ *                            reach[i].  nearest[i] = the distance to the nearest point of that slot's route, in the reference's
+ *                            double arithmetic; the slot's marks get `dist <= reach[i]` OR-ed in.  Entries are independent, and a
+ *                            slot may occur more than once.  Synchronous: one upload of the entry table, one kernel launch per
+ *                            65 535 entries, one copy back and one wait, whatever n is.
+ *   dv_path_routes_coverage  copies slot's marks out (uint8[n], 0/1); n must be the length of the slot's route.
+ *   dv_path_routes_reset     clears one slot's marks, or all with slot < 0.
+ *   dv_path_routes_info      the counts: routes, slots, points of all routes (any pointer may be NULL).
+ * Every route_of_slot and slots entry is checked before anything is enqueued: DV_ERR_INVALID names the first bad one, and nothing
+ * is marked or reallocated.  Without routes (or, for error / coverage / reset, without slots): DV_ERR_STATE.  On DV_ERR_OOM routes,
+ * slots and marks stay as they were.
+ */
+int dv_path_routes_set(dv_ctx *ctx, const double *xy, const int64_t *first, int n_routes);
+int dv_path_routes_slots(dv_ctx *ctx, const int32_t *route_of_slot, int n_slots);
+int dv_path_routes_error(dv_ctx *ctx, const int32_t *slots, const double *x, const double *y, const double *reach, int64_t n,
+                         double *nearest);
+int dv_path_routes_coverage(dv_ctx *ctx, int slot, uint8_t *out, int64_t n);
+int dv_path_routes_reset(dv_ctx *ctx, int slot);
+int dv_path_routes_info(dv_ctx *ctx, int *n_routes, int *n_slots, int64_t *n_points);
 
 /* ---- scoring ----------------------------------------------------------- */
 /* func(scene, fambuf) of util.pyx:14-20: fambuf[f] for one patch uint8[h,w,3] against every local view. */

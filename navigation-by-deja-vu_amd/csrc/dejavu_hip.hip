@@ -286,6 +286,15 @@ struct dv_ctx {
     unsigned long long err_enq = 0, err_deq = 0;   // answers requested / collected
     int agent_pending = 0;                    // headings of the agent step begun and not yet ended (dv_agent_step_begin / _end)
     bool err_on_main = false;                 // the last metric computation rode on the step's own stream (dv_agent_step)
+    // the same metrics against several routes (dejavu_path_routes.inl: dv_path_routes_*); independent of the one path above
+    double* rt_xy = nullptr;                  // [rt_first.back()][2]: the routes' points, one route after the other
+    std::vector<int64_t> rt_first;            // [routes + 1]: route r is points rt_first[r] .. rt_first[r + 1]; empty: no routes set
+    unsigned char* rt_cover = nullptr;        // the slots' coverage marks, ragged and back to back
+    std::vector<int32_t> rt_slot_route;       // [slots]: the route of every slot
+    std::vector<int64_t> rt_slot_first;       // [slots + 1]: slot j's marks are bytes rt_slot_first[j] .. rt_slot_first[j + 1] of rt_cover
+    unsigned char* rt_tab = nullptr;          // a dv_path_routes_error call's entries, then its minima, on the device
+    unsigned char* rt_tab_host = nullptr;     // ... and in pinned host memory
+    size_t rt_tab_cap = 0, rt_tab_host_cap = 0;   // bytes
 
     // heat-equation field of the landscape generator (dejavu_diffuse.inl): independent of everything above
     double* d_diff[2] = {nullptr, nullptr};   // [n][n] each; d_diff[diff_cur] is the current field
@@ -378,6 +387,7 @@ static void use_set(dv_ctx* c, int which);
 static void diffuse_free(dv_ctx* c);
 static void infomax_free(dv_ctx* c);
 static void mb_free(dv_ctx* c);
+static void path_routes_free(dv_ctx* c);
 static void free_library(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
     use_set(c, 0);
@@ -477,6 +487,7 @@ extern "C" void dv_destroy(dv_ctx* c) {
     diffuse_free(c);
     infomax_free(c);
     mb_free(c);
+    path_routes_free(c);
     if (c->d_land) (void)hipFree(c->d_land);
     if (c->d_lut) (void)hipFree(c->d_lut);
     if (c->d_poses) (void)hipFree(c->d_poses);
@@ -3680,4 +3691,5 @@ extern "C" int dv_stream_read_gbps(dv_ctx* c, int64_t n_bytes, int iters, double
 #include "dejavu_diffuse.inl"   // dv_diffuse_*: the landscape generator's heat equation (kernels and host side)
 #include "dejavu_infomax.inl"   // dv_infomax_*: the Infomax familiarity model (kernels and host side)
 #include "dejavu_mushroom.inl"  // dv_mb_*: the mushroom-body familiarity model (kernels and host side)
+#include "dejavu_path_routes.inl"   // dv_path_routes_*: the error / coverage metrics against several routes (host side)
 #include "dejavu_group.inl"     // dv_group_*: one process, several devices -- host logic above the C ABI

@@ -2700,6 +2700,57 @@ k_path_error_batch(PathBatchArgs pa) {
     }
 }
 
+// update_error for the members of an ensemble whose trials have training routes of their OWN (dv_path_routes_error): the routes lie back
+// to back in one array, the slots' coverage arrays -- each as long as its route, no padding -- back to back in another, and entry j of
+// a table on the device says where its route and its marks begin, how long they are, where the member stands and how far it reaches.
+// Block (b, j) takes the points [1024 (b + t gridDim.x), + 1024) of entry j's route, t = 0, 1, ...: the grid is as wide as the longest
+// route among the call's entries needs (256 blocks at the most), so a block whose first point lies past its own entry's route leaves
+// at once -- all of it: the test is the same for every thread, and it comes before the barrier.  The arithmetic is path_error_block's;
+// the minimum is folded as the bit pattern of a non-negative double (bit order = value order) through the wave, the four waves and one
+// integer atomicMin per block, so it does not depend on the order the blocks arrive in.  Two entries of a call may share a slot: both
+// store the same byte value, 1.
+constexpr int kPathRoutePoints = 1024;        // points of a block's trip: 4 per thread
+struct PathRouteEntry { long long first, n, cover; double x, y, reach; };
+__global__ void __launch_bounds__(256)
+k_path_error_routes(const double* __restrict__ xy, unsigned char* __restrict__ marks, const PathRouteEntry* __restrict__ tab,
+                    unsigned long long* __restrict__ minkey, long long j0) {
+    __shared__ unsigned long long wmin[4];
+    const long long j = j0 + blockIdx.y;
+    const PathRouteEntry e = tab[j];
+    if ((long long)blockIdx.x * kPathRoutePoints >= e.n) return;
+    const double x = e.x, y = e.y, reach = e.reach;
+    const double* __restrict__ pts = xy + 2 * e.first;
+    unsigned char* __restrict__ cover = marks + e.cover;
+    unsigned long long key = ~0ull;
+    for (long long base = (long long)blockIdx.x * kPathRoutePoints; base < e.n; base += (long long)gridDim.x * kPathRoutePoints) {
+#pragma unroll
+        for (int k = 0; k < kPathRoutePoints / 256; ++k) {
+            const long long i = base + k * 256 + threadIdx.x;
+            if (i < e.n) {
+                double dx = pts[2 * i] - x, dy = pts[2 * i + 1] - y;
+                dx *= dx;
+                dy *= dy;
+                const double dist = sqrt(dx + dy);
+                if (dist <= reach) cover[i] = 1;
+                const unsigned long long kk = (unsigned long long)__double_as_longlong(dist);     // dist >= 0: bit order = value order
+                key = kk < key ? kk : key;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(key, o);
+        key = other < key ? other : key;
+    }
+    if ((threadIdx.x & 63) == 0) wmin[threadIdx.x >> 6] = key;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long m = wmin[0];
+        for (int i = 1; i < 4; ++i) m = wmin[i] < m ? wmin[i] : m;
+        atomicMin(&minkey[j], m);
+    }
+}
+
 struct PoseSet { Pose p[kMaxHeadings]; };
 
 template <int MODE>

@@ -396,7 +396,7 @@ class NavBySceneFamiliarity(object):
             self._host_coverage = np.zeros(len(self.training_path), dtype=bool)
             if getattr(self, "_metric_slot", None) is not None:
                 self._ens._drop_errors(self)
-                self._engine.path_reset_slot(self._metric_slot)
+                self._ens._reset_marks(self)                     # (the ensemble knows which of the engine's slots are its members')
             elif getattr(self, "_metrics_on_device", False):
                 self._engine.path_reset()
 
@@ -451,7 +451,7 @@ class NavBySceneFamiliarity(object):
     def _coverage_array(self):
         if getattr(self, "_metric_slot", None) is not None and self.training_path is not None:
             self._ens._flush_errors()
-            return self._engine.path_coverage_slot(self._metric_slot, len(self.training_path))
+            return self._ens._read_marks(self)
         if getattr(self, "_metrics_on_device", False) and self.training_path is not None:
             self._collect_errors()
             return self._engine.path_coverage(len(self.training_path))

@@ -782,6 +782,125 @@ class FamiliarityEngine(object):
     def path_reset_slot(self, slot=-1):
         self._check(self._lib.dv_path_reset_slot(self._ctx, int(slot)), "dv_path_reset_slot")
 
+    # -- the same metrics against several routes: a path per route, a coverage array per slot (include/dejavu.h: dv_path_routes_*) ----
+    _route_first = None          # int64[R + 1]: the bounds of the routes set (path_routes_set); None: no routes
+    _route_of_slot = None        # int32[n_slots]: the route of every slot (path_routes_slots); None: no slots
+
+    @staticmethod
+    def _route_ints(table, what, hi, of):
+        """`table` as int32[n] with every entry in [0, hi), or ValueError naming `what`: checked before any library call.  hi = None:
+        there is nothing to index yet, and the library answers DV_ERR_STATE."""
+        arr = np.asarray(table)
+        if arr.shape == (0,):
+            arr = arr.astype(np.int32)                           # (an empty list has no dtype to speak of)
+        if arr.dtype.kind not in "iu":
+            raise ValueError("%s must hold integers, got dtype %s" % (what, arr.dtype))
+        if arr.ndim != 1:
+            raise ValueError("%s must have one dimension, got shape %r" % (what, arr.shape))
+        if hi is not None and len(arr) and (arr.min() < 0 or arr.max() >= hi):
+            bad = np.flatnonzero((arr < 0) | (arr >= hi))
+            raise ValueError("%s[%d] = %d outside [0, %s = %d)" % (what, bad[0], arr[bad[0]], of, hi))
+        return np.ascontiguousarray(arr, dtype=np.int32)
+
+    def path_routes_set(self, routes, first=None):
+        """routes: a sequence of R arrays float64[n_r, 2] (n_r >= 1) -- or, with `first` (integers [R + 1], rising from 0), all routes'
+        points in one float64[first[-1], 2].  None detaches.  Drops the slots and their marks."""
+        if routes is None:
+            self._check(self._lib.dv_path_routes_set(self._ctx, None, None, 0), "dv_path_routes_set")
+            self._route_first = self._route_of_slot = None
+            return
+        if first is None:
+            parts = []
+            for r, route in enumerate(routes):
+                part = np.asarray(route)
+                if part.dtype != np.float64 or part.ndim != 2 or part.shape[1] != 2 or len(part) < 1:
+                    raise ValueError("routes[%d] must be float64[n, 2] with n >= 1, got %s%r" % (r, part.dtype, part.shape))
+                parts.append(part)
+            if not parts:
+                raise ValueError("routes must hold at least one route")
+            first = np.cumsum([0] + [len(p) for p in parts])
+            pts = np.ascontiguousarray(np.concatenate(parts))
+        else:
+            pts = np.asarray(routes)
+            if pts.dtype != np.float64 or pts.ndim != 2 or pts.shape[1] != 2:
+                raise ValueError("the routes' points must be float64[n, 2], got %s%r" % (pts.dtype, pts.shape))
+            pts = np.ascontiguousarray(pts)
+        bounds = np.asarray(first)
+        if bounds.dtype.kind not in "iu" or bounds.ndim != 1 or len(bounds) < 2:
+            raise ValueError("first must hold integers [R + 1] with R >= 1, got %s%r" % (bounds.dtype, bounds.shape))
+        bounds = np.ascontiguousarray(bounds, dtype=np.int64)
+        if bounds[0] != 0:
+            raise ValueError("first[0] must be 0, got %d" % bounds[0])
+        if (np.diff(bounds) < 1).any():
+            r = int(np.flatnonzero(np.diff(bounds) < 1)[0])
+            raise ValueError("first must rise: first[%d] = %d after first[%d] = %d (a route has at least one point)"
+                             % (r + 1, bounds[r + 1], r, bounds[r]))
+        if bounds[-1] != len(pts):
+            raise ValueError("first[-1] = %d, but there are %d points" % (bounds[-1], len(pts)))
+        self._check(self._lib.dv_path_routes_set(self._ctx, N.f64ptr(pts), N.i64ptr(bounds), len(bounds) - 1), "dv_path_routes_set")
+        self._route_first, self._route_of_slot = bounds, None
+
+    def path_routes_slots(self, route_of_slot):
+        """Slot j gets coverage marks of its own for route route_of_slot[j], cleared (what the slots held is dropped).  An empty table,
+        or None, frees them."""
+        table = self._route_ints([] if route_of_slot is None else route_of_slot, "route_of_slot",
+                                 None if self._route_first is None else len(self._route_first) - 1, "n_routes")
+        self._check(self._lib.dv_path_routes_slots(self._ctx, table.ctypes.data_as(N._i32p), len(table)), "dv_path_routes_slots")
+        self._route_of_slot = table if len(table) else None
+
+    def path_routes_error(self, slots, xs, ys, reach):
+        """update_error (NavBySceneFamiliarity.py:252-276) for n entries at once, each against ITS slot's route and with its OWN reach:
+        float64[n] of the distances to the nearest point of each entry's route; the slots' marks updated."""
+        slots = self._route_ints(slots, "slots", None if self._route_of_slot is None else len(self._route_of_slot), "n_slots")
+        n = len(slots)
+        vals = []
+        for name, v in (("xs", xs), ("ys", ys), ("reach", reach)):
+            arr = np.asarray(v)
+            if arr.shape == (0,):
+                arr = arr.astype(np.float64)
+            if arr.dtype != np.float64:
+                raise ValueError("%s must be float64, got dtype %s" % (name, arr.dtype))
+            if arr.shape != (n,):
+                raise ValueError("%s must have shape (%d,), one per entry of slots, got %r" % (name, n, arr.shape))
+            vals.append(np.ascontiguousarray(arr))
+        out = np.empty(n, dtype=np.float64)
+        self._check(self._lib.dv_path_routes_error(self._ctx, slots.ctypes.data_as(N._i32p), N.f64ptr(vals[0]), N.f64ptr(vals[1]),
+                                                   N.f64ptr(vals[2]), n, N.f64ptr(out)), "dv_path_routes_error")
+        return out
+
+    def _route_slot(self, slot):
+        n_slots = None if self._route_of_slot is None else len(self._route_of_slot)
+        if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)) or slot < 0 or (n_slots is not None and slot >= n_slots):
+            raise ValueError("slot must be an integer in [0, n_slots%s), got %r" % ("" if n_slots is None else " = %d" % n_slots, slot))
+        return int(slot)
+
+    def path_routes_coverage(self, slot, n):
+        """bool[n]: the marks of `slot`; n must be the length of the slot's route."""
+        slot = self._route_slot(slot)
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+            raise ValueError("n must be the length of slot %d's route, got %r" % (slot, n))
+        if self._route_of_slot is not None:
+            r = self._route_of_slot[slot]
+            length = int(self._route_first[r + 1] - self._route_first[r])
+            if n != length:
+                raise ValueError("n must be %d, the length of slot %d's route, got %r" % (length, slot, n))
+        out = np.empty(int(n), dtype=np.uint8)
+        self._check(self._lib.dv_path_routes_coverage(self._ctx, slot, N.u8ptr(out), int(n)), "dv_path_routes_coverage")
+        return out.astype(bool)
+
+    def path_routes_reset(self, slot=-1):
+        """Clears the marks of one slot, or of all (slot < 0)."""
+        if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)):
+            raise ValueError("slot must be an integer, got %r" % (slot,))
+        slot = self._route_slot(slot) if slot >= 0 else -1
+        self._check(self._lib.dv_path_routes_reset(self._ctx, slot), "dv_path_routes_reset")
+
+    def path_routes_info(self):
+        """dict(n_routes, n_slots, n_points), as the library counts them."""
+        nr, ns, npts = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+        self._check(self._lib.dv_path_routes_info(self._ctx, ctypes.byref(nr), ctypes.byref(ns), ctypes.byref(npts)), "dv_path_routes_info")
+        return dict(n_routes=nr.value, n_slots=ns.value, n_points=npts.value)
+
     def stream_read_gbps(self, n_bytes=1 << 30, iters=10):
         g = ctypes.c_double(0)
         self._check(self._lib.dv_stream_read_gbps(self._ctx, int(n_bytes), int(iters), ctypes.byref(g)),

@@ -87,9 +87,7 @@ class NavEnsemble(object):
         if not self._pending:
             return
         pend, self._pending = self._pending, []
-        a0 = pend[0][0]
-        nearest = self.engine.path_error_batch([a._metric_slot for a, _, _ in pend], [x for _, x, _ in pend], [y for _, _, y in pend],
-                                               a0.coverage_threshold_factor * a0.step_size)
+        nearest = self._metrics_call(pend)
         for (a, _, _), d in zip(pend, nearest.tolist()):
             try:
                 a._take_error(d)
@@ -97,6 +95,20 @@ class NavEnsemble(object):
                 if a is raise_for:
                     raise
                 self._too_far[id(a)] = e
+
+    # What a member's slot on the device is asked: the members' agents go through these, so that every kind of ensemble issues the
+    # engine calls of ITS slots (here: the one training path's, dv_path_slots).
+    def _metrics_call(self, pend):
+        """update_error of the (member, x, y) of `pend` in one device call -> the distances to the nearest training point."""
+        a0 = pend[0][0]
+        return self.engine.path_error_batch([a._metric_slot for a, _, _ in pend], [x for _, x, _ in pend], [y for _, _, y in pend],
+                                            a0.coverage_threshold_factor * a0.step_size)
+
+    def _read_marks(self, agent):
+        return self.engine.path_coverage_slot(agent._metric_slot, len(agent.training_path))
+
+    def _reset_marks(self, agent):
+        self.engine.path_reset_slot(agent._metric_slot)
 
     @classmethod
     def from_agent(cls, agent, poses, chem_weights=None):
@@ -367,20 +379,66 @@ class MushroomEnsemble(_OneValueEnsemble):
 class _RouteEnsemble(_OneValueEnsemble):
     """What MushroomRouteEnsemble and InfomaxRouteEnsemble share: trials that differ in their TRAINING ROUTE as well as in their start.
     The engine's one model holds a bank per route; from_routes trains all routes in one device call (`_train_banks`), and a step scores
-    every running member under its own route's bank in ONE device call (`_batch_call`, which takes the members' banks).  Members' error
-    metrics stay on the host (the device's path slots hold one path); a member steps with its ensemble only."""
-    _metrics_on_slots = False
+    every running member under its own route's bank in ONE device call (`_batch_call`, which takes the members' banks).  A member steps
+    with its ensemble only.
+
+    Members' error metrics (update_error, :252-276): metrics="host", the default, leaves them to every member's own NumPy pass over its
+    route.  metrics="device" sets the members' routes on the engine once (path_routes_set), gives every member a slot of coverage marks
+    as long as its own route (path_routes_slots, in member order), and takes the metrics of all members that stepped in ONE
+    path_routes_error call per ensemble step -- every member with its own coverage_threshold_factor * step_size; the numbers are the
+    host's, bit for bit, and "too far from the path" stops a member in the same step, before it marks anything (a member whose
+    max_distance_to_training_path is below its coverage reach has its marks taken in a second call: _metrics_call)."""
+    _metrics_on_slots = False    # (NavEnsemble's slots hold ONE training path: the routed slots are made below)
     _one_route = None            # the name of the ensemble whose members share one trained route
     _info_call = None            # the engine's per-bank info
+    METRICS = ("host", "device")
 
-    def __init__(self, agents):
+    def __init__(self, agents, metrics="host"):
         name = type(self).__name__
+        if metrics not in self.METRICS:
+            raise ValueError("metrics must be one of %r, got %r" % (self.METRICS, metrics))
         for a in agents:
             if getattr(a, "memory_bank", None) is None:
                 raise ValueError("%s takes the members %s.from_routes makes (agents with a memory_bank); %s steps agents that share one "
                                  "trained route" % (name, name, self._one_route))
         super(_RouteEnsemble, self).__init__(agents)
         self._banks = np.array([a.memory_bank for a in agents], dtype=np.int32)
+        self.metrics = metrics
+        if metrics == "device":
+            routes, route_of = [], []                              # the members' routes, each once, in the order the members bring them
+            for a in self.agents:
+                at = [k for k, r in enumerate(routes) if r is a.training_path]
+                if not at:
+                    routes.append(a.training_path)
+                route_of.append(at[0] if at else len(routes) - 1)
+            self.engine.path_routes_set(routes)
+            self.engine.path_routes_slots(route_of)
+            for j, a in enumerate(self.agents):
+                a._metric_slot, a._ens = j, self
+
+    def _metrics_call(self, pend):
+        slots = np.array([a._metric_slot for a, _, _ in pend], dtype=np.int32)
+        xs = np.array([x for _, x, _ in pend], dtype=np.float64)
+        ys = np.array([y for _, _, y in pend], dtype=np.float64)
+        reach = np.array([a.coverage_threshold_factor * a.step_size for a, _, _ in pend], dtype=np.float64)
+        # The reference stops a member that is too far BEFORE it marks anything (:264-271).  Where max_distance_to_training_path is at
+        # least the reach that needs no care: too far is then out of reach of every point.  A member whose limit is below its reach
+        # sends a reach that marks nothing, and its marks follow in a second call once its distance is known to be within the limit.
+        limit = np.array([a.max_distance_to_training_path for a, _, _ in pend], dtype=np.float64)
+        late = limit < reach
+        if not late.any():
+            return self.engine.path_routes_error(slots, xs, ys, reach)
+        nearest = self.engine.path_routes_error(slots, xs, ys, np.where(late, -1.0, reach))
+        mark = late & (nearest <= limit)
+        if mark.any():
+            self.engine.path_routes_error(slots[mark], xs[mark], ys[mark], reach[mark])
+        return nearest
+
+    def _read_marks(self, agent):
+        return self.engine.path_routes_coverage(agent._metric_slot, len(agent.training_path))
+
+    def _reset_marks(self, agent):
+        self.engine.path_routes_reset(agent._metric_slot)
 
     @classmethod
     def _reject_banked(cls, agent):
@@ -400,8 +458,17 @@ class _RouteEnsemble(_OneValueEnsemble):
         """`agent`: an UNTRAINED agent of the ensemble's model with the GPU sensor model; routes: R arrays float64[n_r, 2];
         starts: iterable of (route_index, (x, y), angle), one member each (the first is `agent` itself, the others copies of it on the
         same engine).  Every route is trained into its own bank, all in one call; member i gets the training_path, training_path_length
-        and familiar_scenes of routes[route_index_i], and that route's bank as its `memory_bank`."""
+        and familiar_scenes of routes[route_index_i], and that route's bank as its `memory_bank`.  The members' error metrics run on
+        the host; from_routes_with chooses."""
+        return cls.from_routes_with(agent, routes, starts)
+
+    @classmethod
+    def from_routes_with(cls, agent, routes, starts, metrics="host"):
+        """from_routes with the members' error metrics on the host ("host": every member's own NumPy pass, as from_routes) or on the
+        device ("device": all members' in one call per ensemble step, each against its own route; see the class)."""
         import copy
+        if metrics not in cls.METRICS:
+            raise ValueError("metrics must be one of %r, got %r" % (cls.METRICS, metrics))
         cls._reject_others(agent)
         model = getattr(agent, "familiarity_model", None)
         if getattr(model, "metric", None) != cls._metric:
@@ -447,13 +514,13 @@ class _RouteEnsemble(_OneValueEnsemble):
             a.angle_familiarity = np.full(agent.n_test_angles, np.nan)
             a.scene_familiarity = np.zeros(len(route), dtype=np.float64)
             a._scene_is_inf = False
-            a._metrics_on_device = False                         # (update_error's NumPy branch: the device's slots hold one path)
+            a._metrics_on_device = False                         # (update_error's NumPy branch, until the ensemble gives it a slot)
             a._metric_slot, a._ens, a._spec = None, None, None
             a.step_familiarity = np.inf
             a.position, a.angle = pos, ang
             a.reset_error()
             members.append(a)
-        return cls(members)
+        return cls(members, metrics=metrics)
 
     def _device_step(self, idx, xs, ys, angs):
         results = getattr(self.engine, self._batch_call)(xs, ys, angs, self._banks[idx])

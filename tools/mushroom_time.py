@@ -2,7 +2,7 @@
 """Times the mushroom-body familiarity model (navsim_amd.mushroom_familiarity; include/dejavu.h: dv_mb_*) on GPU 0 and writes
 profiles/mushroom_time.json.
 
-    python tools/mushroom_time.py [--sides 32,64] [--views 1000] [--calls 200] [--reps 5] [--blocks single,ensemble[,banks]]
+    python tools/mushroom_time.py [--sides 32,64] [--views 1000] [--calls 200] [--reps 5] [--blocks single,ensemble[,banks][,metrics]]
                                   [--out profiles/mushroom_time.json]
 
 Per sensor side s (views of s x s) with K = 20000 Kenyon cells, fan-in 10 and 200 firing cells: microseconds per agent step
@@ -23,6 +23,13 @@ microseconds per ensemble step of dv_mbank_sense_step and of dv_batch_mb_sense_s
 yardstick) at the same poses, alternating windows in the same child process; their ratio is banked_over_unbanked.  And training: 4
 routes of --views views each in ONE dv_mbank_train_from_poses call on one engine, against four dv_mb_train_from_poses calls on four
 engines (the sum of the four engines' own timers).
+
+Metrics block (--blocks metrics): MushroomRouteEnsemble of 4 routes x 8 members x 16 headings at 32x32 views, made twice in one child
+process -- from_routes_with(metrics="host"), every member's update_error a NumPy pass over its own route, and metrics="device", all
+members' in one dv_path_routes_error call -- and stepped from the same starts, so both walk the same poses: WALL-CLOCK microseconds per
+ens.step_forward(), Python included, in alternating windows of --ensemble-calls steps, for routes of about 3 500 points (a grid trial's)
+and of about 50 000 (the sin path's arclen is set to reach the count); their ratio is host_over_device.  And the path_routes_error call
+alone, at the members' last positions.
 
 A block that is not measured keeps the rows it has in the output file.
 
@@ -227,6 +234,70 @@ def banks_child(side, n_views, n_calls, reps):
     print(json.dumps(out))
 
 
+METRIC_ROUTES, METRIC_MEMBERS, METRIC_HEADINGS, METRIC_SIDE = 4, 8, 16, 32
+METRIC_POINTS = (3500, 50000)
+
+
+def metrics_child(n_calls, reps):
+    """The metrics block on the GPU -> one JSON line on stdout."""
+    from navsim_amd import MushroomRouteEnsemble, NavBySceneFamiliarity, mushroom_familiarity, synth
+    land = synth.synth_landscape(3, 600, 4)
+    out = dict(side=METRIC_SIDE, routes=METRIC_ROUTES, members=METRIC_ROUTES * METRIC_MEMBERS, headings=METRIC_HEADINGS, n_kc=K,
+               steps_per_window=n_calls, timer="wall clock (time.perf_counter) around ens.step_forward(), median of %d windows" % reps, sizes=[])
+    for target in METRIC_POINTS:
+        # the curve of curveness c over x in [100, 500] is 400 sqrt(2) long and a little more: arclen to reach `target` points
+        routes = [synth.sin_training_path(c, 100, 400, arclen=400 * np.sqrt(2.0) / target) for c in (0.0, 0.2, 0.4, 0.6)]
+        starts = []
+        for r, route in enumerate(routes):
+            for m in range(METRIC_MEMBERS):
+                k = (1 + m) * len(route) // (4 * METRIC_MEMBERS)                        # along the route's first quarter
+                d = route[k + 1] - route[k]
+                starts.append((r, (float(route[k][0] + 0.3), float(route[k][1] - 0.2)), float(np.arctan2(d[1], d[0]) % (2 * np.pi))))
+        ens = {}
+        for mode in ("host", "device"):
+            agent = NavBySceneFamiliarity(land, (METRIC_SIDE, METRIC_SIDE), 1.0, n_test_angles=METRIC_HEADINGS, familiarity_model=mushroom_familiarity())
+            ens[mode] = MushroomRouteEnsemble.from_routes_with(agent, routes, starts, metrics=mode)
+
+        def window(e):
+            t0 = time.perf_counter()
+            for _ in range(n_calls):
+                e.step_forward()
+            return (time.perf_counter() - t0) * 1e6 / n_calls                          # us per ensemble step
+
+        for mode in ("host", "device"):                                                 # warm-up of both (code load, clocks, the buffers)
+            window(ens[mode])
+        t = dict(host=[], device=[])
+        for _ in range(reps):                                                           # alternating windows, both at the same poses
+            for mode in ("host", "device"):
+                t[mode].append(window(ens[mode]))
+        running = [len(ens[mode].active) for mode in ("host", "device")]
+        same = all(a.position == b.position and a.navigation_error == b.navigation_error and a.percent_recapitulated == b.percent_recapitulated
+                   for a, b in zip(ens["host"].agents, ens["device"].agents))
+        assert same and running[0] == running[1], (same, running)                      # (both modes walked the same poses to the same marks)
+        # the routed call alone, at the members' last positions (its marks are the ensemble's own: measured last)
+        dev = ens["device"]
+        slots = np.arange(len(starts), dtype=np.int32)
+        xs = np.array([a.position[0] for a in dev.agents])
+        ys = np.array([a.position[1] for a in dev.agents])
+        reach = np.array([a.coverage_threshold_factor * a.step_size for a in dev.agents])
+
+        def call_window():
+            t0 = time.perf_counter()
+            for _ in range(n_calls):
+                dev.engine.path_routes_error(slots, xs, ys, reach)
+            return (time.perf_counter() - t0) * 1e6 / n_calls
+
+        call_window()
+        tc = [call_window() for _ in range(reps)]
+        out["sizes"].append(dict(route_points=[len(r) for r in routes], host_us_per_step=spread(t["host"]), device_us_per_step=spread(t["device"]),
+                                 host_over_device=round(float(np.median(t["host"]) / np.median(t["device"])), 3),
+                                 path_routes_error_us_per_call=spread(tc), members_running=running[1]))
+        for e in ens.values():
+            e.agents[0].clear_training()
+            e.engine.close()
+    print(json.dumps(out))
+
+
 def cpu_row(side, n_calls):
     """The NumPy statement on this host: wall clock, microseconds per call that scores A patches."""
     from tests import helpers_mushroom as H
@@ -251,11 +322,12 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--limit", type=int, default=240, help="seconds allowed to each GPU child")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mushroom_time.json"))
-    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and the agent step), ensemble, banks")
+    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and the agent step), ensemble, banks, metrics")
     ap.add_argument("--ensemble-calls", type=int, default=30, help="ensemble steps per timed window")
     ap.add_argument("--child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--ensemble-child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--banks-child", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--metrics-child", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
         gpu_child(args.child, args.views, args.calls, args.reps)
@@ -266,13 +338,16 @@ def main():
     if args.banks_child:
         banks_child(args.banks_child, args.views, args.ensemble_calls, args.reps)
         return 0
+    if args.metrics_child:
+        metrics_child(args.ensemble_calls, args.reps)
+        return 0
     blocks = args.blocks.split(",")
     result = dict(tool="tools/mushroom_time.py", timer="hipEvent pair (dv_timer_start/stop), median of %d windows after a warm-up" % args.reps,
-                  sizes=[], ensembles=[], banks=[])
+                  sizes=[], ensembles=[], banks=[], metrics=[])
     if os.path.exists(args.out):                                  # a block that is not measured keeps its rows
         with open(args.out) as f:
             kept = json.load(f)
-        for block, key in (("single", "sizes"), ("ensemble", "ensembles"), ("banks", "banks")):
+        for block, key in (("single", "sizes"), ("ensemble", "ensembles"), ("banks", "banks"), ("metrics", "metrics")):
             if block not in blocks:
                 result[key] = kept.get(key, [])
     for side in [int(x) for x in args.sides.split(",")] if "ensemble" in blocks else []:
@@ -291,6 +366,14 @@ def main():
             print("GPU measurement of the banks of side %d ended with status %d: nothing more is run" % (side, p.returncode), file=sys.stderr)
             return p.returncode
         result["banks"].append(json.loads(p.stdout.strip().splitlines()[-1]))
+    if "metrics" in blocks:
+        cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--metrics-child", "1",
+               "--ensemble-calls", str(args.ensemble_calls), "--reps", str(args.reps)]
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, universal_newlines=True)
+        if p.returncode != 0:
+            print("GPU measurement of the route ensembles' metrics ended with status %d: nothing more is run" % p.returncode, file=sys.stderr)
+            return p.returncode
+        result["metrics"].append(json.loads(p.stdout.strip().splitlines()[-1]))
     for side in [int(x) for x in args.sides.split(",")] if "single" in blocks else []:
         cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child", str(side), "--views", str(args.views),
                "--calls", str(args.calls), "--reps", str(args.reps)]

@@ -747,6 +747,43 @@ int dv_ibank_read_weights(dv_ctx *ctx, int bank, double *out);
 int dv_ibank_set_weights(dv_ctx *ctx, int bank, const double *weights);
 int dv_ibank_info(dv_ctx *ctx, int *n_banks, int64_t *views_trained, int32_t *finite);
 
+/* ---- landscape sets ---------------------------------------------------------- */
+/*
+ * Several HSV landscapes of any shapes resident together in ONE context, and a landscape index per pose in the sensed calls of the
+ * banked models: the landscape replicates of a grid (and, with a bank per route, their routes) train in one call and step in one call.
+ * The set is one allocation with the landscapes back to back, no padding.  The sensor geometry, the level table and the mask stay the
+ * context's one configuration (dv_configure_sensor), shared by all landscapes of the set.  dv_set_landscape's landscape and every call
+ * that reads it are untouched by a set, and the set by them: dv_set_landscape, dv_mb_end and dv_infomax_end leave the set alone;
+ * dv_destroy frees it.  A landscape table is int32, one entry per pose or view (lands_sense, training) or per member (a step); every
+ * entry is checked against [0, n_lands) before anything of the call reaches the device: DV_ERR_INVALID names the first entry out of
+ * range, and nothing was trained, scored, uploaded or reallocated.  DV_ERR_STATE without a set.
+ *   set              lands: uint8, landscape l is [rows[l]][cols[l]][3] and follows landscape l - 1 directly.  n_lands >= 1, channels 3.
+ *                    The replacement is built first and put in place when complete: DV_ERR_OOM leaves the old set as it was.
+ *   clear            no set; its memory is freed.
+ *   info             n_lands (0: no set), the shapes (the caller's arrays of n_lands entries: ask for n_lands first) and the bytes of
+ *                    the set; any pointer may be NULL.
+ *   sense            dv_sense with pose v on landscape land_of_pose[v].  A negative index wraps by the pose's own rows and cols; a
+ *                    footprint past the end of its own landscape: DV_ERR_INDEX, and the message names the first such pose.
+ *   dv_lands_mbank_train_from_poses / dv_lands_ibank_train_from_poses   as dv_mbank_ / dv_ibank_train_from_poses, view v sensed on landscape
+ *                    land_of_view[v]: the same slabs, the same chains, and DV_ERR_INDEX trains nothing in any bank.
+ *   dv_lands_mbank_sense_step / dv_lands_ibank_sense_step   as dv_mbank_ / dv_ibank_sense_step, member i sensed on landscape land_of_member[i]: one enqueue,
+ *                    one wait, results in the caller's order, DV_RES_SENSE_ERROR for a member whose footprint leaves its own landscape.
+ */
+int dv_lands_set(dv_ctx *ctx, const uint8_t *lands, const int32_t *rows, const int32_t *cols, int n_lands, int channels);
+int dv_lands_clear(dv_ctx *ctx);
+int dv_lands_info(dv_ctx *ctx, int *n_lands, int32_t *rows, int32_t *cols, int64_t *bytes);
+int dv_lands_sense(dv_ctx *ctx, const double *x, const double *y, const double *angle, const int32_t *land_of_pose, int n, uint8_t *out);
+int dv_lands_mbank_train_from_poses(dv_ctx *ctx, const double *x, const double *y, const double *angle, int64_t n,
+                                    const int32_t *bank_of_view, const int32_t *land_of_view, uint8_t *out_views);
+int dv_lands_ibank_train_from_poses(dv_ctx *ctx, const double *x, const double *y, const double *angle, int64_t n,
+                                    const int32_t *bank_of_view, const int32_t *land_of_view, uint8_t *out_views);
+int dv_lands_mbank_sense_step(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
+                              const int32_t *bank_of_member, const int32_t *land_of_member, double *angle_fam, int32_t *best_heading,
+                              uint32_t *flags);
+int dv_lands_ibank_sense_step(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
+                              const int32_t *bank_of_member, const int32_t *land_of_member, double *angle_fam, int32_t *best_heading,
+                              uint32_t *flags);
+
 /* ---- measurement ------------------------------------------------------- */
 /* hipEvent pair on the context's stream around whatever is enqueued between the two calls. */
 int dv_timer_start(dv_ctx *ctx);

@@ -356,6 +356,17 @@ struct dv_ctx {
     int* mb_bank_of = nullptr;                // a banked call's table on the device: the bank of every view, or of every member
     size_t mb_bank_of_cap = 0;                // bytes
     std::vector<int32_t> mb_bank_host;        // what mb_bank_of holds (empty: nothing known), so that an unchanged table is not sent again
+    // landscape set (dejavu_lands.inl: dv_lands_*): independent of d_land above; the sensor configuration is shared
+    unsigned char* ld_lands = nullptr;        // the landscapes back to back, no padding (nullptr: no set)
+    LandEntry* ld_tab = nullptr;              // [n_lands]: byte offset, rows, cols
+    long long ld_bytes = 0;
+    std::vector<int32_t> ld_rows, ld_cols;    // [n_lands]
+    int* ld_of = nullptr;                     // a call's table on the device: the landscape of every view, or of every member
+    size_t ld_of_cap = 0;                     // bytes
+    std::vector<int32_t> ld_of_host;          // what ld_of holds (empty: nothing known)
+    int* ld_err = nullptr;                    // [n]: k_sense_lands' word per pose (dv_lands_sense, training from poses)
+    size_t ld_err_cap = 0;                    // bytes
+    std::vector<int> ld_err_host;
 
     // measurement
     hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -387,6 +398,7 @@ static void use_set(dv_ctx* c, int which);
 static void diffuse_free(dv_ctx* c);
 static void infomax_free(dv_ctx* c);
 static void mb_free(dv_ctx* c);
+static void lands_free(dv_ctx* c);
 static void path_routes_free(dv_ctx* c);
 static void free_library(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
@@ -487,6 +499,7 @@ extern "C" void dv_destroy(dv_ctx* c) {
     diffuse_free(c);
     infomax_free(c);
     mb_free(c);
+    lands_free(c);
     path_routes_free(c);
     if (c->d_land) (void)hipFree(c->d_land);
     if (c->d_lut) (void)hipFree(c->d_lut);
@@ -3689,6 +3702,7 @@ extern "C" int dv_stream_read_gbps(dv_ctx* c, int64_t n_bytes, int iters, double
 }
 
 #include "dejavu_diffuse.inl"   // dv_diffuse_*: the landscape generator's heat equation (kernels and host side)
+#include "dejavu_lands.inl"     // dv_lands_*: landscape sets, a landscape per pose in the banked models' sensed calls (kernel and host side)
 #include "dejavu_infomax.inl"   // dv_infomax_*: the Infomax familiarity model (kernels and host side)
 #include "dejavu_mushroom.inl"  // dv_mb_*: the mushroom-body familiarity model (kernels and host side)
 #include "dejavu_path_routes.inl"   // dv_path_routes_*: the error / coverage metrics against several routes (host side)

@@ -937,10 +937,13 @@ static int ibank_train_device(dv_ctx* c, const unsigned char* d_src, long long v
 // An ensemble's step under banks: member i's columns multiply the weights of bank bank_of[i].  The host sorts the members by bank
 // (stably), hands the device their patches or poses in that order and a table of column blocks that never mix banks; k_im_decide_banks
 // maps the columns back, so the results come in the caller's order.  One enqueue, one wait, as infomax_batch.
+// land_of != nullptr (poses only): member i senses landscape land_of[i] of the set (dejavu_lands.inl); the table rides the members'
+// permutation, so the device's entry p is the landscape of the member at place p, and k_sense_lands indexes it by the sorted column.
 static int ibank_batch(dv_ctx* c, const char* who, const uint8_t* planes, const double* x, const double* y, const double* angles, int n_agents, int A,
-                       const int32_t* bank_of, double* angle_fam, int32_t* best_heading, uint32_t* flags) {
+                       const int32_t* bank_of, const int32_t* land_of, double* angle_fam, int32_t* best_heading, uint32_t* flags) {
     int rc = ibank_check(c, who, "bank_of_member", bank_of, n_agents);
     if (rc) return rc;
+    if (land_of) { rc = lands_check(c, who, "land_of_member", land_of, n_agents); if (rc) return rc; }
     const long long C = (long long)n_agents * A;
     const int B = c->im_banks;
     if (C + (long long)kImHeadings * B > 0x7fffffffll - kImHeadings)
@@ -986,6 +989,11 @@ static int ibank_batch(dv_ctx* c, const char* who, const uint8_t* planes, const 
     if (!rc && !planes) rc = grow_buffer(c, c->im_perr, c->im_perr_cap, (size_t)C * sizeof(int));
     if (!rc) rc = ensure_sense_buffer(c, (size_t)slab * N * (planes ? 1 : 3));
     if (!rc) rc = ibank_table(c, t, true);
+    if (!rc && land_of) {
+        std::vector<int32_t> sorted((size_t)n_agents);
+        for (int p = 0; p < n_agents; ++p) sorted[(size_t)p] = land_of[(size_t)order[(size_t)p]];
+        rc = lands_upload(c, sorted.data(), n_agents);
+    }
     if (rc) return rc;
     const ImBlock* blocks = reinterpret_cast<const ImBlock*>(c->im_ktab_host.data());
     const ImBlock* d_blocks = reinterpret_cast<const ImBlock*>(c->im_ktab);
@@ -1016,9 +1024,14 @@ static int ibank_batch(dv_ctx* c, const char* who, const uint8_t* planes, const 
             hipLaunchKernelGGL(k_im_prep, dim3((unsigned)nc), dim3(256), 0, c->stream, c->d_sense, (long long)N, 1, 0, c->im_N, c->im_bx);
         } else {
             const long long total = nc * (long long)N;
-            hipLaunchKernelGGL(k_sense_each, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, c->d_land, c->d_poses + c0, (int)nc,
-                               c->sensor, c->d_lut, c->d_sense, c->im_perr + c0);
-            HIP_TRY(c, hipGetLastError());
+            if (land_of) {
+                rc = lands_launch_sense(c, c0, c0, A, nc, c->d_sense, c->im_perr + c0);
+                if (rc) return rc;
+            } else {
+                hipLaunchKernelGGL(k_sense_each, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, c->d_land, c->d_poses + c0, (int)nc,
+                                   c->sensor, c->d_lut, c->d_sense, c->im_perr + c0);
+                HIP_TRY(c, hipGetLastError());
+            }
             hipLaunchKernelGGL(k_im_prep, dim3((unsigned)nc), dim3(256), 0, c->stream, c->d_sense, 3ll * (long long)N, 3, c->im_channel, c->im_N,
                                c->im_bx);
         }
@@ -1103,30 +1116,45 @@ extern "C" int dv_ibank_train_u8(dv_ctx* c, const uint8_t* planes, int64_t n, co
     return ibank_report(c, "dv_ibank_train_u8", bank_of_view, n);
 }
 
-extern "C" int dv_ibank_train_from_poses(dv_ctx* c, const double* x, const double* y, const double* angle, int64_t n, const int32_t* bank_of_view,
-                                         uint8_t* out_views) {
-    if (!c) return DV_ERR_INVALID;
-    int rc = infomax_need(c, "dv_ibank_train_from_poses");
+// land_of == nullptr: the poses are on the context's one landscape (k_sense); else pose v is on landscape land_of[v] of the set.
+static int ibank_train_from_poses(dv_ctx* c, const char* who, const double* x, const double* y, const double* angle, int64_t n,
+                                  const int32_t* bank_of_view, const int32_t* land_of, uint8_t* out_views) {
+    int rc = infomax_need(c, who);
     if (rc) return rc;
-    if (!x || !y || !angle || n < 1 || n > 0x7fffffff) return fail(c, DV_ERR_INVALID, "dv_ibank_train_from_poses: bad arguments");
-    rc = sensor_fits(c, "dv_ibank_train_from_poses", c->im_hh, c->im_ww);
+    if (!x || !y || !angle || n < 1 || n > 0x7fffffff) return fail(c, DV_ERR_INVALID, "%s: bad arguments", who);
+    rc = sensor_fits(c, who, c->im_hh, c->im_ww);
     if (rc) return rc;
-    rc = ibank_check(c, "dv_ibank_train_from_poses", "bank_of_view", bank_of_view, n);
+    rc = ibank_check(c, who, "bank_of_view", bank_of_view, n);
     if (rc) return rc;
+    if (land_of) { rc = lands_check(c, who, "land_of_view", land_of, n); if (rc) return rc; }
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)n * (size_t)c->im_N * 3;
     rc = ensure_sense_buffer(c, bytes);
+    if (!rc && land_of) rc = lands_upload(c, land_of, n);
     if (rc) return rc;
-    rc = enqueue_sense(c, x, y, angle, n, c->d_sense);
+    rc = land_of ? lands_enqueue_sense(c, x, y, angle, n) : enqueue_sense(c, x, y, angle, n, c->d_sense);
     if (rc) return rc;
     if (out_views) HIP_TRY(c, hipMemcpyAsync(out_views, c->d_sense, bytes, hipMemcpyDeviceToHost, c->stream));
-    rc = check_sense_error(c);                                // DV_ERR_INDEX: no bank has been trained on anything
+    rc = land_of ? lands_check_sense_error(c, who, n) : check_sense_error(c);   // DV_ERR_INDEX: no bank has been trained on anything
     if (rc) return rc;
     rc = ibank_train_device(c, c->d_sense, 3ll * c->im_N, 3, c->im_channel, n, bank_of_view);
     if (rc) return rc;
     rc = ibank_check_finite(c);
     if (rc) return rc;
-    return ibank_report(c, "dv_ibank_train_from_poses", bank_of_view, n);
+    return ibank_report(c, who, bank_of_view, n);
+}
+
+extern "C" int dv_ibank_train_from_poses(dv_ctx* c, const double* x, const double* y, const double* angle, int64_t n, const int32_t* bank_of_view,
+                                         uint8_t* out_views) {
+    if (!c) return DV_ERR_INVALID;
+    return ibank_train_from_poses(c, "dv_ibank_train_from_poses", x, y, angle, n, bank_of_view, nullptr, out_views);
+}
+
+extern "C" int dv_lands_ibank_train_from_poses(dv_ctx* c, const double* x, const double* y, const double* angle, int64_t n,
+                                               const int32_t* bank_of_view, const int32_t* land_of_view, uint8_t* out_views) {
+    if (!c) return DV_ERR_INVALID;
+    if (!land_of_view) return fail(c, DV_ERR_INVALID, "dv_lands_ibank_train_from_poses: land_of_view is NULL");
+    return ibank_train_from_poses(c, "dv_lands_ibank_train_from_poses", x, y, angle, n, bank_of_view, land_of_view, out_views);
 }
 
 extern "C" int dv_ibank_step_u8(dv_ctx* c, const uint8_t* planes, int n_agents, int n_headings, const int32_t* bank_of_member, double* angle_fam,
@@ -1136,7 +1164,7 @@ extern "C" int dv_ibank_step_u8(dv_ctx* c, const uint8_t* planes, int n_agents, 
     if (rc) return rc;
     if (!planes || !bank_of_member || !angle_fam || !best_heading || n_agents < 1 || n_headings < 1)
         return fail(c, DV_ERR_INVALID, "dv_ibank_step_u8: NULL argument, n_agents < 1 or n_headings < 1");
-    return ibank_batch(c, "dv_ibank_step_u8", planes, nullptr, nullptr, nullptr, n_agents, n_headings, bank_of_member, angle_fam, best_heading, nullptr);
+    return ibank_batch(c, "dv_ibank_step_u8", planes, nullptr, nullptr, nullptr, n_agents, n_headings, bank_of_member, nullptr, angle_fam, best_heading, nullptr);
 }
 
 extern "C" int dv_ibank_sense_step(dv_ctx* c, const double* x, const double* y, const double* angles, int n_agents, int n_headings,
@@ -1148,7 +1176,21 @@ extern "C" int dv_ibank_sense_step(dv_ctx* c, const double* x, const double* y, 
         return fail(c, DV_ERR_INVALID, "dv_ibank_sense_step: NULL argument, n_agents < 1 or n_headings < 1");
     rc = sensor_fits(c, "dv_ibank_sense_step", c->im_hh, c->im_ww);
     if (rc) return rc;
-    return ibank_batch(c, "dv_ibank_sense_step", nullptr, x, y, angles, n_agents, n_headings, bank_of_member, angle_fam, best_heading, flags);
+    return ibank_batch(c, "dv_ibank_sense_step", nullptr, x, y, angles, n_agents, n_headings, bank_of_member, nullptr, angle_fam, best_heading, flags);
+}
+
+extern "C" int dv_lands_ibank_sense_step(dv_ctx* c, const double* x, const double* y, const double* angles, int n_agents, int n_headings,
+                                         const int32_t* bank_of_member, const int32_t* land_of_member, double* angle_fam, int32_t* best_heading,
+                                         uint32_t* flags) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = infomax_need(c, "dv_lands_ibank_sense_step");
+    if (rc) return rc;
+    if (!x || !y || !angles || !bank_of_member || !land_of_member || !angle_fam || !best_heading || !flags || n_agents < 1 || n_headings < 1)
+        return fail(c, DV_ERR_INVALID, "dv_lands_ibank_sense_step: NULL argument, n_agents < 1 or n_headings < 1");
+    rc = sensor_fits(c, "dv_lands_ibank_sense_step", c->im_hh, c->im_ww);
+    if (rc) return rc;
+    return ibank_batch(c, "dv_lands_ibank_sense_step", nullptr, x, y, angles, n_agents, n_headings, bank_of_member, land_of_member, angle_fam,
+                       best_heading, flags);
 }
 
 static int ibank_one(dv_ctx* c, const char* who, int bank) {

@@ -31,6 +31,10 @@
 // The connectivity, the selection and the LDS plane are the same.  Training views of many banks in one launch is safe for the reason one
 // route is: every writer of a byte stores 0, and a workgroup writes inside its own bank only, so no order between views or banks
 // matters and nothing is atomic.  The host checks every entry of a bank table against [0, n_banks) before a call's first launch.
+//
+// Landscape sets (dejavu_lands.inl).  k_mb_pose_bank_lands is k_mb_pose_bank with one more table: the column's landscape,
+// land_of[(col0 + blockIdx.x) / per], whose first byte and shape mb_fill_pose is handed instead of the context's one landscape.  The
+// plane still goes from the landscape to LDS; everything after it is mb_view.
 namespace dv {
 
 static constexpr int kMbTrain = 0, kMbScore = 1, kMbMask = 2;
@@ -241,6 +245,20 @@ __global__ __launch_bounds__(256) void k_mb_decide_batch(const int* __restrict__
     }
 }
 
+// k_mb_pose_bank on a landscape set: the workgroup's column senses its member's own landscape (land_of_column).
+__global__ __launch_bounds__(kMbWaves * 64) void k_mb_pose_bank_lands(const unsigned char* __restrict__ lands, const LandEntry* __restrict__ tab,
+                                                                      const int* __restrict__ land_of, const Pose* __restrict__ poses, SensorCfg g,
+                                                                      const unsigned char* __restrict__ lut, int channel,
+                                                                      const unsigned short* __restrict__ conn, int K, int c, int n_active,
+                                                                      unsigned char* __restrict__ wt, int* __restrict__ d, int* __restrict__ err,
+                                                                      const int* __restrict__ bank_of, unsigned col0, unsigned per) {
+    extern __shared__ unsigned mb_lds[];
+    const int N = g.sh * g.sw;
+    const unsigned char* land = land_of_column(lands, tab, land_of, col0 + blockIdx.x, per, g);
+    mb_view<kMbScore>(mb_lds, [&](unsigned char* plane, int tid) { mb_fill_pose(plane, tid, land, poses, g, lut, channel, N, err); },
+                      (int)blockIdx.x, N, conn, K, c, n_active, mb_bank(wt, K, bank_of, col0, per), d, nullptr, nullptr);
+}
+
 // zeros[b] = the zero weights of bank b = blockIdx.x (wt: [banks][K]).
 __global__ __launch_bounds__(256) void k_mb_count(const unsigned char* __restrict__ wt, int K, long long* __restrict__ zeros) {
     __shared__ int red[256];
@@ -385,6 +403,7 @@ extern "C" int dv_mb_begin(dv_ctx* c, int h, int w, int channel, int n_kc, int f
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_bank<kMbTrain>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_bank<kMbScore>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_pose_bank, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_pose_bank_lands, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = hipMemcpyAsync(c->mb_conn, ct.data(), ct.size() * sizeof(unsigned short), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->mb_wt, 1, K, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);           // `ct` is this call's
@@ -425,24 +444,27 @@ extern "C" int dv_mb_train_u8(dv_ctx* c, const uint8_t* planes, int64_t n) {
     return mb_train_u8(c, "dv_mb_train_u8", planes, n, nullptr);
 }
 
-// Sense n poses and train on their compared plane; bank_of as mb_train_u8's.
+// Sense n poses and train on their compared plane; bank_of as mb_train_u8's.  land_of == nullptr: the poses are on the context's one
+// landscape (k_sense); else pose v is on landscape land_of[v] of the set (k_sense_lands).
 static int mb_train_from_poses(dv_ctx* c, const char* who, const double* x, const double* y, const double* angle, int64_t n, const int32_t* bank_of,
-                               uint8_t* out_views) {
+                               const int32_t* land_of, uint8_t* out_views) {
     int rc = mb_need(c, who);
     if (rc) return rc;
     if (!x || !y || !angle || n < 1 || n > 0x7fffffff) return fail(c, DV_ERR_INVALID, "%s: bad arguments", who);
     rc = sensor_fits(c, who, c->mb_hh, c->mb_ww);
     if (rc) return rc;
     if (bank_of) { rc = mbank_check(c, who, "bank_of_view", bank_of, n); if (rc) return rc; }
+    if (land_of) { rc = lands_check(c, who, "land_of_view", land_of, n); if (rc) return rc; }
     HIP_TRY(c, hipSetDevice(c->device));
     if (bank_of) { rc = mbank_upload(c, bank_of, n); if (rc) return rc; }
+    if (land_of) { rc = lands_upload(c, land_of, n); if (rc) return rc; }
     const size_t bytes = (size_t)n * (size_t)c->mb_N * 3;
     rc = ensure_sense_buffer(c, bytes);
     if (rc) return rc;
-    rc = enqueue_sense(c, x, y, angle, n, c->d_sense);
+    rc = land_of ? lands_enqueue_sense(c, x, y, angle, n) : enqueue_sense(c, x, y, angle, n, c->d_sense);
     if (rc) return rc;
     if (out_views) HIP_TRY(c, hipMemcpyAsync(out_views, c->d_sense, bytes, hipMemcpyDeviceToHost, c->stream));
-    rc = check_sense_error(c);                                // (synchronises: nothing is trained from a footprint off the landscape)
+    rc = land_of ? lands_check_sense_error(c, who, n) : check_sense_error(c);   // (synchronises: nothing is trained from a footprint off the landscape)
     if (rc) return rc;
     const long long stride = 3ll * c->mb_N;
     for (int64_t v0 = 0; v0 < n; v0 += kMbSlabViews) {
@@ -459,7 +481,7 @@ static int mb_train_from_poses(dv_ctx* c, const char* who, const double* x, cons
 
 extern "C" int dv_mb_train_from_poses(dv_ctx* c, const double* x, const double* y, const double* angle, int64_t n, uint8_t* out_views) {
     if (!c) return DV_ERR_INVALID;
-    return mb_train_from_poses(c, "dv_mb_train_from_poses", x, y, angle, n, nullptr, out_views);
+    return mb_train_from_poses(c, "dv_mb_train_from_poses", x, y, angle, n, nullptr, nullptr, out_views);
 }
 
 extern "C" int dv_mb_score_u8(dv_ctx* c, const uint8_t* planes, int n, double* familiarity) {
@@ -551,11 +573,13 @@ extern "C" int dv_mb_sense_step(dv_ctx* c, double x, double y, const double* ang
 // launches follow one another on the stream; the host waits once, for the one copy of the packed results.
 // bank_of == nullptr: every member scores under bank 0 (the dv_batch_mb_* calls); else member i under bank bank_of[i], through the
 // banked kernels -- the same enqueue, with the members' table uploaded ahead of the launches.
+// land_of != nullptr (poses and banks only): member i senses landscape land_of[i] of the set, through k_mb_pose_bank_lands.
 static int mb_batch(dv_ctx* c, const char* who, const uint8_t* planes, const double* x, const double* y, const double* angles, int n_agents, int A,
-                    const int32_t* bank_of, double* angle_fam, int32_t* best_heading, uint32_t* flags) {
+                    const int32_t* bank_of, const int32_t* land_of, double* angle_fam, int32_t* best_heading, uint32_t* flags) {
     const long long C = (long long)n_agents * A;
     if (C > 0x7fffffffll) return fail(c, DV_ERR_INVALID, "%s: %d agents x %d headings are too many columns", who, n_agents, A);
     if (bank_of) { const int rb = mbank_check(c, who, "bank_of_member", bank_of, n_agents); if (rb) return rb; }
+    if (land_of) { const int rl = lands_check(c, who, "land_of_member", land_of, n_agents); if (rl) return rl; }
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t N = (size_t)c->mb_N;
     long long slab = planes ? (long long)mb_slab(N) : (long long)kMbSlabViews;
@@ -566,6 +590,7 @@ static int mb_batch(dv_ctx* c, const char* who, const uint8_t* planes, const dou
     if (!rc && !planes) rc = grow_buffer(c, c->mb_berr, c->mb_berr_cap, (size_t)C * sizeof(int));
     if (!rc && planes) rc = ensure_sense_buffer(c, (size_t)slab * N);
     if (!rc && bank_of) rc = mbank_upload(c, bank_of, n_agents);
+    if (!rc && land_of) rc = lands_upload(c, land_of, n_agents);
     if (rc) return rc;
     if (!planes) {
         rc = upload_member_poses(c, x, y, angles, n_agents, A);
@@ -578,6 +603,11 @@ static int mb_batch(dv_ctx* c, const char* who, const uint8_t* planes, const dou
             rc = bank_of ? mb_launch_bank<kMbScore>(c, c->d_sense, (long long)N, 1, 0, nc, c->mb_bd + c0, c->mb_bank_of, c0, A)
                          : mb_launch<kMbScore>(c, c->d_sense, (long long)N, 1, 0, nc, c->mb_bd + c0, nullptr, nullptr);
             if (rc) return rc;
+        } else if (land_of) {
+            hipLaunchKernelGGL(k_mb_pose_bank_lands, dim3((unsigned)nc), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, c->ld_lands, c->ld_tab,
+                               (const int*)c->ld_of, c->d_poses + c0, c->sensor, c->d_lut, c->mb_channel, c->mb_conn, c->mb_K, c->mb_c, c->mb_active,
+                               c->mb_wt, c->mb_bd + c0, c->mb_berr + c0, (const int*)c->mb_bank_of, (unsigned)c0, (unsigned)A);
+            HIP_TRY(c, hipGetLastError());
         } else if (bank_of) {
             hipLaunchKernelGGL(k_mb_pose_bank, dim3((unsigned)nc), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, c->d_land, c->d_poses + c0, c->sensor,
                                c->d_lut, c->mb_channel, c->mb_conn, c->mb_K, c->mb_c, c->mb_active, c->mb_wt, c->mb_bd + c0, c->mb_berr + c0,
@@ -605,7 +635,7 @@ extern "C" int dv_batch_mb_step_u8(dv_ctx* c, const uint8_t* planes, int n_agent
     if (rc) return rc;
     if (!planes || !angle_fam || !best_heading || n_agents < 1 || n_headings < 1)
         return fail(c, DV_ERR_INVALID, "dv_batch_mb_step_u8: NULL argument, n_agents < 1 or n_headings < 1");
-    return mb_batch(c, "dv_batch_mb_step_u8", planes, nullptr, nullptr, nullptr, n_agents, n_headings, nullptr, angle_fam, best_heading, nullptr);
+    return mb_batch(c, "dv_batch_mb_step_u8", planes, nullptr, nullptr, nullptr, n_agents, n_headings, nullptr, nullptr, angle_fam, best_heading, nullptr);
 }
 
 extern "C" int dv_batch_mb_sense_step(dv_ctx* c, const double* x, const double* y, const double* angles, int n_agents, int n_headings,
@@ -617,7 +647,7 @@ extern "C" int dv_batch_mb_sense_step(dv_ctx* c, const double* x, const double* 
         return fail(c, DV_ERR_INVALID, "dv_batch_mb_sense_step: NULL argument, n_agents < 1 or n_headings < 1");
     rc = sensor_fits(c, "dv_batch_mb_sense_step", c->mb_hh, c->mb_ww);
     if (rc) return rc;
-    return mb_batch(c, "dv_batch_mb_sense_step", nullptr, x, y, angles, n_agents, n_headings, nullptr, angle_fam, best_heading, flags);
+    return mb_batch(c, "dv_batch_mb_sense_step", nullptr, x, y, angles, n_agents, n_headings, nullptr, nullptr, angle_fam, best_heading, flags);
 }
 
 extern "C" int dv_mb_read_weights(dv_ctx* c, uint8_t* out) {
@@ -711,7 +741,16 @@ extern "C" int dv_mbank_train_from_poses(dv_ctx* c, const double* x, const doubl
     int rc = mb_need(c, "dv_mbank_train_from_poses");
     if (rc) return rc;
     if (!bank_of_view) return fail(c, DV_ERR_INVALID, "dv_mbank_train_from_poses: bank_of_view is NULL");
-    return mb_train_from_poses(c, "dv_mbank_train_from_poses", x, y, angle, n, bank_of_view, out_views);
+    return mb_train_from_poses(c, "dv_mbank_train_from_poses", x, y, angle, n, bank_of_view, nullptr, out_views);
+}
+
+extern "C" int dv_lands_mbank_train_from_poses(dv_ctx* c, const double* x, const double* y, const double* angle, int64_t n, const int32_t* bank_of_view,
+                                               const int32_t* land_of_view, uint8_t* out_views) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = mb_need(c, "dv_lands_mbank_train_from_poses");
+    if (rc) return rc;
+    if (!bank_of_view || !land_of_view) return fail(c, DV_ERR_INVALID, "dv_lands_mbank_train_from_poses: bank_of_view or land_of_view is NULL");
+    return mb_train_from_poses(c, "dv_lands_mbank_train_from_poses", x, y, angle, n, bank_of_view, land_of_view, out_views);
 }
 
 extern "C" int dv_mbank_step_u8(dv_ctx* c, const uint8_t* planes, int n_agents, int n_headings, const int32_t* bank_of_member, double* angle_fam,
@@ -721,7 +760,7 @@ extern "C" int dv_mbank_step_u8(dv_ctx* c, const uint8_t* planes, int n_agents, 
     if (rc) return rc;
     if (!planes || !bank_of_member || !angle_fam || !best_heading || n_agents < 1 || n_headings < 1)
         return fail(c, DV_ERR_INVALID, "dv_mbank_step_u8: NULL argument, n_agents < 1 or n_headings < 1");
-    return mb_batch(c, "dv_mbank_step_u8", planes, nullptr, nullptr, nullptr, n_agents, n_headings, bank_of_member, angle_fam, best_heading, nullptr);
+    return mb_batch(c, "dv_mbank_step_u8", planes, nullptr, nullptr, nullptr, n_agents, n_headings, bank_of_member, nullptr, angle_fam, best_heading, nullptr);
 }
 
 extern "C" int dv_mbank_sense_step(dv_ctx* c, const double* x, const double* y, const double* angles, int n_agents, int n_headings,
@@ -733,7 +772,21 @@ extern "C" int dv_mbank_sense_step(dv_ctx* c, const double* x, const double* y, 
         return fail(c, DV_ERR_INVALID, "dv_mbank_sense_step: NULL argument, n_agents < 1 or n_headings < 1");
     rc = sensor_fits(c, "dv_mbank_sense_step", c->mb_hh, c->mb_ww);
     if (rc) return rc;
-    return mb_batch(c, "dv_mbank_sense_step", nullptr, x, y, angles, n_agents, n_headings, bank_of_member, angle_fam, best_heading, flags);
+    return mb_batch(c, "dv_mbank_sense_step", nullptr, x, y, angles, n_agents, n_headings, bank_of_member, nullptr, angle_fam, best_heading, flags);
+}
+
+extern "C" int dv_lands_mbank_sense_step(dv_ctx* c, const double* x, const double* y, const double* angles, int n_agents, int n_headings,
+                                         const int32_t* bank_of_member, const int32_t* land_of_member, double* angle_fam, int32_t* best_heading,
+                                         uint32_t* flags) {
+    if (!c) return DV_ERR_INVALID;
+    int rc = mb_need(c, "dv_lands_mbank_sense_step");
+    if (rc) return rc;
+    if (!x || !y || !angles || !bank_of_member || !land_of_member || !angle_fam || !best_heading || !flags || n_agents < 1 || n_headings < 1)
+        return fail(c, DV_ERR_INVALID, "dv_lands_mbank_sense_step: NULL argument, n_agents < 1 or n_headings < 1");
+    rc = sensor_fits(c, "dv_lands_mbank_sense_step", c->mb_hh, c->mb_ww);
+    if (rc) return rc;
+    return mb_batch(c, "dv_lands_mbank_sense_step", nullptr, x, y, angles, n_agents, n_headings, bank_of_member, land_of_member, angle_fam,
+                    best_heading, flags);
 }
 
 static int mbank_one(dv_ctx* c, const char* who, int bank) {

@@ -272,6 +272,14 @@ PROTOTYPES = {
     "dv_ibank_read_weights": (ctypes.c_int, [_ctx_p, ctypes.c_int, _f64p]),
     "dv_ibank_set_weights": (ctypes.c_int, [_ctx_p, ctypes.c_int, _f64p]),
     "dv_ibank_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64), _i32p]),
+    "dv_lands_set": (ctypes.c_int, [_ctx_p, _u8p, _i32p, _i32p, ctypes.c_int, ctypes.c_int]),
+    "dv_lands_clear": (ctypes.c_int, [_ctx_p]),
+    "dv_lands_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), _i32p, _i32p, _i64p]),
+    "dv_lands_sense": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, _i32p, ctypes.c_int, _u8p]),
+    "dv_lands_mbank_train_from_poses": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int64, _i32p, _i32p, _u8p]),
+    "dv_lands_ibank_train_from_poses": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int64, _i32p, _i32p, _u8p]),
+    "dv_lands_mbank_sense_step": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _i32p, _i32p, _f64p, _i32p, _u32p]),
+    "dv_lands_ibank_sense_step": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _i32p, _i32p, _f64p, _i32p, _u32p]),
     "dv_synchronize": (ctypes.c_int, [_ctx_p]),
     "dv_timer_start": (ctypes.c_int, [_ctx_p]),
     "dv_timer_stop": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_float)]),

@@ -1081,13 +1081,20 @@ class FamiliarityEngine(object):
         banks = self._bank_table(bank_of_view, planes.shape[0], "bank_of_view", self.infomax_banks)
         self._check(self._lib.dv_ibank_train_u8(self._ctx, N.u8ptr(planes), planes.shape[0], banks.ctypes.data_as(N._i32p)), "dv_ibank_train_u8")
 
-    def ibank_train_from_poses(self, x, y, angle, bank_of_view, want_views=True):
+    def ibank_train_from_poses(self, x, y, angle, bank_of_view, want_views=True, land_of_view=None):
         """infomax_train_from_poses with view v trained into bank bank_of_view[v] (the routes of a grid, trained in one call); returns
         the views (uint8[n,h,w,3]) when want_views."""
         x, y, angle = self._pose_arrays(x, y, angle)
         banks = self._bank_table(bank_of_view, len(x), "bank_of_view", self.infomax_banks)
+        lands = None if land_of_view is None else self._land_table(land_of_view, len(x), "land_of_view")
         h, w = self.sensor_shape
         views = np.empty((len(x), h, w, 3), dtype=np.uint8) if want_views else None
+        if lands is not None:
+            self._check_sense(self._lib.dv_lands_ibank_train_from_poses(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), len(x),
+                                                                        banks.ctypes.data_as(N._i32p), lands.ctypes.data_as(N._i32p),
+                                                                        N.u8ptr(views) if want_views else None),
+                              "dv_lands_ibank_train_from_poses")
+            return views
         self._check_sense(self._lib.dv_ibank_train_from_poses(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), len(x),
                                                               banks.ctypes.data_as(N._i32p), N.u8ptr(views) if want_views else None),
                           "dv_ibank_train_from_poses")
@@ -1107,7 +1114,7 @@ class FamiliarityEngine(object):
                                                best.ctypes.data_as(N._i32p)), "dv_ibank_step_u8")
         return OneValueBatchResults(fam, best, np.zeros(n, dtype=np.uint32))
 
-    def ibank_sense_step_batch(self, x, y, angles, bank_of_member):
+    def ibank_sense_step_batch(self, x, y, angles, bank_of_member, land_of_member=None):
         """infomax_sense_step_batch with member i scored under bank bank_of_member[i] -> OneValueBatchResults: one enqueue and one wait."""
         x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
         y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
@@ -1116,9 +1123,16 @@ class FamiliarityEngine(object):
             raise ValueError("x[N], y[N] and angles[N, A] expected (N, A >= 1), got shapes %r, %r and %r" % (x.shape, y.shape, angles.shape))
         n, A = angles.shape
         banks = self._bank_table(bank_of_member, n, "bank_of_member", self.infomax_banks)
+        lands = None if land_of_member is None else self._land_table(land_of_member, n, "land_of_member")
         fam = np.empty((n, A), dtype=np.float64)
         best = np.full(n, -1, dtype=np.int32)
         flags = np.zeros(n, dtype=np.uint32)
+        if lands is not None:
+            self._check(self._lib.dv_lands_ibank_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A,
+                                                            banks.ctypes.data_as(N._i32p), lands.ctypes.data_as(N._i32p), N.f64ptr(fam),
+                                                            best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)),
+                        "dv_lands_ibank_sense_step")
+            return OneValueBatchResults(fam, best, flags)
         self._check(self._lib.dv_ibank_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, banks.ctypes.data_as(N._i32p),
                                                   N.f64ptr(fam), best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)),
                     "dv_ibank_sense_step")
@@ -1260,13 +1274,20 @@ class FamiliarityEngine(object):
         banks = self._bank_table(bank_of_view, planes.shape[0], "bank_of_view")
         self._check(self._lib.dv_mbank_train_u8(self._ctx, N.u8ptr(planes), planes.shape[0], banks.ctypes.data_as(N._i32p)), "dv_mbank_train_u8")
 
-    def mbank_train_from_poses(self, x, y, angle, bank_of_view, want_views=True):
+    def mbank_train_from_poses(self, x, y, angle, bank_of_view, want_views=True, land_of_view=None):
         """mb_train_from_poses with view v depressing bank bank_of_view[v] (the routes of a grid, trained in one call); returns the
         views (uint8[n,h,w,3]) when want_views."""
         x, y, angle = self._pose_arrays(x, y, angle)
         banks = self._bank_table(bank_of_view, len(x), "bank_of_view")
+        lands = None if land_of_view is None else self._land_table(land_of_view, len(x), "land_of_view")
         h, w = self.sensor_shape
         views = np.empty((len(x), h, w, 3), dtype=np.uint8) if want_views else None
+        if lands is not None:
+            self._check_sense(self._lib.dv_lands_mbank_train_from_poses(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), len(x),
+                                                                        banks.ctypes.data_as(N._i32p), lands.ctypes.data_as(N._i32p),
+                                                                        N.u8ptr(views) if want_views else None),
+                              "dv_lands_mbank_train_from_poses")
+            return views
         self._check_sense(self._lib.dv_mbank_train_from_poses(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), len(x),
                                                               banks.ctypes.data_as(N._i32p), N.u8ptr(views) if want_views else None),
                           "dv_mbank_train_from_poses")
@@ -1286,7 +1307,7 @@ class FamiliarityEngine(object):
                                                best.ctypes.data_as(N._i32p)), "dv_mbank_step_u8")
         return OneValueBatchResults(fam, best, np.zeros(n, dtype=np.uint32))
 
-    def mbank_sense_step_batch(self, x, y, angles, bank_of_member):
+    def mbank_sense_step_batch(self, x, y, angles, bank_of_member, land_of_member=None):
         """mb_sense_step_batch with member i scored under bank bank_of_member[i] -> OneValueBatchResults: one enqueue and one wait."""
         x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
         y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
@@ -1295,9 +1316,16 @@ class FamiliarityEngine(object):
             raise ValueError("x[N], y[N] and angles[N, A] expected (N, A >= 1), got shapes %r, %r and %r" % (x.shape, y.shape, angles.shape))
         n, A = angles.shape
         banks = self._bank_table(bank_of_member, n, "bank_of_member")
+        lands = None if land_of_member is None else self._land_table(land_of_member, n, "land_of_member")
         fam = np.empty((n, A), dtype=np.float64)
         best = np.full(n, -1, dtype=np.int32)
         flags = np.zeros(n, dtype=np.uint32)
+        if lands is not None:
+            self._check(self._lib.dv_lands_mbank_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A,
+                                                            banks.ctypes.data_as(N._i32p), lands.ctypes.data_as(N._i32p), N.f64ptr(fam),
+                                                            best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)),
+                        "dv_lands_mbank_sense_step")
+            return OneValueBatchResults(fam, best, flags)
         self._check(self._lib.dv_mbank_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, banks.ctypes.data_as(N._i32p),
                                                   N.f64ptr(fam), best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)),
                     "dv_mbank_sense_step")
@@ -1330,3 +1358,64 @@ class FamiliarityEngine(object):
         i64p = ctypes.POINTER(ctypes.c_int64)
         self._check(self._lib.dv_mbank_info(self._ctx, None, views.ctypes.data_as(i64p), zeros.ctypes.data_as(i64p)), "dv_mbank_info")
         return dict(n_banks=nb.value, views_trained=views, n_depressed=zeros)
+
+    # -- landscape sets: several landscapes resident together, a landscape per pose (include/dejavu.h: dv_lands_*) -----------------
+    n_lands = 0                  # landscapes of the set (lands_set; 0: none)
+
+    def _land_table(self, table, n, what):
+        """`table` as int32[n] with every entry in [0, n_lands), or ValueError naming `what`: checked before any library call."""
+        if not self.n_lands:
+            raise N.EngineError("%s given, but the engine holds no landscape set: lands_set first (DV_ERR_STATE)" % what)
+        arr = np.asarray(table)
+        if arr.shape == (0,):
+            arr = arr.astype(np.int32)                           # (an empty list has no dtype to speak of)
+        if arr.dtype.kind not in "iu":
+            raise ValueError("%s must hold integers (a landscape per entry), got dtype %s" % (what, arr.dtype))
+        if arr.shape != (n,):
+            raise ValueError("%s must have shape (%d,), got %r" % (what, n, arr.shape))
+        if n and (arr.min() < 0 or arr.max() >= self.n_lands):
+            bad = np.flatnonzero((arr < 0) | (arr >= self.n_lands))
+            raise ValueError("%s[%d] = %d outside [0, n_lands = %d)" % (what, bad[0], arr[bad[0]], self.n_lands))
+        return np.ascontiguousarray(arr, dtype=np.int32)
+
+    def lands_set(self, landscapes):
+        """landscapes: a list of uint8[rows, cols, 3] HSV of any shapes and strides (copied), kept resident together beside the engine's
+        one landscape (set_landscape), which they leave alone.  The sensor configuration is the engine's one (configure_sensor)."""
+        lands = [N.as_u8(l, "landscapes[%d]" % i) for i, l in enumerate(landscapes)]
+        if not lands:
+            raise ValueError("no landscapes: a set holds at least one")
+        for i, l in enumerate(lands):
+            if l.ndim != 3 or l.shape[2] != 3 or l.shape[0] < 1 or l.shape[1] < 1:
+                raise ValueError("landscapes[%d] must be uint8[rows, cols, 3], got shape %r" % (i, l.shape))
+        flat = np.concatenate([l.reshape(-1) for l in lands])
+        rows = np.array([l.shape[0] for l in lands], dtype=np.int32)
+        cols = np.array([l.shape[1] for l in lands], dtype=np.int32)
+        self._check(self._lib.dv_lands_set(self._ctx, N.u8ptr(flat), rows.ctypes.data_as(N._i32p), cols.ctypes.data_as(N._i32p), len(lands), 3),
+                    "dv_lands_set")
+        self.n_lands = len(lands)
+
+    def lands_clear(self):
+        self._check(self._lib.dv_lands_clear(self._ctx), "dv_lands_clear")
+        self.n_lands = 0
+
+    def lands_info(self):
+        """dict(n_lands, shapes: list of (rows, cols), bytes)."""
+        nl, nbytes = ctypes.c_int(0), ctypes.c_int64(0)
+        self._check(self._lib.dv_lands_info(self._ctx, ctypes.byref(nl), None, None, ctypes.byref(nbytes)), "dv_lands_info")
+        rows = np.zeros(max(nl.value, 1), dtype=np.int32)
+        cols = np.zeros(max(nl.value, 1), dtype=np.int32)
+        self._check(self._lib.dv_lands_info(self._ctx, None, rows.ctypes.data_as(N._i32p), cols.ctypes.data_as(N._i32p), None), "dv_lands_info")
+        return dict(n_lands=nl.value, shapes=[(int(r), int(c)) for r, c in zip(rows[:nl.value], cols[:nl.value])], bytes=nbytes.value)
+
+    def lands_sense(self, x, y, angle, land_of_pose):
+        """sense() with pose v on landscape land_of_pose[v] of the set -> uint8[n, h, w, 3].  IndexError names the first pose whose
+        footprint leaves its own landscape."""
+        x, y, angle = self._pose_arrays(x, y, angle)
+        lands = self._land_table(land_of_pose, len(x), "land_of_pose")
+        if len(x) < 1:
+            raise ValueError("no poses")
+        h, w = self.sensor_shape
+        out = np.empty((len(x), h, w, 3), dtype=np.uint8)
+        self._check_sense(self._lib.dv_lands_sense(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), lands.ctypes.data_as(N._i32p), len(x),
+                                                   N.u8ptr(out)), "dv_lands_sense")
+        return out

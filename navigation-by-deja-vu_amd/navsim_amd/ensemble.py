@@ -387,7 +387,12 @@ class _RouteEnsemble(_OneValueEnsemble):
     as long as its own route (path_routes_slots, in member order), and takes the metrics of all members that stepped in ONE
     path_routes_error call per ensemble step -- every member with its own coverage_threshold_factor * step_size; the numbers are the
     host's, bit for bit, and "too far from the path" stops a member in the same step, before it marks anything (a member whose
-    max_distance_to_training_path is below its coverage reach has its marks taken in a second call: _metrics_call)."""
+    max_distance_to_training_path is below its coverage reach has its marks taken in a second call: _metrics_call).
+
+    from_landscapes makes trials that differ in their LANDSCAPE as well: the engine holds the landscapes as a set
+    (FamiliarityEngine.lands_set), every route is sensed on its own landscape, and a step hands the device the members' landscapes
+    beside their banks.  Members on landscapes of one shape keep the vectorised host path of a step; members on landscapes of
+    different shapes work out their headings one by one (headings_to_test), each against its own bounds."""
     _metrics_on_slots = False    # (NavEnsemble's slots hold ONE training path: the routed slots are made below)
     _one_route = None            # the name of the ensemble whose members share one trained route
     _info_call = None            # the engine's per-bank info
@@ -403,6 +408,15 @@ class _RouteEnsemble(_OneValueEnsemble):
                                  "trained route" % (name, name, self._one_route))
         super(_RouteEnsemble, self).__init__(agents)
         self._banks = np.array([a.memory_bank for a in agents], dtype=np.int32)
+        on_set = [a.landscape_index is not None for a in agents]
+        if any(on_set) and not all(on_set):
+            raise ValueError("%s: members on a landscape set (from_landscapes) and members on the engine's one landscape do not mix" % name)
+        self._lands = np.array([a.landscape_index for a in agents], dtype=np.int32) if all(on_set) else None
+        if self._lands is not None:
+            # NavEnsemble asks for ONE landscape object; what the vectorised path needs is one set of bounds: landscapes of one shape
+            a0 = agents[0]
+            self._uniform = all(a.step_size == a0.step_size and a.landscape.shape == a0.landscape.shape and a._sensor_r == a0._sensor_r and
+                                np.array_equal(a.angle_offsets, a0.angle_offsets) for a in agents)
         self.metrics = metrics
         if metrics == "device":
             routes, route_of = [], []                              # the members' routes, each once, in the order the members bring them
@@ -449,8 +463,9 @@ class _RouteEnsemble(_OneValueEnsemble):
         raise ValueError("%s is made from routes (from_routes); %s.from_agent clones a trained agent" % (cls.__name__, cls._one_route))
 
     @staticmethod
-    def _train_banks(eng, n_routes, x, y, headings, bank_of_view):
-        """One bank per route on the engine's fresh model, every view trained into its route's bank in one call -> the views."""
+    def _train_banks(eng, n_routes, x, y, headings, bank_of_view, land_of_view=None):
+        """One bank per route on the engine's fresh model, every view trained into its route's bank in one call -> the views.
+        land_of_view: the landscape of the engine's set every view is sensed on (None: the engine's one landscape)."""
         raise NotImplementedError
 
     @classmethod
@@ -466,6 +481,12 @@ class _RouteEnsemble(_OneValueEnsemble):
     def from_routes_with(cls, agent, routes, starts, metrics="host"):
         """from_routes with the members' error metrics on the host ("host": every member's own NumPy pass, as from_routes) or on the
         device ("device": all members' in one call per ensemble step, each against its own route; see the class)."""
+        return cls._from_routes(agent, routes, starts, metrics, None, None)
+
+    @classmethod
+    def _from_routes(cls, agent, routes, starts, metrics, lands, land_of_route):
+        """from_routes_with (lands None: every route on the agent's own landscape, the engine's one), or from_landscapes (route r on
+        lands[land_of_route[r]] of the engine's landscape set)."""
         import copy
         if metrics not in cls.METRICS:
             raise ValueError("metrics must be one of %r, got %r" % (cls.METRICS, metrics))
@@ -487,9 +508,10 @@ class _RouteEnsemble(_OneValueEnsemble):
         for i, (r, _, _) in enumerate(starts):
             if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 0 <= r < len(routes):
                 raise ValueError("starts[%d]: route_index %r outside [0, %d)" % (i, r, len(routes)))
-        for route in routes:
+        for k, route in enumerate(routes):                        # (the agent's own bounds test, on the route's own landscape)
+            probe = agent if lands is None else cls._on_landscape(copy.copy(agent), lands[land_of_route[k]])
             for pt in route:
-                agent._check_bounds(pt)
+                probe._check_bounds(pt)
         # the views of a route look along ITS steps (train_from_path: towards the next point, the last heading once more)
         headings = []
         for route in routes:
@@ -500,7 +522,12 @@ class _RouteEnsemble(_OneValueEnsemble):
         points = np.concatenate(routes)
         bank_of_view = np.repeat(np.arange(len(routes), dtype=np.int32), [len(r) for r in routes])
         model.begin(eng, agent.sensor_dimensions[1], agent.sensor_dimensions[0])
-        views = cls._train_banks(eng, len(routes), points[:, 0], points[:, 1], np.concatenate(headings), bank_of_view)
+        if lands is None:
+            views = cls._train_banks(eng, len(routes), points[:, 0], points[:, 1], np.concatenate(headings), bank_of_view)
+        else:
+            eng.lands_set(lands)
+            land_of_view = np.repeat(np.array(land_of_route, dtype=np.int32), [len(r) for r in routes])
+            views = cls._train_banks(eng, len(routes), points[:, 0], points[:, 1], np.concatenate(headings), bank_of_view, land_of_view)
         func = model.from_engine(eng, views)
         members = []
         for k, (r, pos, ang) in enumerate(starts):
@@ -511,6 +538,9 @@ class _RouteEnsemble(_OneValueEnsemble):
             a.familiar_scenes = views[first[r]:first[r + 1]]
             a._familiarity_func = func
             a.memory_bank = int(r)
+            if lands is not None:
+                a.landscape_index = land_of_route[r]
+                cls._on_landscape(a, lands[a.landscape_index])
             a.angle_familiarity = np.full(agent.n_test_angles, np.nan)
             a.scene_familiarity = np.zeros(len(route), dtype=np.float64)
             a._scene_is_inf = False
@@ -522,8 +552,39 @@ class _RouteEnsemble(_OneValueEnsemble):
             members.append(a)
         return cls(members, metrics=metrics)
 
+    @staticmethod
+    def _on_landscape(agent, landscape):
+        """`agent` on `landscape`: its bounds are worked out again from that landscape's shape -> the agent."""
+        agent.landscape = landscape
+        agent._bounds = agent._bounds_arr = None
+        return agent
+
+    @classmethod
+    def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host"):
+        """Trials that differ in their LANDSCAPE, their training route and their start.  `agent`: an UNTRAINED agent of the ensemble's
+        model with the GPU sensor model; landscapes: a list of uint8[rows, cols, 3] of any shapes; routes: a list of
+        (landscape_index, float64[n_r, 2]); starts and metrics as from_routes_with.  The landscapes become the engine's landscape set,
+        every route is bounds-checked against and sensed on ITS landscape and trained into its own bank, all routes in one call.
+        Member i gets what from_routes gives it, and the landscape of its route: `landscape` (so its bounds, and the host sensor
+        model, are that landscape's) and `landscape_index`."""
+        lands = [np.asarray(l) for l in landscapes]
+        if not lands or any(l.dtype != np.uint8 or l.ndim != 3 or l.shape[2] != 3 for l in lands):
+            raise ValueError("landscapes must be one or more arrays uint8[rows, cols, 3]")
+        routes = list(routes)
+        for k, rt in enumerate(routes):
+            if not isinstance(rt, (tuple, list)) or len(rt) != 2:
+                raise ValueError("routes[%d] must be (landscape_index, float64[n_r, 2])" % k)
+            l = rt[0]
+            if isinstance(l, bool) or not isinstance(l, (int, np.integer)) or not 0 <= l < len(lands):
+                raise ValueError("routes[%d]: landscape_index %r outside [0, %d)" % (k, l, len(lands)))
+        land_of_route = [int(l) for l, _ in routes]
+        return cls._from_routes(agent, [pts for _, pts in routes], starts, metrics, lands, land_of_route)
+
     def _device_step(self, idx, xs, ys, angs):
-        results = getattr(self.engine, self._batch_call)(xs, ys, angs, self._banks[idx])
+        if self._lands is not None:
+            results = getattr(self.engine, self._batch_call)(xs, ys, angs, self._banks[idx], land_of_member=self._lands[idx])
+        else:
+            results = getattr(self.engine, self._batch_call)(xs, ys, angs, self._banks[idx])
         self._rows = {id(self.agents[i]): results.angle_familiarity[k] for k, i in enumerate(idx)}
         return results
 
@@ -546,9 +607,11 @@ class MushroomRouteEnsemble(_RouteEnsemble):
     _reject_others = MushroomEnsemble._reject_others
 
     @staticmethod
-    def _train_banks(eng, n_routes, x, y, headings, bank_of_view):
+    def _train_banks(eng, n_routes, x, y, headings, bank_of_view, land_of_view=None):
         eng.mbank_set(n_routes)
-        return eng.mbank_train_from_poses(x, y, headings, bank_of_view)
+        if land_of_view is None:
+            return eng.mbank_train_from_poses(x, y, headings, bank_of_view)
+        return eng.mbank_train_from_poses(x, y, headings, bank_of_view, land_of_view=land_of_view)
 
 
 class InfomaxRouteEnsemble(_RouteEnsemble):
@@ -565,6 +628,8 @@ class InfomaxRouteEnsemble(_RouteEnsemble):
     _reject_others = InfomaxEnsemble._reject_others
 
     @staticmethod
-    def _train_banks(eng, n_routes, x, y, headings, bank_of_view):
+    def _train_banks(eng, n_routes, x, y, headings, bank_of_view, land_of_view=None):
         eng.ibank_set(n_routes, eng.infomax_read_weights())          # (bank 0 holds the W0 the model's begin has just drawn)
-        return eng.ibank_train_from_poses(x, y, headings, bank_of_view)
+        if land_of_view is None:
+            return eng.ibank_train_from_poses(x, y, headings, bank_of_view)
+        return eng.ibank_train_from_poses(x, y, headings, bank_of_view, land_of_view=land_of_view)

@@ -2,7 +2,7 @@
 """Times the mushroom-body familiarity model (navsim_amd.mushroom_familiarity; include/dejavu.h: dv_mb_*) on GPU 0 and writes
 profiles/mushroom_time.json.
 
-    python tools/mushroom_time.py [--sides 32,64] [--views 1000] [--calls 200] [--reps 5] [--blocks single,ensemble[,banks][,metrics]]
+    python tools/mushroom_time.py [--sides 32,64] [--views 1000] [--calls 200] [--reps 5] [--blocks single,ensemble[,banks][,metrics][,lands]]
                                   [--out profiles/mushroom_time.json]
 
 Per sensor side s (views of s x s) with K = 20000 Kenyon cells, fan-in 10 and 200 firing cells: microseconds per agent step
@@ -30,6 +30,16 @@ members' in one dv_path_routes_error call -- and stepped from the same starts, s
 ens.step_forward(), Python included, in alternating windows of --ensemble-calls steps, for routes of about 3 500 points (a grid trial's)
 and of about 50 000 (the sin path's arclen is set to reach the count); their ratio is host_over_device.  And the path_routes_error call
 alone, at the members' last positions.
+
+Lands block (--blocks lands): per side, the banks block's two layouts over 4 banks AND 4 landscapes of three shapes held as a
+landscape set (dv_lands_set; member i in bank i % 4 on landscape 3 i % 4) -- (a) microseconds per ensemble step of
+dv_lands_mbank_sense_step against dv_mbank_sense_step at the same poses on ONE landscape (the call as it was before landscape sets,
+in the SAME build of the library: its code path is untouched),
+hipEvent pairs in alternating windows, ratio lands_over_one_landscape; (b) the same members as four engines of one landscape each,
+every engine stepping its landscape's members in turn -- what a user did before -- against the one call, both WALL CLOCK (four
+streams have no common event pair), ratio four_engines_over_lands_wall; the four engines' rows are checked to be the one call's bits;
+(c) 4 routes of --views views on the 4 landscapes trained in ONE dv_lands_mbank_train_from_poses call against four
+dv_mb_train_from_poses calls on four engines (the sum of their timers, and wall clock).
 
 A block that is not measured keeps the rows it has in the output file.
 
@@ -234,6 +244,129 @@ def banks_child(side, n_views, n_calls, reps):
     print(json.dumps(out))
 
 
+LAND_SHAPES = ((600, 600), (560, 600), (600, 540), (600, 600))     # rows, cols: the poses lie inside all of them
+
+
+def lands_child(side, n_views, n_calls, reps):
+    """The lands block of one size on the GPU -> one JSON line on stdout."""
+    from navsim_amd import NavBySceneFamiliarity, mushroom_familiarity, synth
+    from navsim_amd.util import mushroom_connectivity
+    N = side * side
+    lands = [np.ascontiguousarray(synth.synth_landscape(3 + l, 600, 4)[:r, :c]) for l, (r, c) in enumerate(LAND_SHAPES)]
+    L = len(lands)
+    out = dict(side=side, N=N, n_kc=K, fan_in=FAN_IN, n_active=N_ACTIVE, n_banks=N_BANKS, n_lands=L, land_shapes=LAND_SHAPES,
+               calls_per_window=n_calls, views_per_route=n_views, layouts=[])
+    conn = mushroom_connectivity(K, N, FAN_IN, 0)
+
+    def engine(land, A):
+        agent = NavBySceneFamiliarity(land, (side, side), 1.0, n_test_angles=A, familiarity_model=mushroom_familiarity())
+        agent._engine.mb_begin(side, side, conn, N_ACTIVE, 2)
+        agent._engine.mbank_set(N_BANKS)
+        return agent, agent._engine                              # (landscape and sensor attached)
+
+    for n, A in ENSEMBLES:
+        agent, eng = engine(lands[0], A)
+        eng.lands_set(lands)
+        rng = np.random.default_rng(n * 100 + A)
+        xs, ys = rng.uniform(150, 390, n), rng.uniform(150, 390, n)
+        angs = (rng.uniform(0, 2 * np.pi, n)[:, None] + agent.angle_offsets[None, :]) % (2 * np.pi)
+        banks = (np.arange(n) % N_BANKS).astype(np.int32)
+        land_of = (3 * np.arange(n) % L).astype(np.int32)
+        eng.mbank_train_from_poses(xs, ys, angs[:, A // 2].copy(), banks, want_views=False, land_of_view=land_of)   # (some weights at 0)
+        four = [engine(lands[l], A)[1] for l in range(L)]
+        for e in four:
+            for r in range(N_BANKS):
+                e.mbank_set_weights(r, eng.mbank_read_weights(r))
+        mine = [np.flatnonzero(land_of == l) for l in range(L)]
+        parts = [(four[l], xs[m].copy(), ys[m].copy(), angs[m].copy(), banks[m].copy()) for l, m in enumerate(mine)]
+
+        def on_set():
+            w0 = time.perf_counter()
+            eng.timer_start()
+            for _ in range(n_calls):
+                res = eng.mbank_sense_step_batch(xs, ys, angs, banks, land_of_member=land_of)
+            return eng.timer_stop() * 1e3 / n_calls, (time.perf_counter() - w0) * 1e6 / n_calls, res
+
+        def one_landscape():
+            eng.timer_start()
+            for _ in range(n_calls):
+                eng.mbank_sense_step_batch(xs, ys, angs, banks)
+            return eng.timer_stop() * 1e3 / n_calls
+
+        def four_engines():
+            w0 = time.perf_counter()
+            for _ in range(n_calls):
+                rows = [e.mbank_sense_step_batch(x, y, a, b) for e, x, y, a, b in parts]
+            return (time.perf_counter() - w0) * 1e6 / n_calls, rows
+
+        _, _, res = on_set()                                      # warm-up of all three (code load, clocks, the buffers)
+        one_landscape()
+        _, rows = four_engines()
+        assert not res.flags.any() and res.angle_familiarity.min() < 0
+        for m, row in zip(mine, rows):                            # the same bits as an engine of that landscape alone
+            assert np.array_equal(res.angle_familiarity[m], row.angle_familiarity) and np.array_equal(res.best_idex[m], row.best_idex)
+        ts, ws, t1, w4 = [], [], [], []
+        for _ in range(reps):                                     # alternating windows
+            a, b, _ = on_set()
+            ts.append(a)
+            ws.append(b)
+            t1.append(one_landscape())
+            w4.append(four_engines()[0])
+        out["layouts"].append(dict(members=n, headings=A, lands_us_per_step=spread(ts), one_landscape_us_per_step=spread(t1),
+                                   lands_over_one_landscape=round(float(np.median(ts) / np.median(t1)), 3),
+                                   lands_wall_us_per_step=spread(ws), four_engines_wall_us_per_step=spread(w4),
+                                   four_engines_over_lands_wall=round(float(np.median(w4) / np.median(ws)), 3)))
+        for e in four + [eng]:
+            e.close()
+    # training: L routes on L landscapes in one call on one engine, against one call per route on an engine each
+    engines = [engine(lands[l], HEADINGS[0])[1] for l in range(L)]
+    engines[0].lands_set(lands)
+    rng = np.random.default_rng(side + 7)
+    total = L * n_views
+    xs, ys, angs = rng.uniform(150, 390, total), rng.uniform(150, 390, total), rng.uniform(0, 2 * np.pi, total)
+    route_of = np.repeat(np.arange(L, dtype=np.int32), n_views)
+
+    def one_call():
+        eng = engines[0]
+        eng.mbank_set(N_BANKS)
+        w0 = time.perf_counter()
+        eng.timer_start()
+        eng.mbank_train_from_poses(xs, ys, angs, route_of, want_views=False, land_of_view=route_of)
+        return eng.timer_stop() * 1e3, (time.perf_counter() - w0) * 1e6
+
+    def call_per_route():
+        t = wall = 0.0
+        for r, eng in enumerate(engines):
+            eng.mbank_set(1)
+            sl = slice(r * n_views, (r + 1) * n_views)
+            w0 = time.perf_counter()
+            eng.timer_start()
+            eng.mb_train_from_poses(xs[sl], ys[sl], angs[sl], want_views=False)
+            t += eng.timer_stop() * 1e3
+            wall += (time.perf_counter() - w0) * 1e6
+        return t, wall
+
+    one_call()
+    zeros = engines[0].mbank_info()["n_depressed"].tolist()
+    call_per_route()
+    assert zeros == [e.mb_info()["n_depressed"] for e in engines] and all(0 < z <= K for z in zeros)
+    t1, t4, w1, w4 = [], [], [], []
+    for _ in range(reps):
+        a, b = one_call()
+        t1.append(a)
+        w1.append(b)
+        a, b = call_per_route()
+        t4.append(a)
+        w4.append(b)
+    out["train"] = dict(routes=L, views_per_route=n_views, one_lands_call_us=spread(t1), call_per_route_us=spread(t4),
+                        per_route_over_lands=round(float(np.median(t4) / np.median(t1)), 3), one_lands_call_wall_us=spread(w1),
+                        call_per_route_wall_us=spread(w4), per_route_over_lands_wall=round(float(np.median(w4) / np.median(w1)), 3),
+                        n_depressed=zeros)
+    for e in engines:
+        e.close()
+    print(json.dumps(out))
+
+
 METRIC_ROUTES, METRIC_MEMBERS, METRIC_HEADINGS, METRIC_SIDE = 4, 8, 16, 32
 METRIC_POINTS = (3500, 50000)
 
@@ -322,12 +455,13 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--limit", type=int, default=240, help="seconds allowed to each GPU child")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mushroom_time.json"))
-    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and the agent step), ensemble, banks, metrics")
+    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and the agent step), ensemble, banks, metrics, lands")
     ap.add_argument("--ensemble-calls", type=int, default=30, help="ensemble steps per timed window")
     ap.add_argument("--child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--ensemble-child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--banks-child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--metrics-child", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--lands-child", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
         gpu_child(args.child, args.views, args.calls, args.reps)
@@ -341,13 +475,16 @@ def main():
     if args.metrics_child:
         metrics_child(args.ensemble_calls, args.reps)
         return 0
+    if args.lands_child:
+        lands_child(args.lands_child, args.views, args.ensemble_calls, args.reps)
+        return 0
     blocks = args.blocks.split(",")
     result = dict(tool="tools/mushroom_time.py", timer="hipEvent pair (dv_timer_start/stop), median of %d windows after a warm-up" % args.reps,
-                  sizes=[], ensembles=[], banks=[], metrics=[])
+                  sizes=[], ensembles=[], banks=[], metrics=[], lands=[])
     if os.path.exists(args.out):                                  # a block that is not measured keeps its rows
         with open(args.out) as f:
             kept = json.load(f)
-        for block, key in (("single", "sizes"), ("ensemble", "ensembles"), ("banks", "banks"), ("metrics", "metrics")):
+        for block, key in (("single", "sizes"), ("ensemble", "ensembles"), ("banks", "banks"), ("metrics", "metrics"), ("lands", "lands")):
             if block not in blocks:
                 result[key] = kept.get(key, [])
     for side in [int(x) for x in args.sides.split(",")] if "ensemble" in blocks else []:
@@ -366,6 +503,14 @@ def main():
             print("GPU measurement of the banks of side %d ended with status %d: nothing more is run" % (side, p.returncode), file=sys.stderr)
             return p.returncode
         result["banks"].append(json.loads(p.stdout.strip().splitlines()[-1]))
+    for side in [int(x) for x in args.sides.split(",")] if "lands" in blocks else []:
+        cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--lands-child", str(side), "--views", str(args.views),
+               "--ensemble-calls", str(args.ensemble_calls), "--reps", str(args.reps)]
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, universal_newlines=True)
+        if p.returncode != 0:
+            print("GPU measurement of the landscape sets of side %d ended with status %d: nothing more is run" % (side, p.returncode), file=sys.stderr)
+            return p.returncode
+        result["lands"].append(json.loads(p.stdout.strip().splitlines()[-1]))
     if "metrics" in blocks:
         cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--metrics-child", "1",
                "--ensemble-calls", str(args.ensemble_calls), "--reps", str(args.reps)]

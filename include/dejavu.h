@@ -317,6 +317,30 @@ int dv_path_routes_error(dv_ctx *ctx, const int32_t *slots, const double *x, con
 int dv_path_routes_coverage(dv_ctx *ctx, int slot, uint8_t *out, int64_t n);
 int dv_path_routes_reset(dv_ctx *ctx, int slot);
 int dv_path_routes_info(dv_ctx *ctx, int *n_routes, int *n_slots, int64_t *n_points);
+/*
+ * The three coverage statistics of a trial's result row (percent_recapitulated, percent_recapitulated_forgiving, n_captures;
+ * NavBySceneFamiliarity.py:212-249) taken from the marks where they lie, instead of copying the marks out and looping over them on
+ * the host.  With n marks, run[p] the number of consecutive set marks ending at p (0 where mark p is clear) and `window` the number
+ * of marks the reference takes as int(n_consecutive_scenes * n), an entry's three int64 are
+ *     covered  = the number of set marks                                     (path coverage = covered / n)
+ *     furthest = the largest p + 1 with run[p] >= window, 0 without one      (forgiving coverage = furthest / n)
+ *     captures = the number of p in [window, n) with run[p] == window        (n_captures)
+ * which equal the reference's loops for every window >= 0 (window = 0: furthest = n, captures = the clear marks; window > n: both 0).
+ *   dv_marks_summary         the agent's marks (those dv_path_coverage copies out): out3 = int64[3].
+ *   dv_marks_summary_slots   n entries over the slots of dv_path_slots: entry i is slot slots[i] under window[i]; out = int64[n][3].
+ *   dv_marks_summary_routes  the same over the slots of dv_path_routes_slots, each as long as its own route.
+ * Entries are independent, and a slot may occur more than once with different windows.  The calls only read marks.  They run on the
+ * context's stream behind every metrics call made before them, and are synchronous: one upload of the entry table, one kernel launch
+ * per 65 535 entries (a workgroup per entry, DV_MARKS_PER_TRIP marks a trip, DV_MARKS_PER_THREAD per thread), one copy back and one
+ * wait.  Every slot and every window is checked before anything is enqueued: DV_ERR_INVALID names the first entry out of range or
+ * below 0.  Without a training path, slots or routes: DV_ERR_STATE.  n = 0: DV_OK, nothing happens.  Marks and index arithmetic are
+ * 64-bit: no length is refused.
+ */
+#define DV_MARKS_PER_THREAD 16
+#define DV_MARKS_PER_TRIP 4096
+int dv_marks_summary(dv_ctx *ctx, int64_t window, int64_t *out3);
+int dv_marks_summary_slots(dv_ctx *ctx, const int32_t *slots, const int64_t *window, int n, int64_t *out);
+int dv_marks_summary_routes(dv_ctx *ctx, const int32_t *slots, const int64_t *window, int64_t n, int64_t *out);
 
 /* ---- scoring ----------------------------------------------------------- */
 /* func(scene, fambuf) of util.pyx:14-20: fambuf[f] for one patch uint8[h,w,3] against every local view. */

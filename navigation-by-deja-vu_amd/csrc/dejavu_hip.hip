@@ -3706,4 +3706,5 @@ extern "C" int dv_stream_read_gbps(dv_ctx* c, int64_t n_bytes, int iters, double
 #include "dejavu_infomax.inl"   // dv_infomax_*: the Infomax familiarity model (kernels and host side)
 #include "dejavu_mushroom.inl"  // dv_mb_*: the mushroom-body familiarity model (kernels and host side)
 #include "dejavu_path_routes.inl"   // dv_path_routes_*: the error / coverage metrics against several routes (host side)
+#include "dejavu_marks.inl"     // dv_marks_*: the coverage statistics of a result row, from the marks on the device (kernel and host side)
 #include "dejavu_group.inl"     // dv_group_*: one process, several devices -- host logic above the C ABI

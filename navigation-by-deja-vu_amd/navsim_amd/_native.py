@@ -23,6 +23,8 @@ DV_RES_SENSE_ERROR = 16
 DV_DIFFUSE_AUTO = 0
 DV_DIFFUSE_PLAIN = 1
 DV_DIFFUSE_BLOCKED = 2
+DV_MARKS_PER_THREAD = 16                 # k_marks_summary: marks a thread takes in a trip of its workgroup ...
+DV_MARKS_PER_TRIP = 4096                 # ... and a workgroup of 256 threads (include/dejavu.h)
 
 ERROR_NAMES = {-1: "DV_ERR_INVALID", -2: "DV_ERR_HIP", -3: "DV_ERR_STATE", -4: "DV_ERR_OOM", -5: "DV_ERR_INDEX"}
 
@@ -170,6 +172,9 @@ PROTOTYPES = {
     "dv_path_routes_coverage": (ctypes.c_int, [_ctx_p, ctypes.c_int, _u8p, ctypes.c_int64]),
     "dv_path_routes_reset": (ctypes.c_int, [_ctx_p, ctypes.c_int]),
     "dv_path_routes_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _i64p]),
+    "dv_marks_summary": (ctypes.c_int, [_ctx_p, ctypes.c_int64, _i64p]),
+    "dv_marks_summary_slots": (ctypes.c_int, [_ctx_p, _i32p, _i64p, ctypes.c_int, _i64p]),
+    "dv_marks_summary_routes": (ctypes.c_int, [_ctx_p, _i32p, _i64p, ctypes.c_int64, _i64p]),
     "dv_score": (ctypes.c_int, [_ctx_p, _u8p, _f64p]),
     "dv_step": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(StepResult), _f64p]),
     "dv_step_batch": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, ctypes.c_uint32,

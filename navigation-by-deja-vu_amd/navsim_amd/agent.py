@@ -116,6 +116,30 @@ def downscale_chem(image, factor_rows, factor_cols):
     return out
 
 
+def marks_summary_host(marks, window):
+    """(covered, furthest, captures) of coverage marks under a window of `window` marks, as Python ints: the three coverage metrics of
+    the reference (percent_recapitulated, percent_recapitulated_forgiving, n_captures; :212-249) restated over run[p], the number of
+    consecutive set marks ending at p (0 where mark p is clear):
+        covered  = the number of set marks
+        furthest = the largest p + 1 with run[p] >= window, 0 without one     (the forgiving loop returns i / n for the largest i whose
+                   `window` marks before it are all set: run[i - 1] >= window)
+        captures = the number of p in [window, n) with run[p] == window       (the capture loop counts the clear marks i followed by
+                   `window` set ones: the run ending at p = i + window is exactly `window` long)
+    The device's statement of the same (FamiliarityEngine.marks_summary*) and this one are held to the loops by the tests."""
+    m = np.asarray(marks) != 0
+    n = len(m)
+    idx = np.arange(n, dtype=np.int64)
+    run = idx - np.maximum.accumulate(np.where(m, -1, idx))      # p - (the last clear mark at or before p; -1 when there is none)
+    reached = np.flatnonzero(run >= window)
+    return (int(np.count_nonzero(m)), int(reached[-1]) + 1 if len(reached) else 0,
+            int(np.count_nonzero(run[window:] == window)) if window <= n else 0)
+
+
+def coverage_row(covered, furthest, captures, n):
+    """The three coverage columns of a result row from a summary of n marks, in the types the agent's three methods give."""
+    return {"path_coverage": np.int64(covered) / n, "percent_forgiving": int(furthest) / n, "n_captures": int(captures)}
+
+
 class NavBySceneFamiliarity(object):
     """Agent that walks a landscape by scene familiarity (navsim/NavBySceneFamiliarity.py:57-329).
 
@@ -493,6 +517,22 @@ class NavBySceneFamiliarity(object):
             if (not cov[i]) and np.all(cov[i + 1:i + 1 + win]):
                 count += 1
         return count
+
+    def coverage_summary(self, n_consecutive_scenes=0.05):
+        """{"path_coverage", "percent_forgiving", "n_captures"}: percent_recapitulated, percent_recapitulated_forgiving(n_consecutive_scenes)
+        and n_captures(n_consecutive_scenes) in one pass over the marks -- on the device, where the agent's marks are there and its
+        engine has the call (FamiliarityEngine.marks_summary), else marks_summary_host on the marks the three methods read."""
+        if n_consecutive_scenes < 0:
+            raise ValueError("n_consecutive_scenes must be >= 0, got %r" % (n_consecutive_scenes,))
+        win = self._window(n_consecutive_scenes)
+        on_device = (getattr(self, "_metric_slot", None) is None and getattr(self, "_metrics_on_device", False)
+                     and self.training_path is not None and callable(getattr(self._engine, "marks_summary", None)))
+        if on_device:
+            self._collect_errors()
+            got = self._engine.marks_summary(win).tolist()
+        else:
+            got = marks_summary_host(self._coverage_array, win)      # (flushes or collects what is pending, wherever the marks are)
+        return coverage_row(got[0], got[1], got[2], len(self.training_path))
 
     def update_error(self):
         self.navigated_for_frames += 1

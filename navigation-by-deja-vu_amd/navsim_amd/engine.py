@@ -718,6 +718,7 @@ class FamiliarityEngine(object):
     # -- error / coverage metrics on the device (NavBySceneFamiliarity.py:252-276) ----------------
     def set_training_path(self, points):
         """points: float64[n, 2] (x, y), or None to detach.  Clears the coverage marks."""
+        self._path_slot_count = None                             # (the library drops the slots with the path)
         if points is None:
             self._check(self._lib.dv_set_training_path(self._ctx, None, 0), "dv_set_training_path")
             return
@@ -763,6 +764,7 @@ class FamiliarityEngine(object):
     # update_error for the agents of an ensemble: a coverage array per agent (slot) on the device
     def path_slots(self, n_slots):
         self._check(self._lib.dv_path_slots(self._ctx, int(n_slots)), "dv_path_slots")
+        self._path_slot_count = int(n_slots) or None
 
     def path_error_batch(self, slots, xs, ys, reach):
         """nearest[i] of agent slots[i] at (xs[i], ys[i]) (NavBySceneFamiliarity.py:252-276 for all of them at once); its marks updated."""
@@ -900,6 +902,58 @@ class FamiliarityEngine(object):
         nr, ns, npts = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
         self._check(self._lib.dv_path_routes_info(self._ctx, ctypes.byref(nr), ctypes.byref(ns), ctypes.byref(npts)), "dv_path_routes_info")
         return dict(n_routes=nr.value, n_slots=ns.value, n_points=npts.value)
+
+    # -- the coverage statistics of a result row, from the marks on the device (include/dejavu.h: dv_marks_*) ---------------------------
+    _path_slot_count = None      # the slots of the one training path (path_slots); None: none made through this engine
+
+    @staticmethod
+    def _marks_window(window, what="window"):
+        if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 0:
+            raise ValueError("%s must be an integer >= 0, got %r" % (what, window))
+        return int(window)
+
+    @staticmethod
+    def _marks_windows(windows, n):
+        arr = np.asarray(windows)
+        if arr.shape == (0,):
+            arr = arr.astype(np.int64)
+        if arr.dtype.kind not in "iu":
+            raise ValueError("windows must hold integers, got dtype %s" % arr.dtype)
+        if arr.shape != (n,):
+            raise ValueError("windows must have shape (%d,), one per entry of slots, got %r" % (n, arr.shape))
+        if n and arr.min() < 0:
+            bad = int(np.flatnonzero(arr < 0)[0])
+            raise ValueError("windows[%d] = %d < 0" % (bad, arr[bad]))
+        return np.ascontiguousarray(arr, dtype=np.int64)
+
+    def marks_summary(self, window):
+        """int64[3] = (covered, furthest, captures) of the agent's marks (those path_coverage copies out) under `window` marks:
+        the set marks; the largest p + 1 such that the `window` marks ending at p are all set (0 without one); the runs of exactly
+        `window` set marks behind a clear mark.  Over n marks they are percent_recapitulated * n, percent_recapitulated_forgiving * n
+        and n_captures of the reference (NavBySceneFamiliarity.py:212-249)."""
+        window = self._marks_window(window)
+        out = np.empty(3, dtype=np.int64)
+        self._check(self._lib.dv_marks_summary(self._ctx, window, N.i64ptr(out)), "dv_marks_summary")
+        return out
+
+    def _marks_summary_many(self, symbol, slots, windows, n_slots, made_by):
+        if n_slots is None:
+            raise ValueError("no slots set (%s)" % made_by)
+        slots = self._route_ints(slots, "slots", n_slots, "n_slots")
+        n = len(slots)
+        windows = self._marks_windows(windows, n)
+        out = np.empty((n, 3), dtype=np.int64)
+        self._check(getattr(self._lib, symbol)(self._ctx, slots.ctypes.data_as(N._i32p), N.i64ptr(windows), n, N.i64ptr(out)), symbol)
+        return out
+
+    def marks_summary_slots(self, slots, windows):
+        """marks_summary for n entries at once over the slots of path_slots: int64[n, 3], entry i slot slots[i] under windows[i]."""
+        return self._marks_summary_many("dv_marks_summary_slots", slots, windows, self._path_slot_count, "path_slots")
+
+    def marks_summary_routes(self, slots, windows):
+        """marks_summary for n entries at once over the slots of path_routes_slots, each as long as its own route: int64[n, 3]."""
+        return self._marks_summary_many("dv_marks_summary_routes", slots, windows,
+                                        None if self._route_of_slot is None else len(self._route_of_slot), "path_routes_slots")
 
     def stream_read_gbps(self, n_bytes=1 << 30, iters=10):
         g = ctypes.c_double(0)

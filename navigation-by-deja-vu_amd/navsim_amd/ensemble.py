@@ -18,7 +18,7 @@ single agent works its minimum out when it is read.
 """
 import numpy as np
 
-from .agent import StopNavigationException, OutOfLandscapeBoundsException
+from .agent import StopNavigationException, OutOfLandscapeBoundsException, coverage_row
 from .util import reject_infomax, reject_mushroom, reject_banked
 
 
@@ -109,6 +109,35 @@ class NavEnsemble(object):
 
     def _reset_marks(self, agent):
         self.engine.path_reset_slot(agent._metric_slot)
+
+    _summary_call = "marks_summary_slots"     # the engine call `_marks_summary` makes
+
+    def _marks_summary(self, members, windows):
+        """int64[n, 3]: (covered, furthest, captures) of every member's slot under its own window, in one device call."""
+        return self.engine.marks_summary_slots([a._metric_slot for a in members], windows)
+
+    def coverage_summary(self, n_consecutive_scenes=0.05):
+        """One {"path_coverage", "percent_forgiving", "n_captures"} per member: what its percent_recapitulated,
+        percent_recapitulated_forgiving(n_consecutive_scenes) and n_captures(n_consecutive_scenes) give.  The members whose marks lie in
+        a slot on the device are all answered by ONE device call, each under the window of its own route's length; a member without a
+        slot, and every member where the engine has no such call, by its own three methods."""
+        if n_consecutive_scenes < 0:
+            raise ValueError("n_consecutive_scenes must be >= 0, got %r" % (n_consecutive_scenes,))
+        rows = [None] * len(self.agents)
+        held = [i for i, a in enumerate(self.agents) if getattr(a, "_metric_slot", None) is not None and getattr(a, "_ens", None) is self
+                and a.training_path is not None]
+        if held and callable(getattr(self.engine, self._summary_call, None)):
+            self._flush_errors()
+            members = [self.agents[i] for i in held]
+            got = self._marks_summary(members, [a._window(n_consecutive_scenes) for a in members])
+            for i, a, (covered, furthest, captures) in zip(held, members, got.tolist()):
+                rows[i] = coverage_row(covered, furthest, captures, len(a.training_path))
+        for i, a in enumerate(self.agents):
+            if rows[i] is None:
+                rows[i] = {"path_coverage": a.percent_recapitulated,
+                           "percent_forgiving": a.percent_recapitulated_forgiving(n_consecutive_scenes=n_consecutive_scenes),
+                           "n_captures": a.n_captures(n_consecutive_scenes=n_consecutive_scenes)}
+        return rows
 
     @classmethod
     def from_agent(cls, agent, poses, chem_weights=None):
@@ -453,6 +482,11 @@ class _RouteEnsemble(_OneValueEnsemble):
 
     def _reset_marks(self, agent):
         self.engine.path_routes_reset(agent._metric_slot)
+
+    _summary_call = "marks_summary_routes"
+
+    def _marks_summary(self, members, windows):
+        return self.engine.marks_summary_routes([a._metric_slot for a in members], windows)
 
     @classmethod
     def _reject_banked(cls, agent):

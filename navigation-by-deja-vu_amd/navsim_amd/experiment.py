@@ -78,13 +78,19 @@ def run_experiment(nsf, frames=None):
     except StopNavigationException as stop:
         status = stop.get_code()
         nsf.stopped_with_exception = stop
+    if callable(getattr(nsf, "coverage_summary", None)):          # the three coverage columns from one pass over the marks
+        cover = nsf.coverage_summary(N_CONSECUTIVE_SCENES)
+    else:
+        cover = {"path_coverage": nsf.percent_recapitulated,
+                 "percent_forgiving": nsf.percent_recapitulated_forgiving(n_consecutive_scenes=N_CONSECUTIVE_SCENES),
+                 "n_captures": nsf.n_captures(n_consecutive_scenes=N_CONSECUTIVE_SCENES)}
     return {
-        "path_coverage": nsf.percent_recapitulated,
+        "path_coverage": cover["path_coverage"],
         "rmsd_error": nsf.navigation_error,
         "completed_frames": completed,
         "stop_status": status,
-        "percent_forgiving": nsf.percent_recapitulated_forgiving(n_consecutive_scenes=N_CONSECUTIVE_SCENES),
-        "n_captures": nsf.n_captures(n_consecutive_scenes=N_CONSECUTIVE_SCENES),
+        "percent_forgiving": cover["percent_forgiving"],
+        "n_captures": cover["n_captures"],
     }
 
 
@@ -95,15 +101,16 @@ def run_ensemble(ens, frames=None):
         # every member its own trial's count (members on one path: one value, as a lone run_experiment gives each)
         frames = [int(FRAME_FACTOR * nsf.training_path_length / nsf.step_size) for nsf in ens.agents]
     done = ens.run(frames)
+    cover = ens.coverage_summary(N_CONSECUTIVE_SCENES)            # every member's three coverage columns: one device call for all
     rows = []
     for i, nsf in enumerate(ens.agents):
         scored = nsf._n_navigation_error > 0                      # an agent stopped before its first step has no error yet
         rows.append({
-            "path_coverage": nsf.percent_recapitulated,
+            "path_coverage": cover[i]["path_coverage"],
             "rmsd_error": nsf.navigation_error if scored else float("nan"),
             "completed_frames": done[i],
             "stop_status": ens.stop_status[i],
-            "percent_forgiving": nsf.percent_recapitulated_forgiving(n_consecutive_scenes=N_CONSECUTIVE_SCENES),
-            "n_captures": nsf.n_captures(n_consecutive_scenes=N_CONSECUTIVE_SCENES),
+            "percent_forgiving": cover[i]["percent_forgiving"],
+            "n_captures": cover[i]["n_captures"],
         })
     return rows

@@ -2,7 +2,7 @@
 """Times the mushroom-body familiarity model (navsim_amd.mushroom_familiarity; include/dejavu.h: dv_mb_*) on GPU 0 and writes
 profiles/mushroom_time.json.
 
-    python tools/mushroom_time.py [--sides 32,64] [--views 1000] [--calls 200] [--reps 5] [--blocks single,ensemble[,banks][,metrics][,lands]]
+    python tools/mushroom_time.py [--sides 32,64] [--views 1000] [--calls 200] [--reps 5] [--blocks single,ensemble[,banks][,metrics][,lands][,rows]]
                                   [--out profiles/mushroom_time.json]
 
 Per sensor side s (views of s x s) with K = 20000 Kenyon cells, fan-in 10 and 200 firing cells: microseconds per agent step
@@ -40,6 +40,14 @@ every engine stepping its landscape's members in turn -- what a user did before 
 streams have no common event pair), ratio four_engines_over_lands_wall; the four engines' rows are checked to be the one call's bits;
 (c) 4 routes of --views views on the 4 landscapes trained in ONE dv_lands_mbank_train_from_poses call against four
 dv_mb_train_from_poses calls on four engines (the sum of their timers, and wall clock).
+
+Rows block (--blocks rows): the metrics block's MushroomRouteEnsemble with metrics="device" (4 routes x 8 members, both route sizes),
+stepped --row-frames frames; then the three coverage columns of all members' result rows built two ways in alternating windows of the
+same child process -- (a) every member's percent_recapitulated, percent_recapitulated_forgiving(0.05) and n_captures(0.05), as
+run_ensemble built them before: three copies of the member's marks and two Python loops over them; (b) ens.coverage_summary(0.05): one
+dv_marks_summary_routes call for all members -- WALL-CLOCK microseconds per build of all rows, Python included (a window is one build
+of (a), 20 of (b)), their ratio methods_over_summary; and alone: the 3 x 32 path_routes_coverage copies of (a) without its loops (wall
+clock), and the marks_summary_routes call between a hipEvent pair.  The two builds are checked to give equal rows.
 
 A block that is not measured keeps the rows it has in the output file.
 
@@ -431,6 +439,81 @@ def metrics_child(n_calls, reps):
     print(json.dumps(out))
 
 
+def rows_child(n_frames, reps):
+    """The rows block on the GPU -> one JSON line on stdout."""
+    from navsim_amd import MushroomRouteEnsemble, NavBySceneFamiliarity, mushroom_familiarity, synth
+    from navsim_amd.experiment import N_CONSECUTIVE_SCENES as FRAC
+    land = synth.synth_landscape(3, 600, 4)
+    summary_builds = 20
+    out = dict(side=METRIC_SIDE, routes=METRIC_ROUTES, members=METRIC_ROUTES * METRIC_MEMBERS, headings=METRIC_HEADINGS, n_kc=K,
+               frames_stepped=n_frames, n_consecutive_scenes=FRAC,
+               timer="wall clock (time.perf_counter) around the build of all members' coverage columns, median of %d windows; "
+                     "a window is 1 build by the three methods, %d by coverage_summary" % (reps, summary_builds), sizes=[])
+    for target in METRIC_POINTS:
+        routes = [synth.sin_training_path(c, 100, 400, arclen=400 * np.sqrt(2.0) / target) for c in (0.0, 0.2, 0.4, 0.6)]
+        starts = []
+        for r, route in enumerate(routes):
+            for m in range(METRIC_MEMBERS):
+                k = (1 + m) * len(route) // (4 * METRIC_MEMBERS)                        # along the route's first quarter
+                d = route[k + 1] - route[k]
+                starts.append((r, (float(route[k][0] + 0.3), float(route[k][1] - 0.2)), float(np.arctan2(d[1], d[0]) % (2 * np.pi))))
+        agent = NavBySceneFamiliarity(land, (METRIC_SIDE, METRIC_SIDE), 1.0, n_test_angles=METRIC_HEADINGS, familiarity_model=mushroom_familiarity())
+        ens = MushroomRouteEnsemble.from_routes_with(agent, routes, starts, metrics="device")
+        for _ in range(n_frames):
+            ens.step_forward()
+        eng = ens.engine
+
+        def by_methods():
+            t0 = time.perf_counter()
+            rows = [{"path_coverage": a.percent_recapitulated, "percent_forgiving": a.percent_recapitulated_forgiving(n_consecutive_scenes=FRAC),
+                     "n_captures": a.n_captures(n_consecutive_scenes=FRAC)} for a in ens.agents]
+            return (time.perf_counter() - t0) * 1e6, rows
+
+        def by_summary():
+            t0 = time.perf_counter()
+            for _ in range(summary_builds):
+                rows = ens.coverage_summary(FRAC)
+            return (time.perf_counter() - t0) * 1e6 / summary_builds, rows
+
+        def copies():
+            t0 = time.perf_counter()
+            for a in ens.agents:
+                for _ in range(3):
+                    eng.path_routes_coverage(a._metric_slot, len(a.training_path))
+            return (time.perf_counter() - t0) * 1e6
+
+        slots = np.arange(len(ens.agents), dtype=np.int32)
+        wins = np.array([a._window(FRAC) for a in ens.agents], dtype=np.int64)
+
+        def call_alone():
+            eng.timer_start()
+            for _ in range(summary_builds):
+                eng.marks_summary_routes(slots, wins)
+            return eng.timer_stop() * 1e3 / summary_builds
+
+        _, rows_a = by_methods()                                                        # warm-up of all (code load, clocks, the buffers)
+        _, rows_b = by_summary()
+        copies()
+        call_alone()
+        assert rows_a == rows_b, "the two builds differ"
+        ta, tb, tc, td = [], [], [], []
+        for _ in range(reps):                                                           # alternating windows, the same marks
+            ta.append(by_methods()[0])
+            tb.append(by_summary()[0])
+            tc.append(copies())
+            td.append(call_alone())
+        covered = [r["path_coverage"] for r in rows_b]
+        out["sizes"].append(dict(route_points=[len(r) for r in routes], windows=sorted(set(wins.tolist())),
+                                 three_methods_us_per_build=spread(ta), coverage_summary_us_per_build=spread(tb),
+                                 methods_over_summary=round(float(np.median(ta) / np.median(tb)), 1),
+                                 coverage_copies_alone_us=spread(tc), marks_summary_routes_event_us_per_call=spread(td),
+                                 path_coverage_min_max=[round(float(min(covered)), 4), round(float(max(covered)), 4)],
+                                 members_running=len(ens.active), rows_equal=True))
+        ens.agents[0].clear_training()
+        eng.close()
+    print(json.dumps(out))
+
+
 def cpu_row(side, n_calls):
     """The NumPy statement on this host: wall clock, microseconds per call that scores A patches."""
     from tests import helpers_mushroom as H
@@ -455,13 +538,15 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--limit", type=int, default=240, help="seconds allowed to each GPU child")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mushroom_time.json"))
-    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and the agent step), ensemble, banks, metrics, lands")
+    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and the agent step), ensemble, banks, metrics, lands, rows")
     ap.add_argument("--ensemble-calls", type=int, default=30, help="ensemble steps per timed window")
     ap.add_argument("--child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--ensemble-child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--banks-child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--metrics-child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--lands-child", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--rows-child", type=int, default=0, help=argparse.SUPPRESS)
+    ap.add_argument("--row-frames", type=int, default=300, help="frames the rows block steps its ensemble before it builds the rows")
     args = ap.parse_args()
     if args.child:
         gpu_child(args.child, args.views, args.calls, args.reps)
@@ -478,13 +563,16 @@ def main():
     if args.lands_child:
         lands_child(args.lands_child, args.views, args.ensemble_calls, args.reps)
         return 0
+    if args.rows_child:
+        rows_child(args.row_frames, args.reps)
+        return 0
     blocks = args.blocks.split(",")
     result = dict(tool="tools/mushroom_time.py", timer="hipEvent pair (dv_timer_start/stop), median of %d windows after a warm-up" % args.reps,
-                  sizes=[], ensembles=[], banks=[], metrics=[], lands=[])
+                  sizes=[], ensembles=[], banks=[], metrics=[], lands=[], rows=[])
     if os.path.exists(args.out):                                  # a block that is not measured keeps its rows
         with open(args.out) as f:
             kept = json.load(f)
-        for block, key in (("single", "sizes"), ("ensemble", "ensembles"), ("banks", "banks"), ("metrics", "metrics"), ("lands", "lands")):
+        for block, key in (("single", "sizes"), ("ensemble", "ensembles"), ("banks", "banks"), ("metrics", "metrics"), ("lands", "lands"), ("rows", "rows")):
             if block not in blocks:
                 result[key] = kept.get(key, [])
     for side in [int(x) for x in args.sides.split(",")] if "ensemble" in blocks else []:
@@ -519,6 +607,14 @@ def main():
             print("GPU measurement of the route ensembles' metrics ended with status %d: nothing more is run" % p.returncode, file=sys.stderr)
             return p.returncode
         result["metrics"].append(json.loads(p.stdout.strip().splitlines()[-1]))
+    if "rows" in blocks:
+        cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--rows-child", "1",
+               "--row-frames", str(args.row_frames), "--reps", str(args.reps)]
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, universal_newlines=True)
+        if p.returncode != 0:
+            print("GPU measurement of the result rows ended with status %d: nothing more is run" % p.returncode, file=sys.stderr)
+            return p.returncode
+        result["rows"].append(json.loads(p.stdout.strip().splitlines()[-1]))
     for side in [int(x) for x in args.sides.split(",")] if "single" in blocks else []:
         cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--child", str(side), "--views", str(args.views),
                "--calls", str(args.calls), "--reps", str(args.reps)]

@@ -842,12 +842,14 @@ int dv_patches_on_level(dv_ctx *ctx);
 /* Form of the last integer scoring pass, as flags: DV_FORM_MATRIX_CORES (bit-plane library on the matrix cores, workgroup
  * shape 6), DV_FORM_FP4 (its fp4 coefficients: the prep's patches were on-level), DV_FORM_FUSED_FINISH (the kernel
  * finished its scores itself; the step ended in k_fold), DV_FORM_CODES (the fp4 form's body read the value rows as 3-bit level
- * codes, the code tiles of dv_lib_info.code_tile_bytes).  Waits for the stream when the fp4 word has to be read.
+ * codes, the code tiles of dv_lib_info.code_tile_bytes), DV_FORM_CONSUMERS8 (... in the registers of all eight waves of a workgroup,
+ * items of 16 view groups: DEJAVU_LREG8).  Waits for the stream when the fp4 word has to be read.
  * Diagnostic for benchmarks and tests; negative on error. */
 #define DV_FORM_MATRIX_CORES 1
 #define DV_FORM_FP4 2
 #define DV_FORM_FUSED_FINISH 4
 #define DV_FORM_CODES 8
+#define DV_FORM_CONSUMERS8 16
 int dv_scoring_form(dv_ctx *ctx);
 
 const char *dv_version(void);

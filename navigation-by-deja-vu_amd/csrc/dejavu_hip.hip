@@ -185,6 +185,7 @@ struct dv_ctx {
     int vcode_env = -1;
     bool code_all = false;                    // DEJAVU_VCODE=1 and the tiles exist
     bool last_codes = false;                  // the last matrix-core pass was launched with a body that reads code rows
+    bool last_consumers8 = false;             // ... into the registers of all eight waves (LcRegCode8)
     int last_form = 0;                        // DV_FORM_* of the last integer scoring pass (fp4 bit: the fp4 image existed)
     int fuse_env = 1;                         // DEJAVU_FUSE=0: one-chunk matrix-core passes leave their sums to k_finish instead of finishing them
     int lc_env = 1;                           // DEJAVU_LC: 0 every wave loads and multiplies, 1 loader / consumer waves (stages of 4, ring of 3), 2 (stages of 2, ring of 5)
@@ -225,6 +226,7 @@ struct dv_ctx {
     int deferred_force = 0, deferred_seq = 0; // ... with these arguments
     int lc22_env = 1;                         // DEJAVU_LC22=0: passes of 64 headings keep one view group per consumer (sad_lc_fp4 with two heading tiles; A/B)
     int lreg_env = 1;                         // DEJAVU_LIBREG=0: single-pass fp4 steps of 32 headings keep the library rows in the LDS ring (sad_lc_fp4; A/B)
+    int lreg8_env = -1;                       // DEJAVU_LREG8: 0 the register-ring body on code rows never has eight consumer waves, 1 wherever it fits (tests); unset: mfma_plan's rule
     int chain_order_env = -1;                 // DEJAVU_CHAIN_ORDER (A/B): how a chain of ensemble passes is laid out on its stream, see run_batch
     int chains_env = 2;                       // DEJAVU_CHAINS=1: ensemble passes one after the other on one stream, as in round 3 (A/B)
     StepResultDev* h_result = nullptr;        // pinned, mapped: the kernels write the result record into it
@@ -481,6 +483,7 @@ extern "C" int dv_create(dv_ctx** out, int device_id) {
     env_int("DEJAVU_CHAIN_ORDER", c->chain_order_env, -1, 2);
     env_int("DEJAVU_LC22", c->lc22_env, 0, 1);
     env_int("DEJAVU_LIBREG", c->lreg_env, 0, 1);
+    env_int("DEJAVU_LREG8", c->lreg8_env, 0, 1);
     env_int("DEJAVU_NT", c->nt_env, 0, 1);
     env_int("DEJAVU_TEST_FAIL_ALLOC", c->fail_alloc_env, 0, 64);
     env_int("DEJAVU_DIFFUSE_AUTO", c->diff_auto_env, 1, 2);
@@ -2090,7 +2093,7 @@ extern "C" int dv_scoring_form(dv_ctx* c) {
     if (!(c->last_form & DV_FORM_FP4)) return c->last_form;
     const int on_level = read_on_level(c);                 // the dual kernel ran: which image it took is on the device
     if (on_level < 0) return on_level;
-    return on_level ? c->last_form : c->last_form & ~(DV_FORM_FP4 | DV_FORM_CODES);    // (the int8 form reads the bit tiles)
+    return on_level ? c->last_form : c->last_form & ~(DV_FORM_FP4 | DV_FORM_CODES | DV_FORM_CONSUMERS8);    // (the int8 form reads the bit tiles)
 }
 
 extern "C" int dv_clear_library(dv_ctx* c) {
@@ -2345,11 +2348,12 @@ static FuseArgs fuse_args(const dv_ctx* c) {
 //   Lc, LcShort, LcCode, LcReg, LcRegCode: loader and consumer waves (sad_lc_fp4) -- stages of 4 K-steps and a ring of 3, stages of 2
 //     and a ring of 5 (DEJAVU_LC=2), 3-bit code rows (DEJAVU_VCODE=1), the library rows in the consumers' registers
 //     (sad_lc_fp4_lreg), and those with the value rows as 3-bit codes (where the code tiles were built);
+//   LcRegCode8: the code rows in the registers of all eight waves (sad_lc_fp4_lreg8: no loader waves, items of 16 view groups);
 //   Lc2Tiles, Lc2TilesCode: sad_lc_fp4 with two heading tiles per view group (64 resident headings in one pass);
 //   Lc22: k_sad_lc22, two view groups x two heading tiles per consumer (fused finishing only).
 // Every fp4 body has the int8 ring body <SK8, TILES, RD8> beside it for off-level patches, and the loader / consumer bodies the fp4
 // ring body <SK4, TILES, RD4> for chunked passes.
-enum class Body { Ring, Ring2, RingA, RingB, Lc, LcShort, LcCode, LcReg, LcRegCode, Lc2Tiles, Lc2TilesCode, Lc22, Count };
+enum class Body { Ring, Ring2, RingA, RingB, Lc, LcShort, LcCode, LcReg, LcRegCode, LcRegCode8, Lc2Tiles, Lc2TilesCode, Lc22, Count };
 
 // <int8 stage, ring | fp4 stage, ring (ring body) | view groups per wave | fp4 stage, ring (loader / consumer body; stage 0: none),
 // code rows, heading tiles per view group>: the template arguments of k_sad_mfma_dual (k_sad_lc22: SKL, RDL; it has no fp4 ring
@@ -2366,6 +2370,7 @@ constexpr BodyShape kBodyShapes[] = {
     /* LcCode       */ {4, 2, 2, 4, 1, 4, 3, true, 1},
     /* LcReg        */ {4, 2, 2, 4, 1, kLregStage, 3, false, 1},
     /* LcRegCode    */ {4, 2, 2, 4, 1, kLregStage, 3, true, 1},
+    /* LcRegCode8   */ {4, 2, 2, 4, 1, kLreg8Sel, 3, true, 1},
     /* Lc2Tiles     */ {4, 2, 2, 4, 1, 4, 3, false, 2},
     /* Lc2TilesCode */ {4, 2, 2, 4, 1, 4, 3, true, 2},
     /* Lc22         */ {4, 2, 0, 0, 1, 2, 3, false, 2},
@@ -2382,8 +2387,8 @@ constexpr auto body_kernel() {
 }
 
 // View groups of 32 per work item of a body: 8 waves x TILES groups, shared among the heading tiles (Lc22: two groups for each of its
-// four consumers).
-constexpr int body_view_groups(Body b) { return b == Body::Lc22 ? 8 : 8 * body_shape(b).TILES / body_shape(b).HT; }
+// four consumers; LcRegCode8: two groups for each of its eight consumers, which its ring bodies take as two ranges of 8).
+constexpr int body_view_groups(Body b) { return b == Body::Lc22 ? 8 : b == Body::LcRegCode8 ? 16 : 8 * body_shape(b).TILES / body_shape(b).HT; }
 
 // Dynamic LDS of a body's kernel: the largest of its bodies' rings -- [RD][coefficient rows SK * 8 | library rows 8 waves x SK x TILES]
 // of 1 KB for the int8 one (sad_ring_i8) -- then the fused finishing's scratch (a second heading tile adds its 64 running-summary
@@ -2396,6 +2401,7 @@ constexpr int body_lds_bytes() {
     int lc = 0;
     if constexpr (B == Body::Lc22) lc = lc22_ring_bytes<s.SKL, s.RDL>() + kLc22ParkBytes;
     else if constexpr (s.SKL == kLregStage) lc = lreg_ring_bytes<s.SKL, s.RDL>();
+    else if constexpr (s.SKL == kLreg8Sel) lc = lreg_ring_bytes<kLregStage, s.RDL>();
     else if constexpr (s.SKL > 0) lc = lc_ring_bytes<s.SKL, s.RDL>();
     if (lc > ring) ring = lc;
     return ring + (FUSE ? kFuseScratchBytes + (s.HT - 1) * 512 : 0);
@@ -2436,6 +2442,7 @@ static void launch_body(dv_ctx* c, int nchunk, int has_hs) {
     bcfg.vcode = s.LCODE ? 1 : 0;
     const uint4* ftiles = s.LCODE ? c->d_ctiles : c->d_btiles;
     c->last_codes = s.LCODE && nchunk == 1;
+    c->last_consumers8 = B == Body::LcRegCode8 && nchunk == 1;
     for (int a_off = 0; a_off < c->APAD; a_off += 32 * s.HT) {
         const uint4* coef = c->d_coef + (size_t)(a_off / 32) * nkt * 512;
         const uint4* coef4 = c->fp4_ok ? c->d_coef4 + (size_t)(a_off / 32) * nkt * 256 : nullptr;
@@ -2477,6 +2484,10 @@ static bool lreg_fits(const dv_ctx* c) {
 // ... and with the value rows as codes: value K-steps, in whole stages of eight (two code stages of four, k_bitpack_code).
 static bool lreg_code_fits(const dv_ctx* c) {
     return lreg_fits(c) && c->cfg.hasv && c->bcfg.T[1] == 4 && c->bcfg.NK[1] > 0 && c->bcfg.NK[1] % kLregStage == 0;
+}
+// ... and in all eight waves' registers (sad_lc_fp4_lreg8): the same stages
+static bool lreg8_fits(const dv_ctx* c) {
+    return lreg_code_fits(c);
 }
 
 // A matrix-core pass over the resident library for `apad` resident headings: the body, the chunks its K-steps are cut into, and
@@ -2528,12 +2539,19 @@ static MfmaPlan mfma_plan(dv_ctx* c, int apad, bool fuse_request, bool assume_co
     // (Lc22 was chosen with may_fuse and >= 160 ranges, lc22_fits excludes the mixed layout: one chunk, fused)
     if (body == Body::Lc && nchunk == 1 && c->lreg_env && lreg_fits(c)) body = Body::LcReg;
     if (body == Body::LcReg && (c->d_ctiles || assume_code_tiles) && lreg_code_fits(c)) body = Body::LcRegCode;
+    // Eight consumer waves and items of 16 view groups where those still fill two rounds of the 256 workgroups (500 000 views x 128x128:
+    // 977 items; 50 000 x 64x64 has 98 and the ensemble block's 100 000 x 128x128 196: they keep four consumers and items of 8).
+    // DEJAVU_LREG8 = 1: whatever the item count (tests), 0: never.  (measured at 500 000 views.)
+    if (body == Body::LcRegCode && lreg8_fits(c) && c->lreg8_env != 0 &&
+        (c->lreg8_env == 1 || item_groups(G32, body_view_groups(Body::LcRegCode8)) >= 512))
+        body = Body::LcRegCode8;
     return {body, nchunk, fuse_request && c->fuse_env && nchunk == 1};
 }
 
 // build_bit_planes, before it builds the code tiles by default: this library's single-pass step of <= 32 headings would read them.
 static bool plan_reads_codes(dv_ctx* c) {
-    return mfma_plan(c, 32, true, true).body == Body::LcRegCode;
+    const Body body = mfma_plan(c, 32, true, true).body;
+    return body == Body::LcRegCode || body == Body::LcRegCode8;
 }
 
 // An ensemble pass of `apad` resident headings would finish its scores inside the scoring kernel (fused epilogue: nothing shared is
@@ -2567,6 +2585,7 @@ static void launch_mfma(dv_ctx* c, int has_hs) {
         case Body::LcCode: return launch_planned<Body::LcCode>(c, p, has_hs);
         case Body::LcReg: return launch_planned<Body::LcReg>(c, p, has_hs);
         case Body::LcRegCode: return launch_planned<Body::LcRegCode>(c, p, has_hs);
+        case Body::LcRegCode8: return launch_planned<Body::LcRegCode8>(c, p, has_hs);
         case Body::Lc2Tiles: return launch_planned<Body::Lc2Tiles>(c, p, has_hs);
         case Body::Lc2TilesCode: return launch_planned<Body::Lc2TilesCode>(c, p, has_hs);
         case Body::Lc22: return launch_planned<Body::Lc22>(c, p, has_hs);
@@ -2610,7 +2629,7 @@ static int launch_int_scoring(dv_ctx* c, hipEvent_t after_tiles, int* n_partial,
         } else
         launch_mfma(c, has_hs_sum);
         c->last_form = DV_FORM_MATRIX_CORES | (c->fp4_ok ? DV_FORM_FP4 : 0) | (c->epilogue_fused ? DV_FORM_FUSED_FINISH : 0) |
-                       (c->fp4_ok && c->last_codes ? DV_FORM_CODES : 0);
+                       (c->fp4_ok && c->last_codes ? DV_FORM_CODES : 0) | (c->fp4_ok && c->last_consumers8 ? DV_FORM_CONSUMERS8 : 0);
         c->int_hsconst = c->mixed ? c->d_acc[c->acc_parity].hs : c->d_acc[c->acc_parity].bhs;
         c->int_vconst = c->d_acc[c->acc_parity].bv;
     } else if (g.generic) {

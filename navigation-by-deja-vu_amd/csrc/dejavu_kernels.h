@@ -4737,6 +4737,332 @@ sad_lc_fp4_lreg(const uint4* __restrict__ btiles, const uint4* __restrict__ coef
     DV_STAMP(5);
 }
 
+// ------------------------------------------------------------------ register-ring fp4 body on code rows, eight consumer waves
+// sad_lc_fp4_lreg<.., CODE> keeps 12 KB of library chunks in flight per consumer and has four consumers: 48 KB per CU, where the
+// same body on thermometer rows holds 64 KB and streams faster.  A consumer has no registers left for a deeper ring -- but its four
+// loader partners own 256 registers each as well and use almost none.  Here ALL EIGHT waves are consumers of the CODE form (two
+// view groups each, the same ring xr[8][2], the same peeled stage loops, decode and accumulator classes): eight rings, 96 KB per
+// CU on their way, an item of 16 view groups, and two consumers per SIMD whose mask arithmetic and MFMAs overlap.  CODE rows only:
+// with compiler-visible library loads an outstanding LDS-DMA would make the compiler wait vmcnt(0) at their next use.
+// The coefficient rows keep the ring protocol of sad_lc_fp4 (stages of SK K-steps, RD slots, one raw s_barrier per stage), with the
+// stage's 32 LDS-DMA instructions split eight ways: wave w brings the four rows of the stage's K-step w.  Barrier X (the one every
+// wave passes with all its reads of stage X - 1 in registers: in front of the last K-step of stage X - 1, or at the top of an
+// item) publishes stage X and frees the slot of stage X - 1, which receives stage X + RD - 1; stages are numbered through all of
+// the workgroup's items (the coefficient image is the same for every item), so an item's fill rides on the one before it.
+// Where the DMAs go out, and what that does to the counted waits (run_code): a wave issues its four DMAs of a stage behind the
+// barrier AND behind the library pieces that K-step sends, at the very end of stage X - 1 -- its last vector-memory instructions (at
+// the top of an item: the first of stage X; nothing is sent in between).  vmcnt retires in order, so in every K-step of a stage the queue is
+//     [the stage's own pieces, oldest first] [the 4 DMAs issued at its barrier] [the pieces sent so far in this stage],
+// and every wait of sad_lc_fp4_lreg's run_code grows by exactly PER = 4, whatever kinds of stages meet.  (Right behind the barrier
+// instead, the DMAs would stand in front of the last K-step's pieces -- one, three or none, depending on the pair of stages BEFORE
+// this one, and the count of a peeled loop's first trip would differ from its later trips'.)
+// The publish needs no wait of its own: a wave's DMAs of stage X went out at barrier X - 2, in front of every piece of stage X - 1,
+// and barrier X stands behind counted waits for pieces of stage X - 1 -- they have landed.  Only the very first barrier has
+// nothing in front of it (the prologue waits by count).  An LDS row is read only behind the barrier that follows that.
+// What the compiler adds around an item's end (hconst is loaded once per kernel; store_sums' stores and the finishing's few global
+// accesses are younger than every piece the next waits are for: the counts hold, a little early) may drain the queue once per item.
+constexpr int kLreg8Sel = 88;                                           // SKL of k_sad_mfma_dual that selects this body (eight consumers, stages of kLregStage)
+
+// LDS-DMA with a uniform base: 64 lanes x 16 B at `base` + `voff` -> 1 KB of LDS at lds_byte_addr
+__device__ __forceinline__ void lds_dma_16_s(unsigned voff, unsigned long long base, unsigned lds_byte_addr) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(base), "s"(lds_byte_addr) : "memory");
+}
+
+template <int SK, int RD, bool FUSE>
+__device__ __forceinline__ void
+sad_lc_fp4_lreg8(const uint4* __restrict__ ctiles, const uint4* __restrict__ coef4, int* __restrict__ part, const LibCfg& c, const BitCfg& b,
+                 int apad_total, int a_off, int has_hs_sum, const FuseArgs& fz, int n_gq) {
+    extern __shared__ uint4 lds_ring[];
+    constexpr int TL = 2;                                               // view groups per consumer
+    constexpr int NW = 8;
+    constexpr int KCOEF = 4;                                            // coefficient rows per K-step
+    constexpr int SLOTB = SK * KCOEF * 1024;
+    constexpr int PER = SK * KCOEF / NW;                                // LDS-DMA instructions per wave and stage
+    constexpr int RING = RD * SLOTB;
+    static_assert(SK == NW && PER == KCOEF && RD == 3, "wave w brings K-step w of a stage; the waits below know RD - 1 = 2 stages ahead");
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long G32 = c.Fpad / 32, GQ = n_gq;
+    const int NKT = b.NK[0] + b.NK[1];
+    const int nst = NKT / SK;                                           // (whole stages: the host checks, lreg_code_fits)
+    const int NK0 = b.NK[0];
+    const long long gbytes = (long long)b.GSC * 256;                    // between view groups
+    const unsigned lds_base = (unsigned)(unsigned long long)(lds_ptr_t)lds_ring;
+    unsigned long long* scratch0 = reinterpret_cast<unsigned long long*>(reinterpret_cast<unsigned char*>(lds_ring) + RING);
+    const unsigned char* lib_bytes = reinterpret_cast<const unsigned char*>(ctiles);
+    DV_STAMP(0);
+    if constexpr (FUSE) fused_block_begin(scratch0, true);
+    const long long n_mine = GQ > (long long)blockIdx.x ? (GQ - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;       // items of this workgroup
+
+    int hconst[2] = {0, 0};                                             // this lane's heading constants (fused_finish)
+    if (FUSE) {
+        const int a = a_off + (lane & 31), ac = a < fz.A_real ? a : fz.A_real - 1;
+        hconst[0] = acc_sum(fz.hsconst, ac);
+        hconst[1] = fz.vconst ? acc_sum(fz.vconst, ac) : 0;
+        // (used here, so that the compiler waits for them now and not, with vmcnt(0), at their first use in every item's finishing)
+        asm volatile("" : "+v"(hconst[0]), "+v"(hconst[1]));
+    }
+    // widths of the two accumulator classes, per segment: position 0 | positions 1, 2, 3 (equal where they stand for something)
+    auto w_of = [&](int seg, int cls) -> int {
+        if (cls == 0) return b.wacc[seg][0];
+        const int w1 = b.wacc[seg][1], w2 = b.wacc[seg][2], w3 = b.wacc[seg][3];
+        return w1 ? w1 : (w2 ? w2 : w3);
+    };
+    const unsigned voff = (unsigned)lane * 16u;
+    // ---- coefficient rows: this wave's K-step of the stage it issues next, dstage of an item (any item: one image), into ring slot dslot.
+    // Past the workgroup's last item the stages of an item that does not exist go on (hot in L2), so that the counts stay uniform.
+    int dstage = 0, dslot = 0;
+    const unsigned long long coef_wave = (unsigned long long)coef4 + (unsigned long long)wave * (KCOEF * 1024);
+    auto issue_dma = [&]() {
+        const unsigned long long src = coef_wave + (unsigned long long)dstage * (unsigned)SLOTB;
+        const unsigned dst = lds_base + (unsigned)dslot * (unsigned)SLOTB + (unsigned)wave * (KCOEF * 1024);
+        static_for<PER>([&](auto sc) {
+            constexpr int s_ = decltype(sc)::value;
+            lds_dma_16_s(voff, src + s_ * 1024, __builtin_amdgcn_readfirstlane(dst + s_ * 1024));
+        });
+        dslot = dslot + 1 == RD ? 0 : dslot + 1;
+        dstage = dstage + 1 == nst ? 0 : dstage + 1;
+    };
+    // ---- library cursor: the stage (lj, lkb / SK) whose pieces the ring receives next -- a saturation stage (eight 1-KB rows per view
+    // group) or a value stage (six 1-KB chunks of code dwords), piece e of either to xr[e] (sad_lc_fp4_lreg, CODE)
+    long long lj = 0;
+    int lkb = 0;
+    const int n_sat = has_hs_sum ? NK0 / SK : 0;                        // saturation stages of an item (value stages follow)
+    unsigned long long cbase[TL] = {0, 0}, cstage[TL] = {0, 0};         // the cursor item's view groups; the cursor's stage in them
+    auto cursor_stage = [&]() {
+        // a value stage starts NK[0] KB + 768 B per value K-step into the group (a group is far smaller than 4 GB)
+        const int vk = lkb - n_sat * SK;
+        const unsigned off = (unsigned)lkb * 1024u - (unsigned)(vk > 0 ? vk : 0) * 256u;
+#pragma unroll
+        for (int t = 0; t < TL; ++t) cstage[t] = cbase[t] + off;
+    };
+    auto cursor_item = [&]() {
+        const long long item = blockIdx.x + (lj < n_mine ? lj : 0) * gridDim.x;         // (past the last item: re-reads of the first)
+        const long long g0 = (item * G32) / GQ, g1 = ((item + 1) * G32) / GQ;
+#pragma unroll
+        for (int t = 0; t < TL; ++t) {
+            const long long g = g0 + wave * TL + t;
+            cbase[t] = (unsigned long long)(lib_bytes + (g < g1 ? g : g0) * gbytes);
+        }
+        cursor_stage();
+    };
+    v4u_t xr[SK][TL];                                                   // the register ring
+    auto load_piece = [&](auto ec) {
+        constexpr int e = decltype(ec)::value;
+#pragma unroll
+        for (int t = 0; t < TL; ++t) lib_load16_nt<(e & 3) * 1024>(xr[e][t], voff, cstage[t] + (e >> 2) * 4096u);
+    };
+    auto cursor_next = [&]() {                                          // behind a stage's loads
+        lkb += SK;
+        if (lkb >= nst * SK) { lkb = 0; ++lj; cursor_item(); }
+        else cursor_stage();
+    };
+    if (n_mine > 0) {                                                   // (the host launches no workgroup without items)
+        issue_dma();                                                    // stages 0 and 1, in FRONT of the first stage's pieces: the
+        issue_dma();                                                    //   third goes out at the first barrier, behind them, as ever after
+        cursor_item();
+        static_for<6>([&](auto ec) { load_piece(ec); });
+        if (n_sat > 0) {
+            load_piece(IntC<6>{});
+            load_piece(IntC<7>{});
+            wait_vmcnt_le<PER + TL * 8>();                              // this wave's rows of stage 0 have landed: stage 1's and the pieces are younger
+        } else {
+            wait_vmcnt_le<PER + TL * 6>();
+        }
+        cursor_next();
+    }
+    int cslot = 0;                                                      // ring slot of the current stage
+    for (long long j = 0; j < n_mine; ++j) {
+        const long long item = blockIdx.x + j * gridDim.x;
+        const long long g0 = (item * G32) / GQ, g1 = ((item + 1) * G32) / GQ;
+        long long gidx[TL];
+        bool live[TL];
+#pragma unroll
+        for (int t = 0; t < TL; ++t) {
+            const long long g = g0 + wave * TL + t;
+            live[t] = g < g1;
+            gidx[t] = live[t] ? g : g0;
+        }
+        int tot_hs[TL][16], tot_v[TL][16];
+#pragma unroll
+        for (int t = 0; t < TL; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { tot_hs[t][r] = 0; tot_v[t][r] = 0; }
+        // unfused passes store a segment's sums as soon as its accumulators are flushed (as sad_lc_fp4's store_sums)
+        auto store_sums = [&](const int (&tot)[TL][16], int seg) {
+            const int rows = (apad_total - a_off) < 32 ? (apad_total - a_off) : 32;
+#pragma unroll
+            for (int t = 0; t < TL; ++t) {
+                if (!live[t]) continue;
+                const int type_row = seg ? has_hs_sum : 0;
+                int* dst = part + ((long long)type_row * apad_total + a_off) * c.Fpad + gidx[t] * 32 + (lane & 31);
+                int half = lane >> 5;                                   // opaque, as in sad_lc_fp4
+                asm volatile("" : "+v"(half));
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int m = (r & 3) + 8 * (r >> 2) + 4 * half;
+                    if (m < rows) dst[(long long)m * c.Fpad] = tot[t][r];
+                }
+            }
+        };
+        {
+            v16f_t acc[TL][2];
+            auto clear = [&]() {
+#pragma unroll
+                for (int t = 0; t < TL; ++t)
+#pragma unroll
+                    for (int cl = 0; cl < 2; ++cl)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) acc[t][cl][r] = 0.f;
+            };
+            auto flush = [&](int (&dst)[TL][16], int seg) {
+                const int w0 = w_of(seg, 0), w1 = w_of(seg, 1);
+#pragma unroll
+                for (int t = 0; t < TL; ++t)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) dst[t][r] = __mul24(w0, (int)acc[t][0][r]) + __mul24(w1, (int)acc[t][1][r]);
+            };
+            clear();
+            v4u_t a[2][4];                                              // the four coefficient rows of K-step kk in a[kk & 1]
+            auto fetch = [&](int slot_i, auto kc) {
+                constexpr int kk = decltype(kc)::value;
+                const unsigned sad = lds_base + (unsigned)slot_i * (unsigned)SLOTB + (unsigned)lane * 16u;
+                static_for<4>([&](auto sc) { constexpr int s_ = decltype(sc)::value; lds_read16<(kk * KCOEF + s_) * 1024>(a[kk & 1][s_], sad); });
+            };
+            __builtin_amdgcn_s_barrier();                               // stage (j, 0) is in LDS; the slot of the stage before it is free
+            issue_dma();
+            if (j == 0) DV_STAMP(1);
+            fetch(cslot, IntC<0>{});
+            // stages [s0, s1) of kind CK (0: saturation rows, 1: value codes) while the cursor's stage is of kind LK: sad_lc_fp4_lreg's
+            // run_code with this wave's PER DMAs, issued at the stage's barrier, younger than every piece of the stage (above)
+            auto run_code = [&](int s0, int s1, auto ckc, auto lkc) {
+                constexpr int CK = decltype(ckc)::value, LK = decltype(lkc)::value;
+                for (int st = s0; st < s1; ++st) {
+                    const int nslot = cslot + 1 == RD ? 0 : cslot + 1;
+                    static_for<SK>([&](auto kc) {
+                        constexpr int kk = decltype(kc)::value;
+                        if constexpr (kk + 1 < SK) {
+                            fetch(cslot, IntC<kk + 1>{});               // one K-step ahead
+                            lds_wait<4>();                              // all but the newest K-step's reads have landed
+                        } else {
+                            lds_wait<0>();                              // everything this wave will use of the slot is in registers
+                            if (st + 1 < nst) {
+                                __builtin_amdgcn_s_barrier();           // stage st + 1 is in LDS; this slot is free
+                                fetch(nslot, IntC<0>{});
+                            }
+                        }
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) lds_tie(a[kk & 1][s]);
+                        constexpr unsigned m = 0x22222222u;             // (whole stages: no K-step without K-elements)
+                        constexpr int h3 = 3 * (kk / 4), q = kk % 4;
+                        constexpr int newest = CK ? h3 + (q < 2 ? q : 2) : kk;
+                        constexpr int sent = CK ? kk - (kk + 3) / 4 : (LK == 0 || kk < 6 ? kk : 6);
+                        // younger than the newest piece this K-step reads: the stage's later pieces, the DMAs, what went out before kk
+                        wait_vmcnt_le<TL * ((CK ? 6 : 8) - 1 - newest + sent) + PER>();
+                        unsigned bo[TL][4][4];
+                        if constexpr (CK == 0) {
+#pragma unroll
+                            for (int t = 0; t < TL; ++t) lds_tie(xr[kk][t]);
+#pragma unroll
+                            for (int t = 0; t < TL; ++t) {
+                                const unsigned x[4] = {xr[kk][t].x, xr[kk][t].y, xr[kk][t].z, xr[kk][t].w};
+#pragma unroll
+                                for (int d = 0; d < 4; ++d) {
+                                    bo[t][0][d] = (x[d] << 1) & m;
+                                    bo[t][1][d] = x[d] & m;
+                                    bo[t][2][d] = (x[d] >> 1) & m;
+                                    bo[t][3][d] = (x[d] >> 2) & m;
+                                }
+                            }
+                            if constexpr (LK == 0 || kk < 6) load_piece(kc);
+                        } else {
+                            // the K-step's three code dwords are dwords 3 q .. 3 q + 2 of the half stage's twelve (chunks h3 .. h3 + 2)
+#pragma unroll
+                            for (int t = 0; t < TL; ++t) {
+                                if constexpr (q < 2) lds_tie(xr[h3][t]);
+                                if constexpr (q == 1 || q == 2) lds_tie(xr[h3 + 1][t]);
+                                if constexpr (q >= 2) lds_tie(xr[h3 + 2][t]);
+                            }
+#pragma unroll
+                            for (int t = 0; t < TL; ++t) {
+                                unsigned x[4];
+                                if constexpr (q == 0) { x[0] = xr[h3][t].x; x[1] = xr[h3][t].y; x[2] = xr[h3][t].z; }
+                                else if constexpr (q == 1) { x[0] = xr[h3][t].w; x[1] = xr[h3 + 1][t].x; x[2] = xr[h3 + 1][t].y; }
+                                else if constexpr (q == 2) { x[0] = xr[h3 + 1][t].z; x[1] = xr[h3 + 1][t].w; x[2] = xr[h3 + 2][t].x; }
+                                else { x[0] = xr[h3 + 2][t].y; x[1] = xr[h3 + 2][t].z; x[2] = xr[h3 + 2][t].w; }
+                                // the fourth dword's pixels: bit 3 of the three code dwords' nibbles
+                                x[3] = ((x[0] >> 3) & 0x11111111u) | ((x[1] >> 2) & 0x22222222u) | ((x[2] >> 1) & 0x44444444u);
+                                // code b2 b1 b0 -> thermometer bit of every position on the 1.0 bit: t1 = b0 | b1, t2 = b1, t3 = b2, t4 = b0 & b2
+#pragma unroll
+                                for (int d = 0; d < 4; ++d) {
+                                    bo[t][0][d] = ((x[d] << 1) | x[d]) & m;
+                                    bo[t][1][d] = x[d] & m;
+                                    bo[t][2][d] = (x[d] >> 1) & m;
+                                    bo[t][3][d] = (x[d] << 1) & (x[d] >> 1) & m;
+                                }
+                            }
+                            if constexpr (q > 0) load_piece(IntC<kk - 1 - kk / 4>{});
+                            if constexpr (LK == 0 && kk == SK - 1) { load_piece(IntC<6>{}); load_piece(IntC<7>{}); }
+                        }
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) {
+                            const v4u_t& av = a[kk & 1][s];
+                            const v8i_t ao = v8i_t{(int)av.x, (int)av.y, (int)av.z, (int)av.w, 0, 0, 0, 0};
+#pragma unroll
+                            for (int t = 0; t < TL; ++t) {
+                                const v8i_t bv = v8i_t{(int)bo[t][s][0], (int)bo[t][s][1], (int)bo[t][s][2], (int)bo[t][s][3], 0, 0, 0, 0};
+                                if constexpr (FUSE) acc[t][s ? 1 : 0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(bv, ao, acc[t][s ? 1 : 0], 4, 4, 0, 0, 0, 0);   // views x headings
+                                else acc[t][s ? 1 : 0] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(ao, bv, acc[t][s ? 1 : 0], 4, 4, 0, 0, 0, 0);
+                            }
+                        }
+                    });
+                    // behind the last K-step's barrier and behind its pieces.  (Behind its MFMAs as well: a branch between a piece's
+                    // load and the K-step's MFMAs made the compiler finish the masks of the piece's OLD value behind the load, give
+                    // the new value other registers and copy them at the loop's back edge -- while the load was still in flight.)
+                    if (st + 1 < nst) issue_dma();
+                    cursor_next();
+                    cslot = nslot;
+                }
+            };
+            // saturation stages (when the library has that segment), then the value stages; the accumulators change hands at the boundary
+            // (the host checks: value K-steps in whole stages, at least one; hs_end == n_sat < nst)
+            const int hs_end = has_hs_sum ? NK0 / SK : 0;
+            if (hs_end > 0) {
+                run_code(0, hs_end - 1, IntC<0>{}, IntC<0>{});
+                run_code(hs_end - 1, hs_end, IntC<0>{}, IntC<1>{});
+                flush(tot_hs, 0);
+                // (unfused: these stores are younger than every load the next waits are for -- the counts hold, a little early)
+                if constexpr (!FUSE) store_sums(tot_hs, 0);
+                clear();
+            }
+            // the last value stage's cursor is in the next item's first stage: saturation, or value like the stages before it
+            run_code(hs_end, hs_end > 0 ? nst - 1 : nst, IntC<1>{}, IntC<1>{});
+            if (hs_end > 0) run_code(nst - 1, nst, IntC<1>{}, IntC<0>{});
+            flush(tot_v, 1);
+            if constexpr (!FUSE) {
+                // (a sum without K-steps is stored as the zeros it was initialised to)
+                if (has_hs_sum && hs_end == 0) store_sums(tot_hs, 0);
+                store_sums(tot_v, 1);
+            }
+        }
+        if (j == 0) DV_STAMP(2);
+        if constexpr (FUSE) {
+            if (j == 0) DV_STAMP(3);
+            auto of_hs = [&](int t, int r) -> int { return tot_hs[t][r]; };
+            auto of_v = [&](int t, int r) -> int { return tot_v[t][r]; };
+            fused_finish<TL, NW, true>(of_hs, of_v, gidx, live, scratch0, c, fz, a_off, has_hs_sum, j, lane, wave, (int)(j & 1), NW, hconst);
+            if (j == 0) DV_STAMP(4);
+        }
+    }
+    wait_vmcnt_le<0>();                                                 // the re-reads past the last item, into LDS and registers
+    if constexpr (FUSE) {
+        if (a_off < fz.A_real) fused_block_end(scratch0, fz, c, a_off);
+    }
+    DV_STAMP(5);
+}
+
 // ------------------------------------------------------------------ loader / consumer body, two view groups x two heading tiles
 // sad_lc_fp4 with two heading tiles (HT = 2: the ensemble passes of 64 headings) gives a consumer ONE view group: per K-step it reads
 // eight coefficient rows and one library row from LDS for eight MFMAs, and the CU's LDS moves 4 x 9 KB of reads + 12 KB of LDS-DMA =
@@ -5087,7 +5413,10 @@ k_sad_mfma_dual(const uint4* __restrict__ btiles, const uint4* __restrict__ ftil
     if constexpr (SKL > 0) {
         static_assert(TILES == 1, "the loader / consumer body cuts the library into ranges of 8 / HT view groups; the other bodies must agree");
         if (fp4 && nchunk == 1) {
-            if constexpr (SKL == kLregStage) {                          // the library rows in the consumers' registers (LCODE: value rows as codes)
+            if constexpr (SKL == kLreg8Sel) {                           // ... in all eight waves' registers, code rows only
+                static_assert(HT == 1 && LCODE, "sad_lc_fp4_lreg8: one heading tile, code rows");
+                sad_lc_fp4_lreg8<kLregStage, RDL, FUSE>(ftiles, coef4, part, c, b, apad_total, a_off, has_hs_sum, fz, n_gq);
+            } else if constexpr (SKL == kLregStage) {                        // the library rows in the consumers' registers (LCODE: value rows as codes)
                 static_assert(HT == 1, "sad_lc_fp4_lreg: one heading tile");
                 sad_lc_fp4_lreg<SKL, RDL, FUSE, LCODE>(LCODE ? ftiles : btiles, coef4, part, c, b, apad_total, a_off, has_hs_sum, fz, n_gq);
             } else {
@@ -5097,6 +5426,9 @@ k_sad_mfma_dual(const uint4* __restrict__ btiles, const uint4* __restrict__ ftil
         }
     }
     const int NKT = b.NK[0] + b.NK[1];
+    // the ring bodies take 8 view groups per item: a 16-group item of sad_lc_fp4_lreg8 as two ranges of at most 8 -- ranges 2 q and
+    // 2 q + 1 of the cut into 2 n_gq are exactly item q's groups ((2 q G32) / (2 n_gq) = (q G32) / n_gq), each at most ceil(16 / 2)
+    if constexpr (SKL == kLreg8Sel) n_gq *= 2;
 #pragma unroll 1
     for (int h = 0; h < HT; ++h) {
         if (h > 0 && a_off + 32 * h >= apad_total) break;

@@ -752,11 +752,11 @@ class FamiliarityEngine(object):
 
     def scoring_form(self):
         """Form of the last integer scoring pass (dv_scoring_form): matrix cores / fp4 coefficients / fused finishing / value rows
-        read as 3-bit codes."""
+        read as 3-bit codes / those in the registers of all eight waves of a workgroup."""
         rc = self._lib.dv_scoring_form(self._ctx)
         if rc < 0:
             self._check(rc, "dv_scoring_form")
-        return dict(matrix_cores=bool(rc & 1), fp4=bool(rc & 2), fused_finish=bool(rc & 4), codes=bool(rc & 8))
+        return dict(matrix_cores=bool(rc & 1), fp4=bool(rc & 2), fused_finish=bool(rc & 4), codes=bool(rc & 8), consumers8=bool(rc & 16))
 
     def path_reset(self):
         self._check(self._lib.dv_path_reset(self._ctx), "dv_path_reset")

@@ -808,6 +808,54 @@ int dv_lands_ibank_sense_step(dv_ctx *ctx, const double *x, const double *y, con
                               const int32_t *bank_of_member, const int32_t *land_of_member, double *angle_fam, int32_t *best_heading,
                               uint32_t *flags);
 
+/* ---- route view store: perfect-memory members on their own routes ------------ */
+/*
+ * The sensed views of R training routes side by side as raw HSV bytes, and a step that scores every member's headings against the
+ * views of ITS OWN route only: the sads_hsv model (navsim/util.pyx:31-73) for ensembles of trials that differ in their training route
+ * and their landscape.  Route r is views [first[r], first[r + 1]) (first: int64[n_routes + 1], first[0] = 0, at least 2 views a
+ * route).  The store stands beside the library (dv_set_library and every dv_step* / dv_sense_step* call work unchanged beside it and
+ * after it is cleared); its layout depends on neither the data nor a weight.  Views of h x w with h * w <= 4096.
+ * A step's tables are route_of_member (int32[n_agents], in [0, n_routes)), chem_weights (double[n_agents], in [0, 1]) and, for
+ * sensed calls on a live landscape set, land_of_member (int32[n_agents]; NULL: the context's one landscape).  Every entry, and first,
+ * is checked before anything of the call reaches the device: DV_ERR_INVALID names it and nothing changes.  DV_ERR_STATE without a store.
+ *   set_u8           views: uint8[first[n_routes]][h][w][3].  The replacement is built first: an error leaves the old store as it was.
+ *   set_from_poses   senses the n = first[n_routes] views in one call, on the context's landscape or view v on landscape land_of_view[v]
+ *                    of the live set; out_views (may be NULL) receives them.  DV_ERR_INDEX names the first view whose footprint leaves
+ *                    its own landscape, and the store stays as it was.
+ *   step_u8          patches: uint8[n_agents][n_headings][h][w][3].  angle_fam[i * n_headings + a]: the reference's value (bit for
+ *                    bit) of the most familiar view of member i's route for heading a, angle_view (may be NULL) the first view that
+ *                    attains it (an index within the route), best_heading[i] the first maximum of member i's row (np.argmax).  Any
+ *                    n_headings >= 1, any n_agents (scored in slabs of what a 64 MiB score buffer holds; DEJAVU_RVIEWS_SLAB = columns,
+ *                    read at dv_create, sets another slab size for tests).  flags: DV_RVIEWS_EXACT scores every view as the reference's
+ *                    sequential sum (as dv_set_exact does); the default finds the candidates with exact integer sums and scores
+ *                    those again, with the same results.
+ *   sense_step       step_u8 with the patches sensed at (x[i], y[i]) along angles[i * n_headings + a]: one enqueue, one wait.
+ *                    member_flags[i] carries DV_RES_SENSE_ERROR for a member whose footprint leaves its own landscape (its row is
+ *                    unspecified, its best_heading -1); the others are scored.
+ *   scene_u8 / scene scene_familiarity of the members: per view of member i's route the least value over its headings, the members'
+ *                    rows back to back in scene_fam (n_out doubles: the sum of the members' route lengths).  A member with
+ *                    DV_RES_SENSE_ERROR gets a row of +inf.  member_flags may be NULL.
+ *   info             n_routes (0: no store), first (the caller's n_routes + 1 entries: ask for n_routes first), the views' shape and
+ *                    the bytes of the store; any pointer may be NULL.
+ *   clear            no store; its memory is freed.
+ */
+#define DV_RVIEWS_EXACT 1u
+int dv_rviews_set_u8(dv_ctx *ctx, const uint8_t *views, const int64_t *first, int n_routes, int h, int w);
+int dv_rviews_set_from_poses(dv_ctx *ctx, const double *x, const double *y, const double *angle, int64_t n, const int64_t *first,
+                             int n_routes, const int32_t *land_of_view, uint8_t *out_views);
+int dv_rviews_step_u8(dv_ctx *ctx, const uint8_t *patches, int n_agents, int n_headings, const int32_t *route_of_member,
+                      const double *chem_weights, uint32_t flags, double *angle_fam, int64_t *angle_view, int32_t *best_heading);
+int dv_rviews_sense_step(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
+                         const int32_t *route_of_member, const double *chem_weights, const int32_t *land_of_member, uint32_t flags,
+                         double *angle_fam, int64_t *angle_view, int32_t *best_heading, uint32_t *member_flags);
+int dv_rviews_scene_u8(dv_ctx *ctx, const uint8_t *patches, int n_agents, int n_headings, const int32_t *route_of_member,
+                       const double *chem_weights, int64_t n_out, double *scene_fam);
+int dv_rviews_scene(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
+                    const int32_t *route_of_member, const double *chem_weights, const int32_t *land_of_member, int64_t n_out,
+                    double *scene_fam, uint32_t *member_flags);
+int dv_rviews_info(dv_ctx *ctx, int *n_routes, int64_t *first, int *h, int *w, int64_t *bytes);
+int dv_rviews_clear(dv_ctx *ctx);
+
 /* ---- measurement ------------------------------------------------------- */
 /* hipEvent pair on the context's stream around whatever is enqueued between the two calls. */
 int dv_timer_start(dv_ctx *ctx);

@@ -28,6 +28,7 @@
 #include <string>
 #include <vector>
 
+namespace dv { struct RvRoute; }   // (dejavu_rviews.inl)
 using namespace dv;
 
 static_assert(sizeof(StepResultDev) == sizeof(dv_step_result) + sizeof(unsigned long long) &&
@@ -369,6 +370,25 @@ struct dv_ctx {
     int* ld_err = nullptr;                    // [n]: k_sense_lands' word per pose (dv_lands_sense, training from poses)
     size_t ld_err_cap = 0;                    // bytes
     std::vector<int> ld_err_host;
+    // route view store (dejavu_rviews.inl: dv_rviews_*): independent of the library above
+    unsigned* rv_planes = nullptr;            // groups of 64 views, three byte planes each (nullptr: no store)
+    RvRoute* rv_routes = nullptr;             // [n_routes]: first group, views
+    std::vector<int64_t> rv_first;            // [n_routes + 1] (empty: no store)
+    int rv_h = 0, rv_w = 0, rv_lmax = 0;      // the views' shape; the longest route
+    long long rv_bytes = 0;
+    double rv_delta = 0.0;                    // the tie window's delta for rv_h x rv_w views
+    int rv_slab_env = 0;                      // DEJAVU_RVIEWS_SLAB: columns of a slab (0: what the score buffer holds)
+    double* rv_fast = nullptr;                // [slab columns][lstride]: a slab's scores
+    int* rv_marked = nullptr;                 // [C]: columns left to the exact-all pass
+    unsigned char* rv_out = nullptr;          // a step's results: fam[C], view[C], best[N], flags[N]
+    unsigned char* rv_tab = nullptr;          // a call's tables (RvPlan)
+    int* rv_err = nullptr;                    // [C]: the sensing kernels' word per pose
+    double* rv_scene = nullptr;               // dv_rviews_scene's rows
+    unsigned* rv_prep = nullptr;              // [C][3][Pw]: a step's patches as byte planes
+    size_t rv_prep_cap = 0;                   // bytes
+    size_t rv_fast_cap = 0, rv_marked_cap = 0, rv_out_cap = 0, rv_tab_cap = 0, rv_err_cap = 0, rv_scene_cap = 0;   // bytes
+    std::vector<unsigned char> rv_tab_host;   // what rv_tab holds (empty: nothing known)
+    std::vector<unsigned char> rv_out_host;
 
     // measurement
     hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -401,6 +421,7 @@ static void diffuse_free(dv_ctx* c);
 static void infomax_free(dv_ctx* c);
 static void mb_free(dv_ctx* c);
 static void lands_free(dv_ctx* c);
+static void rviews_free(dv_ctx* c);
 static void path_routes_free(dv_ctx* c);
 static void free_library(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
@@ -479,6 +500,7 @@ extern "C" int dv_create(dv_ctx** out, int device_id) {
     env_int("DEJAVU_MIXED", c->mixed_env, 0, 1);
     env_int("DEJAVU_TUNE_ALL", c->tune_all_env, 0, 1);
     env_int("DEJAVU_SSD_MFMA", c->ssd_mfma_env, 0, 3);
+    env_int("DEJAVU_RVIEWS_SLAB", c->rv_slab_env, 1, 32768);
     env_int("DEJAVU_CHAINS", c->chains_env, 1, 3);
     env_int("DEJAVU_CHAIN_ORDER", c->chain_order_env, -1, 2);
     env_int("DEJAVU_LC22", c->lc22_env, 0, 1);
@@ -503,6 +525,7 @@ extern "C" void dv_destroy(dv_ctx* c) {
     infomax_free(c);
     mb_free(c);
     lands_free(c);
+    rviews_free(c);
     path_routes_free(c);
     if (c->d_land) (void)hipFree(c->d_land);
     if (c->d_lut) (void)hipFree(c->d_lut);
@@ -3722,6 +3745,7 @@ extern "C" int dv_stream_read_gbps(dv_ctx* c, int64_t n_bytes, int iters, double
 
 #include "dejavu_diffuse.inl"   // dv_diffuse_*: the landscape generator's heat equation (kernels and host side)
 #include "dejavu_lands.inl"     // dv_lands_*: landscape sets, a landscape per pose in the banked models' sensed calls (kernel and host side)
+#include "dejavu_rviews.inl"    // dv_rviews_*: route view store, perfect-memory members scored on their own routes (kernels and host side)
 #include "dejavu_infomax.inl"   // dv_infomax_*: the Infomax familiarity model (kernels and host side)
 #include "dejavu_mushroom.inl"  // dv_mb_*: the mushroom-body familiarity model (kernels and host side)
 #include "dejavu_path_routes.inl"   // dv_path_routes_*: the error / coverage metrics against several routes (host side)

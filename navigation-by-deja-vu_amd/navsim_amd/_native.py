@@ -20,6 +20,7 @@ DV_RES_RESOLVED = 1
 DV_RES_EXACT_ALL = 2
 DV_RES_OVERFLOW = 4
 DV_RES_SENSE_ERROR = 16
+DV_RVIEWS_EXACT = 1
 DV_DIFFUSE_AUTO = 0
 DV_DIFFUSE_PLAIN = 1
 DV_DIFFUSE_BLOCKED = 2
@@ -285,6 +286,17 @@ PROTOTYPES = {
     "dv_lands_ibank_train_from_poses": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int64, _i32p, _i32p, _u8p]),
     "dv_lands_mbank_sense_step": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _i32p, _i32p, _f64p, _i32p, _u32p]),
     "dv_lands_ibank_sense_step": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _i32p, _i32p, _f64p, _i32p, _u32p]),
+    "dv_rviews_set_u8": (ctypes.c_int, [_ctx_p, _u8p, _i64p, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "dv_rviews_set_from_poses": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int64, _i64p, ctypes.c_int, _i32p, _u8p]),
+    "dv_rviews_step_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, _i32p, _f64p, ctypes.c_uint32, _f64p, _i64p, _i32p]),
+    "dv_rviews_sense_step": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _i32p, _f64p, _i32p, ctypes.c_uint32,
+                                            _f64p, _i64p, _i32p, _u32p]),
+    "dv_rviews_scene_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, _i32p, _f64p, ctypes.c_int64, _f64p]),
+    "dv_rviews_scene": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _i32p, _f64p, _i32p, ctypes.c_int64, _f64p,
+                                       _u32p]),
+    "dv_rviews_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), _i64p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                      _i64p]),
+    "dv_rviews_clear": (ctypes.c_int, [_ctx_p]),
     "dv_synchronize": (ctypes.c_int, [_ctx_p]),
     "dv_timer_start": (ctypes.c_int, [_ctx_p]),
     "dv_timer_stop": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_float)]),

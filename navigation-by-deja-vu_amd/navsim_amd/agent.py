@@ -592,14 +592,19 @@ class NavBySceneFamiliarity(object):
 
     # ---- the step (:279-329) -------------------------------------------------------------------
     def step_forward(self, fake=False):
+        if self.memory_bank is not None:
+            # (a step of its own scores under bank 0 of the model: only its ensemble's batches score it under its own bank -- or, for the
+            # perfect-memory model, against its own route's views of the store)
+            name = route_ensemble_name(self)
+            if name == "SadsRouteEnsemble":
+                raise ValueError("this ensemble member's route is route %d of the view store it shares: step it with its %s"
+                                 % (self.memory_bank, name))
+            raise ValueError("this ensemble member's route is kept in memory bank %d of a model it shares: step it with its %s"
+                             % (self.memory_bank, name))
         if self.chem_weight is not None and self.chem_weight != getattr(self.familiarity_model, "chem_weight", None):
             # (a step of its own runs the library's weight: only its ensemble's batches score it under its own)
             raise ValueError("this ensemble member scores under chem_weight %r, the library under %r: step it with its NavEnsemble"
                              % (self.chem_weight, getattr(self.familiarity_model, "chem_weight", None)))
-        if self.memory_bank is not None:
-            # (a step of its own scores under bank 0 of the model: only its ensemble's batches score it under its own bank)
-            raise ValueError("this ensemble member's route is kept in memory bank %d of a model it shares: step it with its %s"
-                             % (self.memory_bank, route_ensemble_name(self)))
         position = self.position
         self.angle_familiarity[:] = np.nan
         assert len(self.familiar_scenes) == len(self._scene_fam)

@@ -66,7 +66,16 @@ class OneValueBatchResults(object):
         return self.n
 
 
-InfomaxBatchResults = OneValueBatchResults     # the name it had while Infomax was the only such model
+class RouteViewResults(OneValueBatchResults):
+    """A step on the route view store (dv_rviews_step_u8 / dv_rviews_sense_step): OneValueBatchResults and angle_view[n, A] (int64),
+    the first view of the member's own route that attains angle_familiarity."""
+
+    def __init__(self, angle_familiarity, angle_view, best_idex, flags):
+        OneValueBatchResults.__init__(self, angle_familiarity, best_idex, flags)
+        self.angle_view = angle_view
+
+
+InfomaxBatchResults = OneValueBatchResults    # the name it had while Infomax was the only such model
 
 # The one-value models -- no library, ONE value per heading: metric -> (prefix of the single calls' symbols, of the batch calls', the
 # engine attribute that holds the model's (h, w)).
@@ -1473,3 +1482,163 @@ class FamiliarityEngine(object):
         self._check_sense(self._lib.dv_lands_sense(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), lands.ctypes.data_as(N._i32p), len(x),
                                                    N.u8ptr(out)), "dv_lands_sense")
         return out
+
+    # -- route view store: perfect-memory members scored on their own routes (include/dejavu.h: dv_rviews_*) ------------------------
+    rviews_first = None          # int64[n_routes + 1] of the store (rviews_set_u8 / rviews_set_from_poses; None: no store)
+    rviews_shape = None          # (h, w) of its views
+    RVIEWS_MAX_PIXELS = 4096
+
+    @staticmethod
+    def _rviews_first(first, n):
+        """`first` as int64[R + 1]: 0, ascending by at least 2, ending at n -- or ValueError naming the entry."""
+        arr = np.asarray(first)
+        if arr.ndim != 1 or arr.shape[0] < 2:
+            raise ValueError("first must have shape (n_routes + 1,) with n_routes >= 1, got %r" % (arr.shape,))
+        if arr.dtype.kind not in "iu":
+            raise ValueError("first must hold integers (a route's first view), got dtype %s" % arr.dtype)
+        arr = np.ascontiguousarray(arr, dtype=np.int64)
+        if arr[0] != 0:
+            raise ValueError("first[0] = %d, not 0" % arr[0])
+        short = np.flatnonzero(np.diff(arr) < 2)
+        if len(short):
+            raise ValueError("first[%d] = %d: route %d would hold %d views (a route holds at least 2)"
+                             % (short[0] + 1, arr[short[0] + 1], short[0], arr[short[0] + 1] - arr[short[0]]))
+        if arr[-1] != n:
+            raise ValueError("first[%d] = %d, but there are %d views" % (len(arr) - 1, arr[-1], n))
+        return arr
+
+    def _rviews_tables(self, n, route_of_member, chem_weights, land_of_member=None):
+        """The tables of a step as (int32[n], float64[n], int32[n] or None), every entry in range -- checked before any library call."""
+        if self.rviews_first is None:
+            raise N.EngineError("no route views: rviews_set_u8 or rviews_set_from_poses first (DV_ERR_STATE)")
+        routes = self._bank_table(route_of_member, n, "route_of_member", len(self.rviews_first) - 1)
+        w = np.asarray(chem_weights)
+        if w.dtype.kind not in "fiu":
+            raise ValueError("chem_weights must hold numbers, got dtype %s" % w.dtype)
+        if w.shape != (n,):
+            raise ValueError("chem_weights must have shape (%d,), got %r" % (n, w.shape))
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        bad = np.flatnonzero(~((w >= 0.0) & (w <= 1.0)))
+        if len(bad):
+            raise ValueError("chem_weights[%d] = %r outside [0, 1]" % (bad[0], float(w[bad[0]])))
+        lands = None if land_of_member is None else self._land_table(land_of_member, n, "land_of_member")
+        return routes, w, lands
+
+    def rviews_set_u8(self, views, first):
+        """views: uint8[n, h, w, 3], route r = views[first[r]:first[r + 1]]: the store of the routes' views, for tests without a sensor."""
+        views = N.as_u8(views, "views")
+        if views.ndim != 4 or views.shape[3] != 3 or views.shape[1] < 1 or views.shape[2] < 1:
+            raise ValueError("views must be uint8[n, h, w, 3], got shape %r" % (views.shape,))
+        if views.shape[1] * views.shape[2] > self.RVIEWS_MAX_PIXELS:
+            raise ValueError("views of %d x %d: h * w must be <= %d" % (views.shape[1], views.shape[2], self.RVIEWS_MAX_PIXELS))
+        first = self._rviews_first(first, views.shape[0])
+        self._check(self._lib.dv_rviews_set_u8(self._ctx, N.u8ptr(views), N.i64ptr(first), len(first) - 1, views.shape[1], views.shape[2]),
+                    "dv_rviews_set_u8")
+        self.rviews_first, self.rviews_shape = first, (views.shape[1], views.shape[2])
+
+    def rviews_set_from_poses(self, x, y, angle, first, land_of_view=None, want_views=True):
+        """Senses the views of all routes in one call into the store (view v on landscape land_of_view[v] of the live set; None: on the
+        engine's landscape); returns them (uint8[n, h, w, 3]) when want_views.  IndexError names the first view whose footprint leaves
+        its own landscape, and the store stays as it was."""
+        x, y, angle = self._pose_arrays(x, y, angle)
+        first = self._rviews_first(first, len(x))
+        lands = None if land_of_view is None else self._land_table(land_of_view, len(x), "land_of_view")
+        h, w = self.sensor_shape
+        views = np.empty((len(x), h, w, 3), dtype=np.uint8) if want_views else None
+        self._check_sense(self._lib.dv_rviews_set_from_poses(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), len(x), N.i64ptr(first),
+                                                             len(first) - 1, None if lands is None else lands.ctypes.data_as(N._i32p),
+                                                             N.u8ptr(views) if want_views else None), "dv_rviews_set_from_poses")
+        self.rviews_first, self.rviews_shape = first, (h, w)
+        return views
+
+    def rviews_clear(self):
+        self._check(self._lib.dv_rviews_clear(self._ctx), "dv_rviews_clear")
+        self.rviews_first = self.rviews_shape = None
+
+    def rviews_info(self):
+        """dict(n_routes, first int64[n_routes + 1], shape (h, w), bytes)."""
+        nr, h, w, nbytes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+        self._check(self._lib.dv_rviews_info(self._ctx, ctypes.byref(nr), None, ctypes.byref(h), ctypes.byref(w), ctypes.byref(nbytes)),
+                    "dv_rviews_info")
+        first = np.zeros(nr.value + 1, dtype=np.int64)
+        if nr.value:
+            self._check(self._lib.dv_rviews_info(self._ctx, None, N.i64ptr(first), None, None, None), "dv_rviews_info")
+        return dict(n_routes=nr.value, first=first, shape=(h.value, w.value), bytes=nbytes.value)
+
+    def _rviews_patches(self, patches):
+        patches = N.as_u8(patches, "patches")
+        if self.rviews_first is None:
+            raise N.EngineError("no route views: rviews_set_u8 or rviews_set_from_poses first (DV_ERR_STATE)")
+        if patches.ndim != 5 or patches.shape[0] < 1 or patches.shape[1] < 1 or patches.shape[2:] != self.rviews_shape + (3,):
+            raise ValueError("patches must be uint8[n, A, %d, %d, 3] with n, A >= 1, got shape %r" % (self.rviews_shape + (patches.shape,)))
+        return patches
+
+    @staticmethod
+    def _rviews_poses(x, y, angles):
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        angles = np.ascontiguousarray(angles, dtype=np.float64)
+        if angles.ndim != 2 or len(x) != len(y) or angles.shape[0] != len(x) or angles.shape[0] < 1 or angles.shape[1] < 1:
+            raise ValueError("x[N], y[N] and angles[N, A] expected (N, A >= 1), got shapes %r, %r and %r" % (x.shape, y.shape, angles.shape))
+        return x, y, angles
+
+    def rviews_step_u8(self, patches, route_of_member, chem_weights, exact=False):
+        """patches: uint8[n, A, h, w, 3]; member i is scored against the views of route route_of_member[i] under chem_weights[i] ->
+        RouteViewResults: angle_familiarity[n, A] (the reference's bits), angle_view[n, A] (the first view of the route that attains
+        it), best_idex[n] (np.argmax of the row), flags[n]."""
+        patches = self._rviews_patches(patches)
+        n, A = patches.shape[:2]
+        routes, w, _ = self._rviews_tables(n, route_of_member, chem_weights)
+        fam = np.empty((n, A), dtype=np.float64)
+        view = np.empty((n, A), dtype=np.int64)
+        best = np.full(n, -1, dtype=np.int32)
+        self._check(self._lib.dv_rviews_step_u8(self._ctx, N.u8ptr(patches), n, A, routes.ctypes.data_as(N._i32p), N.f64ptr(w),
+                                                N.DV_RVIEWS_EXACT if exact else 0, N.f64ptr(fam), N.i64ptr(view), best.ctypes.data_as(N._i32p)),
+                    "dv_rviews_step_u8")
+        return RouteViewResults(fam, view, best, np.zeros(n, dtype=np.uint32))
+
+    def rviews_sense_step(self, x, y, angles, route_of_member, chem_weights, land_of_member=None, exact=False):
+        """rviews_step_u8 with member i's patches sensed at (x[i], y[i]) along angles[i] (on landscape land_of_member[i] of the live
+        set): one enqueue and one wait.  flags[i] carries DV_RES_SENSE_ERROR = 16 for a member whose footprint leaves its landscape."""
+        x, y, angles = self._rviews_poses(x, y, angles)
+        n, A = angles.shape
+        routes, w, lands = self._rviews_tables(n, route_of_member, chem_weights, land_of_member)
+        fam = np.empty((n, A), dtype=np.float64)
+        view = np.empty((n, A), dtype=np.int64)
+        best = np.full(n, -1, dtype=np.int32)
+        flags = np.zeros(n, dtype=np.uint32)
+        self._check(self._lib.dv_rviews_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, routes.ctypes.data_as(N._i32p),
+                                                   N.f64ptr(w), None if lands is None else lands.ctypes.data_as(N._i32p),
+                                                   N.DV_RVIEWS_EXACT if exact else 0, N.f64ptr(fam), N.i64ptr(view),
+                                                   best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)), "dv_rviews_sense_step")
+        return RouteViewResults(fam, view, best, flags)
+
+    def _rviews_rows(self, routes):
+        lens = np.diff(self.rviews_first)[routes]
+        return np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+
+    def rviews_scene_u8(self, patches, route_of_member, chem_weights):
+        """scene_familiarity of every member -> a list of float64[len(route of member i)]: per view the least value over the headings."""
+        patches = self._rviews_patches(patches)
+        n, A = patches.shape[:2]
+        routes, w, _ = self._rviews_tables(n, route_of_member, chem_weights)
+        row0 = self._rviews_rows(routes)
+        out = np.empty(row0[-1], dtype=np.float64)
+        self._check(self._lib.dv_rviews_scene_u8(self._ctx, N.u8ptr(patches), n, A, routes.ctypes.data_as(N._i32p), N.f64ptr(w), len(out),
+                                                 N.f64ptr(out)), "dv_rviews_scene_u8")
+        return [out[row0[i]:row0[i + 1]] for i in range(n)]
+
+    def rviews_scene(self, x, y, angles, route_of_member, chem_weights, land_of_member=None, want_flags=False):
+        """rviews_scene_u8 with the patches sensed as rviews_sense_step senses them; a member whose footprint leaves its landscape gets
+        a row of +inf and DV_RES_SENSE_ERROR = 16 in its flag.  want_flags: returns (rows, flags uint32[n])."""
+        x, y, angles = self._rviews_poses(x, y, angles)
+        n, A = angles.shape
+        routes, w, lands = self._rviews_tables(n, route_of_member, chem_weights, land_of_member)
+        row0 = self._rviews_rows(routes)
+        out = np.empty(row0[-1], dtype=np.float64)
+        flags = np.zeros(n, dtype=np.uint32)
+        self._check(self._lib.dv_rviews_scene(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, routes.ctypes.data_as(N._i32p),
+                                              N.f64ptr(w), None if lands is None else lands.ctypes.data_as(N._i32p), len(out), N.f64ptr(out),
+                                              flags.ctypes.data_as(N._u32p)), "dv_rviews_scene")
+        rows = [out[row0[i]:row0[i + 1]] for i in range(n)]
+        return (rows, flags) if want_flags else rows

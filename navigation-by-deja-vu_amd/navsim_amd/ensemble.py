@@ -496,6 +496,17 @@ class _RouteEnsemble(_OneValueEnsemble):
     def from_agent(cls, agent, poses):
         raise ValueError("%s is made from routes (from_routes); %s.from_agent clones a trained agent" % (cls.__name__, cls._one_route))
 
+    @classmethod
+    def _check_model(cls, model):
+        """Raises ValueError for an agent's familiarity_model that is not the ensemble's."""
+        if getattr(model, "metric", None) != cls._metric:
+            raise ValueError("%s takes %s; NavEnsemble steps the library-based models" % (cls.__name__, cls._takes))
+
+    @staticmethod
+    def _begin_model(model, eng, agent):
+        """A fresh model of the agent's views on the engine, before the routes are trained."""
+        model.begin(eng, agent.sensor_dimensions[1], agent.sensor_dimensions[0])
+
     @staticmethod
     def _train_banks(eng, n_routes, x, y, headings, bank_of_view, land_of_view=None):
         """One bank per route on the engine's fresh model, every view trained into its route's bank in one call -> the views.
@@ -526,8 +537,7 @@ class _RouteEnsemble(_OneValueEnsemble):
             raise ValueError("metrics must be one of %r, got %r" % (cls.METRICS, metrics))
         cls._reject_others(agent)
         model = getattr(agent, "familiarity_model", None)
-        if getattr(model, "metric", None) != cls._metric:
-            raise ValueError("%s takes %s; NavEnsemble steps the library-based models" % (cls.__name__, cls._takes))
+        cls._check_model(model)
         eng = getattr(agent, "_engine", None)
         if eng is None:
             raise ValueError("%s needs agents whose sensor model runs on the GPU (use_gpu_sensor=True)" % cls.__name__)
@@ -555,7 +565,7 @@ class _RouteEnsemble(_OneValueEnsemble):
         first = np.cumsum([0] + [len(r) for r in routes])
         points = np.concatenate(routes)
         bank_of_view = np.repeat(np.arange(len(routes), dtype=np.int32), [len(r) for r in routes])
-        model.begin(eng, agent.sensor_dimensions[1], agent.sensor_dimensions[0])
+        cls._begin_model(model, eng, agent)
         if lands is None:
             views = cls._train_banks(eng, len(routes), points[:, 0], points[:, 1], np.concatenate(headings), bank_of_view)
         else:
@@ -667,3 +677,117 @@ class InfomaxRouteEnsemble(_RouteEnsemble):
         if land_of_view is None:
             return eng.ibank_train_from_poses(x, y, headings, bank_of_view)
         return eng.ibank_train_from_poses(x, y, headings, bank_of_view, land_of_view=land_of_view)
+
+
+class SadsRouteEnsemble(_RouteEnsemble):
+    """The route ensemble of the reference's own model, perfect memory (util.sads_familiarity): trials that differ in their start, their
+    chem_weight, their TRAINING ROUTE and their LANDSCAPE step as one ensemble.  The engine keeps the sensed views of all routes side by
+    side (FamiliarityEngine.rviews_set_from_poses: one call senses them all), and a step scores every running member's headings against
+    the views of ITS OWN route under its own weight in ONE device call (dv_rviews_sense_step).  A member's angle_familiarity after a
+    step is the reference's row bit for bit (what a lone agent made with exact=True gives at the same pose); its scene_familiarity is
+    worked out when read (dv_rviews_scene), as NavEnsemble's members'.  A member's `memory_bank` is its route's place in the store.
+    Made by from_routes / from_routes_with / from_landscapes (see _RouteEnsemble); chem_weights: one per member, default the model's."""
+    _metric = None
+    _takes = "agents of the perfect-memory model (familiarity_model=sads_familiarity(...))"
+    _info_call = "rviews_info"               # dict(n_routes, first int64[R + 1], shape, bytes)
+    _one_route = "NavEnsemble"
+
+    @classmethod
+    def _check_model(cls, model):
+        metric = getattr(model, "metric", None)
+        if metric == "infomax":
+            raise ValueError("SadsRouteEnsemble does not take an Infomax model: navsim_amd.InfomaxRouteEnsemble steps that one")
+        if metric == "mushroom":
+            raise ValueError("SadsRouteEnsemble does not take a mushroom-body model: navsim_amd.MushroomRouteEnsemble steps that one")
+        if metric is not None or not callable(getattr(model, "from_engine", None)) or getattr(model, "chem_weight", None) is None:
+            raise ValueError("SadsRouteEnsemble takes %s; the SSD models and foreign plug-ins have no routed form" % cls._takes)
+
+    @classmethod
+    def _check_member(cls, agent):
+        func = getattr(agent, "_familiarity_func", None)
+        cls._check_model(getattr(agent, "familiarity_model", None))
+        if getattr(func, "metric", None) is not None:
+            raise ValueError("SadsRouteEnsemble takes %s" % cls._takes)
+        if getattr(agent, "_engine", None) is None:
+            raise ValueError("SadsRouteEnsemble needs agents whose sensor model runs on the GPU (use_gpu_sensor=True)")
+        if agent.training_path is None or func is None or getattr(func, "engine", None) is not agent._engine:
+            raise ValueError("SadsRouteEnsemble needs the members from_routes makes")
+
+    @staticmethod
+    def _begin_model(model, eng, agent):
+        """(nothing to begin: the store is made by the call that senses the routes)"""
+
+    @staticmethod
+    def _train_banks(eng, n_routes, x, y, headings, bank_of_view, land_of_view=None):
+        first = np.concatenate([[0], np.cumsum(np.bincount(bank_of_view, minlength=n_routes))]).astype(np.int64)
+        return eng.rviews_set_from_poses(x, y, headings, first, land_of_view=land_of_view)
+
+    def __init__(self, agents, metrics="host"):
+        super(SadsRouteEnsemble, self).__init__(agents, metrics=metrics)
+        self._set_weights([a.chem_weight for a in self.agents])
+
+    def _set_weights(self, weights):
+        """Member i scores under weights[i] (None: the model's own), kept as its `chem_weight`."""
+        w = [float(a.familiarity_model.chem_weight if x is None else x) for a, x in zip(self.agents, weights)]
+        for a, x in zip(self.agents, w):
+            a.chem_weight = x
+        self._weights = np.array(w, dtype=np.float64)
+
+    @staticmethod
+    def _weights_arg(chem_weights, starts):
+        if chem_weights is None:
+            return None
+        starts = list(starts)
+        w = [float(x) for x in chem_weights]
+        if len(w) != len(starts):
+            raise ValueError("chem_weights holds %d weights for %d starts" % (len(w), len(starts)))
+        if not all(0.0 <= x <= 1.0 for x in w):
+            raise ValueError("chem_weights must lie in [0, 1], got %r" % (w,))
+        return w
+
+    @classmethod
+    def from_routes_with(cls, agent, routes, starts, metrics="host", chem_weights=None):
+        """_RouteEnsemble.from_routes_with, and chem_weights: member i scores under chem_weights[i] (None: the model's weight)."""
+        starts = list(starts)
+        w = cls._weights_arg(chem_weights, starts)
+        ens = cls._from_routes(agent, routes, starts, metrics, None, None)
+        if w is not None:
+            ens._set_weights(w)
+        return ens
+
+    @classmethod
+    def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host", chem_weights=None):
+        """_RouteEnsemble.from_landscapes, and chem_weights as from_routes_with takes them."""
+        starts = list(starts)
+        w = cls._weights_arg(chem_weights, starts)
+        ens = super(SadsRouteEnsemble, cls).from_landscapes(agent, landscapes, routes, starts, metrics=metrics)
+        if w is not None:
+            ens._set_weights(w)
+        return ens
+
+    def _device_step(self, idx, xs, ys, angs):
+        return self.engine.rviews_sense_step(xs, ys, angs, self._banks[idx], self._weights[idx],
+                                             land_of_member=None if self._lands is None else self._lands[idx])
+
+    _note_scene = NavEnsemble._note_scene        # (a per-view minimum to work out when read, not the one-value models' fill)
+
+    def _read_scene(self):
+        todo = [a for a in self.agents if a._scene_stale is not None and a._scene_owner is self]
+        if not todo:
+            return
+        st = [a._scene_stale for a in todo]
+        lands = None if self._lands is None else [a.landscape_index for a in todo]
+        rows = self.engine.rviews_scene([t[0] for t in st], [t[1] for t in st], np.stack([t[2] for t in st]), [a.memory_bank for a in todo],
+                                        [t[3] for t in st], land_of_member=lands)
+        for a, row in zip(todo, rows):
+            a._scene_stale = None
+            a._scene_owner = None
+            a._scene_fam[:] = row
+
+    def scene_familiarity(self):
+        """A list of float64[len(route of member i)]: every member's scene_familiarity after its last step, as NavEnsemble gives it
+        (the rows are as long as the members' own routes, so they do not stack)."""
+        if any(not a.track_scene_familiarity for a in self.agents):
+            raise ValueError("construct the agents with track_scene_familiarity=True (the default) to read scene_familiarity")
+        self._read_scene()
+        return [a.scene_familiarity.copy() for a in self.agents]

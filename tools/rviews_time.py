@@ -1,0 +1,148 @@
+#!/usr/bin/env python3
+"""Times a step of the route view store (dv_rviews_sense_step, navsim_amd.SadsRouteEnsemble) at a slice of the reference's grid and
+writes profiles/rviews_time.json.
+
+    python tools/rviews_time.py [--sides 32,64] [--calls 30] [--reps 5] [--out profiles/rviews_time.json]
+
+Shape: 4 routes x 8 starts x 10 headings = 32 trials of 320 columns, views of side x side.  The routes have the grid's length:
+synth.sin_training_path with arclen = step_size / n_test_angles (scripts/run_experiment.py:207) on a 900 x 900 landscape, one curve
+a route.  Per side, medians (and the spread) of --reps alternating windows of --calls steps in one process:
+
+  routed_call_us        the routed call alone (dv_rviews_sense_step for all 32 members at fixed poses), by a hipEvent pair
+  routed_exact_call_us  the same call in its exact form (every view as the reference's sequential double sum)
+  ensemble_step_wall_us SadsRouteEnsemble.step_forward(fake=True), wall clock: the call and the host's share of a step
+  four_engines_wall_us  the same 32 trials as four NavEnsembles on four engines (a library a route) stepped in turn, wall clock --
+                        what there was before the store; four streams have no common event pair
+  four_engines_over_routed_wall   the ratio of the two wall-clock medians, whichever way it falls
+
+The routed call's rows are checked against the four engines' rows before anything is timed (same best headings, scores within 1e-12
+relative: the engines score in their default mode).  A window without a GPU fails; nothing here falls back."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "navigation-by-deja-vu_amd"))
+sys.path.insert(0, ROOT)
+
+CURVES = (0.0, 0.2, 0.35, 0.5)
+STARTS_PER_ROUTE, HEADINGS, STEP_SIZE, CHEM_WEIGHT, LAND = 8, 10, 2.0, 0.25, 900
+
+
+def spread(samples):
+    return dict(median=round(float(np.median(samples)), 3), min=round(float(min(samples)), 3), max=round(float(max(samples)), 3))
+
+
+def starts_of(routes):
+    """8 starts a route: beside points spread along it, looking along the route with a small offset."""
+    out = []
+    for r, path in enumerate(routes):
+        for k in range(STARTS_PER_ROUTE):
+            i = (k + 1) * len(path) // (STARTS_PER_ROUTE + 2)
+            d = path[i + 1] - path[i]
+            out.append((r, (float(path[i][0] + 0.7 * (k % 3 - 1)), float(path[i][1] - 0.5 * (k % 2))), float(np.arctan2(d[1], d[0]) % (2 * np.pi)) + 0.05 * k))
+    return out
+
+
+def measure(side, n_calls, reps):
+    import navsim_amd
+    from navsim_amd import synth
+    land = synth.synth_landscape(3, LAND, 4)
+    routes = [synth.sin_training_path(c, 0.2 * LAND, 0.6 * LAND, arclen=STEP_SIZE / HEADINGS) for c in CURVES]
+    starts = starts_of(routes)
+
+    def agent():
+        return navsim_amd.NavBySceneFamiliarity(land, (side, side), STEP_SIZE, n_test_angles=HEADINGS, track_scene_familiarity=False,
+                                                familiarity_model=navsim_amd.sads_familiarity(CHEM_WEIGHT))
+
+    t0 = time.perf_counter()
+    ens = navsim_amd.SadsRouteEnsemble.from_routes_with(agent(), routes, starts, metrics="device")
+    ens.engine.synchronize()
+    train_routed_s = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    four = []
+    for r, path in enumerate(routes):
+        a = agent()
+        a.train_from_path(path)
+        four.append(navsim_amd.NavEnsemble.from_agent(a, [(pos, ang) for rr, pos, ang in starts if rr == r]))
+        a._engine.synchronize()
+    train_four_s = time.perf_counter() - t0
+    eng = ens.engine
+    n = len(starts)
+    xs = np.array([p[0] for _, p, _ in starts])
+    ys = np.array([p[1] for _, p, _ in starts])
+    angs = (np.array([a for _, _, a in starts])[:, None] + ens.agents[0].angle_offsets[None, :]) % (2 * np.pi)
+    route_of = np.array([r for r, _, _ in starts], dtype=np.int32)
+    weights = np.full(n, CHEM_WEIGHT)
+    mine = [np.flatnonzero(route_of == r) for r in range(len(routes))]
+
+    def routed(exact=False):
+        eng.timer_start()
+        for _ in range(n_calls):
+            res = eng.rviews_sense_step(xs, ys, angs, route_of, weights, exact=exact)
+        return eng.timer_stop() * 1e3 / n_calls, res
+
+    def ensemble_steps():
+        w0 = time.perf_counter()
+        for _ in range(n_calls):
+            ens.step_forward(fake=True)
+        return (time.perf_counter() - w0) * 1e6 / n_calls
+
+    def four_engines():
+        w0 = time.perf_counter()
+        for _ in range(n_calls):
+            for e in four:
+                e.step_forward(fake=True)
+        return (time.perf_counter() - w0) * 1e6 / n_calls
+
+    _, res = routed()                                             # warm-up of every form (code load, clocks, the buffers)
+    _, res_exact = routed(True)
+    assert np.array_equal(res.angle_familiarity.view(np.uint64), res_exact.angle_familiarity.view(np.uint64))
+    assert np.array_equal(res.angle_view, res_exact.angle_view) and np.array_equal(res.best_idex, res_exact.best_idex) and not res.flags.any()
+    for r, m in enumerate(mine):                                  # the same decisions as an engine that holds that route's library alone
+        got = four[r].engine.sense_step_batch(xs[m], ys[m], angs[m])
+        assert np.array_equal(got.best_idex, res.best_idex[m])
+        np.testing.assert_allclose(got.angle_familiarity, res.angle_familiarity[m], rtol=1e-12, atol=0)
+    ensemble_steps()
+    four_engines()
+    assert len(ens.active) == n and all(len(e.active) == len(m) for e, m in zip(four, mine))
+    tr, te, ws, w4 = [], [], [], []
+    for _ in range(reps):                                         # alternating windows
+        tr.append(routed()[0])
+        te.append(routed(True)[0])
+        ws.append(ensemble_steps())
+        w4.append(four_engines())
+    info = eng.rviews_info()
+    out = dict(side=side, routes=len(routes), route_views=[len(r) for r in routes], members=n, headings=HEADINGS, columns=n * HEADINGS,
+               chem_weight=CHEM_WEIGHT, calls_per_window=n_calls, windows=reps, store_bytes=info["bytes"],
+               routed_call_us=spread(tr), routed_exact_call_us=spread(te), ensemble_step_wall_us=spread(ws),
+               four_engines_wall_us=spread(w4), four_engines_over_routed_wall=round(float(np.median(w4) / np.median(ws)), 3),
+               train_routed_s=round(train_routed_s, 3), train_four_engines_s=round(train_four_s, 3))
+    for e in [ens] + four:
+        e.engine.close()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sides", default="32,64")
+    ap.add_argument("--calls", type=int, default=30)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rviews_time.json"))
+    args = ap.parse_args()
+    rows = [measure(int(s), args.calls, args.reps) for s in args.sides.split(",")]
+    import torch                                                  # (after the windows: only to ask the device its name)
+    doc = dict(tool="tools/rviews_time.py", device=torch.cuda.get_device_name(0), step_form="step_forward(fake=True)", note="medians of alternating windows in one process; wall-clock figures "
+               "include the host's share of a step", sizes=rows)
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print(json.dumps(doc))
+
+
+if __name__ == "__main__":
+    main()

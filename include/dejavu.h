@@ -776,7 +776,8 @@ int dv_ibank_info(dv_ctx *ctx, int *n_banks, int64_t *views_trained, int32_t *fi
  * Several HSV landscapes of any shapes resident together in ONE context, and a landscape index per pose in the sensed calls of the
  * banked models: the landscape replicates of a grid (and, with a bank per route, their routes) train in one call and step in one call.
  * The set is one allocation with the landscapes back to back, no padding.  The sensor geometry, the level table and the mask stay the
- * context's one configuration (dv_configure_sensor), shared by all landscapes of the set.  dv_set_landscape's landscape and every call
+ * context's one configuration (dv_configure_sensor), shared by all landscapes of the set unless a sensor table gives every landscape
+ * its own (dv_sensors_set, below).  dv_set_landscape's landscape and every call
  * that reads it are untouched by a set, and the set by them: dv_set_landscape, dv_mb_end and dv_infomax_end leave the set alone;
  * dv_destroy frees it.  A landscape table is int32, one entry per pose or view (lands_sense, training) or per member (a step); every
  * entry is checked against [0, n_lands) before anything of the call reaches the device: DV_ERR_INVALID names the first entry out of
@@ -807,6 +808,29 @@ int dv_lands_mbank_sense_step(dv_ctx *ctx, const double *x, const double *y, con
 int dv_lands_ibank_sense_step(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
                               const int32_t *bank_of_member, const int32_t *land_of_member, double *angle_fam, int32_t *best_heading,
                               uint32_t *flags);
+
+/* ---- sensor tables: a sensor configuration per landscape of the set ----------- */
+/*
+ * Entry l of a sensor table is the sensor that landscape l of the live landscape set is sensed with: sensor_pixel_dimensions (pw[l],
+ * ph[l]), mask_middle_n mask_n[l] and a level table uint8[3][256] of its own (luts: the entries' tables back to back).  The sensor's
+ * w x h stays the context's one for all entries (dv_configure_sensor): the one-value models and the route view store are built on it.
+ * A trial that uses two sensors on one landscape enters that landscape into the set twice.
+ * With a table, every call that takes a landscape table senses a pose under its landscape's entry, with no new argument:
+ * dv_lands_sense, dv_lands_mbank_ / dv_lands_ibank_train_from_poses, dv_lands_mbank_ / dv_lands_ibank_sense_step, and
+ * dv_rviews_set_from_poses / dv_rviews_sense_step / dv_rviews_scene with a land_of_* table.  The footprint that must stay on a pose's
+ * landscape is its entry's own, (w pw) x (h ph).  A call with land_of_* == NULL, and every call that takes no landscape table, senses
+ * the context's landscape under the context's sensor, table or not; with no table every call does what it did before.
+ *   set              n == n_lands of the live set (DV_ERR_STATE without a set or a configured sensor, DV_ERR_INVALID otherwise).  Every
+ *                    entry is checked as dv_configure_sensor checks its own -- pw, ph >= 1, pw * ph <= 4096, 0 <= mask_n <= w / 2 -- and
+ *                    DV_ERR_INVALID names the entry.  The replacement is built first: an error leaves the old table as it was.
+ *   clear            no table: the context's one sensor for every landscape again.
+ *   info             n (0: no table) and the entries (the caller's arrays of n, luts of n * 768: ask for n first); any pointer may be NULL.
+ * dv_lands_set and dv_lands_clear drop a live table (the entries it belonged to are gone), as does a dv_configure_sensor that changes
+ * w x h; dv_destroy frees it.
+ */
+int dv_sensors_set(dv_ctx *ctx, const int32_t *pw, const int32_t *ph, const int32_t *mask_n, const uint8_t *luts, int n);
+int dv_sensors_clear(dv_ctx *ctx);
+int dv_sensors_info(dv_ctx *ctx, int *n, int32_t *pw, int32_t *ph, int32_t *mask_n, uint8_t *luts);
 
 /* ---- route view store: perfect-memory members on their own routes ------------ */
 /*

@@ -370,6 +370,11 @@ struct dv_ctx {
     int* ld_err = nullptr;                    // [n]: k_sense_lands' word per pose (dv_lands_sense, training from poses)
     size_t ld_err_cap = 0;                    // bytes
     std::vector<int> ld_err_host;
+    // sensor table of the landscape set (dejavu_sensors.inl: dv_sensors_*): entry l is the sensor landscape l is sensed with
+    SensorEntry* sn_tab = nullptr;            // [n_lands]: pixel block and mask (nullptr: no table, the context's one sensor for all)
+    unsigned char* sn_luts = nullptr;         // [n_lands][3][256]: the entries' level tables
+    std::vector<int32_t> sn_pw, sn_ph, sn_mask;   // [n_lands] (empty: no table)
+    std::vector<uint8_t> sn_luts_host;        // [n_lands][3][256]
     // route view store (dejavu_rviews.inl: dv_rviews_*): independent of the library above
     unsigned* rv_planes = nullptr;            // groups of 64 views, three byte planes each (nullptr: no store)
     RvRoute* rv_routes = nullptr;             // [n_routes]: first group, views
@@ -421,6 +426,7 @@ static void diffuse_free(dv_ctx* c);
 static void infomax_free(dv_ctx* c);
 static void mb_free(dv_ctx* c);
 static void lands_free(dv_ctx* c);
+static void sensors_free(dv_ctx* c);
 static void rviews_free(dv_ctx* c);
 static void path_routes_free(dv_ctx* c);
 static void free_library(dv_ctx* c) {
@@ -1460,6 +1466,7 @@ extern "C" int dv_configure_sensor(dv_ctx* c, int sw, int sh, int pw, int ph, co
     }
     HIP_TRY(c, hipMemcpyAsync(c->d_lut, lut, 768, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->have_sensor && (c->sensor.sw != sw || c->sensor.sh != sh)) sensors_free(c);   // (a sensor table's masks were checked against the old w)
     c->sensor.sw = sw; c->sensor.sh = sh; c->sensor.pw = pw; c->sensor.ph = ph; c->sensor.mask_n = mask_n;
     c->have_sensor = true;
     return DV_OK;
@@ -3745,6 +3752,7 @@ extern "C" int dv_stream_read_gbps(dv_ctx* c, int64_t n_bytes, int iters, double
 
 #include "dejavu_diffuse.inl"   // dv_diffuse_*: the landscape generator's heat equation (kernels and host side)
 #include "dejavu_lands.inl"     // dv_lands_*: landscape sets, a landscape per pose in the banked models' sensed calls (kernel and host side)
+#include "dejavu_sensors.inl"   // dv_sensors_*: a sensor configuration per landscape of the set (kernel and host side)
 #include "dejavu_rviews.inl"    // dv_rviews_*: route view store, perfect-memory members scored on their own routes (kernels and host side)
 #include "dejavu_infomax.inl"   // dv_infomax_*: the Infomax familiarity model (kernels and host side)
 #include "dejavu_mushroom.inl"  // dv_mb_*: the mushroom-body familiarity model (kernels and host side)

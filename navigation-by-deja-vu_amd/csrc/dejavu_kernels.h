@@ -2435,6 +2435,7 @@ struct SensorCfg {
 };
 struct Pose { double x, y, c, s; };   // position and cos/sin of -(pi/2 - angle), computed by the host's libm
 struct LandEntry { long long base; int rows, cols; };   // a landscape of a set (dejavu_lands.inl): its first byte within the set, its shape
+struct SensorEntry { int pw, ph, mask_n; };               // the sensor a landscape of a set is sensed with (dejavu_sensors.inl); sw x sh stay the context's
 
 __device__ __forceinline__ bool sense_fetch(const unsigned char* __restrict__ land, const SensorCfg& g, const Pose& p,
                                             int i, int j, unsigned& H, unsigned& S, unsigned& V) {

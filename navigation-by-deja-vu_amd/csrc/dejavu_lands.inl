@@ -1,9 +1,10 @@
 // Landscape sets (include/dejavu.h: dv_lands_*): several HSV landscapes of any shapes resident together, and a landscape index per
 // pose in the sensed calls of the banked models.  The set is one allocation, the landscapes back to back with no padding (a 211 x 173
 // landscape is 109 509 bytes, so its successor begins at an odd byte: the sensor model reads bytes, sense_fetch, and asks for no
-// alignment), and a table LandEntry { base, rows, cols }[n_lands] beside it.  The sensor geometry, the level table and the mask stay
-// the context's one configuration (dv_configure_sensor); dv_set_landscape's landscape, d_land, and every call that reads it are
-// untouched by a set, and the set by them.
+// alignment), and a table LandEntry { base, rows, cols }[n_lands] beside it.  The sensor geometry, the level table and the mask are
+// the context's one configuration (dv_configure_sensor) unless the set has a sensor table (dejavu_sensors.inl), which gives every
+// landscape a pixel block, a mask and a level table of its own; dv_set_landscape's landscape, d_land, and every call that reads it
+// are untouched by a set, and the set by them.
 //
 // A pose's landscape is land_of[(col0 + pose) / per], the rule mb_bank uses for banks: per = 1 in training (a landscape per view),
 // per = A in an ensemble's step (a landscape per member), col0 the launch's first column within the call.
@@ -39,8 +40,11 @@ __global__ void k_sense_lands(const unsigned char* __restrict__ lands, const Lan
 
 }  // namespace dv
 
+static int sensors_launch_sense(dv_ctx* c, long long p0, long long col0, int per, long long n, unsigned char* d_out, int* err);   // (dejavu_sensors.inl)
+
 static void lands_free(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
+    sensors_free(c);                                           // (a sensor table belongs to the entries of its set)
     F(c->ld_lands); F(c->ld_tab); F(c->ld_of); F(c->ld_err);
     c->ld_of_cap = c->ld_err_cap = 0;
     c->ld_bytes = 0;
@@ -81,8 +85,10 @@ static int lands_upload(dv_ctx* c, const int32_t* land_of, int64_t n) {
 }
 
 // Enqueue k_sense_lands for `n` poses that are resident in d_poses from `p0` on and are columns col0 .. of the call, into d_out
-// (uint8[n][sh][sw][3]); err: int[n], zeroed by the caller.
+// (uint8[n][sh][sw][3]); err: int[n], zeroed by the caller.  Where the set has a sensor table (dejavu_sensors.inl) the pose's sensor is
+// its landscape's entry, through the kernel form that reads the table.
 static int lands_launch_sense(dv_ctx* c, long long p0, long long col0, int per, long long n, unsigned char* d_out, int* err) {
+    if (c->sn_tab) return sensors_launch_sense(c, p0, col0, per, n, d_out, err);
     const long long total = n * c->sensor.sh * c->sensor.sw;
     hipLaunchKernelGGL(k_sense_lands, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, c->ld_lands, c->ld_tab, (const int*)c->ld_of,
                        (unsigned)col0, (unsigned)per, c->d_poses + p0, (int)n, c->sensor, c->d_lut, d_out, err);
@@ -148,6 +154,7 @@ extern "C" int dv_lands_set(dv_ctx* c, const uint8_t* lands, const int32_t* rows
     c->ld_bytes = bytes;
     c->ld_rows.assign(rows, rows + n_lands);
     c->ld_cols.assign(cols, cols + n_lands);
+    sensors_free(c);                                                    // (the entries a sensor table belonged to are gone)
     return DV_OK;
 }
 

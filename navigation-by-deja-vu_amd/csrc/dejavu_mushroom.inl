@@ -34,7 +34,8 @@
 //
 // Landscape sets (dejavu_lands.inl).  k_mb_pose_bank_lands is k_mb_pose_bank with one more table: the column's landscape,
 // land_of[(col0 + blockIdx.x) / per], whose first byte and shape mb_fill_pose is handed instead of the context's one landscape.  The
-// plane still goes from the landscape to LDS; everything after it is mb_view.
+// plane still goes from the landscape to LDS; everything after it is mb_view.  k_mb_pose_bank_lands_sensors reads the column's sensor
+// (pixel block, mask, level table) from the set's sensor table as well (dejavu_sensors.inl); it is launched only where a table is live.
 namespace dv {
 
 static constexpr int kMbTrain = 0, kMbScore = 1, kMbMask = 2;
@@ -259,6 +260,23 @@ __global__ __launch_bounds__(kMbWaves * 64) void k_mb_pose_bank_lands(const unsi
                       (int)blockIdx.x, N, conn, K, c, n_active, mb_bank(wt, K, bank_of, col0, per), d, nullptr, nullptr);
 }
 
+// ... and under the landscape's own sensor where the set has a sensor table (dejavu_sensors.inl): the workgroup is one column, so one
+// entry, and every thread of it walks the same pixel block.
+__global__ __launch_bounds__(kMbWaves * 64) void k_mb_pose_bank_lands_sensors(const unsigned char* __restrict__ lands, const LandEntry* __restrict__ tab,
+                                                                              const SensorEntry* __restrict__ sens, const unsigned char* __restrict__ luts,
+                                                                              const int* __restrict__ land_of, const Pose* __restrict__ poses, SensorCfg g,
+                                                                              int channel, const unsigned short* __restrict__ conn, int K, int c,
+                                                                              int n_active, unsigned char* __restrict__ wt, int* __restrict__ d,
+                                                                              int* __restrict__ err, const int* __restrict__ bank_of, unsigned col0,
+                                                                              unsigned per) {
+    extern __shared__ unsigned mb_lds[];
+    const int N = g.sh * g.sw;
+    const unsigned char* lut;
+    const unsigned char* land = land_sensor_of_column(lands, tab, sens, luts, land_of, col0 + blockIdx.x, per, g, lut);
+    mb_view<kMbScore>(mb_lds, [&](unsigned char* plane, int tid) { mb_fill_pose(plane, tid, land, poses, g, lut, channel, N, err); },
+                      (int)blockIdx.x, N, conn, K, c, n_active, mb_bank(wt, K, bank_of, col0, per), d, nullptr, nullptr);
+}
+
 // zeros[b] = the zero weights of bank b = blockIdx.x (wt: [banks][K]).
 __global__ __launch_bounds__(256) void k_mb_count(const unsigned char* __restrict__ wt, int K, long long* __restrict__ zeros) {
     __shared__ int red[256];
@@ -404,6 +422,7 @@ extern "C" int dv_mb_begin(dv_ctx* c, int h, int w, int channel, int n_kc, int f
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_bank<kMbScore>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_pose_bank, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_pose_bank_lands, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_pose_bank_lands_sensors, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = hipMemcpyAsync(c->mb_conn, ct.data(), ct.size() * sizeof(unsigned short), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->mb_wt, 1, K, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);           // `ct` is this call's
@@ -573,7 +592,8 @@ extern "C" int dv_mb_sense_step(dv_ctx* c, double x, double y, const double* ang
 // launches follow one another on the stream; the host waits once, for the one copy of the packed results.
 // bank_of == nullptr: every member scores under bank 0 (the dv_batch_mb_* calls); else member i under bank bank_of[i], through the
 // banked kernels -- the same enqueue, with the members' table uploaded ahead of the launches.
-// land_of != nullptr (poses and banks only): member i senses landscape land_of[i] of the set, through k_mb_pose_bank_lands.
+// land_of != nullptr (poses and banks only): member i senses landscape land_of[i] of the set, through k_mb_pose_bank_lands, or through
+// k_mb_pose_bank_lands_sensors under that landscape's own sensor where the set has a sensor table.
 static int mb_batch(dv_ctx* c, const char* who, const uint8_t* planes, const double* x, const double* y, const double* angles, int n_agents, int A,
                     const int32_t* bank_of, const int32_t* land_of, double* angle_fam, int32_t* best_heading, uint32_t* flags) {
     const long long C = (long long)n_agents * A;
@@ -603,6 +623,11 @@ static int mb_batch(dv_ctx* c, const char* who, const uint8_t* planes, const dou
             rc = bank_of ? mb_launch_bank<kMbScore>(c, c->d_sense, (long long)N, 1, 0, nc, c->mb_bd + c0, c->mb_bank_of, c0, A)
                          : mb_launch<kMbScore>(c, c->d_sense, (long long)N, 1, 0, nc, c->mb_bd + c0, nullptr, nullptr);
             if (rc) return rc;
+        } else if (land_of && c->sn_tab) {
+            hipLaunchKernelGGL(k_mb_pose_bank_lands_sensors, dim3((unsigned)nc), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, c->ld_lands, c->ld_tab,
+                               c->sn_tab, c->sn_luts, (const int*)c->ld_of, c->d_poses + c0, c->sensor, c->mb_channel, c->mb_conn, c->mb_K, c->mb_c,
+                               c->mb_active, c->mb_wt, c->mb_bd + c0, c->mb_berr + c0, (const int*)c->mb_bank_of, (unsigned)c0, (unsigned)A);
+            HIP_TRY(c, hipGetLastError());
         } else if (land_of) {
             hipLaunchKernelGGL(k_mb_pose_bank_lands, dim3((unsigned)nc), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, c->ld_lands, c->ld_tab,
                                (const int*)c->ld_of, c->d_poses + c0, c->sensor, c->d_lut, c->mb_channel, c->mb_conn, c->mb_K, c->mb_c, c->mb_active,

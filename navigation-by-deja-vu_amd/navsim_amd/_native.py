@@ -286,6 +286,9 @@ PROTOTYPES = {
     "dv_lands_ibank_train_from_poses": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int64, _i32p, _i32p, _u8p]),
     "dv_lands_mbank_sense_step": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _i32p, _i32p, _f64p, _i32p, _u32p]),
     "dv_lands_ibank_sense_step": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _i32p, _i32p, _f64p, _i32p, _u32p]),
+    "dv_sensors_set": (ctypes.c_int, [_ctx_p, _i32p, _i32p, _i32p, _u8p, ctypes.c_int]),
+    "dv_sensors_clear": (ctypes.c_int, [_ctx_p]),
+    "dv_sensors_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), _i32p, _i32p, _i32p, _u8p]),
     "dv_rviews_set_u8": (ctypes.c_int, [_ctx_p, _u8p, _i64p, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "dv_rviews_set_from_poses": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int64, _i64p, ctypes.c_int, _i32p, _u8p]),
     "dv_rviews_step_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, _i32p, _f64p, ctypes.c_uint32, _f64p, _i64p, _i32p]),

@@ -153,6 +153,7 @@ class NavBySceneFamiliarity(object):
     chem_weight = None              # a NavEnsemble member's own weight (NavEnsemble.from_agent(chem_weights=...)); None: the model's
     memory_bank = None              # a route ensemble's member: its own bank of the shared mushroom-body or Infomax model; None: the model's one
     landscape_index = None          # ... made by from_landscapes: its landscape's place in the engine's landscape set; None: the engine's one
+    sensor_index = None             # ... made by from_landscapes(sensors=...): its entry of the set's sensor table (its landscape's); None: the engine's one sensor
 
     def __init__(self,
                  landscape,
@@ -384,6 +385,8 @@ class NavBySceneFamiliarity(object):
     def get_sensor_mat(self, position, angle):
         self._check_bounds(position)
         if self._engine is not None:
+            if self.sensor_index is not None:      # its landscape's entry of the sensor table: the engine's one sensor is not this member's
+                return self._engine.lands_sense([position[0]], [position[1]], [angle], [self.landscape_index])[0]
             return self._engine.sense([position[0]], [position[1]], [angle])[0]
 
         fill_sensor_from(self._landscape_glimpse_buf, position[0], position[1], angle, self.landscape)

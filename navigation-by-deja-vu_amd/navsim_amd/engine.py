@@ -231,7 +231,10 @@ class FamiliarityEngine(object):
         self._check(self._lib.dv_configure_sensor(self._ctx, int(sensor_dimensions[0]), int(sensor_dimensions[1]),
                                                   int(sensor_pixel_dimensions[0]), int(sensor_pixel_dimensions[1]),
                                                   N.u8ptr(lut), int(mask_middle_n)), "dv_configure_sensor")
-        self.sensor_shape = (int(sensor_dimensions[1]), int(sensor_dimensions[0]))
+        shape = (int(sensor_dimensions[1]), int(sensor_dimensions[0]))
+        if getattr(self, "sensor_shape", shape) != shape:
+            self.n_sensors = 0                                   # (a sensor table was checked against the old w x h: the library drops it)
+        self.sensor_shape = shape
 
     @staticmethod
     def _pose_arrays(x, y, angle):
@@ -1443,7 +1446,8 @@ class FamiliarityEngine(object):
 
     def lands_set(self, landscapes):
         """landscapes: a list of uint8[rows, cols, 3] HSV of any shapes and strides (copied), kept resident together beside the engine's
-        one landscape (set_landscape), which they leave alone.  The sensor configuration is the engine's one (configure_sensor)."""
+        one landscape (set_landscape), which they leave alone.  The sensor configuration is the engine's one (configure_sensor) until
+        sensors_set gives every landscape of the set its own; a new set drops that table."""
         lands = [N.as_u8(l, "landscapes[%d]" % i) for i, l in enumerate(landscapes)]
         if not lands:
             raise ValueError("no landscapes: a set holds at least one")
@@ -1456,10 +1460,12 @@ class FamiliarityEngine(object):
         self._check(self._lib.dv_lands_set(self._ctx, N.u8ptr(flat), rows.ctypes.data_as(N._i32p), cols.ctypes.data_as(N._i32p), len(lands), 3),
                     "dv_lands_set")
         self.n_lands = len(lands)
+        self.n_sensors = 0                                       # (a sensor table belonged to the old set's entries: the library drops it)
 
     def lands_clear(self):
         self._check(self._lib.dv_lands_clear(self._ctx), "dv_lands_clear")
         self.n_lands = 0
+        self.n_sensors = 0
 
     def lands_info(self):
         """dict(n_lands, shapes: list of (rows, cols), bytes)."""
@@ -1482,6 +1488,61 @@ class FamiliarityEngine(object):
         self._check_sense(self._lib.dv_lands_sense(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), lands.ctypes.data_as(N._i32p), len(x),
                                                    N.u8ptr(out)), "dv_lands_sense")
         return out
+
+    # -- sensor tables: a sensor configuration per landscape of the set (include/dejavu.h: dv_sensors_*) ---------------------------
+    n_sensors = 0                # entries of the set's sensor table (sensors_set; 0: the engine's one sensor for every landscape)
+    SENSOR_MAX_BLOCK = 4096      # pw * ph of a sensor pixel, as dv_configure_sensor bounds it
+
+    def sensors_set(self, pixel_dimensions, luts, masks):
+        """A sensor per landscape of the live set: entry l is what landscape l is sensed with by every call that takes a landscape
+        table.  pixel_dimensions: integers [n_lands, 2], (pw, ph) a row; luts: uint8[n_lands, 3, 256] level tables; masks: integers
+        [n_lands] (mask_middle_n).  The sensor's w x h stays the engine's one (configure_sensor).  Dtype, shape and range are checked
+        before any library call; ValueError names the entry."""
+        if not self.n_lands:
+            raise N.EngineError("sensors_set: the engine holds no landscape set: lands_set first (DV_ERR_STATE)")
+        if getattr(self, "sensor_shape", None) is None:
+            raise N.EngineError("sensors_set: no sensor configured: configure_sensor sets the w x h all entries share (DV_ERR_STATE)")
+        n = self.n_lands
+        px, mk, lt = np.asarray(pixel_dimensions), np.asarray(masks), np.asarray(luts)
+        for arr, what, shape in ((px, "pixel_dimensions", (n, 2)), (mk, "masks", (n,))):
+            if arr.dtype.kind not in "iu":
+                raise ValueError("%s must hold integers, got dtype %s" % (what, arr.dtype))
+            if arr.shape != shape:
+                raise ValueError("%s must have shape %r (an entry per landscape of the set), got %r" % (what, shape, arr.shape))
+        if lt.dtype != np.uint8:
+            raise ValueError("luts must be uint8 level tables, got dtype %s" % lt.dtype)
+        if lt.shape != (n, 3, 256):
+            raise ValueError("luts must have shape %r (an entry per landscape of the set), got %r" % ((n, 3, 256), lt.shape))
+        w = self.sensor_shape[1]
+        for l in range(n):
+            pw, ph, m = int(px[l, 0]), int(px[l, 1]), int(mk[l])
+            if pw < 1 or ph < 1 or pw * ph > self.SENSOR_MAX_BLOCK:
+                raise ValueError("pixel_dimensions[%d] = (%d, %d): pw, ph >= 1 and pw * ph <= %d" % (l, pw, ph, self.SENSOR_MAX_BLOCK))
+            if not 0 <= m <= w // 2:
+                raise ValueError("masks[%d] = %d outside [0, w / 2 = %d]" % (l, m, w // 2))
+        pw = np.ascontiguousarray(px[:, 0], dtype=np.int32)
+        ph = np.ascontiguousarray(px[:, 1], dtype=np.int32)
+        mk = np.ascontiguousarray(mk, dtype=np.int32)
+        lt = np.ascontiguousarray(lt)
+        self._check(self._lib.dv_sensors_set(self._ctx, pw.ctypes.data_as(N._i32p), ph.ctypes.data_as(N._i32p), mk.ctypes.data_as(N._i32p),
+                                             N.u8ptr(lt), n), "dv_sensors_set")
+        self.n_sensors = n
+
+    def sensors_clear(self):
+        self._check(self._lib.dv_sensors_clear(self._ctx), "dv_sensors_clear")
+        self.n_sensors = 0
+
+    def sensors_info(self):
+        """dict(n_sensors, pixel_dimensions int32[n, 2], masks int32[n], luts uint8[n, 3, 256]) of the live table (n = 0: none)."""
+        n = ctypes.c_int(0)
+        self._check(self._lib.dv_sensors_info(self._ctx, ctypes.byref(n), None, None, None, None), "dv_sensors_info")
+        k = max(n.value, 1)
+        pw, ph, mk = (np.zeros(k, dtype=np.int32) for _ in range(3))
+        lt = np.zeros((k, 3, 256), dtype=np.uint8)
+        self._check(self._lib.dv_sensors_info(self._ctx, None, pw.ctypes.data_as(N._i32p), ph.ctypes.data_as(N._i32p), mk.ctypes.data_as(N._i32p),
+                                              N.u8ptr(lt)), "dv_sensors_info")
+        self.n_sensors = n.value
+        return dict(n_sensors=n.value, pixel_dimensions=np.stack([pw, ph], axis=1)[:n.value], masks=mk[:n.value], luts=lt[:n.value])
 
     # -- route view store: perfect-memory members scored on their own routes (include/dejavu.h: dv_rviews_*) ------------------------
     rviews_first = None          # int64[n_routes + 1] of the store (rviews_set_u8 / rviews_set_from_poses; None: no store)

@@ -421,7 +421,12 @@ class _RouteEnsemble(_OneValueEnsemble):
     from_landscapes makes trials that differ in their LANDSCAPE as well: the engine holds the landscapes as a set
     (FamiliarityEngine.lands_set), every route is sensed on its own landscape, and a step hands the device the members' landscapes
     beside their banks.  Members on landscapes of one shape keep the vectorised host path of a step; members on landscapes of
-    different shapes work out their headings one by one (headings_to_test), each against its own bounds."""
+    different shapes work out their headings one by one (headings_to_test), each against its own bounds.
+
+    from_landscapes(sensors=[...]) makes trials that differ in their SENSOR too: entry l of the list is the sensor landscape l is sensed
+    with -- its sensor_pixel_dimensions, n_sensor_levels and mask_middle_n; w x h stays the engine's one -- kept on the engine as the
+    set's sensor table (FamiliarityEngine.sensors_set).  A trial that uses two sensors on one landscape enters that landscape twice.
+    The members of a route on landscape l carry that entry's configuration, so their bounds are their own footprint's."""
     _metrics_on_slots = False    # (NavEnsemble's slots hold ONE training path: the routed slots are made below)
     _one_route = None            # the name of the ensemble whose members share one trained route
     _info_call = None            # the engine's per-bank info
@@ -529,9 +534,9 @@ class _RouteEnsemble(_OneValueEnsemble):
         return cls._from_routes(agent, routes, starts, metrics, None, None)
 
     @classmethod
-    def _from_routes(cls, agent, routes, starts, metrics, lands, land_of_route):
+    def _from_routes(cls, agent, routes, starts, metrics, lands, land_of_route, sensors=None):
         """from_routes_with (lands None: every route on the agent's own landscape, the engine's one), or from_landscapes (route r on
-        lands[land_of_route[r]] of the engine's landscape set)."""
+        lands[land_of_route[r]] of the engine's landscape set; sensors: None, or _sensor_entries' entry per landscape)."""
         import copy
         if metrics not in cls.METRICS:
             raise ValueError("metrics must be one of %r, got %r" % (cls.METRICS, metrics))
@@ -553,7 +558,8 @@ class _RouteEnsemble(_OneValueEnsemble):
             if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 0 <= r < len(routes):
                 raise ValueError("starts[%d]: route_index %r outside [0, %d)" % (i, r, len(routes)))
         for k, route in enumerate(routes):                        # (the agent's own bounds test, on the route's own landscape)
-            probe = agent if lands is None else cls._on_landscape(copy.copy(agent), lands[land_of_route[k]])
+            probe = agent if lands is None else cls._on_landscape(copy.copy(agent), lands[land_of_route[k]],
+                                                                  None if sensors is None else sensors[land_of_route[k]])
             for pt in route:
                 probe._check_bounds(pt)
         # the views of a route look along ITS steps (train_from_path: towards the next point, the last heading once more)
@@ -570,6 +576,9 @@ class _RouteEnsemble(_OneValueEnsemble):
             views = cls._train_banks(eng, len(routes), points[:, 0], points[:, 1], np.concatenate(headings), bank_of_view)
         else:
             eng.lands_set(lands)
+            if sensors is not None:
+                eng.sensors_set([e["sensor_pixel_dimensions"] for e in sensors], np.stack([e["lut"] for e in sensors]),
+                                [e["mask_middle_n"] for e in sensors])
             land_of_view = np.repeat(np.array(land_of_route, dtype=np.int32), [len(r) for r in routes])
             views = cls._train_banks(eng, len(routes), points[:, 0], points[:, 1], np.concatenate(headings), bank_of_view, land_of_view)
         func = model.from_engine(eng, views)
@@ -584,7 +593,7 @@ class _RouteEnsemble(_OneValueEnsemble):
             a.memory_bank = int(r)
             if lands is not None:
                 a.landscape_index = land_of_route[r]
-                cls._on_landscape(a, lands[a.landscape_index])
+                cls._on_landscape(a, lands[a.landscape_index], None if sensors is None else sensors[a.landscape_index])
             a.angle_familiarity = np.full(agent.n_test_angles, np.nan)
             a.scene_familiarity = np.zeros(len(route), dtype=np.float64)
             a._scene_is_inf = False
@@ -597,20 +606,76 @@ class _RouteEnsemble(_OneValueEnsemble):
         return cls(members, metrics=metrics)
 
     @staticmethod
-    def _on_landscape(agent, landscape):
-        """`agent` on `landscape`: its bounds are worked out again from that landscape's shape -> the agent."""
+    def _on_landscape(agent, landscape, sensor=None):
+        """`agent` on `landscape`: its bounds are worked out again from that landscape's shape -> the agent.  sensor: that landscape's
+        entry of the sensor table (_sensor_entries), which the agent then carries: its bounds are its own footprint's."""
         agent.landscape = landscape
+        if sensor is not None:
+            agent.sensor_index = sensor["index"]
+            agent.sensor_pixel_dimensions = sensor["sensor_pixel_dimensions"].copy()
+            agent.n_sensor_levels = sensor["n_sensor_levels"]
+            agent.mask_middle_n = sensor["mask_middle_n"]
+            extent = agent.sensor_dimensions * agent.sensor_pixel_dimensions
+            agent._sensor_r = np.max(extent / 2)
+            agent._landscape_glimpse_buf = np.empty((extent[1], extent[0], 3), dtype=np.uint8)
         agent._bounds = agent._bounds_arr = None
         return agent
 
+    SENSOR_KEYS = ("sensor_pixel_dimensions", "n_sensor_levels", "mask_middle_n")
+
     @classmethod
-    def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host"):
+    def _sensor_entries(cls, agent, n_lands, sensors):
+        """from_landscapes' `sensors` as a list of dict(index, sensor_pixel_dimensions int[2], n_sensor_levels (3-tuple), mask_middle_n,
+        lut uint8[3, 256]), an entry per landscape; a key an entry leaves out takes the agent's value.  ValueError names the entry."""
+        import copy
+        sensors = list(sensors)
+        if len(sensors) != n_lands:
+            raise ValueError("sensors holds %d entries for %d landscapes: one per landscape (None: the agent's own configuration)"
+                             % (len(sensors), n_lands))
+        w = int(agent.sensor_dimensions[0])
+        out = []
+        for l, s in enumerate(sensors):
+            if s is not None and not isinstance(s, dict):
+                raise ValueError("sensors[%d] must be None or a dict with any of %r" % (l, cls.SENSOR_KEYS))
+            s = dict(s or {})
+            if "sensor_dimensions" in s:
+                raise ValueError("sensors[%d]: sensor_dimensions cannot differ between entries: w × h is the engine's one" % l)
+            extra = sorted(set(s) - set(cls.SENSOR_KEYS))
+            if extra:
+                raise ValueError("sensors[%d]: unknown keys %r (an entry holds any of %r)" % (l, extra, cls.SENSOR_KEYS))
+            px = np.asarray(s.get("sensor_pixel_dimensions", agent.sensor_pixel_dimensions))
+            if px.dtype.kind not in "iu" or px.shape != (2,) or px.min() < 1 or int(px[0]) * int(px[1]) > 4096:
+                raise ValueError("sensors[%d]: sensor_pixel_dimensions must be two integers (pw, ph) >= 1 with pw * ph <= 4096, got %r"
+                                 % (l, s.get("sensor_pixel_dimensions")))
+            if np.any((agent.sensor_dimensions * px) % 2 != 0):
+                raise ValueError("sensors[%d]: the sensor's extent %r in landscape pixels must be even" % (l, (agent.sensor_dimensions * px).tolist()))
+            levels = s.get("n_sensor_levels", agent.n_sensor_levels)
+            if not isinstance(levels, tuple):
+                levels = (256, 256, levels)
+            if len(levels) != 3 or not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 2 <= v <= 256 for v in levels):
+                raise ValueError("sensors[%d]: n_sensor_levels must be in [2, 256] (one value, or a tuple of three), got %r" % (l, levels))
+            mask = s.get("mask_middle_n", agent.mask_middle_n)
+            if isinstance(mask, bool) or not isinstance(mask, (int, np.integer)) or not 0 <= mask <= w // 2:
+                raise ValueError("sensors[%d]: mask_middle_n %r outside [0, w / 2 = %d]" % (l, mask, w // 2))
+            probe = copy.copy(agent)                              # the agent's own level arithmetic, on the entry's levels
+            probe.n_sensor_levels = tuple(int(v) for v in levels)
+            out.append(dict(index=l, sensor_pixel_dimensions=px.astype(np.asarray(agent.sensor_pixel_dimensions).dtype),
+                            n_sensor_levels=probe.n_sensor_levels, mask_middle_n=int(mask), lut=probe._level_tables()))
+        return out
+
+    @classmethod
+    def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host", sensors=None):
         """Trials that differ in their LANDSCAPE, their training route and their start.  `agent`: an UNTRAINED agent of the ensemble's
         model with the GPU sensor model; landscapes: a list of uint8[rows, cols, 3] of any shapes; routes: a list of
         (landscape_index, float64[n_r, 2]); starts and metrics as from_routes_with.  The landscapes become the engine's landscape set,
         every route is bounds-checked against and sensed on ITS landscape and trained into its own bank, all routes in one call.
         Member i gets what from_routes gives it, and the landscape of its route: `landscape` (so its bounds, and the host sensor
-        model, are that landscape's) and `landscape_index`."""
+        model, are that landscape's) and `landscape_index`.
+        sensors: None (every landscape under the agent's own sensor, the engine's one), or a list as long as `landscapes`: entry l is
+        None (the agent's own configuration) or a dict with any of sensor_pixel_dimensions, n_sensor_levels and mask_middle_n, the
+        sensor landscape l is sensed with; sensor_dimensions is refused (w × h is the engine's one).  Two sensors on one landscape:
+        enter the landscape twice.  The members of a route on landscape l carry that entry's configuration and `sensor_index`, so
+        their bounds are their own footprint's and their get_sensor_mat senses under their own entry."""
         lands = [np.asarray(l) for l in landscapes]
         if not lands or any(l.dtype != np.uint8 or l.ndim != 3 or l.shape[2] != 3 for l in lands):
             raise ValueError("landscapes must be one or more arrays uint8[rows, cols, 3]")
@@ -622,7 +687,8 @@ class _RouteEnsemble(_OneValueEnsemble):
             if isinstance(l, bool) or not isinstance(l, (int, np.integer)) or not 0 <= l < len(lands):
                 raise ValueError("routes[%d]: landscape_index %r outside [0, %d)" % (k, l, len(lands)))
         land_of_route = [int(l) for l, _ in routes]
-        return cls._from_routes(agent, [pts for _, pts in routes], starts, metrics, lands, land_of_route)
+        entries = None if sensors is None else cls._sensor_entries(agent, len(lands), sensors)
+        return cls._from_routes(agent, [pts for _, pts in routes], starts, metrics, lands, land_of_route, entries)
 
     def _device_step(self, idx, xs, ys, angs):
         if self._lands is not None:
@@ -756,11 +822,11 @@ class SadsRouteEnsemble(_RouteEnsemble):
         return ens
 
     @classmethod
-    def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host", chem_weights=None):
+    def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host", chem_weights=None, sensors=None):
         """_RouteEnsemble.from_landscapes, and chem_weights as from_routes_with takes them."""
         starts = list(starts)
         w = cls._weights_arg(chem_weights, starts)
-        ens = super(SadsRouteEnsemble, cls).from_landscapes(agent, landscapes, routes, starts, metrics=metrics)
+        ens = super(SadsRouteEnsemble, cls).from_landscapes(agent, landscapes, routes, starts, metrics=metrics, sensors=sensors)
         if w is not None:
             ens._set_weights(w)
         return ens

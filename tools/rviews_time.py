@@ -2,7 +2,7 @@
 """Times a step of the route view store (dv_rviews_sense_step, navsim_amd.SadsRouteEnsemble) at a slice of the reference's grid and
 writes profiles/rviews_time.json.
 
-    python tools/rviews_time.py [--sides 32,64] [--calls 30] [--reps 5] [--out profiles/rviews_time.json]
+    python tools/rviews_time.py [--sides 32,64] [--calls 30] [--reps 5] [--blocks routes[,sensors]] [--out profiles/rviews_time.json]
 
 Shape: 4 routes x 8 starts x 10 headings = 32 trials of 320 columns, views of side x side.  The routes have the grid's length:
 synth.sin_training_path with arclen = step_size / n_test_angles (scripts/run_experiment.py:207) on a 900 x 900 landscape, one curve
@@ -16,7 +16,12 @@ a route.  Per side, medians (and the spread) of --reps alternating windows of --
   four_engines_over_routed_wall   the ratio of the two wall-clock medians, whichever way it falls
 
 The routed call's rows are checked against the four engines' rows before anything is timed (same best headings, scores within 1e-12
-relative: the engines score in their default mode).  A window without a GPU fails; nothing here falls back."""
+relative: the engines score in their default mode).  A window without a GPU fails; nothing here falls back.
+
+Sensors block (--blocks sensors): dv_rviews_sense_step with a landscape per member on a set of 4 landscapes, without a sensor table,
+with a table of four entries equal to the engine's sensor and with a table of four different entries, in alternating windows of one
+process (tools/sensors_block.py, which states the shape and the figures); its rows are the file's "sensors".  A block that is not
+measured keeps its rows."""
 import argparse
 import json
 import os
@@ -133,16 +138,31 @@ def main():
     ap.add_argument("--calls", type=int, default=30)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rviews_time.json"))
+    ap.add_argument("--blocks", default="routes", help="which blocks to measure: routes (the routed step against four engines), sensors")
+    ap.add_argument("--limit", type=int, default=240, help="seconds allowed to the sensors block's GPU child")
     args = ap.parse_args()
-    rows = [measure(int(s), args.calls, args.reps) for s in args.sides.split(",")]
+    blocks = args.blocks.split(",")
+    kept = {}
+    if os.path.exists(args.out):                                  # a block that is not measured keeps its rows
+        with open(args.out) as f:
+            kept = json.load(f)
+    sensors = kept.get("sensors", [])
+    if "sensors" in blocks:                                       # (a child of its own, before this process opens the GPU)
+        import sensors_block
+        rc, row = sensors_block.run_child(args.limit, args.calls, args.reps, "rviews")
+        if rc != 0:
+            return rc
+        sensors = [row]
+    rows = [measure(int(s), args.calls, args.reps) for s in args.sides.split(",")] if "routes" in blocks else kept.get("sizes", [])
     import torch                                                  # (after the windows: only to ask the device its name)
     doc = dict(tool="tools/rviews_time.py", device=torch.cuda.get_device_name(0), step_form="step_forward(fake=True)", note="medians of alternating windows in one process; wall-clock figures "
-               "include the host's share of a step", sizes=rows)
+               "include the host's share of a step", sizes=rows, sensors=sensors)
     with open(args.out, "w") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")
     print(json.dumps(doc))
+    return 0
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

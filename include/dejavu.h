@@ -915,13 +915,18 @@ int dv_patches_on_level(dv_ctx *ctx);
  * shape 6), DV_FORM_FP4 (its fp4 coefficients: the prep's patches were on-level), DV_FORM_FUSED_FINISH (the kernel
  * finished its scores itself; the step ended in k_fold), DV_FORM_CODES (the fp4 form's body read the value rows as 3-bit level
  * codes, the code tiles of dv_lib_info.code_tile_bytes), DV_FORM_CONSUMERS8 (... in the registers of all eight waves of a workgroup,
- * items of 16 view groups: DEJAVU_LREG8).  Waits for the stream when the fp4 word has to be read.
+ * items of 16 view groups: DEJAVU_LREG8).  Bits DV_FORM_BODY_SHIFT .. of a matrix-core pass name the kernel body the host launched,
+ * 1 + its index in DV_FORM_BODY_NAMES (0: none); with the fp4 flag clear the launch took that body's int8 form.
+ * Waits for the stream when the fp4 word has to be read.
  * Diagnostic for benchmarks and tests; negative on error. */
 #define DV_FORM_MATRIX_CORES 1
 #define DV_FORM_FP4 2
 #define DV_FORM_FUSED_FINISH 4
 #define DV_FORM_CODES 8
 #define DV_FORM_CONSUMERS8 16
+#define DV_FORM_BODY_SHIFT 8
+#define DV_FORM_BODY_BITS 5
+#define DV_FORM_BODY_NAMES "Ring Ring2 RingA RingB Lc LcShort LcCode LcReg LcRegCode LcRegCode8 Lc2Tiles Lc2TilesCode Lc22"
 int dv_scoring_form(dv_ctx *ctx);
 
 const char *dv_version(void);

@@ -174,7 +174,7 @@ struct dv_ctx {
     // fp4 form of the matrix-core kernel (sad_ring_fp4): possible when every plane of a segment has one gap width
     bool fp4_ok = false;                      // this library's planes qualify (build_bit_planes)
     int fp4_env = 1;                          // DEJAVU_FP4=0: never
-    uint4* d_coef4 = nullptr;                 // [pass][K-step][4][64] E2M1 sign images (k_patch_prep)
+    uint4* d_coef4 = nullptr;                 // [pass][K-step][4][64] E2M1 images: sign x the bit position's magnitude (k_patch_prep)
     uint4* d_ctiles = nullptr;                // [Fpad/32][GSC][64] code tiles (k_bitpack_code), when they were built
     size_t ctile_bytes = 0;
     // Five-level value planes as 3-bit codes (k_bitpack_code: a third copy of the library, 5 bits per pixel).  Which body reads them
@@ -187,6 +187,7 @@ struct dv_ctx {
     bool code_all = false;                    // DEJAVU_VCODE=1 and the tiles exist
     bool last_codes = false;                  // the last matrix-core pass was launched with a body that reads code rows
     bool last_consumers8 = false;             // ... into the registers of all eight waves (LcRegCode8)
+    int last_body = -1;                       // ... and which body it was (enum Body; dv_scoring_form reports it)
     int last_form = 0;                        // DV_FORM_* of the last integer scoring pass (fp4 bit: the fp4 image existed)
     int fuse_env = 1;                         // DEJAVU_FUSE=0: one-chunk matrix-core passes leave their sums to k_finish instead of finishing them
     int lc_env = 1;                           // DEJAVU_LC: 0 every wave loads and multiplies, 1 loader / consumer waves (stages of 4, ring of 3), 2 (stages of 2, ring of 5)
@@ -2383,7 +2384,9 @@ static FuseArgs fuse_args(const dv_ctx* c) {
 //   Lc22: k_sad_lc22, two view groups x two heading tiles per consumer (fused finishing only).
 // Every fp4 body has the int8 ring body <SK8, TILES, RD8> beside it for off-level patches, and the loader / consumer bodies the fp4
 // ring body <SK4, TILES, RD4> for chunked passes.
+// (the order is the C ABI's: dv_scoring_form reports a body as its index + 1, include/dejavu.h)
 enum class Body { Ring, Ring2, RingA, RingB, Lc, LcShort, LcCode, LcReg, LcRegCode, LcRegCode8, Lc2Tiles, Lc2TilesCode, Lc22, Count };
+static_assert((int)Body::Count < (1 << DV_FORM_BODY_BITS), "dv_scoring_form's body field");
 
 // <int8 stage, ring | fp4 stage, ring (ring body) | view groups per wave | fp4 stage, ring (loader / consumer body; stage 0: none),
 // code rows, heading tiles per view group>: the template arguments of k_sad_mfma_dual (k_sad_lc22: SKL, RDL; it has no fp4 ring
@@ -2473,6 +2476,7 @@ static void launch_body(dv_ctx* c, int nchunk, int has_hs) {
     const uint4* ftiles = s.LCODE ? c->d_ctiles : c->d_btiles;
     c->last_codes = s.LCODE && nchunk == 1;
     c->last_consumers8 = B == Body::LcRegCode8 && nchunk == 1;
+    c->last_body = (int)B;
     for (int a_off = 0; a_off < c->APAD; a_off += 32 * s.HT) {
         const uint4* coef = c->d_coef + (size_t)(a_off / 32) * nkt * 512;
         const uint4* coef4 = c->fp4_ok ? c->d_coef4 + (size_t)(a_off / 32) * nkt * 256 : nullptr;
@@ -2659,7 +2663,8 @@ static int launch_int_scoring(dv_ctx* c, hipEvent_t after_tiles, int* n_partial,
         } else
         launch_mfma(c, has_hs_sum);
         c->last_form = DV_FORM_MATRIX_CORES | (c->fp4_ok ? DV_FORM_FP4 : 0) | (c->epilogue_fused ? DV_FORM_FUSED_FINISH : 0) |
-                       (c->fp4_ok && c->last_codes ? DV_FORM_CODES : 0) | (c->fp4_ok && c->last_consumers8 ? DV_FORM_CONSUMERS8 : 0);
+                       (c->fp4_ok && c->last_codes ? DV_FORM_CODES : 0) | (c->fp4_ok && c->last_consumers8 ? DV_FORM_CONSUMERS8 : 0) |
+                       ((c->last_body + 1) << DV_FORM_BODY_SHIFT);
         c->int_hsconst = c->mixed ? c->d_acc[c->acc_parity].hs : c->d_acc[c->acc_parity].bhs;
         c->int_vconst = c->d_acc[c->acc_parity].bv;
     } else if (g.generic) {

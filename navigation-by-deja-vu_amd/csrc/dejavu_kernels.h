@@ -2889,7 +2889,10 @@ k_patch_prep(const unsigned char* __restrict__ land, const PoseSet poses, int A,
             const int al_ = (int)s_pl[tb & 0xffu][tid] - (int)((tb >> 8) & 0xffu);
             if (pb.fp4) {
                 const int wf = (int)(tb >> 24);                            // 0: a copy of a split gap's first plane
-                if (real && wf) atomicOr(&s_img4[((kidx * 4 + (beta & 3)) * 2 + half) * 4 + j], (al_ >= wf ? 0xAu : 0x2u) << (4 * (beta >> 2)));
+                // the magnitude undoes the E2M1 value of the library bit where the scoring bodies leave it: positions 0 and 3 (brought
+                // down to bit 0) read 0.5 -> 2.0 here, position 1 reads 1 -> 1.0, position 2 reads 2 -> 0.5: every product is +-1
+                const unsigned mag = (0x4124u >> (4 * (beta & 3))) & 0xfu;
+                if (real && wf) atomicOr(&s_img4[((kidx * 4 + (beta & 3)) * 2 + half) * 4 + j], (al_ >= wf ? 0x8u | mag : mag) << (4 * (beta >> 2)));
             }
             const int wd = (int)((tb >> 16) & 0xffu);
             const int alpha = al_ < 0 ? 0 : (al_ > wd ? wd : al_);
@@ -3588,12 +3591,14 @@ sad_ring_i8(const uint4* __restrict__ btiles, const uint4* __restrict__ coef, in
 // widths agree; a gap wider than 127 was split for the int8 form into planes with the same bits: its first plane
 // stands for the whole gap here and the copies get coefficient 0), the sum over the K-elements on bit b is
 //     sum B (w - 2 alpha) = w_b * sum B * (+-1):
-// the signs are exact in fp4 (E2M1: +-1.0), the library bits too (bit 0/1/2 of a nibble ARE the E2M1 values 0.5/1/2, bit 3
-// comes down by a shift), and v_mfma_f32_32x32x64_f8f6f4 multiplies 64 K-elements in the time the int8 form takes for 32
+// the signs are exact in fp4, the library bits too (bit 0/1/2 of a nibble ARE the E2M1 values 0.5/1/2, bit 3 comes down to
+// bit 0 by a shift), and the coefficient of bit position b carries the inverse magnitude +-{2, 1, 0.5, 2} (E2M1 holds all of
+// them: k_patch_prep), so every product is +-1 with the library bit left where it is -- no shift but position 3's.
+// v_mfma_f32_32x32x64_f8f6f4 multiplies 64 K-elements in the time the int8 form takes for 32
 // (measured: 21.2 vs 18.3 ns per instruction and SIMD, tools/exp/mfma_fp4.hip).  The SAME bit tiles are the B operand:
 // K-element <-> (dword j, bit 4i + b) pairs with nibble i of coefficient image b of that K-step (k_patch_prep), and any
-// pairing works as long as both operands use it.  Sums of +-{0.5, 1, 2} stay exact in the fp32 accumulators (below 2^24
-// in halves); the four accumulators (one per bit position) are multiplied by their widths as integers at the end: the int32 sums are
+// pairing works as long as both operands use it.  Sums of +-1 stay exact in the fp32 accumulators (below 2^24);
+// the four accumulators (one per bit position) are multiplied by their widths as integers at the end: the int32 sums are
 // the int8 form's, bit for bit.  With the coefficient image half the size, the kernel is left to the HBM stream.
 typedef int v8i_t __attribute__((ext_vector_type(8)));
 typedef float v16f_t __attribute__((ext_vector_type(16)));
@@ -3715,7 +3720,7 @@ fp4_segment(const unsigned char* const (&lib)[TILES], const bool (&live)[TILES],
                 for (int t = 0; t < TILES; ++t)
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        totf[t][r] = __mul24(wf[0], (int)(2.f * acc[t][0][r])) + __mul24(wf[1], (int)acc[t][1][r]) + __mul24(wf[2], (int)(0.5f * acc[t][2][r])) +
+                        totf[t][r] = __mul24(wf[0], (int)acc[t][0][r]) + __mul24(wf[1], (int)acc[t][1][r]) + __mul24(wf[2], (int)acc[t][2][r]) +
                                      __mul24(wf[3], (int)acc[t][3][r]);
 #pragma unroll
                 for (int t = 0; t < TILES; ++t)
@@ -3768,9 +3773,10 @@ fp4_segment(const unsigned char* const (&lib)[TILES], const bool (&live)[TILES],
                     const unsigned x[4] = {xl[k & 1][t].x, xl[k & 1][t].y, xl[k & 1][t].z, xl[k & 1][t].w};
 #pragma unroll
                     for (int s = 0; s < 4; ++s) {
-                        // bit s of every nibble as an E2M1 value: 0.5 / 1 / 2 in place, bit 3 shifted down to the 1.0 position
-                        const unsigned m = on ? (s < 3 ? (0x11111111u << s) : 0x22222222u) : 0u;
-                        const int sh = s < 3 ? 0 : 2;
+                        // bit s of every nibble as an E2M1 value: 0.5 / 1 / 2 in place, bit 3 shifted down to the 0.5 position; the
+                        // coefficient row of the position carries the inverse magnitude (k_patch_prep), so every product is +-1
+                        const unsigned m = on ? (s < 3 ? (0x11111111u << s) : 0x11111111u) : 0u;
+                        const int sh = s < 3 ? 0 : 3;
                         mfma(t, s, a[k & 1][s], (x[0] >> sh) & m, (x[1] >> sh) & m, (x[2] >> sh) & m, (x[3] >> sh) & m);
                     }
                 }
@@ -3785,13 +3791,13 @@ fp4_segment(const unsigned char* const (&lib)[TILES], const bool (&live)[TILES],
         __builtin_amdgcn_s_barrier();
         DV_STAMP(2);
     }
-    // bits stood for 0.5 / 1 / 2 / 1: signed counts 2 acc0, acc1, acc2 / 2, acc3 -- integers -- each times the gap width of the
-    // planes on that bit position (widths < 256, |counts| < 2^23)
+    // every product was +-1 (the coefficient magnitudes undo the bits' 0.5 / 1 / 2 / 0.5): the accumulators are the signed counts --
+    // integers -- each times the gap width of the planes on that bit position (widths < 256, |counts| < 2^23)
 #pragma unroll
     for (int t = 0; t < TILES; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            tot[t][r] = __mul24(w[0], (int)(2.f * acc[t][0][r])) + __mul24(w[1], (int)acc[t][1][r]) + __mul24(w[2], (int)(0.5f * acc[t][2][r])) +
+            tot[t][r] = __mul24(w[0], (int)acc[t][0][r]) + __mul24(w[1], (int)acc[t][1][r]) + __mul24(w[2], (int)acc[t][2][r]) +
                         __mul24(w[3], (int)acc[t][3][r]);
 }
 
@@ -4143,15 +4149,14 @@ sad_lc_fp4(const uint4* __restrict__ ftiles, const uint4* __restrict__ coef4, in
                     });
                 }
             };
-            // bits stood for 0.5 / 1 / 2 / 1 (code rows: 0.5): signed counts 2 acc0, acc1, acc2 / 2, acc3 (code rows: 2 acc3) -- integers
-            auto flush = [&](int (&dst)[2][16], const int (&wd)[4], bool code) {
-                const float f3 = code ? 2.f : 1.f;
+            // bits stood for 0.5 / 1 / 2 / 0.5 against coefficients of 2 / 1 / 0.5 / 2 (k_patch_prep): the accumulators are signed counts
+            auto flush = [&](int (&dst)[2][16], const int (&wd)[4]) {
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        dst[u][r] = __mul24(wd[0], (int)(2.f * acc[u][0][r])) + __mul24(wd[1], (int)acc[u][1][r]) + __mul24(wd[2], (int)(0.5f * acc[u][2][r])) +
-                                    __mul24(wd[3], (int)(f3 * acc[u][3][r]));
+                        dst[u][r] = __mul24(wd[0], (int)acc[u][0][r]) + __mul24(wd[1], (int)acc[u][1][r]) + __mul24(wd[2], (int)acc[u][2][r]) +
+                                    __mul24(wd[3], (int)acc[u][3][r]);
             };
             __builtin_amdgcn_s_barrier();                               // stage (j, 0) is in LDS
             if (j == 0) DV_STAMP(1);
@@ -4204,17 +4209,19 @@ sad_lc_fp4(const uint4* __restrict__ ftiles, const uint4* __restrict__ coef4, in
                             }
 #endif
                             if constexpr (!code_stage) {
-                                // bit s of every nibble as an E2M1 value: 0.5 / 1 / 2 in place, bit 3 shifted down to the 1.0 position
-                                const unsigned m = on ? (s < 3 ? (0x11111111u << s) : 0x22222222u) : 0u;
-                                const int sh = s < 3 ? 0 : 2;
+                                // bit s of every nibble as an E2M1 value: 0.5 / 1 / 2 in place, bit 3 shifted down to the 0.5 position (the
+                                // coefficient row of the position carries the inverse magnitude: k_patch_prep)
+                                const unsigned m = on ? (s < 3 ? (0x11111111u << s) : 0x11111111u) : 0u;
+                                const int sh = s < 3 ? 0 : 3;
 #pragma unroll
                                 for (int d = 0; d < 4; ++d) o[d] = (x[d] >> sh) & m;
                             } else {
-                                // E2M1 operands of the four thermometer planes: t1, t4 as 0.5 (bit 0), t2 as 1 (bit 1), t3 as 2 (bit 2)
+                                // E2M1 operands of the four thermometer planes, where the coefficient rows expect them: t1 = b0 | b1 and
+                                // t4 = b0 & b1 (== b0 & b2 on the five stored codes) as 0.5 (bit 0), t2 = b1 as 1 (bit 1), t3 = b2 as 2 (bit 2)
                                 const unsigned m = on ? 0x11111111u : 0u;
 #pragma unroll
                                 for (int d = 0; d < 4; ++d)
-                                    o[d] = s == 0 ? (x[d] | (x[d] >> 1)) & m : s == 1 ? x[d] & (m << 1) : s == 2 ? x[d] & (m << 2) : x[d] & (x[d] >> 2) & m;
+                                    o[d] = s == 0 ? (x[d] | (x[d] >> 1)) & m : s == 1 ? x[d] & (m << 1) : s == 2 ? x[d] & (m << 2) : x[d] & (x[d] >> 1) & m;
                             }
                         };
                         auto load_x = [&](int t, unsigned (&x)[4]) {
@@ -4261,7 +4268,7 @@ sad_lc_fp4(const uint4* __restrict__ ftiles, const uint4* __restrict__ coef4, in
             const int hs_end = (has_hs_sum && !(c.hasv && b.NK[1] > 0)) ? nst : nst0; // (no V K-steps: all of them)
             run_stages(0, hs_end, IntC<0>{});
             if (hs_end > 0 && hs_end < nst) {
-                flush(tot_hs, b.wacc[0], false);
+                flush(tot_hs, b.wacc[0]);
                 if constexpr (!FUSE) store_sums(tot_hs, 0);
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
@@ -4272,8 +4279,8 @@ sad_lc_fp4(const uint4* __restrict__ ftiles, const uint4* __restrict__ coef4, in
             }
             if constexpr (CODE) run_stages(hs_end, nst, IntC<1>{});
             else run_stages(hs_end, nst, IntC<0>{});
-            if (hs_end < nst) flush(tot_v, b.wacc[1], codev);           // what the accumulators hold at the end: the V segment's sums,
-            else flush(tot_hs, b.wacc[0], false);                       // unless there are no V K-steps
+            if (hs_end < nst) flush(tot_v, b.wacc[1]);                  // what the accumulators hold at the end: the V segment's sums,
+            else flush(tot_hs, b.wacc[0]);                              // unless there are no V K-steps
             if constexpr (!FUSE) {
                 // (a sum without K-steps is stored as the zeros it was initialised to: the mixed layout's saturation rows, a constant value plane)
                 if (has_hs_sum && !(hs_end > 0 && hs_end < nst)) store_sums(tot_hs, 0);
@@ -4320,7 +4327,7 @@ sad_lc_fp4(const uint4* __restrict__ ftiles, const uint4* __restrict__ coef4, in
 // not drain while the consumers finish an item.  The loaders move the coefficient rows only (4 per K-step, shared by all four
 // consumers) with the ring protocol of sad_lc_fp4: one barrier per stage.
 // The register ring (64 registers) fits beside the accumulators because the bit positions of one width share one (as in
-// sad_lc22_fp4): every position's library bit is moved to the 1.0 bit of its nibble, position 0 accumulates in one block,
+// sad_lc22_fp4): every position's product is +-1 (the coefficient rows' magnitudes), position 0 accumulates in one block,
 // positions 1, 2, 3 -- whose widths must agree per segment (the host checks, lreg_fits) -- in the other.  The counts are
 // integers (|count| < 2^24), so the sums are bit for bit sad_lc_fp4's.  HT = 1; the saturation / value boundary NK[0] must be a
 // whole number of stages (the host checks).
@@ -4561,8 +4568,9 @@ sad_lc_fp4_lreg(const uint4* __restrict__ btiles, const uint4* __restrict__ coef
                             }
 #pragma unroll
                             for (int s = 0; s < 4; ++s) lds_tie(a[kk & 1][s]);
-                            // every position's bit to the 1.0 bit of its nibble (E2M1 0010): positions 0 / 2 / 3 by a shift
-                            const unsigned m = kb + kk < NKT ? 0x22222222u : 0u;
+                            // positions 0 / 1 / 2 stay where they read 0.5 / 1 / 2, position 3 comes down to the 0.5 bit: the coefficient
+                            // rows carry 2 / 1 / 0.5 / 2 (k_patch_prep), every product is +-1 and positions 1, 2, 3 can share an accumulator
+                            const unsigned m = kb + kk < NKT ? 0x11111111u : 0u;
                             unsigned bo[TL][4][4];
                             // (pinned to this K-step: the compiler hoisted masks of K-step 6 into K-step 1, and its vmcnt wait for
                             // them drained the ring there -- every use of xr[kk] now waits behind this volatile no-op, in order)
@@ -4573,10 +4581,10 @@ sad_lc_fp4_lreg(const uint4* __restrict__ btiles, const uint4* __restrict__ coef
                                 const unsigned x[4] = {xr[kk][t].x, xr[kk][t].y, xr[kk][t].z, xr[kk][t].w};
 #pragma unroll
                                 for (int d = 0; d < 4; ++d) {
-                                    bo[t][0][d] = (x[d] << 1) & m;
-                                    bo[t][1][d] = x[d] & m;
-                                    bo[t][2][d] = (x[d] >> 1) & m;
-                                    bo[t][3][d] = (x[d] >> 2) & m;
+                                    bo[t][0][d] = x[d] & m;
+                                    bo[t][1][d] = x[d] & (m << 1);
+                                    bo[t][2][d] = x[d] & (m << 2);
+                                    bo[t][3][d] = (x[d] >> 3) & m;
                                 }
                             }
                             load_row(kk);                               // K-step kk of the cursor's stage into the registers just read
@@ -4622,7 +4630,7 @@ sad_lc_fp4_lreg(const uint4* __restrict__ btiles, const uint4* __restrict__ coef
                             }
 #pragma unroll
                             for (int s = 0; s < 4; ++s) lds_tie(a[kk & 1][s]);
-                            constexpr unsigned m = 0x22222222u;         // (whole stages: no K-step without K-elements)
+                            constexpr unsigned m = 0x11111111u;         // (whole stages: no K-step without K-elements)
                             constexpr int h3 = 3 * (kk / 4), q = kk % 4;
                             constexpr int newest = CK ? h3 + (q < 2 ? q : 2) : kk;
                             constexpr int sent = CK ? kk - (kk + 3) / 4 : (LK == 0 || kk < 6 ? kk : 6);
@@ -4636,10 +4644,10 @@ sad_lc_fp4_lreg(const uint4* __restrict__ btiles, const uint4* __restrict__ coef
                                     const unsigned x[4] = {xr[kk][t].x, xr[kk][t].y, xr[kk][t].z, xr[kk][t].w};
 #pragma unroll
                                     for (int d = 0; d < 4; ++d) {
-                                        bo[t][0][d] = (x[d] << 1) & m;
-                                        bo[t][1][d] = x[d] & m;
-                                        bo[t][2][d] = (x[d] >> 1) & m;
-                                        bo[t][3][d] = (x[d] >> 2) & m;
+                                        bo[t][0][d] = x[d] & m;
+                                        bo[t][1][d] = x[d] & (m << 1);
+                                        bo[t][2][d] = x[d] & (m << 2);
+                                        bo[t][3][d] = (x[d] >> 3) & m;
                                     }
                                 }
                                 if constexpr (LK == 0 || kk < 6) load_piece(kc);
@@ -4660,13 +4668,15 @@ sad_lc_fp4_lreg(const uint4* __restrict__ btiles, const uint4* __restrict__ coef
                                     else { x[0] = xr[h3 + 2][t].y; x[1] = xr[h3 + 2][t].z; x[2] = xr[h3 + 2][t].w; }
                                     // the fourth dword's pixels: bit 3 of the three code dwords' nibbles
                                     x[3] = ((x[0] >> 3) & 0x11111111u) | ((x[1] >> 2) & 0x22222222u) | ((x[2] >> 1) & 0x44444444u);
-                                    // code b2 b1 b0 -> thermometer bit of every position on the 1.0 bit: t1 = b0 | b1, t2 = b1, t3 = b2, t4 = b0 & b2
+                                    // code b2 b1 b0 -> the thermometer bits where the coefficient rows expect them (k_patch_prep): t1 = b0 | b1 and
+                                    // t4 = b0 & b1 (== b0 & b2 on the five stored codes) on the 0.5 bit, t2 = b1 and t3 = b2 in place (1 and 2)
 #pragma unroll
                                     for (int d = 0; d < 4; ++d) {
-                                        bo[t][0][d] = ((x[d] << 1) | x[d]) & m;
-                                        bo[t][1][d] = x[d] & m;
-                                        bo[t][2][d] = (x[d] >> 1) & m;
-                                        bo[t][3][d] = (x[d] << 1) & (x[d] >> 1) & m;
+                                        const unsigned xs = x[d] >> 1;
+                                        bo[t][0][d] = (x[d] | xs) & m;
+                                        bo[t][1][d] = x[d] & (m << 1);
+                                        bo[t][2][d] = x[d] & (m << 2);
+                                        bo[t][3][d] = (x[d] & xs) & m;
                                     }
                                 }
                                 if constexpr (q > 0) load_piece(IntC<kk - 1 - kk / 4>{});
@@ -4956,7 +4966,7 @@ sad_lc_fp4_lreg8(const uint4* __restrict__ ctiles, const uint4* __restrict__ coe
                         }
 #pragma unroll
                         for (int s = 0; s < 4; ++s) lds_tie(a[kk & 1][s]);
-                        constexpr unsigned m = 0x22222222u;             // (whole stages: no K-step without K-elements)
+                        constexpr unsigned m = 0x11111111u;             // (whole stages: no K-step without K-elements)
                         constexpr int h3 = 3 * (kk / 4), q = kk % 4;
                         constexpr int newest = CK ? h3 + (q < 2 ? q : 2) : kk;
                         constexpr int sent = CK ? kk - (kk + 3) / 4 : (LK == 0 || kk < 6 ? kk : 6);
@@ -4971,10 +4981,10 @@ sad_lc_fp4_lreg8(const uint4* __restrict__ ctiles, const uint4* __restrict__ coe
                                 const unsigned x[4] = {xr[kk][t].x, xr[kk][t].y, xr[kk][t].z, xr[kk][t].w};
 #pragma unroll
                                 for (int d = 0; d < 4; ++d) {
-                                    bo[t][0][d] = (x[d] << 1) & m;
-                                    bo[t][1][d] = x[d] & m;
-                                    bo[t][2][d] = (x[d] >> 1) & m;
-                                    bo[t][3][d] = (x[d] >> 2) & m;
+                                    bo[t][0][d] = x[d] & m;
+                                    bo[t][1][d] = x[d] & (m << 1);
+                                    bo[t][2][d] = x[d] & (m << 2);
+                                    bo[t][3][d] = (x[d] >> 3) & m;
                                 }
                             }
                             if constexpr (LK == 0 || kk < 6) load_piece(kc);
@@ -4995,13 +5005,15 @@ sad_lc_fp4_lreg8(const uint4* __restrict__ ctiles, const uint4* __restrict__ coe
                                 else { x[0] = xr[h3 + 2][t].y; x[1] = xr[h3 + 2][t].z; x[2] = xr[h3 + 2][t].w; }
                                 // the fourth dword's pixels: bit 3 of the three code dwords' nibbles
                                 x[3] = ((x[0] >> 3) & 0x11111111u) | ((x[1] >> 2) & 0x22222222u) | ((x[2] >> 1) & 0x44444444u);
-                                // code b2 b1 b0 -> thermometer bit of every position on the 1.0 bit: t1 = b0 | b1, t2 = b1, t3 = b2, t4 = b0 & b2
+                                // code b2 b1 b0 -> the thermometer bits where the coefficient rows expect them (k_patch_prep): t1 = b0 | b1 and
+                                // t4 = b0 & b1 (== b0 & b2 on the five stored codes) on the 0.5 bit, t2 = b1 and t3 = b2 in place (1 and 2)
 #pragma unroll
                                 for (int d = 0; d < 4; ++d) {
-                                    bo[t][0][d] = ((x[d] << 1) | x[d]) & m;
-                                    bo[t][1][d] = x[d] & m;
-                                    bo[t][2][d] = (x[d] >> 1) & m;
-                                    bo[t][3][d] = (x[d] << 1) & (x[d] >> 1) & m;
+                                    const unsigned xs = x[d] >> 1;
+                                    bo[t][0][d] = (x[d] | xs) & m;
+                                    bo[t][1][d] = x[d] & (m << 1);
+                                    bo[t][2][d] = x[d] & (m << 2);
+                                    bo[t][3][d] = (x[d] & xs) & m;
                                 }
                             }
                             if constexpr (q > 0) load_piece(IntC<kk - 1 - kk / 4>{});
@@ -5071,8 +5083,8 @@ sad_lc_fp4_lreg8(const uint4* __restrict__ ctiles, const uint4* __restrict__ coe
 // K-step against 256 of MFMA time, bound by LDS bandwidth (neither the matrix pipe nor HBM: 3.5 TB/s).  Here a consumer takes TWO
 // view groups and both tiles: the eight coefficient rows serve sixteen MFMAs, (8 + 2) KB of reads + 16 KB of DMA per 64 MFMAs =
 // 0.875 KB per MFMA.  Sixteen accumulators of 16 registers would not fit a wave (2 groups x 2 tiles x 4 bit positions), so the
-// bit positions of one gap width SHARE an accumulator: every position's library bit is moved to the 1.0 bit of its nibble (a shift
-// and a mask; sad_lc_fp4 leaves bits 0 / 1 / 2 where they stand for 0.5 / 1 / 2 and weights the four accumulators at the end), and
+// bit positions of one gap width SHARE an accumulator: the coefficient row of a bit position carries the inverse of the E2M1 value
+// its library bit stands for (2 / 1 / 0.5 / 2 against bits 0 / 1 / 2 in place and bit 3 brought down to bit 0: k_patch_prep), and
 // the sums of +-1 of positions 1, 2, 3 -- whose widths must agree (the host checks: 63, 64, 64, 64 of the five sensor levels do) --
 // accumulate in one register block, position 0 in the other: 8 blocks = 128 registers.  The saturation segment's counts (one width:
 // the host checks) wait for the value segment in LDS as int16 (|count| <= K-elements of the segment <= 32767: the host checks),
@@ -5276,8 +5288,9 @@ sad_lc22_fp4(const uint4* __restrict__ ftiles, const uint4* __restrict__ coef4, 
                             if constexpr (h == 0) {
 #pragma unroll
                                 for (int t = 0; t < TL; ++t) lds_tie(xl[k & 1][t]);
-                                // every position's bit to the 1.0 bit of its nibble (E2M1 0010): positions 0 / 2 / 3 by a shift
-                                const unsigned m = kb + k < NKT ? 0x22222222u : 0u;
+                                // positions 0 / 1 / 2 stay where they read 0.5 / 1 / 2, position 3 comes down to the 0.5 bit (the
+                                // coefficient rows carry 2 / 1 / 0.5 / 2: sad_lc_fp4_lreg)
+                                const unsigned m = kb + k < NKT ? 0x11111111u : 0u;
 #pragma unroll
                                 for (int t = 0; t < TL; ++t) {
                                     const unsigned x[4] = {xl[k & 1][t].x, xl[k & 1][t].y, xl[k & 1][t].z, xl[k & 1][t].w};
@@ -5286,10 +5299,10 @@ sad_lc22_fp4(const uint4* __restrict__ ftiles, const uint4* __restrict__ coef4, 
 #ifdef DEJAVU_EXP22
                                         if (DEJAVU_EXP22 & 8) { bo[t][0][d] = bo[t][1][d] = bo[t][2][d] = bo[t][3][d] = x[d]; continue; }   // bit 3: no masks
 #endif
-                                        bo[t][0][d] = (x[d] << 1) & m;
-                                        bo[t][1][d] = x[d] & m;
-                                        bo[t][2][d] = (x[d] >> 1) & m;
-                                        bo[t][3][d] = (x[d] >> 2) & m;
+                                        bo[t][0][d] = x[d] & m;
+                                        bo[t][1][d] = x[d] & (m << 1);
+                                        bo[t][2][d] = x[d] & (m << 2);
+                                        bo[t][3][d] = (x[d] >> 3) & m;
                                     }
                                 }
                             }

@@ -20,6 +20,9 @@ DV_RES_RESOLVED = 1
 DV_RES_EXACT_ALL = 2
 DV_RES_OVERFLOW = 4
 DV_RES_SENSE_ERROR = 16
+DV_FORM_BODY_SHIFT = 8                   # dv_scoring_form: 1 + index of the launched body's name, DV_FORM_BODY_BITS wide
+DV_FORM_BODY_BITS = 5
+DV_FORM_BODY_NAMES = "Ring Ring2 RingA RingB Lc LcShort LcCode LcReg LcRegCode LcRegCode8 Lc2Tiles Lc2TilesCode Lc22".split()
 DV_RVIEWS_EXACT = 1
 DV_DIFFUSE_AUTO = 0
 DV_DIFFUSE_PLAIN = 1

@@ -764,11 +764,14 @@ class FamiliarityEngine(object):
 
     def scoring_form(self):
         """Form of the last integer scoring pass (dv_scoring_form): matrix cores / fp4 coefficients / fused finishing / value rows
-        read as 3-bit codes / those in the registers of all eight waves of a workgroup."""
+        read as 3-bit codes / those in the registers of all eight waves of a workgroup / the name of the kernel body the host
+        launched for a matrix-core pass (`body`, None otherwise: include/dejavu.h, DV_FORM_BODY_NAMES)."""
         rc = self._lib.dv_scoring_form(self._ctx)
         if rc < 0:
             self._check(rc, "dv_scoring_form")
-        return dict(matrix_cores=bool(rc & 1), fp4=bool(rc & 2), fused_finish=bool(rc & 4), codes=bool(rc & 8), consumers8=bool(rc & 16))
+        body = (rc >> N.DV_FORM_BODY_SHIFT) & ((1 << N.DV_FORM_BODY_BITS) - 1)
+        return dict(matrix_cores=bool(rc & 1), fp4=bool(rc & 2), fused_finish=bool(rc & 4), codes=bool(rc & 8), consumers8=bool(rc & 16),
+                    body=N.DV_FORM_BODY_NAMES[body - 1] if body else None)
 
     def path_reset(self):
         self._check(self._lib.dv_path_reset(self._ctx), "dv_path_reset")

@@ -92,6 +92,16 @@ struct PackedResults {
     std::vector<unsigned char> host;          // where the copy lands
 };
 
+// A call's table mirrored on the device: the host keeps what the device's table holds, so that an unchanged one is not sent again
+// (table_upload, beside grow_buffer).
+struct MirroredTable {
+    unsigned char* dev = nullptr;
+    size_t cap = 0;                           // bytes
+    std::vector<unsigned char> host;          // what dev holds (empty: nothing known)
+    template <class T> const T* device() const { return reinterpret_cast<const T*>(dev); }
+    template <class T> const T* record() const { return reinterpret_cast<const T*>(host.data()); }
+};
+
 struct dv_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -335,10 +345,9 @@ struct dv_ctx {
     double* im_kh[2] = {nullptr, nullptr};    // [im_banks][M] each: banked training's h
     double* im_ku = nullptr;                  // [im_banks][N]
     double* im_kupart = nullptr;              // [im_banks][row blocks][N]
-    int* im_ktab = nullptr;                   // a banked call's table on the device (training: chains; a step: column blocks and members)
-    size_t im_ktab_cap = 0;                   // bytes
-    std::vector<int> im_ktab_host;            // what im_ktab holds
-    bool im_ktab_step = false;                // im_ktab holds a step's table: an equal one is not sent again
+    // a banked call's table of ints (training: chains; a step: column blocks and members).  Both share the buffer: no kernel writes
+    // it, so a table of equal content is the same table whichever call built it
+    MirroredTable im_ktab;
     std::vector<double> im_kpose;             // a banked step's poses in bank order: x, y, angles
     std::vector<uint8_t> im_kplanes;          // ... or its uploaded planes
     // mushroom-body familiarity model (dejavu_mushroom.inl): fixed fan-in, one byte of weight per Kenyon cell; independent of the above
@@ -357,17 +366,13 @@ struct dv_ctx {
     int mb_K = 0, mb_N = 0, mb_c = 0, mb_active = 0, mb_hh = 0, mb_ww = 0, mb_channel = 2;
     int mb_banks = 1;                         // memories that share the connectivity (dv_mbank_set; 1 after dv_mb_begin)
     std::vector<int64_t> mb_views = std::vector<int64_t>(1, 0);   // [mb_banks]: views trained on since dv_mb_begin / dv_mbank_set
-    int* mb_bank_of = nullptr;                // a banked call's table on the device: the bank of every view, or of every member
-    size_t mb_bank_of_cap = 0;                // bytes
-    std::vector<int32_t> mb_bank_host;        // what mb_bank_of holds (empty: nothing known), so that an unchanged table is not sent again
+    MirroredTable mb_bank_of;                 // a banked call's table of ints: the bank of every view, or of every member
     // landscape set (dejavu_lands.inl: dv_lands_*): independent of d_land above; the sensor configuration is shared
     unsigned char* ld_lands = nullptr;        // the landscapes back to back, no padding (nullptr: no set)
     LandEntry* ld_tab = nullptr;              // [n_lands]: byte offset, rows, cols
     long long ld_bytes = 0;
     std::vector<int32_t> ld_rows, ld_cols;    // [n_lands]
-    int* ld_of = nullptr;                     // a call's table on the device: the landscape of every view, or of every member
-    size_t ld_of_cap = 0;                     // bytes
-    std::vector<int32_t> ld_of_host;          // what ld_of holds (empty: nothing known)
+    MirroredTable ld_of;                      // a call's table of ints: the landscape of every view, or of every member
     int* ld_err = nullptr;                    // [n]: k_sense_lands' word per pose (dv_lands_sense, training from poses)
     size_t ld_err_cap = 0;                    // bytes
     std::vector<int> ld_err_host;
@@ -387,13 +392,12 @@ struct dv_ctx {
     double* rv_fast = nullptr;                // [slab columns][lstride]: a slab's scores
     int* rv_marked = nullptr;                 // [C]: columns left to the exact-all pass
     unsigned char* rv_out = nullptr;          // a step's results: fam[C], view[C], best[N], flags[N]
-    unsigned char* rv_tab = nullptr;          // a call's tables (RvPlan)
+    MirroredTable rv_tab;                     // a call's tables (RvPlan)
     int* rv_err = nullptr;                    // [C]: the sensing kernels' word per pose
     double* rv_scene = nullptr;               // dv_rviews_scene's rows
     unsigned* rv_prep = nullptr;              // [C][3][Pw]: a step's patches as byte planes
     size_t rv_prep_cap = 0;                   // bytes
-    size_t rv_fast_cap = 0, rv_marked_cap = 0, rv_out_cap = 0, rv_tab_cap = 0, rv_err_cap = 0, rv_scene_cap = 0;   // bytes
-    std::vector<unsigned char> rv_tab_host;   // what rv_tab holds (empty: nothing known)
+    size_t rv_fast_cap = 0, rv_marked_cap = 0, rv_out_cap = 0, rv_err_cap = 0, rv_scene_cap = 0;   // bytes
     std::vector<unsigned char> rv_out_host;
 
     // measurement
@@ -1530,6 +1534,34 @@ static int grow_buffer(dv_ctx* c, T*& p, size_t& cap, size_t bytes) {
     HIP_TRY(c, hipMalloc((void**)&p, bytes));
     cap = bytes;
     return DV_OK;
+}
+
+// A call's index table, checked entry by entry before anything of the call reaches the device: the first entry outside [0, limit).
+static int index_check(dv_ctx* c, const char* who, const char* what, const int32_t* table, int64_t n, int limit, const char* limit_name) {
+    if (!table) return fail(c, DV_ERR_INVALID, "%s: %s is NULL", who, what);
+    for (int64_t i = 0; i < n; ++i)
+        if (table[i] < 0 || table[i] >= limit)
+            return fail(c, DV_ERR_INVALID, "%s: %s[%lld] = %d outside [0, %s = %d)", who, what, (long long)i, (int)table[i], limit_name, limit);
+    return DV_OK;
+}
+
+// Enqueue `data` for the device's table, unless the table holds the same already (an ensemble's tables change only when a member
+// stops, so most steps upload nothing).  The copy reads the context's own record, never `data`: the record stays until the next
+// table, so a call that fails before it has waited for the stream leaves nothing pending on memory of its caller's.
+static int table_upload(dv_ctx* c, MirroredTable& t, const void* data, size_t bytes) {
+    if (!bytes || (t.host.size() == bytes && !std::memcmp(t.host.data(), data, bytes))) return DV_OK;
+    t.host.clear();
+    int rc = grow_buffer(c, t.dev, t.cap, bytes);
+    if (rc) return rc;
+    t.host.assign((const unsigned char*)data, (const unsigned char*)data + bytes);
+    rc = [&] { HIP_TRY(c, hipMemcpyAsync(t.dev, t.host.data(), bytes, hipMemcpyHostToDevice, c->stream)); return (int)DV_OK; }();
+    if (rc) t.host.clear();                                   // (an upload that failed: nothing is known of the device's table)
+    return rc;
+}
+
+static void table_free(MirroredTable& t) {
+    if (t.dev) (void)hipFree(t.dev);
+    t = MirroredTable{};
 }
 
 // Is the sensor model there, and are its views the hh x ww ones the model of `who` was begun with?

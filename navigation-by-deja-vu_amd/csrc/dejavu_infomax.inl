@@ -453,10 +453,8 @@ static void infomax_free(dv_ctx* c) {
     c->im_bx_cap = c->im_bdpart_cap = c->im_res.cap = c->im_perr_cap = 0;
     c->im_M = c->im_N = c->im_hh = c->im_ww = 0;
     c->im_xs_cap = 0;
-    F(c->im_kh[0]); F(c->im_kh[1]); F(c->im_ku); F(c->im_kupart); F(c->im_ktab);
-    c->im_ktab_cap = 0;
-    c->im_ktab_step = false;
-    c->im_ktab_host.clear();
+    F(c->im_kh[0]); F(c->im_kh[1]); F(c->im_ku); F(c->im_kupart);
+    table_free(c->im_ktab);
     c->im_banks = 1;
     c->im_views.assign(1, 0);
     c->im_finite.assign(1, 1);
@@ -831,10 +829,8 @@ static int ibank_check_finite(dv_ctx* c) {
 // A banked call's table, checked entry by entry before anything of the call reaches the device: first every entry's range, then that
 // no entry names a bank whose weights are not finite.
 static int ibank_check(dv_ctx* c, const char* who, const char* what, const int32_t* bank_of, int64_t n) {
-    if (!bank_of) return fail(c, DV_ERR_INVALID, "%s: %s is NULL", who, what);
-    for (int64_t i = 0; i < n; ++i)
-        if (bank_of[i] < 0 || bank_of[i] >= c->im_banks)
-            return fail(c, DV_ERR_INVALID, "%s: %s[%lld] = %d outside [0, n_banks = %d)", who, what, (long long)i, (int)bank_of[i], c->im_banks);
+    const int rc = index_check(c, who, what, bank_of, n, c->im_banks, "n_banks");
+    if (rc) return rc;
     for (int64_t i = 0; i < n; ++i)
         if (!c->im_finite[(size_t)bank_of[i]])
             return fail(c, DV_ERR_STATE, "%s: %s[%lld] names bank %d, whose weights are not finite (learning_rate %g is too large for its views: the rule diverged)",
@@ -870,18 +866,6 @@ static int ibank_buffers(dv_ctx* c) {
     return DV_OK;
 }
 
-// Send the table `t` to im_ktab unless the device holds exactly it (an ensemble's step table changes only when a member stops).
-static int ibank_table(dv_ctx* c, std::vector<int>& t, bool step) {
-    if (step && c->im_ktab_step && t == c->im_ktab_host) return DV_OK;
-    c->im_ktab_step = false;
-    int rc = grow_buffer(c, c->im_ktab, c->im_ktab_cap, t.size() * sizeof(int));
-    if (rc) return rc;
-    c->im_ktab_host.swap(t);                                  // (kept until the next table: the copy below borrows it)
-    HIP_TRY(c, hipMemcpyAsync(c->im_ktab, c->im_ktab_host.data(), c->im_ktab_host.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    c->im_ktab_step = step;
-    return DV_OK;
-}
-
 // Enqueue the banks' training chains over n views resident on the device (layout as k_im_prep's src), view v into bank bank_of[v]: per
 // slab of x vectors one k_im_prep over all its views, one k_im_gemv_banks for every chain's first h, then step s = the s-th view of every
 // bank that has one, in three launches.
@@ -903,16 +887,16 @@ static int ibank_train_device(dv_ctx* c, const unsigned char* d_src, long long v
         for (int b = 0; b < B; ++b) { start[b] = cur[(size_t)b] = run; run += len[b]; }
         for (int64_t v = 0; v < nb; ++v) t[idx0 + (size_t)cur[(size_t)bank_of[b0 + v]]++] = (int)v;
     }
-    rc = ibank_table(c, t, false);
+    rc = table_upload(c, c->im_ktab, t.data(), t.size() * sizeof(int));
     if (rc) return rc;
-    const int* d_idx = c->im_ktab + idx0;
+    const int* d_idx = c->im_ktab.device<int>() + idx0;
     const double rate = c->im_eta / (double)N;
     const unsigned row_blocks = (unsigned)((M + 3) / 4), col_blocks = (unsigned)((N + 255) / 256);
     const int n_rb = (M + kImRowsPerBlock - 1) / kImRowsPerBlock;
     for (int64_t k = 0; k < n_slabs; ++k) {
         const int64_t b0 = k * cap, nb = n - b0 < cap ? n - b0 : cap;
-        const int* len = c->im_ktab_host.data() + (size_t)k * 2 * (size_t)B;
-        const int* d_tab = c->im_ktab + (size_t)k * 2 * (size_t)B;
+        const int* len = c->im_ktab.record<int>() + (size_t)k * 2 * (size_t)B;
+        const int* d_tab = c->im_ktab.device<int>() + (size_t)k * 2 * (size_t)B;
         int steps = 0;
         for (int b = 0; b < B; ++b) steps = len[b] > steps ? len[b] : steps;
         hipLaunchKernelGGL(k_im_prep, dim3((unsigned)nb), dim3(256), 0, c->stream, d_src + (size_t)b0 * (size_t)view_stride, view_stride, px_stride,
@@ -988,15 +972,15 @@ static int ibank_batch(dv_ctx* c, const char* who, const uint8_t* planes, const 
     if (!rc) rc = packed_device(c, c->im_res, C, n_agents, d_fam, d_best, d_flags);
     if (!rc && !planes) rc = grow_buffer(c, c->im_perr, c->im_perr_cap, (size_t)C * sizeof(int));
     if (!rc) rc = ensure_sense_buffer(c, (size_t)slab * N * (planes ? 1 : 3));
-    if (!rc) rc = ibank_table(c, t, true);
+    if (!rc) rc = table_upload(c, c->im_ktab, t.data(), t.size() * sizeof(int));
     if (!rc && land_of) {
         std::vector<int32_t> sorted((size_t)n_agents);
         for (int p = 0; p < n_agents; ++p) sorted[(size_t)p] = land_of[(size_t)order[(size_t)p]];
         rc = lands_upload(c, sorted.data(), n_agents);
     }
     if (rc) return rc;
-    const ImBlock* blocks = reinterpret_cast<const ImBlock*>(c->im_ktab_host.data());
-    const ImBlock* d_blocks = reinterpret_cast<const ImBlock*>(c->im_ktab);
+    const ImBlock* blocks = c->im_ktab.record<ImBlock>();
+    const ImBlock* d_blocks = c->im_ktab.device<ImBlock>();
     if (planes) {
         c->im_kplanes.resize((size_t)C * N);
         for (int p = 0; p < n_agents; ++p)
@@ -1047,7 +1031,7 @@ static int ibank_batch(dv_ctx* c, const char* who, const uint8_t* planes, const 
         k0 += nk;
     }
     hipLaunchKernelGGL(k_im_decide_banks, dim3((unsigned)n_agents), dim3(256), 0, c->stream, c->im_bdpart, tiles, cpad, A,
-                       planes ? nullptr : c->im_perr, c->im_ktab + 4 * n_blocks, d_fam, d_best, d_flags);
+                       planes ? nullptr : c->im_perr, c->im_ktab.device<int>() + 4 * n_blocks, d_fam, d_best, d_flags);
     HIP_TRY(c, hipGetLastError());
     rc = packed_fetch(c, c->im_res, C, n_agents);
     if (rc) return rc;
@@ -1085,7 +1069,6 @@ extern "C" int dv_ibank_set(dv_ctx* c, int n_banks, const double* w0) {
     c->im_banks = n_banks;
     c->im_views.assign((size_t)n_banks, 0);
     c->im_finite.assign((size_t)n_banks, 1);
-    c->im_ktab_step = false;
     return ibank_check_finite(c);
 }
 

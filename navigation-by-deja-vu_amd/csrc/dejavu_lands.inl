@@ -15,7 +15,7 @@
 //   k_mb_pose_bank_lands   (dejavu_mushroom.inl) k_mb_pose_bank whose mb_fill_pose reads the workgroup's member's landscape.
 //
 // The host checks every entry of a landscape table against [0, n_lands) before a call's first enqueue, and keeps what the device's
-// table holds so that an unchanged one is not sent again (as mbank_upload).
+// table holds so that an unchanged one is not sent again (index_check and table_upload).
 namespace dv {
 
 // The landscape of column `col` of a call: g's rows / cols become the entry's; returns the landscape's first byte.
@@ -45,12 +45,12 @@ static int sensors_launch_sense(dv_ctx* c, long long p0, long long col0, int per
 static void lands_free(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
     sensors_free(c);                                           // (a sensor table belongs to the entries of its set)
-    F(c->ld_lands); F(c->ld_tab); F(c->ld_of); F(c->ld_err);
-    c->ld_of_cap = c->ld_err_cap = 0;
+    F(c->ld_lands); F(c->ld_tab); F(c->ld_err);
+    c->ld_err_cap = 0;
+    table_free(c->ld_of);
     c->ld_bytes = 0;
     c->ld_rows.clear();
     c->ld_cols.clear();
-    c->ld_of_host.clear();
     c->ld_err_host.clear();
 }
 
@@ -61,27 +61,13 @@ static int lands_need(dv_ctx* c, const char* who) {
 
 // A call's landscape table, checked entry by entry before anything of the call reaches the device ...
 static int lands_check(dv_ctx* c, const char* who, const char* what, const int32_t* land_of, int64_t n) {
-    if (!land_of) return fail(c, DV_ERR_INVALID, "%s: %s is NULL", who, what);
-    int rc = lands_need(c, who);
-    if (rc) return rc;
-    const int L = (int)c->ld_rows.size();
-    for (int64_t i = 0; i < n; ++i)
-        if (land_of[i] < 0 || land_of[i] >= L)
-            return fail(c, DV_ERR_INVALID, "%s: %s[%lld] = %d outside [0, n_lands = %d)", who, what, (long long)i, (int)land_of[i], L);
-    return DV_OK;
+    if (land_of) { const int rc = lands_need(c, who); if (rc) return rc; }   // (a NULL table is refused first, whether there is a set or not)
+    return index_check(c, who, what, land_of, n, (int)c->ld_rows.size(), "n_lands");
 }
 
-// ... and then enqueued for the device, unless the device's table holds the same already.  The copy reads the context's own record of
-// the table, so `land_of` may be a temporary of the caller's.
+// ... and then enqueued for the device, unless the device's table holds the same already (`land_of` may be a temporary of the caller's).
 static int lands_upload(dv_ctx* c, const int32_t* land_of, int64_t n) {
-    if (n < 1) return DV_OK;
-    if ((int64_t)c->ld_of_host.size() == n && std::equal(land_of, land_of + n, c->ld_of_host.begin())) return DV_OK;
-    c->ld_of_host.clear();
-    int rc = grow_buffer(c, c->ld_of, c->ld_of_cap, (size_t)n * sizeof(int));
-    if (rc) return rc;
-    c->ld_of_host.assign(land_of, land_of + n);               // (kept until the next table: every caller waits for the stream before it returns)
-    HIP_TRY(c, hipMemcpyAsync(c->ld_of, c->ld_of_host.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    return DV_OK;
+    return table_upload(c, c->ld_of, land_of, (size_t)n * sizeof(int));
 }
 
 // Enqueue k_sense_lands for `n` poses that are resident in d_poses from `p0` on and are columns col0 .. of the call, into d_out
@@ -90,7 +76,7 @@ static int lands_upload(dv_ctx* c, const int32_t* land_of, int64_t n) {
 static int lands_launch_sense(dv_ctx* c, long long p0, long long col0, int per, long long n, unsigned char* d_out, int* err) {
     if (c->sn_tab) return sensors_launch_sense(c, p0, col0, per, n, d_out, err);
     const long long total = n * c->sensor.sh * c->sensor.sw;
-    hipLaunchKernelGGL(k_sense_lands, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, c->ld_lands, c->ld_tab, (const int*)c->ld_of,
+    hipLaunchKernelGGL(k_sense_lands, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, c->ld_lands, c->ld_tab, c->ld_of.device<int>(),
                        (unsigned)col0, (unsigned)per, c->d_poses + p0, (int)n, c->sensor, c->d_lut, d_out, err);
     HIP_TRY(c, hipGetLastError());
     return DV_OK;
@@ -112,7 +98,7 @@ static int lands_check_sense_error(dv_ctx* c, const char* who, long long n) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (long long v = 0; v < n; ++v)
         if (c->ld_err_host[(size_t)v]) {
-            const int l = c->ld_of_host[(size_t)v];
+            const int l = c->ld_of.record<int>()[(size_t)v];
             return fail(c, DV_ERR_INDEX, "%s: the sensor footprint of pose %lld reaches past the end of its landscape %d (%d x %d) (index out of bounds)",
                         who, v, l, c->ld_rows[(size_t)l], c->ld_cols[(size_t)l]);
         }

@@ -179,10 +179,8 @@ extern "C" int dv_marks_summary_slots(dv_ctx* c, const int32_t* slots, const int
         return fail(c, DV_ERR_STATE, "dv_marks_summary_slots: no coverage slots (dv_set_training_path, dv_path_slots)");
     if (n < 0 || (n > 0 && (!slots || !window || !out))) return fail(c, DV_ERR_INVALID, "dv_marks_summary_slots: NULL argument or n < 0");
     if (n == 0) return DV_OK;
-    for (int i = 0; i < n; ++i)
-        if (slots[i] < 0 || slots[i] >= c->n_cover_slots)
-            return fail(c, DV_ERR_INVALID, "dv_marks_summary_slots: slots[%d] = %d outside [0, n_slots = %d)", i, (int)slots[i], c->n_cover_slots);
-    int rc = marks_windows(c, "dv_marks_summary_slots", window, n);
+    int rc = index_check(c, "dv_marks_summary_slots", "slots", slots, n, c->n_cover_slots, "n_slots");
+    if (!rc) rc = marks_windows(c, "dv_marks_summary_slots", window, n);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     rc = marks_reserve(c, "dv_marks_summary_slots", (size_t)n * (sizeof(MarksEntry) + 3 * sizeof(long long)));
@@ -198,11 +196,8 @@ extern "C" int dv_marks_summary_routes(dv_ctx* c, const int32_t* slots, const in
     if (rc) return rc;
     if (n < 0 || (n > 0 && (!slots || !window || !out))) return fail(c, DV_ERR_INVALID, "dv_marks_summary_routes: NULL argument or n < 0");
     if (n == 0) return DV_OK;
-    const int n_slots = (int)c->rt_slot_route.size();
-    for (int64_t i = 0; i < n; ++i)
-        if (slots[i] < 0 || slots[i] >= n_slots)
-            return fail(c, DV_ERR_INVALID, "dv_marks_summary_routes: slots[%lld] = %d outside [0, n_slots = %d)", (long long)i, (int)slots[i], n_slots);
-    rc = marks_windows(c, "dv_marks_summary_routes", window, n);
+    rc = index_check(c, "dv_marks_summary_routes", "slots", slots, n, (int)c->rt_slot_route.size(), "n_slots");
+    if (!rc) rc = marks_windows(c, "dv_marks_summary_routes", window, n);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     rc = marks_reserve(c, "dv_marks_summary_routes", (size_t)n * (sizeof(MarksEntry) + 3 * sizeof(long long)));

@@ -302,12 +302,12 @@ static constexpr size_t kMbStageBytes = 64u << 20;           // ... and the byte
 
 static void mb_free(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-    F(c->mb_conn); F(c->mb_wt); F(c->mb_d); F(c->mb_fired); F(c->mb_zeros); F(c->mb_bd); F(c->mb_berr); F(c->mb_bank_of); F(c->mb_res.dev);
-    c->mb_d_cap = c->mb_fired_cap = c->mb_bd_cap = c->mb_berr_cap = c->mb_bank_of_cap = c->mb_res.cap = 0;
+    F(c->mb_conn); F(c->mb_wt); F(c->mb_d); F(c->mb_fired); F(c->mb_zeros); F(c->mb_bd); F(c->mb_berr); F(c->mb_res.dev);
+    c->mb_d_cap = c->mb_fired_cap = c->mb_bd_cap = c->mb_berr_cap = c->mb_res.cap = 0;
+    table_free(c->mb_bank_of);
     c->mb_K = c->mb_N = c->mb_c = c->mb_active = c->mb_hh = c->mb_ww = 0;
     c->mb_banks = 1;
     c->mb_views.assign(1, 0);
-    c->mb_bank_host.clear();
 }
 
 static int mb_need(dv_ctx* c, const char* who) {
@@ -356,24 +356,12 @@ static void mb_count_views(dv_ctx* c, int64_t n, const int32_t* bank_of) {
 
 // A banked call's table, checked entry by entry before anything of the call reaches the device ...
 static int mbank_check(dv_ctx* c, const char* who, const char* what, const int32_t* bank_of, int64_t n) {
-    if (!bank_of) return fail(c, DV_ERR_INVALID, "%s: %s is NULL", who, what);
-    for (int64_t i = 0; i < n; ++i)
-        if (bank_of[i] < 0 || bank_of[i] >= c->mb_banks)
-            return fail(c, DV_ERR_INVALID, "%s: %s[%lld] = %d outside [0, n_banks = %d)", who, what, (long long)i, (int)bank_of[i], c->mb_banks);
-    return DV_OK;
+    return index_check(c, who, what, bank_of, n, c->mb_banks, "n_banks");
 }
 
-// ... and then enqueued for the device (`bank_of` is borrowed: every caller waits for the stream before it returns).  The host keeps
-// what the device's table holds: an ensemble's banks change only when a member stops, so most steps find it there and upload nothing.
+// ... and then enqueued for the device, unless the device's table holds the same already.
 static int mbank_upload(dv_ctx* c, const int32_t* bank_of, int64_t n) {
-    if (n < 1) return DV_OK;
-    if ((int64_t)c->mb_bank_host.size() == n && std::equal(bank_of, bank_of + n, c->mb_bank_host.begin())) return DV_OK;
-    c->mb_bank_host.clear();
-    int rc = grow_buffer(c, c->mb_bank_of, c->mb_bank_of_cap, (size_t)n * sizeof(int));
-    if (rc) return rc;
-    HIP_TRY(c, hipMemcpyAsync(c->mb_bank_of, bank_of, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    c->mb_bank_host.assign(bank_of, bank_of + n);
-    return DV_OK;
+    return table_upload(c, c->mb_bank_of, bank_of, (size_t)n * sizeof(int));
 }
 
 extern "C" int dv_mb_end(dv_ctx* c) {
@@ -449,7 +437,7 @@ static int mb_train_u8(dv_ctx* c, const char* who, const uint8_t* planes, int64_
     for (int64_t v0 = 0; v0 < n; v0 += slab) {
         const int64_t ns = n - v0 < slab ? n - v0 : slab;
         HIP_TRY(c, hipMemcpyAsync(c->d_sense, planes + (size_t)v0 * N, (size_t)ns * N, hipMemcpyHostToDevice, c->stream));
-        rc = bank_of ? mb_launch_bank<kMbTrain>(c, c->d_sense, (long long)N, 1, 0, (int)ns, nullptr, c->mb_bank_of + v0, 0, 1)
+        rc = bank_of ? mb_launch_bank<kMbTrain>(c, c->d_sense, (long long)N, 1, 0, (int)ns, nullptr, c->mb_bank_of.device<int>() + v0, 0, 1)
                      : mb_launch<kMbTrain>(c, c->d_sense, (long long)N, 1, 0, (int)ns, nullptr, nullptr, nullptr);
         if (rc) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->stream));          // the slab is reused, `planes` is borrowed
@@ -489,7 +477,7 @@ static int mb_train_from_poses(dv_ctx* c, const char* who, const double* x, cons
     for (int64_t v0 = 0; v0 < n; v0 += kMbSlabViews) {
         const int64_t ns = n - v0 < kMbSlabViews ? n - v0 : kMbSlabViews;
         const unsigned char* src = c->d_sense + (size_t)v0 * (size_t)stride;
-        rc = bank_of ? mb_launch_bank<kMbTrain>(c, src, stride, 3, c->mb_channel, (int)ns, nullptr, c->mb_bank_of + v0, 0, 1)
+        rc = bank_of ? mb_launch_bank<kMbTrain>(c, src, stride, 3, c->mb_channel, (int)ns, nullptr, c->mb_bank_of.device<int>() + v0, 0, 1)
                      : mb_launch<kMbTrain>(c, src, stride, 3, c->mb_channel, (int)ns, nullptr, nullptr, nullptr);
         if (rc) return rc;
     }
@@ -620,23 +608,23 @@ static int mb_batch(dv_ctx* c, const char* who, const uint8_t* planes, const dou
         const int nc = (int)(C - c0 < slab ? C - c0 : slab);
         if (planes) {
             HIP_TRY(c, hipMemcpyAsync(c->d_sense, planes + (size_t)c0 * N, (size_t)nc * N, hipMemcpyHostToDevice, c->stream));
-            rc = bank_of ? mb_launch_bank<kMbScore>(c, c->d_sense, (long long)N, 1, 0, nc, c->mb_bd + c0, c->mb_bank_of, c0, A)
+            rc = bank_of ? mb_launch_bank<kMbScore>(c, c->d_sense, (long long)N, 1, 0, nc, c->mb_bd + c0, c->mb_bank_of.device<int>(), c0, A)
                          : mb_launch<kMbScore>(c, c->d_sense, (long long)N, 1, 0, nc, c->mb_bd + c0, nullptr, nullptr);
             if (rc) return rc;
         } else if (land_of && c->sn_tab) {
             hipLaunchKernelGGL(k_mb_pose_bank_lands_sensors, dim3((unsigned)nc), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, c->ld_lands, c->ld_tab,
-                               c->sn_tab, c->sn_luts, (const int*)c->ld_of, c->d_poses + c0, c->sensor, c->mb_channel, c->mb_conn, c->mb_K, c->mb_c,
-                               c->mb_active, c->mb_wt, c->mb_bd + c0, c->mb_berr + c0, (const int*)c->mb_bank_of, (unsigned)c0, (unsigned)A);
+                               c->sn_tab, c->sn_luts, c->ld_of.device<int>(), c->d_poses + c0, c->sensor, c->mb_channel, c->mb_conn, c->mb_K, c->mb_c,
+                               c->mb_active, c->mb_wt, c->mb_bd + c0, c->mb_berr + c0, c->mb_bank_of.device<int>(), (unsigned)c0, (unsigned)A);
             HIP_TRY(c, hipGetLastError());
         } else if (land_of) {
             hipLaunchKernelGGL(k_mb_pose_bank_lands, dim3((unsigned)nc), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, c->ld_lands, c->ld_tab,
-                               (const int*)c->ld_of, c->d_poses + c0, c->sensor, c->d_lut, c->mb_channel, c->mb_conn, c->mb_K, c->mb_c, c->mb_active,
-                               c->mb_wt, c->mb_bd + c0, c->mb_berr + c0, (const int*)c->mb_bank_of, (unsigned)c0, (unsigned)A);
+                               c->ld_of.device<int>(), c->d_poses + c0, c->sensor, c->d_lut, c->mb_channel, c->mb_conn, c->mb_K, c->mb_c, c->mb_active,
+                               c->mb_wt, c->mb_bd + c0, c->mb_berr + c0, c->mb_bank_of.device<int>(), (unsigned)c0, (unsigned)A);
             HIP_TRY(c, hipGetLastError());
         } else if (bank_of) {
             hipLaunchKernelGGL(k_mb_pose_bank, dim3((unsigned)nc), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, c->d_land, c->d_poses + c0, c->sensor,
                                c->d_lut, c->mb_channel, c->mb_conn, c->mb_K, c->mb_c, c->mb_active, c->mb_wt, c->mb_bd + c0, c->mb_berr + c0,
-                               (const int*)c->mb_bank_of, (unsigned)c0, (unsigned)A);
+                               c->mb_bank_of.device<int>(), (unsigned)c0, (unsigned)A);
             HIP_TRY(c, hipGetLastError());
         } else {
             hipLaunchKernelGGL(k_mb_pose, dim3((unsigned)nc), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, c->d_land, c->d_poses + c0, c->sensor,

@@ -69,13 +69,11 @@ extern "C" int dv_path_routes_slots(dv_ctx* c, const int32_t* route_of_slot, int
     int rc = path_routes_need(c, "dv_path_routes_slots", false);
     if (rc) return rc;
     if (n_slots < 0) return fail(c, DV_ERR_INVALID, "dv_path_routes_slots: n_slots %d < 0", n_slots);
-    if (n_slots > 0 && !route_of_slot) return fail(c, DV_ERR_INVALID, "dv_path_routes_slots: route_of_slot is NULL");
-    const int n_routes = (int)c->rt_first.size() - 1;
+    if (n_slots > 0) rc = index_check(c, "dv_path_routes_slots", "route_of_slot", route_of_slot, n_slots, (int)c->rt_first.size() - 1, "n_routes");
+    if (rc) return rc;
     std::vector<int64_t> base((size_t)n_slots + 1, 0);
     for (int j = 0; j < n_slots; ++j) {
         const int r = route_of_slot[j];
-        if (r < 0 || r >= n_routes)
-            return fail(c, DV_ERR_INVALID, "dv_path_routes_slots: route_of_slot[%d] = %d outside [0, n_routes = %d)", j, r, n_routes);
         base[(size_t)j + 1] = base[(size_t)j] + (c->rt_first[(size_t)r + 1] - c->rt_first[(size_t)r]);
     }
     HIP_TRY(c, hipSetDevice(c->device));
@@ -111,10 +109,8 @@ extern "C" int dv_path_routes_error(dv_ctx* c, const int32_t* slots, const doubl
     if (n < 0 || (n > 0 && (!slots || !x || !y || !reach || !nearest)))
         return fail(c, DV_ERR_INVALID, "dv_path_routes_error: NULL argument or n < 0");
     if (n == 0) return DV_OK;
-    const int n_slots = (int)c->rt_slot_route.size();
-    for (int64_t i = 0; i < n; ++i)
-        if (slots[i] < 0 || slots[i] >= n_slots)
-            return fail(c, DV_ERR_INVALID, "dv_path_routes_error: slots[%lld] = %d outside [0, n_slots = %d)", (long long)i, (int)slots[i], n_slots);
+    rc = index_check(c, "dv_path_routes_error", "slots", slots, n, (int)c->rt_slot_route.size(), "n_slots");
+    if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     // the call's table: n entries, then n minima that start as all ones -- one upload for both
     const size_t tab_bytes = (size_t)n * sizeof(PathRouteEntry), bytes = tab_bytes + (size_t)n * sizeof(unsigned long long);

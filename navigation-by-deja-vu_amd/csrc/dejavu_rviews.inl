@@ -267,10 +267,10 @@ k_rv_scene(const unsigned* __restrict__ planes, const RvRoute* __restrict__ rout
 
 static void rviews_free(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-    F(c->rv_planes); F(c->rv_routes); F(c->rv_fast); F(c->rv_marked); F(c->rv_out); F(c->rv_tab); F(c->rv_err); F(c->rv_scene); F(c->rv_prep);
-    c->rv_fast_cap = c->rv_marked_cap = c->rv_out_cap = c->rv_tab_cap = c->rv_err_cap = c->rv_scene_cap = c->rv_prep_cap = 0;
+    F(c->rv_planes); F(c->rv_routes); F(c->rv_fast); F(c->rv_marked); F(c->rv_out); F(c->rv_err); F(c->rv_scene); F(c->rv_prep);
+    c->rv_fast_cap = c->rv_marked_cap = c->rv_out_cap = c->rv_err_cap = c->rv_scene_cap = c->rv_prep_cap = 0;
     c->rv_first.clear();
-    c->rv_tab_host.clear();
+    table_free(c->rv_tab);
     c->rv_h = c->rv_w = 0;
     c->rv_lmax = 0;
     c->rv_bytes = 0;
@@ -342,7 +342,7 @@ static int rviews_build(dv_ctx* c, const char* who, const unsigned char* d_raw, 
     c->rv_lmax = lmax;
     c->rv_bytes = (long long)(dwords * 4);
     c->rv_delta = 4.0 * (P + 8.0) * std::ldexp(1.0, -53) * P;           // alloc_library's c->delta
-    c->rv_tab_host.clear();
+    c->rv_tab.host.clear();
     return DV_OK;
 }
 
@@ -448,10 +448,8 @@ static int rviews_check_tables(dv_ctx* c, const char* who, int N, int A, const i
     if (!route_of_member || !chem_weights) return fail(c, DV_ERR_INVALID, "%s: NULL table", who);
     int rc = rviews_need(c, who);
     if (rc) return rc;
-    const int R = (int)c->rv_first.size() - 1;
-    for (int i = 0; i < N; ++i)
-        if (route_of_member[i] < 0 || route_of_member[i] >= R)
-            return fail(c, DV_ERR_INVALID, "%s: route_of_member[%d] = %d outside [0, n_routes = %d)", who, i, (int)route_of_member[i], R);
+    rc = index_check(c, who, "route_of_member", route_of_member, N, (int)c->rv_first.size() - 1, "n_routes");
+    if (rc) return rc;
     for (int i = 0; i < N; ++i)
         if (!(chem_weights[i] >= 0.0 && chem_weights[i] <= 1.0))
             return fail(c, DV_ERR_INVALID, "%s: chem_weights[%d] = %g outside [0, 1]", who, i, chem_weights[i]);
@@ -511,13 +509,7 @@ static int rviews_plan(dv_ctx* c, RvPlan& p, int N, int A, const int32_t* route_
     if (row0) std::memcpy(tab.data() + p.off_row0, row0, (size_t)N * sizeof(long long));
     std::memcpy(tab.data() + p.off_col, col_of.data(), col_of.size() * sizeof(int));
     std::memcpy(tab.data() + p.off_route, route_of_member, (size_t)N * sizeof(int));
-    if (tab == c->rv_tab_host) return DV_OK;
-    c->rv_tab_host.clear();
-    int rc = grow_buffer(c, c->rv_tab, c->rv_tab_cap, tab.size());
-    if (rc) return rc;
-    c->rv_tab_host.swap(tab);                                           // (kept until the next table: every caller waits for the stream)
-    HIP_TRY(c, hipMemcpyAsync(c->rv_tab, c->rv_tab_host.data(), c->rv_tab_host.size(), hipMemcpyHostToDevice, c->stream));
-    return DV_OK;
+    return table_upload(c, c->rv_tab, tab.data(), tab.size());
 }
 
 // Score the C columns whose patches lie in d_sense (uint8[C][P][3], the caller's order); err: a word per column, or nullptr.
@@ -529,10 +521,10 @@ static int rviews_run(dv_ctx* c, const RvPlan& p, bool exact, const int* err, do
     const size_t out_bytes = (size_t)p.C * 16 + (size_t)p.N * 8;
     if (!rc) rc = grow_buffer(c, c->rv_out, c->rv_out_cap, out_bytes);
     if (rc) return rc;
-    const AgentW* wts = reinterpret_cast<const AgentW*>(c->rv_tab + p.off_wts);
-    const RvTile* tiles = reinterpret_cast<const RvTile*>(c->rv_tab + p.off_tiles);
-    const int* col_of = reinterpret_cast<const int*>(c->rv_tab + p.off_col);
-    const int* route_of = reinterpret_cast<const int*>(c->rv_tab + p.off_route);
+    const AgentW* wts = reinterpret_cast<const AgentW*>(c->rv_tab.dev + p.off_wts);
+    const RvTile* tiles = reinterpret_cast<const RvTile*>(c->rv_tab.dev + p.off_tiles);
+    const int* col_of = reinterpret_cast<const int*>(c->rv_tab.dev + p.off_col);
+    const int* route_of = reinterpret_cast<const int*>(c->rv_tab.dev + p.off_route);
     double* d_fam = reinterpret_cast<double*>(c->rv_out);
     long long* d_view = reinterpret_cast<long long*>(c->rv_out + (size_t)p.C * 8);
     int* d_best = reinterpret_cast<int*>(c->rv_out + (size_t)p.C * 16);
@@ -653,8 +645,8 @@ static int rviews_scene_run(dv_ctx* c, int N, int A, const int32_t* route_of_mem
     for (int i0 = 0; i0 < N; i0 += 32768) {
         const int ni = std::min(N - i0, 32768);
         hipLaunchKernelGGL(k_rv_scene, dim3((unsigned)((c->rv_lmax + 255) / 256), (unsigned)ni), dim3(256), 0, c->stream, c->rv_planes, c->rv_routes,
-                           reinterpret_cast<const int*>(c->rv_tab + p.off_route) + i0, reinterpret_cast<const long long*>(c->rv_tab + p.off_row0) + i0,
-                           c->d_sense + (size_t)i0 * A * P * 3, reinterpret_cast<const AgentW*>(c->rv_tab + p.off_wts) + i0, A, P, Pw, c->rv_scene);
+                           reinterpret_cast<const int*>(c->rv_tab.dev + p.off_route) + i0, reinterpret_cast<const long long*>(c->rv_tab.dev + p.off_row0) + i0,
+                           c->d_sense + (size_t)i0 * A * P * 3, reinterpret_cast<const AgentW*>(c->rv_tab.dev + p.off_wts) + i0, A, P, Pw, c->rv_scene);
     }
     HIP_TRY(c, hipGetLastError());
     std::vector<int> herr;

@@ -59,7 +59,7 @@ static void sensors_free(dv_ctx* c) {
 static int sensors_launch_sense(dv_ctx* c, long long p0, long long col0, int per, long long n, unsigned char* d_out, int* err) {
     const long long total = n * c->sensor.sh * c->sensor.sw;
     hipLaunchKernelGGL(k_sense_lands_sensors, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, c->ld_lands, c->ld_tab, c->sn_tab,
-                       c->sn_luts, (const int*)c->ld_of, (unsigned)col0, (unsigned)per, c->d_poses + p0, (int)n, c->sensor, d_out, err);
+                       c->sn_luts, c->ld_of.device<int>(), (unsigned)col0, (unsigned)per, c->d_poses + p0, (int)n, c->sensor, d_out, err);
     HIP_TRY(c, hipGetLastError());
     return DV_OK;
 }

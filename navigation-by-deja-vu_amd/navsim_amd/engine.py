@@ -78,9 +78,10 @@ class RouteViewResults(OneValueBatchResults):
 InfomaxBatchResults = OneValueBatchResults    # the name it had while Infomax was the only such model
 
 # The one-value models -- no library, ONE value per heading: metric -> (prefix of the single calls' symbols, of the batch calls', the
-# engine attribute that holds the model's (h, w)).
-_ONE_VALUE = {"infomax": ("dv_infomax_", "dv_batch_infomax_", "infomax_shape"),
-              "mushroom": ("dv_mb_", "dv_batch_mb_", "mb_shape")}
+# engine attribute that holds the model's (h, w), prefix of the banked calls' symbols, of the banked calls on a landscape set, the
+# engine attribute that holds the model's number of banks).
+_ONE_VALUE = {"infomax": ("dv_infomax_", "dv_batch_infomax_", "infomax_shape", "dv_ibank_", "dv_lands_ibank_", "infomax_banks"),
+              "mushroom": ("dv_mb_", "dv_batch_mb_", "mb_shape", "dv_mbank_", "dv_lands_mbank_", "mb_banks")}
 ONE_VALUE_METRICS = tuple(_ONE_VALUE)
 
 
@@ -804,16 +805,19 @@ class FamiliarityEngine(object):
     _route_of_slot = None        # int32[n_slots]: the route of every slot (path_routes_slots); None: no slots
 
     @staticmethod
-    def _route_ints(table, what, hi, of):
-        """`table` as int32[n] with every entry in [0, hi), or ValueError naming `what`: checked before any library call.  hi = None:
-        there is nothing to index yet, and the library answers DV_ERR_STATE."""
+    def _index_table(table, what, hi, of, n=None, per=None):
+        """`table` as int32[n] (n = None: of any length) with every entry in [0, hi), or ValueError naming `what`: checked before any
+        library call.  `of` names hi, `per` what an entry stands for.  hi = None: there is nothing to index yet, and the library
+        answers DV_ERR_STATE."""
         arr = np.asarray(table)
         if arr.shape == (0,):
             arr = arr.astype(np.int32)                           # (an empty list has no dtype to speak of)
         if arr.dtype.kind not in "iu":
-            raise ValueError("%s must hold integers, got dtype %s" % (what, arr.dtype))
-        if arr.ndim != 1:
+            raise ValueError("%s must hold integers%s, got dtype %s" % (what, " (a %s per entry)" % per if per else "", arr.dtype))
+        if n is None and arr.ndim != 1:
             raise ValueError("%s must have one dimension, got shape %r" % (what, arr.shape))
+        if n is not None and arr.shape != (n,):
+            raise ValueError("%s must have shape (%d,), got %r" % (what, n, arr.shape))
         if hi is not None and len(arr) and (arr.min() < 0 or arr.max() >= hi):
             bad = np.flatnonzero((arr < 0) | (arr >= hi))
             raise ValueError("%s[%d] = %d outside [0, %s = %d)" % (what, bad[0], arr[bad[0]], of, hi))
@@ -860,7 +864,7 @@ class FamiliarityEngine(object):
     def path_routes_slots(self, route_of_slot):
         """Slot j gets coverage marks of its own for route route_of_slot[j], cleared (what the slots held is dropped).  An empty table,
         or None, frees them."""
-        table = self._route_ints([] if route_of_slot is None else route_of_slot, "route_of_slot",
+        table = self._index_table([] if route_of_slot is None else route_of_slot, "route_of_slot",
                                  None if self._route_first is None else len(self._route_first) - 1, "n_routes")
         self._check(self._lib.dv_path_routes_slots(self._ctx, table.ctypes.data_as(N._i32p), len(table)), "dv_path_routes_slots")
         self._route_of_slot = table if len(table) else None
@@ -868,7 +872,7 @@ class FamiliarityEngine(object):
     def path_routes_error(self, slots, xs, ys, reach):
         """update_error (NavBySceneFamiliarity.py:252-276) for n entries at once, each against ITS slot's route and with its OWN reach:
         float64[n] of the distances to the nearest point of each entry's route; the slots' marks updated."""
-        slots = self._route_ints(slots, "slots", None if self._route_of_slot is None else len(self._route_of_slot), "n_slots")
+        slots = self._index_table(slots, "slots", None if self._route_of_slot is None else len(self._route_of_slot), "n_slots")
         n = len(slots)
         vals = []
         for name, v in (("xs", xs), ("ys", ys), ("reach", reach)):
@@ -954,7 +958,7 @@ class FamiliarityEngine(object):
     def _marks_summary_many(self, symbol, slots, windows, n_slots, made_by):
         if n_slots is None:
             raise ValueError("no slots set (%s)" % made_by)
-        slots = self._route_ints(slots, "slots", n_slots, "n_slots")
+        slots = self._index_table(slots, "slots", n_slots, "n_slots")
         n = len(slots)
         windows = self._marks_windows(windows, n)
         out = np.empty((n, 3), dtype=np.int64)
@@ -991,6 +995,29 @@ class FamiliarityEngine(object):
 
     def _ov_planes(self, metric, planes):
         return self._model_planes(getattr(self, _ONE_VALUE[metric][2], None), planes, "planes")
+
+    @staticmethod
+    def _member_poses(x, y, angles):
+        """An ensemble's poses as float64 x[N], y[N] and angles[N, A]."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        angles = np.ascontiguousarray(angles, dtype=np.float64)
+        if angles.ndim != 2 or len(x) != len(y) or angles.shape[0] != len(x) or angles.shape[0] < 1 or angles.shape[1] < 1:
+            raise ValueError("x[N], y[N] and angles[N, A] expected (N, A >= 1), got shapes %r, %r and %r" % (x.shape, y.shape, angles.shape))
+        return x, y, angles
+
+    @staticmethod
+    def _member_planes(planes):
+        """An ensemble's uploaded patches as uint8[n, A, ...]: member i's A headings in row i."""
+        planes = N.as_u8(planes, "planes")
+        if planes.ndim != 4 or planes.shape[0] < 1 or planes.shape[1] < 1:
+            raise ValueError("planes must be uint8[n,A,h,w] with n, A >= 1, got shape %r" % (planes.shape,))
+        return planes
+
+    @staticmethod
+    def _member_results(n, A):
+        """The buffers a step of n members x A headings answers into: angle_familiarity, best_idex, flags."""
+        return np.empty((n, A), dtype=np.float64), np.full(n, -1, dtype=np.int32), np.zeros(n, dtype=np.uint32)
 
     def one_value(self, metric):
         """The bound train_u8, train_from_poses, score_u8, sense_step and end of the one-value model `metric` ("infomax" or
@@ -1034,29 +1061,68 @@ class FamiliarityEngine(object):
 
     def _ov_step_batch_u8(self, metric, planes):
         name = _ONE_VALUE[metric][1] + "step_u8"
-        planes = N.as_u8(planes, "planes")
-        if planes.ndim != 4 or planes.shape[0] < 1 or planes.shape[1] < 1:
-            raise ValueError("planes must be uint8[n,A,h,w] with n, A >= 1, got shape %r" % (planes.shape,))
+        planes = self._member_planes(planes)
         n, A = planes.shape[:2]
         flat = self._ov_planes(metric, planes.reshape((n * A,) + planes.shape[2:]))
-        fam = np.empty((n, A), dtype=np.float64)
-        best = np.full(n, -1, dtype=np.int32)
+        fam, best, flags = self._member_results(n, A)
         self._check(getattr(self._lib, name)(self._ctx, N.u8ptr(flat), n, A, N.f64ptr(fam), best.ctypes.data_as(N._i32p)), name)
-        return OneValueBatchResults(fam, best, np.zeros(n, dtype=np.uint32))
+        return OneValueBatchResults(fam, best, flags)
 
     def _ov_sense_step_batch(self, metric, x, y, angles):
         name = _ONE_VALUE[metric][1] + "sense_step"
-        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
-        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
-        angles = np.ascontiguousarray(angles, dtype=np.float64)
-        if angles.ndim != 2 or len(x) != len(y) or angles.shape[0] != len(x) or angles.shape[0] < 1 or angles.shape[1] < 1:
-            raise ValueError("x[N], y[N] and angles[N, A] expected (N, A >= 1), got shapes %r, %r and %r" % (x.shape, y.shape, angles.shape))
+        x, y, angles = self._member_poses(x, y, angles)
         n, A = angles.shape
-        fam = np.empty((n, A), dtype=np.float64)
-        best = np.full(n, -1, dtype=np.int32)
-        flags = np.zeros(n, dtype=np.uint32)
+        fam, best, flags = self._member_results(n, A)
         self._check(getattr(self._lib, name)(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, N.f64ptr(fam),
                                              best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)), name)
+        return OneValueBatchResults(fam, best, flags)
+
+    # -- ... and their banked calls (dv_ibank_*, dv_mbank_*): the same, with a bank per view or per member -------------------------
+    def _bank_table(self, metric, table, n, what):
+        return self._index_table(table, what, getattr(self, _ONE_VALUE[metric][5]), "n_banks", n, "bank")
+
+    def _bank_symbol(self, metric, op, land_of, n, what):
+        """The symbol of the banked call `op` and what follows the bank table in its arguments: nothing, or (land_of is not None: the
+        call on the live landscape set) the landscape table, checked."""
+        if land_of is None:
+            return _ONE_VALUE[metric][3] + op, ()
+        return _ONE_VALUE[metric][4] + op, (self._land_table(land_of, n, what).ctypes.data_as(N._i32p),)
+
+    def _bank_train_u8(self, metric, planes, bank_of_view):
+        name = _ONE_VALUE[metric][3] + "train_u8"
+        planes = self._ov_planes(metric, planes)
+        banks = self._bank_table(metric, bank_of_view, planes.shape[0], "bank_of_view")
+        self._check(getattr(self._lib, name)(self._ctx, N.u8ptr(planes), planes.shape[0], banks.ctypes.data_as(N._i32p)), name)
+
+    def _bank_train_from_poses(self, metric, x, y, angle, bank_of_view, want_views, land_of_view):
+        x, y, angle = self._pose_arrays(x, y, angle)
+        banks = self._bank_table(metric, bank_of_view, len(x), "bank_of_view")
+        name, lands = self._bank_symbol(metric, "train_from_poses", land_of_view, len(x), "land_of_view")
+        h, w = self.sensor_shape
+        views = np.empty((len(x), h, w, 3), dtype=np.uint8) if want_views else None
+        self._check_sense(getattr(self._lib, name)(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), len(x), banks.ctypes.data_as(N._i32p),
+                                                   *lands, N.u8ptr(views) if want_views else None), name)
+        return views
+
+    def _bank_step_batch_u8(self, metric, planes, bank_of_member):
+        name = _ONE_VALUE[metric][3] + "step_u8"
+        planes = self._member_planes(planes)
+        n, A = planes.shape[:2]
+        banks = self._bank_table(metric, bank_of_member, n, "bank_of_member")
+        flat = self._ov_planes(metric, planes.reshape((n * A,) + planes.shape[2:]))
+        fam, best, flags = self._member_results(n, A)
+        self._check(getattr(self._lib, name)(self._ctx, N.u8ptr(flat), n, A, banks.ctypes.data_as(N._i32p), N.f64ptr(fam),
+                                             best.ctypes.data_as(N._i32p)), name)
+        return OneValueBatchResults(fam, best, flags)
+
+    def _bank_sense_step_batch(self, metric, x, y, angles, bank_of_member, land_of_member):
+        x, y, angles = self._member_poses(x, y, angles)
+        n, A = angles.shape
+        banks = self._bank_table(metric, bank_of_member, n, "bank_of_member")
+        name, lands = self._bank_symbol(metric, "sense_step", land_of_member, n, "land_of_member")
+        fam, best, flags = self._member_results(n, A)
+        self._check(getattr(self._lib, name)(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, banks.ctypes.data_as(N._i32p),
+                                             *lands, N.f64ptr(fam), best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)), name)
         return OneValueBatchResults(fam, best, flags)
 
     # -- Infomax familiarity model: one layer of weights instead of a library (include/dejavu.h: dv_infomax_*) ----------------
@@ -1146,66 +1212,20 @@ class FamiliarityEngine(object):
     def ibank_train_u8(self, planes, bank_of_view):
         """infomax_train_u8 with view v trained into bank bank_of_view[v]: every bank's views in their order, the banks' chains in
         lockstep, three launches a step for all of them."""
-        planes = self._ov_planes("infomax", planes)
-        banks = self._bank_table(bank_of_view, planes.shape[0], "bank_of_view", self.infomax_banks)
-        self._check(self._lib.dv_ibank_train_u8(self._ctx, N.u8ptr(planes), planes.shape[0], banks.ctypes.data_as(N._i32p)), "dv_ibank_train_u8")
+        self._bank_train_u8("infomax", planes, bank_of_view)
 
     def ibank_train_from_poses(self, x, y, angle, bank_of_view, want_views=True, land_of_view=None):
         """infomax_train_from_poses with view v trained into bank bank_of_view[v] (the routes of a grid, trained in one call); returns
         the views (uint8[n,h,w,3]) when want_views."""
-        x, y, angle = self._pose_arrays(x, y, angle)
-        banks = self._bank_table(bank_of_view, len(x), "bank_of_view", self.infomax_banks)
-        lands = None if land_of_view is None else self._land_table(land_of_view, len(x), "land_of_view")
-        h, w = self.sensor_shape
-        views = np.empty((len(x), h, w, 3), dtype=np.uint8) if want_views else None
-        if lands is not None:
-            self._check_sense(self._lib.dv_lands_ibank_train_from_poses(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), len(x),
-                                                                        banks.ctypes.data_as(N._i32p), lands.ctypes.data_as(N._i32p),
-                                                                        N.u8ptr(views) if want_views else None),
-                              "dv_lands_ibank_train_from_poses")
-            return views
-        self._check_sense(self._lib.dv_ibank_train_from_poses(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), len(x),
-                                                              banks.ctypes.data_as(N._i32p), N.u8ptr(views) if want_views else None),
-                          "dv_ibank_train_from_poses")
-        return views
+        return self._bank_train_from_poses("infomax", x, y, angle, bank_of_view, want_views, land_of_view)
 
     def ibank_step_batch_u8(self, planes, bank_of_member):
         """infomax_step_batch_u8 with member i scored under bank bank_of_member[i] -> OneValueBatchResults, in the caller's order."""
-        planes = N.as_u8(planes, "planes")
-        if planes.ndim != 4 or planes.shape[0] < 1 or planes.shape[1] < 1:
-            raise ValueError("planes must be uint8[n,A,h,w] with n, A >= 1, got shape %r" % (planes.shape,))
-        n, A = planes.shape[:2]
-        banks = self._bank_table(bank_of_member, n, "bank_of_member", self.infomax_banks)
-        flat = self._ov_planes("infomax", planes.reshape((n * A,) + planes.shape[2:]))
-        fam = np.empty((n, A), dtype=np.float64)
-        best = np.full(n, -1, dtype=np.int32)
-        self._check(self._lib.dv_ibank_step_u8(self._ctx, N.u8ptr(flat), n, A, banks.ctypes.data_as(N._i32p), N.f64ptr(fam),
-                                               best.ctypes.data_as(N._i32p)), "dv_ibank_step_u8")
-        return OneValueBatchResults(fam, best, np.zeros(n, dtype=np.uint32))
+        return self._bank_step_batch_u8("infomax", planes, bank_of_member)
 
     def ibank_sense_step_batch(self, x, y, angles, bank_of_member, land_of_member=None):
         """infomax_sense_step_batch with member i scored under bank bank_of_member[i] -> OneValueBatchResults: one enqueue and one wait."""
-        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
-        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
-        angles = np.ascontiguousarray(angles, dtype=np.float64)
-        if angles.ndim != 2 or len(x) != len(y) or angles.shape[0] != len(x) or angles.shape[0] < 1 or angles.shape[1] < 1:
-            raise ValueError("x[N], y[N] and angles[N, A] expected (N, A >= 1), got shapes %r, %r and %r" % (x.shape, y.shape, angles.shape))
-        n, A = angles.shape
-        banks = self._bank_table(bank_of_member, n, "bank_of_member", self.infomax_banks)
-        lands = None if land_of_member is None else self._land_table(land_of_member, n, "land_of_member")
-        fam = np.empty((n, A), dtype=np.float64)
-        best = np.full(n, -1, dtype=np.int32)
-        flags = np.zeros(n, dtype=np.uint32)
-        if lands is not None:
-            self._check(self._lib.dv_lands_ibank_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A,
-                                                            banks.ctypes.data_as(N._i32p), lands.ctypes.data_as(N._i32p), N.f64ptr(fam),
-                                                            best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)),
-                        "dv_lands_ibank_sense_step")
-            return OneValueBatchResults(fam, best, flags)
-        self._check(self._lib.dv_ibank_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, banks.ctypes.data_as(N._i32p),
-                                                  N.f64ptr(fam), best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)),
-                    "dv_ibank_sense_step")
-        return OneValueBatchResults(fam, best, flags)
+        return self._bank_sense_step_batch("infomax", x, y, angles, bank_of_member, land_of_member)
 
     def ibank_read_weights(self, bank):
         """float64[n_hidden, h*w] of one bank."""
@@ -1307,22 +1327,6 @@ class FamiliarityEngine(object):
     # -- memory banks of the mushroom-body model: several memories behind one connectivity (include/dejavu.h: dv_mbank_*) ---------
     mb_banks = 1                 # memories of the model (mbank_set; 1 after mb_begin)
 
-    def _bank_table(self, table, n, what, n_banks=None):
-        """`table` as int32[n] with every entry in [0, n_banks) (default: mb_banks), or ValueError naming `what`: checked before any
-        library call."""
-        n_banks = self.mb_banks if n_banks is None else n_banks
-        arr = np.asarray(table)
-        if arr.shape == (0,):
-            arr = arr.astype(np.int32)                           # (an empty list has no dtype to speak of)
-        if arr.dtype.kind not in "iu":
-            raise ValueError("%s must hold integers (a bank per entry), got dtype %s" % (what, arr.dtype))
-        if arr.shape != (n,):
-            raise ValueError("%s must have shape (%d,), got %r" % (what, n, arr.shape))
-        if n and (arr.min() < 0 or arr.max() >= n_banks):
-            bad = np.flatnonzero((arr < 0) | (arr >= n_banks))
-            raise ValueError("%s[%d] = %d outside [0, n_banks = %d)" % (what, bad[0], arr[bad[0]], n_banks))
-        return np.ascontiguousarray(arr, dtype=np.int32)
-
     def _bank_index(self, bank, n_banks=None):
         n_banks = self.mb_banks if n_banks is None else n_banks
         if isinstance(bank, bool) or not isinstance(bank, (int, np.integer)) or not 0 <= bank < n_banks:
@@ -1339,66 +1343,20 @@ class FamiliarityEngine(object):
 
     def mbank_train_u8(self, planes, bank_of_view):
         """mb_train_u8 with view v depressing bank bank_of_view[v]: the views of all banks in the same launches."""
-        planes = self._ov_planes("mushroom", planes)
-        banks = self._bank_table(bank_of_view, planes.shape[0], "bank_of_view")
-        self._check(self._lib.dv_mbank_train_u8(self._ctx, N.u8ptr(planes), planes.shape[0], banks.ctypes.data_as(N._i32p)), "dv_mbank_train_u8")
+        self._bank_train_u8("mushroom", planes, bank_of_view)
 
     def mbank_train_from_poses(self, x, y, angle, bank_of_view, want_views=True, land_of_view=None):
         """mb_train_from_poses with view v depressing bank bank_of_view[v] (the routes of a grid, trained in one call); returns the
         views (uint8[n,h,w,3]) when want_views."""
-        x, y, angle = self._pose_arrays(x, y, angle)
-        banks = self._bank_table(bank_of_view, len(x), "bank_of_view")
-        lands = None if land_of_view is None else self._land_table(land_of_view, len(x), "land_of_view")
-        h, w = self.sensor_shape
-        views = np.empty((len(x), h, w, 3), dtype=np.uint8) if want_views else None
-        if lands is not None:
-            self._check_sense(self._lib.dv_lands_mbank_train_from_poses(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), len(x),
-                                                                        banks.ctypes.data_as(N._i32p), lands.ctypes.data_as(N._i32p),
-                                                                        N.u8ptr(views) if want_views else None),
-                              "dv_lands_mbank_train_from_poses")
-            return views
-        self._check_sense(self._lib.dv_mbank_train_from_poses(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angle), len(x),
-                                                              banks.ctypes.data_as(N._i32p), N.u8ptr(views) if want_views else None),
-                          "dv_mbank_train_from_poses")
-        return views
+        return self._bank_train_from_poses("mushroom", x, y, angle, bank_of_view, want_views, land_of_view)
 
     def mbank_step_batch_u8(self, planes, bank_of_member):
         """mb_step_batch_u8 with member i scored under bank bank_of_member[i] -> OneValueBatchResults."""
-        planes = N.as_u8(planes, "planes")
-        if planes.ndim != 4 or planes.shape[0] < 1 or planes.shape[1] < 1:
-            raise ValueError("planes must be uint8[n,A,h,w] with n, A >= 1, got shape %r" % (planes.shape,))
-        n, A = planes.shape[:2]
-        banks = self._bank_table(bank_of_member, n, "bank_of_member")
-        flat = self._ov_planes("mushroom", planes.reshape((n * A,) + planes.shape[2:]))
-        fam = np.empty((n, A), dtype=np.float64)
-        best = np.full(n, -1, dtype=np.int32)
-        self._check(self._lib.dv_mbank_step_u8(self._ctx, N.u8ptr(flat), n, A, banks.ctypes.data_as(N._i32p), N.f64ptr(fam),
-                                               best.ctypes.data_as(N._i32p)), "dv_mbank_step_u8")
-        return OneValueBatchResults(fam, best, np.zeros(n, dtype=np.uint32))
+        return self._bank_step_batch_u8("mushroom", planes, bank_of_member)
 
     def mbank_sense_step_batch(self, x, y, angles, bank_of_member, land_of_member=None):
         """mb_sense_step_batch with member i scored under bank bank_of_member[i] -> OneValueBatchResults: one enqueue and one wait."""
-        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
-        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
-        angles = np.ascontiguousarray(angles, dtype=np.float64)
-        if angles.ndim != 2 or len(x) != len(y) or angles.shape[0] != len(x) or angles.shape[0] < 1 or angles.shape[1] < 1:
-            raise ValueError("x[N], y[N] and angles[N, A] expected (N, A >= 1), got shapes %r, %r and %r" % (x.shape, y.shape, angles.shape))
-        n, A = angles.shape
-        banks = self._bank_table(bank_of_member, n, "bank_of_member")
-        lands = None if land_of_member is None else self._land_table(land_of_member, n, "land_of_member")
-        fam = np.empty((n, A), dtype=np.float64)
-        best = np.full(n, -1, dtype=np.int32)
-        flags = np.zeros(n, dtype=np.uint32)
-        if lands is not None:
-            self._check(self._lib.dv_lands_mbank_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A,
-                                                            banks.ctypes.data_as(N._i32p), lands.ctypes.data_as(N._i32p), N.f64ptr(fam),
-                                                            best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)),
-                        "dv_lands_mbank_sense_step")
-            return OneValueBatchResults(fam, best, flags)
-        self._check(self._lib.dv_mbank_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, banks.ctypes.data_as(N._i32p),
-                                                  N.f64ptr(fam), best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)),
-                    "dv_mbank_sense_step")
-        return OneValueBatchResults(fam, best, flags)
+        return self._bank_sense_step_batch("mushroom", x, y, angles, bank_of_member, land_of_member)
 
     def mbank_read_weights(self, bank=None):
         """uint8[n_kc] of one bank; bank=None: all of them, uint8[n_banks, n_kc]."""
@@ -1435,17 +1393,7 @@ class FamiliarityEngine(object):
         """`table` as int32[n] with every entry in [0, n_lands), or ValueError naming `what`: checked before any library call."""
         if not self.n_lands:
             raise N.EngineError("%s given, but the engine holds no landscape set: lands_set first (DV_ERR_STATE)" % what)
-        arr = np.asarray(table)
-        if arr.shape == (0,):
-            arr = arr.astype(np.int32)                           # (an empty list has no dtype to speak of)
-        if arr.dtype.kind not in "iu":
-            raise ValueError("%s must hold integers (a landscape per entry), got dtype %s" % (what, arr.dtype))
-        if arr.shape != (n,):
-            raise ValueError("%s must have shape (%d,), got %r" % (what, n, arr.shape))
-        if n and (arr.min() < 0 or arr.max() >= self.n_lands):
-            bad = np.flatnonzero((arr < 0) | (arr >= self.n_lands))
-            raise ValueError("%s[%d] = %d outside [0, n_lands = %d)" % (what, bad[0], arr[bad[0]], self.n_lands))
-        return np.ascontiguousarray(arr, dtype=np.int32)
+        return self._index_table(table, what, self.n_lands, "n_lands", n, "landscape")
 
     def lands_set(self, landscapes):
         """landscapes: a list of uint8[rows, cols, 3] HSV of any shapes and strides (copied), kept resident together beside the engine's
@@ -1575,7 +1523,7 @@ class FamiliarityEngine(object):
         """The tables of a step as (int32[n], float64[n], int32[n] or None), every entry in range -- checked before any library call."""
         if self.rviews_first is None:
             raise N.EngineError("no route views: rviews_set_u8 or rviews_set_from_poses first (DV_ERR_STATE)")
-        routes = self._bank_table(route_of_member, n, "route_of_member", len(self.rviews_first) - 1)
+        routes = self._index_table(route_of_member, "route_of_member", len(self.rviews_first) - 1, "n_banks", n, "bank")
         w = np.asarray(chem_weights)
         if w.dtype.kind not in "fiu":
             raise ValueError("chem_weights must hold numbers, got dtype %s" % w.dtype)
@@ -1637,15 +1585,6 @@ class FamiliarityEngine(object):
             raise ValueError("patches must be uint8[n, A, %d, %d, 3] with n, A >= 1, got shape %r" % (self.rviews_shape + (patches.shape,)))
         return patches
 
-    @staticmethod
-    def _rviews_poses(x, y, angles):
-        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
-        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
-        angles = np.ascontiguousarray(angles, dtype=np.float64)
-        if angles.ndim != 2 or len(x) != len(y) or angles.shape[0] != len(x) or angles.shape[0] < 1 or angles.shape[1] < 1:
-            raise ValueError("x[N], y[N] and angles[N, A] expected (N, A >= 1), got shapes %r, %r and %r" % (x.shape, y.shape, angles.shape))
-        return x, y, angles
-
     def rviews_step_u8(self, patches, route_of_member, chem_weights, exact=False):
         """patches: uint8[n, A, h, w, 3]; member i is scored against the views of route route_of_member[i] under chem_weights[i] ->
         RouteViewResults: angle_familiarity[n, A] (the reference's bits), angle_view[n, A] (the first view of the route that attains
@@ -1653,24 +1592,21 @@ class FamiliarityEngine(object):
         patches = self._rviews_patches(patches)
         n, A = patches.shape[:2]
         routes, w, _ = self._rviews_tables(n, route_of_member, chem_weights)
-        fam = np.empty((n, A), dtype=np.float64)
+        fam, best, flags = self._member_results(n, A)
         view = np.empty((n, A), dtype=np.int64)
-        best = np.full(n, -1, dtype=np.int32)
         self._check(self._lib.dv_rviews_step_u8(self._ctx, N.u8ptr(patches), n, A, routes.ctypes.data_as(N._i32p), N.f64ptr(w),
                                                 N.DV_RVIEWS_EXACT if exact else 0, N.f64ptr(fam), N.i64ptr(view), best.ctypes.data_as(N._i32p)),
                     "dv_rviews_step_u8")
-        return RouteViewResults(fam, view, best, np.zeros(n, dtype=np.uint32))
+        return RouteViewResults(fam, view, best, flags)
 
     def rviews_sense_step(self, x, y, angles, route_of_member, chem_weights, land_of_member=None, exact=False):
         """rviews_step_u8 with member i's patches sensed at (x[i], y[i]) along angles[i] (on landscape land_of_member[i] of the live
         set): one enqueue and one wait.  flags[i] carries DV_RES_SENSE_ERROR = 16 for a member whose footprint leaves its landscape."""
-        x, y, angles = self._rviews_poses(x, y, angles)
+        x, y, angles = self._member_poses(x, y, angles)
         n, A = angles.shape
         routes, w, lands = self._rviews_tables(n, route_of_member, chem_weights, land_of_member)
-        fam = np.empty((n, A), dtype=np.float64)
+        fam, best, flags = self._member_results(n, A)
         view = np.empty((n, A), dtype=np.int64)
-        best = np.full(n, -1, dtype=np.int32)
-        flags = np.zeros(n, dtype=np.uint32)
         self._check(self._lib.dv_rviews_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, routes.ctypes.data_as(N._i32p),
                                                    N.f64ptr(w), None if lands is None else lands.ctypes.data_as(N._i32p),
                                                    N.DV_RVIEWS_EXACT if exact else 0, N.f64ptr(fam), N.i64ptr(view),
@@ -1695,7 +1631,7 @@ class FamiliarityEngine(object):
     def rviews_scene(self, x, y, angles, route_of_member, chem_weights, land_of_member=None, want_flags=False):
         """rviews_scene_u8 with the patches sensed as rviews_sense_step senses them; a member whose footprint leaves its landscape gets
         a row of +inf and DV_RES_SENSE_ERROR = 16 in its flag.  want_flags: returns (rows, flags uint32[n])."""
-        x, y, angles = self._rviews_poses(x, y, angles)
+        x, y, angles = self._member_poses(x, y, angles)
         n, A = angles.shape
         routes, w, lands = self._rviews_tables(n, route_of_member, chem_weights, land_of_member)
         row0 = self._rviews_rows(routes)

@@ -169,6 +169,26 @@ def test_step_scores_every_member_under_its_own_bank(eng, lone, key):
                 same_bits(results[(n, A)].angle_familiarity[i], lone.infomax_score_u8(d["planes"][i]), (key, n, A, int(i), r))
 
 
+@pytest.mark.parametrize("key", ("5x3_f2", "40x1"))                                      # 15 pixels and 40: N % 4 != 0 beside N % 4 == 0
+def test_training_and_steps_take_turns_at_one_table_buffer(eng, lone, key):
+    """A training call's chains and a step's column blocks go to the same device buffer, and a table is sent only when its content is
+    not the one the buffer holds: train, step, train on the same tables, step on the same tables, then training twice running (the
+    second finds its own table there).  Every bank is its chain alone and every row the single model's score, bit for bit."""
+    b, d = HB.bank_data(key), HB.layout_data(key, 5, 13)
+    begin(eng, b)
+    for rounds in (1, 2, 4):
+        for _ in range(1 if rounds < 4 else 2):
+            eng.ibank_train_u8(b["views"], b["bank_of"].copy())
+        res = eng.ibank_step_batch_u8(d["planes"], d["banks"].copy())
+        assert eng.ibank_info()["views_trained"].tolist() == (rounds * b["counts"]).tolist()
+        for r in range(HB.R):
+            own = b["views"][b["bank_of"] == r]
+            same_bits(eng.ibank_read_weights(r), lone_chain(lone, b, np.concatenate([own] * rounds)), (key, rounds, r))
+            for i in np.flatnonzero(d["banks"] == r):                                    # (lone holds the chain's weights now)
+                same_bits(res.angle_familiarity[i], lone.infomax_score_u8(d["planes"][i]), (key, rounds, int(i), r))
+        assert res.best_idex.tolist() == np.argmax(res.angle_familiarity, axis=1).tolist()
+
+
 # ---- 3. sensed: three routes on the landscape of helpers_infomax.SENSED ----------------------------------------------------------------------
 def _sensed_agent():
     return H.sensed_agent(infomax_familiarity(**HB.SENSED_MODEL), True)

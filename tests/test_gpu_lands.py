@@ -342,6 +342,43 @@ def test_refused_tables_leave_the_set_the_banks_and_the_buffers_as_they_were(eng
     same_bits(after.angle_familiarity, before.angle_familiarity)
 
 
+@pytest.mark.parametrize("model", ("mushroom", "infomax"))
+def test_the_bank_table_and_the_landscape_table_change_apart(engines, model):
+    """A set of two landscapes, five members: a step, a step with the same land_of_member under other banks, then a step with the same
+    bank_of_member on other landscapes.  Each table is kept on the device by its own record (and Infomax sends the landscapes in bank
+    order, so its landscape table changes with the banks).  Every row is the one-landscape engine's of that landscape and bank."""
+    _, ones = engines("sq")
+    case = HL.step_case("sq", 5, 13)
+    xs, ys, angs = case["xs"], case["ys"], case["angs"]
+    if model == "mushroom":
+        begin, step = (lambda eng: mb_begin(eng, "sq", 2, False, HL.mb_banks("sq", 2)[2])), "mbank_sense_step_batch"
+    else:
+        begin, step = (lambda eng: im_begin(eng, "sq", 2, HL.im_banks("sq", 2)[1])), "ibank_sense_step_batch"
+    lands_a, lands_b = np.array([0, 1, 1, 0, 1], np.int32), np.array([1, 0, 1, 1, 0], np.int32)
+    banks_p, banks_q = np.array([1, 0, 2, 0, 1], np.int32), np.array([2, 2, 0, 1, 0], np.int32)
+    e = one_land_engine("sq", HL.lands()[0])
+    try:
+        e.lands_set(list(HL.lands()[:2]))
+        for eng in [e] + ones[:2]:
+            begin(eng)
+        rows = []
+        for lands, banks in ((lands_a, banks_p), (lands_a, banks_q), (lands_b, banks_q)):
+            want = np.empty((5, 13))
+            for l in range(2):
+                m = np.flatnonzero(lands == l)
+                want[m] = getattr(ones[l], step)(xs[m], ys[m], angs[m], banks[m]).angle_familiarity
+            res = getattr(e, step)(xs, ys, angs, banks.copy(), land_of_member=lands.copy())
+            assert not res.flags.any()
+            same_bits(res.angle_familiarity, want)
+            assert res.best_idex.tolist() == np.argmax(want, axis=1).tolist()
+            rows.append(want)
+        # a table left over from the step before would show: every member whose entry changed has another row
+        assert all(not np.array_equal(rows[0][i], rows[1][i]) for i in np.flatnonzero(banks_p != banks_q))
+        assert all(not np.array_equal(rows[1][i], rows[2][i]) for i in np.flatnonzero(lands_a != lands_b))
+    finally:
+        e.close()
+
+
 def test_the_one_landscape_calls_keep_their_bits_beside_a_set_and_after_it_is_cleared():
     name = "sq"
     plain = one_land_engine(name, HL.lands()[0])

@@ -71,6 +71,42 @@ def test_training_and_scoring_are_the_statement_bank_by_bank(eng, key):
     assert eng.mbank_info()["views_trained"].tolist() == (2 * b["counts"]).tolist()
 
 
+def test_the_devices_bank_table_follows_the_calls(eng):
+    """The device holds ONE bank table, for views and for members alike, and the host sends it only when its content changes.  The
+    smallest case (3 x 5 views, 37 cells), 4 members x 2 headings: a first table, the same again (nothing sent), another of the same
+    length, a training call whose bank_of_view equals it (the members' table serves the views), the step after it, five members (the
+    buffer grows), and back to the first table.  Every step is the statement under the weights as trained so far."""
+    b = HB.bank_data("5x3_k37")
+    h, w, args = b["h"], b["w"], (b["conn"], b["n_active"])
+    first, more = HI.route_views(141, 3, h, w), HI.route_views(142, 4, h, w)
+    planes = HI.route_views(143, 10, h, w).reshape(5, 2, h, w).copy()
+    planes[:3, 0], planes[3, 1], planes[4, 0] = first, more[1], more[3]                  # what some bank was trained on, beside what none was
+    T1, T2, T5 = np.array([0, 1, 2, 1], np.int32), np.array([2, 0, 1, 0], np.int32), np.array([1, 2, 0, 2, 1], np.int32)
+
+    def want(wts, table):
+        return np.stack([H.familiarity(wts[r], planes[i], *args) for i, r in enumerate(table)])
+
+    w0 = HB.train_banks(first, [0, 1, 2], *args, b["K"])
+    w1 = np.stack([H.train(w0[r], more[T2 == r], *args) for r in range(HB.R)])
+    assert (w1 != w0).any(axis=1).all()                                                  # the training call shows in every bank
+    rows = [want(w0, T1), want(w0, T2), want(w1, T2), want(w1, T1)]
+    assert all(not np.array_equal(rows[a], rows[c]) for a in range(4) for c in range(a + 1, 4))     # so does a stale table, or a stale bank
+
+    def step(table, wts):
+        res = eng.mbank_step_batch_u8(planes[:len(table)], table)
+        same(res, want(wts, table), np.argmax(want(wts, table), axis=1))
+
+    begin(eng, b, w0)                                                                    # (mb_begin: the device's table is gone)
+    step(T1, w0)
+    step(T1.copy(), w0)
+    step(T2, w0)
+    eng.mbank_train_u8(more, T2.copy())
+    assert np.array_equal(eng.mbank_read_weights(), w1)
+    step(T2, w1)
+    step(T5, w1)
+    step(T1, w1)
+
+
 # ---- 2. isolation ----------------------------------------------------------------------------------------------------------------------------
 def test_banks_do_not_touch_one_another(eng):
     b = HB.bank_data("16x16_k1043")

@@ -181,6 +181,32 @@ def test_bank_table_checks_come_before_any_library_call():
     assert e.infomax_banks == 1
 
 
+def test_a_banked_call_is_bounded_by_its_own_models_banks():
+    """The two models' banked calls share one host path; what tells them apart is whose bank count bounds the table.  With 2 Infomax
+    banks and 5 mushroom banks a table that names bank 4 reaches every dv_mbank_* symbol and no dv_ibank_* one, and with the counts
+    exchanged the reverse."""
+    h, w, A = 3, 5, 2
+    table = [0, 4]
+    views, xy = np.zeros((2, h, w), np.uint8), np.ones(2)
+    planes, angs = np.zeros((2, A, h, w), np.uint8), np.zeros((2, A))
+    ops = (("train_u8", "train_u8", (views,)), ("train_from_poses", "train_from_poses", (xy, xy, xy)),
+           ("step_batch_u8", "step_u8", (planes,)), ("sense_step_batch", "sense_step", (xy, xy, angs)))
+    for ibanks, mbanks in ((2, 5), (5, 2)):
+        lib = _Recorder()
+        e = _engine_without_a_device(lib, (h, w), ibanks)
+        e.mb_shape, e.mb_banks = (h, w), mbanks
+        for prefix, banks in (("ibank_", ibanks), ("mbank_", mbanks)):
+            for method, op, args in ops:
+                del lib.calls[:]
+                if banks == 5:
+                    getattr(e, prefix + method)(*args + (table,))
+                    assert lib.calls == [("dv_" + prefix + op, len(N.PROTOTYPES["dv_" + prefix + op][1]))], (prefix, method, lib.calls)
+                else:
+                    with pytest.raises(ValueError, match=r"\[1\] = 4 outside \[0, n_banks = 2\)"):
+                        getattr(e, prefix + method)(*args + (table,))
+                    assert lib.calls == [], (prefix, method, lib.calls)
+
+
 # ---- refusals --------------------------------------------------------------------------------------------------------------------------------
 LAND = synth.synth_landscape(3, 300, 4)
 

@@ -880,6 +880,27 @@ int dv_rviews_scene(dv_ctx *ctx, const double *x, const double *y, const double 
 int dv_rviews_info(dv_ctx *ctx, int *n_routes, int64_t *first, int *h, int *w, int64_t *bytes);
 int dv_rviews_clear(dv_ctx *ctx);
 
+/* ---- windowed steps on the route view store: perfect memory with a temporal window ---- */
+/*
+ * dv_rviews_step_u8 / dv_rviews_sense_step with member i scored against views [win_lo[i], win_hi[i]) of its own route only (sequence-
+ * aware matching: the views a few places behind and ahead of the one the member matched last).  angle_fam is the reference's value bit
+ * for bit of the most familiar view INSIDE the window, angle_view (may be NULL) the least route-relative index that attains it (so
+ * win_lo[i] <= angle_view < win_hi[i]), best_heading and member_flags as in the unwindowed calls: what the unwindowed step gives on
+ * the slice of the route alone, with win_lo[i] added to its view indices.  flags: DV_RVIEWS_EXACT as in dv_rviews_step_u8.
+ * Beside the unwindowed calls' checks, for every member 0 <= win_lo[i] < win_hi[i] <= the views of its route and
+ * win_hi[i] - win_lo[i] <= DV_RVWIN_MAX_VIEWS, else DV_ERR_INVALID names member i and its values; DV_ERR_STATE without a store.  A
+ * refused call changes nothing: the store, the tables the unwindowed calls keep on the device and their results stay as they were.
+ * A call is the sensing launch, one launch for the patches' byte planes, ONE scoring launch (no score buffer) and the deciding launch.
+ */
+#define DV_RVWIN_MAX_VIEWS 512
+int dv_rvwin_step_u8(dv_ctx *ctx, const uint8_t *patches, int n_agents, int n_headings, const int32_t *route_of_member,
+                     const double *chem_weights, const int32_t *win_lo, const int32_t *win_hi, uint32_t flags,
+                     double *angle_fam, int64_t *angle_view, int32_t *best_heading);
+int dv_rvwin_sense_step(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
+                        const int32_t *route_of_member, const double *chem_weights, const int32_t *land_of_member,
+                        const int32_t *win_lo, const int32_t *win_hi, uint32_t flags,
+                        double *angle_fam, int64_t *angle_view, int32_t *best_heading, uint32_t *member_flags);
+
 /* ---- measurement ------------------------------------------------------- */
 /* hipEvent pair on the context's stream around whatever is enqueued between the two calls. */
 int dv_timer_start(dv_ctx *ctx);

@@ -399,6 +399,9 @@ struct dv_ctx {
     size_t rv_prep_cap = 0;                   // bytes
     size_t rv_fast_cap = 0, rv_marked_cap = 0, rv_out_cap = 0, rv_err_cap = 0, rv_scene_cap = 0;   // bytes
     std::vector<unsigned char> rv_out_host;
+    MirroredTable rvw_tab;                    // a windowed call's tables (dejavu_rvwin.inl: weights, windows); never rv_tab
+    bool rvw_lds_opted = false;               // k_rvwin_score's LDS above 64 KB has been asked for
+    int rvw_split_env = 1;                    // DEJAVU_RVWIN_SPLIT: 0 = a window of one or two chunks is not cut by pixels (measurements)
 
     // measurement
     hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -512,6 +515,7 @@ extern "C" int dv_create(dv_ctx** out, int device_id) {
     env_int("DEJAVU_TUNE_ALL", c->tune_all_env, 0, 1);
     env_int("DEJAVU_SSD_MFMA", c->ssd_mfma_env, 0, 3);
     env_int("DEJAVU_RVIEWS_SLAB", c->rv_slab_env, 1, 32768);
+    env_int("DEJAVU_RVWIN_SPLIT", c->rvw_split_env, 0, 1);
     env_int("DEJAVU_CHAINS", c->chains_env, 1, 3);
     env_int("DEJAVU_CHAIN_ORDER", c->chain_order_env, -1, 2);
     env_int("DEJAVU_LC22", c->lc22_env, 0, 1);
@@ -3791,7 +3795,8 @@ extern "C" int dv_stream_read_gbps(dv_ctx* c, int64_t n_bytes, int iters, double
 #include "dejavu_lands.inl"     // dv_lands_*: landscape sets, a landscape per pose in the banked models' sensed calls (kernel and host side)
 #include "dejavu_sensors.inl"   // dv_sensors_*: a sensor configuration per landscape of the set (kernel and host side)
 #include "dejavu_rviews.inl"    // dv_rviews_*: route view store, perfect-memory members scored on their own routes (kernels and host side)
-#include "dejavu_infomax.inl"   // dv_infomax_*: the Infomax familiarity model (kernels and host side)
+#include "dejavu_rvwin.inl"     // dv_rvwin_*: windowed perfect memory on the route view store, scored in one fused launch (kernel and host side)
+#include "dejavu_infomax.inl"  // dv_infomax_*: the Infomax familiarity model (kernels and host side)
 #include "dejavu_mushroom.inl"  // dv_mb_*: the mushroom-body familiarity model (kernels and host side)
 #include "dejavu_path_routes.inl"   // dv_path_routes_*: the error / coverage metrics against several routes (host side)
 #include "dejavu_marks.inl"     // dv_marks_*: the coverage statistics of a result row, from the marks on the device (kernel and host side)

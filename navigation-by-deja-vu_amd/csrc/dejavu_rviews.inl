@@ -271,6 +271,7 @@ static void rviews_free(dv_ctx* c) {
     c->rv_fast_cap = c->rv_marked_cap = c->rv_out_cap = c->rv_err_cap = c->rv_scene_cap = c->rv_prep_cap = 0;
     c->rv_first.clear();
     table_free(c->rv_tab);
+    table_free(c->rvw_tab);
     c->rv_h = c->rv_w = 0;
     c->rv_lmax = 0;
     c->rv_bytes = 0;

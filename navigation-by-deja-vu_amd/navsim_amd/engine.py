@@ -1613,6 +1613,60 @@ class FamiliarityEngine(object):
                                                    best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)), "dv_rviews_sense_step")
         return RouteViewResults(fam, view, best, flags)
 
+    # -- windowed steps on the store: perfect memory with a temporal window (include/dejavu.h: dv_rvwin_*) ---------------------------
+    RVWIN_MAX_VIEWS = N.DV_RVWIN_MAX_VIEWS
+
+    def _rvwin_windows(self, routes, win_lo, win_hi):
+        """The windows of a step as two int32[n]: member i's [win_lo[i], win_hi[i]) holds 1 to RVWIN_MAX_VIEWS views of its route --
+        or ValueError naming the member.  Checked before any library call."""
+        n = len(routes)
+        out = []
+        for what, arr in (("win_lo", win_lo), ("win_hi", win_hi)):
+            arr = np.asarray(arr)
+            if arr.dtype.kind not in "iu":
+                raise ValueError("%s must hold integers (a view of the member's route per entry), got dtype %s" % (what, arr.dtype))
+            if arr.shape != (n,):
+                raise ValueError("%s must have shape (%d,), got %r" % (what, n, arr.shape))
+            out.append(arr.astype(np.int64))
+        lo, hi = out
+        lens = np.diff(self.rviews_first)[routes]
+        bad = np.flatnonzero((lo < 0) | (lo >= hi) | (hi > lens) | (hi - lo > self.RVWIN_MAX_VIEWS))
+        if len(bad):
+            i = int(bad[0])
+            raise ValueError("member %d: window [%d, %d) must hold 1 to %d views within its route %d of %d views"
+                             % (i, lo[i], hi[i], self.RVWIN_MAX_VIEWS, routes[i], lens[i]))
+        return np.ascontiguousarray(lo, dtype=np.int32), np.ascontiguousarray(hi, dtype=np.int32)
+
+    def rvwin_step_u8(self, patches, route_of_member, chem_weights, win_lo, win_hi, exact=False):
+        """rviews_step_u8 with member i scored against views [win_lo[i], win_hi[i]) of its route only (at most RVWIN_MAX_VIEWS), in one
+        fused scoring launch -> RouteViewResults: what the unwindowed step gives on that slice of the route, angle_view counted from
+        the route's first view."""
+        patches = self._rviews_patches(patches)
+        n, A = patches.shape[:2]
+        routes, w, _ = self._rviews_tables(n, route_of_member, chem_weights)
+        lo, hi = self._rvwin_windows(routes, win_lo, win_hi)
+        fam, best, flags = self._member_results(n, A)
+        view = np.empty((n, A), dtype=np.int64)
+        self._check(self._lib.dv_rvwin_step_u8(self._ctx, N.u8ptr(patches), n, A, routes.ctypes.data_as(N._i32p), N.f64ptr(w),
+                                               lo.ctypes.data_as(N._i32p), hi.ctypes.data_as(N._i32p), N.DV_RVIEWS_EXACT if exact else 0,
+                                               N.f64ptr(fam), N.i64ptr(view), best.ctypes.data_as(N._i32p)), "dv_rvwin_step_u8")
+        return RouteViewResults(fam, view, best, flags)
+
+    def rvwin_sense_step(self, x, y, angles, route_of_member, chem_weights, win_lo, win_hi, land_of_member=None, exact=False):
+        """rvwin_step_u8 with the patches sensed as rviews_sense_step senses them: one enqueue and one wait."""
+        x, y, angles = self._member_poses(x, y, angles)
+        n, A = angles.shape
+        routes, w, lands = self._rviews_tables(n, route_of_member, chem_weights, land_of_member)
+        lo, hi = self._rvwin_windows(routes, win_lo, win_hi)
+        fam, best, flags = self._member_results(n, A)
+        view = np.empty((n, A), dtype=np.int64)
+        self._check(self._lib.dv_rvwin_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, routes.ctypes.data_as(N._i32p),
+                                                  N.f64ptr(w), None if lands is None else lands.ctypes.data_as(N._i32p),
+                                                  lo.ctypes.data_as(N._i32p), hi.ctypes.data_as(N._i32p), N.DV_RVIEWS_EXACT if exact else 0,
+                                                  N.f64ptr(fam), N.i64ptr(view), best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)),
+                    "dv_rvwin_sense_step")
+        return RouteViewResults(fam, view, best, flags)
+
     def _rviews_rows(self, routes):
         lens = np.diff(self.rviews_first)[routes]
         return np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)

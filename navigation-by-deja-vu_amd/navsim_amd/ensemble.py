@@ -752,7 +752,14 @@ class SadsRouteEnsemble(_RouteEnsemble):
     the views of ITS OWN route under its own weight in ONE device call (dv_rviews_sense_step).  A member's angle_familiarity after a
     step is the reference's row bit for bit (what a lone agent made with exact=True gives at the same pose); its scene_familiarity is
     worked out when read (dv_rviews_scene), as NavEnsemble's members'.  A member's `memory_bank` is its route's place in the store.
-    Made by from_routes / from_routes_with / from_landscapes (see _RouteEnsemble); chem_weights: one per member, default the model's."""
+    Made by from_routes / from_routes_with / from_landscapes (see _RouteEnsemble); chem_weights: one per member, default the model's.
+
+    window=... makes members of perfect memory WITH A TEMPORAL WINDOW (sequence-aware matching): such a member carries `window` =
+    (behind, ahead) and `memory_index`, the view of its own route its last applied step matched (angle_view of the heading it chose; a
+    flagged or stopped member keeps its value).  With a memory_index m its step scores views [max(0, m - behind), min(len, m + ahead + 1))
+    only (dv_rvwin_sense_step: one fused scoring launch), with the bits of oracle.step on that slice; with memory_index None (the
+    first step without window_centres, or after relocalise()) it scores the whole route.  Its scene_familiarity is +inf outside the
+    window of its last step.  Members without a window beside it step as ever: at most two device calls a step."""
     _metric = None
     _takes = "agents of the perfect-memory model (familiarity_model=sads_familiarity(...))"
     _info_call = "rviews_info"               # dict(n_routes, first int64[R + 1], shape, bytes)
@@ -811,31 +818,137 @@ class SadsRouteEnsemble(_RouteEnsemble):
             raise ValueError("chem_weights must lie in [0, 1], got %r" % (w,))
         return w
 
+    WINDOW_MAX_VIEWS = 512                       # views of a member's window at most (FamiliarityEngine.RVWIN_MAX_VIEWS)
+
     @classmethod
-    def from_routes_with(cls, agent, routes, starts, metrics="host", chem_weights=None):
-        """_RouteEnsemble.from_routes_with, and chem_weights: member i scores under chem_weights[i] (None: the model's weight)."""
+    def _windows_arg(cls, window, window_centres, starts, route_lengths):
+        """`window` and `window_centres` of from_routes_with / from_landscapes as two lists with an entry per start: (behind, ahead) or
+        None (the member keeps its whole route), and the initial memory_index or None.  ValueError names the entry."""
+        n = len(starts)
+        if window is None:
+            if window_centres is not None:
+                raise ValueError("window_centres without window: a centre is the middle of a member's window")
+            return [None] * n, [None] * n
+
+        def pair(w, what):
+            if isinstance(w, (int, np.integer)) and not isinstance(w, bool):
+                w = (w, w)
+            ok = isinstance(w, (tuple, list)) and len(w) == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and v >= 0
+                                                                      for v in w)
+            if not ok:
+                raise ValueError("%s must be an int W >= 0 (W views behind and ahead) or a pair (behind, ahead) of such, got %r" % (what, w))
+            if w[0] + w[1] + 1 > cls.WINDOW_MAX_VIEWS:
+                raise ValueError("%s = %r: a window holds behind + ahead + 1 <= %d views" % (what, tuple(w), cls.WINDOW_MAX_VIEWS))
+            return (int(w[0]), int(w[1]))
+        if isinstance(window, list):                                # (a list: an entry per start; a pair is a tuple)
+            if len(window) != n:
+                raise ValueError("window holds %d entries for %d starts" % (len(window), n))
+            wins = [None if w is None else pair(w, "window[%d]" % i) for i, w in enumerate(window)]
+        else:
+            wins = [pair(window, "window")] * n
+        centres = [None] * n
+        if window_centres is not None:
+            centres = list(window_centres)
+            if len(centres) != n:
+                raise ValueError("window_centres holds %d entries for %d starts" % (len(centres), n))
+            for i, m in enumerate(centres):
+                if m is None:
+                    continue
+                if isinstance(m, bool) or not isinstance(m, (int, np.integer)):
+                    raise ValueError("window_centres[%d] must be None or a view index within the member's route, got %r" % (i, m))
+                if wins[i] is None:
+                    raise ValueError("window_centres[%d] = %d, but member %d has no window" % (i, m, i))
+                r = starts[i][0]
+                if isinstance(r, (int, np.integer)) and 0 <= r < len(route_lengths) and not 0 <= m < route_lengths[r]:
+                    raise ValueError("window_centres[%d] = %d outside [0, %d), the views of route %d" % (i, m, route_lengths[r], r))
+                centres[i] = int(m)
+        return wins, centres
+
+    def _set_windows(self, wins, centres):
+        for a, w, m in zip(self.agents, wins, centres):
+            a.window, a.memory_index = w, m
+
+    @classmethod
+    def from_routes_with(cls, agent, routes, starts, metrics="host", chem_weights=None, window=None, window_centres=None):
+        """_RouteEnsemble.from_routes_with, and chem_weights: member i scores under chem_weights[i] (None: the model's weight).
+        window: None (perfect memory: every step scores the whole route), or perfect memory with a temporal window -- an int W
+        (W views behind and W ahead of the view the member matched last), a pair (behind, ahead), or a list with such an entry, or
+        None, per start.  window_centres: a list with the initial `memory_index` (a view of the member's own route) or None per start;
+        a windowed member without one scores its whole route in its first step (see the class)."""
         starts = list(starts)
         w = cls._weights_arg(chem_weights, starts)
+        routes = list(routes)
+        wins, centres = cls._windows_arg(window, window_centres, starts, [len(r) for r in routes])
         ens = cls._from_routes(agent, routes, starts, metrics, None, None)
         if w is not None:
             ens._set_weights(w)
+        ens._set_windows(wins, centres)
         return ens
 
     @classmethod
-    def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host", chem_weights=None, sensors=None):
-        """_RouteEnsemble.from_landscapes, and chem_weights as from_routes_with takes them."""
+    def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host", chem_weights=None, sensors=None, window=None,
+                        window_centres=None):
+        """_RouteEnsemble.from_landscapes, and chem_weights, window and window_centres as from_routes_with takes them."""
         starts = list(starts)
         w = cls._weights_arg(chem_weights, starts)
+        routes = list(routes)
+        lengths = [len(rt[1]) if isinstance(rt, (tuple, list)) and len(rt) == 2 else 0 for rt in routes]
+        wins, centres = cls._windows_arg(window, window_centres, starts, lengths)
         ens = super(SadsRouteEnsemble, cls).from_landscapes(agent, landscapes, routes, starts, metrics=metrics, sensors=sensors)
         if w is not None:
             ens._set_weights(w)
+        ens._set_windows(wins, centres)
         return ens
 
-    def _device_step(self, idx, xs, ys, angs):
-        return self.engine.rviews_sense_step(xs, ys, angs, self._banks[idx], self._weights[idx],
-                                             land_of_member=None if self._lands is None else self._lands[idx])
+    def relocalise(self, members=None):
+        """The members `members` (indices; None: all) forget which view they matched last: memory_index = None, so that their next step
+        scores the whole route (global localisation) and centres their window anew."""
+        for i in (range(len(self.agents)) if members is None else members):
+            self.agents[i].memory_index = None
 
-    _note_scene = NavEnsemble._note_scene        # (a per-view minimum to work out when read, not the one-value models' fill)
+    def _window_of(self, agent):
+        """[lo, hi) of the coming step of a member with a window and a centre: clipped at both ends of its route; else None."""
+        w, m = getattr(agent, "window", None), getattr(agent, "memory_index", None)
+        if w is None or m is None:
+            return None
+        return max(0, m - w[0]), min(len(agent.training_path), m + w[1] + 1)
+
+    def _device_step(self, idx, xs, ys, angs):
+        """A member with a window and a centre goes to rvwin_sense_step, every other to rviews_sense_step: at most two device calls, and
+        with no window anywhere the one call there was.  The results come back as one RouteViewResults in the caller's order."""
+        from .engine import RouteViewResults
+        wins = [self._window_of(self.agents[i]) for i in idx]
+        lands = None if self._lands is None else self._lands[idx]
+        self._step_windows = {id(self.agents[i]): w for i, w in zip(idx, wins)}
+        ks = [k for k, w in enumerate(wins) if w is not None]
+        if not ks:
+            results = self.engine.rviews_sense_step(xs, ys, angs, self._banks[idx], self._weights[idx], land_of_member=lands)
+        else:
+            xs, ys, angs = np.asarray(xs, dtype=np.float64), np.asarray(ys, dtype=np.float64), np.asarray(angs, dtype=np.float64)
+            banks, weights = self._banks[idx], self._weights[idx]
+            rest = [k for k, w in enumerate(wins) if w is None]
+            parts = [(ks, self.engine.rvwin_sense_step(xs[ks], ys[ks], angs[ks], banks[ks], weights[ks], [wins[k][0] for k in ks],
+                                                       [wins[k][1] for k in ks], land_of_member=None if lands is None else lands[ks]))]
+            if rest:
+                parts.append((rest, self.engine.rviews_sense_step(xs[rest], ys[rest], angs[rest], banks[rest], weights[rest],
+                                                                  land_of_member=None if lands is None else lands[rest])))
+            n, A = angs.shape
+            results = RouteViewResults(np.empty((n, A)), np.empty((n, A), dtype=np.int64), np.empty(n, dtype=np.int32),
+                                       np.empty(n, dtype=np.uint32))
+            for at, r in parts:
+                results.angle_familiarity[at], results.angle_view[at] = r.angle_familiarity, r.angle_view
+                results.best_idex[at], results.flags[at] = r.best_idex, r.flags
+        # a member that is about to apply this step (every one that is not flagged) remembers the view its chosen heading matched
+        for k, i in enumerate(idx):
+            a = self.agents[i]
+            if getattr(a, "window", None) is not None and not results.flags[k] & 16:
+                a.memory_index = int(results.angle_view[k, results.best_idex[k]])
+        return results
+
+    def _note_scene(self, agent, x, y, headings, weight):
+        """NavEnsemble's note (a per-view minimum to work out when read, not the one-value models' fill), and the window of the step."""
+        NavEnsemble._note_scene(self, agent, x, y, headings, weight)
+        agent._scene_stale = (x, y, headings, weight, getattr(self, "_step_windows", {}).get(id(agent)))
 
     def _read_scene(self):
         todo = [a for a in self.agents if a._scene_stale is not None and a._scene_owner is self]
@@ -845,10 +958,13 @@ class SadsRouteEnsemble(_RouteEnsemble):
         lands = None if self._lands is None else [a.landscape_index for a in todo]
         rows = self.engine.rviews_scene([t[0] for t in st], [t[1] for t in st], np.stack([t[2] for t in st]), [a.memory_bank for a in todo],
                                         [t[3] for t in st], land_of_member=lands)
-        for a, row in zip(todo, rows):
+        for a, row, t in zip(todo, rows, st):
             a._scene_stale = None
             a._scene_owner = None
             a._scene_fam[:] = row
+            if len(t) > 4 and t[4] is not None:                    # a windowed step scored views [lo, hi) only: the others keep the
+                a._scene_fam[:t[4][0]] = np.inf                   # reference's value for views never scored (:287)
+                a._scene_fam[t[4][1]:] = np.inf
 
     def scene_familiarity(self):
         """A list of float64[len(route of member i)]: every member's scene_familiarity after its last step, as NavEnsemble gives it

@@ -2,7 +2,7 @@
 """Times a step of the route view store (dv_rviews_sense_step, navsim_amd.SadsRouteEnsemble) at a slice of the reference's grid and
 writes profiles/rviews_time.json.
 
-    python tools/rviews_time.py [--sides 32,64] [--calls 30] [--reps 5] [--blocks routes[,sensors]] [--out profiles/rviews_time.json]
+    python tools/rviews_time.py [--sides 32,64] [--calls 30] [--reps 5] [--blocks routes[,sensors][,window]] [--out profiles/rviews_time.json]
 
 Shape: 4 routes x 8 starts x 10 headings = 32 trials of 320 columns, views of side x side.  The routes have the grid's length:
 synth.sin_training_path with arclen = step_size / n_test_angles (scripts/run_experiment.py:207) on a 900 x 900 landscape, one curve
@@ -21,7 +21,15 @@ relative: the engines score in their default mode).  A window without a GPU fail
 Sensors block (--blocks sensors): dv_rviews_sense_step with a landscape per member on a set of 4 landscapes, without a sensor table,
 with a table of four entries equal to the engine's sensor and with a table of four different entries, in alternating windows of one
 process (tools/sensors_block.py, which states the shape and the figures); its rows are the file's "sensors".  A block that is not
-measured keeps its rows."""
+measured keeps its rows.
+
+Window block (--blocks window): the same slice with every member under a temporal window (dv_rvwin_sense_step: one fused scoring
+launch), WINDOWS = (50, 50) and (255, 256) centred on each pose's nearest route point, against the unwindowed dv_rviews_sense_step at
+the same poses, in alternating windows of one process: per side unwindowed_call_us and, per window, windowed_call_us /
+windowed_exact_call_us (hipEvent pairs), ensemble_step_wall_us (SadsRouteEnsemble(window=...).step_forward(fake=True), wall clock) and
+the two ratios; uncut_101_views_call_us is the 101-view call with the kernel's pixel cut switched off (DEJAVU_RVWIN_SPLIT=0).  The fast
+and exact forms, and the cut and uncut kernels, are checked to agree on their bits before anything is timed.  The block is the file's
+"window" key; measured alone it leaves every other key as it was."""
 import argparse
 import json
 import os
@@ -132,13 +140,103 @@ def measure(side, n_calls, reps):
     return out
 
 
+WINDOWS = ((50, 50), (255, 256))
+
+
+def measure_window(side, n_calls, reps):
+    """The window block's row of one side: the routed call without a window against dv_rvwin_sense_step under WINDOWS, at the same
+    poses, every window centred on its pose's nearest route point."""
+    import navsim_amd
+    from navsim_amd import synth
+    land = synth.synth_landscape(3, LAND, 4)
+    routes = [synth.sin_training_path(c, 0.2 * LAND, 0.6 * LAND, arclen=STEP_SIZE / HEADINGS) for c in CURVES]
+    starts = starts_of(routes)
+    centres = [int(np.argmin(np.linalg.norm(routes[r] - np.array(pos), axis=1))) for r, pos, _ in starts]
+
+    def ensemble(window, split=True):
+        if not split:
+            os.environ["DEJAVU_RVWIN_SPLIT"] = "0"                # (read when the agent's engine is created)
+        try:
+            a = navsim_amd.NavBySceneFamiliarity(land, (side, side), STEP_SIZE, n_test_angles=HEADINGS, track_scene_familiarity=False,
+                                                 familiarity_model=navsim_amd.sads_familiarity(CHEM_WEIGHT))
+        finally:
+            os.environ.pop("DEJAVU_RVWIN_SPLIT", None)
+        return navsim_amd.SadsRouteEnsemble.from_routes_with(a, routes, starts, metrics="device", window=window,
+                                                             window_centres=None if window is None else centres)
+
+    plain = ensemble(None)
+    windowed = [ensemble(w) for w in WINDOWS]
+    uncut = ensemble(WINDOWS[0], split=False)
+    n = len(starts)
+    xs = np.array([p[0] for _, p, _ in starts])
+    ys = np.array([p[1] for _, p, _ in starts])
+    angs = (np.array([a for _, _, a in starts])[:, None] + plain.agents[0].angle_offsets[None, :]) % (2 * np.pi)
+    route_of = np.array([r for r, _, _ in starts], dtype=np.int32)
+    weights = np.full(n, CHEM_WEIGHT)
+    lens = np.array([len(routes[r]) for r in route_of])
+    bounds = [(np.maximum(0, np.array(centres) - b), np.minimum(lens, np.array(centres) + a + 1)) for b, a in WINDOWS]
+
+    def call(eng, k=None, exact=False):
+        eng.timer_start()
+        for _ in range(n_calls):
+            if k is None:
+                res = eng.rviews_sense_step(xs, ys, angs, route_of, weights, exact=exact)
+            else:
+                res = eng.rvwin_sense_step(xs, ys, angs, route_of, weights, bounds[k][0], bounds[k][1], exact=exact)
+        return eng.timer_stop() * 1e3 / n_calls, res
+
+    def wall(ens):
+        w0 = time.perf_counter()
+        for _ in range(n_calls):
+            ens.step_forward(fake=True)
+        return (time.perf_counter() - w0) * 1e6 / n_calls
+
+    call(plain.engine)                                            # warm-up of every form, and the forms agree
+    for k, e in enumerate(windowed):
+        _, fast = call(e.engine, k)
+        _, exact = call(e.engine, k, exact=True)
+        assert np.array_equal(fast.angle_familiarity.view(np.uint64), exact.angle_familiarity.view(np.uint64))
+        assert np.array_equal(fast.angle_view, exact.angle_view) and np.array_equal(fast.best_idex, exact.best_idex) and not fast.flags.any()
+        assert (fast.angle_view >= bounds[k][0][:, None]).all() and (fast.angle_view < bounds[k][1][:, None]).all()
+    _, cut = call(windowed[0].engine, 0)
+    _, whole = call(uncut.engine, 0)
+    assert np.array_equal(cut.angle_familiarity.view(np.uint64), whole.angle_familiarity.view(np.uint64))
+    for e in [plain, uncut] + windowed:
+        wall(e)
+    t_plain, t_uncut, w_plain = [], [], []
+    t_win, t_exact, w_win = [[] for _ in WINDOWS], [[] for _ in WINDOWS], [[] for _ in WINDOWS]
+    for _ in range(reps):                                         # alternating windows
+        t_plain.append(call(plain.engine)[0])
+        for k, e in enumerate(windowed):
+            t_win[k].append(call(e.engine, k)[0])
+            t_exact[k].append(call(e.engine, k, exact=True)[0])
+        t_uncut.append(call(uncut.engine, 0)[0])
+        w_plain.append(wall(plain))
+        for k, e in enumerate(windowed):
+            w_win[k].append(wall(e))
+    rows = []
+    for k, (b, a) in enumerate(WINDOWS):
+        rows.append(dict(behind=b, ahead=a, views=int((bounds[k][1] - bounds[k][0]).max()), windowed_call_us=spread(t_win[k]),
+                         windowed_exact_call_us=spread(t_exact[k]), ensemble_step_wall_us=spread(w_win[k]),
+                         unwindowed_over_windowed_call=round(float(np.median(t_plain) / np.median(t_win[k])), 3),
+                         unwindowed_over_windowed_wall=round(float(np.median(w_plain) / np.median(w_win[k])), 3),
+                         members_running=len(windowed[k].active)))
+    out = dict(side=side, routes=len(routes), route_views=[len(r) for r in routes], members=n, headings=HEADINGS, columns=n * HEADINGS,
+               chem_weight=CHEM_WEIGHT, calls_per_window=n_calls, windows=reps, column_block=4, views_per_wave_chunk=64,
+               unwindowed_call_us=spread(t_plain), unwindowed_ensemble_step_wall_us=spread(w_plain), members_running=len(plain.active),
+               windowed=rows, uncut_101_views_call_us=spread(t_uncut))
+    for e in [plain, uncut] + windowed:
+        e.engine.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sides", default="32,64")
     ap.add_argument("--calls", type=int, default=30)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rviews_time.json"))
-    ap.add_argument("--blocks", default="routes", help="which blocks to measure: routes (the routed step against four engines), sensors")
+    ap.add_argument("--blocks", default="routes", help="which blocks to measure: routes (the routed step against four engines), sensors, window")
     ap.add_argument("--limit", type=int, default=240, help="seconds allowed to the sensors block's GPU child")
     args = ap.parse_args()
     blocks = args.blocks.split(",")
@@ -157,6 +255,11 @@ def main():
     import torch                                                  # (after the windows: only to ask the device its name)
     doc = dict(tool="tools/rviews_time.py", device=torch.cuda.get_device_name(0), step_form="step_forward(fake=True)", note="medians of alternating windows in one process; wall-clock figures "
                "include the host's share of a step", sizes=rows, sensors=sensors)
+    if "window" in blocks:                                        # a key of its own: the keys that were there stay as they were
+        doc = dict(doc if ("routes" in blocks or "sensors" in blocks or not kept) else kept, window=dict(device=torch.cuda.get_device_name(0), windows=[list(w) for w in WINDOWS],
+                                            sizes=[measure_window(int(s), args.calls, args.reps) for s in args.sides.split(",")]))
+    elif "window" in kept:
+        doc["window"] = kept["window"]
     with open(args.out, "w") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")

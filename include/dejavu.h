@@ -49,6 +49,8 @@ enum {
 #define DV_RES_SENSE_ERROR 16u     /* batched calls: THIS agent's sensor footprint reached past the end of the landscape (the
                                       reference's IndexError for that trial); its other fields are meaningless.  The
                                       single-agent calls return DV_ERR_INDEX instead. */
+#define DV_RES_RELOCALISED 32u     /* dv_rvreloc_*: THIS member's windowed familiarity lay below its threshold; its row is the
+                                      whole-route step's, not the window's */
 
 /*
  * Result of one step (replaces NavBySceneFamiliarity.py:313-316).
@@ -900,6 +902,31 @@ int dv_rvwin_sense_step(dv_ctx *ctx, const double *x, const double *y, const dou
                         const int32_t *route_of_member, const double *chem_weights, const int32_t *land_of_member,
                         const int32_t *win_lo, const int32_t *win_hi, uint32_t flags,
                         double *angle_fam, int64_t *angle_view, int32_t *best_heading, uint32_t *member_flags);
+
+/*
+ * Re-localisation inside the windowed step.  dv_rvreloc_step_u8 / dv_rvreloc_sense_step are dv_rvwin_step_u8 / dv_rvwin_sense_step
+ * with a threshold per member, reloc_below (double[n_agents], in the unit of angle_fam, so at most h * w), behind win_hi; member_flags
+ * (uint32[n_agents], not NULL) is an output of both.  THE RULE: once the windowed scores of the step exist, a member that is not
+ * flagged DV_RES_SENSE_ERROR is LOST iff max_a angle_fam_window[a] < reloc_below[i] -- a strict < on the doubles as they are, so -inf
+ * never triggers and +inf always does.  A lost member's row (angle_fam, angle_view, its part in best_heading) is the whole-route step's
+ * bit for bit, what dv_rviews_step_u8 gives at the same patches (more than 256 candidates included); nothing of the windowed attempt
+ * remains in it, and its flag word carries DV_RES_RELOCALISED.  Every other member's row is dv_rvwin_*'s bit for bit.
+ * Checks: the windowed calls', and DV_ERR_INVALID naming the member for a NaN in reloc_below (and for n_headings above 32768); all
+ * of them run before anything reaches the device, and a refused call changes nothing (see dv_rvwin_*).
+ * A call is ONE enqueue and ONE wait, and the host reads nothing in between: the sensing launch, the byte planes, the windowed scoring
+ * launch, then per group of consecutive members whose columns fit the score buffer of the unwindowed calls (64 MiB, or
+ * DEJAVU_RVIEWS_SLAB columns) a launch that applies the rule and writes the lost columns' plan on the device and the unwindowed
+ * calls' scoring launches on that plan (grids sized for "every member lost"; a workgroup past the device's counts returns at once),
+ * the deciding launch and one copy out.  DV_RVIEWS_EXACT: the rule reads the exact windowed values and the lost columns take the
+ * exact pass.
+ */
+int dv_rvreloc_step_u8(dv_ctx *ctx, const uint8_t *patches, int n_agents, int n_headings, const int32_t *route_of_member,
+                       const double *chem_weights, const int32_t *win_lo, const int32_t *win_hi, const double *reloc_below,
+                       uint32_t flags, double *angle_fam, int64_t *angle_view, int32_t *best_heading, uint32_t *member_flags);
+int dv_rvreloc_sense_step(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
+                          const int32_t *route_of_member, const double *chem_weights, const int32_t *land_of_member,
+                          const int32_t *win_lo, const int32_t *win_hi, const double *reloc_below, uint32_t flags,
+                          double *angle_fam, int64_t *angle_view, int32_t *best_heading, uint32_t *member_flags);
 
 /* ---- measurement ------------------------------------------------------- */
 /* hipEvent pair on the context's stream around whatever is enqueued between the two calls. */

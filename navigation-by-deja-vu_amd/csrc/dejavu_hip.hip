@@ -400,6 +400,8 @@ struct dv_ctx {
     size_t rv_fast_cap = 0, rv_marked_cap = 0, rv_out_cap = 0, rv_err_cap = 0, rv_scene_cap = 0;   // bytes
     std::vector<unsigned char> rv_out_host;
     MirroredTable rvw_tab;                    // a windowed call's tables (dejavu_rvwin.inl: weights, windows); never rv_tab
+    unsigned char* rvw_plan = nullptr;        // what the device writes of a relocalising call's plan (dejavu_rvreloc.inl)
+    size_t rvw_plan_cap = 0;                  // bytes
     bool rvw_lds_opted = false;               // k_rvwin_score's LDS above 64 KB has been asked for
     int rvw_split_env = 1;                    // DEJAVU_RVWIN_SPLIT: 0 = a window of one or two chunks is not cut by pixels (measurements)
 
@@ -3795,6 +3797,7 @@ extern "C" int dv_stream_read_gbps(dv_ctx* c, int64_t n_bytes, int iters, double
 #include "dejavu_lands.inl"     // dv_lands_*: landscape sets, a landscape per pose in the banked models' sensed calls (kernel and host side)
 #include "dejavu_sensors.inl"   // dv_sensors_*: a sensor configuration per landscape of the set (kernel and host side)
 #include "dejavu_rviews.inl"    // dv_rviews_*: route view store, perfect-memory members scored on their own routes (kernels and host side)
+#include "dejavu_rvreloc.inl"   // k_rvreloc_*: lost windowed members re-localise inside the step, planned and scored on the device (kernels and host side)
 #include "dejavu_rvwin.inl"     // dv_rvwin_*: windowed perfect memory on the route view store, scored in one fused launch (kernel and host side)
 #include "dejavu_infomax.inl"  // dv_infomax_*: the Infomax familiarity model (kernels and host side)
 #include "dejavu_mushroom.inl"  // dv_mb_*: the mushroom-body familiarity model (kernels and host side)

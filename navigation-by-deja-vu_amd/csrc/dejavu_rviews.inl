@@ -66,13 +66,13 @@ __global__ void k_rv_prep(const unsigned char* __restrict__ patches, long long C
 
 // Workgroup = (vpw groups of 64 views of the tile's route) x (one tile): with T the call's tile width, the 4 waves are T / 4 column
 // blocks times vpw = 4 / (T / 4) view groups (T = 16: 1 group, 8: 2, 4: 4; T = 12: 1 group and an idle wave).  A lane holds one
-// view's dwords and the two sums of its wave's kRvBlock columns.
-__global__ void __launch_bounds__(256)
-k_rv_score(const unsigned* __restrict__ planes, const RvRoute* __restrict__ routes, const RvTile* __restrict__ tiles,
-           const int* __restrict__ col_of, const unsigned* __restrict__ prepped, const AgentW* __restrict__ wts, int A, int P, int Pw, int T,
-           double* __restrict__ fast, int slab_s0, long long lstride) {
+// view's dwords and the two sums of its wave's kRvBlock columns.  (The body is k_rv_score's and, with a plan the device wrote,
+// k_rvreloc_score's of dejavu_rvreloc.inl: one statement of the sums.)
+__device__ __forceinline__ void rv_score_tile(const unsigned* __restrict__ planes, const RvRoute* __restrict__ routes, const RvTile tile,
+                                              const int* __restrict__ col_of, const unsigned* __restrict__ prepped,
+                                              const AgentW* __restrict__ wts, int A, int P, int Pw, int T, double* __restrict__ fast, int slab_s0,
+                                              long long lstride) {
     extern __shared__ unsigned rv_lds[];                              // [round4(n)][3][Pw]
-    const RvTile tile = tiles[blockIdx.y];
     const RvRoute rt = routes[tile.route];
     const int ncb = T / kRvBlock, vpw = 4 / ncb > 0 ? 4 / ncb : 1;
     if ((long long)blockIdx.x * vpw * 64 >= rt.len) return;           // (the whole workgroup)
@@ -120,6 +120,13 @@ k_rv_score(const unsigned* __restrict__ planes, const RvRoute* __restrict__ rout
     }
 }
 
+__global__ void __launch_bounds__(256)
+k_rv_score(const unsigned* __restrict__ planes, const RvRoute* __restrict__ routes, const RvTile* __restrict__ tiles,
+           const int* __restrict__ col_of, const unsigned* __restrict__ prepped, const AgentW* __restrict__ wts, int A, int P, int Pw, int T,
+           double* __restrict__ fast, int slab_s0, long long lstride) {
+    rv_score_tile(planes, routes, tiles[blockIdx.y], col_of, prepped, wts, A, P, Pw, T, fast, slab_s0, lstride);
+}
+
 // The reference's value of one (patch, view): per-pixel terms in its operation order, added in pixel order (util.pyx:44-73).
 __device__ __forceinline__ double rv_exact_view(const unsigned* __restrict__ base, const unsigned char* __restrict__ patch, int P, int Pw,
                                                 double cw, double wv) {
@@ -144,11 +151,13 @@ __device__ __forceinline__ const unsigned* rv_view_base(const unsigned* __restri
     return planes + (rt.g0 + (f >> 6)) * 3 * Pw * 64 + (f & 63);
 }
 
-// Every view of the marked columns of a slab (force: of all its columns); grid = (256-view chunks, the slab's columns).
-__global__ void __launch_bounds__(256)
-k_rv_exact(const unsigned* __restrict__ planes, const RvRoute* __restrict__ routes, const int* __restrict__ col_of,
-           const int* __restrict__ route_of_member, const unsigned char* __restrict__ patches, const AgentW* __restrict__ wts, int A, int P,
-           int Pw, const int* __restrict__ marked, int force, double* __restrict__ fast, int slab_s0, long long lstride) {
+// Every view of the marked columns of a slab (force: of all its columns); grid = (256-view chunks, the slab's columns).  (The body is
+// k_rv_exact's and k_rvreloc_exact's.)
+__device__ __forceinline__ void rv_exact_column(const unsigned* __restrict__ planes, const RvRoute* __restrict__ routes,
+                                                const int* __restrict__ col_of, const int* __restrict__ route_of_member,
+                                                const unsigned char* __restrict__ patches, const AgentW* __restrict__ wts, int A, int P, int Pw,
+                                                const int* __restrict__ marked, int force, double* __restrict__ fast, int slab_s0,
+                                                long long lstride) {
     const int s = slab_s0 + blockIdx.y;
     if (!force && !marked[s]) return;
     const int oc = col_of[s];
@@ -157,6 +166,13 @@ k_rv_exact(const unsigned* __restrict__ planes, const RvRoute* __restrict__ rout
     if (f >= rt.len) return;
     const AgentW w = wts[oc / A];
     fast[(long long)blockIdx.y * lstride + f] = rv_exact_view(rv_view_base(planes, rt, f, Pw), patches + (long long)oc * P * 3, P, Pw, w.cw, w.wv);
+}
+
+__global__ void __launch_bounds__(256)
+k_rv_exact(const unsigned* __restrict__ planes, const RvRoute* __restrict__ routes, const int* __restrict__ col_of,
+           const int* __restrict__ route_of_member, const unsigned char* __restrict__ patches, const AgentW* __restrict__ wts, int A, int P,
+           int Pw, const int* __restrict__ marked, int force, double* __restrict__ fast, int slab_s0, long long lstride) {
+    rv_exact_column(planes, routes, col_of, route_of_member, patches, wts, A, P, Pw, marked, force, fast, slab_s0, lstride);
 }
 
 // The largest of v over the workgroup's 256 threads and the least idx among the threads that hold it (red, redi: 256 entries each).
@@ -178,17 +194,15 @@ __device__ __forceinline__ void rv_block_max(double& v, long long& idx, double* 
 }
 
 // EXACT = 0: the rows hold fast scores (see the head of the file).  EXACT = 1: the rows of the marked columns (force: of all) hold the
-// reference's values: the maximum and its first view.
+// reference's values: the maximum and its first view.  (The body is k_rv_pick's and k_rvreloc_pick's; red, redi, cand, n_cand: the
+// kernel's static LDS.)
 template <int EXACT>
-__global__ void __launch_bounds__(256)
-k_rv_pick(const unsigned* __restrict__ planes, const RvRoute* __restrict__ routes, const int* __restrict__ col_of,
-          const int* __restrict__ route_of_member, const unsigned char* __restrict__ patches, const AgentW* __restrict__ wts, int A, int P, int Pw,
-          const double* __restrict__ fast, int slab_s0, long long lstride, double delta, int* __restrict__ marked, int force,
-          double* __restrict__ out_fam, long long* __restrict__ out_view) {
-    __shared__ double red[256];
-    __shared__ long long redi[256];
-    __shared__ int cand[kRvCandCap];
-    __shared__ int n_cand;
+__device__ __forceinline__ void rv_pick_column(const unsigned* __restrict__ planes, const RvRoute* __restrict__ routes,
+                                               const int* __restrict__ col_of, const int* __restrict__ route_of_member,
+                                               const unsigned char* __restrict__ patches, const AgentW* __restrict__ wts, int A, int P, int Pw,
+                                               const double* __restrict__ fast, int slab_s0, long long lstride, double delta,
+                                               int* __restrict__ marked, int force, double* __restrict__ out_fam, long long* __restrict__ out_view,
+                                               double* red, long long* redi, int* cand, int& n_cand) {
     const int s = slab_s0 + blockIdx.x;
     if (EXACT && !force && !marked[s]) return;
     const int oc = col_of[s];
@@ -229,9 +243,24 @@ k_rv_pick(const unsigned* __restrict__ planes, const RvRoute* __restrict__ route
     if (threadIdx.x == 0) { marked[s] = 0; out_fam[oc] = v; out_view[oc] = vf; }
 }
 
-// A member's first maximum over its A columns (np.argmax) and its flag: err is a word per column (nullptr: patches were uploaded).
-__global__ void k_rv_best(const double* __restrict__ fam, const int* __restrict__ err, int n, int A, int* __restrict__ best,
-                          unsigned* __restrict__ flags) {
+template <int EXACT>
+__global__ void __launch_bounds__(256)
+k_rv_pick(const unsigned* __restrict__ planes, const RvRoute* __restrict__ routes, const int* __restrict__ col_of,
+          const int* __restrict__ route_of_member, const unsigned char* __restrict__ patches, const AgentW* __restrict__ wts, int A, int P, int Pw,
+          const double* __restrict__ fast, int slab_s0, long long lstride, double delta, int* __restrict__ marked, int force,
+          double* __restrict__ out_fam, long long* __restrict__ out_view) {
+    __shared__ double red[256];
+    __shared__ long long redi[256];
+    __shared__ int cand[kRvCandCap];
+    __shared__ int n_cand;
+    rv_pick_column<EXACT>(planes, routes, col_of, route_of_member, patches, wts, A, P, Pw, fast, slab_s0, lstride, delta, marked, force, out_fam,
+                          out_view, red, redi, cand, n_cand);
+}
+
+// A member's first maximum over its A columns (np.argmax) and its flags: err is a word per column (nullptr: patches were uploaded),
+// lost a word per member (nullptr but in a relocalising call: dejavu_rvreloc.inl).
+__global__ void k_rv_best(const double* __restrict__ fam, const int* __restrict__ err, const int* __restrict__ lost, int n, int A,
+                          int* __restrict__ best, unsigned* __restrict__ flags) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     int b = 0, off = 0;
@@ -240,7 +269,7 @@ __global__ void k_rv_best(const double* __restrict__ fam, const int* __restrict_
         if (err && err[(long long)i * A + a]) off = 1;
     }
     best[i] = off ? -1 : b;
-    flags[i] = off ? 16u : 0u;                                         // DV_RES_SENSE_ERROR
+    flags[i] = off ? 16u : lost && lost[i] ? 32u : 0u;                 // DV_RES_SENSE_ERROR, DV_RES_RELOCALISED
 }
 
 // scene_familiarity: per view of the member's route the least exact value over the member's A headings (strict <, from +inf: :287,
@@ -267,7 +296,8 @@ k_rv_scene(const unsigned* __restrict__ planes, const RvRoute* __restrict__ rout
 
 static void rviews_free(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-    F(c->rv_planes); F(c->rv_routes); F(c->rv_fast); F(c->rv_marked); F(c->rv_out); F(c->rv_err); F(c->rv_scene); F(c->rv_prep);
+    F(c->rv_planes); F(c->rv_routes); F(c->rv_fast); F(c->rv_marked); F(c->rv_out); F(c->rv_err); F(c->rv_scene); F(c->rv_prep); F(c->rvw_plan);
+    c->rvw_plan_cap = 0;
     c->rv_fast_cap = c->rv_marked_cap = c->rv_out_cap = c->rv_err_cap = c->rv_scene_cap = c->rv_prep_cap = 0;
     c->rv_first.clear();
     table_free(c->rv_tab);
@@ -556,7 +586,7 @@ static int rviews_run(dv_ctx* c, const RvPlan& p, bool exact, const int* err, do
                            Pw, c->rv_fast, s0, p.lstride, c->rv_delta, c->rv_marked, exact ? 1 : 0, d_fam, d_view);
         HIP_TRY(c, hipGetLastError());
     }
-    hipLaunchKernelGGL(k_rv_best, dim3((unsigned)((p.N + 255) / 256)), dim3(256), 0, c->stream, d_fam, err, p.N, A, d_best, d_flags);
+    hipLaunchKernelGGL(k_rv_best, dim3((unsigned)((p.N + 255) / 256)), dim3(256), 0, c->stream, d_fam, err, nullptr, p.N, A, d_best, d_flags);
     HIP_TRY(c, hipGetLastError());
     c->rv_out_host.resize(out_bytes);
     HIP_TRY(c, hipMemcpyAsync(c->rv_out_host.data(), c->rv_out, out_bytes, hipMemcpyDeviceToHost, c->stream));

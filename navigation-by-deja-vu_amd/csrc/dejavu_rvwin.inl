@@ -2,7 +2,8 @@
 // against views [win_lo[i], win_hi[i]) of ITS OWN route only, at most DV_RVWIN_MAX_VIEWS of them, and the whole of it -- integer sums,
 // fast scores, candidates, the reference's sequential doubles, the first maximum -- is ONE launch whose scores never leave LDS.  The
 // store, its layout, the sensing (rviews_sense_members), the patches' byte planes (k_rv_prep), the per-view sums (k_rv_score's own),
-// the exact value (rv_exact_view) and the deciding launch (k_rv_best) are dejavu_rviews.inl's; nothing there changes.
+// the exact value (rv_exact_view) and the deciding launch (k_rv_best) are dejavu_rviews.inl's; nothing there changes.  The same calls with
+// a threshold per member (dv_rvreloc_*, at the end of this file) add dejavu_rvreloc.inl's chain between the scoring and the deciding launch.
 //
 //   k_rvwin_score  workgroup = (a block of kRvBlock columns, one member).  The block's patches go to LDS as byte planes.  A wave takes
 //                  64-view chunks of the member's window in turn (wave w: chunks w, w + 4, ...), a lane one view f = lo + j -- the
@@ -229,10 +230,11 @@ static int rvwin_check(dv_ctx* c, const char* who, int N, int A, const int32_t* 
 
 // Score the N * A columns whose patches lie in d_sense, member i against its window; err: a word per column, or nullptr.  The call's
 // tables travel in one copy to a table of their own (rvw_tab): the unwindowed calls' rv_tab, and what its mirror says of the device,
-// stay as they were.
+// stay as they were.  reloc_below (nullptr but in dv_rvreloc_*): the members' thresholds; the call's tables grow by dejavu_rvreloc.inl's,
+// and its chain by the plan and the whole-route scoring of the lost members, between the windowed scoring and the deciding launch.
 static int rvwin_run(dv_ctx* c, int N, int A, const int32_t* route_of_member, const double* chem_weights, const int32_t* win_lo,
                      const int32_t* win_hi, bool exact, const int* err, double* angle_fam, int64_t* angle_view, int32_t* best_heading,
-                     uint32_t* member_flags) {
+                     uint32_t* member_flags, const double* reloc_below = nullptr) {
     const int P = c->rv_h * c->rv_w, Pw = (P + 3) / 4, C = N * A;
     const size_t off_win = (size_t)N * sizeof(AgentW);
     std::vector<unsigned char> tab(off_win + (size_t)N * sizeof(RvWin), 0);
@@ -242,7 +244,10 @@ static int rvwin_run(dv_ctx* c, int N, int A, const int32_t* route_of_member, co
         w[i] = AgentW{chem_weights[i], 0.5 * chem_weights[i], 1 - chem_weights[i], 0.0};   // as rviews_plan computes its own
         win[i] = RvWin{route_of_member[i], win_lo[i], win_hi[i], 0};
     }
+    RvReloc reloc;
+    if (reloc_below) rvreloc_tables(c, reloc, N, A, route_of_member, reloc_below, tab);
     int rc = table_upload(c, c->rvw_tab, tab.data(), tab.size());
+    if (!rc && reloc_below) rc = rvreloc_buffers(c, reloc);
     const size_t out_bytes = (size_t)C * 16 + (size_t)N * 8;
     if (!rc) rc = grow_buffer(c, c->rv_out, c->rv_out_cap, out_bytes);
     if (!rc && !exact) rc = grow_buffer(c, c->rv_prep, c->rv_prep_cap, (size_t)C * 3 * Pw * 4);
@@ -274,7 +279,12 @@ static int rvwin_run(dv_ctx* c, int N, int A, const int32_t* route_of_member, co
                                wts, i0, A, P, Pw, c->rv_delta, c->rvw_split_env, d_fam, d_view);
     }
     HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(k_rv_best, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, d_fam, err, N, A, d_best, d_flags);
+    if (reloc_below) {
+        rc = rvreloc_enqueue(c, reloc, exact, err, wts, d_fam, d_view);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(k_rv_best, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, d_fam, err,
+                       reloc_below ? rvreloc_dev(c, reloc).lost : nullptr, N, A, d_best, d_flags);
     HIP_TRY(c, hipGetLastError());
     c->rv_out_host.resize(out_bytes);
     HIP_TRY(c, hipMemcpyAsync(c->rv_out_host.data(), c->rv_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -316,4 +326,38 @@ extern "C" int dv_rvwin_sense_step(dv_ctx* c, const double* x, const double* y, 
     if (rc) return rc;
     return rvwin_run(c, n_agents, n_headings, route_of_member, chem_weights, win_lo, win_hi, c->exact || (flags & DV_RVIEWS_EXACT), c->rv_err,
                      angle_fam, angle_view, best_heading, member_flags);
+}
+
+// ---- the two windowed calls with a threshold per member: a lost member re-localises inside the step (dejavu_rvreloc.inl) ------------------
+extern "C" int dv_rvreloc_step_u8(dv_ctx* c, const uint8_t* patches, int n_agents, int n_headings, const int32_t* route_of_member,
+                                  const double* chem_weights, const int32_t* win_lo, const int32_t* win_hi, const double* reloc_below,
+                                  uint32_t flags, double* angle_fam, int64_t* angle_view, int32_t* best_heading, uint32_t* member_flags) {
+    const char* who = "dv_rvreloc_step_u8";
+    if (!c) return DV_ERR_INVALID;
+    if (!patches || !angle_fam || !best_heading || !member_flags) return fail(c, DV_ERR_INVALID, "%s: NULL argument", who);
+    int rc = rvwin_check(c, who, n_agents, n_headings, route_of_member, chem_weights, win_lo, win_hi);
+    if (!rc) rc = rvreloc_check(c, who, n_agents, n_headings, reloc_below);
+    if (rc) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)n_agents * n_headings * c->rv_h * c->rv_w * 3;
+    rc = ensure_sense_buffer(c, bytes);
+    if (rc) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->d_sense, patches, bytes, hipMemcpyHostToDevice, c->stream));
+    return rvwin_run(c, n_agents, n_headings, route_of_member, chem_weights, win_lo, win_hi, c->exact || (flags & DV_RVIEWS_EXACT), nullptr,
+                     angle_fam, angle_view, best_heading, member_flags, reloc_below);
+}
+
+extern "C" int dv_rvreloc_sense_step(dv_ctx* c, const double* x, const double* y, const double* angles, int n_agents, int n_headings,
+                                     const int32_t* route_of_member, const double* chem_weights, const int32_t* land_of_member,
+                                     const int32_t* win_lo, const int32_t* win_hi, const double* reloc_below, uint32_t flags,
+                                     double* angle_fam, int64_t* angle_view, int32_t* best_heading, uint32_t* member_flags) {
+    const char* who = "dv_rvreloc_sense_step";
+    if (!c) return DV_ERR_INVALID;
+    if (!angle_fam || !best_heading || !member_flags) return fail(c, DV_ERR_INVALID, "%s: NULL argument", who);
+    int rc = rvwin_check(c, who, n_agents, n_headings, route_of_member, chem_weights, win_lo, win_hi);
+    if (!rc) rc = rvreloc_check(c, who, n_agents, n_headings, reloc_below);
+    if (!rc) rc = rviews_sense_members(c, who, x, y, angles, n_agents, n_headings, route_of_member, chem_weights, land_of_member);
+    if (rc) return rc;
+    return rvwin_run(c, n_agents, n_headings, route_of_member, chem_weights, win_lo, win_hi, c->exact || (flags & DV_RVIEWS_EXACT), c->rv_err,
+                     angle_fam, angle_view, best_heading, member_flags, reloc_below);
 }

@@ -24,6 +24,7 @@ DV_FORM_BODY_SHIFT = 8                   # dv_scoring_form: 1 + index of the lau
 DV_FORM_BODY_BITS = 5
 DV_FORM_BODY_NAMES = "Ring Ring2 RingA RingB Lc LcShort LcCode LcReg LcRegCode LcRegCode8 Lc2Tiles Lc2TilesCode Lc22".split()
 DV_RVIEWS_EXACT = 1
+DV_RES_RELOCALISED = 32                  # dv_rvreloc_*: the member's row is the whole-route step's (its window's best lay below its threshold)
 DV_RVWIN_MAX_VIEWS = 512                 # views of a window of dv_rvwin_* at most
 DV_DIFFUSE_AUTO = 0
 DV_DIFFUSE_PLAIN = 1
@@ -308,6 +309,10 @@ PROTOTYPES = {
                                         _i32p]),
     "dv_rvwin_sense_step": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _i32p, _f64p, _i32p, _i32p, _i32p,
                                            ctypes.c_uint32, _f64p, _i64p, _i32p, _u32p]),
+    "dv_rvreloc_step_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, _i32p, _f64p, _i32p, _i32p, _f64p, ctypes.c_uint32, _f64p,
+                                          _i64p, _i32p, _u32p]),
+    "dv_rvreloc_sense_step": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _i32p, _f64p, _i32p, _i32p, _i32p, _f64p,
+                                             ctypes.c_uint32, _f64p, _i64p, _i32p, _u32p]),
     "dv_synchronize": (ctypes.c_int, [_ctx_p]),
     "dv_timer_start": (ctypes.c_int, [_ctx_p]),
     "dv_timer_stop": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_float)]),

@@ -74,6 +74,11 @@ class RouteViewResults(OneValueBatchResults):
         OneValueBatchResults.__init__(self, angle_familiarity, best_idex, flags)
         self.angle_view = angle_view
 
+    @property
+    def relocalised(self):
+        """bool[n]: the member's windowed best lay below its threshold, and its row is the whole-route step's (DV_RES_RELOCALISED)."""
+        return (np.asarray(self.flags) & N.DV_RES_RELOCALISED) != 0
+
 
 InfomaxBatchResults = OneValueBatchResults    # the name it had while Infomax was the only such model
 
@@ -1637,29 +1642,65 @@ class FamiliarityEngine(object):
                              % (i, lo[i], hi[i], self.RVWIN_MAX_VIEWS, routes[i], lens[i]))
         return np.ascontiguousarray(lo, dtype=np.int32), np.ascontiguousarray(hi, dtype=np.int32)
 
-    def rvwin_step_u8(self, patches, route_of_member, chem_weights, win_lo, win_hi, exact=False):
+    @staticmethod
+    def _rvwin_thresholds(reloc_below, n):
+        """reloc_below of a step as float64[n] (None: None), no NaN -- checked before any library call."""
+        if reloc_below is None:
+            return None
+        t = np.asarray(reloc_below)
+        if t.dtype.kind not in "fiu":
+            raise ValueError("reloc_below must hold numbers (a familiarity per member; -inf: never), got dtype %s" % t.dtype)
+        if t.shape != (n,):
+            raise ValueError("reloc_below must have shape (%d,), got %r" % (n, t.shape))
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        bad = np.flatnonzero(np.isnan(t))
+        if len(bad):
+            raise ValueError("member %d: reloc_below is NaN" % bad[0])
+        return t
+
+    def rvwin_step_u8(self, patches, route_of_member, chem_weights, win_lo, win_hi, exact=False, reloc_below=None):
         """rviews_step_u8 with member i scored against views [win_lo[i], win_hi[i]) of its route only (at most RVWIN_MAX_VIEWS), in one
         fused scoring launch -> RouteViewResults: what the unwindowed step gives on that slice of the route, angle_view counted from
-        the route's first view."""
+        the route's first view.  reloc_below (float64[n]; None: the call as it ever was): member i whose largest windowed
+        angle_familiarity is < reloc_below[i] is lost, and its row is rviews_step_u8's on its whole route, in the same enqueue
+        (dv_rvreloc_step_u8); results.relocalised says which."""
         patches = self._rviews_patches(patches)
         n, A = patches.shape[:2]
         routes, w, _ = self._rviews_tables(n, route_of_member, chem_weights)
         lo, hi = self._rvwin_windows(routes, win_lo, win_hi)
+        tau = self._rvwin_thresholds(reloc_below, n)
         fam, best, flags = self._member_results(n, A)
         view = np.empty((n, A), dtype=np.int64)
+        if tau is not None:
+            self._check(self._lib.dv_rvreloc_step_u8(self._ctx, N.u8ptr(patches), n, A, routes.ctypes.data_as(N._i32p), N.f64ptr(w),
+                                                     lo.ctypes.data_as(N._i32p), hi.ctypes.data_as(N._i32p), N.f64ptr(tau),
+                                                     N.DV_RVIEWS_EXACT if exact else 0, N.f64ptr(fam), N.i64ptr(view),
+                                                     best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)), "dv_rvreloc_step_u8")
+            return RouteViewResults(fam, view, best, flags)
         self._check(self._lib.dv_rvwin_step_u8(self._ctx, N.u8ptr(patches), n, A, routes.ctypes.data_as(N._i32p), N.f64ptr(w),
                                                lo.ctypes.data_as(N._i32p), hi.ctypes.data_as(N._i32p), N.DV_RVIEWS_EXACT if exact else 0,
                                                N.f64ptr(fam), N.i64ptr(view), best.ctypes.data_as(N._i32p)), "dv_rvwin_step_u8")
         return RouteViewResults(fam, view, best, flags)
 
-    def rvwin_sense_step(self, x, y, angles, route_of_member, chem_weights, win_lo, win_hi, land_of_member=None, exact=False):
-        """rvwin_step_u8 with the patches sensed as rviews_sense_step senses them: one enqueue and one wait."""
+    def rvwin_sense_step(self, x, y, angles, route_of_member, chem_weights, win_lo, win_hi, land_of_member=None, exact=False,
+                         reloc_below=None):
+        """rvwin_step_u8 with the patches sensed as rviews_sense_step senses them: one enqueue and one wait (with reloc_below too:
+        dv_rvreloc_sense_step; a member flagged DV_RES_SENSE_ERROR is never lost)."""
         x, y, angles = self._member_poses(x, y, angles)
         n, A = angles.shape
         routes, w, lands = self._rviews_tables(n, route_of_member, chem_weights, land_of_member)
         lo, hi = self._rvwin_windows(routes, win_lo, win_hi)
+        tau = self._rvwin_thresholds(reloc_below, n)
         fam, best, flags = self._member_results(n, A)
         view = np.empty((n, A), dtype=np.int64)
+        if tau is not None:
+            self._check(self._lib.dv_rvreloc_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A,
+                                                        routes.ctypes.data_as(N._i32p), N.f64ptr(w),
+                                                        None if lands is None else lands.ctypes.data_as(N._i32p), lo.ctypes.data_as(N._i32p),
+                                                        hi.ctypes.data_as(N._i32p), N.f64ptr(tau), N.DV_RVIEWS_EXACT if exact else 0,
+                                                        N.f64ptr(fam), N.i64ptr(view), best.ctypes.data_as(N._i32p),
+                                                        flags.ctypes.data_as(N._u32p)), "dv_rvreloc_sense_step")
+            return RouteViewResults(fam, view, best, flags)
         self._check(self._lib.dv_rvwin_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, routes.ctypes.data_as(N._i32p),
                                                   N.f64ptr(w), None if lands is None else lands.ctypes.data_as(N._i32p),
                                                   lo.ctypes.data_as(N._i32p), hi.ctypes.data_as(N._i32p), N.DV_RVIEWS_EXACT if exact else 0,

@@ -759,7 +759,13 @@ class SadsRouteEnsemble(_RouteEnsemble):
     flagged or stopped member keeps its value).  With a memory_index m its step scores views [max(0, m - behind), min(len, m + ahead + 1))
     only (dv_rvwin_sense_step: one fused scoring launch), with the bits of oracle.step on that slice; with memory_index None (the
     first step without window_centres, or after relocalise()) it scores the whole route.  Its scene_familiarity is +inf outside the
-    window of its last step.  Members without a window beside it step as ever: at most two device calls a step."""
+    window of its last step.  Members without a window beside it step as ever: at most two device calls a step.
+
+    relocalise_below=... gives windowed members a LOSS TEST: such a member carries `relocalise_below` (a familiarity, so at most
+    max_familiarity), and a step whose largest windowed angle_familiarity is < that value (strictly, on the reference's doubles) is
+    redone against the whole route INSIDE the same device call (dv_rvreloc_sense_step): the member's row, its memory_index and its
+    scene_familiarity (nothing masked) are the whole-route step's, `relocalised` says that its last applied step was such a one, and
+    `n_relocalisations` counts them.  A member that drifted off its window finds itself again without anybody calling relocalise()."""
     _metric = None
     _takes = "agents of the perfect-memory model (familiarity_model=sads_familiarity(...))"
     _info_call = "rviews_info"               # dict(n_routes, first int64[R + 1], shape, bytes)
@@ -864,40 +870,72 @@ class SadsRouteEnsemble(_RouteEnsemble):
                 centres[i] = int(m)
         return wins, centres
 
-    def _set_windows(self, wins, centres):
-        for a, w, m in zip(self.agents, wins, centres):
+    def _set_windows(self, wins, centres, thresholds=None):
+        for i, (a, w, m) in enumerate(zip(self.agents, wins, centres)):
             a.window, a.memory_index = w, m
+            a.relocalise_below = None if thresholds is None else thresholds[i]
+            a.relocalised, a.n_relocalisations = False, 0
+
+    @staticmethod
+    def _thresholds_arg(relocalise_below, wins):
+        """`relocalise_below` of from_routes_with / from_landscapes as a list with a float or None per start (wins: _windows_arg's):
+        a threshold belongs to a member with a window.  ValueError names the entry."""
+        n = len(wins)
+        if relocalise_below is None:
+            return [None] * n
+
+        def one(t, what):
+            if isinstance(t, bool) or not isinstance(t, (int, float, np.integer, np.floating)):
+                raise ValueError("%s must be a familiarity (a float) or None, got %r" % (what, t))
+            if np.isnan(t):
+                raise ValueError("%s is NaN" % what)
+            return float(t)
+        if isinstance(relocalise_below, (list, tuple)):
+            if len(relocalise_below) != n:
+                raise ValueError("relocalise_below holds %d entries for %d starts" % (len(relocalise_below), n))
+            out = [None if t is None else one(t, "relocalise_below[%d]" % i) for i, t in enumerate(relocalise_below)]
+        else:
+            out = [one(relocalise_below, "relocalise_below")] * n
+        for i, (t, w) in enumerate(zip(out, wins)):
+            if t is not None and w is None:
+                raise ValueError("relocalise_below[%d] = %r, but member %d has no window: the threshold is a windowed member's loss test"
+                                 % (i, t, i))
+        return out
 
     @classmethod
-    def from_routes_with(cls, agent, routes, starts, metrics="host", chem_weights=None, window=None, window_centres=None):
+    def from_routes_with(cls, agent, routes, starts, metrics="host", chem_weights=None, window=None, window_centres=None,
+                         relocalise_below=None):
         """_RouteEnsemble.from_routes_with, and chem_weights: member i scores under chem_weights[i] (None: the model's weight).
         window: None (perfect memory: every step scores the whole route), or perfect memory with a temporal window -- an int W
         (W views behind and W ahead of the view the member matched last), a pair (behind, ahead), or a list with such an entry, or
         None, per start.  window_centres: a list with the initial `memory_index` (a view of the member's own route) or None per start;
-        a windowed member without one scores its whole route in its first step (see the class)."""
+        a windowed member without one scores its whole route in its first step (see the class).  relocalise_below: None, a float (every
+        member's threshold), or a list with a float or None per start; a member with a threshold must have a window."""
         starts = list(starts)
         w = cls._weights_arg(chem_weights, starts)
         routes = list(routes)
         wins, centres = cls._windows_arg(window, window_centres, starts, [len(r) for r in routes])
+        thresholds = cls._thresholds_arg(relocalise_below, wins)
         ens = cls._from_routes(agent, routes, starts, metrics, None, None)
         if w is not None:
             ens._set_weights(w)
-        ens._set_windows(wins, centres)
+        ens._set_windows(wins, centres, thresholds)
         return ens
 
     @classmethod
     def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host", chem_weights=None, sensors=None, window=None,
-                        window_centres=None):
-        """_RouteEnsemble.from_landscapes, and chem_weights, window and window_centres as from_routes_with takes them."""
+                        window_centres=None, relocalise_below=None):
+        """_RouteEnsemble.from_landscapes, and chem_weights, window, window_centres and relocalise_below as from_routes_with takes them."""
         starts = list(starts)
         w = cls._weights_arg(chem_weights, starts)
         routes = list(routes)
         lengths = [len(rt[1]) if isinstance(rt, (tuple, list)) and len(rt) == 2 else 0 for rt in routes]
         wins, centres = cls._windows_arg(window, window_centres, starts, lengths)
+        thresholds = cls._thresholds_arg(relocalise_below, wins)
         ens = super(SadsRouteEnsemble, cls).from_landscapes(agent, landscapes, routes, starts, metrics=metrics, sensors=sensors)
         if w is not None:
             ens._set_weights(w)
-        ens._set_windows(wins, centres)
+        ens._set_windows(wins, centres, thresholds)
         return ens
 
     def relocalise(self, members=None):
@@ -915,7 +953,9 @@ class SadsRouteEnsemble(_RouteEnsemble):
 
     def _device_step(self, idx, xs, ys, angs):
         """A member with a window and a centre goes to rvwin_sense_step, every other to rviews_sense_step: at most two device calls, and
-        with no window anywhere the one call there was.  The results come back as one RouteViewResults in the caller's order."""
+        with no window anywhere the one call there was.  Where a member of the windowed call has a threshold (relocalise_below) the call
+        carries every member's (-inf for those without: never lost), and a lost member's row comes back as the whole route's; with no
+        threshold anywhere the calls are the ones there were.  The results come back as one RouteViewResults in the caller's order."""
         from .engine import RouteViewResults
         wins = [self._window_of(self.agents[i]) for i in idx]
         lands = None if self._lands is None else self._lands[idx]
@@ -927,8 +967,10 @@ class SadsRouteEnsemble(_RouteEnsemble):
             xs, ys, angs = np.asarray(xs, dtype=np.float64), np.asarray(ys, dtype=np.float64), np.asarray(angs, dtype=np.float64)
             banks, weights = self._banks[idx], self._weights[idx]
             rest = [k for k, w in enumerate(wins) if w is None]
+            taus = [getattr(self.agents[idx[k]], "relocalise_below", None) for k in ks]
+            more = {} if all(t is None for t in taus) else dict(reloc_below=np.array([-np.inf if t is None else t for t in taus]))
             parts = [(ks, self.engine.rvwin_sense_step(xs[ks], ys[ks], angs[ks], banks[ks], weights[ks], [wins[k][0] for k in ks],
-                                                       [wins[k][1] for k in ks], land_of_member=None if lands is None else lands[ks]))]
+                                                       [wins[k][1] for k in ks], land_of_member=None if lands is None else lands[ks], **more))]
             if rest:
                 parts.append((rest, self.engine.rviews_sense_step(xs[rest], ys[rest], angs[rest], banks[rest], weights[rest],
                                                                   land_of_member=None if lands is None else lands[rest])))
@@ -943,6 +985,10 @@ class SadsRouteEnsemble(_RouteEnsemble):
             a = self.agents[i]
             if getattr(a, "window", None) is not None and not results.flags[k] & 16:
                 a.memory_index = int(results.angle_view[k, results.best_idex[k]])
+                a.relocalised = bool(results.flags[k] & 32)           # (DV_RES_RELOCALISED: the step was the global search, by the rule)
+                if a.relocalised:
+                    a.n_relocalisations = getattr(a, "n_relocalisations", 0) + 1
+                    self._step_windows[id(a)] = None                  # its scene_familiarity is the whole route's row: nothing is masked
         return results
 
     def _note_scene(self, agent, x, y, headings, weight):

@@ -2,7 +2,7 @@
 """Times a step of the route view store (dv_rviews_sense_step, navsim_amd.SadsRouteEnsemble) at a slice of the reference's grid and
 writes profiles/rviews_time.json.
 
-    python tools/rviews_time.py [--sides 32,64] [--calls 30] [--reps 5] [--blocks routes[,sensors][,window]] [--out profiles/rviews_time.json]
+    python tools/rviews_time.py [--sides 32,64] [--calls 30] [--reps 5] [--blocks routes[,sensors][,window][,reloc]] [--out profiles/rviews_time.json]
 
 Shape: 4 routes x 8 starts x 10 headings = 32 trials of 320 columns, views of side x side.  The routes have the grid's length:
 synth.sin_training_path with arclen = step_size / n_test_angles (scripts/run_experiment.py:207) on a 900 x 900 landscape, one curve
@@ -29,7 +29,15 @@ the same poses, in alternating windows of one process: per side unwindowed_call_
 windowed_exact_call_us (hipEvent pairs), ensemble_step_wall_us (SadsRouteEnsemble(window=...).step_forward(fake=True), wall clock) and
 the two ratios; uncut_101_views_call_us is the 101-view call with the kernel's pixel cut switched off (DEJAVU_RVWIN_SPLIT=0).  The fast
 and exact forms, and the cut and uncut kernels, are checked to agree on their bits before anything is timed.  The block is the file's
-"window" key; measured alone it leaves every other key as it was."""
+"window" key; measured alone it leaves every other key as it was.
+
+Reloc block (--blocks reloc): the same slice under a window of 101 views with the loss test inside the call (dv_rvreloc_sense_step,
+rvwin_sense_step(reloc_below=...)), in alternating windows of one process, hipEvent pairs: windowed_call_us (dv_rvwin_sense_step, no
+thresholds), reloc_none_lost_call_us (every threshold -inf: the price of the planning launch and the empty worst-case grids),
+reloc_4_lost_call_us (one member a route at +inf) and reloc_all_lost_call_us (all 32), against the host's way at the same poses --
+host_4_lost_call_us / host_all_lost_call_us: the windowed call, then rviews_sense_step on the lost members (two enqueues, two waits, the
+lost members sensed twice) -- and unwindowed_call_us.  The device's and the host's way are checked to agree on their bits before
+anything is timed.  The block is the file's "reloc" key; measured alone it leaves every other key as it was."""
 import argparse
 import json
 import os
@@ -230,13 +238,92 @@ def measure_window(side, n_calls, reps):
     return out
 
 
+RELOC_WINDOW = (50, 50)
+
+
+def measure_reloc(side, n_calls, reps):
+    """The reloc block's row of one side."""
+    import navsim_amd
+    from navsim_amd import synth
+    land = synth.synth_landscape(3, LAND, 4)
+    routes = [synth.sin_training_path(c, 0.2 * LAND, 0.6 * LAND, arclen=STEP_SIZE / HEADINGS) for c in CURVES]
+    starts = starts_of(routes)
+    centres = np.array([int(np.argmin(np.linalg.norm(routes[r] - np.array(pos), axis=1))) for r, pos, _ in starts])
+    a = navsim_amd.NavBySceneFamiliarity(land, (side, side), STEP_SIZE, n_test_angles=HEADINGS, track_scene_familiarity=False,
+                                         familiarity_model=navsim_amd.sads_familiarity(CHEM_WEIGHT))
+    ens = navsim_amd.SadsRouteEnsemble.from_routes_with(a, routes, starts, metrics="device", window=RELOC_WINDOW, window_centres=centres.tolist())
+    eng = ens.engine
+    n = len(starts)
+    xs = np.array([p[0] for _, p, _ in starts])
+    ys = np.array([p[1] for _, p, _ in starts])
+    angs = (np.array([a for _, _, a in starts])[:, None] + ens.agents[0].angle_offsets[None, :]) % (2 * np.pi)
+    route_of = np.array([r for r, _, _ in starts], dtype=np.int32)
+    weights = np.full(n, CHEM_WEIGHT)
+    lens = np.array([len(routes[r]) for r in route_of])
+    lo, hi = np.maximum(0, centres - RELOC_WINDOW[0]), np.minimum(lens, centres + RELOC_WINDOW[1] + 1)
+    four = np.arange(0, n, STARTS_PER_ROUTE)                     # one member a route
+    taus = dict(none=np.full(n, -np.inf), four=np.where(np.isin(np.arange(n), four), np.inf, -np.inf), all=np.full(n, np.inf))
+    lost_of = dict(four=four, all=np.arange(n))
+
+    def device(which):
+        eng.timer_start()
+        for _ in range(n_calls):
+            res = eng.rvwin_sense_step(xs, ys, angs, route_of, weights, lo, hi, reloc_below=None if which is None else taus[which])
+        return eng.timer_stop() * 1e3 / n_calls, res
+
+    def host(which):
+        m = lost_of[which]
+        eng.timer_start()
+        for _ in range(n_calls):
+            res = eng.rvwin_sense_step(xs, ys, angs, route_of, weights, lo, hi)
+            again = eng.rviews_sense_step(xs[m], ys[m], angs[m], route_of[m], weights[m])
+        return eng.timer_stop() * 1e3 / n_calls, res, again
+
+    def unwindowed():
+        eng.timer_start()
+        for _ in range(n_calls):
+            eng.rviews_sense_step(xs, ys, angs, route_of, weights)
+        return eng.timer_stop() * 1e3 / n_calls
+
+    _, plain = device(None)                                        # warm-up of every form, and the forms agree
+    _, none = device("none")
+    assert np.array_equal(none.angle_familiarity.view(np.uint64), plain.angle_familiarity.view(np.uint64)) and not none.flags.any()
+    for which in ("four", "all"):
+        _, got = device(which)
+        _, win, again = host(which)
+        m = lost_of[which]
+        fam, view = win.angle_familiarity.copy(), win.angle_view.copy()
+        fam[m], view[m] = again.angle_familiarity, again.angle_view
+        assert np.array_equal(got.angle_familiarity.view(np.uint64), fam.view(np.uint64)) and np.array_equal(got.angle_view, view)
+        assert np.array_equal(np.flatnonzero(got.relocalised), m)
+    unwindowed()
+    t = {k: [] for k in ("windowed", "none", "four", "all", "host_four", "host_all", "unwindowed")}
+    for _ in range(reps):                                         # alternating windows
+        t["windowed"].append(device(None)[0])
+        for which in ("none", "four", "all"):
+            t[which].append(device(which)[0])
+        for which in ("four", "all"):
+            t["host_" + which].append(host(which)[0])
+        t["unwindowed"].append(unwindowed())
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    out = dict(side=side, routes=len(routes), route_views=[len(r) for r in routes], members=n, headings=HEADINGS, columns=n * HEADINGS,
+               chem_weight=CHEM_WEIGHT, calls_per_window=n_calls, windows=reps, window_views=int((hi - lo).max()),
+               windowed_call_us=spread(t["windowed"]), reloc_none_lost_call_us=spread(t["none"]), reloc_4_lost_call_us=spread(t["four"]),
+               reloc_all_lost_call_us=spread(t["all"]), host_4_lost_call_us=spread(t["host_four"]), host_all_lost_call_us=spread(t["host_all"]),
+               unwindowed_call_us=spread(t["unwindowed"]), none_lost_over_windowed=round(med["none"] / med["windowed"], 3),
+               none_lost_minus_windowed_us=round(med["none"] - med["windowed"], 3),
+               host_over_device_4_lost=round(med["host_four"] / med["four"], 3), host_over_device_all_lost=round(med["host_all"] / med["all"], 3))
+    eng.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sides", default="32,64")
     ap.add_argument("--calls", type=int, default=30)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rviews_time.json"))
-    ap.add_argument("--blocks", default="routes", help="which blocks to measure: routes (the routed step against four engines), sensors, window")
+    ap.add_argument("--blocks", default="routes", help="which blocks to measure: routes (the routed step against four engines), sensors, window, reloc")
     ap.add_argument("--limit", type=int, default=240, help="seconds allowed to the sensors block's GPU child")
     args = ap.parse_args()
     blocks = args.blocks.split(",")
@@ -260,6 +347,13 @@ def main():
                                             sizes=[measure_window(int(s), args.calls, args.reps) for s in args.sides.split(",")]))
     elif "window" in kept:
         doc["window"] = kept["window"]
+    if "reloc" in blocks:                                         # a key of its own, as the window block's
+        if not ({"routes", "sensors", "window"} & set(blocks)) and kept:
+            doc = dict(kept)
+        doc["reloc"] = dict(device=torch.cuda.get_device_name(0), window=list(RELOC_WINDOW),
+                            sizes=[measure_reloc(int(s), args.calls, args.reps) for s in args.sides.split(",")])
+    elif "reloc" in kept:
+        doc["reloc"] = kept["reloc"]
     with open(args.out, "w") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")

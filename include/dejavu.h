@@ -732,6 +732,39 @@ int dv_mbank_read_weights(dv_ctx *ctx, int bank, uint8_t *out);
 int dv_mbank_set_weights(dv_ctx *ctx, int bank, const uint8_t *weights);
 int dv_mbank_info(dv_ctx *ctx, int *n_banks, int64_t *views_trained, int64_t *n_depressed);
 
+/* ---- mushroom-body population tables ---------------------------------------- */
+/*
+ * Banks with cells, wiring, quota and compared channel of their own.  A population is (channel, n_kc, fan_in, n_active,
+ * conn int32[n_kc][fan_in]); the views' h x w, so n_pixels, stay the ones dv_mb_begin fixed.  A table gives the context n_pops
+ * populations and n_banks banks; population_of_bank[b] names bank b's, and several banks may share one (routes x one wiring).  The
+ * weights are ragged: bank b holds uint8[n_kc of its population].  While a table is live
+ *   - the banked calls (dv_mbank_train_u8, dv_mbank_train_from_poses, dv_lands_mbank_train_from_poses, dv_mbank_step_u8,
+ *     dv_mbank_sense_step, dv_lands_mbank_sense_step; with or without a sensor table) take no new argument: view v is trained, or member i
+ *     scored, through its bank's own cells, wiring, quota and channel, in the same launches as the views and members of every other bank;
+ *   - dv_mbank_read_weights / dv_mbank_set_weights move n_kc bytes of the bank's own population (the 0/1 check runs on that length), and
+ *     dv_mbank_info counts each bank's zero weights over its own length;
+ *   - the calls that assume the begin's wiring behind bank 0 (dv_mb_train_u8, dv_mb_train_from_poses, dv_mb_score_u8, dv_mb_activity_u8,
+ *     dv_mb_sense_step, dv_batch_mb_step_u8, dv_batch_mb_sense_step, dv_mb_read_weights, dv_mb_set_weights) return DV_ERR_STATE, naming
+ *     dv_mbpop_clear;
+ *   - dv_mb_info keeps describing the model dv_mb_begin made (n_kc, n_pixels, fan_in, n_active, bytes); its two counts, views_trained
+ *     and n_depressed, are bank 0's, n_depressed over the cells of bank 0's own population.
+ * Without a table every call launches what it launched before there were tables.
+ *   set     conn_concat holds population p's int32[n_kc[p]][fan_in[p]], one after another.  DV_ERR_STATE without a model.  Every entry is
+ *           checked as dv_mb_begin checks its own -- n_kc in [1, 2^24], fan_in in [1, 16], n_active in [1, n_kc], channel in [0, 2], every
+ *           conn value in [0, n_pixels), population_of_bank in [0, n_pops) -- before anything reaches the device: DV_ERR_INVALID names the
+ *           population and the entry.  All weights start at 1 and all view counts at 0 (whatever was trained before is dropped).  On an
+ *           allocation failure the model, its banks and an earlier table stay as they were.
+ *   clear   back to one bank of the begin's population, weights 1.  dv_mbank_set, dv_mb_begin and dv_mb_end drop the table too.
+ *   info    n_pops and n_banks (both 0 without a table); per population n_kc, fan_in, n_active, channel (the caller's arrays of n_pops
+ *           entries); per bank population_of_bank, views_trained, n_depressed (arrays of n_banks entries); bytes: the table's device
+ *           bytes (weights, wirings, descriptors).  Ask for the counts first; any pointer may be NULL.
+ */
+int dv_mbpop_set(dv_ctx *ctx, int n_pops, const int32_t *n_kc, const int32_t *fan_in, const int32_t *n_active, const int32_t *channel,
+                 const int32_t *conn_concat, int n_banks, const int32_t *population_of_bank);
+int dv_mbpop_clear(dv_ctx *ctx);
+int dv_mbpop_info(dv_ctx *ctx, int *n_pops, int *n_banks, int32_t *n_kc, int32_t *fan_in, int32_t *n_active, int32_t *channel,
+                  int32_t *population_of_bank, int64_t *views_trained, int64_t *n_depressed, int64_t *bytes);
+
 /* ---- Infomax weight banks --------------------------------------------------- */
 /*
  * Several Infomax models of one shape and one learning rate in ONE context: the weights are float64[n_banks][n_hidden][h * w], bank b

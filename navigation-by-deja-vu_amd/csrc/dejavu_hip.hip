@@ -367,6 +367,15 @@ struct dv_ctx {
     int mb_banks = 1;                         // memories that share the connectivity (dv_mbank_set; 1 after dv_mb_begin)
     std::vector<int64_t> mb_views = std::vector<int64_t>(1, 0);   // [mb_banks]: views trained on since dv_mb_begin / dv_mbank_set
     MirroredTable mb_bank_of;                 // a banked call's table of ints: the bank of every view, or of every member
+    // population table of the model (dejavu_mbpop.inl: dv_mbpop_*): the banks' own cells, wiring, quota and channel; mbp_pops == 0: none,
+    // and mb_wt is [mb_banks][mb_K].  Live: mb_wt is ragged, bank b at mbp_wt_off[b], and mb_conn (the begin's wiring) is not read.
+    int mbp_pops = 0;
+    unsigned short* mbp_conn = nullptr;       // the populations' [fan_in_p][n_kc_p], one after another
+    MirroredTable mbp_desc;                   // [mb_banks] dv::MbPopBank: what a workgroup reads of its bank
+    std::vector<int> mbp_K, mbp_c, mbp_active, mbp_channel;   // [mbp_pops]
+    std::vector<int> mbp_of_bank;             // [mb_banks]: the bank's population
+    std::vector<size_t> mbp_wt_off;           // [mb_banks + 1]: prefix sums of the banks' n_kc
+    size_t mbp_lds = 0, mbp_bytes = 0;        // a launch's dynamic LDS (the most a population asks for); the table's device bytes
     // landscape set (dejavu_lands.inl: dv_lands_*): independent of d_land above; the sensor configuration is shared
     unsigned char* ld_lands = nullptr;        // the landscapes back to back, no padding (nullptr: no set)
     LandEntry* ld_tab = nullptr;              // [n_lands]: byte offset, rows, cols
@@ -3801,6 +3810,7 @@ extern "C" int dv_stream_read_gbps(dv_ctx* c, int64_t n_bytes, int iters, double
 #include "dejavu_rvwin.inl"     // dv_rvwin_*: windowed perfect memory on the route view store, scored in one fused launch (kernel and host side)
 #include "dejavu_infomax.inl"  // dv_infomax_*: the Infomax familiarity model (kernels and host side)
 #include "dejavu_mushroom.inl"  // dv_mb_*: the mushroom-body familiarity model (kernels and host side)
+#include "dejavu_mbpop.inl"     // dv_mbpop_*: population tables, a bank's own cells, wiring and channel (kernels and host side)
 #include "dejavu_path_routes.inl"   // dv_path_routes_*: the error / coverage metrics against several routes (host side)
 #include "dejavu_marks.inl"     // dv_marks_*: the coverage statistics of a result row, from the marks on the device (kernel and host side)
 #include "dejavu_group.inl"     // dv_group_*: one process, several devices -- host logic above the C ABI

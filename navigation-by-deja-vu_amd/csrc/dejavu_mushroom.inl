@@ -36,6 +36,11 @@
 // land_of[(col0 + blockIdx.x) / per], whose first byte and shape mb_fill_pose is handed instead of the context's one landscape.  The
 // plane still goes from the landscape to LDS; everything after it is mb_view.  k_mb_pose_bank_lands_sensors reads the column's sensor
 // (pixel block, mask, level table) from the set's sensor table as well (dejavu_sensors.inl); it is launched only where a table is live.
+//
+// Population tables (dejavu_mbpop.inl).  A live table (c->mbp_pops > 0) gives every bank cells, wiring, quota and channel of its own:
+// wt is then ragged, and the banked host paths below (mb_launch_bank, mb_batch's sensed launch, the banks' weights and counts) hand
+// over to k_mbpop_*, which are mb_view on a per-bank descriptor.  The kernels of this file are launched only without a table, and
+// the calls that assume this file's one wiring behind bank 0 are refused while one is live (mb_need_bank0).
 namespace dv {
 
 static constexpr int kMbTrain = 0, kMbScore = 1, kMbMask = 2;
@@ -300,11 +305,21 @@ static constexpr int kMbMaxCells = 1 << 24;
 static constexpr int kMbSlabViews = 8192;                    // views of one launch (one workgroup each) ...
 static constexpr size_t kMbStageBytes = 64u << 20;           // ... and the bytes of uploaded planes, or of fired masks, it may stage
 
+// Population tables (dejavu_mbpop.inl, which follows this file): a live one (c->mbp_pops > 0) gives every bank cells, wiring and
+// channel of its own, and the banked calls below go through its kernels.
+static void mbpop_drop(dv_ctx* c);
+static hipError_t mbpop_lds_cap(int lds);
+static int mbpop_launch_bank(dv_ctx* c, int mode, const unsigned char* d_src, long long view_stride, int px_stride, int by_channel, int n, int* d,
+                             const int* d_bank_of, long long col0, int per);
+static int mbpop_launch_pose(dv_ctx* c, bool on_lands, long long c0, int nc, int A);
+static int mbpop_count(dv_ctx* c);
+
 static void mb_free(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
     F(c->mb_conn); F(c->mb_wt); F(c->mb_d); F(c->mb_fired); F(c->mb_zeros); F(c->mb_bd); F(c->mb_berr); F(c->mb_res.dev);
     c->mb_d_cap = c->mb_fired_cap = c->mb_bd_cap = c->mb_berr_cap = c->mb_res.cap = 0;
     table_free(c->mb_bank_of);
+    mbpop_drop(c);
     c->mb_K = c->mb_N = c->mb_c = c->mb_active = c->mb_hh = c->mb_ww = 0;
     c->mb_banks = 1;
     c->mb_views.assign(1, 0);
@@ -312,6 +327,15 @@ static void mb_free(dv_ctx* c) {
 
 static int mb_need(dv_ctx* c, const char* who) {
     if (!c->mb_wt) return fail(c, DV_ERR_STATE, "%s: no mushroom-body model (dv_mb_begin first)", who);
+    return DV_OK;
+}
+
+// The calls that assume the begin's wiring behind bank 0 (dv_mb_*, dv_batch_mb_*): refused while a population table is live.
+static int mb_need_bank0(dv_ctx* c, const char* who) {
+    int rc = mb_need(c, who);
+    if (rc) return rc;
+    if (c->mbp_pops)
+        return fail(c, DV_ERR_STATE, "%s: a population table is live, and bank 0 is no longer the model dv_mb_begin made (dv_mbpop_clear first, or the dv_mbank_ call)", who);
     return DV_OK;
 }
 
@@ -342,6 +366,8 @@ static int mb_launch(dv_ctx* c, const unsigned char* d_src, long long view_strid
 template <int MODE>
 static int mb_launch_bank(dv_ctx* c, const unsigned char* d_src, long long view_stride, int px_stride, int offset, int n, int* d, const int* d_bank_of,
                           long long col0, int per) {
+    // (under a population table a strided source is the sensed views, read at the bank's own channel instead of `offset`)
+    if (c->mbp_pops) return mbpop_launch_bank(c, MODE, d_src, view_stride, px_stride, px_stride == 3, n, d, d_bank_of, col0, per);
     hipLaunchKernelGGL((k_mb_bank<MODE>), dim3((unsigned)n), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, d_src, view_stride, px_stride, offset,
                        c->mb_N, c->mb_conn, c->mb_K, c->mb_c, c->mb_active, c->mb_wt, d, d_bank_of, (unsigned)col0, (unsigned)per);
     HIP_TRY(c, hipGetLastError());
@@ -411,6 +437,7 @@ extern "C" int dv_mb_begin(dv_ctx* c, int h, int w, int channel, int n_kc, int f
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_pose_bank, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_pose_bank_lands, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_pose_bank_lands_sensors, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess) e = mbpop_lds_cap(lds);
     if (e == hipSuccess) e = hipMemcpyAsync(c->mb_conn, ct.data(), ct.size() * sizeof(unsigned short), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->mb_wt, 1, K, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);           // `ct` is this call's
@@ -448,6 +475,8 @@ static int mb_train_u8(dv_ctx* c, const char* who, const uint8_t* planes, int64_
 
 extern "C" int dv_mb_train_u8(dv_ctx* c, const uint8_t* planes, int64_t n) {
     if (!c) return DV_ERR_INVALID;
+    int rc = mb_need_bank0(c, "dv_mb_train_u8");
+    if (rc) return rc;
     return mb_train_u8(c, "dv_mb_train_u8", planes, n, nullptr);
 }
 
@@ -488,12 +517,14 @@ static int mb_train_from_poses(dv_ctx* c, const char* who, const double* x, cons
 
 extern "C" int dv_mb_train_from_poses(dv_ctx* c, const double* x, const double* y, const double* angle, int64_t n, uint8_t* out_views) {
     if (!c) return DV_ERR_INVALID;
+    int rc = mb_need_bank0(c, "dv_mb_train_from_poses");
+    if (rc) return rc;
     return mb_train_from_poses(c, "dv_mb_train_from_poses", x, y, angle, n, nullptr, nullptr, out_views);
 }
 
 extern "C" int dv_mb_score_u8(dv_ctx* c, const uint8_t* planes, int n, double* familiarity) {
     if (!c) return DV_ERR_INVALID;
-    int rc = mb_need(c, "dv_mb_score_u8");
+    int rc = mb_need_bank0(c, "dv_mb_score_u8");
     if (rc) return rc;
     if (!planes || !familiarity || n < 1) return fail(c, DV_ERR_INVALID, "dv_mb_score_u8: NULL argument or n < 1");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -518,7 +549,7 @@ extern "C" int dv_mb_score_u8(dv_ctx* c, const uint8_t* planes, int n, double* f
 
 extern "C" int dv_mb_activity_u8(dv_ctx* c, const uint8_t* planes, int n, uint8_t* fired, int32_t* threshold) {
     if (!c) return DV_ERR_INVALID;
-    int rc = mb_need(c, "dv_mb_activity_u8");
+    int rc = mb_need_bank0(c, "dv_mb_activity_u8");
     if (rc) return rc;
     if (!planes || n < 1) return fail(c, DV_ERR_INVALID, "dv_mb_activity_u8: planes is NULL or n < 1");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -543,7 +574,7 @@ extern "C" int dv_mb_activity_u8(dv_ctx* c, const uint8_t* planes, int n, uint8_
 
 extern "C" int dv_mb_sense_step(dv_ctx* c, double x, double y, const double* angles, int n, double* angle_fam, int32_t* best_heading) {
     if (!c) return DV_ERR_INVALID;
-    int rc = mb_need(c, "dv_mb_sense_step");
+    int rc = mb_need_bank0(c, "dv_mb_sense_step");
     if (rc) return rc;
     if (!angles || !angle_fam || !best_heading || n < 1) return fail(c, DV_ERR_INVALID, "dv_mb_sense_step: NULL argument or n_headings < 1");
     rc = sensor_fits(c, "dv_mb_sense_step", c->mb_hh, c->mb_ww);
@@ -611,6 +642,9 @@ static int mb_batch(dv_ctx* c, const char* who, const uint8_t* planes, const dou
             rc = bank_of ? mb_launch_bank<kMbScore>(c, c->d_sense, (long long)N, 1, 0, nc, c->mb_bd + c0, c->mb_bank_of.device<int>(), c0, A)
                          : mb_launch<kMbScore>(c, c->d_sense, (long long)N, 1, 0, nc, c->mb_bd + c0, nullptr, nullptr);
             if (rc) return rc;
+        } else if (c->mbp_pops) {                               // (bank_of is there: the bank-0 calls are refused under a table)
+            rc = mbpop_launch_pose(c, land_of != nullptr, c0, nc, A);
+            if (rc) return rc;
         } else if (land_of && c->sn_tab) {
             hipLaunchKernelGGL(k_mb_pose_bank_lands_sensors, dim3((unsigned)nc), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, c->ld_lands, c->ld_tab,
                                c->sn_tab, c->sn_luts, c->ld_of.device<int>(), c->d_poses + c0, c->sensor, c->mb_channel, c->mb_conn, c->mb_K, c->mb_c,
@@ -644,7 +678,7 @@ static int mb_batch(dv_ctx* c, const char* who, const uint8_t* planes, const dou
 
 extern "C" int dv_batch_mb_step_u8(dv_ctx* c, const uint8_t* planes, int n_agents, int n_headings, double* angle_fam, int32_t* best_heading) {
     if (!c) return DV_ERR_INVALID;
-    int rc = mb_need(c, "dv_batch_mb_step_u8");
+    int rc = mb_need_bank0(c, "dv_batch_mb_step_u8");
     if (rc) return rc;
     if (!planes || !angle_fam || !best_heading || n_agents < 1 || n_headings < 1)
         return fail(c, DV_ERR_INVALID, "dv_batch_mb_step_u8: NULL argument, n_agents < 1 or n_headings < 1");
@@ -654,7 +688,7 @@ extern "C" int dv_batch_mb_step_u8(dv_ctx* c, const uint8_t* planes, int n_agent
 extern "C" int dv_batch_mb_sense_step(dv_ctx* c, const double* x, const double* y, const double* angles, int n_agents, int n_headings,
                                       double* angle_fam, int32_t* best_heading, uint32_t* flags) {
     if (!c) return DV_ERR_INVALID;
-    int rc = mb_need(c, "dv_batch_mb_sense_step");
+    int rc = mb_need_bank0(c, "dv_batch_mb_sense_step");
     if (rc) return rc;
     if (!x || !y || !angles || !angle_fam || !best_heading || !flags || n_agents < 1 || n_headings < 1)
         return fail(c, DV_ERR_INVALID, "dv_batch_mb_sense_step: NULL argument, n_agents < 1 or n_headings < 1");
@@ -665,7 +699,7 @@ extern "C" int dv_batch_mb_sense_step(dv_ctx* c, const double* x, const double* 
 
 extern "C" int dv_mb_read_weights(dv_ctx* c, uint8_t* out) {
     if (!c) return DV_ERR_INVALID;
-    int rc = mb_need(c, "dv_mb_read_weights");
+    int rc = mb_need_bank0(c, "dv_mb_read_weights");
     if (rc) return rc;
     if (!out) return fail(c, DV_ERR_INVALID, "dv_mb_read_weights: out is NULL");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -676,7 +710,7 @@ extern "C" int dv_mb_read_weights(dv_ctx* c, uint8_t* out) {
 
 extern "C" int dv_mb_set_weights(dv_ctx* c, const uint8_t* weights) {
     if (!c) return DV_ERR_INVALID;
-    int rc = mb_need(c, "dv_mb_set_weights");
+    int rc = mb_need_bank0(c, "dv_mb_set_weights");
     if (rc) return rc;
     if (!weights) return fail(c, DV_ERR_INVALID, "dv_mb_set_weights: weights is NULL");
     for (int k = 0; k < c->mb_K; ++k)
@@ -701,8 +735,13 @@ extern "C" int dv_mb_info(dv_ctx* c, int* n_kc, int* n_pixels, int* fan_in, int*
         if (c->mb_wt) {
             long long z = 0;
             HIP_TRY(c, hipSetDevice(c->device));
-            hipLaunchKernelGGL(k_mb_count, dim3(1), dim3(256), 0, c->stream, c->mb_wt, c->mb_K, c->mb_zeros);
-            HIP_TRY(c, hipGetLastError());
+            if (c->mbp_pops) {                                // bank 0's, over the cells of its own population
+                int rc = mbpop_count(c);
+                if (rc) return rc;
+            } else {
+                hipLaunchKernelGGL(k_mb_count, dim3(1), dim3(256), 0, c->stream, c->mb_wt, c->mb_K, c->mb_zeros);
+                HIP_TRY(c, hipGetLastError());
+            }
             HIP_TRY(c, hipMemcpyAsync(&z, c->mb_zeros, sizeof z, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             *n_depressed = (int64_t)z;
@@ -737,6 +776,7 @@ extern "C" int dv_mbank_set(dv_ctx* c, int n_banks) {
     c->mb_zeros = zeros;
     c->mb_banks = n_banks;
     c->mb_views.assign((size_t)n_banks, 0);
+    mbpop_drop(c);                                            // the banks are the begin's population's again
     return DV_OK;
 }
 
@@ -809,13 +849,21 @@ static int mbank_one(dv_ctx* c, const char* who, int bank) {
     return DV_OK;
 }
 
+// Where bank `bank` lies in mb_wt and how long it is: n_kc of the model, or under a population table of the bank's own population.
+static void mbank_span(const dv_ctx* c, int bank, size_t& off, size_t& len) {
+    if (c->mbp_pops) { off = c->mbp_wt_off[(size_t)bank]; len = (size_t)c->mbp_K[(size_t)c->mbp_of_bank[(size_t)bank]]; }
+    else { off = (size_t)bank * (size_t)c->mb_K; len = (size_t)c->mb_K; }
+}
+
 extern "C" int dv_mbank_read_weights(dv_ctx* c, int bank, uint8_t* out) {
     if (!c) return DV_ERR_INVALID;
     int rc = mbank_one(c, "dv_mbank_read_weights", bank);
     if (rc) return rc;
     if (!out) return fail(c, DV_ERR_INVALID, "dv_mbank_read_weights: out is NULL");
+    size_t off, len;
+    mbank_span(c, bank, off, len);
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(out, c->mb_wt + (size_t)bank * (size_t)c->mb_K, (size_t)c->mb_K, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out, c->mb_wt + off, len, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return DV_OK;
 }
@@ -825,10 +873,12 @@ extern "C" int dv_mbank_set_weights(dv_ctx* c, int bank, const uint8_t* weights)
     int rc = mbank_one(c, "dv_mbank_set_weights", bank);
     if (rc) return rc;
     if (!weights) return fail(c, DV_ERR_INVALID, "dv_mbank_set_weights: weights is NULL");
-    for (int k = 0; k < c->mb_K; ++k)
-        if (weights[k] > 1) return fail(c, DV_ERR_INVALID, "dv_mbank_set_weights: weights[%d] = %d is neither 0 nor 1", k, (int)weights[k]);
+    size_t off, len;
+    mbank_span(c, bank, off, len);
+    for (size_t k = 0; k < len; ++k)
+        if (weights[k] > 1) return fail(c, DV_ERR_INVALID, "dv_mbank_set_weights: weights[%d] = %d is neither 0 nor 1", (int)k, (int)weights[k]);
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(c->mb_wt + (size_t)bank * (size_t)c->mb_K, weights, (size_t)c->mb_K, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->mb_wt + off, weights, len, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));              // `weights` is borrowed for this call only
     return DV_OK;
 }
@@ -843,8 +893,13 @@ extern "C" int dv_mbank_info(dv_ctx* c, int* n_banks, int64_t* views_trained, in
         if (c->mb_wt) {
             std::vector<long long> z(B);
             HIP_TRY(c, hipSetDevice(c->device));
-            hipLaunchKernelGGL(k_mb_count, dim3((unsigned)B), dim3(256), 0, c->stream, c->mb_wt, c->mb_K, c->mb_zeros);
-            HIP_TRY(c, hipGetLastError());
+            if (c->mbp_pops) {                                // ragged banks: each over its own population's cells
+                int rc = mbpop_count(c);
+                if (rc) return rc;
+            } else {
+                hipLaunchKernelGGL(k_mb_count, dim3((unsigned)B), dim3(256), 0, c->stream, c->mb_wt, c->mb_K, c->mb_zeros);
+                HIP_TRY(c, hipGetLastError());
+            }
             HIP_TRY(c, hipMemcpyAsync(z.data(), c->mb_zeros, B * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             for (size_t b = 0; b < B; ++b) n_depressed[b] = (int64_t)z[b];

@@ -275,6 +275,10 @@ PROTOTYPES = {
     "dv_mbank_read_weights": (ctypes.c_int, [_ctx_p, ctypes.c_int, _u8p]),
     "dv_mbank_set_weights": (ctypes.c_int, [_ctx_p, ctypes.c_int, _u8p]),
     "dv_mbank_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "dv_mbpop_set": (ctypes.c_int, [_ctx_p, ctypes.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, ctypes.c_int, _i32p]),
+    "dv_mbpop_clear": (ctypes.c_int, [_ctx_p]),
+    "dv_mbpop_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _i32p, _i32p, _i32p, _i32p, _i32p,
+                                     ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "dv_ibank_set": (ctypes.c_int, [_ctx_p, ctypes.c_int, _f64p]),
     "dv_ibank_train_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int64, _i32p]),
     "dv_ibank_train_from_poses": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int64, _i32p, _u8p]),

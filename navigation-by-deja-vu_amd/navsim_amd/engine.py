@@ -1266,6 +1266,7 @@ class FamiliarityEngine(object):
                                           conn.ctypes.data_as(N._i32p)), "dv_mb_begin")
         self.mb_shape = (int(h), int(w))
         self.mb_banks = 1
+        self.mb_pops = None
 
     def mb_train_u8(self, planes):
         """Depress the cells that fire for each of uint8[n,h,w] planes: one launch for all of them, in no order."""
@@ -1328,6 +1329,7 @@ class FamiliarityEngine(object):
         self._check(self._lib.dv_mb_end(self._ctx), "dv_mb_end")
         self.mb_shape = None
         self.mb_banks = 1
+        self.mb_pops = None
 
     # -- memory banks of the mushroom-body model: several memories behind one connectivity (include/dejavu.h: dv_mbank_*) ---------
     mb_banks = 1                 # memories of the model (mbank_set; 1 after mb_begin)
@@ -1345,6 +1347,7 @@ class FamiliarityEngine(object):
             raise ValueError("n_banks must be an integer >= 1, got %r" % (n_banks,))
         self._check(self._lib.dv_mbank_set(self._ctx, int(n_banks)), "dv_mbank_set")
         self.mb_banks = int(n_banks)
+        self.mb_pops = None
 
     def mbank_train_u8(self, planes, bank_of_view):
         """mb_train_u8 with view v depressing bank bank_of_view[v]: the views of all banks in the same launches."""
@@ -1363,10 +1366,21 @@ class FamiliarityEngine(object):
         """mb_sense_step_batch with member i scored under bank bank_of_member[i] -> OneValueBatchResults: one enqueue and one wait."""
         return self._bank_sense_step_batch("mushroom", x, y, angles, bank_of_member, land_of_member)
 
+    def _bank_cells(self, bank):
+        """n_kc of bank `bank` under the live population table."""
+        return self.mb_pops[self.mb_pop_of_bank[bank]]["n_kc"]
+
     def mbank_read_weights(self, bank=None):
-        """uint8[n_kc] of one bank; bank=None: all of them, uint8[n_banks, n_kc]."""
+        """uint8[n_kc] of one bank; bank=None: all of them, uint8[n_banks, n_kc] -- or, while a population table is live (mbpop_set), a
+        list of n_banks arrays, each uint8[n_kc of the bank's own population]: the banks are ragged."""
         if bank is not None:
             bank = self._bank_index(bank)
+        if self.mb_pops is not None:
+            out = []
+            for b in (range(self.mb_banks) if bank is None else (bank,)):
+                out.append(np.empty(self._bank_cells(b), dtype=np.uint8))
+                self._check(self._lib.dv_mbank_read_weights(self._ctx, b, N.u8ptr(out[-1])), "dv_mbank_read_weights")
+            return out if bank is None else out[0]
         n_kc = max(self.mb_info()["n_kc"], 1)
         out = np.empty((self.mb_banks if bank is None else 1, n_kc), dtype=np.uint8)
         for row, b in enumerate(range(self.mb_banks) if bank is None else (bank,)):
@@ -1375,7 +1389,7 @@ class FamiliarityEngine(object):
 
     def mbank_set_weights(self, bank, weights):
         bank = self._bank_index(bank)
-        n_kc = self.mb_info()["n_kc"]
+        n_kc = self._bank_cells(bank) if self.mb_pops is not None else self.mb_info()["n_kc"]
         weights = N.as_u8(weights, "weights")
         if n_kc and weights.shape != (n_kc,):
             raise ValueError("weights must be uint8[%d], got shape %r" % (n_kc, weights.shape))
@@ -1390,6 +1404,91 @@ class FamiliarityEngine(object):
         i64p = ctypes.POINTER(ctypes.c_int64)
         self._check(self._lib.dv_mbank_info(self._ctx, None, views.ctypes.data_as(i64p), zeros.ctypes.data_as(i64p)), "dv_mbank_info")
         return dict(n_banks=nb.value, views_trained=views, n_depressed=zeros)
+
+    # -- population tables of the mushroom-body model: a bank's own cells, wiring, quota and channel (include/dejavu.h: dv_mbpop_*) --
+    mb_pops = None               # the live table's populations, dict(channel, n_kc, fan_in, n_active) each (mbpop_set; None: no table)
+    mb_pop_of_bank = None        # int32[n_banks]: the population of every bank of the live table
+    MB_MAX_CELLS, MB_MAX_FAN_IN = 1 << 24, 16
+
+    @classmethod
+    def _population(cls, p, pop, n_pixels):
+        """populations[p] as (dict(channel, n_kc, fan_in, n_active), conn int32[n_kc, fan_in]), or ValueError naming the entry.
+        n_pixels: h * w of the model (None: no model yet, and the library answers DV_ERR_STATE)."""
+        who = "populations[%d]" % p
+        if not isinstance(pop, dict) or "conn" not in pop or "n_active" not in pop:
+            raise ValueError("%s must be a dict with conn and n_active (util.mushroom_population makes one)" % who)
+        extra = sorted(set(pop) - {"conn", "n_active", "channel", "n_kc", "fan_in", "seed", "sparsity"})
+        if extra:
+            raise ValueError("%s: unknown keys %r" % (who, extra))
+        conn = np.asarray(pop["conn"])
+        if conn.dtype.kind not in "iu":
+            raise ValueError("%s: conn must hold integers, got dtype %s" % (who, conn.dtype))
+        if conn.ndim != 2:
+            raise ValueError("%s: conn must be int32[n_kc, fan_in], got shape %r" % (who, conn.shape))
+        n_kc, fan_in = conn.shape
+
+        def whole(v):
+            return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+        for key, have in (("n_kc", n_kc), ("fan_in", fan_in)):
+            if key in pop and not (whole(pop[key]) and pop[key] == have):
+                raise ValueError("%s: %s = %r, but conn has shape %r" % (who, key, pop[key], conn.shape))
+        if not 1 <= n_kc <= cls.MB_MAX_CELLS:
+            raise ValueError("%s: n_kc %d outside [1, %d]" % (who, n_kc, cls.MB_MAX_CELLS))
+        if not 1 <= fan_in <= cls.MB_MAX_FAN_IN:
+            raise ValueError("%s: fan_in %d outside [1, %d]" % (who, fan_in, cls.MB_MAX_FAN_IN))
+        n_active, channel = pop["n_active"], pop.get("channel", 2)
+        if not (whole(n_active) and 1 <= n_active <= n_kc):
+            raise ValueError("%s: n_active %r outside [1, n_kc = %d]" % (who, n_active, n_kc))
+        if not (whole(channel) and 0 <= channel <= 2):
+            raise ValueError("%s: channel %r outside [0, 2]" % (who, channel))
+        if n_pixels is not None and (conn.min() < 0 or conn.max() >= n_pixels):
+            k, j = np.argwhere((conn < 0) | (conn >= n_pixels))[0]
+            raise ValueError("%s: conn[%d][%d] = %d outside [0, %d)" % (who, k, j, conn[k, j], n_pixels))
+        return dict(channel=int(channel), n_kc=int(n_kc), fan_in=int(fan_in), n_active=int(n_active)), np.ascontiguousarray(conn, dtype=np.int32)
+
+    def mbpop_set(self, populations, population_of_bank):
+        """A population table: populations is a list of dicts (util.mushroom_population: channel, n_kc, fan_in, n_active, conn
+        int32[n_kc, fan_in] over the model's h * w pixels), population_of_bank names every bank's population (its length is the number
+        of banks; several banks may share one).  All weights 1; what was trained is dropped.  From here on the mbank_* calls train and
+        score every view and member through its bank's own cells, wiring, quota and channel, and the mb_* calls (bank 0 behind the
+        begin's wiring) are refused until mbpop_clear, mbank_set, mb_begin or mb_end.  Every entry is checked here, before any library
+        call; ValueError names it."""
+        if isinstance(populations, dict) or not hasattr(populations, "__len__") or len(populations) < 1:
+            raise ValueError("populations must be a list of one or more dicts (util.mushroom_population), got %r" % (type(populations).__name__,))
+        n_pixels = None if self.mb_shape is None else self.mb_shape[0] * self.mb_shape[1]
+        pops, conns = zip(*[self._population(p, pop, n_pixels) for p, pop in enumerate(populations)])
+        of_bank = self._index_table(population_of_bank, "population_of_bank", len(pops), "n_pops", per="population")
+        if len(of_bank) < 1:
+            raise ValueError("population_of_bank must name the population of one or more banks, got none")
+        col = lambda key: np.array([p[key] for p in pops], dtype=np.int32)
+        n_kc, fan_in, n_active, channel = col("n_kc"), col("fan_in"), col("n_active"), col("channel")
+        concat = np.ascontiguousarray(np.concatenate([c.reshape(-1) for c in conns]), dtype=np.int32)
+        i32 = lambda a: a.ctypes.data_as(N._i32p)
+        self._check(self._lib.dv_mbpop_set(self._ctx, len(pops), i32(n_kc), i32(fan_in), i32(n_active), i32(channel), i32(concat), len(of_bank),
+                                           i32(of_bank)), "dv_mbpop_set")
+        self.mb_pops, self.mb_pop_of_bank, self.mb_banks = list(pops), of_bank, len(of_bank)
+
+    def mbpop_clear(self):
+        """Back to one bank of the population mb_begin made, weights 1."""
+        self._check(self._lib.dv_mbpop_clear(self._ctx), "dv_mbpop_clear")
+        self.mb_pops, self.mb_pop_of_bank, self.mb_banks = None, None, 1
+
+    def mbpop_info(self):
+        """dict(n_pops, n_banks, n_kc / fan_in / n_active / channel int32[n_pops], population_of_bank int32[n_banks], views_trained /
+        n_depressed int64[n_banks], bytes); n_pops = n_banks = 0 and empty arrays without a table."""
+        P, B, nbytes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+        self._check(self._lib.dv_mbpop_info(self._ctx, ctypes.byref(P), ctypes.byref(B), None, None, None, None, None, None, None,
+                                            ctypes.byref(nbytes)), "dv_mbpop_info")
+        per_pop = [np.zeros(P.value, dtype=np.int32) for _ in range(4)]
+        of_bank = np.zeros(B.value, dtype=np.int32)
+        views, zeros = np.zeros(B.value, dtype=np.int64), np.zeros(B.value, dtype=np.int64)
+        if P.value:
+            self._check(self._lib.dv_mbpop_info(self._ctx, None, None, *([a.ctypes.data_as(N._i32p) for a in per_pop] +
+                                                [of_bank.ctypes.data_as(N._i32p), views.ctypes.data_as(N._i64p), zeros.ctypes.data_as(N._i64p), None])),
+                        "dv_mbpop_info")
+        return dict(n_pops=P.value, n_banks=B.value, n_kc=per_pop[0], fan_in=per_pop[1], n_active=per_pop[2], channel=per_pop[3],
+                    population_of_bank=of_bank, views_trained=views, n_depressed=zeros, bytes=nbytes.value)
 
     # -- landscape sets: several landscapes resident together, a landscape per pose (include/dejavu.h: dv_lands_*) -----------------
     n_lands = 0                  # landscapes of the set (lands_set; 0: none)

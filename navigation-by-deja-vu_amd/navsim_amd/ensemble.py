@@ -528,15 +528,23 @@ class _RouteEnsemble(_OneValueEnsemble):
         return cls.from_routes_with(agent, routes, starts)
 
     @classmethod
-    def from_routes_with(cls, agent, routes, starts, metrics="host"):
+    def from_routes_with(cls, agent, routes, starts, metrics="host", populations=None):
         """from_routes with the members' error metrics on the host ("host": every member's own NumPy pass, as from_routes) or on the
-        device ("device": all members' in one call per ensemble step, each against its own route; see the class)."""
-        return cls._from_routes(agent, routes, starts, metrics, None, None)
+        device ("device": all members' in one call per ensemble step, each against its own route; see the class).
+        populations (MushroomRouteEnsemble): None, or a list with one entry per route, the route's own model parameters -- see
+        MushroomRouteEnsemble."""
+        return cls._from_routes(agent, routes, starts, metrics, None, None, populations=populations)
 
     @classmethod
-    def _from_routes(cls, agent, routes, starts, metrics, lands, land_of_route, sensors=None):
+    def _population_entries(cls, agent, model, n_routes, populations):
+        """`populations` as (the distinct populations, population_of_route), or ValueError naming the entry."""
+        raise ValueError("%s has no populations: MushroomRouteEnsemble gives every route's bank cells and wiring of its own" % cls.__name__)
+
+    @classmethod
+    def _from_routes(cls, agent, routes, starts, metrics, lands, land_of_route, sensors=None, populations=None):
         """from_routes_with (lands None: every route on the agent's own landscape, the engine's one), or from_landscapes (route r on
-        lands[land_of_route[r]] of the engine's landscape set; sensors: None, or _sensor_entries' entry per landscape)."""
+        lands[land_of_route[r]] of the engine's landscape set; sensors: None, or _sensor_entries' entry per landscape).
+        populations: None, or from_routes_with's list (an entry per route)."""
         import copy
         if metrics not in cls.METRICS:
             raise ValueError("metrics must be one of %r, got %r" % (cls.METRICS, metrics))
@@ -557,6 +565,8 @@ class _RouteEnsemble(_OneValueEnsemble):
         for i, (r, _, _) in enumerate(starts):
             if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 0 <= r < len(routes):
                 raise ValueError("starts[%d]: route_index %r outside [0, %d)" % (i, r, len(routes)))
+        pops = None if populations is None else cls._population_entries(agent, model, len(routes), populations)
+        table = {} if pops is None else dict(populations=pops)    # (_train_banks' extra argument, only where there is a table)
         for k, route in enumerate(routes):                        # (the agent's own bounds test, on the route's own landscape)
             probe = agent if lands is None else cls._on_landscape(copy.copy(agent), lands[land_of_route[k]],
                                                                   None if sensors is None else sensors[land_of_route[k]])
@@ -573,14 +583,14 @@ class _RouteEnsemble(_OneValueEnsemble):
         bank_of_view = np.repeat(np.arange(len(routes), dtype=np.int32), [len(r) for r in routes])
         cls._begin_model(model, eng, agent)
         if lands is None:
-            views = cls._train_banks(eng, len(routes), points[:, 0], points[:, 1], np.concatenate(headings), bank_of_view)
+            views = cls._train_banks(eng, len(routes), points[:, 0], points[:, 1], np.concatenate(headings), bank_of_view, **table)
         else:
             eng.lands_set(lands)
             if sensors is not None:
                 eng.sensors_set([e["sensor_pixel_dimensions"] for e in sensors], np.stack([e["lut"] for e in sensors]),
                                 [e["mask_middle_n"] for e in sensors])
             land_of_view = np.repeat(np.array(land_of_route, dtype=np.int32), [len(r) for r in routes])
-            views = cls._train_banks(eng, len(routes), points[:, 0], points[:, 1], np.concatenate(headings), bank_of_view, land_of_view)
+            views = cls._train_banks(eng, len(routes), points[:, 0], points[:, 1], np.concatenate(headings), bank_of_view, land_of_view, **table)
         func = model.from_engine(eng, views)
         members = []
         for k, (r, pos, ang) in enumerate(starts):
@@ -591,6 +601,8 @@ class _RouteEnsemble(_OneValueEnsemble):
             a.familiar_scenes = views[first[r]:first[r + 1]]
             a._familiarity_func = func
             a.memory_bank = int(r)
+            a.population_index = None if pops is None else int(pops[1][r])
+            a.population = None if pops is None else {k: v for k, v in pops[0][a.population_index].items() if k != "conn"}
             if lands is not None:
                 a.landscape_index = land_of_route[r]
                 cls._on_landscape(a, lands[a.landscape_index], None if sensors is None else sensors[a.landscape_index])
@@ -664,7 +676,7 @@ class _RouteEnsemble(_OneValueEnsemble):
         return out
 
     @classmethod
-    def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host", sensors=None):
+    def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host", sensors=None, populations=None):
         """Trials that differ in their LANDSCAPE, their training route and their start.  `agent`: an UNTRAINED agent of the ensemble's
         model with the GPU sensor model; landscapes: a list of uint8[rows, cols, 3] of any shapes; routes: a list of
         (landscape_index, float64[n_r, 2]); starts and metrics as from_routes_with.  The landscapes become the engine's landscape set,
@@ -675,7 +687,8 @@ class _RouteEnsemble(_OneValueEnsemble):
         None (the agent's own configuration) or a dict with any of sensor_pixel_dimensions, n_sensor_levels and mask_middle_n, the
         sensor landscape l is sensed with; sensor_dimensions is refused (w × h is the engine's one).  Two sensors on one landscape:
         enter the landscape twice.  The members of a route on landscape l carry that entry's configuration and `sensor_index`, so
-        their bounds are their own footprint's and their get_sensor_mat senses under their own entry."""
+        their bounds are their own footprint's and their get_sensor_mat senses under their own entry.
+        populations: as from_routes_with's, an entry per route."""
         lands = [np.asarray(l) for l in landscapes]
         if not lands or any(l.dtype != np.uint8 or l.ndim != 3 or l.shape[2] != 3 for l in lands):
             raise ValueError("landscapes must be one or more arrays uint8[rows, cols, 3]")
@@ -688,7 +701,7 @@ class _RouteEnsemble(_OneValueEnsemble):
                 raise ValueError("routes[%d]: landscape_index %r outside [0, %d)" % (k, l, len(lands)))
         land_of_route = [int(l) for l, _ in routes]
         entries = None if sensors is None else cls._sensor_entries(agent, len(lands), sensors)
-        return cls._from_routes(agent, [pts for _, pts in routes], starts, metrics, lands, land_of_route, entries)
+        return cls._from_routes(agent, [pts for _, pts in routes], starts, metrics, lands, land_of_route, entries, populations=populations)
 
     def _device_step(self, idx, xs, ys, angs):
         if self._lands is not None:
@@ -708,7 +721,16 @@ class MushroomRouteEnsemble(_RouteEnsemble):
     landscape, scripts/run_experiment.py:57,208): the model's connectivity is shared, and every route has a memory bank of its own
     (FamiliarityEngine.mbank_set: n_kc bytes a route).  All routes are trained in one device call, and a step scores every running
     member's headings under its own route's bank in ONE device call (dv_mbank_sense_step), with the bits a lone agent trained on that
-    route alone gives at the same pose.  Made by from_routes (see _RouteEnsemble)."""
+    route alone gives at the same pose.  Made by from_routes (see _RouteEnsemble).
+
+    from_routes_with / from_landscapes(populations=[...]) makes trials that differ in the MODEL's own parameters too (capacity sweeps,
+    replicates over the random wiring): the list has one entry per route, None (the agent's model) or a dict with any of n_kc, fan_in,
+    sparsity, seed and channel -- a key an entry leaves out takes the model's value.  Equal entries share one population of the
+    engine's population table (FamiliarityEngine.mbpop_set), and every route's bank has the cells, wiring, quota and channel of its
+    entry; a route under two populations is entered twice, as a landscape under two sensors is.  Members carry `population_index` and
+    `population` (dict(channel, n_kc, fan_in, n_active, sparsity, seed)); both are None without populations.  A member's rows are those
+    of a lone agent built with mushroom_familiarity of its population and trained on its route alone."""
+    POPULATION_KEYS = ("n_kc", "fan_in", "sparsity", "seed", "channel")
     _metric = "mushroom"
     _takes = MushroomEnsemble._takes
     _batch_call = "mbank_sense_step_batch"
@@ -717,11 +739,56 @@ class MushroomRouteEnsemble(_RouteEnsemble):
     _reject_others = MushroomEnsemble._reject_others
 
     @staticmethod
-    def _train_banks(eng, n_routes, x, y, headings, bank_of_view, land_of_view=None):
-        eng.mbank_set(n_routes)
+    def _train_banks(eng, n_routes, x, y, headings, bank_of_view, land_of_view=None, populations=None):
+        if populations is None:
+            eng.mbank_set(n_routes)
+        else:
+            eng.mbpop_set(*populations)                           # bank r is route r's, behind its entry's population
         if land_of_view is None:
             return eng.mbank_train_from_poses(x, y, headings, bank_of_view)
         return eng.mbank_train_from_poses(x, y, headings, bank_of_view, land_of_view=land_of_view)
+
+    @classmethod
+    def _population_entries(cls, agent, model, n_routes, populations):
+        from .util import mushroom_population
+        if isinstance(populations, dict) or not hasattr(populations, "__len__") or len(populations) != n_routes:
+            raise ValueError("populations must be a list with one entry per route (%d), each None or a dict with any of %r"
+                             % (n_routes, cls.POPULATION_KEYS))
+        own = {k: getattr(model, k) for k in cls.POPULATION_KEYS}
+        n_pixels = int(agent.sensor_dimensions[0]) * int(agent.sensor_dimensions[1])
+        keys, pops, of_route = [], [], []
+        for r, entry in enumerate(populations):
+            if entry is not None and not isinstance(entry, dict):
+                raise ValueError("populations[%d] must be None or a dict with any of %r" % (r, cls.POPULATION_KEYS))
+            extra = sorted(set(entry or {}) - set(cls.POPULATION_KEYS))
+            if extra:
+                raise ValueError("populations[%d]: unknown keys %r (an entry holds any of %r)" % (r, extra, cls.POPULATION_KEYS))
+            spec = dict(own, **(entry or {}))
+            try:
+                key = tuple(spec[k] for k in cls.POPULATION_KEYS)
+                if key not in keys:
+                    pop = mushroom_population(n_pixels, **spec)
+                    keys.append(key)
+                    pops.append(dict(pop, sparsity=spec["sparsity"], seed=spec["seed"]))
+            except (ValueError, TypeError) as e:
+                raise ValueError("populations[%d]: %s" % (r, e))
+            of_route.append(keys.index(key))
+        return pops, np.array(of_route, dtype=np.int32)
+
+    def bank_info(self):
+        """_RouteEnsemble.bank_info, and per bank n_kc, n_active and population_of_bank (zeros without populations), so that a bank's
+        fill is n_depressed / n_kc."""
+        info = dict(super(MushroomRouteEnsemble, self).bank_info())
+        pops, n = getattr(self.engine, "mb_pops", None), int(info["n_banks"])
+        if pops is None:
+            model = self.agents[0].familiarity_model
+            of_bank = np.zeros(n, dtype=np.int32)
+            pops = [dict(n_kc=model.n_kc, n_active=model.n_active)]
+        else:
+            of_bank = np.asarray(self.engine.mb_pop_of_bank, dtype=np.int32)
+        info.update(n_kc=np.array([pops[p]["n_kc"] for p in of_bank], dtype=np.int64),
+                    n_active=np.array([pops[p]["n_active"] for p in of_bank], dtype=np.int64), population_of_bank=of_bank)
+        return info
 
 
 class InfomaxRouteEnsemble(_RouteEnsemble):

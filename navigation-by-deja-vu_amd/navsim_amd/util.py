@@ -289,6 +289,17 @@ def mushroom_connectivity(n_kc, n_pixels, fan_in, seed=0):
     return np.random.default_rng(seed).integers(0, int(n_pixels), (int(n_kc), int(fan_in))).astype(np.int32)
 
 
+def mushroom_population(n_pixels, n_kc=20000, fan_in=10, sparsity=0.01, seed=0, channel=2):
+    """One population of a mushroom-body population table (FamiliarityEngine.mbpop_set) over views of n_pixels pixels:
+    dict(channel, n_kc, fan_in, n_active, conn) with conn = mushroom_connectivity(n_kc, n_pixels, fan_in, seed) and
+    n_active = max(1, round(sparsity * n_kc)) -- what mushroom_familiarity of the same arguments begins its engine with."""
+    if isinstance(n_pixels, bool) or not isinstance(n_pixels, (int, np.integer)) or n_pixels < 1:
+        raise ValueError("n_pixels must be a positive integer, got %r" % (n_pixels,))
+    model = mushroom_familiarity(channel=channel, n_kc=n_kc, fan_in=fan_in, sparsity=sparsity, seed=seed)      # (its argument checks)
+    return dict(channel=int(channel), n_kc=int(n_kc), fan_in=int(fan_in), n_active=model.n_active,
+                conn=mushroom_connectivity(n_kc, n_pixels, fan_in, seed))
+
+
 def mushroom_familiarity(channel=2, n_kc=20000, fan_in=10, sparsity=0.01, seed=0, device=0, devices=None):
     """The mushroom-body circuit of Ardin, Peng, Mangan, Lagogiannis & Webb (2016) as a familiarity plug-in of the reference's shape
     (util.pyx:10-25): a memory of fixed size and finite capacity -- one byte of output weight per Kenyon cell -- where sads_familiarity
@@ -326,4 +337,4 @@ def mushroom_familiarity(channel=2, n_kc=20000, fan_in=10, sparsity=0.01, seed=0
         """A fresh model of h x w views on `engine` (the agent calls this before it trains from poses)."""
         engine.mb_begin(h, w, mushroom_connectivity(n_kc, int(h) * int(w), fan_in, seed), n_active, channel)
 
-    return _one_value_familiarity("mushroom", channel, device, begin, n_kc=n_kc, fan_in=fan_in, n_active=n_active)
+    return _one_value_familiarity("mushroom", channel, device, begin, n_kc=n_kc, fan_in=fan_in, n_active=n_active, sparsity=sparsity, seed=seed)

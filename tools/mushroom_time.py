@@ -2,7 +2,7 @@
 """Times the mushroom-body familiarity model (navsim_amd.mushroom_familiarity; include/dejavu.h: dv_mb_*) on GPU 0 and writes
 profiles/mushroom_time.json.
 
-    python tools/mushroom_time.py [--sides 32,64] [--views 1000] [--calls 200] [--reps 5] [--blocks single,ensemble[,banks][,metrics][,lands][,rows][,sensors]]
+    python tools/mushroom_time.py [--sides 32,64] [--views 1000] [--calls 200] [--reps 5] [--blocks single,ensemble[,banks][,metrics][,lands][,rows][,sensors][,populations]]
                                   [--out profiles/mushroom_time.json]
 
 Per sensor side s (views of s x s) with K = 20000 Kenyon cells, fan-in 10 and 200 firing cells: microseconds per agent step
@@ -52,6 +52,10 @@ run_ensemble built them before: three copies of the member's marks and two Pytho
 dv_marks_summary_routes call for all members -- WALL-CLOCK microseconds per build of all rows, Python included (a window is one build
 of (a), 20 of (b)), their ratio methods_over_summary; and alone: the 3 x 32 path_routes_coverage copies of (a) without its loops (wall
 clock), and the marks_summary_routes call between a hipEvent pair.  The two builds are checked to give equal rows.
+
+Populations block (--blocks populations): per side, the banks block's two layouts under population tables (dv_mbpop_set) against the
+banked step without a table at the same poses -- a table equal to the model's, four wirings, three sizes in one table against three
+engines stepped in turn -- and one banked training call over four populations against four engines (tools/populations_block.py).
 
 A block that is not measured keeps the rows it has in the output file.
 
@@ -542,7 +546,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--limit", type=int, default=240, help="seconds allowed to each GPU child")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mushroom_time.json"))
-    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and the agent step), ensemble, banks, metrics, lands, rows, sensors")
+    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and the agent step), ensemble, banks, metrics, lands, rows, sensors, populations")
     ap.add_argument("--ensemble-calls", type=int, default=30, help="ensemble steps per timed window")
     ap.add_argument("--child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--ensemble-child", type=int, default=0, help=argparse.SUPPRESS)
@@ -572,12 +576,12 @@ def main():
         return 0
     blocks = args.blocks.split(",")
     result = dict(tool="tools/mushroom_time.py", timer="hipEvent pair (dv_timer_start/stop), median of %d windows after a warm-up" % args.reps,
-                  sizes=[], ensembles=[], banks=[], metrics=[], lands=[], rows=[], sensors=[])
+                  sizes=[], ensembles=[], banks=[], metrics=[], lands=[], rows=[], sensors=[], populations=[])
     if os.path.exists(args.out):                                  # a block that is not measured keeps its rows
         with open(args.out) as f:
             kept = json.load(f)
         for block, key in (("single", "sizes"), ("ensemble", "ensembles"), ("banks", "banks"), ("metrics", "metrics"), ("lands", "lands"), ("rows", "rows"),
-                           ("sensors", "sensors")):
+                           ("sensors", "sensors"), ("populations", "populations")):
             if block not in blocks:
                 result[key] = kept.get(key, [])
     for side in [int(x) for x in args.sides.split(",")] if "ensemble" in blocks else []:
@@ -610,6 +614,12 @@ def main():
         if rc != 0:
             return rc
         result["sensors"].append(row)
+    for side in [int(x) for x in args.sides.split(",")] if "populations" in blocks else []:
+        import populations_block
+        rc, row = populations_block.run_child(args.limit, side, args.views, args.ensemble_calls, args.reps)
+        if rc != 0:
+            return rc
+        result["populations"].append(row)
     if "metrics" in blocks:
         cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--metrics-child", "1",
                "--ensemble-calls", str(args.ensemble_calls), "--reps", str(args.reps)]

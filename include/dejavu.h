@@ -806,6 +806,46 @@ int dv_ibank_read_weights(dv_ctx *ctx, int bank, double *out);
 int dv_ibank_set_weights(dv_ctx *ctx, int bank, const double *weights);
 int dv_ibank_info(dv_ctx *ctx, int *n_banks, int64_t *views_trained, int32_t *finite);
 
+/* ---- Infomax network tables -------------------------------------------------- */
+/*
+ * Banks with hidden units, learning rate, initial weights and compared channel of their own.  A network is (channel, n_hidden,
+ * learning_rate, W0 float64[n_hidden][h * w]); the views' h x w, so n_pixels, stay the ones dv_infomax_begin fixed.  A table gives the
+ * context n_nets networks and n_banks banks; network_of_bank[b] names bank b's, and several banks may share one (routes x one network).
+ * Bank b starts as a copy of its network's W0.  The weights are ragged: bank b holds float64[n_hidden of its network][h * w].  While a
+ * table is live
+ *   - the banked calls (dv_ibank_train_u8, dv_ibank_train_from_poses, dv_lands_ibank_train_from_poses, dv_ibank_step_u8,
+ *     dv_ibank_sense_step, dv_lands_ibank_sense_step; with or without a sensor table) take no new argument: view v is trained into bank
+ *     bank_of_view[v] through that bank's n_hidden and channel at rate = learning_rate / n_pixels, in the same three launches per
+ *     lockstep step as every other bank's chain, and member i is scored in the same launches as the members of every other bank;
+ *   - a bank's weights after training have the bits of a context begun with its network (dv_infomax_begin(h, w, channel, n_hidden,
+ *     learning_rate, W0)) and trained on that bank's views alone, in their order; a bank that gets no view keeps its bits; a column of a
+ *     step has the bits dv_infomax_score_u8 gives the same patch on that context;
+ *   - dv_ibank_read_weights / dv_ibank_set_weights move n_hidden x n_pixels doubles of the bank's own network; dv_ibank_info is unchanged;
+ *   - divergence is per bank: DV_ERR_STATE names the bank and ITS OWN learning rate, the other banks hold their chains' weights and go on
+ *     working, and dv_ibank_set_weights with finite weights heals the bank;
+ *   - the calls that assume the begin's shape behind bank 0 (dv_infomax_train_u8, dv_infomax_train_from_poses, dv_infomax_score_u8,
+ *     dv_infomax_sense_step, dv_infomax_read_weights, dv_infomax_set_weights, dv_batch_infomax_step_u8, dv_batch_infomax_sense_step)
+ *     return DV_ERR_STATE, naming dv_inet_clear;
+ *   - dv_infomax_info keeps describing the model dv_infomax_begin made (n_hidden, n_pixels, bytes); its two counts, views_trained and
+ *     finite, are bank 0's.
+ * Without a table every call launches what it launched before there were tables.
+ *   set     w0_concat holds network p's float64[n_hidden[p]][h * w], one after another.  DV_ERR_STATE without a model.  Every entry is
+ *           checked as dv_infomax_begin checks its own -- n_hidden in [1, 2^20], learning_rate finite and > 0, channel in [0, 2],
+ *           network_of_bank in [0, n_nets), n_banks in [1, 65535] -- before anything reaches the device: DV_ERR_INVALID names the network
+ *           and the entry.  All view counts start at 0 (whatever was trained before is dropped).  Everything is allocated and every copy
+ *           waited for before the table is installed: on a failure the model, its banks and an earlier table stay as they were.
+ *   clear   back to one bank of the begin's network at the W0 dv_infomax_begin was given.  dv_ibank_set, dv_infomax_begin and
+ *           dv_infomax_end drop the table too.
+ *   info    n_nets and n_banks (both 0 without a table); per network n_hidden, learning_rate, channel (the caller's arrays of n_nets
+ *           entries); per bank network_of_bank, views_trained, finite (arrays of n_banks entries); bytes: the table's device bytes
+ *           (weights, h, u, partial sums, flags, descriptors).  Ask for the counts first; any pointer may be NULL.
+ */
+int dv_inet_set(dv_ctx *ctx, int n_nets, const int32_t *n_hidden, const double *learning_rate, const int32_t *channel,
+                const double *w0_concat, int n_banks, const int32_t *network_of_bank);
+int dv_inet_clear(dv_ctx *ctx);
+int dv_inet_info(dv_ctx *ctx, int *n_nets, int *n_banks, int32_t *n_hidden, double *learning_rate, int32_t *channel,
+                 int32_t *network_of_bank, int64_t *views_trained, int32_t *finite, int64_t *bytes);
+
 /* ---- landscape sets ---------------------------------------------------------- */
 /*
  * Several HSV landscapes of any shapes resident together in ONE context, and a landscape index per pose in the sensed calls of the

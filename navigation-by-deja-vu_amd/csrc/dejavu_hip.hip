@@ -350,6 +350,18 @@ struct dv_ctx {
     MirroredTable im_ktab;
     std::vector<double> im_kpose;             // a banked step's poses in bank order: x, y, angles
     std::vector<uint8_t> im_kplanes;          // ... or its uploaded planes
+    // network table of the model (dejavu_inet.inl: dv_inet_*): the banks' own n_hidden, learning rate, W0 and channel; inet_nets == 0: none,
+    // and im_W is [im_banks][im_M][im_N].  Live: im_W, im_kh[0] (both h, the second inet_h_stride doubles on) and im_kupart are ragged,
+    // bank b's rows beginning at inet_row0[b]; im_M, im_channel and im_eta (the begin's network) are what dv_infomax_info describes.
+    int inet_nets = 0;
+    MirroredTable inet_desc;                  // [im_banks] dv::InetBank: what a workgroup reads of its bank
+    std::vector<int> inet_M, inet_channel;    // [inet_nets]
+    std::vector<double> inet_eta;             // [inet_nets]
+    std::vector<int> inet_of_bank;            // [im_banks]: the bank's network
+    std::vector<size_t> inet_row0;            // [im_banks + 1]: prefix sums of the banks' n_hidden
+    int inet_max_M = 0;                       // the largest n_hidden of the table: what the grids are sized for
+    size_t inet_h_stride = 0, inet_bytes = 0; // doubles from a bank's first h to its second; the table's device bytes
+    std::vector<double> im_w0;                // the W0 dv_infomax_begin was given: what dv_inet_clear returns bank 0 to
     // mushroom-body familiarity model (dejavu_mushroom.inl): fixed fan-in, one byte of weight per Kenyon cell; independent of the above
     unsigned short* mb_conn = nullptr;        // [fan_in][K]: input j of every cell
     unsigned char* mb_wt = nullptr;           // [mb_banks][K]: 1, or 0 once depressed (bank 0 is the dv_mb_* calls' memory)
@@ -3809,6 +3821,7 @@ extern "C" int dv_stream_read_gbps(dv_ctx* c, int64_t n_bytes, int iters, double
 #include "dejavu_rvreloc.inl"   // k_rvreloc_*: lost windowed members re-localise inside the step, planned and scored on the device (kernels and host side)
 #include "dejavu_rvwin.inl"     // dv_rvwin_*: windowed perfect memory on the route view store, scored in one fused launch (kernel and host side)
 #include "dejavu_infomax.inl"  // dv_infomax_*: the Infomax familiarity model (kernels and host side)
+#include "dejavu_inet.inl"      // dv_inet_*: network tables, a bank's own n_hidden, learning rate, W0 and channel (kernels and host side)
 #include "dejavu_mushroom.inl"  // dv_mb_*: the mushroom-body familiarity model (kernels and host side)
 #include "dejavu_mbpop.inl"     // dv_mbpop_*: population tables, a bank's own cells, wiring and channel (kernels and host side)
 #include "dejavu_path_routes.inl"   // dv_path_routes_*: the error / coverage metrics against several routes (host side)

@@ -33,6 +33,12 @@
 // k_im_score_cols over column blocks that never mix banks (a table of blocks from the host: the members sorted by bank),
 // k_im_decide_banks maps the columns back to the caller's members, k_im_finite_banks has a flag word per bank.
 //
+// Network tables (dejavu_inet.inl).  A live table (c->inet_nets > 0) gives every bank an n_hidden, a learning rate, a W0 and a channel of
+// its own: W, h and upart are then ragged, and the banked host paths below (ibank_train_device, ibank_batch, the banks' finite flags,
+// weights and error messages) hand over to k_inet_*, which are this file's device functions on a per-bank descriptor.  The kernels of
+// this file are launched only without a table, and the calls that assume the begin's shape behind bank 0 are refused while one is
+// live (infomax_need_bank0).
+//
 // A heading's column of H does not depend on how many headings ride with it (an MFMA result element is its own dot product), which
 // is what lets the agent's fused step and a plug-in call on one patch agree bit for bit.
 namespace dv {
@@ -446,6 +452,18 @@ __global__ __launch_bounds__(256) void k_im_decide_banks(const double* __restric
 static constexpr long long kImMaxPixels = 1 << 20;            // N of a view
 static constexpr size_t kImStageBytes = 64u << 20;            // x vectors and uploaded planes are staged in slabs of at most this
 
+// Network tables (dejavu_inet.inl, which follows this file): a live one (c->inet_nets > 0) gives every bank a shape, a rate and a channel
+// of its own, and the banked calls below go through its kernels.
+static void inet_drop(dv_ctx* c);
+static int inet_prep(dv_ctx* c, const unsigned char* d_src, long long view_stride, int px_stride, int by_channel, long long n, double* x,
+                     const int* d_bank_of, long long col0, int per);
+static int inet_train_slab(dv_ctx* c, const unsigned char* d_src, long long view_stride, int px_stride, long long nb, const int* d_tab, const int* d_idx,
+                           const int* d_bank_of, int steps);
+static int inet_finite(dv_ctx* c);
+static int inet_score(dv_ctx* c, const dv::ImBlock* d_blocks, size_t nk, long long c0, long long cpad);
+static int inet_decide(dv_ctx* c, int n_agents, long long cpad, int A, const int* perr, const int* d_mem, const int* d_bank_of, double* d_fam, int* d_best,
+                       unsigned* d_flags);
+
 static void infomax_free(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
     F(c->im_W); F(c->im_h[0]); F(c->im_h[1]); F(c->im_u); F(c->im_upart); F(c->im_xs); F(c->im_sx); F(c->im_dpart); F(c->im_d); F(c->im_flag);
@@ -455,6 +473,8 @@ static void infomax_free(dv_ctx* c) {
     c->im_xs_cap = 0;
     F(c->im_kh[0]); F(c->im_kh[1]); F(c->im_ku); F(c->im_kupart);
     table_free(c->im_ktab);
+    inet_drop(c);
+    c->im_w0.clear();
     c->im_banks = 1;
     c->im_views.assign(1, 0);
     c->im_finite.assign(1, 1);
@@ -465,12 +485,35 @@ static int infomax_need(dv_ctx* c, const char* who) {
     return DV_OK;
 }
 
+// The calls that assume the begin's shape behind bank 0 (dv_infomax_*, dv_batch_infomax_*): refused while a network table is live.
+static int infomax_need_bank0(dv_ctx* c, const char* who) {
+    int rc = infomax_need(c, who);
+    if (rc) return rc;
+    if (c->inet_nets)
+        return fail(c, DV_ERR_STATE, "%s: a network table is live, and bank 0 is no longer the model dv_infomax_begin made (dv_inet_clear first, or the dv_ibank_ call)", who);
+    return DV_OK;
+}
+
+// Where bank `bank` lies in im_W, in doubles, and how many it holds: M N of the model, or under a network table of the bank's own network.
+static void ibank_span(const dv_ctx* c, int bank, size_t& off, size_t& len) {
+    const size_t N = (size_t)c->im_N;
+    if (c->inet_nets) { off = c->inet_row0[(size_t)bank] * N; len = (size_t)c->inet_M[(size_t)c->inet_of_bank[(size_t)bank]] * N; }
+    else { len = (size_t)c->im_M * N; off = (size_t)bank * len; }
+}
+
+// The learning rate bank `bank` is trained with: the model's, or under a network table its own network's.
+static double ibank_eta(const dv_ctx* c, int bank) {
+    return c->inet_nets ? c->inet_eta[(size_t)c->inet_of_bank[(size_t)bank]] : c->im_eta;
+}
+
 // Sets im_finite[bank] from the bank's weights as they stand (synchronises the stream).
 static int infomax_check_finite(dv_ctx* c, int bank = 0) {
-    const long long n = (long long)c->im_M * c->im_N;
+    size_t off, len;
+    ibank_span(c, bank, off, len);
+    const long long n = (long long)len;
     HIP_TRY(c, hipMemsetAsync(c->im_flag + bank, 0, sizeof(int), c->stream));
     const long long blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(k_im_finite, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, c->stream, c->im_W + (size_t)bank * (size_t)n, n,
+    hipLaunchKernelGGL(k_im_finite, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, c->stream, c->im_W + off, n,
                        c->im_flag + bank);
     HIP_TRY(c, hipGetLastError());
     int bad = 0;
@@ -587,12 +630,13 @@ extern "C" int dv_infomax_begin(dv_ctx* c, int h, int w, int channel, int n_hidd
                     hipGetErrorString(e));
     }
     c->im_M = M; c->im_N = N; c->im_hh = h; c->im_ww = w; c->im_channel = channel; c->im_eta = learning_rate;
+    c->im_w0.assign(w0, w0 + (size_t)M * (size_t)N);         // (dv_inet_clear returns bank 0 to it)
     return infomax_check_finite(c);
 }
 
 extern "C" int dv_infomax_train_u8(dv_ctx* c, const uint8_t* planes, int64_t n) {
     if (!c) return DV_ERR_INVALID;
-    int rc = infomax_need(c, "dv_infomax_train_u8");
+    int rc = infomax_need_bank0(c, "dv_infomax_train_u8");
     if (rc) return rc;
     if (!planes || n < 0) return fail(c, DV_ERR_INVALID, "dv_infomax_train_u8: planes is NULL or n < 0");
     if (!c->im_finite[0]) return infomax_not_finite(c, "dv_infomax_train_u8");
@@ -616,7 +660,7 @@ extern "C" int dv_infomax_train_u8(dv_ctx* c, const uint8_t* planes, int64_t n) 
 
 extern "C" int dv_infomax_train_from_poses(dv_ctx* c, const double* x, const double* y, const double* angle, int64_t n, uint8_t* out_views) {
     if (!c) return DV_ERR_INVALID;
-    int rc = infomax_need(c, "dv_infomax_train_from_poses");
+    int rc = infomax_need_bank0(c, "dv_infomax_train_from_poses");
     if (rc) return rc;
     if (!x || !y || !angle || n < 1 || n > 0x7fffffff) return fail(c, DV_ERR_INVALID, "dv_infomax_train_from_poses: bad arguments");
     rc = sensor_fits(c, "dv_infomax_train_from_poses", c->im_hh, c->im_ww);
@@ -640,7 +684,7 @@ extern "C" int dv_infomax_train_from_poses(dv_ctx* c, const double* x, const dou
 
 extern "C" int dv_infomax_score_u8(dv_ctx* c, const uint8_t* planes, int n, double* familiarity) {
     if (!c) return DV_ERR_INVALID;
-    int rc = infomax_need(c, "dv_infomax_score_u8");
+    int rc = infomax_need_bank0(c, "dv_infomax_score_u8");
     if (rc) return rc;
     if (!planes || !familiarity || n < 1) return fail(c, DV_ERR_INVALID, "dv_infomax_score_u8: NULL argument or n < 1");
     if (!c->im_finite[0]) return infomax_not_finite(c, "dv_infomax_score_u8");
@@ -661,7 +705,7 @@ extern "C" int dv_infomax_score_u8(dv_ctx* c, const uint8_t* planes, int n, doub
 
 extern "C" int dv_infomax_sense_step(dv_ctx* c, double x, double y, const double* angles, int n, double* angle_fam, int32_t* best_heading) {
     if (!c) return DV_ERR_INVALID;
-    int rc = infomax_need(c, "dv_infomax_sense_step");
+    int rc = infomax_need_bank0(c, "dv_infomax_sense_step");
     if (rc) return rc;
     if (!angles || !angle_fam || !best_heading || n < 1) return fail(c, DV_ERR_INVALID, "dv_infomax_sense_step: NULL argument or n_headings < 1");
     rc = sensor_fits(c, "dv_infomax_sense_step", c->im_hh, c->im_ww);
@@ -756,7 +800,7 @@ static int infomax_batch(dv_ctx* c, const char* who, const uint8_t* planes, cons
 
 extern "C" int dv_batch_infomax_step_u8(dv_ctx* c, const uint8_t* planes, int n_agents, int n_headings, double* angle_fam, int32_t* best_heading) {
     if (!c) return DV_ERR_INVALID;
-    int rc = infomax_need(c, "dv_batch_infomax_step_u8");
+    int rc = infomax_need_bank0(c, "dv_batch_infomax_step_u8");
     if (rc) return rc;
     if (!planes || !angle_fam || !best_heading || n_agents < 1 || n_headings < 1)
         return fail(c, DV_ERR_INVALID, "dv_batch_infomax_step_u8: NULL argument, n_agents < 1 or n_headings < 1");
@@ -767,7 +811,7 @@ extern "C" int dv_batch_infomax_step_u8(dv_ctx* c, const uint8_t* planes, int n_
 extern "C" int dv_batch_infomax_sense_step(dv_ctx* c, const double* x, const double* y, const double* angles, int n_agents, int n_headings,
                                            double* angle_fam, int32_t* best_heading, uint32_t* flags) {
     if (!c) return DV_ERR_INVALID;
-    int rc = infomax_need(c, "dv_batch_infomax_sense_step");
+    int rc = infomax_need_bank0(c, "dv_batch_infomax_sense_step");
     if (rc) return rc;
     if (!x || !y || !angles || !angle_fam || !best_heading || !flags || n_agents < 1 || n_headings < 1)
         return fail(c, DV_ERR_INVALID, "dv_batch_infomax_sense_step: NULL argument, n_agents < 1 or n_headings < 1");
@@ -779,7 +823,7 @@ extern "C" int dv_batch_infomax_sense_step(dv_ctx* c, const double* x, const dou
 
 extern "C" int dv_infomax_read_weights(dv_ctx* c, double* out) {
     if (!c) return DV_ERR_INVALID;
-    int rc = infomax_need(c, "dv_infomax_read_weights");
+    int rc = infomax_need_bank0(c, "dv_infomax_read_weights");
     if (rc) return rc;
     if (!out) return fail(c, DV_ERR_INVALID, "dv_infomax_read_weights: out is NULL");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -790,7 +834,7 @@ extern "C" int dv_infomax_read_weights(dv_ctx* c, double* out) {
 
 extern "C" int dv_infomax_set_weights(dv_ctx* c, const double* weights) {
     if (!c) return DV_ERR_INVALID;
-    int rc = infomax_need(c, "dv_infomax_set_weights");
+    int rc = infomax_need_bank0(c, "dv_infomax_set_weights");
     if (rc) return rc;
     if (!weights) return fail(c, DV_ERR_INVALID, "dv_infomax_set_weights: weights is NULL");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -817,8 +861,13 @@ static int ibank_check_finite(dv_ctx* c) {
     const size_t B = (size_t)c->im_banks;
     HIP_TRY(c, hipMemsetAsync(c->im_flag, 0, B * sizeof(int), c->stream));
     const long long blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(k_im_finite_banks, dim3((unsigned)(blocks < 2048 ? blocks : 2048), (unsigned)B), dim3(256), 0, c->stream, c->im_W, n, c->im_flag);
-    HIP_TRY(c, hipGetLastError());
+    if (c->inet_nets) {                                       // ragged banks: each over its own network's weights
+        const int rc = inet_finite(c);
+        if (rc) return rc;
+    } else {
+        hipLaunchKernelGGL(k_im_finite_banks, dim3((unsigned)(blocks < 2048 ? blocks : 2048), (unsigned)B), dim3(256), 0, c->stream, c->im_W, n, c->im_flag);
+        HIP_TRY(c, hipGetLastError());
+    }
     std::vector<int> bad(B, 0);
     HIP_TRY(c, hipMemcpyAsync(bad.data(), c->im_flag, B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -834,7 +883,7 @@ static int ibank_check(dv_ctx* c, const char* who, const char* what, const int32
     for (int64_t i = 0; i < n; ++i)
         if (!c->im_finite[(size_t)bank_of[i]])
             return fail(c, DV_ERR_STATE, "%s: %s[%lld] names bank %d, whose weights are not finite (learning_rate %g is too large for its views: the rule diverged)",
-                        who, what, (long long)i, (int)bank_of[i], c->im_eta);
+                        who, what, (long long)i, (int)bank_of[i], ibank_eta(c, bank_of[i]));
     return DV_OK;
 }
 
@@ -845,11 +894,12 @@ static int ibank_report(dv_ctx* c, const char* who, const int32_t* bank_of, int6
     for (int b = 0; b < c->im_banks; ++b)
         if (named[(size_t)b] && !c->im_finite[(size_t)b])
             return fail(c, DV_ERR_STATE, "%s: the weights of bank %d are not finite (learning_rate %g is too large for its views: the rule diverged)", who, b,
-                        c->im_eta);
+                        ibank_eta(c, b));
     return DV_OK;
 }
 
-// h, u and upart of every bank: made at the first banked training call after dv_infomax_begin / dv_ibank_set.
+// h, u and upart of every bank: made at the first banked training call after dv_infomax_begin / dv_ibank_set (dv_inet_set has made
+// its own, ragged ones, and im_kh[0] holds them).
 static int ibank_buffers(dv_ctx* c) {
     if (c->im_kh[0]) return DV_OK;
     const size_t B = (size_t)c->im_banks, M = (size_t)c->im_M, N = (size_t)c->im_N, n_rb = (M + kImRowsPerBlock - 1) / kImRowsPerBlock;
@@ -887,6 +937,7 @@ static int ibank_train_device(dv_ctx* c, const unsigned char* d_src, long long v
         for (int b = 0; b < B; ++b) { start[b] = cur[(size_t)b] = run; run += len[b]; }
         for (int64_t v = 0; v < nb; ++v) t[idx0 + (size_t)cur[(size_t)bank_of[b0 + v]]++] = (int)v;
     }
+    if (c->inet_nets) t.insert(t.end(), bank_of, bank_of + n);   // then the views' banks: k_inet_prep reads a view at its bank's channel
     rc = table_upload(c, c->im_ktab, t.data(), t.size() * sizeof(int));
     if (rc) return rc;
     const int* d_idx = c->im_ktab.device<int>() + idx0;
@@ -899,6 +950,11 @@ static int ibank_train_device(dv_ctx* c, const unsigned char* d_src, long long v
         const int* d_tab = c->im_ktab.device<int>() + (size_t)k * 2 * (size_t)B;
         int steps = 0;
         for (int b = 0; b < B; ++b) steps = len[b] > steps ? len[b] : steps;
+        if (c->inet_nets) {                                   // (a strided source is the sensed views, read at the bank's own channel instead of `offset`)
+            rc = inet_train_slab(c, d_src + (size_t)b0 * (size_t)view_stride, view_stride, px_stride, nb, d_tab, d_idx, d_idx + (size_t)n + (size_t)b0, steps);
+            if (rc) return rc;
+            continue;
+        }
         hipLaunchKernelGGL(k_im_prep, dim3((unsigned)nb), dim3(256), 0, c->stream, d_src + (size_t)b0 * (size_t)view_stride, view_stride, px_stride,
                            offset, N, c->im_xs);
         HIP_TRY(c, hipGetLastError());
@@ -934,7 +990,7 @@ static int ibank_batch(dv_ctx* c, const char* who, const uint8_t* planes, const 
         return fail(c, DV_ERR_INVALID, "%s: %d agents x %d headings over %d banks are too many columns", who, n_agents, A, B);
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t N = (size_t)c->im_N;
-    const int M = c->im_M, tiles = (M + 15) / 16;
+    const int M = c->im_M, tiles = ((c->inet_nets ? c->inet_max_M : M) + 15) / 16;   // (a table's grids and dpart: its largest n_hidden)
     // members in bank order: place[i] of member i, order[p] the member at place p; first[b] the first place of bank b
     std::vector<int> first((size_t)B + 1, 0), place((size_t)n_agents), order((size_t)n_agents), dbase((size_t)B);
     for (int i = 0; i < n_agents; ++i) first[(size_t)bank_of[i] + 1] += 1;
@@ -962,6 +1018,10 @@ static int ibank_batch(dv_ctx* c, const char* who, const uint8_t* planes, const 
         t.push_back(dbase[(size_t)b] + (place[(size_t)i] - first[(size_t)b]) * A);
         t.push_back(place[(size_t)i] * A);
     }
+    if (c->inet_nets) {                                       // then the members' banks, in the caller's order (k_inet_decide) and in bank order (k_inet_prep)
+        t.insert(t.end(), bank_of, bank_of + n_agents);
+        for (int p = 0; p < n_agents; ++p) t.push_back(bank_of[(size_t)order[(size_t)p]]);
+    }
     long long slab = (long long)(kImStageBytes / (N * sizeof(double))) / kImHeadings * kImHeadings;
     if (slab < kImHeadings) slab = kImHeadings;
     if (slab > kImSlabColsMax) slab = kImSlabColsMax;
@@ -981,6 +1041,8 @@ static int ibank_batch(dv_ctx* c, const char* who, const uint8_t* planes, const 
     if (rc) return rc;
     const ImBlock* blocks = c->im_ktab.record<ImBlock>();
     const ImBlock* d_blocks = c->im_ktab.device<ImBlock>();
+    const int* d_mem = c->im_ktab.device<int>() + 4 * n_blocks;   // the members' pairs; under a network table their banks follow
+    const int* d_bank_caller = c->inet_nets ? d_mem + 2 * (size_t)n_agents : nullptr, *d_bank_sorted = c->inet_nets ? d_bank_caller + n_agents : nullptr;
     if (planes) {
         c->im_kplanes.resize((size_t)C * N);
         for (int p = 0; p < n_agents; ++p)
@@ -1005,7 +1067,8 @@ static int ibank_batch(dv_ctx* c, const char* who, const uint8_t* planes, const 
         while (k0 + nk < n_blocks && nk < (size_t)(kImSlabColsMax / kImHeadings) && nc + blocks[k0 + nk].nc <= slab) nc += blocks[k0 + nk++].nc;
         if (planes) {
             HIP_TRY(c, hipMemcpyAsync(c->d_sense, c->im_kplanes.data() + (size_t)c0 * N, (size_t)nc * N, hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(k_im_prep, dim3((unsigned)nc), dim3(256), 0, c->stream, c->d_sense, (long long)N, 1, 0, c->im_N, c->im_bx);
+            if (c->inet_nets) { rc = inet_prep(c, c->d_sense, (long long)N, 1, 0, nc, c->im_bx, d_bank_sorted, c0, A); if (rc) return rc; }
+            else hipLaunchKernelGGL(k_im_prep, dim3((unsigned)nc), dim3(256), 0, c->stream, c->d_sense, (long long)N, 1, 0, c->im_N, c->im_bx);
         } else {
             const long long total = nc * (long long)N;
             if (land_of) {
@@ -1016,12 +1079,14 @@ static int ibank_batch(dv_ctx* c, const char* who, const uint8_t* planes, const 
                                    c->sensor, c->d_lut, c->d_sense, c->im_perr + c0);
                 HIP_TRY(c, hipGetLastError());
             }
-            hipLaunchKernelGGL(k_im_prep, dim3((unsigned)nc), dim3(256), 0, c->stream, c->d_sense, 3ll * (long long)N, 3, c->im_channel, c->im_N,
-                               c->im_bx);
+            if (c->inet_nets) { rc = inet_prep(c, c->d_sense, 3ll * (long long)N, 3, 1, nc, c->im_bx, d_bank_sorted, c0, A); if (rc) return rc; }
+            else hipLaunchKernelGGL(k_im_prep, dim3((unsigned)nc), dim3(256), 0, c->stream, c->d_sense, 3ll * (long long)N, 3, c->im_channel, c->im_N,
+                                    c->im_bx);
         }
         HIP_TRY(c, hipGetLastError());
         const dim3 grid((unsigned)tiles, (unsigned)nk);
-        if (N % 4 == 0)
+        if (c->inet_nets) { rc = inet_score(c, d_blocks + k0, nk, c0, cpad); if (rc) return rc; }
+        else if (N % 4 == 0)
             hipLaunchKernelGGL((k_im_score_cols_banks<true>), grid, dim3(kImScoreWaves * 64), 0, c->stream, c->im_W, c->im_bx, M, c->im_N, d_blocks + k0,
                                (int)c0, cpad, c->im_bdpart);
         else
@@ -1030,8 +1095,9 @@ static int ibank_batch(dv_ctx* c, const char* who, const uint8_t* planes, const 
         HIP_TRY(c, hipGetLastError());
         k0 += nk;
     }
-    hipLaunchKernelGGL(k_im_decide_banks, dim3((unsigned)n_agents), dim3(256), 0, c->stream, c->im_bdpart, tiles, cpad, A,
-                       planes ? nullptr : c->im_perr, c->im_ktab.device<int>() + 4 * n_blocks, d_fam, d_best, d_flags);
+    if (c->inet_nets) { rc = inet_decide(c, n_agents, cpad, A, planes ? nullptr : c->im_perr, d_mem, d_bank_caller, d_fam, d_best, d_flags); if (rc) return rc; }
+    else hipLaunchKernelGGL(k_im_decide_banks, dim3((unsigned)n_agents), dim3(256), 0, c->stream, c->im_bdpart, tiles, cpad, A,
+                            planes ? nullptr : c->im_perr, d_mem, d_fam, d_best, d_flags);
     HIP_TRY(c, hipGetLastError());
     rc = packed_fetch(c, c->im_res, C, n_agents);
     if (rc) return rc;
@@ -1069,6 +1135,7 @@ extern "C" int dv_ibank_set(dv_ctx* c, int n_banks, const double* w0) {
     c->im_banks = n_banks;
     c->im_views.assign((size_t)n_banks, 0);
     c->im_finite.assign((size_t)n_banks, 1);
+    inet_drop(c);                                             // the banks are the begin's network's again
     return ibank_check_finite(c);
 }
 
@@ -1189,8 +1256,9 @@ extern "C" int dv_ibank_read_weights(dv_ctx* c, int bank, double* out) {
     if (rc) return rc;
     if (!out) return fail(c, DV_ERR_INVALID, "dv_ibank_read_weights: out is NULL");
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t mn = (size_t)c->im_M * (size_t)c->im_N;
-    HIP_TRY(c, hipMemcpyAsync(out, c->im_W + (size_t)bank * mn, mn * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    size_t off, mn;
+    ibank_span(c, bank, off, mn);
+    HIP_TRY(c, hipMemcpyAsync(out, c->im_W + off, mn * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return DV_OK;
 }
@@ -1201,8 +1269,9 @@ extern "C" int dv_ibank_set_weights(dv_ctx* c, int bank, const double* weights) 
     if (rc) return rc;
     if (!weights) return fail(c, DV_ERR_INVALID, "dv_ibank_set_weights: weights is NULL");
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t mn = (size_t)c->im_M * (size_t)c->im_N;
-    HIP_TRY(c, hipMemcpyAsync(c->im_W + (size_t)bank * mn, weights, mn * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    size_t off, mn;
+    ibank_span(c, bank, off, mn);
+    HIP_TRY(c, hipMemcpyAsync(c->im_W + off, weights, mn * sizeof(double), hipMemcpyHostToDevice, c->stream));
     return infomax_check_finite(c, bank);                     // (synchronises: `weights` is borrowed for this call only)
 }
 

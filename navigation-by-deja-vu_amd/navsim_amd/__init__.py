@@ -9,7 +9,7 @@ scripts/run_experiment.py:84).  Scoring runs only on the GPU through libdejavu_h
 from .agent import (NavBySceneFamiliarity, StopNavigationException, ReachedEndOfTrainingPathException,
                     NavigatingFailedException, TooFarFromTrainingPathException,
                     OutOfLandscapeBoundsException, fill_sensor_from, downscale_chem)
-from .util import sads_familiarity, hip_sads_familiarity, ssd_familiarity, infomax_familiarity, mushroom_familiarity
+from .util import sads_familiarity, hip_sads_familiarity, ssd_familiarity, infomax_familiarity, mushroom_familiarity, infomax_network
 from .engine import FamiliarityEngine
 from .group import FamiliarityGroup
 from ._native import EngineError
@@ -22,7 +22,7 @@ from .generate_landscapes import diffuse, diffuse_series
 __all__ = [
     "NavBySceneFamiliarity", "StopNavigationException", "ReachedEndOfTrainingPathException",
     "NavigatingFailedException", "TooFarFromTrainingPathException", "OutOfLandscapeBoundsException",
-    "sads_familiarity", "hip_sads_familiarity", "ssd_familiarity", "infomax_familiarity", "mushroom_familiarity", "FamiliarityEngine", "FamiliarityGroup", "EngineError",
+    "sads_familiarity", "hip_sads_familiarity", "ssd_familiarity", "infomax_familiarity", "mushroom_familiarity", "infomax_network", "FamiliarityEngine", "FamiliarityGroup", "EngineError",
     "fill_sensor_from", "downscale_chem", "synth", "run_experiment", "run_ensemble", "chop_path_to_len", "NavEnsemble", "InfomaxEnsemble", "MushroomEnsemble", "MushroomRouteEnsemble", "InfomaxRouteEnsemble",
     "SadsRouteEnsemble", "generate_landscapes", "diffuse", "diffuse_series",
 ]

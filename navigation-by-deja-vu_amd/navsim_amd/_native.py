@@ -279,6 +279,10 @@ PROTOTYPES = {
     "dv_mbpop_clear": (ctypes.c_int, [_ctx_p]),
     "dv_mbpop_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _i32p, _i32p, _i32p, _i32p, _i32p,
                                      ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "dv_inet_set": (ctypes.c_int, [_ctx_p, ctypes.c_int, _i32p, _f64p, _i32p, _f64p, ctypes.c_int, _i32p]),
+    "dv_inet_clear": (ctypes.c_int, [_ctx_p]),
+    "dv_inet_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _i32p, _f64p, _i32p, _i32p,
+                                    ctypes.POINTER(ctypes.c_int64), _i32p, ctypes.POINTER(ctypes.c_int64)]),
     "dv_ibank_set": (ctypes.c_int, [_ctx_p, ctypes.c_int, _f64p]),
     "dv_ibank_train_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int64, _i32p]),
     "dv_ibank_train_from_poses": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int64, _i32p, _u8p]),

@@ -1141,6 +1141,7 @@ class FamiliarityEngine(object):
         self.infomax_shape = (int(h), int(w))
         self.infomax_hidden = weights.shape[0]
         self.infomax_banks = 1
+        self.infomax_nets = self.infomax_net_of_bank = None
 
     def infomax_train_u8(self, planes):
         """One more pass of the learning rule over uint8[n,h,w] planes, in order, on the same W."""
@@ -1194,12 +1195,15 @@ class FamiliarityEngine(object):
         self._check(self._lib.dv_infomax_end(self._ctx), "dv_infomax_end")
         self.infomax_shape = None
         self.infomax_banks = 1
+        self.infomax_nets = self.infomax_net_of_bank = None
 
     # -- weight banks of the Infomax model: several models of one shape in one context (include/dejavu.h: dv_ibank_*) ------------
     infomax_banks = 1            # banks of the model (ibank_set; 1 after infomax_begin)
 
-    def _ibank_weights(self, weights, what):
+    def _ibank_weights(self, weights, what, bank=None):
         info = self.infomax_info()
+        if bank is not None and self.infomax_nets is not None:      # the bank's own shape under the live network table
+            info = dict(info, n_hidden=self.infomax_nets[self.infomax_net_of_bank[bank]]["n_hidden"])
         weights = np.ascontiguousarray(weights, dtype=np.float64)
         if info["n_hidden"] and weights.shape != (info["n_hidden"], info["n_pixels"]):
             raise ValueError("%s must be float64[%d,%d], got shape %r" % (what, info["n_hidden"], info["n_pixels"], weights.shape))
@@ -1213,6 +1217,7 @@ class FamiliarityEngine(object):
         weights = self._ibank_weights(weights, "weights")
         self._check(self._lib.dv_ibank_set(self._ctx, int(n_banks), N.f64ptr(weights)), "dv_ibank_set")
         self.infomax_banks = int(n_banks)
+        self.infomax_nets = self.infomax_net_of_bank = None
 
     def ibank_train_u8(self, planes, bank_of_view):
         """infomax_train_u8 with view v trained into bank bank_of_view[v]: every bank's views in their order, the banks' chains in
@@ -1233,16 +1238,18 @@ class FamiliarityEngine(object):
         return self._bank_sense_step_batch("infomax", x, y, angles, bank_of_member, land_of_member)
 
     def ibank_read_weights(self, bank):
-        """float64[n_hidden, h*w] of one bank."""
+        """float64[n_hidden, h*w] of one bank; while a network table is live (inet_set), n_hidden is the bank's own network's."""
         bank = self._bank_index(bank, self.infomax_banks)
         info = self.infomax_info()
+        if self.infomax_nets is not None:
+            info = dict(info, n_hidden=self.infomax_nets[self.infomax_net_of_bank[bank]]["n_hidden"])
         out = np.empty((max(info["n_hidden"], 1), max(info["n_pixels"], 1)), dtype=np.float64)
         self._check(self._lib.dv_ibank_read_weights(self._ctx, bank, N.f64ptr(out)), "dv_ibank_read_weights")
         return out
 
     def ibank_set_weights(self, bank, weights):
         bank = self._bank_index(bank, self.infomax_banks)
-        weights = self._ibank_weights(weights, "weights")
+        weights = self._ibank_weights(weights, "weights", bank)
         self._check(self._lib.dv_ibank_set_weights(self._ctx, bank, N.f64ptr(weights)), "dv_ibank_set_weights")
 
     def ibank_info(self):
@@ -1254,6 +1261,87 @@ class FamiliarityEngine(object):
         self._check(self._lib.dv_ibank_info(self._ctx, None, views.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
                                             finite.ctypes.data_as(N._i32p)), "dv_ibank_info")
         return dict(n_banks=nb.value, views_trained=views, finite=finite.astype(bool))
+
+    # -- network tables of the Infomax model: a bank's own n_hidden, learning rate, W0 and channel (include/dejavu.h: dv_inet_*) ----
+    infomax_nets = None          # the live table's networks, dict(channel, n_hidden, learning_rate) each (inet_set; None: no table)
+    infomax_net_of_bank = None   # int32[n_banks]: the network of every bank of the live table
+    IM_MAX_HIDDEN = 1 << 20
+
+    @classmethod
+    def _network(cls, p, net, n_pixels):
+        """networks[p] as (dict(channel, n_hidden, learning_rate), w0 float64[n_hidden, n_pixels]), or ValueError naming the entry.
+        n_pixels: h * w of the model (None: no model yet, and the library answers DV_ERR_STATE)."""
+        who = "networks[%d]" % p
+        if not isinstance(net, dict) or "w0" not in net or "learning_rate" not in net:
+            raise ValueError("%s must be a dict with w0 and learning_rate (util.infomax_network makes one)" % who)
+        extra = sorted(set(net) - {"w0", "learning_rate", "channel", "n_hidden", "seed"})
+        if extra:
+            raise ValueError("%s: unknown keys %r" % (who, extra))
+        w0 = np.asarray(net["w0"])
+        if w0.dtype != np.float64:
+            raise ValueError("%s: w0 must be float64, got dtype %s" % (who, w0.dtype))
+        if w0.ndim != 2 or (n_pixels is not None and w0.shape[1] != n_pixels):
+            raise ValueError("%s: w0 must be float64[n_hidden, %s], got shape %r" % (who, "h*w" if n_pixels is None else n_pixels, w0.shape))
+        n_hidden = w0.shape[0]
+
+        def whole(v):
+            return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+        if "n_hidden" in net and not (whole(net["n_hidden"]) and net["n_hidden"] == n_hidden):
+            raise ValueError("%s: n_hidden = %r, but w0 has shape %r" % (who, net["n_hidden"], w0.shape))
+        if not 1 <= n_hidden <= cls.IM_MAX_HIDDEN:
+            raise ValueError("%s: n_hidden %d outside [1, %d]" % (who, n_hidden, cls.IM_MAX_HIDDEN))
+        rate, channel = net["learning_rate"], net.get("channel", 2)
+        if isinstance(rate, bool) or not isinstance(rate, (int, float, np.floating, np.integer)) or not (rate > 0 and np.isfinite(rate)):
+            raise ValueError("%s: learning_rate %r must be a positive number" % (who, rate))
+        if not (whole(channel) and 0 <= channel <= 2):
+            raise ValueError("%s: channel %r outside [0, 2]" % (who, channel))
+        return dict(channel=int(channel), n_hidden=int(n_hidden), learning_rate=float(rate)), np.ascontiguousarray(w0)
+
+    def inet_set(self, networks, network_of_bank):
+        """A network table: networks is a list of dicts (util.infomax_network: channel, n_hidden, learning_rate, w0 float64[n_hidden,
+        h*w] over the model's pixels), network_of_bank names every bank's network (its length is the number of banks; several banks
+        may share one).  Every bank starts as a copy of its network's w0; what was trained is dropped.  From here on the ibank_* calls
+        train and score every view and member through its bank's own n_hidden, learning rate and channel, and the infomax_* calls
+        (bank 0 behind the begin's shape) are refused until inet_clear, ibank_set, infomax_begin or infomax_end.  Every entry is
+        checked here, before any library call; ValueError names it."""
+        if isinstance(networks, dict) or not hasattr(networks, "__len__") or len(networks) < 1:
+            raise ValueError("networks must be a list of one or more dicts (util.infomax_network), got %r" % (type(networks).__name__,))
+        n_pixels = None if self.infomax_shape is None else self.infomax_shape[0] * self.infomax_shape[1]
+        nets, w0s = zip(*[self._network(p, net, n_pixels) for p, net in enumerate(networks)])
+        of_bank = self._index_table(network_of_bank, "network_of_bank", len(nets), "n_nets", per="network")
+        if not 1 <= len(of_bank) <= 65535:
+            raise ValueError("network_of_bank must name the network of 1 to 65535 banks, got %d" % len(of_bank))
+        n_hidden = np.array([p["n_hidden"] for p in nets], dtype=np.int32)
+        channel = np.array([p["channel"] for p in nets], dtype=np.int32)
+        rate = np.array([p["learning_rate"] for p in nets], dtype=np.float64)
+        concat = np.ascontiguousarray(np.concatenate([w.reshape(-1) for w in w0s]), dtype=np.float64)
+        i32 = lambda a: a.ctypes.data_as(N._i32p)
+        self._check(self._lib.dv_inet_set(self._ctx, len(nets), i32(n_hidden), N.f64ptr(rate), i32(channel), N.f64ptr(concat), len(of_bank),
+                                          i32(of_bank)), "dv_inet_set")
+        self.infomax_nets, self.infomax_net_of_bank, self.infomax_banks = list(nets), of_bank, len(of_bank)
+
+    def inet_clear(self):
+        """Back to one bank of the network infomax_begin made, at its initial weights."""
+        self._check(self._lib.dv_inet_clear(self._ctx), "dv_inet_clear")
+        self.infomax_nets, self.infomax_net_of_bank, self.infomax_banks = None, None, 1
+
+    def inet_info(self):
+        """dict(n_nets, n_banks, n_hidden / channel int32[n_nets], learning_rate float64[n_nets], network_of_bank int32[n_banks],
+        views_trained int64[n_banks], finite bool[n_banks], bytes); n_nets = n_banks = 0 and empty arrays without a table."""
+        P, B, nbytes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+        self._check(self._lib.dv_inet_info(self._ctx, ctypes.byref(P), ctypes.byref(B), None, None, None, None, None, None, ctypes.byref(nbytes)),
+                    "dv_inet_info")
+        n_hidden, channel = np.zeros(P.value, dtype=np.int32), np.zeros(P.value, dtype=np.int32)
+        rate = np.zeros(P.value, dtype=np.float64)
+        of_bank, finite = np.zeros(B.value, dtype=np.int32), np.zeros(B.value, dtype=np.int32)
+        views = np.zeros(B.value, dtype=np.int64)
+        if P.value:
+            i32 = lambda a: a.ctypes.data_as(N._i32p)
+            self._check(self._lib.dv_inet_info(self._ctx, None, None, i32(n_hidden), N.f64ptr(rate), i32(channel), i32(of_bank),
+                                               views.ctypes.data_as(N._i64p), i32(finite), None), "dv_inet_info")
+        return dict(n_nets=P.value, n_banks=B.value, n_hidden=n_hidden, learning_rate=rate, channel=channel, network_of_bank=of_bank,
+                    views_trained=views, finite=finite.astype(bool), bytes=nbytes.value)
 
     # -- mushroom-body familiarity model: a fixed fan-in and one byte of weight per Kenyon cell (include/dejavu.h: dv_mb_*) --------
     def mb_begin(self, h, w, conn, n_active, channel=2):

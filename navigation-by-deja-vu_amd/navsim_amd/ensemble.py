@@ -541,10 +541,11 @@ class _RouteEnsemble(_OneValueEnsemble):
         raise ValueError("%s has no populations: MushroomRouteEnsemble gives every route's bank cells and wiring of its own" % cls.__name__)
 
     @classmethod
-    def _from_routes(cls, agent, routes, starts, metrics, lands, land_of_route, sensors=None, populations=None):
+    def _from_routes(cls, agent, routes, starts, metrics, lands, land_of_route, sensors=None, populations=None, table=None):
         """from_routes_with (lands None: every route on the agent's own landscape, the engine's one), or from_landscapes (route r on
         lands[land_of_route[r]] of the engine's landscape set; sensors: None, or _sensor_entries' entry per landscape).
-        populations: None, or from_routes_with's list (an entry per route)."""
+        populations: None, or from_routes_with's list (an entry per route).  table: None, or a subclass's own extra argument of
+        _train_banks, by name (InfomaxRouteEnsemble's networks)."""
         import copy
         if metrics not in cls.METRICS:
             raise ValueError("metrics must be one of %r, got %r" % (cls.METRICS, metrics))
@@ -566,7 +567,7 @@ class _RouteEnsemble(_OneValueEnsemble):
             if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 0 <= r < len(routes):
                 raise ValueError("starts[%d]: route_index %r outside [0, %d)" % (i, r, len(routes)))
         pops = None if populations is None else cls._population_entries(agent, model, len(routes), populations)
-        table = {} if pops is None else dict(populations=pops)    # (_train_banks' extra argument, only where there is a table)
+        table = dict(table or {}) if pops is None else dict(populations=pops)    # (_train_banks' extra argument, only where there is a table)
         for k, route in enumerate(routes):                        # (the agent's own bounds test, on the route's own landscape)
             probe = agent if lands is None else cls._on_landscape(copy.copy(agent), lands[land_of_route[k]],
                                                                   None if sensors is None else sensors[land_of_route[k]])
@@ -689,6 +690,13 @@ class _RouteEnsemble(_OneValueEnsemble):
         enter the landscape twice.  The members of a route on landscape l carry that entry's configuration and `sensor_index`, so
         their bounds are their own footprint's and their get_sensor_mat senses under their own entry.
         populations: as from_routes_with's, an entry per route."""
+        lands, points, land_of_route, entries = cls._landscape_args(agent, landscapes, routes, sensors)
+        return cls._from_routes(agent, points, starts, metrics, lands, land_of_route, entries, populations=populations)
+
+    @classmethod
+    def _landscape_args(cls, agent, landscapes, routes, sensors):
+        """from_landscapes' landscapes, routes and sensors, checked -> (the landscapes, every route's points, land_of_route, the
+        sensor entries or None): what _from_routes takes."""
         lands = [np.asarray(l) for l in landscapes]
         if not lands or any(l.dtype != np.uint8 or l.ndim != 3 or l.shape[2] != 3 for l in lands):
             raise ValueError("landscapes must be one or more arrays uint8[rows, cols, 3]")
@@ -701,7 +709,7 @@ class _RouteEnsemble(_OneValueEnsemble):
                 raise ValueError("routes[%d]: landscape_index %r outside [0, %d)" % (k, l, len(lands)))
         land_of_route = [int(l) for l, _ in routes]
         entries = None if sensors is None else cls._sensor_entries(agent, len(lands), sensors)
-        return cls._from_routes(agent, [pts for _, pts in routes], starts, metrics, lands, land_of_route, entries, populations=populations)
+        return lands, [pts for _, pts in routes], land_of_route, entries
 
     def _device_step(self, idx, xs, ys, angs):
         if self._lands is not None:
@@ -796,7 +804,16 @@ class InfomaxRouteEnsemble(_RouteEnsemble):
     bank of its own on the one engine (FamiliarityEngine.ibank_set: n_hidden x h*w doubles a route), every bank begins as the model's own
     seeded W0, all routes are trained in one device call whose chains advance in lockstep (dv_ibank_train_from_poses), and a step scores
     every running member's headings under its own route's W in ONE device call (dv_ibank_sense_step), with the bits a lone agent trained
-    on that route alone gives at the same pose.  Made by from_routes (see _RouteEnsemble)."""
+    on that route alone gives at the same pose.  Made by from_routes (see _RouteEnsemble).
+
+    from_routes_with / from_landscapes(networks=[...]) makes trials that differ in the MODEL's own parameters too (learning-rate and
+    capacity sweeps, replicates over the initial weights): the list has one entry per route, None (the agent's model) or a dict with any
+    of n_hidden, learning_rate, seed and channel -- a key an entry leaves out takes the model's value.  Equal entries share one network
+    of the engine's network table (FamiliarityEngine.inet_set), and every route's bank has the shape, rate, W0 and channel of its entry;
+    a route under two networks is entered twice.  Members carry `network_index` and `network` (dict(channel, n_hidden, learning_rate,
+    seed)); both are None without networks.  A member's rows are those of a lone agent built with infomax_familiarity of its network
+    and trained on its route alone."""
+    NETWORK_KEYS = ("n_hidden", "learning_rate", "seed", "channel")
     _metric = "infomax"
     _takes = InfomaxEnsemble._takes
     _batch_call = "ibank_sense_step_batch"
@@ -805,11 +822,91 @@ class InfomaxRouteEnsemble(_RouteEnsemble):
     _reject_others = InfomaxEnsemble._reject_others
 
     @staticmethod
-    def _train_banks(eng, n_routes, x, y, headings, bank_of_view, land_of_view=None):
-        eng.ibank_set(n_routes, eng.infomax_read_weights())          # (bank 0 holds the W0 the model's begin has just drawn)
+    def _train_banks(eng, n_routes, x, y, headings, bank_of_view, land_of_view=None, networks=None):
+        if networks is None:
+            eng.ibank_set(n_routes, eng.infomax_read_weights())      # (bank 0 holds the W0 the model's begin has just drawn)
+        else:
+            eng.inet_set(*networks)                                   # bank r is route r's, behind its entry's network
         if land_of_view is None:
             return eng.ibank_train_from_poses(x, y, headings, bank_of_view)
         return eng.ibank_train_from_poses(x, y, headings, bank_of_view, land_of_view=land_of_view)
+
+    @classmethod
+    def _population_entries(cls, agent, model, n_routes, populations):
+        raise ValueError("%s has no populations: MushroomRouteEnsemble gives every route's bank cells and wiring of its own (an Infomax "
+                         "route's own n_hidden, learning rate, seed and channel go in networks=)" % cls.__name__)
+
+    @classmethod
+    def _network_entries(cls, agent, model, n_routes, networks):
+        """`networks` as (the distinct networks, network_of_route), or ValueError naming the entry."""
+        from .util import infomax_network
+        if isinstance(networks, dict) or not hasattr(networks, "__len__") or len(networks) != n_routes:
+            raise ValueError("networks must be a list with one entry per route (%d), each None or a dict with any of %r"
+                             % (n_routes, cls.NETWORK_KEYS))
+        own = {k: getattr(model, k) for k in cls.NETWORK_KEYS}
+        n_pixels = int(agent.sensor_dimensions[0]) * int(agent.sensor_dimensions[1])
+        keys, nets, of_route = [], [], []
+        for r, entry in enumerate(networks):
+            if entry is not None and not isinstance(entry, dict):
+                raise ValueError("networks[%d] must be None or a dict with any of %r" % (r, cls.NETWORK_KEYS))
+            extra = sorted(set(entry or {}) - set(cls.NETWORK_KEYS))
+            if extra:
+                raise ValueError("networks[%d]: unknown keys %r (an entry holds any of %r)" % (r, extra, cls.NETWORK_KEYS))
+            spec = dict(own, **(entry or {}))
+            try:
+                net = None
+                if spec["n_hidden"] is not None:
+                    key = tuple(spec[k] for k in cls.NETWORK_KEYS)
+                else:                                             # (None: as many rows as the view has pixels -- equal to that number given)
+                    net = infomax_network(n_pixels, **spec)
+                    key = (net["n_hidden"],) + tuple(spec[k] for k in cls.NETWORK_KEYS[1:])
+                if key not in keys:
+                    net = net or infomax_network(n_pixels, **spec)
+                    keys.append(key)
+                    nets.append(dict(net, seed=spec["seed"]))
+            except (ValueError, TypeError) as e:
+                raise ValueError("networks[%d]: %s" % (r, e))
+            of_route.append(keys.index(key))
+        return nets, np.array(of_route, dtype=np.int32)
+
+    @classmethod
+    def from_routes_with(cls, agent, routes, starts, metrics="host", networks=None):
+        """_RouteEnsemble.from_routes_with; networks: None, or a list with one entry per route, the route's own model parameters
+        (see the class)."""
+        return cls._from_routes(agent, list(routes), starts, metrics, None, None, networks=networks)
+
+    @classmethod
+    def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host", sensors=None, networks=None):
+        """_RouteEnsemble.from_landscapes; networks: as from_routes_with's, an entry per route."""
+        lands, points, land_of_route, entries = cls._landscape_args(agent, landscapes, routes, sensors)
+        return cls._from_routes(agent, points, starts, metrics, lands, land_of_route, entries, networks=networks)
+
+    @classmethod
+    def _from_routes(cls, agent, routes, starts, metrics, lands, land_of_route, sensors=None, networks=None):
+        nets = None
+        if networks is not None:
+            model = getattr(agent, "familiarity_model", None)
+            cls._check_model(model)
+            nets = cls._network_entries(agent, model, len(routes), networks)
+        ens = super(InfomaxRouteEnsemble, cls)._from_routes(agent, routes, starts, metrics, lands, land_of_route, sensors,
+                                                            table=None if nets is None else dict(networks=nets))
+        for a in ens.agents:
+            a.network_index = None if nets is None else int(nets[1][a.memory_bank])
+            a.network = None if nets is None else {k: v for k, v in nets[0][a.network_index].items() if k != "w0"}
+        return ens
+
+    def bank_info(self):
+        """_RouteEnsemble.bank_info, and per bank n_hidden, learning_rate and network_of_bank (zeros without networks)."""
+        info = dict(super(InfomaxRouteEnsemble, self).bank_info())
+        nets, n = getattr(self.engine, "infomax_nets", None), int(info["n_banks"])
+        if nets is None:
+            of_bank = np.zeros(n, dtype=np.int32)
+            nets = [dict(n_hidden=self.engine.infomax_hidden, learning_rate=self.agents[0].familiarity_model.learning_rate)]
+        else:
+            of_bank = np.asarray(self.engine.infomax_net_of_bank, dtype=np.int32)
+        info.update(n_hidden=np.array([nets[p]["n_hidden"] for p in of_bank], dtype=np.int64),
+                    learning_rate=np.array([nets[p]["learning_rate"] for p in of_bank], dtype=np.float64), network_of_bank=of_bank)
+        return info
 
 
 class SadsRouteEnsemble(_RouteEnsemble):

@@ -280,7 +280,18 @@ def infomax_familiarity(channel=2, learning_rate=0.01, seed=0, n_hidden=None, de
         n = int(h) * int(w)
         engine.infomax_begin(h, w, infomax_initial_weights(n if n_hidden is None else n_hidden, n, seed), channel, learning_rate)
 
-    return _one_value_familiarity("infomax", channel, device, begin, learning_rate=learning_rate)
+    return _one_value_familiarity("infomax", channel, device, begin, learning_rate=learning_rate, seed=seed, n_hidden=n_hidden)
+
+
+def infomax_network(n_pixels, n_hidden=None, learning_rate=0.01, seed=0, channel=2):
+    """One network of an Infomax network table (FamiliarityEngine.inet_set) over views of n_pixels pixels:
+    dict(channel, n_hidden, learning_rate, w0) with n_hidden = n_pixels where None is given and
+    w0 = infomax_initial_weights(n_hidden, n_pixels, seed) -- what infomax_familiarity of the same arguments begins its engine with."""
+    if isinstance(n_pixels, bool) or not isinstance(n_pixels, (int, np.integer)) or n_pixels < 1:
+        raise ValueError("n_pixels must be a positive integer, got %r" % (n_pixels,))
+    infomax_familiarity(channel=channel, learning_rate=learning_rate, seed=seed, n_hidden=n_hidden)      # (its argument checks)
+    m = int(n_pixels) if n_hidden is None else int(n_hidden)
+    return dict(channel=int(channel), n_hidden=m, learning_rate=float(learning_rate), w0=infomax_initial_weights(m, n_pixels, seed))
 
 
 def mushroom_connectivity(n_kc, n_pixels, fan_in, seed=0):

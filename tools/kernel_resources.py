@@ -2,7 +2,10 @@
 """Register / scratch table of every kernel in the BUILT libdejavu_hip.so (what ships), read from the code object's
 metadata -- to catch a change that sends a scoring kernel to scratch or costs it its occupancy.
 
-    python tools/kernel_resources.py [filter]
+    python tools/kernel_resources.py [filter | group]
+
+A group (GROUPS) names the kernels of one feature beside the twins they are held to: `inet`, the network-table kernels of the Infomax
+model and the banked kernels whose budget they keep (tests/test_inet_resources.py).
 
 `kernel_table()` is what tests/test_host_logic.py:test_shipped_scoring_kernels_use_no_scratch checks (no compile: the
 gfx950 code object is unbundled from the library's .hip_fatbin section and its notes are parsed)."""
@@ -46,9 +49,19 @@ def kernel_table(lib=LIB):
     return rows
 
 
+# group -> the prefixes of its kernels' names
+GROUPS = {"inet": ("k_inet_", "k_im_prep", "k_im_gemv_banks", "k_im_upart_banks", "k_im_ureduce_banks", "k_im_update_banks", "k_im_finite_banks",
+                   "k_im_score_cols_banks", "k_im_decide_banks")}
+
+
+def group_rows(group, lib=LIB):
+    """The rows of kernel_table() that belong to GROUPS[group]."""
+    return [r for r in kernel_table(lib) if r["name"].startswith(GROUPS[group])]
+
+
 if __name__ == "__main__":
     flt = sys.argv[1] if len(sys.argv) > 1 else ""
     print("%-60s %5s %5s %7s %6s" % ("kernel", "VGPR", "SGPR", "scratch", "LDS"))
-    for r in kernel_table():
-        if flt in r["name"]:
+    for r in group_rows(flt) if flt in GROUPS else kernel_table():
+        if flt in GROUPS or flt in r["name"]:
             print("%-60s %5s %5s %7s %6s" % (r["name"][:60], r.get("vgpr"), r.get("sgpr"), r.get("scratch"), r.get("lds")))

@@ -104,6 +104,59 @@ def wrong_bank_shows(fam_all, banks, i, r):
     return bool(np.argmax(own) != np.argmax(other) or np.max(np.abs(own - other) / np.abs(own)) > 1000 * H.TOL)
 
 
+# ---- steps past one launch, without a network table: the layouts of tests/helpers_inet.py under banks of one shape -------------------------
+# SLAB: helpers_inet.SLAB's 688 members x 12 headings of 32 x 32 views over four banks (the byte bound: launch 2 begins at column 8176,
+# inside a member of bank 1), every bank with M = 24 rows (a ragged second row tile) and trained weights of its own.
+# BLOCKS: helpers_inet.BLOCKS' 16385 banks of one member x 3 headings of 7 x 5 views (the block-count bound: 16384 blocks and one), M = 15,
+# banks 0, 16383 and 16384 trained.  Measured as the table above, weights / scores: SLAB 2.4e-16 / 6.5e-16, BLOCKS 1.7e-16 / 5.7e-16.
+SLAB = dict(M=24, eta=0.02, seed=471)
+BLOCKS = dict(M=15, eta=0.01, seed=481)
+
+
+@functools.lru_cache(maxsize=None)
+def slab_step_data():
+    """dict(W0, Ws [4], views, bank_of, planes uint8[688,12,32,32], banks, fam, first, second, margin, h, w): helpers_inet.slab_members
+    under four banks of one shape, bank b trained from W0 on the views helpers_inet.slab_deal() gives it."""
+    from tests import helpers_inet as HN
+    t = HN.SLAB
+    W0 = H.initial_weights(SLAB["M"], t["w"] * t["h"], SLAB["seed"])
+    views = H.route_views(SLAB["seed"] + 10, sum(t["trained"]), t["h"], t["w"])
+    bank_of = HN.slab_deal()
+    Ws = train_banks(W0, views, bank_of, eta=SLAB["eta"], n_banks=len(t["members"]))
+    assert all(np.isfinite(W).all() for W in Ws)
+    assert all(HN.rel(Ws[a], Ws[b]) > 1e-6 for a in range(4) for b in range(a + 1, 4)) and all(HN.rel(W, W0) > 1e-6 for W in Ws)
+    banks = HN.slab_layout()["banks"]
+    planes, fam, first, second, margin = HN.slab_members(lambda p: slab_scores(Ws, p, banks))
+    for a in [W0, views, bank_of] + Ws:
+        a.setflags(write=False)
+    return dict(W0=W0, Ws=Ws, views=views, bank_of=bank_of, planes=planes, banks=banks, fam=fam, first=first, second=second, margin=margin,
+                h=t["h"], w=t["w"])
+
+
+def slab_scores(Ws, planes, banks, **kw):
+    return np.stack([H.familiarity(Ws[b], planes[i], **kw) for i, b in enumerate(banks)])
+
+
+@functools.lru_cache(maxsize=None)
+def blocks_data():
+    """dict(W0, trained {bank: W}, fam float64[16385, 3], + helpers_inet.blocks_layout()): every bank W0 but the three trained ones."""
+    from tests import helpers_inet as HN
+    lay = HN.blocks_layout()
+    W0 = H.initial_weights(BLOCKS["M"], lay["N"], BLOCKS["seed"])
+    trained = {b: H.train(W0, lay["views"][lay["bank_of"] == b], eta=BLOCKS["eta"]) for b in HN.BLOCKS["trained"]}
+    assert all(np.isfinite(W).all() and HN.rel(W, W0) > 1e-6 for W in trained.values())
+    fam = blocks_scores(W0, trained)
+    for a in [W0, fam] + list(trained.values()):
+        a.setflags(write=False)
+    return dict(lay, W0=W0, trained=trained, fam=fam, h=HN.BLOCKS["h"], w=HN.BLOCKS["w"])
+
+
+def blocks_scores(W0, trained, **kw):
+    from tests import helpers_inet as HN
+    lay = HN.blocks_layout()
+    return HN.blocks_scores(lay, np.zeros(len(lay["banks"]), dtype=np.int32), [W0], trained, **kw)
+
+
 # ---- sensed banks: three short routes of unequal length on helpers_infomax.SENSED's landscape, its 32x32 sensor -----------------------
 CURVES = (0.2, 0.5, 0.8)
 SENSED_POINTS = (15, 9, 12)

@@ -3,7 +3,8 @@ trained in shared lockstep launches and scored member by member.  Against lone e
 the doubles' uint64 views.  Against the NumPy statement run per bank with that bank's W0, rate and channel (tests/helpers_inet.py over
 tests/helpers_infomax.py): within helpers_infomax.TOL, relative to max|W| and max|d|, every figure printed before it is asserted.
 InfomaxRouteEnsemble(networks=...) against lone agents built with infomax_familiarity of the member's network and trained on its route
-alone."""
+alone.  The steps of section 5b run past one launch (helpers_inet.SLAB: the staging slab's bytes; helpers_inet.BLOCKS: the scoring grid's
+blocks); tests/test_inet_host.py asserts of their layouts that the second launch is reached and that an index local to it would show."""
 import csv
 import io
 
@@ -227,6 +228,125 @@ def test_the_last_view_past_a_slab_keeps_its_own_bank_and_a_cut_call_its_bits(en
     eng.ibank_train_u8(d["views"][cut:], d["bank_of"][cut:])
     for b in range(2):
         same_bits(eng.ibank_read_weights(b), got[b], ("cut at", cut, b))
+
+
+# ---- 5b. a step past one launch: the byte bound (8192 columns of 32 x 32 views) and the block-count bound (16384 blocks) --------------------
+def launch_2(lay):
+    """The caller's members with a column in launch 2."""
+    return lay["order"][lay["c0"] // lay["A"]:]
+
+
+def test_a_step_past_the_slab_scores_its_second_launch_under_the_blocks_own_banks(eng, lone):
+    """helpers_inet.SLAB on uploaded patches: launch 2 begins at column 8176, inside a member of bank 1, and holds a block of 44, 24 and 12
+    columns of banks 1, 2 and 3 (M = 17, 33 and 5 under a grid sized for bank 0's 49) -- k_inet_score_cols<true> behind a non-zero
+    x_first, k_inet_decide over columns of two launches."""
+    d, lay = HN.slab_step_data(), HN.slab_layout()
+    got = train_table(eng, d)
+    for b in range(4):
+        close(got[b], d["Ws"][b], "32x32 slab layout, bank %d weights" % b)
+    res = eng.ibank_step_batch_u8(d["planes"], d["banks"])
+    assert not res.flags.any()
+    behind = launch_2(lay)
+    close(res.angle_familiarity[behind], d["fam"][behind], "32x32 slab layout, the %d members of launch 2" % len(behind))
+    close(res.angle_familiarity, d["fam"], "32x32 slab layout, %d members x %d headings" % d["fam"].shape)
+    rows = np.arange(len(d["banks"]))
+    same_bits(res.angle_familiarity[rows, d["first"]], res.angle_familiarity[rows, d["second"]], "equal patches")
+    assert res.best_idex.tolist() == d["first"].tolist()                                  # the first of the two maxima, across the cut too
+    check_against_lone_engines(lone, d, got, d["planes"], d["banks"], res)
+    again = eng.ibank_step_batch_u8(d["planes"], d["banks"])                              # the table and the stage buffers are reused
+    same_bits(again.angle_familiarity, res.angle_familiarity, "the second call")
+    assert again.best_idex.tolist() == res.best_idex.tolist() and not again.flags.any()
+
+
+@pytest.fixture(scope="module")
+def sensing():
+    """An engine with helpers_lands' 32 x 32 sensor, landscape 0 as its one landscape and the four landscapes as a set."""
+    c = HL.SENSORS["sq"]
+    e = navsim_amd.FamiliarityEngine(device=0)
+    e.set_landscape(HL.lands()[0])
+    e.configure_sensor(c["sensor"], c["pixel"], HL.level_tables("sq"), c["mask"])
+    e.lands_set(list(HL.lands()))
+    yield e
+    e.close()
+
+
+@pytest.mark.parametrize("form", ("set", "one"))
+def test_a_sensed_step_past_the_slab_reads_every_member_at_its_own_banks_channel(sensing, form):
+    """helpers_inet.SLAB sensed from poses, bank 0 on channel 2 and banks 1, 2, 3 on 0, 1, 0.  set: every member on its own landscape of
+    the set (lands_launch_sense at c0); one: all on the engine's one landscape (k_sense_each at d_poses + c0).  Then a member of launch
+    2 is moved off its landscape: its flag alone is set (im_perr + c0)."""
+    e = sensing
+    d, lay = HN.slab_sense_data(), HN.slab_layout()
+    begin_table(e, d["h"], d["w"], d["nets"], d["net_of_bank"])
+    e.ibank_train_u8(d["views"], d["bank_of"])
+    for b in range(4):
+        close(e.ibank_read_weights(b), d["Ws"][b], "32x32 slab layout, sensed (%s), bank %d weights" % (form, b))
+    table = dict(land_of_member=d["lands"]) if form == "set" else {}
+    want = d["fam_" + form]
+    res = e.ibank_sense_step_batch(d["xs"], d["ys"], d["angs"], d["banks"], **table)
+    assert not res.flags.any()
+    behind = launch_2(lay)
+    close(res.angle_familiarity[behind], want[behind], "32x32 slab layout, sensed (%s), the %d members of launch 2" % (form, len(behind)))
+    close(res.angle_familiarity, want, "32x32 slab layout, sensed (%s)" % form)
+    assert res.best_idex.tolist() == np.argmax(res.angle_familiarity, axis=1).tolist()
+    m = d["flagged"]
+    xs, ys = d["xs"].copy(), d["ys"].copy()
+    if form == "set":
+        lands = d["lands"].copy()
+        xs[m], ys[m], lands[m] = HN.OFF_THE_SET
+        table = dict(land_of_member=lands)
+    else:
+        xs[m], ys[m] = HN.OFF_THE_ONE
+    off = e.ibank_sense_step_batch(xs, ys, d["angs"], d["banks"], **table)
+    keep = np.delete(np.arange(len(xs)), m)
+    assert off.flags[m] == HS.SENSE_ERROR and off.best_idex[m] == -1 and not off.flags[keep].any()
+    same_bits(off.angle_familiarity[keep], res.angle_familiarity[keep], "beside a flagged member of launch 2")
+    assert off.best_idex[keep].tolist() == res.best_idex[keep].tolist()
+
+
+def lone_rows(lone, d, net, W, members, res):
+    begin_lone(lone, d["h"], d["w"], net)
+    if W is not None:
+        lone.infomax_set_weights(W)
+    for i in members:
+        same_bits(lone.infomax_score_u8(np.ascontiguousarray(d["planes"][i])), res.angle_familiarity[i], ("member", int(i), "bank", int(d["banks"][i])))
+
+
+def test_a_step_of_16385_blocks_scores_the_last_block_in_a_launch_of_its_own(eng, lone):
+    """helpers_inet.BLOCKS: 16385 banks of one member x 3 headings of 7 x 5 views in a scrambled order; the scoring grid's y extent takes
+    16384 blocks, so launch 2 is bank 16384's one block at c0 = 49152 (k_inet_score_cols<false>; M = 3 under a grid sized for 17).
+    Banks 0, 16383 and 16384 are trained in one call, with 16385 as the training grids' y and z extents.  Device memory: X 67.1 MB
+    (239616 columns x 35 x 8: the slab, far from full), dpart 16.8 MB (2 row tiles x 1048640 padded columns x 8), the ragged weights
+    32.1 MB (114 701 rows x 35 x 8), h, u and upart 11.0 MB."""
+    d = HN.blocks_data()
+    B = HN.BLOCKS["banks"]
+    begin_table(eng, d["h"], d["w"], d["nets"], d["net_of_bank"])
+    eng.ibank_train_u8(d["views"], d["bank_of"])
+    info = eng.inet_info()
+    counts = np.zeros(B, dtype=np.int64)
+    counts[list(d["trained"])] = HN.BLOCKS["views"]
+    assert info["n_banks"] == B and info["views_trained"].tolist() == counts.tolist() and info["finite"].all()
+    got = {b: eng.ibank_read_weights(b) for b in d["trained"]}
+    for b, W in d["trained"].items():
+        close(got[b], W, "7x5 bank %d of 16385, weights" % b)
+    res = eng.ibank_step_batch_u8(d["planes"], d["banks"])
+    assert not res.flags.any()
+    close(res.angle_familiarity[d["last"]], d["fam"][d["last"]], "7x5, 16385 blocks: the member of launch 2")
+    close(res.angle_familiarity, d["fam"], "7x5, 16385 blocks")
+    assert res.best_idex.tolist() == np.argmax(res.angle_familiarity, axis=1).tolist()
+    clear = np.flatnonzero(np.sort(d["fam"], axis=1)[:, -1] - np.sort(d["fam"], axis=1)[:, -2] > 1000 * H.TOL * np.abs(d["fam"]).max())
+    assert len(clear) > B // 2 and res.best_idex[clear].tolist() == np.argmax(d["fam"][clear], axis=1).tolist()
+    for b in d["trained"]:                                                                # lone engines: the trained banks ...
+        net = d["nets"][d["net_of_bank"][b]]
+        begin_lone(lone, d["h"], d["w"], net)
+        lone.infomax_train_u8(np.ascontiguousarray(d["views"][d["bank_of"] == b]))
+        same_bits(lone.infomax_read_weights(), got[b], ("weights of bank", b))
+        lone_rows(lone, d, net, got[b], [d["order"][b]], res)
+    for b in (1, 2, 3, 8191, 8192, B - 4, B - 3):                                         # ... and a handful at their W0, up to the last blocks
+        same_bits(eng.ibank_read_weights(b), d["nets"][d["net_of_bank"][b]]["w0"], b)
+        lone_rows(lone, d, d["nets"][d["net_of_bank"][b]], None, [d["order"][b]], res)
+    again = eng.ibank_step_batch_u8(d["planes"], d["banks"])
+    same_bits(again.angle_familiarity, res.angle_familiarity, "the second call")
 
 
 # ---- 6. divergence is a bank's own ------------------------------------------------------------------------------------------------------------

@@ -189,6 +189,79 @@ def test_training_and_steps_take_turns_at_one_table_buffer(eng, lone, key):
         assert res.best_idex.tolist() == np.argmax(res.angle_familiarity, axis=1).tolist()
 
 
+# ---- 2b. steps past one launch: the byte bound and the block-count bound (layouts of tests/helpers_inet.py) ----------------------------------
+def close(got, want, what):
+    err = float(np.max(np.abs(np.asarray(got) - want)) / np.max(np.abs(want)))
+    print("infomax banks, %s: relative error %.3e (bound %.1e)" % (what, err, H.TOL))
+    assert err <= H.TOL, (what, err)
+
+
+def test_a_step_past_the_slab_scores_its_second_launch_behind_an_uploaded_slab(eng, lone):
+    """688 members x 12 headings of 32 x 32 views over four banks of M = 24: launch 2 begins at column 8176, inside a member of bank 1,
+    with blocks of 44, 24 and 12 columns of banks 1, 2 and 3 -- k_im_score_cols_banks<true> at a non-zero x_first behind a slab of
+    uploaded planes, and k_im_decide_banks over a member whose columns come from two launches."""
+    from tests import helpers_inet as HN
+    d, lay = HB.slab_step_data(), HN.slab_layout()
+    begin(eng, d, n_banks=4, eta=HB.SLAB["eta"], weights=d["Ws"])
+    res = eng.ibank_step_batch_u8(d["planes"], d["banks"])
+    assert not res.flags.any()
+    behind = lay["order"][lay["c0"] // lay["A"]:]
+    close(res.angle_familiarity[behind], d["fam"][behind], "32x32 slab layout, the %d members of launch 2" % len(behind))
+    close(res.angle_familiarity, d["fam"], "32x32 slab layout, %d members x %d headings" % d["fam"].shape)
+    rows = np.arange(len(d["banks"]))
+    same_bits(res.angle_familiarity[rows, d["first"]], res.angle_familiarity[rows, d["second"]], "equal patches")
+    assert res.best_idex.tolist() == d["first"].tolist()                                  # the first of two equal maxima, across the cut too
+    lone.infomax_begin(d["h"], d["w"], d["W0"], 2, HB.SLAB["eta"])
+    for r in range(4):
+        lone.infomax_set_weights(d["Ws"][r])
+        for i in np.flatnonzero(d["banks"] == r):
+            same_bits(res.angle_familiarity[i], lone.infomax_score_u8(d["planes"][i]), (int(i), r))
+    again = eng.ibank_step_batch_u8(d["planes"], d["banks"])
+    same_bits(again.angle_familiarity, res.angle_familiarity, "the second call")
+    # ... and trained on the device, every bank is its chain alone
+    begin(eng, d, n_banks=4, eta=HB.SLAB["eta"])
+    eng.ibank_train_u8(d["views"], d["bank_of"])
+    for r in range(4):
+        close(eng.ibank_read_weights(r), d["Ws"][r], "32x32 slab layout, bank %d weights" % r)
+
+
+def test_a_step_of_16385_blocks_scores_the_last_block_in_a_launch_of_its_own(eng, lone):
+    """16385 banks of M = 15, one member x 3 headings of 7 x 5 views each, in a scrambled order: the scoring grid's y extent takes 16384
+    blocks, launch 2 is bank 16384's one block at c0 = 49152 (k_im_score_cols_banks<false>).  Banks 0, 16383 and 16384 hold trained
+    weights.  Device memory: X 67.1 MB (239616 columns x 35 x 8: the slab, far from full), dpart 8.4 MB (one row tile x 1048640 padded
+    columns x 8), weights 68.8 MB (16385 x 15 x 35 x 8)."""
+    d = HB.blocks_data()
+    B = len(d["banks"])
+    eng.infomax_begin(d["h"], d["w"], d["W0"], 2, HB.BLOCKS["eta"])
+    eng.ibank_set(B, d["W0"])
+    for b, W in d["trained"].items():
+        eng.ibank_set_weights(b, W)
+    res = eng.ibank_step_batch_u8(d["planes"], d["banks"])
+    assert not res.flags.any()
+    close(res.angle_familiarity[d["last"]], d["fam"][d["last"]], "7x5, 16385 blocks: the member of launch 2")
+    close(res.angle_familiarity, d["fam"], "7x5, 16385 blocks")
+    assert res.best_idex.tolist() == np.argmax(res.angle_familiarity, axis=1).tolist()
+    lone.infomax_begin(d["h"], d["w"], d["W0"], 2, HB.BLOCKS["eta"])
+    for b in (1, 2, 8191, 8192, B - 4, B - 3):                                            # banks at W0, up to the last blocks of launch 1
+        i = d["order"][b]
+        same_bits(res.angle_familiarity[i], lone.infomax_score_u8(d["planes"][i]), b)
+    for b, W in d["trained"].items():                                                     # ... and both sides of block 16384
+        lone.infomax_set_weights(W)
+        i = d["order"][b]
+        same_bits(res.angle_familiarity[i], lone.infomax_score_u8(d["planes"][i]), b)
+    again = eng.ibank_step_batch_u8(d["planes"], d["banks"])
+    same_bits(again.angle_familiarity, res.angle_familiarity, "the second call")
+    # the three banks trained on the device, with 16385 as the training grids' extents
+    eng.ibank_set(B, d["W0"])
+    eng.ibank_train_u8(d["views"], d["bank_of"])
+    counts = np.zeros(B, dtype=np.int64)
+    counts[list(d["trained"])] = 3
+    assert eng.ibank_info()["views_trained"].tolist() == counts.tolist()
+    for b, W in d["trained"].items():
+        close(eng.ibank_read_weights(b), W, "7x5 bank %d of 16385, weights" % b)
+    same_bits(eng.ibank_read_weights(B - 3), d["W0"], "an untrained bank")
+
+
 # ---- 3. sensed: three routes on the landscape of helpers_infomax.SENSED ----------------------------------------------------------------------
 def _sensed_agent():
     return H.sensed_agent(infomax_familiarity(**HB.SENSED_MODEL), True)

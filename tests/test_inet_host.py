@@ -1,6 +1,7 @@
 """Network tables of the Infomax model without a device: the binding surface of the dv_inet_* calls, where the kernels live, the engine's
 argument checks (made before any library call), util.infomax_network against the draws of infomax_familiarity's begin, and the networks=
-plumbing of InfomaxRouteEnsemble against a fake engine's call log (tests/helpers_inet.py)."""
+plumbing of InfomaxRouteEnsemble against a fake engine's call log (tests/helpers_inet.py), and the layouts of the steps that run past one
+launch: where the cut falls by the kernel file's constants, what a launch-local index would change, the tolerance rule on them."""
 import ctypes
 import inspect
 import os
@@ -61,6 +62,130 @@ def test_the_kernels_live_in_their_own_file_and_the_bodies_are_read_not_copied()
     assert not re.findall(r"\bvoid\s+(k_inet[a-z0-9_]*)\s*\(", old)
     assert '#include "dejavu_inet.inl"' in open(os.path.join(csrc, "dejavu_hip.hip")).read()
     assert "dejavu_inet.inl" in open(os.path.join(csrc, "Makefile")).read()
+
+
+# ---- a step past one launch: the layouts of tests/test_gpu_inet.py reach the edges they are there for ---------------------------------------
+def test_step_slabs_states_the_cut_of_the_kernel_files_constants():
+    stage, cols_max, heads = HN.slab_constants()
+    src = open(os.path.join(REPO, "navigation-by-deja-vu_amd", "csrc", "dejavu_infomax.inl")).read()
+    for name in ("kImStageBytes", "kImSlabColsMax", "kImHeadings"):
+        assert len(re.findall(r"constexpr\s+[a-z_ ]+\s+%s\s*=" % name, src)) == 1, name
+    assert "nk < (size_t)(kImSlabColsMax / kImHeadings) && nc + blocks[k0 + nk].nc <= slab" in src        # the rule step_slabs restates
+    assert heads == 64 and stage % (8 * heads) == 0 and cols_max % heads == 0
+    slab = stage // (8 * 1024)
+    # one bank: whole blocks fill the slab to its last column, and the next block begins the next launch
+    assert [(c0, nc, len(b)) for c0, nc, b in HN.step_slabs([slab + 1], 1, 1024)] == [(0, slab, slab // heads), (slab, 1, 1)]
+    # two banks: the first one's ragged block leaves the slab short, and no block mixes banks
+    got = HN.step_slabs([3, slab], 1, 1024)
+    assert [(c0, nc, len(b)) for c0, nc, b in got] == [(0, 3 + slab - heads, slab // heads), (3 + slab - heads, heads, 1)]
+    assert got[0][2][0] == (0, 0, 3, 0) and got[0][2][1] == (1, 3, heads, heads) and got[1][2][0] == (1, 3 + slab - heads, heads, slab)
+    # an empty bank has no block; a call within the slab is one launch
+    assert HN.step_slabs([2, 0, 1], 70, 35) == [(0, 210, [(0, 0, 64, 0), (0, 64, 64, 64), (0, 128, 12, 128), (2, 140, 64, 192), (2, 204, 6, 256)])]
+    # the widest step of the tests before these: 14 members x 70 headings at N = 35, one launch
+    assert len(HN.step_slabs(np.bincount(HN.STEP_BANKS, minlength=7).tolist(), 70, 35)) == 1
+
+
+def _own_bank_score(d):
+    return lambda bank, planes: H.familiarity(d["Ws"][bank], planes)
+
+
+def test_the_slab_layout_cuts_a_member_of_bank_1_and_a_wrong_index_would_show():
+    lay, d = HN.slab_layout(), HN.slab_step_data()
+    A, c0 = lay["A"], lay["c0"]
+    assert (c0, lay["nc1"], lay["nc2"], lay["slab"], lay["cut"]) == (8176, 8176, 80, 8192, 4) and d["N"] % 4 == 0
+    assert [b[:3] for b in lay["launches"][1][2]] == [(1, 8176, 44), (2, 8220, 24), (3, 8244, 12)]
+    assert [len(b) for _, _, b in lay["launches"]] == [128, 3] and sorted(set(b[2] for b in lay["launches"][0][2])) == [48, 64]
+    assert np.bincount(d["banks"]).tolist() == list(HN.SLAB["members"]) and (np.diff(d["banks"]) < 0).any()   # the caller's order is not sorted
+    assert [net["n_hidden"] for net in d["nets"]] == [49, 17, 33, 5] and [net["channel"] for net in d["nets"]] == [2, 0, 1, 0]
+    assert np.bincount(d["bank_of"]).tolist() == list(HN.SLAB["trained"]) and d["bank_of"][:4].tolist() == [0, 1, 2, 3]
+    s = lay["straddler"]
+    assert lay["place"][s] * A < c0 < (lay["place"][s] + 1) * A and d["first"][s] < lay["cut"] <= d["second"][s]
+    print("%s: two equal maxima a member, ahead of the third by at least %.2e relative" % (HN.SLAB_NAME, d["margin"]))
+    cols = d["planes"][lay["order"]].reshape((-1,) + d["planes"].shape[2:])
+    bank, x = HN.wrong_index_margins(lay, cols, _own_bank_score(d))
+    told = ~np.isnan(x)
+    print("    launch 2 under the bank of the launch-local place: off by %.2e at least; X read at c %% slab: off by %.2e at least (%d of %d columns)"
+          % (bank.min(), x[told].min(), told.sum(), len(x)))
+    assert bank.min() > 1e-6 and x[told].min() > 1e-6 and told.sum() == lay["nc2"] - (lay["slab"] - c0)
+    mine = slice(0, A - lay["cut"])                                                        # the straddling member's columns of launch 2
+    assert bank[mine].min() > 1e-6 and np.isnan(x[mine]).all()                             # (X behind launch 1's columns: nothing of this call)
+    # ... so for the straddling member: x_first taken at its member's first column, or at a whole block (X read `cut` or c0 % 64 columns on)
+    right = d["fam"][s, lay["cut"]:]
+    assert np.array_equal(right, H.familiarity(d["Ws"][1], cols[c0:c0 + A - lay["cut"]]))
+    for shift in (lay["cut"], c0 % 64):
+        held = cols[c0 + shift:c0 + shift + A - lay["cut"]]
+        assert (np.abs(H.familiarity(d["Ws"][1], held) - right) / np.abs(right)).min() > 1e-6, shift
+
+
+def test_the_tolerance_rule_on_the_slab_layouts_weights_and_scores():
+    d = HN.slab_step_data()
+    w = HN.weight_discrepancy(d["nets"], d["net_of_bank"], d["views"], d["bank_of"], d["Ws"])
+    s = HN.score_discrepancy(lambda **kw: HN.scores(d["nets"], d["net_of_bank"], d["Ws"], d["planes"], d["banks"], **kw), d["fam"])
+    print("%s, uploaded: largest discrepancy of the statement: weights %.2e, scores %.2e (1000 x under TOL %.1e)" % (HN.SLAB_NAME, w, s, H.TOL))
+    assert 1000 * max(w, s) <= H.TOL
+
+
+def test_the_sensed_slab_layout_mixes_channels_and_landscapes_across_the_cut():
+    from tests import helpers_lands as HL
+    lay, d = HN.slab_layout(), HN.slab_sense_data()
+    A, c0, order = lay["A"], lay["c0"], lay["order"]
+    assert HL.SENSORS["sq"]["sensor"] == (HN.SLAB["w"], HN.SLAB["h"])
+    # the first column of launch 2: bank 1 reads channel 0, the bank of the launch-local place (bank 0) channel 2, and the planes differ
+    s, a = lay["straddler"], lay["cut"]
+    assert order[c0 // A] == s and d["banks"][order[0]] == 0 and (d["nets"][0]["channel"], d["nets"][1]["channel"]) == (2, 0)
+    for scenes in (d["scenes_set"], d["scenes_one"]):
+        assert not np.array_equal(scenes[s, a, ..., 0], scenes[s, a, ..., 2])
+        wrong = H.familiarity(d["Ws"][1], scenes[s, a:a + 1, ..., 2])[0]
+        right = H.familiarity(d["Ws"][1], scenes[s, a:a + 1, ..., 0])[0]
+        assert abs(wrong - right) / abs(right) > 1e-6
+    # every member of launch 2 stands on another landscape than the member at its launch-local place, and its view there is another
+    behind = order[c0 // A:]
+    local = order[:len(behind)]
+    assert (d["lands"][behind] != d["lands"][local]).all() and len(set(d["lands"][behind].tolist())) > 1
+    for i, j in zip(behind, local):
+        assert not np.array_equal(d["scenes_set"][i, A - 1], HL.host_scene("sq", d["xs"][i], d["ys"][i], d["angs"][i, A - 1], d["lands"][j]))
+    # the set's and the one landscape's steps differ where a member is not on landscape 0
+    off0 = d["lands"] != 0
+    assert (np.abs(d["fam_set"][off0] - d["fam_one"][off0]).max(axis=1) > 1e-6 * np.abs(d["fam_one"][off0]).max()).all()
+    assert np.array_equal(d["fam_set"][~off0], d["fam_one"][~off0])
+    # the member that is moved off its landscape lies behind c0 and is not the straddling one
+    m = d["flagged"]
+    assert lay["place"][m] * A >= c0 + A and m != s and lay["place"][m] != len(order) - 1
+    x, y, l = HN.OFF_THE_SET
+    assert all(HL.is_off("sq", x, y, ang, l) for ang in d["angs"][m]) and all(HL.is_off("sq", *HN.OFF_THE_ONE, ang, 0) for ang in d["angs"][m])
+    worst = 0.0
+    for scenes, fam in ((d["scenes_set"], d["fam_set"]), (d["scenes_one"], d["fam_one"])):
+        worst = max(worst, HN.score_discrepancy(lambda **kw: HN.scores(d["nets"], d["net_of_bank"], d["Ws"], scenes, d["banks"], **kw), fam))
+    print("%s, sensed: largest discrepancy of the statement's scores %.2e (1000 x under TOL %.1e)" % (HN.SLAB_NAME, worst, H.TOL))
+    assert 1000 * worst <= H.TOL
+
+
+def test_the_blocks_layout_is_16384_blocks_and_one_and_a_wrong_bank_would_show():
+    d = HN.blocks_data()
+    B, A = HN.BLOCKS["banks"], d["A"]
+    assert [(c0, nc, len(b)) for c0, nc, b in d["launches"]] == [(0, 49152, 16384), (49152, 3, 1)] and d["N"] % 4 != 0 and A == 3
+    assert sorted(d["banks"].tolist()) == list(range(B)) and d["last"] != B - 1 and d["banks"][d["last"]] == B - 1
+    M = np.array([net["n_hidden"] for net in d["nets"]])
+    assert M.tolist() == [1, 3, 17] and M[d["net_of_bank"][B - 1]] == 3 and M[d["net_of_bank"][B - 2]] == 17
+    assert (d["net_of_bank"][:B - 2] == np.arange(B - 2) % 3).all() and sorted(d["trained"]) == [0, B - 2, B - 1]
+    assert d["bank_of"].tolist() == [0, B - 2, B - 1] * 3
+    # launch 2's row under the bank of sorted place 0 (bank 0) and under the bank one block back (bank 16383)
+    i = d["last"]
+    right = d["fam"][i]
+    assert right.tolist() == H.familiarity(d["trained"][B - 1], d["planes"][i]).tolist()
+    assert (np.abs(H.familiarity(d["trained"][0], d["planes"][i]) - right) / np.abs(right)).min() > 1e-6
+    assert (np.abs(H.familiarity(d["trained"][B - 2], d["planes"][i]) - right) / np.abs(right)).min() > 1e-6
+    j = int(d["order"][B - 2])
+    assert d["fam"][j].tolist() == H.familiarity(d["trained"][B - 2], d["planes"][j]).tolist()
+    # ... and read at the launch-local column of X, the planes of the member at place 0
+    assert (np.abs(H.familiarity(d["trained"][B - 1], d["planes"][d["order"][0]]) - right) / np.abs(right)).min() > 1e-6
+    lay = HN.blocks_layout()
+    kinds, w0s = d["net_of_bank"], [net["w0"] for net in d["nets"]]
+    s = HN.score_discrepancy(lambda **kw: HN.blocks_scores(lay, kinds, w0s, d["trained"], **kw), d["fam"])
+    w = max(H.chain_discrepancy(d["nets"][kinds[b]]["w0"], d["views"][d["bank_of"] == b], W, d["nets"][kinds[b]]["learning_rate"])
+            for b, W in d["trained"].items())
+    print("%s: largest discrepancy of the statement: weights %.2e, scores %.2e (1000 x under TOL %.1e)" % (HN.BLOCKS_NAME, w, s, H.TOL))
+    assert 1000 * max(w, s) <= H.TOL
 
 
 # ---- infomax_network ---------------------------------------------------------------------------------------------------------------------------

@@ -82,6 +82,45 @@ def test_the_banks_tell_the_members_apart_and_best_headings_are_clear(key, n, A)
         assert len(set(d["banks"].tolist())) > 1
 
 
+# ---- steps past one launch -------------------------------------------------------------------------------------------------------------------
+def test_the_slab_layout_under_banks_of_one_shape_cuts_a_member_and_a_wrong_index_would_show():
+    from tests import helpers_inet as HN
+    lay, d = HN.slab_layout(), HB.slab_step_data()
+    A, c0, s = lay["A"], lay["c0"], lay["straddler"]
+    assert (c0, lay["nc1"], lay["nc2"], lay["cut"]) == (8176, 8176, 80, 4) and [b[:3] for b in lay["launches"][1][2]] == [(1, 8176, 44), (2, 8220, 24), (3, 8244, 12)]
+    assert d["Ws"][0].shape == (24, 1024) and np.bincount(d["bank_of"]).tolist() == list(HN.SLAB["trained"])
+    assert np.array_equal(d["banks"], lay["banks"]) and (np.diff(d["banks"]) < 0).any()
+    assert d["first"][s] < lay["cut"] <= d["second"][s] and d["margin"] > 1000 * H.TOL
+    cols = d["planes"][lay["order"]].reshape((-1,) + d["planes"].shape[2:])
+    bank, x = HN.wrong_index_margins(lay, cols, lambda b, planes: H.familiarity(d["Ws"][b], planes))
+    told = ~np.isnan(x)
+    print("%s, M = 24 a bank: maxima ahead by %.2e; launch 2 under the launch-local place's bank off by %.2e at least, X read at c %% slab by %.2e"
+          % (HN.SLAB_NAME, d["margin"], bank.min(), x[told].min()))
+    assert bank.min() > 1e-6 and x[told].min() > 1e-6 and told.sum() == 64
+    w = max(H.chain_discrepancy(d["W0"], d["views"][d["bank_of"] == b], d["Ws"][b], HB.SLAB["eta"]) for b in range(4))
+    sc = HN.score_discrepancy(lambda **kw: HB.slab_scores(d["Ws"], d["planes"], d["banks"], **kw), d["fam"])
+    print("    largest discrepancy of the statement: weights %.2e, scores %.2e (1000 x under TOL %.1e)" % (w, sc, H.TOL))
+    assert 1000 * max(w, sc) <= H.TOL
+
+
+def test_the_blocks_layout_under_banks_of_one_shape_is_16384_blocks_and_one():
+    from tests import helpers_inet as HN
+    d = HB.blocks_data()
+    B = HN.BLOCKS["banks"]
+    assert [(c0, nc, len(b)) for c0, nc, b in d["launches"]] == [(0, 49152, 16384), (49152, 3, 1)] and d["W0"].shape == (15, 35)
+    assert sorted(d["trained"]) == [0, B - 2, B - 1] and d["last"] != B - 1 and d["banks"][d["last"]] == B - 1
+    i = d["last"]
+    right = d["fam"][i]
+    assert right.tolist() == H.familiarity(d["trained"][B - 1], d["planes"][i]).tolist()
+    for W in (d["trained"][0], d["trained"][B - 2], d["W0"]):                             # the bank of sorted place 0, one block back, no bank's
+        assert (np.abs(H.familiarity(W, d["planes"][i]) - right) / np.abs(right)).min() > 1e-6
+    assert (np.abs(H.familiarity(d["trained"][B - 1], d["planes"][d["order"][0]]) - right) / np.abs(right)).min() > 1e-6
+    w = max(H.chain_discrepancy(d["W0"], d["views"][d["bank_of"] == b], W, HB.BLOCKS["eta"]) for b, W in d["trained"].items())
+    sc = HN.score_discrepancy(lambda **kw: HB.blocks_scores(d["W0"], d["trained"], **kw), d["fam"])
+    print("%s, M = 15 a bank: largest discrepancy of the statement: weights %.2e, scores %.2e (1000 x under TOL %.1e)" % (HN.BLOCKS_NAME, w, sc, H.TOL))
+    assert 1000 * max(w, sc) <= H.TOL
+
+
 # ---- binding surface -------------------------------------------------------------------------------------------------------------------------
 def test_header_bindings_and_engine_agree_on_the_ibank_names():
     header = open(os.path.join(REPO, "include", "dejavu.h")).read()

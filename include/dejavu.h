@@ -1001,6 +1001,38 @@ int dv_rvreloc_sense_step(dv_ctx *ctx, const double *x, const double *y, const d
                           const int32_t *win_lo, const int32_t *win_hi, const double *reloc_below, uint32_t flags,
                           double *angle_fam, int64_t *angle_view, int32_t *best_heading, uint32_t *member_flags);
 
+/* ---- SSD on the route view store: exact sum of squared differences of one channel ---- */
+/*
+ * The reference's `ssds` (navsim/util.pyx:171-184) of channel `channel` (0, 1 or 2: H, S or V; one value per call) between every
+ * member's patches and the views of ITS OWN route of the live store (dv_rviews_set_u8 / dv_rviews_set_from_poses, unchanged), on
+ * the int8 matrix cores: sum (a - b)^2 = sum a'^2 + sum b'^2 - 2 sum a' b' with a' = a - 128, b' = b - 128, in integers, so every
+ * value is the exact integer the reference's float64 loop gives and ties are decided by index alone.  The store is read as it lies;
+ * nothing of it, and nothing dv_rviews_* keeps on the device, is written.
+ *   step_u8          patches: uint8[n_agents][n_headings][h][w][3].  angle_ssd[i * n_headings + a]: the least ssds(patch[..., channel],
+ *                    view[..., channel]) over the views of member i's route (an integer below 2^31, as a double), angle_view (may be
+ *                    NULL) the LEAST route-relative view index that attains it, best_heading[i] the FIRST heading with the least
+ *                    angle_ssd (np.argmax(-angle_ssd)).  Any n_headings >= 1, any n_agents.
+ *   sense_step       step_u8 with the patches sensed as dv_rviews_sense_step senses them (landscape sets and sensor tables included):
+ *                    one enqueue, one wait.  member_flags[i] carries DV_RES_SENSE_ERROR for a member whose footprint leaves its own
+ *                    landscape (its row is unspecified, its best_heading -1); the others are scored.
+ *   scene_u8 / scene per view of member i's route the LARGEST ssds over its headings (-scene_ssd is the reference's scene_familiarity),
+ *                    the members' rows back to back as in dv_rviews_scene (n_out doubles).  A member with DV_RES_SENSE_ERROR gets a
+ *                    row of -inf.  member_flags may be NULL.
+ * Checks: dv_rviews_*'s and 0 <= channel <= 2, all before anything reaches the device; DV_ERR_INVALID names the entry and a refused
+ * call changes nothing; DV_ERR_STATE without a store.  The view norms are worked out at the first call on a (store, channel) and kept
+ * until the store is replaced or cleared.
+ */
+int dv_rvssd_step_u8(dv_ctx *ctx, const uint8_t *patches, int n_agents, int n_headings, const int32_t *route_of_member, int channel,
+                     double *angle_ssd, int64_t *angle_view, int32_t *best_heading);
+int dv_rvssd_sense_step(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
+                        const int32_t *route_of_member, const int32_t *land_of_member, int channel,
+                        double *angle_ssd, int64_t *angle_view, int32_t *best_heading, uint32_t *member_flags);
+int dv_rvssd_scene_u8(dv_ctx *ctx, const uint8_t *patches, int n_agents, int n_headings, const int32_t *route_of_member, int channel,
+                      int64_t n_out, double *scene_ssd);
+int dv_rvssd_scene(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
+                   const int32_t *route_of_member, const int32_t *land_of_member, int channel,
+                   int64_t n_out, double *scene_ssd, uint32_t *member_flags);
+
 /* ---- measurement ------------------------------------------------------- */
 /* hipEvent pair on the context's stream around whatever is enqueued between the two calls. */
 int dv_timer_start(dv_ctx *ctx);

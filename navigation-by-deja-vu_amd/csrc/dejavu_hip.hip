@@ -425,6 +425,16 @@ struct dv_ctx {
     size_t rvw_plan_cap = 0;                  // bytes
     bool rvw_lds_opted = false;               // k_rvwin_score's LDS above 64 KB has been asked for
     int rvw_split_env = 1;                    // DEJAVU_RVWIN_SPLIT: 0 = a window of one or two chunks is not cut by pixels (measurements)
+    unsigned long long rv_gen = 1;            // counts the stores made and cleared: what is derived from a store is that generation's
+    // SSD on the store (dejavu_rvssd.inl: dv_rvssd_*): reads rv_planes and rv_routes, writes nothing of the store's or of dv_rviews_*'s
+    unsigned* rvs_vnorm = nullptr;            // [3][groups][64]: sum (x - 128)^2 per view of a channel
+    unsigned long long rvs_norm_gen[3] = {0, 0, 0};   // the store generation channel ch's norms are of (0: none)
+    unsigned* rvs_op = nullptr;               // [C][Kp * 8] operand dwords of the sorted columns, then pnorm[C]
+    unsigned long long* rvs_keys = nullptr;   // [C]: ssd << 32 | view of the sorted columns
+    unsigned char* rvs_out = nullptr;         // a step's results: ssd[C], view[C], best[N], flags[N]
+    unsigned* rvs_rows = nullptr;             // a scene call's integer rows, then the doubles
+    size_t rvs_vnorm_cap = 0, rvs_op_cap = 0, rvs_keys_cap = 0, rvs_out_cap = 0, rvs_rows_cap = 0;   // bytes
+    MirroredTable rvs_tab;                    // a call's tables (RvssdPlan); never rv_tab
 
     // measurement
     hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -459,6 +469,7 @@ static void mb_free(dv_ctx* c);
 static void lands_free(dv_ctx* c);
 static void sensors_free(dv_ctx* c);
 static void rviews_free(dv_ctx* c);
+static void rvssd_free(dv_ctx* c);
 static void path_routes_free(dv_ctx* c);
 static void free_library(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
@@ -564,6 +575,7 @@ extern "C" void dv_destroy(dv_ctx* c) {
     mb_free(c);
     lands_free(c);
     rviews_free(c);
+    rvssd_free(c);
     path_routes_free(c);
     if (c->d_land) (void)hipFree(c->d_land);
     if (c->d_lut) (void)hipFree(c->d_lut);
@@ -3820,6 +3832,7 @@ extern "C" int dv_stream_read_gbps(dv_ctx* c, int64_t n_bytes, int iters, double
 #include "dejavu_rviews.inl"    // dv_rviews_*: route view store, perfect-memory members scored on their own routes (kernels and host side)
 #include "dejavu_rvreloc.inl"   // k_rvreloc_*: lost windowed members re-localise inside the step, planned and scored on the device (kernels and host side)
 #include "dejavu_rvwin.inl"     // dv_rvwin_*: windowed perfect memory on the route view store, scored in one fused launch (kernel and host side)
+#include "dejavu_rvssd.inl"     // dv_rvssd_*: exact SSD of one channel on the route view store, on the int8 matrix cores (kernels and host side)
 #include "dejavu_infomax.inl"  // dv_infomax_*: the Infomax familiarity model (kernels and host side)
 #include "dejavu_inet.inl"      // dv_inet_*: network tables, a bank's own n_hidden, learning rate, W0 and channel (kernels and host side)
 #include "dejavu_mushroom.inl"  // dv_mb_*: the mushroom-body familiarity model (kernels and host side)

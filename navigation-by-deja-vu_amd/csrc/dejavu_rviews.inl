@@ -305,6 +305,7 @@ static void rviews_free(dv_ctx* c) {
     c->rv_h = c->rv_w = 0;
     c->rv_lmax = 0;
     c->rv_bytes = 0;
+    ++c->rv_gen;
 }
 
 static int rviews_need(dv_ctx* c, const char* who) {
@@ -374,6 +375,7 @@ static int rviews_build(dv_ctx* c, const char* who, const unsigned char* d_raw, 
     c->rv_bytes = (long long)(dwords * 4);
     c->rv_delta = 4.0 * (P + 8.0) * std::ldexp(1.0, -53) * P;           // alloc_library's c->delta
     c->rv_tab.host.clear();
+    ++c->rv_gen;                                                        // (what dejavu_rvssd.inl keeps of the old store is void)
     return DV_OK;
 }
 

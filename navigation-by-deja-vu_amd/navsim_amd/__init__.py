@@ -15,7 +15,7 @@ from .group import FamiliarityGroup
 from ._native import EngineError
 from . import synth
 from .experiment import run_experiment, run_ensemble, chop_path_to_len
-from .ensemble import NavEnsemble, InfomaxEnsemble, MushroomEnsemble, MushroomRouteEnsemble, InfomaxRouteEnsemble, SadsRouteEnsemble
+from .ensemble import NavEnsemble, InfomaxEnsemble, MushroomEnsemble, MushroomRouteEnsemble, InfomaxRouteEnsemble, SadsRouteEnsemble, SsdRouteEnsemble
 from . import generate_landscapes
 from .generate_landscapes import diffuse, diffuse_series
 
@@ -24,5 +24,5 @@ __all__ = [
     "NavigatingFailedException", "TooFarFromTrainingPathException", "OutOfLandscapeBoundsException",
     "sads_familiarity", "hip_sads_familiarity", "ssd_familiarity", "infomax_familiarity", "mushroom_familiarity", "infomax_network", "FamiliarityEngine", "FamiliarityGroup", "EngineError",
     "fill_sensor_from", "downscale_chem", "synth", "run_experiment", "run_ensemble", "chop_path_to_len", "NavEnsemble", "InfomaxEnsemble", "MushroomEnsemble", "MushroomRouteEnsemble", "InfomaxRouteEnsemble",
-    "SadsRouteEnsemble", "generate_landscapes", "diffuse", "diffuse_series",
+    "SadsRouteEnsemble", "SsdRouteEnsemble", "generate_landscapes", "diffuse", "diffuse_series",
 ]

@@ -313,6 +313,12 @@ PROTOTYPES = {
     "dv_rviews_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), _i64p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                       _i64p]),
     "dv_rviews_clear": (ctypes.c_int, [_ctx_p]),
+    "dv_rvssd_step_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, _f64p, _i64p, _i32p]),
+    "dv_rvssd_sense_step": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _i32p, _i32p, ctypes.c_int, _f64p, _i64p,
+                                           _i32p, _u32p]),
+    "dv_rvssd_scene_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, ctypes.c_int64, _f64p]),
+    "dv_rvssd_scene": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _i32p, _i32p, ctypes.c_int, ctypes.c_int64, _f64p,
+                                      _u32p]),
     "dv_rvwin_step_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, _i32p, _f64p, _i32p, _i32p, ctypes.c_uint32, _f64p, _i64p,
                                         _i32p]),
     "dv_rvwin_sense_step": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _i32p, _f64p, _i32p, _i32p, _i32p,

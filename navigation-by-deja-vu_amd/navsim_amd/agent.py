@@ -599,7 +599,7 @@ class NavBySceneFamiliarity(object):
             # (a step of its own scores under bank 0 of the model: only its ensemble's batches score it under its own bank -- or, for the
             # perfect-memory model, against its own route's views of the store)
             name = route_ensemble_name(self)
-            if name == "SadsRouteEnsemble":
+            if name in ("SadsRouteEnsemble", "SsdRouteEnsemble"):
                 raise ValueError("this ensemble member's route is route %d of the view store it shares: step it with its %s"
                                  % (self.memory_bank, name))
             raise ValueError("this ensemble member's route is kept in memory bank %d of a model it shares: step it with its %s"

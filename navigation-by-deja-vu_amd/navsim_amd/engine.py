@@ -80,6 +80,16 @@ class RouteViewResults(OneValueBatchResults):
         return (np.asarray(self.flags) & N.DV_RES_RELOCALISED) != 0
 
 
+class RouteSsdResults(RouteViewResults):
+    """An SSD step on the route view store (dv_rvssd_step_u8 / dv_rvssd_sense_step): angle_ssd[n, A] (float64 holding the exact
+    integers), angle_view[n, A] the least view of the member's route that attains it, best_idex[n] the first least heading, and
+    angle_familiarity = np.negative(angle_ssd): the lone SSD agent's bits, -0.0 included."""
+
+    def __init__(self, angle_ssd, angle_view, best_idex, flags):
+        RouteViewResults.__init__(self, np.negative(angle_ssd), angle_view, best_idex, flags)
+        self.angle_ssd = angle_ssd
+
+
 InfomaxBatchResults = OneValueBatchResults    # the name it had while Infomax was the only such model
 
 # The one-value models -- no library, ONE value per heading: metric -> (prefix of the single calls' symbols, of the batch calls', the
@@ -1922,5 +1932,69 @@ class FamiliarityEngine(object):
         self._check(self._lib.dv_rviews_scene(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, routes.ctypes.data_as(N._i32p),
                                               N.f64ptr(w), None if lands is None else lands.ctypes.data_as(N._i32p), len(out), N.f64ptr(out),
                                               flags.ctypes.data_as(N._u32p)), "dv_rviews_scene")
+        rows = [out[row0[i]:row0[i + 1]] for i in range(n)]
+        return (rows, flags) if want_flags else rows
+
+    # -- SSD on the store: exact ssds of one channel on the int8 matrix cores (include/dejavu.h: dv_rvssd_*) ------------------------
+    def _rvssd_tables(self, n, route_of_member, channel, land_of_member=None):
+        """The tables of an SSD call as (int32[n], channel, int32[n] or None) -- checked before any library call."""
+        if self.rviews_first is None:
+            raise N.EngineError("no route views: rviews_set_u8 or rviews_set_from_poses first (DV_ERR_STATE)")
+        if isinstance(channel, bool) or not isinstance(channel, (int, np.integer)) or not 0 <= channel <= 2:
+            raise ValueError("channel must be 0, 1 or 2 (H, S or V), got %r" % (channel,))
+        routes = self._index_table(route_of_member, "route_of_member", len(self.rviews_first) - 1, "n_banks", n, "bank")
+        lands = None if land_of_member is None else self._land_table(land_of_member, n, "land_of_member")
+        return routes, int(channel), lands
+
+    def rvssd_step_u8(self, patches, route_of_member, channel=2):
+        """patches: uint8[n, A, h, w, 3]; member i's channel `channel` is scored as the reference's ssds against the views of route
+        route_of_member[i] -> RouteSsdResults: angle_ssd[n, A] (exact integers as float64), angle_view[n, A] (the least view of the
+        route that attains it), best_idex[n] (the first least heading), flags[n], angle_familiarity = -angle_ssd."""
+        patches = self._rviews_patches(patches)
+        n, A = patches.shape[:2]
+        routes, channel, _ = self._rvssd_tables(n, route_of_member, channel)
+        ssd, best, flags = self._member_results(n, A)
+        view = np.empty((n, A), dtype=np.int64)
+        self._check(self._lib.dv_rvssd_step_u8(self._ctx, N.u8ptr(patches), n, A, routes.ctypes.data_as(N._i32p), channel, N.f64ptr(ssd),
+                                               N.i64ptr(view), best.ctypes.data_as(N._i32p)), "dv_rvssd_step_u8")
+        return RouteSsdResults(ssd, view, best, flags)
+
+    def rvssd_sense_step(self, x, y, angles, route_of_member, channel=2, land_of_member=None):
+        """rvssd_step_u8 with member i's patches sensed at (x[i], y[i]) along angles[i] (on landscape land_of_member[i] of the live
+        set): one enqueue and one wait.  flags[i] carries DV_RES_SENSE_ERROR = 16 for a member whose footprint leaves its landscape."""
+        x, y, angles = self._member_poses(x, y, angles)
+        n, A = angles.shape
+        routes, channel, lands = self._rvssd_tables(n, route_of_member, channel, land_of_member)
+        ssd, best, flags = self._member_results(n, A)
+        view = np.empty((n, A), dtype=np.int64)
+        self._check(self._lib.dv_rvssd_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, routes.ctypes.data_as(N._i32p),
+                                                  None if lands is None else lands.ctypes.data_as(N._i32p), channel, N.f64ptr(ssd),
+                                                  N.i64ptr(view), best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)),
+                    "dv_rvssd_sense_step")
+        return RouteSsdResults(ssd, view, best, flags)
+
+    def rvssd_scene_u8(self, patches, route_of_member, channel=2):
+        """Per member a float64[len(its route)]: per view the largest ssds over the headings (its negative is scene_familiarity)."""
+        patches = self._rviews_patches(patches)
+        n, A = patches.shape[:2]
+        routes, channel, _ = self._rvssd_tables(n, route_of_member, channel)
+        row0 = self._rviews_rows(routes)
+        out = np.empty(row0[-1], dtype=np.float64)
+        self._check(self._lib.dv_rvssd_scene_u8(self._ctx, N.u8ptr(patches), n, A, routes.ctypes.data_as(N._i32p), channel, len(out),
+                                                N.f64ptr(out)), "dv_rvssd_scene_u8")
+        return [out[row0[i]:row0[i + 1]] for i in range(n)]
+
+    def rvssd_scene(self, x, y, angles, route_of_member, channel=2, land_of_member=None, want_flags=False):
+        """rvssd_scene_u8 with the patches sensed as rvssd_sense_step senses them; a member whose footprint leaves its landscape gets
+        a row of -inf and DV_RES_SENSE_ERROR = 16 in its flag.  want_flags: returns (rows, flags uint32[n])."""
+        x, y, angles = self._member_poses(x, y, angles)
+        n, A = angles.shape
+        routes, channel, lands = self._rvssd_tables(n, route_of_member, channel, land_of_member)
+        row0 = self._rviews_rows(routes)
+        out = np.empty(row0[-1], dtype=np.float64)
+        flags = np.zeros(n, dtype=np.uint32)
+        self._check(self._lib.dv_rvssd_scene(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, routes.ctypes.data_as(N._i32p),
+                                             None if lands is None else lands.ctypes.data_as(N._i32p), channel, len(out), N.f64ptr(out),
+                                             flags.ctypes.data_as(N._u32p)), "dv_rvssd_scene")
         rows = [out[row0[i]:row0[i + 1]] for i in range(n)]
         return (rows, flags) if want_flags else rows

@@ -19,7 +19,7 @@ single agent works its minimum out when it is read.
 import numpy as np
 
 from .agent import StopNavigationException, OutOfLandscapeBoundsException, coverage_row
-from .util import reject_infomax, reject_mushroom, reject_banked
+from .util import reject_infomax, reject_mushroom, reject_banked, route_ensemble_name
 
 
 class NavEnsemble(object):
@@ -495,7 +495,9 @@ class _RouteEnsemble(_OneValueEnsemble):
 
     @classmethod
     def _reject_banked(cls, agent):
-        """(its own members are the banked ones)"""
+        """(its own members are the banked ones; an SsdRouteEnsemble's carry a route of the view store, not a bank of this model)"""
+        if getattr(agent, "memory_bank", None) is not None and route_ensemble_name(agent) == "SsdRouteEnsemble" and cls.__name__ != "SsdRouteEnsemble":
+            reject_banked(agent, cls.__name__)
 
     @classmethod
     def from_agent(cls, agent, poses):
@@ -943,6 +945,8 @@ class SadsRouteEnsemble(_RouteEnsemble):
         if metric == "mushroom":
             raise ValueError("SadsRouteEnsemble does not take a mushroom-body model: navsim_amd.MushroomRouteEnsemble steps that one")
         if metric is not None or not callable(getattr(model, "from_engine", None)) or getattr(model, "chem_weight", None) is None:
+            if metric == "ssd":
+                raise ValueError("SadsRouteEnsemble takes %s; navsim_amd.SsdRouteEnsemble steps the SSD model" % cls._takes)
             raise ValueError("SadsRouteEnsemble takes %s; the SSD models and foreign plug-ins have no routed form" % cls._takes)
 
     @classmethod
@@ -1183,3 +1187,92 @@ class SadsRouteEnsemble(_RouteEnsemble):
             raise ValueError("construct the agents with track_scene_familiarity=True (the default) to read scene_familiarity")
         self._read_scene()
         return [a.scene_familiarity.copy() for a in self.agents]
+
+
+class SsdRouteEnsemble(_RouteEnsemble):
+    """The route ensemble of the north star's literal metric, the sum of squared differences (util.ssd_familiarity(channel)): trials
+    that differ in their start, their TRAINING ROUTE and their LANDSCAPE step as one ensemble.  The views of all routes lie in the
+    engine's route view store (FamiliarityEngine.rviews_set_from_poses: one call senses them all, the store SadsRouteEnsemble uses),
+    and a step scores channel `channel` of every running member's headings against the views of ITS OWN route on the int8 matrix cores
+    in ONE device call (dv_rvssd_sense_step).  Every score is the exact integer of the reference's `ssds`, so a member's
+    angle_familiarity (-SSD) is a lone agent's row bit for bit, and ties go to the first heading as np.argmax decides them.  A
+    member's scene_familiarity is worked out when read (dv_rvssd_scene); its `memory_bank` is its route's place in the store.
+    All members share the model's one channel.  Made by from_routes / from_routes_with / from_landscapes (see _RouteEnsemble)."""
+    _metric = "ssd"
+    _takes = "agents of the SSD model (familiarity_model=ssd_familiarity(channel))"
+    _info_call = "rviews_info"               # dict(n_routes, first int64[R + 1], shape, bytes)
+    _one_route = "a lone NavBySceneFamiliarity"
+
+    @classmethod
+    def from_agent(cls, agent, poses):
+        raise ValueError("SsdRouteEnsemble is made from routes (from_routes): it takes an untrained agent and trains every route itself")
+
+    @classmethod
+    def _reject_others(cls, agent):
+        for obj in (agent, getattr(agent, "familiarity_model", None), getattr(agent, "_familiarity_func", None)):
+            metric = getattr(obj, "metric", None)
+            if metric == "infomax":
+                raise ValueError("SsdRouteEnsemble does not take an Infomax model: navsim_amd.InfomaxRouteEnsemble steps that one")
+            if metric == "mushroom":
+                raise ValueError("SsdRouteEnsemble does not take a mushroom-body model: navsim_amd.MushroomRouteEnsemble steps that one")
+
+    @classmethod
+    def _reject_banked(cls, agent):
+        """Its own members are the banked ones; another route ensemble's are refused by name."""
+        if getattr(agent, "memory_bank", None) is not None and route_ensemble_name(agent) != cls.__name__:
+            reject_banked(agent, cls.__name__)
+
+    @classmethod
+    def _check_model(cls, model):
+        cls._reject_others(model)
+        if getattr(model, "metric", None) != "ssd" or getattr(model, "channel", None) not in (0, 1, 2):
+            if getattr(model, "metric", None) is None and getattr(model, "chem_weight", None) is not None:
+                raise ValueError("SsdRouteEnsemble does not take a perfect-memory model: navsim_amd.SadsRouteEnsemble steps that one")
+            raise ValueError("SsdRouteEnsemble takes %s" % cls._takes)
+
+    @classmethod
+    def _check_member(cls, agent):
+        func = getattr(agent, "_familiarity_func", None)
+        cls._reject_banked(agent)
+        cls._check_model(getattr(agent, "familiarity_model", None))
+        if getattr(agent, "_engine", None) is None:
+            raise ValueError("SsdRouteEnsemble needs agents whose sensor model runs on the GPU (use_gpu_sensor=True)")
+        if agent.training_path is None or func is None or getattr(func, "engine", None) is not agent._engine:
+            raise ValueError("SsdRouteEnsemble needs the members from_routes makes")
+
+    @staticmethod
+    def _begin_model(model, eng, agent):
+        """(nothing to begin: the store is made by the call that senses the routes)"""
+
+    _train_banks = staticmethod(SadsRouteEnsemble._train_banks)
+
+    def __init__(self, agents, metrics="host"):
+        channels = [getattr(getattr(a, "familiarity_model", None), "channel", None) for a in agents]
+        for i, ch in enumerate(channels):
+            if ch in (0, 1, 2) and ch != channels[0] and channels[0] in (0, 1, 2):
+                raise ValueError("SsdRouteEnsemble: member %d compares channel %d, member 0 channel %d: the members of an ensemble share "
+                                 "one channel" % (i, ch, channels[0]))
+        super(SsdRouteEnsemble, self).__init__(agents, metrics=metrics)
+        self.channel = int(channels[0])
+
+    def _device_step(self, idx, xs, ys, angs):
+        return self.engine.rvssd_sense_step(xs, ys, angs, self._banks[idx], self.channel,
+                                            land_of_member=None if self._lands is None else self._lands[idx])
+
+    # scene_familiarity: worked out when read, as SadsRouteEnsemble's members' (a per-view extreme, not the one-value models' fill)
+    _note_scene = NavEnsemble._note_scene
+
+    def _read_scene(self):
+        todo = [a for a in self.agents if a._scene_stale is not None and a._scene_owner is self]
+        if not todo:
+            return
+        st = [a._scene_stale for a in todo]
+        lands = None if self._lands is None else [a.landscape_index for a in todo]
+        rows = self.engine.rvssd_scene([t[0] for t in st], [t[1] for t in st], np.stack([t[2] for t in st]), [a.memory_bank for a in todo],
+                                       self.channel, land_of_member=lands)
+        for a, row in zip(todo, rows):
+            a._scene_stale = None
+            a._scene_owner = None
+            np.negative(row, out=a._scene_fam)                    # min over headings of -SSD = -(max over headings of SSD)
+
+    scene_familiarity = SadsRouteEnsemble.scene_familiarity

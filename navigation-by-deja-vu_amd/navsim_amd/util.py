@@ -166,6 +166,8 @@ def route_ensemble_name(agent):
     metrics = [getattr(obj, "metric", None) for obj in (agent, getattr(agent, "familiarity_model", None), getattr(agent, "_familiarity_func", None))]
     if "infomax" in metrics:
         return "InfomaxRouteEnsemble"
+    if any(str(m).startswith("ssd") for m in metrics if m is not None):
+        return "SsdRouteEnsemble"                                 # (ssd_familiarity: "ssd", its bound func "ssd_u8")
     if all(m is None for m in metrics) and getattr(getattr(agent, "familiarity_model", None), "chem_weight", None) is not None:
         return "SadsRouteEnsemble"                                # (the perfect-memory model's product carries a weight and no metric)
     return "MushroomRouteEnsemble"
@@ -175,9 +177,9 @@ def reject_banked(agent, what):
     """The refusal of every ensemble but the member's own route ensemble (navsim_amd.MushroomRouteEnsemble, InfomaxRouteEnsemble): the
     member's route is kept in a bank of its own (agent.memory_bank), and the other ensembles' steps score under the model's first bank."""
     if getattr(agent, "memory_bank", None) is not None:
-        if route_ensemble_name(agent) == "SadsRouteEnsemble":
-            raise ValueError("%s does not take a member of a SadsRouteEnsemble: its route is route %d of the engine's view store, "
-                             "and only that ensemble's step scores it there" % (what, agent.memory_bank))
+        if route_ensemble_name(agent) in ("SadsRouteEnsemble", "SsdRouteEnsemble"):
+            raise ValueError("%s does not take a member of a %s: its route is route %d of the engine's view store, "
+                             "and only that ensemble's step scores it there" % (what, route_ensemble_name(agent), agent.memory_bank))
         raise ValueError("%s does not take a member of a %s: its route is kept in memory bank %d of the shared model, "
                          "and only that ensemble's step scores it there" % (what, route_ensemble_name(agent), agent.memory_bank))
 

@@ -2,7 +2,7 @@
 """Times a step of the route view store (dv_rviews_sense_step, navsim_amd.SadsRouteEnsemble) at a slice of the reference's grid and
 writes profiles/rviews_time.json.
 
-    python tools/rviews_time.py [--sides 32,64] [--calls 30] [--reps 5] [--blocks routes[,sensors][,window][,reloc]] [--out profiles/rviews_time.json]
+    python tools/rviews_time.py [--sides 32,64] [--calls 30] [--reps 5] [--blocks routes[,sensors][,window][,reloc][,ssd]] [--out profiles/rviews_time.json]
 
 Shape: 4 routes x 8 starts x 10 headings = 32 trials of 320 columns, views of side x side.  The routes have the grid's length:
 synth.sin_training_path with arclen = step_size / n_test_angles (scripts/run_experiment.py:207) on a 900 x 900 landscape, one curve
@@ -37,7 +37,13 @@ thresholds), reloc_none_lost_call_us (every threshold -inf: the price of the pla
 reloc_4_lost_call_us (one member a route at +inf) and reloc_all_lost_call_us (all 32), against the host's way at the same poses --
 host_4_lost_call_us / host_all_lost_call_us: the windowed call, then rviews_sense_step on the lost members (two enqueues, two waits, the
 lost members sensed twice) -- and unwindowed_call_us.  The device's and the host's way are checked to agree on their bits before
-anything is timed.  The block is the file's "reloc" key; measured alone it leaves every other key as it was."""
+anything is timed.  The block is the file's "reloc" key; measured alone it leaves every other key as it was.
+
+SSD block (--blocks ssd): the same slice scored as exact SSD of one channel on the int8 matrix cores (dv_rvssd_sense_step) against the
+perfect-memory call (dv_rviews_sense_step) at the same poses on the SAME engine and store, in alternating windows of one process, hipEvent
+pairs: ssd_call_us and sads_call_us, their ratio, and ensemble_step_wall_us (SsdRouteEnsemble.step_forward(fake=True), wall clock).  Two
+members' rows are checked against a NumPy int64 statement on the store's own views before anything is timed.  The block is the file's
+"ssd" key; measured alone it leaves every other key as it was."""
 import argparse
 import json
 import os
@@ -317,13 +323,77 @@ def measure_reloc(side, n_calls, reps):
     return out
 
 
+SSD_CHANNEL = 2
+
+
+def measure_ssd(side, n_calls, reps):
+    """The ssd block's row of one side."""
+    import navsim_amd
+    from navsim_amd import synth
+    land = synth.synth_landscape(3, LAND, 4)
+    routes = [synth.sin_training_path(c, 0.2 * LAND, 0.6 * LAND, arclen=STEP_SIZE / HEADINGS) for c in CURVES]
+    starts = starts_of(routes)
+    a = navsim_amd.NavBySceneFamiliarity(land, (side, side), STEP_SIZE, n_test_angles=HEADINGS, track_scene_familiarity=False,
+                                         familiarity_model=navsim_amd.ssd_familiarity(SSD_CHANNEL))
+    ens = navsim_amd.SsdRouteEnsemble.from_routes_with(a, routes, starts, metrics="device")
+    eng = ens.engine
+    n = len(starts)
+    xs = np.array([p[0] for _, p, _ in starts])
+    ys = np.array([p[1] for _, p, _ in starts])
+    angs = (np.array([a for _, _, a in starts])[:, None] + ens.agents[0].angle_offsets[None, :]) % (2 * np.pi)
+    route_of = np.array([r for r, _, _ in starts], dtype=np.int32)
+    weights = np.full(n, CHEM_WEIGHT)
+
+    def ssd():
+        eng.timer_start()
+        for _ in range(n_calls):
+            res = eng.rvssd_sense_step(xs, ys, angs, route_of, SSD_CHANNEL)
+        return eng.timer_stop() * 1e3 / n_calls, res
+
+    def sads():
+        eng.timer_start()
+        for _ in range(n_calls):
+            res = eng.rviews_sense_step(xs, ys, angs, route_of, weights)
+        return eng.timer_stop() * 1e3 / n_calls, res
+
+    def wall():
+        w0 = time.perf_counter()
+        for _ in range(n_calls):
+            ens.step_forward(fake=True)
+        return (time.perf_counter() - w0) * 1e6 / n_calls
+
+    _, res = ssd()                                                # warm-up of both calls, and the SSD rows are the integers
+    _, plain = sads()
+    assert not res.flags.any() and not plain.flags.any()
+    for i in (0, n - 1):
+        lib = ens.agents[i].familiar_scenes[..., SSD_CHANNEL].reshape(len(routes[route_of[i]]), -1).astype(np.int64)
+        pats = eng.sense(np.full(HEADINGS, xs[i]), np.full(HEADINGS, ys[i]), angs[i])[..., SSD_CHANNEL].reshape(HEADINGS, -1).astype(np.int64)
+        rows = np.stack([((p[None, :] - lib) ** 2).sum(axis=1) for p in pats])
+        assert np.array_equal(res.angle_ssd[i], rows.min(axis=1).astype(np.float64)) and np.array_equal(res.angle_view[i], rows.argmin(axis=1))
+        assert res.best_idex[i] == int(np.argmin(rows.min(axis=1)))
+    wall()
+    assert len(ens.active) == n
+    t_ssd, t_sads, w = [], [], []
+    for _ in range(reps):                                         # alternating windows
+        t_ssd.append(ssd()[0])
+        t_sads.append(sads()[0])
+        w.append(wall())
+    info = eng.rviews_info()
+    out = dict(side=side, routes=len(routes), route_views=[len(r) for r in routes], members=n, headings=HEADINGS, columns=n * HEADINGS,
+               channel=SSD_CHANNEL, chem_weight=CHEM_WEIGHT, calls_per_window=n_calls, windows=reps, store_bytes=info["bytes"],
+               tile_columns=32, view_groups_per_workgroup=4, ssd_call_us=spread(t_ssd), sads_call_us=spread(t_sads),
+               ensemble_step_wall_us=spread(w), sads_over_ssd_call=round(float(np.median(t_sads) / np.median(t_ssd)), 3))
+    eng.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sides", default="32,64")
     ap.add_argument("--calls", type=int, default=30)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rviews_time.json"))
-    ap.add_argument("--blocks", default="routes", help="which blocks to measure: routes (the routed step against four engines), sensors, window, reloc")
+    ap.add_argument("--blocks", default="routes", help="which blocks to measure: routes (the routed step against four engines), sensors, window, reloc, ssd")
     ap.add_argument("--limit", type=int, default=240, help="seconds allowed to the sensors block's GPU child")
     args = ap.parse_args()
     blocks = args.blocks.split(",")
@@ -354,6 +424,13 @@ def main():
                             sizes=[measure_reloc(int(s), args.calls, args.reps) for s in args.sides.split(",")])
     elif "reloc" in kept:
         doc["reloc"] = kept["reloc"]
+    if "ssd" in blocks:                                           # a key of its own, as the window block's
+        if not ({"routes", "sensors", "window", "reloc"} & set(blocks)) and kept:
+            doc = dict(kept)
+        doc["ssd"] = dict(device=torch.cuda.get_device_name(0), channel=SSD_CHANNEL,
+                          sizes=[measure_ssd(int(s), args.calls, args.reps) for s in args.sides.split(",")])
+    elif "ssd" in kept:
+        doc["ssd"] = kept["ssd"]
     with open(args.out, "w") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")

@@ -1033,6 +1033,31 @@ int dv_rvssd_scene(dv_ctx *ctx, const double *x, const double *y, const double *
                    const int32_t *route_of_member, const int32_t *land_of_member, int channel,
                    int64_t n_out, double *scene_ssd, uint32_t *member_flags);
 
+/* ---- SSD on the route view store with a temporal window, and re-localisation inside the step ---- */
+/*
+ * dv_rvssd_step_u8 / dv_rvssd_sense_step with member i scored against views [win_lo[i], win_hi[i]) of its own route only: what the
+ * unwindowed call gives on that slice of the route alone, with win_lo[i] added to its view indices (so win_lo[i] <= angle_view <
+ * win_hi[i]); every value an exact integer, ties by index alone.  A call is the sensing launch, the operand rows, ONE scoring launch in
+ * the caller's column order (no sort, no atomics, no unsort) and the deciding launch.
+ * reloc_below (double[n_agents], or NULL: no loss test), in the unit of the model's familiarity, -SSD, so useful values are <= 0.  THE
+ * RULE: a member that is not flagged DV_RES_SENSE_ERROR is LOST iff max_a(-angle_ssd_window[a]) < reloc_below[i] -- a strict < on the
+ * doubles as they are, so -inf never triggers and +inf always does.  A lost member's row (angle_ssd, angle_view, its best_heading) is
+ * dv_rvssd_step_u8's on its whole route, bit for bit, and its flag word carries DV_RES_RELOCALISED; every other member's row is the
+ * windowed one.  The loss test, the plan of the lost columns, their whole-route scoring and the write-back are enqueued between the
+ * windowed scoring and the deciding launch: ONE enqueue and ONE wait, and the host reads nothing in between.
+ * member_flags (uint32[n_agents]): an output; step_u8 takes NULL when reloc_below is NULL.
+ * Checks, all before anything reaches the device (a refused call changes nothing): dv_rvssd_*'s; dv_rvwin_*'s window rule (0 <=
+ * win_lo[i] < win_hi[i] <= the views of the route, at most DV_RVWIN_MAX_VIEWS views; DV_ERR_INVALID names member, window and route);
+ * with reloc_below, DV_ERR_INVALID naming the member for a NaN, and for n_headings above 32768.  DV_ERR_STATE without a store.
+ */
+int dv_rvssdw_step_u8(dv_ctx *ctx, const uint8_t *patches, int n_agents, int n_headings, const int32_t *route_of_member,
+                      const int32_t *win_lo, const int32_t *win_hi, const double *reloc_below, int channel,
+                      double *angle_ssd, int64_t *angle_view, int32_t *best_heading, uint32_t *member_flags);
+int dv_rvssdw_sense_step(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
+                         const int32_t *route_of_member, const int32_t *land_of_member, const int32_t *win_lo, const int32_t *win_hi,
+                         const double *reloc_below, int channel,
+                         double *angle_ssd, int64_t *angle_view, int32_t *best_heading, uint32_t *member_flags);
+
 /* ---- measurement ------------------------------------------------------- */
 /* hipEvent pair on the context's stream around whatever is enqueued between the two calls. */
 int dv_timer_start(dv_ctx *ctx);

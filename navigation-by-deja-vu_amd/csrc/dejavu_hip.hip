@@ -435,6 +435,9 @@ struct dv_ctx {
     unsigned* rvs_rows = nullptr;             // a scene call's integer rows, then the doubles
     size_t rvs_vnorm_cap = 0, rvs_op_cap = 0, rvs_keys_cap = 0, rvs_out_cap = 0, rvs_rows_cap = 0;   // bytes
     MirroredTable rvs_tab;                    // a call's tables (RvssdPlan); never rv_tab
+    MirroredTable rvsw_tab;                   // a windowed SSD call's tables (dejavu_rvssdw.inl: windows, thresholds, order); never rvs_tab
+    unsigned char* rvs_plan = nullptr;        // what the device writes of a relocalising SSD call's plan (dejavu_rvssdw.inl)
+    size_t rvs_plan_cap = 0;                  // bytes
 
     // measurement
     hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -3833,6 +3836,7 @@ extern "C" int dv_stream_read_gbps(dv_ctx* c, int64_t n_bytes, int iters, double
 #include "dejavu_rvreloc.inl"   // k_rvreloc_*: lost windowed members re-localise inside the step, planned and scored on the device (kernels and host side)
 #include "dejavu_rvwin.inl"     // dv_rvwin_*: windowed perfect memory on the route view store, scored in one fused launch (kernel and host side)
 #include "dejavu_rvssd.inl"     // dv_rvssd_*: exact SSD of one channel on the route view store, on the int8 matrix cores (kernels and host side)
+#include "dejavu_rvssdw.inl"    // dv_rvssdw_*: dv_rvssd_* with a temporal window, lost members re-localised inside the step (kernels and host side)
 #include "dejavu_infomax.inl"  // dv_infomax_*: the Infomax familiarity model (kernels and host side)
 #include "dejavu_inet.inl"      // dv_inet_*: network tables, a bank's own n_hidden, learning rate, W0 and channel (kernels and host side)
 #include "dejavu_mushroom.inl"  // dv_mb_*: the mushroom-body familiarity model (kernels and host side)

@@ -37,13 +37,15 @@ __device__ __forceinline__ int rvreloc_scan(bool keep, int* ws, int& total) {
     return before;
 }
 
-// order, run0, run1: the group's ng sorted places (member; first place of its route's run; one past its last).  pm: [ng + 1].
+// The plan of ONE workgroup (k_rvreloc_plan's body, and k_rvssdw_plan's of dejavu_rvssdw.inl).  order, run0, run1: the group's ng
+// sorted places (member; first place of its route's run; one past its last).  pm: [ng + 1].  ws: 4 ints of LDS.  NEG = 0: fam holds
+// familiarities; NEG = 1: their negatives (SSDs: the familiarity is -fam, an exact negation).
 // (pm, col_of: written and read here, across workgroup barriers: not __restrict__.)
-__global__ void __launch_bounds__(256)
-k_rvreloc_plan(const double* __restrict__ fam, const int* __restrict__ err, const double* __restrict__ tau, const int* __restrict__ route_of,
-               const int* __restrict__ order, const int* __restrict__ run0, const int* __restrict__ run1, int ng, int A, int T,
-               int* __restrict__ lost, int* pm, int* col_of, RvTile* __restrict__ tiles, int* __restrict__ cnt) {
-    __shared__ int ws[4];
+template <int NEG>
+__device__ __forceinline__ void rvreloc_plan(const double* __restrict__ fam, const int* __restrict__ err, const double* __restrict__ tau,
+                                             const int* __restrict__ route_of, const int* __restrict__ order, const int* __restrict__ run0,
+                                             const int* __restrict__ run1, int ng, int A, int T, int* __restrict__ lost, int* pm, int* col_of,
+                                             RvTile* __restrict__ tiles, int* __restrict__ cnt, int* ws) {
     const int tid = (int)threadIdx.x;
     int base = 0;
     for (int m0 = 0; m0 < ng; m0 += 256) {
@@ -54,7 +56,7 @@ k_rvreloc_plan(const double* __restrict__ fam, const int* __restrict__ err, cons
             double mx = -__builtin_inf();
             int off = 0;
             for (int a = 0; a < A; ++a) {
-                const double v = fam[(long long)i * A + a];
+                const double v = NEG ? -fam[(long long)i * A + a] : fam[(long long)i * A + a];
                 if (v > mx) mx = v;
                 if (err && err[(long long)i * A + a]) off = 1;
             }
@@ -90,6 +92,14 @@ k_rvreloc_plan(const double* __restrict__ fam, const int* __restrict__ err, cons
         tbase += total;
     }
     if (tid == 0) { cnt[0] = tbase; cnt[1] = base * A; }
+}
+
+__global__ void __launch_bounds__(256)
+k_rvreloc_plan(const double* __restrict__ fam, const int* __restrict__ err, const double* __restrict__ tau, const int* __restrict__ route_of,
+               const int* __restrict__ order, const int* __restrict__ run0, const int* __restrict__ run1, int ng, int A, int T,
+               int* __restrict__ lost, int* pm, int* col_of, RvTile* __restrict__ tiles, int* __restrict__ cnt) {
+    __shared__ int ws[4];
+    rvreloc_plan<0>(fam, err, tau, route_of, order, run0, run1, ng, A, T, lost, pm, col_of, tiles, cnt, ws);
 }
 
 __global__ void __launch_bounds__(256)
@@ -143,14 +153,10 @@ static int rvreloc_check(dv_ctx* c, const char* who, int N, int A, const double*
     return DV_OK;
 }
 
-// The groups, each group's route-sorted order and runs, behind what `tab` holds already (the windowed call's weights and windows).
-static void rvreloc_tables(const dv_ctx* c, RvReloc& r, int N, int A, const int32_t* route_of_member, const double* reloc_below,
-                           std::vector<unsigned char>& tab) {
-    const int P = c->rv_h * c->rv_w, Pw = (P + 3) / 4;
-    r.N = N; r.A = A;
-    r.T = std::min(kRvTileMax, kRvLdsBytes / (3 * Pw * 4) / kRvBlock * kRvBlock);          // rviews_plan's rule
-    r.lstride = ((long long)c->rv_lmax + 63) / 64 * 64;
-    r.gm = std::min(N, std::max(1, rviews_slab_columns(c, r.lstride) / A));
+// The route-sorted order and the runs of r.N members of r.A headings, in groups of r.gm consecutive members and tiles of r.T columns
+// (set by the caller), behind what `tab` holds already; the thresholds and the routes beside them.
+static void rvreloc_order_tables(RvReloc& r, const int32_t* route_of_member, const double* reloc_below, std::vector<unsigned char>& tab) {
+    const int N = r.N, A = r.A;
     r.max_tiles = 0;
     r.group_tiles.clear();
     std::vector<int> order((size_t)N), run0((size_t)N), run1((size_t)N);
@@ -182,26 +188,40 @@ static void rvreloc_tables(const dv_ctx* c, RvReloc& r, int N, int A, const int3
     std::memcpy(tab.data() + r.off_run1, run1.data(), (size_t)N * sizeof(int));
 }
 
+// The SADS call's groups (what the score buffer holds) and tile width, and their tables behind the windowed call's weights and windows.
+static void rvreloc_tables(const dv_ctx* c, RvReloc& r, int N, int A, const int32_t* route_of_member, const double* reloc_below,
+                           std::vector<unsigned char>& tab) {
+    const int P = c->rv_h * c->rv_w, Pw = (P + 3) / 4;
+    r.N = N; r.A = A;
+    r.T = std::min(kRvTileMax, kRvLdsBytes / (3 * Pw * 4) / kRvBlock * kRvBlock);          // rviews_plan's rule
+    r.lstride = ((long long)c->rv_lmax + 63) / 64 * 64;
+    r.gm = std::min(N, std::max(1, rviews_slab_columns(c, r.lstride) / A));
+    rvreloc_order_tables(r, route_of_member, reloc_below, tab);
+}
+
 // What the device writes of a plan (rvw_plan): lost[N], pm[gm + 1], cnt[2], col_of[gm A], tiles[max_tiles].
 struct RvRelocDev { int* lost; int* pm; int* cnt; int* col_of; RvTile* tiles; };
 
-static RvRelocDev rvreloc_dev(const dv_ctx* c, const RvReloc& r) {
+static RvRelocDev rvreloc_dev(unsigned char* plan, const RvReloc& r) {
     RvRelocDev d;
-    d.lost = reinterpret_cast<int*>(c->rvw_plan);
+    d.lost = reinterpret_cast<int*>(plan);
     d.pm = d.lost + r.N;
     d.cnt = d.pm + r.gm + 1;
     d.col_of = d.cnt + 2;
     size_t tiles_at = ((size_t)r.N + r.gm + 3 + (size_t)r.gm * r.A) * sizeof(int);
     tiles_at = (tiles_at + 15) / 16 * 16;
-    d.tiles = reinterpret_cast<RvTile*>(c->rvw_plan + tiles_at);
+    d.tiles = reinterpret_cast<RvTile*>(plan + tiles_at);
     return d;
+}
+
+static size_t rvreloc_plan_bytes(const RvReloc& r) {
+    const size_t plan = ((size_t)r.N + r.gm + 3 + (size_t)r.gm * r.A) * sizeof(int);
+    return (plan + 15) / 16 * 16 + (size_t)r.max_tiles * sizeof(RvTile);
 }
 
 static int rvreloc_buffers(dv_ctx* c, const RvReloc& r) {
     const size_t gcols = (size_t)r.gm * r.A;
-    size_t plan = ((size_t)r.N + r.gm + 3 + gcols) * sizeof(int);
-    plan = (plan + 15) / 16 * 16 + (size_t)r.max_tiles * sizeof(RvTile);
-    int rc = grow_buffer(c, c->rvw_plan, c->rvw_plan_cap, plan);
+    int rc = grow_buffer(c, c->rvw_plan, c->rvw_plan_cap, rvreloc_plan_bytes(r));
     if (!rc) rc = grow_buffer(c, c->rv_fast, c->rv_fast_cap, gcols * (size_t)r.lstride * sizeof(double));
     if (!rc) rc = grow_buffer(c, c->rv_marked, c->rv_marked_cap, gcols * sizeof(int));
     return rc;
@@ -210,7 +230,7 @@ static int rvreloc_buffers(dv_ctx* c, const RvReloc& r) {
 // Behind the windowed scoring launches of the call: per group the plan and the whole-route scoring of its lost columns.
 static int rvreloc_enqueue(dv_ctx* c, const RvReloc& r, bool exact, const int* err, const AgentW* wts, double* d_fam, long long* d_view) {
     const int P = c->rv_h * c->rv_w, Pw = (P + 3) / 4, A = r.A;
-    const RvRelocDev d = rvreloc_dev(c, r);
+    const RvRelocDev d = rvreloc_dev(c->rvw_plan, r);
     const double* tau = reinterpret_cast<const double*>(c->rvw_tab.dev + r.off_tau);
     const int* route_of = reinterpret_cast<const int*>(c->rvw_tab.dev + r.off_route);
     const int* order = reinterpret_cast<const int*>(c->rvw_tab.dev + r.off_order);

@@ -23,6 +23,8 @@
 //                   32-bit integer atomicMax on a zeroed word.  A minimum (maximum) of integers does not depend on the order.
 //   k_rvssd_best    a member's first least column (np.argmax(-angle_ssd)), its off-landscape flag, and the results as doubles.
 //   k_rvssd_rows    a scene call's integer rows as doubles.
+// The scoring kernel's body lies in device functions (rvssd_load_step, rvssd_group_acc, rvssd_value, rvssd_key_min, rvssd_score_tile)
+// that the windowed calls' kernels (dejavu_rvssdw.inl) are made of as well: one statement of the arithmetic.
 namespace dv {
 
 constexpr int kRvssdTile = 32;               // columns of a tile at most: the MFMA's M
@@ -49,13 +51,13 @@ k_rvssd_norms(const unsigned* __restrict__ planes, long long n_groups, int chann
 }
 
 // grid = columns, workgroup = sorted column s: op[s][Kp * 8] dwords (dword d = pixels 4d .. 4d+3 of the channel, x ^ 0x80, 0 past P)
-// and pnorm[s].
+// and pnorm[s].  col_of nullptr: the caller's own order (s is the caller's column).
 __global__ void __launch_bounds__(256)
 k_rvssd_prep(const unsigned char* __restrict__ patches, const int* __restrict__ col_of, int channel, int P, int Kp, unsigned* __restrict__ op,
              unsigned* __restrict__ pnorm) {
     __shared__ unsigned red[4];
     const long long s = blockIdx.x;
-    const unsigned char* __restrict__ p = patches + (long long)col_of[s] * P * 3 + channel;
+    const unsigned char* __restrict__ p = patches + (col_of ? (long long)col_of[s] : s) * P * 3 + channel;
     unsigned nrm = 0;
     for (int d = threadIdx.x; d < Kp * 8; d += 256) {
         unsigned w = 0;
@@ -76,41 +78,50 @@ k_rvssd_prep(const unsigned char* __restrict__ patches, const int* __restrict__ 
     if (threadIdx.x == 0) pnorm[s] = red[0] + red[1] + red[2] + red[3];
 }
 
-// SCENE = 0: keys[s] takes the least ssd << 32 | view of sorted column s.  SCENE = 1: rows[row0[member] + view] takes the largest ssd
-// over the member's columns.  grid = (ceil(groups of the longest route / 4), tiles).
-template <int SCENE>
-__global__ void __launch_bounds__(256)
-k_rvssd_score(const unsigned* __restrict__ planes, const RvRoute* __restrict__ routes, const RvTile* __restrict__ tiles,
-              const int* __restrict__ col_of, const unsigned* __restrict__ op, const unsigned* __restrict__ pnorm,
-              const unsigned* __restrict__ vnorm, int channel, int A, int P, int Pw, int Kp, unsigned long long* __restrict__ keys,
-              const long long* __restrict__ row0, unsigned* __restrict__ rows) {
-    const RvTile tile = tiles[blockIdx.y];
-    const RvRoute rt = routes[tile.route];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long gl = (long long)blockIdx.x * kRvssdGroupsPerBlock + wave;       // the wave's view group within the route
-    if (gl * 64 >= rt.len) return;
-    const int col = lane & 31, hi = lane >> 5;
-    const bool has_col = col < tile.n;
-    // A: column `col` of the tile, 16 bytes at pixel 32 k + 16 hi (a column past the tile's: zeros, never read back)
-    const uint4* __restrict__ arow = reinterpret_cast<const uint4*>(op + (long long)(tile.s0 + (has_col ? col : 0)) * Kp * 8) + hi;
-    // B: views col and 32 + col of the group, dwords 8 k + 4 hi .. + 3 of the channel's plane
-    const unsigned* __restrict__ vb = planes + ((rt.g0 + gl) * 3 + channel) * Pw * 64 + col;
-    v16i_t acc0, acc1;
+// The operands of K-step k of one view group whose 8 dwords all lie in the plane: a, the lane's 16 bytes of its column's operand row
+// (zeros where the column does not exist); b0 / b1, dwords 8 k + 4 hi .. + 3 of views lane & 31 and 32 + (lane & 31), XORed.
+__device__ __forceinline__ void rvssd_load_step(const uint4* __restrict__ arow, bool has_col, const unsigned* __restrict__ vb, int hi, int k,
+                                                v4i_t& a, v4i_t& b0, v4i_t& b1) {
+    const uint4 a4 = arow[2 * k];
+    a = has_col ? v4i_t{(int)a4.x, (int)a4.y, (int)a4.z, (int)a4.w} : v4i_t{0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const unsigned* __restrict__ src = vb + (long long)(8 * k + 4 * hi + j) * 64;
+        b0[j] = (int)(src[0] ^ 0x80808080u);
+        b1[j] = (int)(src[32] ^ 0x80808080u);
+    }
+}
+
+// The cross terms of one view group: acc0 / acc1 = (the 32 columns of the operand rows) x (views 0 .. 31 / 32 .. 63 of the group), over
+// all Kp K-steps.  arow: the lane's column's operand row at its 16 bytes of a K-step (column lane & 31, bytes 16 hi ..; has_col: the
+// column exists, else zeros); vb: the group's plane of the channel at view lane & 31.  What k_rvssd_score and k_rvssdw_score
+// (dejavu_rvssdw.inl) share: the K loop, the B operand's lane map, the XOR and the last partial K-step.  AHEAD: K-steps whose loads
+// are issued together before their MFMAs (1: a step at a time; a workgroup that walks its view groups one after the other, with little
+// else on its CU to hide a load behind, takes more).  Integer sums: the order of the K-steps does not show.
+template <int AHEAD>
+__device__ __forceinline__ void rvssd_group_acc(const uint4* __restrict__ arow, bool has_col, const unsigned* __restrict__ vb, int hi, int Pw, int Kp,
+                                                v16i_t& acc0, v16i_t& acc1) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0;
     const int kfull = Pw / 8;                                                        // K-steps whose 8 dwords all lie in the plane
-    for (int k = 0; k < kfull; ++k) {
-        const uint4 a4 = arow[2 * k];
-        const v4i_t a = has_col ? v4i_t{(int)a4.x, (int)a4.y, (int)a4.z, (int)a4.w} : v4i_t{0, 0, 0, 0};
-        v4i_t b0, b1;
+    int k = 0;
+    for (; k + AHEAD <= kfull; k += AHEAD) {
+        v4i_t a[AHEAD], b0[AHEAD], b1[AHEAD];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const unsigned* __restrict__ src = vb + (long long)(8 * k + 4 * hi + j) * 64;
-            b0[j] = (int)(src[0] ^ 0x80808080u);
-            b1[j] = (int)(src[32] ^ 0x80808080u);
+        for (int u = 0; u < AHEAD; ++u) rvssd_load_step(arow, has_col, vb, hi, k + u, a[u], b0[u], b1[u]);
+#pragma unroll
+        for (int u = 0; u < AHEAD; ++u) {
+            acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[u], b0[u], acc0, 0, 0, 0);  // columns x views
+            acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a[u], b1[u], acc1, 0, 0, 0);
         }
-        acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b0, acc0, 0, 0, 0);          // columns x views
-        acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b1, acc1, 0, 0, 0);
+    }
+    if constexpr (AHEAD > 1) {
+        for (; k < kfull; ++k) {                                                     // the full K-steps that are left
+            v4i_t a, b0, b1;
+            rvssd_load_step(arow, has_col, vb, hi, k, a, b0, b1);
+            acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b0, acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b1, acc1, 0, 0, 0);
+        }
     }
     if (kfull < Kp) {                                                                // the last K-step: dwords q >= Pw are not the plane's
         const uint4 a4 = arow[2 * kfull];
@@ -126,6 +137,48 @@ k_rvssd_score(const unsigned* __restrict__ planes, const RvRoute* __restrict__ r
         acc0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b0, acc0, 0, 0, 0);
         acc1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b1, acc1, 0, 0, 0);
     }
+}
+
+// The epilogue: the exact SSD from the two norms and the cross term.
+__device__ __forceinline__ int rvssd_value(int vnorm, int pnorm, int acc) { return vnorm + pnorm - 2 * acc; }
+
+// The least ssd << 32 | view over the 32 lanes of a half-wave, each with its two views f0 and f1 (live: the view counts, else all ones);
+// every lane of the half-wave gets it.
+__device__ __forceinline__ unsigned long long rvssd_key_min(int ssd0, int ssd1, long long f0, long long f1, bool live0, bool live1) {
+    const unsigned long long none = ~0ull;
+    const unsigned long long k0 = live0 ? ((unsigned long long)(unsigned)ssd0 << 32) | (unsigned long long)f0 : none;
+    const unsigned long long k1 = live1 ? ((unsigned long long)(unsigned)ssd1 << 32) | (unsigned long long)f1 : none;
+    unsigned long long key = k0 < k1 ? k0 : k1;
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) {                                               // over the 32 views of the half-wave
+        const unsigned long long other = __shfl_xor(key, o);
+        key = other < key ? other : key;
+    }
+    return key;
+}
+
+// One workgroup of k_rvssd_score: 4 view groups (chunk `gchunk` of the tile's route) against one tile.  BYCOL = 0: the operand rows
+// and norms lie in the tiles' column order (op[s], pnorm[s]); BYCOL = 1: in the caller's (op[col_of[s]], pnorm[col_of[s]]: the rows
+// of a windowed call, dejavu_rvssdw.inl, whose plan the device wrote).
+template <int SCENE, int BYCOL>
+__device__ __forceinline__ void rvssd_score_tile(const unsigned* __restrict__ planes, const RvRoute* __restrict__ routes, const RvTile tile, int gchunk,
+                                                 const int* __restrict__ col_of, const unsigned* __restrict__ op,
+                                                 const unsigned* __restrict__ pnorm, const unsigned* __restrict__ vnorm, int channel, int A, int P,
+                                                 int Pw, int Kp, unsigned long long* __restrict__ keys, const long long* __restrict__ row0,
+                                                 unsigned* __restrict__ rows) {
+    const RvRoute rt = routes[tile.route];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long gl = (long long)gchunk * kRvssdGroupsPerBlock + wave;            // the wave's view group within the route
+    if (gl * 64 >= rt.len) return;
+    const int col = lane & 31, hi = lane >> 5;
+    const bool has_col = col < tile.n;
+    // A: column `col` of the tile, 16 bytes at pixel 32 k + 16 hi (a column past the tile's: zeros, never read back)
+    const int srow = tile.s0 + (has_col ? col : 0);
+    const uint4* __restrict__ arow = reinterpret_cast<const uint4*>(op + (long long)(BYCOL ? col_of[srow] : srow) * Kp * 8) + hi;
+    // B: views col and 32 + col of the group, dwords 8 k + 4 hi .. + 3 of the channel's plane
+    const unsigned* __restrict__ vb = planes + ((rt.g0 + gl) * 3 + channel) * Pw * 64 + col;
+    v16i_t acc0, acc1;
+    rvssd_group_acc<1>(arow, has_col, vb, hi, Pw, Kp, acc0, acc1);
     // register r of a lane is (column m = (r & 3) + 8 (r >> 2) + 4 hi, view = lane & 31) of its half
     const long long f0 = gl * 64 + col, f1 = f0 + 32;                               // the lane's two views within the route
     const bool live0 = f0 < rt.len, live1 = f1 < rt.len;
@@ -136,8 +189,8 @@ k_rvssd_score(const unsigned* __restrict__ planes, const RvRoute* __restrict__ r
         const int m = (r & 3) + 8 * (r >> 2) + 4 * hi;
         const bool mine = m < tile.n;                                                // (the same in the 32 lanes of a half-wave)
         const int s = tile.s0 + (mine ? m : 0);
-        const int pn = (int)pnorm[s];
-        const int ssd0 = vn0 + pn - 2 * acc0[r], ssd1 = vn1 + pn - 2 * acc1[r];
+        const int pn = (int)pnorm[BYCOL ? col_of[s] : s];
+        const int ssd0 = rvssd_value(vn0, pn, acc0[r]), ssd1 = rvssd_value(vn1, pn, acc1[r]);
         if (SCENE) {
             if (mine) {
                 unsigned* __restrict__ row = rows + row0[col_of[s] / A];
@@ -145,18 +198,21 @@ k_rvssd_score(const unsigned* __restrict__ planes, const RvRoute* __restrict__ r
                 if (live1) atomicMax(&row[f1], (unsigned)ssd1);
             }
         } else {
-            const unsigned long long none = ~0ull;
-            const unsigned long long k0 = live0 ? ((unsigned long long)(unsigned)ssd0 << 32) | (unsigned long long)f0 : none;
-            const unsigned long long k1 = live1 ? ((unsigned long long)(unsigned)ssd1 << 32) | (unsigned long long)f1 : none;
-            unsigned long long key = k0 < k1 ? k0 : k1;
-#pragma unroll
-            for (int o = 16; o > 0; o >>= 1) {                                       // over the 32 views of the half-wave
-                const unsigned long long other = __shfl_xor(key, o);
-                key = other < key ? other : key;
-            }
-            if (mine && col == 0 && key != none) atomicMin(&keys[s], key);
+            const unsigned long long key = rvssd_key_min(ssd0, ssd1, f0, f1, live0, live1);
+            if (mine && col == 0 && key != ~0ull) atomicMin(&keys[s], key);
         }
     }
+}
+
+// SCENE = 0: keys[s] takes the least ssd << 32 | view of sorted column s.  SCENE = 1: rows[row0[member] + view] takes the largest ssd
+// over the member's columns.  grid = (ceil(groups of the longest route / 4), tiles).
+template <int SCENE>
+__global__ void __launch_bounds__(256)
+k_rvssd_score(const unsigned* __restrict__ planes, const RvRoute* __restrict__ routes, const RvTile* __restrict__ tiles,
+              const int* __restrict__ col_of, const unsigned* __restrict__ op, const unsigned* __restrict__ pnorm,
+              const unsigned* __restrict__ vnorm, int channel, int A, int P, int Pw, int Kp, unsigned long long* __restrict__ keys,
+              const long long* __restrict__ row0, unsigned* __restrict__ rows) {
+    rvssd_score_tile<SCENE, 0>(planes, routes, tiles[blockIdx.y], (int)blockIdx.x, col_of, op, pnorm, vnorm, channel, A, P, Pw, Kp, keys, row0, rows);
 }
 
 // keys[s] of the sorted columns -> ssd[oc], view[oc] of the caller's columns; grid = ceil(C / 256).
@@ -170,9 +226,11 @@ k_rvssd_unsort(const unsigned long long* __restrict__ keys, const int* __restric
     view[col_of[s]] = (long long)(key & 0xffffffffull);
 }
 
-// A member's first least column (np.argmax of the negated row) and its flags: err is a word per column (nullptr: patches were uploaded).
+// A member's first least column (np.argmax of the negated row) and its flags: err is a word per column (nullptr: patches were uploaded),
+// lost a word per member (nullptr but in a relocalising call: dejavu_rvssdw.inl).
 __global__ void __launch_bounds__(256)
-k_rvssd_best(const double* __restrict__ ssd, const int* __restrict__ err, int n, int A, int* __restrict__ best, unsigned* __restrict__ flags) {
+k_rvssd_best(const double* __restrict__ ssd, const int* __restrict__ err, const int* __restrict__ lost, int n, int A, int* __restrict__ best,
+             unsigned* __restrict__ flags) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     int b = 0, off = 0;
@@ -181,7 +239,7 @@ k_rvssd_best(const double* __restrict__ ssd, const int* __restrict__ err, int n,
         if (err && err[(long long)i * A + a]) off = 1;
     }
     best[i] = off ? -1 : b;
-    flags[i] = off ? 16u : 0u;                                                       // DV_RES_SENSE_ERROR
+    flags[i] = off ? 16u : lost && lost[i] ? 32u : 0u;                               // DV_RES_SENSE_ERROR, DV_RES_RELOCALISED
 }
 
 // A scene call's integer rows as doubles, in place behind them; grid = ceil(total / 256).
@@ -195,10 +253,11 @@ k_rvssd_rows(const unsigned* __restrict__ rows, long long total, double* __restr
 
 static void rvssd_free(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-    F(c->rvs_vnorm); F(c->rvs_op); F(c->rvs_keys); F(c->rvs_out); F(c->rvs_rows);
-    c->rvs_vnorm_cap = c->rvs_op_cap = c->rvs_keys_cap = c->rvs_out_cap = c->rvs_rows_cap = 0;
+    F(c->rvs_vnorm); F(c->rvs_op); F(c->rvs_keys); F(c->rvs_out); F(c->rvs_rows); F(c->rvs_plan);
+    c->rvs_vnorm_cap = c->rvs_op_cap = c->rvs_keys_cap = c->rvs_out_cap = c->rvs_rows_cap = c->rvs_plan_cap = 0;
     c->rvs_norm_gen[0] = c->rvs_norm_gen[1] = c->rvs_norm_gen[2] = 0;
     table_free(c->rvs_tab);
+    table_free(c->rvsw_tab);
 }
 
 // The checks of dv_rviews_* and the channel's, before anything of the call reaches the device.
@@ -242,22 +301,32 @@ static int rvssd_plan(dv_ctx* c, RvssdPlan& p, int N, int A, const int32_t* rout
     return table_upload(c, c->rvs_tab, tab.data(), tab.size());
 }
 
-// Enqueue what the step and scene calls share: the channel's view norms (if this store's are not there yet), the operand rows and
-// norms of the columns whose patches lie in d_sense, and the scoring launches.
-template <int SCENE>
-static int rvssd_enqueue_score(dv_ctx* c, const RvssdPlan& p, int channel) {
+// The channel's view norms of the live store, worked out (enqueued) if this store's are not there yet, and room for C operand rows
+// and their norms in rvs_op.
+static int rvssd_norms_and_rows(dv_ctx* c, int channel, int C, unsigned*& vnorm) {
     const int P = c->rv_h * c->rv_w, Pw = (P + 3) / 4, Kp = (P + 31) / 32;
     const long long n_groups = c->rv_bytes / ((long long)3 * Pw * 64 * 4);
     int rc = grow_buffer(c, c->rvs_vnorm, c->rvs_vnorm_cap, (size_t)3 * n_groups * 64 * sizeof(unsigned));
-    if (!rc) rc = grow_buffer(c, c->rvs_op, c->rvs_op_cap, (size_t)p.C * ((size_t)Kp * 32 + sizeof(unsigned)));
+    if (!rc) rc = grow_buffer(c, c->rvs_op, c->rvs_op_cap, (size_t)C * ((size_t)Kp * 32 + sizeof(unsigned)));
     if (rc) return rc;
-    unsigned* vnorm = c->rvs_vnorm + (size_t)channel * n_groups * 64;
+    vnorm = c->rvs_vnorm + (size_t)channel * n_groups * 64;
     if (c->rvs_norm_gen[channel] != c->rv_gen) {
         hipLaunchKernelGGL(k_rvssd_norms, dim3((unsigned)((n_groups * 64 + 255) / 256)), dim3(256), 0, c->stream, c->rv_planes, n_groups, channel, P, Pw,
                            vnorm);
         HIP_TRY(c, hipGetLastError());
         c->rvs_norm_gen[channel] = c->rv_gen;
     }
+    return DV_OK;
+}
+
+// Enqueue what the step and scene calls share: the channel's view norms (if this store's are not there yet), the operand rows and
+// norms of the columns whose patches lie in d_sense, and the scoring launches.
+template <int SCENE>
+static int rvssd_enqueue_score(dv_ctx* c, const RvssdPlan& p, int channel) {
+    const int P = c->rv_h * c->rv_w, Pw = (P + 3) / 4, Kp = (P + 31) / 32;
+    unsigned* vnorm = nullptr;
+    const int rc = rvssd_norms_and_rows(c, channel, p.C, vnorm);
+    if (rc) return rc;
     unsigned* pnorm = c->rvs_op + (size_t)p.C * Kp * 8;
     const RvTile* tiles = reinterpret_cast<const RvTile*>(c->rvs_tab.dev + p.off_tiles);
     const int* col_of = reinterpret_cast<const int*>(c->rvs_tab.dev + p.off_col);
@@ -291,7 +360,7 @@ static int rvssd_run(dv_ctx* c, int N, int A, const int32_t* route_of_member, in
     unsigned* d_flags = reinterpret_cast<unsigned*>(c->rvs_out + (size_t)p.C * 16 + (size_t)p.N * 4);
     hipLaunchKernelGGL(k_rvssd_unsort, dim3((unsigned)((p.C + 255) / 256)), dim3(256), 0, c->stream, c->rvs_keys,
                        reinterpret_cast<const int*>(c->rvs_tab.dev + p.off_col), p.C, d_ssd, d_view);
-    hipLaunchKernelGGL(k_rvssd_best, dim3((unsigned)((p.N + 255) / 256)), dim3(256), 0, c->stream, d_ssd, err, p.N, A, d_best, d_flags);
+    hipLaunchKernelGGL(k_rvssd_best, dim3((unsigned)((p.N + 255) / 256)), dim3(256), 0, c->stream, d_ssd, err, nullptr, p.N, A, d_best, d_flags);
     HIP_TRY(c, hipGetLastError());
     c->rv_out_host.resize(out_bytes);
     HIP_TRY(c, hipMemcpyAsync(c->rv_out_host.data(), c->rvs_out, out_bytes, hipMemcpyDeviceToHost, c->stream));

@@ -284,7 +284,7 @@ static int rvwin_run(dv_ctx* c, int N, int A, const int32_t* route_of_member, co
         if (rc) return rc;
     }
     hipLaunchKernelGGL(k_rv_best, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, d_fam, err,
-                       reloc_below ? rvreloc_dev(c, reloc).lost : nullptr, N, A, d_best, d_flags);
+                       reloc_below ? rvreloc_dev(c->rvw_plan, reloc).lost : nullptr, N, A, d_best, d_flags);
     HIP_TRY(c, hipGetLastError());
     c->rv_out_host.resize(out_bytes);
     HIP_TRY(c, hipMemcpyAsync(c->rv_out_host.data(), c->rv_out, out_bytes, hipMemcpyDeviceToHost, c->stream));

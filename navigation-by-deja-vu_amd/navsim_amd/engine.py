@@ -1973,6 +1973,42 @@ class FamiliarityEngine(object):
                     "dv_rvssd_sense_step")
         return RouteSsdResults(ssd, view, best, flags)
 
+    def rvssdw_step_u8(self, patches, route_of_member, win_lo, win_hi, channel=2, reloc_below=None):
+        """rvssd_step_u8 with member i scored against views [win_lo[i], win_hi[i]) of its route only (at most RVWIN_MAX_VIEWS), in one
+        scoring launch -> RouteSsdResults: what the unwindowed step gives on that slice of the route, angle_view counted from the
+        route's first view.  reloc_below (float64[n], in the unit of angle_familiarity = -SSD; None: no loss test): member i whose
+        largest windowed angle_familiarity is < reloc_below[i] is lost, and its row is rvssd_step_u8's on its whole route, in the same
+        enqueue; results.relocalised says which."""
+        patches = self._rviews_patches(patches)
+        n, A = patches.shape[:2]
+        routes, channel, _ = self._rvssd_tables(n, route_of_member, channel)
+        lo, hi = self._rvwin_windows(routes, win_lo, win_hi)
+        tau = self._rvwin_thresholds(reloc_below, n)
+        ssd, best, flags = self._member_results(n, A)
+        view = np.empty((n, A), dtype=np.int64)
+        self._check(self._lib.dv_rvssdw_step_u8(self._ctx, N.u8ptr(patches), n, A, routes.ctypes.data_as(N._i32p), lo.ctypes.data_as(N._i32p),
+                                                hi.ctypes.data_as(N._i32p), None if tau is None else N.f64ptr(tau), channel, N.f64ptr(ssd),
+                                                N.i64ptr(view), best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)),
+                    "dv_rvssdw_step_u8")
+        return RouteSsdResults(ssd, view, best, flags)
+
+    def rvssdw_sense_step(self, x, y, angles, route_of_member, win_lo, win_hi, channel=2, land_of_member=None, reloc_below=None):
+        """rvssdw_step_u8 with the patches sensed as rvssd_sense_step senses them: one enqueue and one wait, with reloc_below too (a
+        member flagged DV_RES_SENSE_ERROR is never lost)."""
+        x, y, angles = self._member_poses(x, y, angles)
+        n, A = angles.shape
+        routes, channel, lands = self._rvssd_tables(n, route_of_member, channel, land_of_member)
+        lo, hi = self._rvwin_windows(routes, win_lo, win_hi)
+        tau = self._rvwin_thresholds(reloc_below, n)
+        ssd, best, flags = self._member_results(n, A)
+        view = np.empty((n, A), dtype=np.int64)
+        self._check(self._lib.dv_rvssdw_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, routes.ctypes.data_as(N._i32p),
+                                                   None if lands is None else lands.ctypes.data_as(N._i32p), lo.ctypes.data_as(N._i32p),
+                                                   hi.ctypes.data_as(N._i32p), None if tau is None else N.f64ptr(tau), channel, N.f64ptr(ssd),
+                                                   N.i64ptr(view), best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)),
+                    "dv_rvssdw_sense_step")
+        return RouteSsdResults(ssd, view, best, flags)
+
     def rvssd_scene_u8(self, patches, route_of_member, channel=2):
         """Per member a float64[len(its route)]: per view the largest ssds over the headings (its negative is scene_familiarity)."""
         patches = self._rviews_patches(patches)

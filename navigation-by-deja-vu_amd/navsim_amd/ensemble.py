@@ -911,7 +911,127 @@ class InfomaxRouteEnsemble(_RouteEnsemble):
         return info
 
 
-class SadsRouteEnsemble(_RouteEnsemble):
+class _WindowedMembers(object):
+    """What SadsRouteEnsemble and SsdRouteEnsemble share of perfect memory WITH A TEMPORAL WINDOW: the arguments window,
+    window_centres and relocalise_below of from_routes_with / from_landscapes, the members' attributes (window, memory_index,
+    relocalise_below, relocalised, n_relocalisations), relocalise() and the window of a member's coming step."""
+    WINDOW_MAX_VIEWS = 512                       # views of a member's window at most (FamiliarityEngine.RVWIN_MAX_VIEWS)
+
+    @classmethod
+    def _windows_arg(cls, window, window_centres, starts, route_lengths):
+        """`window` and `window_centres` of from_routes_with / from_landscapes as two lists with an entry per start: (behind, ahead) or
+        None (the member keeps its whole route), and the initial memory_index or None.  ValueError names the entry."""
+        n = len(starts)
+        if window is None:
+            if window_centres is not None:
+                raise ValueError("window_centres without window: a centre is the middle of a member's window")
+            return [None] * n, [None] * n
+
+        def pair(w, what):
+            if isinstance(w, (int, np.integer)) and not isinstance(w, bool):
+                w = (w, w)
+            ok = isinstance(w, (tuple, list)) and len(w) == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and v >= 0
+                                                                      for v in w)
+            if not ok:
+                raise ValueError("%s must be an int W >= 0 (W views behind and ahead) or a pair (behind, ahead) of such, got %r" % (what, w))
+            if w[0] + w[1] + 1 > cls.WINDOW_MAX_VIEWS:
+                raise ValueError("%s = %r: a window holds behind + ahead + 1 <= %d views" % (what, tuple(w), cls.WINDOW_MAX_VIEWS))
+            return (int(w[0]), int(w[1]))
+        if isinstance(window, list):                                # (a list: an entry per start; a pair is a tuple)
+            if len(window) != n:
+                raise ValueError("window holds %d entries for %d starts" % (len(window), n))
+            wins = [None if w is None else pair(w, "window[%d]" % i) for i, w in enumerate(window)]
+        else:
+            wins = [pair(window, "window")] * n
+        centres = [None] * n
+        if window_centres is not None:
+            centres = list(window_centres)
+            if len(centres) != n:
+                raise ValueError("window_centres holds %d entries for %d starts" % (len(centres), n))
+            for i, m in enumerate(centres):
+                if m is None:
+                    continue
+                if isinstance(m, bool) or not isinstance(m, (int, np.integer)):
+                    raise ValueError("window_centres[%d] must be None or a view index within the member's route, got %r" % (i, m))
+                if wins[i] is None:
+                    raise ValueError("window_centres[%d] = %d, but member %d has no window" % (i, m, i))
+                r = starts[i][0]
+                if isinstance(r, (int, np.integer)) and 0 <= r < len(route_lengths) and not 0 <= m < route_lengths[r]:
+                    raise ValueError("window_centres[%d] = %d outside [0, %d), the views of route %d" % (i, m, route_lengths[r], r))
+                centres[i] = int(m)
+        return wins, centres
+
+    def _set_windows(self, wins, centres, thresholds=None):
+        for i, (a, w, m) in enumerate(zip(self.agents, wins, centres)):
+            a.window, a.memory_index = w, m
+            a.relocalise_below = None if thresholds is None else thresholds[i]
+            a.relocalised, a.n_relocalisations = False, 0
+
+    @staticmethod
+    def _thresholds_arg(relocalise_below, wins):
+        """`relocalise_below` of from_routes_with / from_landscapes as a list with a float or None per start (wins: _windows_arg's):
+        a threshold belongs to a member with a window.  ValueError names the entry."""
+        n = len(wins)
+        if relocalise_below is None:
+            return [None] * n
+
+        def one(t, what):
+            if isinstance(t, bool) or not isinstance(t, (int, float, np.integer, np.floating)):
+                raise ValueError("%s must be a familiarity (a float) or None, got %r" % (what, t))
+            if np.isnan(t):
+                raise ValueError("%s is NaN" % what)
+            return float(t)
+        if isinstance(relocalise_below, (list, tuple)):
+            if len(relocalise_below) != n:
+                raise ValueError("relocalise_below holds %d entries for %d starts" % (len(relocalise_below), n))
+            out = [None if t is None else one(t, "relocalise_below[%d]" % i) for i, t in enumerate(relocalise_below)]
+        else:
+            out = [one(relocalise_below, "relocalise_below")] * n
+        for i, (t, w) in enumerate(zip(out, wins)):
+            if t is not None and w is None:
+                raise ValueError("relocalise_below[%d] = %r, but member %d has no window: the threshold is a windowed member's loss test"
+                                 % (i, t, i))
+        return out
+
+    def relocalise(self, members=None):
+        """The members `members` (indices; None: all) forget which view they matched last: memory_index = None, so that their next step
+        scores the whole route (global localisation) and centres their window anew."""
+        for i in (range(len(self.agents)) if members is None else members):
+            self.agents[i].memory_index = None
+
+    def _window_of(self, agent):
+        """[lo, hi) of the coming step of a member with a window and a centre: clipped at both ends of its route; else None."""
+        w, m = getattr(agent, "window", None), getattr(agent, "memory_index", None)
+        if w is None or m is None:
+            return None
+        return max(0, m - w[0]), min(len(agent.training_path), m + w[1] + 1)
+
+    def _remember_views(self, idx, results):
+        """After a device step: a member that is about to apply it (every one with a window that is not flagged) remembers the view its
+        chosen heading matched, and whether the step re-localised it."""
+        for k, i in enumerate(idx):
+            a = self.agents[i]
+            if getattr(a, "window", None) is not None and not results.flags[k] & 16:
+                a.memory_index = int(results.angle_view[k, results.best_idex[k]])
+                a.relocalised = bool(results.flags[k] & 32)           # (DV_RES_RELOCALISED: the step was the global search, by the rule)
+                if a.relocalised:
+                    a.n_relocalisations = getattr(a, "n_relocalisations", 0) + 1
+                    self._step_windows[id(a)] = None                  # its scene_familiarity is the whole route's row: nothing is masked
+
+    def _note_scene(self, agent, x, y, headings, weight):
+        """NavEnsemble's note (a per-view extreme to work out when read, not the one-value models' fill), and the window of the step."""
+        NavEnsemble._note_scene(self, agent, x, y, headings, weight)
+        agent._scene_stale = (x, y, headings, weight, getattr(self, "_step_windows", {}).get(id(agent)))
+
+    @staticmethod
+    def _mask_scene(agent, stale):
+        """A windowed step scored views [lo, hi) only: the others keep the reference's value for views never scored (:287)."""
+        if len(stale) > 4 and stale[4] is not None:
+            agent._scene_fam[:stale[4][0]] = np.inf
+            agent._scene_fam[stale[4][1]:] = np.inf
+
+
+class SadsRouteEnsemble(_WindowedMembers, _RouteEnsemble):
     """The route ensemble of the reference's own model, perfect memory (util.sads_familiarity): trials that differ in their start, their
     chem_weight, their TRAINING ROUTE and their LANDSCAPE step as one ensemble.  The engine keeps the sensed views of all routes side by
     side (FamiliarityEngine.rviews_set_from_poses: one call senses them all), and a step scores every running member's headings against
@@ -992,84 +1112,6 @@ class SadsRouteEnsemble(_RouteEnsemble):
             raise ValueError("chem_weights must lie in [0, 1], got %r" % (w,))
         return w
 
-    WINDOW_MAX_VIEWS = 512                       # views of a member's window at most (FamiliarityEngine.RVWIN_MAX_VIEWS)
-
-    @classmethod
-    def _windows_arg(cls, window, window_centres, starts, route_lengths):
-        """`window` and `window_centres` of from_routes_with / from_landscapes as two lists with an entry per start: (behind, ahead) or
-        None (the member keeps its whole route), and the initial memory_index or None.  ValueError names the entry."""
-        n = len(starts)
-        if window is None:
-            if window_centres is not None:
-                raise ValueError("window_centres without window: a centre is the middle of a member's window")
-            return [None] * n, [None] * n
-
-        def pair(w, what):
-            if isinstance(w, (int, np.integer)) and not isinstance(w, bool):
-                w = (w, w)
-            ok = isinstance(w, (tuple, list)) and len(w) == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and v >= 0
-                                                                      for v in w)
-            if not ok:
-                raise ValueError("%s must be an int W >= 0 (W views behind and ahead) or a pair (behind, ahead) of such, got %r" % (what, w))
-            if w[0] + w[1] + 1 > cls.WINDOW_MAX_VIEWS:
-                raise ValueError("%s = %r: a window holds behind + ahead + 1 <= %d views" % (what, tuple(w), cls.WINDOW_MAX_VIEWS))
-            return (int(w[0]), int(w[1]))
-        if isinstance(window, list):                                # (a list: an entry per start; a pair is a tuple)
-            if len(window) != n:
-                raise ValueError("window holds %d entries for %d starts" % (len(window), n))
-            wins = [None if w is None else pair(w, "window[%d]" % i) for i, w in enumerate(window)]
-        else:
-            wins = [pair(window, "window")] * n
-        centres = [None] * n
-        if window_centres is not None:
-            centres = list(window_centres)
-            if len(centres) != n:
-                raise ValueError("window_centres holds %d entries for %d starts" % (len(centres), n))
-            for i, m in enumerate(centres):
-                if m is None:
-                    continue
-                if isinstance(m, bool) or not isinstance(m, (int, np.integer)):
-                    raise ValueError("window_centres[%d] must be None or a view index within the member's route, got %r" % (i, m))
-                if wins[i] is None:
-                    raise ValueError("window_centres[%d] = %d, but member %d has no window" % (i, m, i))
-                r = starts[i][0]
-                if isinstance(r, (int, np.integer)) and 0 <= r < len(route_lengths) and not 0 <= m < route_lengths[r]:
-                    raise ValueError("window_centres[%d] = %d outside [0, %d), the views of route %d" % (i, m, route_lengths[r], r))
-                centres[i] = int(m)
-        return wins, centres
-
-    def _set_windows(self, wins, centres, thresholds=None):
-        for i, (a, w, m) in enumerate(zip(self.agents, wins, centres)):
-            a.window, a.memory_index = w, m
-            a.relocalise_below = None if thresholds is None else thresholds[i]
-            a.relocalised, a.n_relocalisations = False, 0
-
-    @staticmethod
-    def _thresholds_arg(relocalise_below, wins):
-        """`relocalise_below` of from_routes_with / from_landscapes as a list with a float or None per start (wins: _windows_arg's):
-        a threshold belongs to a member with a window.  ValueError names the entry."""
-        n = len(wins)
-        if relocalise_below is None:
-            return [None] * n
-
-        def one(t, what):
-            if isinstance(t, bool) or not isinstance(t, (int, float, np.integer, np.floating)):
-                raise ValueError("%s must be a familiarity (a float) or None, got %r" % (what, t))
-            if np.isnan(t):
-                raise ValueError("%s is NaN" % what)
-            return float(t)
-        if isinstance(relocalise_below, (list, tuple)):
-            if len(relocalise_below) != n:
-                raise ValueError("relocalise_below holds %d entries for %d starts" % (len(relocalise_below), n))
-            out = [None if t is None else one(t, "relocalise_below[%d]" % i) for i, t in enumerate(relocalise_below)]
-        else:
-            out = [one(relocalise_below, "relocalise_below")] * n
-        for i, (t, w) in enumerate(zip(out, wins)):
-            if t is not None and w is None:
-                raise ValueError("relocalise_below[%d] = %r, but member %d has no window: the threshold is a windowed member's loss test"
-                                 % (i, t, i))
-        return out
-
     @classmethod
     def from_routes_with(cls, agent, routes, starts, metrics="host", chem_weights=None, window=None, window_centres=None,
                          relocalise_below=None):
@@ -1106,19 +1148,6 @@ class SadsRouteEnsemble(_RouteEnsemble):
         ens._set_windows(wins, centres, thresholds)
         return ens
 
-    def relocalise(self, members=None):
-        """The members `members` (indices; None: all) forget which view they matched last: memory_index = None, so that their next step
-        scores the whole route (global localisation) and centres their window anew."""
-        for i in (range(len(self.agents)) if members is None else members):
-            self.agents[i].memory_index = None
-
-    def _window_of(self, agent):
-        """[lo, hi) of the coming step of a member with a window and a centre: clipped at both ends of its route; else None."""
-        w, m = getattr(agent, "window", None), getattr(agent, "memory_index", None)
-        if w is None or m is None:
-            return None
-        return max(0, m - w[0]), min(len(agent.training_path), m + w[1] + 1)
-
     def _device_step(self, idx, xs, ys, angs):
         """A member with a window and a centre goes to rvwin_sense_step, every other to rviews_sense_step: at most two device calls, and
         with no window anywhere the one call there was.  Where a member of the windowed call has a threshold (relocalise_below) the call
@@ -1148,21 +1177,8 @@ class SadsRouteEnsemble(_RouteEnsemble):
             for at, r in parts:
                 results.angle_familiarity[at], results.angle_view[at] = r.angle_familiarity, r.angle_view
                 results.best_idex[at], results.flags[at] = r.best_idex, r.flags
-        # a member that is about to apply this step (every one that is not flagged) remembers the view its chosen heading matched
-        for k, i in enumerate(idx):
-            a = self.agents[i]
-            if getattr(a, "window", None) is not None and not results.flags[k] & 16:
-                a.memory_index = int(results.angle_view[k, results.best_idex[k]])
-                a.relocalised = bool(results.flags[k] & 32)           # (DV_RES_RELOCALISED: the step was the global search, by the rule)
-                if a.relocalised:
-                    a.n_relocalisations = getattr(a, "n_relocalisations", 0) + 1
-                    self._step_windows[id(a)] = None                  # its scene_familiarity is the whole route's row: nothing is masked
+        self._remember_views(idx, results)
         return results
-
-    def _note_scene(self, agent, x, y, headings, weight):
-        """NavEnsemble's note (a per-view minimum to work out when read, not the one-value models' fill), and the window of the step."""
-        NavEnsemble._note_scene(self, agent, x, y, headings, weight)
-        agent._scene_stale = (x, y, headings, weight, getattr(self, "_step_windows", {}).get(id(agent)))
 
     def _read_scene(self):
         todo = [a for a in self.agents if a._scene_stale is not None and a._scene_owner is self]
@@ -1176,9 +1192,7 @@ class SadsRouteEnsemble(_RouteEnsemble):
             a._scene_stale = None
             a._scene_owner = None
             a._scene_fam[:] = row
-            if len(t) > 4 and t[4] is not None:                    # a windowed step scored views [lo, hi) only: the others keep the
-                a._scene_fam[:t[4][0]] = np.inf                   # reference's value for views never scored (:287)
-                a._scene_fam[t[4][1]:] = np.inf
+            self._mask_scene(a, t)
 
     def scene_familiarity(self):
         """A list of float64[len(route of member i)]: every member's scene_familiarity after its last step, as NavEnsemble gives it
@@ -1189,7 +1203,7 @@ class SadsRouteEnsemble(_RouteEnsemble):
         return [a.scene_familiarity.copy() for a in self.agents]
 
 
-class SsdRouteEnsemble(_RouteEnsemble):
+class SsdRouteEnsemble(_WindowedMembers, _RouteEnsemble):
     """The route ensemble of the north star's literal metric, the sum of squared differences (util.ssd_familiarity(channel)): trials
     that differ in their start, their TRAINING ROUTE and their LANDSCAPE step as one ensemble.  The views of all routes lie in the
     engine's route view store (FamiliarityEngine.rviews_set_from_poses: one call senses them all, the store SadsRouteEnsemble uses),
@@ -1197,7 +1211,14 @@ class SsdRouteEnsemble(_RouteEnsemble):
     in ONE device call (dv_rvssd_sense_step).  Every score is the exact integer of the reference's `ssds`, so a member's
     angle_familiarity (-SSD) is a lone agent's row bit for bit, and ties go to the first heading as np.argmax decides them.  A
     member's scene_familiarity is worked out when read (dv_rvssd_scene); its `memory_bank` is its route's place in the store.
-    All members share the model's one channel.  Made by from_routes / from_routes_with / from_landscapes (see _RouteEnsemble)."""
+    All members share the model's one channel.  Made by from_routes / from_routes_with / from_landscapes (see _RouteEnsemble).
+
+    window=..., window_centres=..., relocalise_below=... and relocalise() are SadsRouteEnsemble's, with its members' attributes
+    (window, memory_index, relocalise_below, relocalised, n_relocalisations): a member with a window and a memory_index m scores views
+    [max(0, m - behind), min(len, m + ahead + 1)) of its route only (dv_rvssdw_sense_step: exact SSD on that slice), a member without
+    either scores its whole route, at most two device calls a step.  relocalise_below is a familiarity, -SSD, so useful values are
+    <= 0: a step whose largest windowed angle_familiarity is < it is redone against the whole route inside the same device call.
+    scene_familiarity is +inf outside the window of a member's last step, and unmasked after a re-localised one."""
     _metric = "ssd"
     _takes = "agents of the SSD model (familiarity_model=ssd_familiarity(channel))"
     _info_call = "rviews_info"               # dict(n_routes, first int64[R + 1], shape, bytes)
@@ -1255,12 +1276,60 @@ class SsdRouteEnsemble(_RouteEnsemble):
         super(SsdRouteEnsemble, self).__init__(agents, metrics=metrics)
         self.channel = int(channels[0])
 
-    def _device_step(self, idx, xs, ys, angs):
-        return self.engine.rvssd_sense_step(xs, ys, angs, self._banks[idx], self.channel,
-                                            land_of_member=None if self._lands is None else self._lands[idx])
+    @classmethod
+    def from_routes_with(cls, agent, routes, starts, metrics="host", window=None, window_centres=None, relocalise_below=None):
+        """_RouteEnsemble.from_routes_with, and window, window_centres and relocalise_below as SadsRouteEnsemble.from_routes_with takes
+        them (relocalise_below in the unit of angle_familiarity, -SSD)."""
+        starts, routes = list(starts), list(routes)
+        wins, centres = cls._windows_arg(window, window_centres, starts, [len(r) for r in routes])
+        thresholds = cls._thresholds_arg(relocalise_below, wins)
+        ens = cls._from_routes(agent, routes, starts, metrics, None, None)
+        ens._set_windows(wins, centres, thresholds)
+        return ens
 
-    # scene_familiarity: worked out when read, as SadsRouteEnsemble's members' (a per-view extreme, not the one-value models' fill)
-    _note_scene = NavEnsemble._note_scene
+    @classmethod
+    def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host", sensors=None, window=None, window_centres=None,
+                        relocalise_below=None):
+        """_RouteEnsemble.from_landscapes, and window, window_centres and relocalise_below as from_routes_with takes them."""
+        starts, routes = list(starts), list(routes)
+        lengths = [len(rt[1]) if isinstance(rt, (tuple, list)) and len(rt) == 2 else 0 for rt in routes]
+        wins, centres = cls._windows_arg(window, window_centres, starts, lengths)
+        thresholds = cls._thresholds_arg(relocalise_below, wins)
+        ens = super(SsdRouteEnsemble, cls).from_landscapes(agent, landscapes, routes, starts, metrics=metrics, sensors=sensors)
+        ens._set_windows(wins, centres, thresholds)
+        return ens
+
+    def _device_step(self, idx, xs, ys, angs):
+        """A member with a window and a centre goes to rvssdw_sense_step, every other to rvssd_sense_step: at most two device calls,
+        and with no window anywhere the one call there was.  Where a member of the windowed call has a threshold (relocalise_below) the
+        call carries every member's (-inf for those without: never lost).  The results come back as one RouteSsdResults in the caller's
+        order."""
+        from .engine import RouteSsdResults
+        wins = [self._window_of(self.agents[i]) for i in idx]
+        lands = None if self._lands is None else self._lands[idx]
+        self._step_windows = {id(self.agents[i]): w for i, w in zip(idx, wins)}
+        ks = [k for k, w in enumerate(wins) if w is not None]
+        if not ks:
+            results = self.engine.rvssd_sense_step(xs, ys, angs, self._banks[idx], self.channel, land_of_member=lands)
+        else:
+            xs, ys, angs = np.asarray(xs, dtype=np.float64), np.asarray(ys, dtype=np.float64), np.asarray(angs, dtype=np.float64)
+            banks = self._banks[idx]
+            rest = [k for k, w in enumerate(wins) if w is None]
+            taus = [getattr(self.agents[idx[k]], "relocalise_below", None) for k in ks]
+            more = {} if all(t is None for t in taus) else dict(reloc_below=np.array([-np.inf if t is None else t for t in taus]))
+            parts = [(ks, self.engine.rvssdw_sense_step(xs[ks], ys[ks], angs[ks], banks[ks], [wins[k][0] for k in ks], [wins[k][1] for k in ks],
+                                                        self.channel, land_of_member=None if lands is None else lands[ks], **more))]
+            if rest:
+                parts.append((rest, self.engine.rvssd_sense_step(xs[rest], ys[rest], angs[rest], banks[rest], self.channel,
+                                                                 land_of_member=None if lands is None else lands[rest])))
+            n, A = angs.shape
+            results = RouteSsdResults(np.empty((n, A)), np.empty((n, A), dtype=np.int64), np.empty(n, dtype=np.int32),
+                                      np.empty(n, dtype=np.uint32))
+            for at, r in parts:
+                results.angle_ssd[at], results.angle_familiarity[at], results.angle_view[at] = r.angle_ssd, r.angle_familiarity, r.angle_view
+                results.best_idex[at], results.flags[at] = r.best_idex, r.flags
+        self._remember_views(idx, results)
+        return results
 
     def _read_scene(self):
         todo = [a for a in self.agents if a._scene_stale is not None and a._scene_owner is self]
@@ -1270,9 +1339,10 @@ class SsdRouteEnsemble(_RouteEnsemble):
         lands = None if self._lands is None else [a.landscape_index for a in todo]
         rows = self.engine.rvssd_scene([t[0] for t in st], [t[1] for t in st], np.stack([t[2] for t in st]), [a.memory_bank for a in todo],
                                        self.channel, land_of_member=lands)
-        for a, row in zip(todo, rows):
+        for a, row, t in zip(todo, rows, st):
             a._scene_stale = None
             a._scene_owner = None
             np.negative(row, out=a._scene_fam)                    # min over headings of -SSD = -(max over headings of SSD)
+            self._mask_scene(a, t)
 
     scene_familiarity = SadsRouteEnsemble.scene_familiarity

@@ -2,7 +2,7 @@
 """Times a step of the route view store (dv_rviews_sense_step, navsim_amd.SadsRouteEnsemble) at a slice of the reference's grid and
 writes profiles/rviews_time.json.
 
-    python tools/rviews_time.py [--sides 32,64] [--calls 30] [--reps 5] [--blocks routes[,sensors][,window][,reloc][,ssd]] [--out profiles/rviews_time.json]
+    python tools/rviews_time.py [--sides 32,64] [--calls 30] [--reps 5] [--blocks routes[,sensors][,window][,reloc][,ssd][,ssdwin]] [--out profiles/rviews_time.json]
 
 Shape: 4 routes x 8 starts x 10 headings = 32 trials of 320 columns, views of side x side.  The routes have the grid's length:
 synth.sin_training_path with arclen = step_size / n_test_angles (scripts/run_experiment.py:207) on a 900 x 900 landscape, one curve
@@ -43,7 +43,17 @@ SSD block (--blocks ssd): the same slice scored as exact SSD of one channel on t
 perfect-memory call (dv_rviews_sense_step) at the same poses on the SAME engine and store, in alternating windows of one process, hipEvent
 pairs: ssd_call_us and sads_call_us, their ratio, and ensemble_step_wall_us (SsdRouteEnsemble.step_forward(fake=True), wall clock).  Two
 members' rows are checked against a NumPy int64 statement on the store's own views before anything is timed.  The block is the file's
-"ssd" key; measured alone it leaves every other key as it was."""
+"ssd" key; measured alone it leaves every other key as it was.
+
+SSD window block (--blocks ssdwin): the same slice as exact SSD under a temporal window (dv_rvssdw_sense_step), SSDWIN_WINDOWS =
+(50, 50) and (255, 256) centred on each pose's nearest route point, against the unwindowed dv_rvssd_sense_step at the same poses on the
+same engine and store, in alternating windows of one process, hipEvent pairs: unwindowed_call_us and, per window, windowed_call_us and
+its ratio; under the 101-view window the call with thresholds -- reloc_none_lost_call_us (every threshold -inf: the price of the
+planning launch, the cleared keys and the empty worst-case grid), reloc_4_lost_call_us (one member a route at +inf) and
+reloc_all_lost_call_us -- and ensemble_step_wall_us per window (SsdRouteEnsemble(window=...).step_forward(fake=True), wall clock) beside
+the unwindowed ensemble's.  Whole-route windows on the shortest prefix, and the lost members' rows against the unwindowed call, are
+checked on their bits before anything is timed.  The block is the file's "ssdwin" key; measured alone it leaves every other key as it
+was."""
 import argparse
 import json
 import os
@@ -387,13 +397,106 @@ def measure_ssd(side, n_calls, reps):
     return out
 
 
+SSDWIN_WINDOWS = ((50, 50), (255, 256))
+
+
+def measure_ssdwin(side, n_calls, reps):
+    """The ssdwin block's row of one side."""
+    import navsim_amd
+    from navsim_amd import synth
+    land = synth.synth_landscape(3, LAND, 4)
+    routes = [synth.sin_training_path(c, 0.2 * LAND, 0.6 * LAND, arclen=STEP_SIZE / HEADINGS) for c in CURVES]
+    starts = starts_of(routes)
+    centres = np.array([int(np.argmin(np.linalg.norm(routes[r] - np.array(pos), axis=1))) for r, pos, _ in starts])
+
+    def ensemble(window):
+        a = navsim_amd.NavBySceneFamiliarity(land, (side, side), STEP_SIZE, n_test_angles=HEADINGS, track_scene_familiarity=False,
+                                             familiarity_model=navsim_amd.ssd_familiarity(SSD_CHANNEL))
+        return navsim_amd.SsdRouteEnsemble.from_routes_with(a, routes, starts, metrics="device", window=window,
+                                                            window_centres=None if window is None else centres.tolist())
+
+    plain = ensemble(None)
+    windowed = [ensemble(w) for w in SSDWIN_WINDOWS]
+    eng = plain.engine
+    n = len(starts)
+    xs = np.array([p[0] for _, p, _ in starts])
+    ys = np.array([p[1] for _, p, _ in starts])
+    angs = (np.array([a for _, _, a in starts])[:, None] + plain.agents[0].angle_offsets[None, :]) % (2 * np.pi)
+    route_of = np.array([r for r, _, _ in starts], dtype=np.int32)
+    lens = np.array([len(routes[r]) for r in route_of])
+    bounds = [(np.maximum(0, centres - b), np.minimum(lens, centres + a + 1)) for b, a in SSDWIN_WINDOWS]
+    four = np.arange(0, n, STARTS_PER_ROUTE)                     # one member a route
+    taus = dict(none=np.full(n, -np.inf), four=np.where(np.isin(np.arange(n), four), np.inf, -np.inf), all=np.full(n, np.inf))
+    lost_of = dict(none=np.arange(0), four=four, all=np.arange(n))
+
+    def call(k=None, which=None):
+        eng.timer_start()
+        for _ in range(n_calls):
+            if k is None:
+                res = eng.rvssd_sense_step(xs, ys, angs, route_of, SSD_CHANNEL)
+            else:
+                res = eng.rvssdw_sense_step(xs, ys, angs, route_of, bounds[k][0], bounds[k][1], SSD_CHANNEL,
+                                            reloc_below=None if which is None else taus[which])
+        return eng.timer_stop() * 1e3 / n_calls, res
+
+    def wall(ens):
+        w0 = time.perf_counter()
+        for _ in range(n_calls):
+            ens.step_forward(fake=True)
+        return (time.perf_counter() - w0) * 1e6 / n_calls
+
+    _, whole = call()                                             # warm-up of every form, and the forms agree
+    assert not whole.flags.any()
+    for k in range(len(SSDWIN_WINDOWS)):
+        _, res = call(k)
+        assert not res.flags.any() and (res.angle_view >= bounds[k][0][:, None]).all() and (res.angle_view < bounds[k][1][:, None]).all()
+        assert (res.angle_ssd >= whole.angle_ssd).all()
+        inside = (whole.angle_view >= bounds[k][0][:, None]) & (whole.angle_view < bounds[k][1][:, None])
+        assert np.array_equal(res.angle_ssd[inside], whole.angle_ssd[inside]) and np.array_equal(res.angle_view[inside], whole.angle_view[inside])
+    _, win = call(0)
+    for which in ("none", "four", "all"):
+        _, got = call(0, which)
+        m = lost_of[which]
+        ssd, view = win.angle_ssd.copy(), win.angle_view.copy()
+        ssd[m], view[m] = whole.angle_ssd[m], whole.angle_view[m]
+        assert np.array_equal(got.angle_ssd, ssd) and np.array_equal(got.angle_view, view) and np.array_equal(np.flatnonzero(got.relocalised), m)
+    for e in [plain] + windowed:
+        wall(e)
+    t = {key: [] for key in ("unwindowed", "none", "four", "all", "wall_unwindowed")}
+    t_win, w_win = [[] for _ in SSDWIN_WINDOWS], [[] for _ in SSDWIN_WINDOWS]
+    for _ in range(reps):                                         # alternating windows
+        t["unwindowed"].append(call()[0])
+        for k in range(len(SSDWIN_WINDOWS)):
+            t_win[k].append(call(k)[0])
+        for which in ("none", "four", "all"):
+            t[which].append(call(0, which)[0])
+        t["wall_unwindowed"].append(wall(plain))
+        for k, e in enumerate(windowed):
+            w_win[k].append(wall(e))
+    med = float(np.median(t["unwindowed"]))
+    rows = []
+    for k, (b, a) in enumerate(SSDWIN_WINDOWS):
+        rows.append(dict(behind=b, ahead=a, views=int((bounds[k][1] - bounds[k][0]).max()), windowed_call_us=spread(t_win[k]),
+                         ensemble_step_wall_us=spread(w_win[k]), unwindowed_over_windowed_call=round(med / float(np.median(t_win[k])), 3),
+                         members_running=len(windowed[k].active)))
+    m101 = float(np.median(t_win[0]))
+    out = dict(side=side, routes=len(routes), route_views=[len(r) for r in routes], members=n, headings=HEADINGS, columns=n * HEADINGS,
+               channel=SSD_CHANNEL, calls_per_window=n_calls, windows=reps, tile_columns=32, unwindowed_call_us=spread(t["unwindowed"]),
+               unwindowed_ensemble_step_wall_us=spread(t["wall_unwindowed"]), members_running=len(plain.active), windowed=rows,
+               reloc_window_views=rows[0]["views"], reloc_none_lost_call_us=spread(t["none"]), reloc_4_lost_call_us=spread(t["four"]),
+               reloc_all_lost_call_us=spread(t["all"]), none_lost_minus_windowed_us=round(float(np.median(t["none"])) - m101, 3))
+    for e in [plain] + windowed:
+        e.engine.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sides", default="32,64")
     ap.add_argument("--calls", type=int, default=30)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rviews_time.json"))
-    ap.add_argument("--blocks", default="routes", help="which blocks to measure: routes (the routed step against four engines), sensors, window, reloc, ssd")
+    ap.add_argument("--blocks", default="routes", help="which blocks to measure: routes (the routed step against four engines), sensors, window, reloc, ssd, ssdwin")
     ap.add_argument("--limit", type=int, default=240, help="seconds allowed to the sensors block's GPU child")
     args = ap.parse_args()
     blocks = args.blocks.split(",")
@@ -431,6 +534,13 @@ def main():
                           sizes=[measure_ssd(int(s), args.calls, args.reps) for s in args.sides.split(",")])
     elif "ssd" in kept:
         doc["ssd"] = kept["ssd"]
+    if "ssdwin" in blocks:                                        # a key of its own, as the window block's
+        if not ({"routes", "sensors", "window", "reloc", "ssd"} & set(blocks)) and kept:
+            doc = dict(kept)
+        doc["ssdwin"] = dict(device=torch.cuda.get_device_name(0), channel=SSD_CHANNEL, windows=[list(w) for w in SSDWIN_WINDOWS],
+                             sizes=[measure_ssdwin(int(s), args.calls, args.reps) for s in args.sides.split(",")])
+    elif "ssdwin" in kept:
+        doc["ssdwin"] = kept["ssdwin"]
     with open(args.out, "w") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")

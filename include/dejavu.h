@@ -907,6 +907,37 @@ int dv_sensors_set(dv_ctx *ctx, const int32_t *pw, const int32_t *ph, const int3
 int dv_sensors_clear(dv_ctx *ctx);
 int dv_sensors_info(dv_ctx *ctx, int *n, int32_t *pw, int32_t *ph, int32_t *mask_n, uint8_t *luts);
 
+/* ---- noise rows: sensor noise on landscape sets, a reproducible draw per sensing */
+/*
+ * The sensed views are a deterministic function of the pose.  With noise rows live, every sensed call that takes a landscape table
+ * adds an integer draw to the S and V of every sensor pixel, with no new argument: dv_lands_sense, dv_lands_mbank_ /
+ * dv_lands_ibank_train_from_poses, dv_lands_mbank_ / dv_lands_ibank_sense_step, and dv_rviews_set_from_poses and the dv_rviews_ /
+ * dv_rvwin_ / dv_rvssd_ / dv_rvssdw_ sensed steps and scenes with a land_of_* table.  Row i = (keys[i], amp_s[i], amp_v[i]) belongs to
+ * member i of a step or scene call, or to view / pose i of a training, store or dv_lands_sense call.  For sensor pixel j = bi w + bj
+ * (row-major) of the row's heading a (a = 0 where the call has one pose per row), with P = w h and uint64 arithmetic that wraps:
+ *     base = splitmix64(key + seed * 0x9E3779B97F4A7C15)       word = splitmix64(base + (a * P + j))
+ *     d_S  = word & 0xFFFFFFFF, d_V = word >> 32               n_c = ((d_c * (2 * amp_c + 1)) >> 32) - amp_c, in [-amp_c, +amp_c]
+ *     S'   = clamp(S + n_S, 0, 255), V' = clamp(V + n_V, 0, 255)
+ * S and V are the sensor pixel's values after the pixel block's rule and before the level tables; the hue is the noiseless model's
+ * (a zero-saturation pixel has hue 0, decided on the noiseless S); the level tables (the pose's own entry's under a sensor table) and
+ * the mask follow, so masked pixels stay 0.  A row of zero amplitudes gives the noiseless bytes.  The draw depends on the key and the
+ * pixel's place within the row, not on the row's index or on who else is in the call.  A footprint off its landscape is the error it is
+ * without rows.
+ *   rows             n >= 1 rows replace the live ones; built first, in place only when complete.  An unchanged table is not uploaded
+ *                    again.  DV_ERR_STATE without a configured sensor.
+ *   clear            no rows: every call launches exactly what it launched before.
+ *   info             n (0: none), the seed and the rows (the caller's arrays of n: ask for n first); any pointer may be NULL.
+ * While rows are live, a sensed call whose landscape table has not n entries is refused before anything reaches the device
+ * (DV_ERR_INVALID names both counts); a sensed call of the banked models or the route view store WITHOUT a landscape table is refused
+ * with DV_ERR_STATE (it would sense without noise), as is dv_lands_mbank_sense_step under a population table; the uploaded-patch calls
+ * (*_u8), the library path (dv_step*, dv_sense_step*), dv_sense and the single-agent calls are untouched and noiseless.  dv_lands_set,
+ * dv_lands_clear and dv_sensors_clear leave the rows alone; a dv_configure_sensor that changes w x h drops them (P enters the
+ * counter); dv_destroy frees them.
+ */
+int dv_noise_rows(dv_ctx *ctx, uint64_t seed, const uint64_t *keys, const uint8_t *amp_s, const uint8_t *amp_v, int64_t n);
+int dv_noise_clear(dv_ctx *ctx);
+int dv_noise_info(dv_ctx *ctx, int64_t *n, uint64_t *seed, uint64_t *keys, uint8_t *amp_s, uint8_t *amp_v);
+
 /* ---- route view store: perfect-memory members on their own routes ------------ */
 /*
  * The sensed views of R training routes side by side as raw HSV bytes, and a step that scores every member's headings against the

@@ -402,6 +402,14 @@ struct dv_ctx {
     unsigned char* sn_luts = nullptr;         // [n_lands][3][256]: the entries' level tables
     std::vector<int32_t> sn_pw, sn_ph, sn_mask;   // [n_lands] (empty: no table)
     std::vector<uint8_t> sn_luts_host;        // [n_lands][3][256]
+    // noise rows of the sensed calls that take a landscape table (dejavu_noise.inl: dv_noise_*)
+    int64_t nz_n = 0;                         // rows (0: none, every call senses the noiseless model)
+    uint64_t nz_seed = 0;
+    std::vector<uint64_t> nz_keys;            // [nz_n]
+    std::vector<uint8_t> nz_amp_s, nz_amp_v;  // [nz_n]
+    std::vector<NoiseRow> nz_rows;            // [nz_n]: what the device reads of a row, in the caller's order
+    std::vector<NoiseRow> nz_sorted;          // a call's permutation of them (the Infomax banked step)
+    MirroredTable nz_tab;                     // the device's rows, in the order of the call's landscape table
     // route view store (dejavu_rviews.inl: dv_rviews_*): independent of the library above
     unsigned* rv_planes = nullptr;            // groups of 64 views, three byte planes each (nullptr: no store)
     RvRoute* rv_routes = nullptr;             // [n_routes]: first group, views
@@ -471,6 +479,7 @@ static void infomax_free(dv_ctx* c);
 static void mb_free(dv_ctx* c);
 static void lands_free(dv_ctx* c);
 static void sensors_free(dv_ctx* c);
+static void noise_drop(dv_ctx* c);
 static void rviews_free(dv_ctx* c);
 static void rvssd_free(dv_ctx* c);
 static void path_routes_free(dv_ctx* c);
@@ -577,6 +586,7 @@ extern "C" void dv_destroy(dv_ctx* c) {
     infomax_free(c);
     mb_free(c);
     lands_free(c);
+    noise_drop(c);
     rviews_free(c);
     rvssd_free(c);
     path_routes_free(c);
@@ -1513,7 +1523,10 @@ extern "C" int dv_configure_sensor(dv_ctx* c, int sw, int sh, int pw, int ph, co
     }
     HIP_TRY(c, hipMemcpyAsync(c->d_lut, lut, 768, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->have_sensor && (c->sensor.sw != sw || c->sensor.sh != sh)) sensors_free(c);   // (a sensor table's masks were checked against the old w)
+    if (c->have_sensor && (c->sensor.sw != sw || c->sensor.sh != sh)) {
+        sensors_free(c);                                      // (a sensor table's masks were checked against the old w)
+        noise_drop(c);                                        // (w h enters the noise rows' counters)
+    }
     c->sensor.sw = sw; c->sensor.sh = sh; c->sensor.pw = pw; c->sensor.ph = ph; c->sensor.mask_n = mask_n;
     c->have_sensor = true;
     return DV_OK;
@@ -3832,6 +3845,7 @@ extern "C" int dv_stream_read_gbps(dv_ctx* c, int64_t n_bytes, int iters, double
 #include "dejavu_diffuse.inl"   // dv_diffuse_*: the landscape generator's heat equation (kernels and host side)
 #include "dejavu_lands.inl"     // dv_lands_*: landscape sets, a landscape per pose in the banked models' sensed calls (kernel and host side)
 #include "dejavu_sensors.inl"   // dv_sensors_*: a sensor configuration per landscape of the set (kernel and host side)
+#include "dejavu_noise.inl"     // dv_noise_*: a reproducible noise draw per sensing on a landscape set (kernels and host side)
 #include "dejavu_rviews.inl"    // dv_rviews_*: route view store, perfect-memory members scored on their own routes (kernels and host side)
 #include "dejavu_rvreloc.inl"   // k_rvreloc_*: lost windowed members re-localise inside the step, planned and scored on the device (kernels and host side)
 #include "dejavu_rvwin.inl"     // dv_rvwin_*: windowed perfect memory on the route view store, scored in one fused launch (kernel and host side)

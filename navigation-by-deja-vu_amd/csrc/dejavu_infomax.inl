@@ -984,6 +984,7 @@ static int ibank_batch(dv_ctx* c, const char* who, const uint8_t* planes, const 
     int rc = ibank_check(c, who, "bank_of_member", bank_of, n_agents);
     if (rc) return rc;
     if (land_of) { rc = lands_check(c, who, "land_of_member", land_of, n_agents); if (rc) return rc; }
+    else if (!planes) { rc = noise_need_lands(c, who); if (rc) return rc; }
     const long long C = (long long)n_agents * A;
     const int B = c->im_banks;
     if (C + (long long)kImHeadings * B > 0x7fffffffll - kImHeadings)
@@ -1036,7 +1037,7 @@ static int ibank_batch(dv_ctx* c, const char* who, const uint8_t* planes, const 
     if (!rc && land_of) {
         std::vector<int32_t> sorted((size_t)n_agents);
         for (int p = 0; p < n_agents; ++p) sorted[(size_t)p] = land_of[(size_t)order[(size_t)p]];
-        rc = lands_upload(c, sorted.data(), n_agents);
+        rc = lands_upload(c, sorted.data(), n_agents, order.data());   // (live noise rows ride the same permutation)
     }
     if (rc) return rc;
     const ImBlock* blocks = c->im_ktab.record<ImBlock>();
@@ -1177,6 +1178,7 @@ static int ibank_train_from_poses(dv_ctx* c, const char* who, const double* x, c
     rc = ibank_check(c, who, "bank_of_view", bank_of_view, n);
     if (rc) return rc;
     if (land_of) { rc = lands_check(c, who, "land_of_view", land_of, n); if (rc) return rc; }
+    else { rc = noise_need_lands(c, who); if (rc) return rc; }
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)n * (size_t)c->im_N * 3;
     rc = ensure_sense_buffer(c, bytes);

@@ -2437,6 +2437,26 @@ struct Pose { double x, y, c, s; };   // position and cos/sin of -(pi/2 - angle)
 struct LandEntry { long long base; int rows, cols; };   // a landscape of a set (dejavu_lands.inl): its first byte within the set, its shape
 struct SensorEntry { int pw, ph, mask_n; };               // the sensor a landscape of a set is sensed with (dejavu_sensors.inl); sw x sh stay the context's
 
+// Sensor noise (dejavu_noise.inl): a reproducible integer draw per sensing.  A noise row is what one member of a step, or one view of a
+// training call, is sensed under: base = splitmix64(key + seed GOLDEN), made on the host, and the amplitudes of S and V.  Pixel j of
+// the row's heading a draws word = splitmix64(base + (a P + j)): its low half is S's draw, its high half V's, each scaled to an integer
+// in [-amp, +amp] by a 64-bit multiply, added and clamped to [0, 255].  The hook sits between the block rule and the level tables; the
+// hue is the noiseless model's.  NOISE = false (the default of sense_thread and sense_pixel) compiles to what there was before.
+struct NoiseRow { unsigned long long base; unsigned amp_s, amp_v; };
+struct NoiseArgs { const NoiseRow* rows; unsigned col0, per; };   // a launch's rows: pose t of it is column col0 + t, row col / per, heading col % per
+
+__device__ __forceinline__ unsigned noise_add(unsigned v, unsigned long long draw, unsigned amp) {
+    const int n = (int)((draw * (2ull * amp + 1ull)) >> 32) - (int)amp;
+    const int o = (int)v + n;
+    return (unsigned)(o < 0 ? 0 : o > 255 ? 255 : o);
+}
+
+__device__ __forceinline__ void noise_apply(const NoiseRow& r, unsigned long long counter, unsigned& S, unsigned& V) {
+    const unsigned long long word = splitmix64(r.base + counter);
+    S = noise_add(S, word & 0xFFFFFFFFull, r.amp_s);
+    V = noise_add(V, word >> 32, r.amp_v);
+}
+
 __device__ __forceinline__ bool sense_fetch(const unsigned char* __restrict__ land, const SensorCfg& g, const Pose& p,
                                             int i, int j, unsigned& H, unsigned& S, unsigned& V) {
     const double px = (double)j - 0.5 * (double)(g.sw * g.pw);
@@ -2455,9 +2475,10 @@ __device__ __forceinline__ bool sense_fetch(const unsigned char* __restrict__ la
 
 // One thread per sensor pixel of every pose.  out: uint8[n][sh][sw][3].  EACH: err is int[n], a word per pose (an ensemble must know
 // whose footprint left the landscape); else one word for all poses.
-template <bool EACH>
+template <bool EACH, bool NOISE = false>
 __device__ __forceinline__ void sense_thread(const unsigned char* __restrict__ land, const Pose* __restrict__ poses, int n, const SensorCfg& g,
-                                             const unsigned char* __restrict__ lut, unsigned char* __restrict__ out, int* __restrict__ err) {
+                                             const unsigned char* __restrict__ lut, unsigned char* __restrict__ out, int* __restrict__ err,
+                                             const NoiseArgs nz = NoiseArgs{nullptr, 0u, 1u}) {
     const long long total = (long long)n * g.sh * g.sw;
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= total) return;
@@ -2499,6 +2520,10 @@ __device__ __forceinline__ void sense_thread(const unsigned char* __restrict__ l
         else atomicOr(err, 1);
         return;
     }
+    if (NOISE) {
+        const unsigned col = nz.col0 + (unsigned)pose;
+        noise_apply(nz.rows[col / nz.per], (unsigned long long)(col % nz.per) * (unsigned)(g.sh * g.sw) + (unsigned)(bi * g.sw + bj), os, ov);
+    }
     oh = lut[oh]; os = lut[256 + os]; ov = lut[512 + ov];
     const int mid = g.sw / 2;
     if (bj >= mid - g.mask_n && bj < mid + g.mask_n) { oh = 0; os = 0; ov = 0; }
@@ -2517,10 +2542,13 @@ __global__ void k_sense_each(const unsigned char* __restrict__ land, const Pose*
     sense_thread<true>(land, poses, n, g, lut, out, err);
 }
 
-// One sensor pixel of one pose (k_patch_prep senses the headings' patches with it, four pixels per thread).
+// One sensor pixel of one pose (k_patch_prep senses the headings' patches with it, four pixels per thread).  NOISE: the pose's noise row
+// and a P of its heading a; the pixel's counter is a P + bi sw + bj.
+template <bool NOISE = false>
 __device__ __forceinline__ bool sense_pixel(const unsigned char* __restrict__ land, const SensorCfg& g, const Pose& p,
                                             const unsigned char* __restrict__ lut, int bi, int bj,
-                                            unsigned& oh, unsigned& os, unsigned& ov) {
+                                            unsigned& oh, unsigned& os, unsigned& ov, const NoiseRow* __restrict__ row = nullptr,
+                                            unsigned long long a_P = 0) {
     const int nblk = g.pw * g.ph;
     oh = os = ov = 0;
     if (nblk == 1) {
@@ -2546,6 +2574,7 @@ __device__ __forceinline__ bool sense_pixel(const unsigned char* __restrict__ la
         os = (unsigned)(((best_sum / g.ph) * g.pw) & 0xFF);
         ov = (unsigned)(long long)round((double)vsum / (double)nblk);
     }
+    if (NOISE) noise_apply(*row, a_P + (unsigned)(bi * g.sw + bj), os, ov);
     oh = lut[oh]; os = lut[256 + os]; ov = lut[512 + ov];
     const int mid = g.sw / 2;
     if (bj >= mid - g.mask_n && bj < mid + g.mask_n) { oh = 0; os = 0; ov = 0; }

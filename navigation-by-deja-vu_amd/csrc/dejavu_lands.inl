@@ -41,6 +41,9 @@ __global__ void k_sense_lands(const unsigned char* __restrict__ lands, const Lan
 }  // namespace dv
 
 static int sensors_launch_sense(dv_ctx* c, long long p0, long long col0, int per, long long n, unsigned char* d_out, int* err);   // (dejavu_sensors.inl)
+static int noise_launch_sense(dv_ctx* c, long long p0, long long col0, int per, long long n, unsigned char* d_out, int* err);     // (dejavu_noise.inl)
+static int noise_check(dv_ctx* c, const char* who, const char* what, int64_t n);
+static int noise_upload(dv_ctx* c, const int* order);
 
 static void lands_free(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
@@ -62,18 +65,23 @@ static int lands_need(dv_ctx* c, const char* who) {
 // A call's landscape table, checked entry by entry before anything of the call reaches the device ...
 static int lands_check(dv_ctx* c, const char* who, const char* what, const int32_t* land_of, int64_t n) {
     if (land_of) { const int rc = lands_need(c, who); if (rc) return rc; }   // (a NULL table is refused first, whether there is a set or not)
-    return index_check(c, who, what, land_of, n, (int)c->ld_rows.size(), "n_lands");
+    const int rc = index_check(c, who, what, land_of, n, (int)c->ld_rows.size(), "n_lands");
+    return rc ? rc : noise_check(c, who, what, n);             // (live noise rows: one per entry of this table, dejavu_noise.inl)
 }
 
 // ... and then enqueued for the device, unless the device's table holds the same already (`land_of` may be a temporary of the caller's).
-static int lands_upload(dv_ctx* c, const int32_t* land_of, int64_t n) {
-    return table_upload(c, c->ld_of, land_of, (size_t)n * sizeof(int));
+// Live noise rows ride along, in the order of the table's entries: `order` (nullptr: the caller's own) is the permutation a call has
+// given its table, entry p being the caller's order[p].
+static int lands_upload(dv_ctx* c, const int32_t* land_of, int64_t n, const int* order = nullptr) {
+    const int rc = table_upload(c, c->ld_of, land_of, (size_t)n * sizeof(int));
+    return rc ? rc : noise_upload(c, order);
 }
 
 // Enqueue k_sense_lands for `n` poses that are resident in d_poses from `p0` on and are columns col0 .. of the call, into d_out
 // (uint8[n][sh][sw][3]); err: int[n], zeroed by the caller.  Where the set has a sensor table (dejavu_sensors.inl) the pose's sensor is
-// its landscape's entry, through the kernel form that reads the table.
+// its landscape's entry, through the kernel form that reads the table; where noise rows are live (dejavu_noise.inl), the noise forms.
 static int lands_launch_sense(dv_ctx* c, long long p0, long long col0, int per, long long n, unsigned char* d_out, int* err) {
+    if (c->nz_n) return noise_launch_sense(c, p0, col0, per, n, d_out, err);
     if (c->sn_tab) return sensors_launch_sense(c, p0, col0, per, n, d_out, err);
     const long long total = n * c->sensor.sh * c->sensor.sw;
     hipLaunchKernelGGL(k_sense_lands, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, c->ld_lands, c->ld_tab, c->ld_of.device<int>(),

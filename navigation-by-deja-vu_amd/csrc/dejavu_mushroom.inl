@@ -157,14 +157,17 @@ __device__ __forceinline__ void mb_fill_staged(unsigned char* plane, int tid, co
 
 // The sensor model: workgroup v senses channel `channel` of the g.sh x g.sw pixels at poses[v] into its LDS plane.  A pixel off the
 // landscape contributes 0 and the selection runs all the same (every thread reaches every barrier); err[v] is written by this workgroup
-// alone, 1 when any of its pixels was off, so the caller clears nothing beforehand.
+// alone, 1 when any of its pixels was off, so the caller clears nothing beforehand.  NOISE (dejavu_noise.inl): the column's noise row
+// and a N of its heading a within its member; pixel j draws at counter a N + j.
+template <bool NOISE = false>
 __device__ __forceinline__ void mb_fill_pose(unsigned char* plane, int tid, const unsigned char* __restrict__ land, const Pose* __restrict__ poses,
-                                             const SensorCfg& g, const unsigned char* __restrict__ lut, int channel, int N, int* __restrict__ err) {
+                                             const SensorCfg& g, const unsigned char* __restrict__ lut, int channel, int N, int* __restrict__ err,
+                                             const NoiseRow* __restrict__ row = nullptr, unsigned long long a_N = 0) {
     const Pose p = poses[blockIdx.x];
     int off = 0;
     for (int j = tid; j < N; j += kMbWaves * 64) {
         unsigned H, S, V;
-        if (!sense_pixel(land, g, p, lut, j / g.sw, j % g.sw, H, S, V)) { off = 1; H = S = V = 0; }
+        if (!sense_pixel<NOISE>(land, g, p, lut, j / g.sw, j % g.sw, H, S, V, row, a_N)) { off = 1; H = S = V = 0; }
         plane[j] = (unsigned char)(channel == 0 ? H : channel == 1 ? S : V);
     }
     off = __syncthreads_or(off);
@@ -279,6 +282,45 @@ __global__ __launch_bounds__(kMbWaves * 64) void k_mb_pose_bank_lands_sensors(co
     const unsigned char* lut;
     const unsigned char* land = land_sensor_of_column(lands, tab, sens, luts, land_of, col0 + blockIdx.x, per, g, lut);
     mb_view<kMbScore>(mb_lds, [&](unsigned char* plane, int tid) { mb_fill_pose(plane, tid, land, poses, g, lut, channel, N, err); },
+                      (int)blockIdx.x, N, conn, K, c, n_active, mb_bank(wt, K, bank_of, col0, per), d, nullptr, nullptr);
+}
+
+// The two forms above under noise rows (dejavu_noise.inl): the workgroup's column col0 + blockIdx.x is heading col % per of row col / per.
+__global__ __launch_bounds__(kMbWaves * 64) void k_mb_pose_bank_lands_noise(const unsigned char* __restrict__ lands, const LandEntry* __restrict__ tab,
+                                                                            const int* __restrict__ land_of, const NoiseRow* __restrict__ rows,
+                                                                            const Pose* __restrict__ poses, SensorCfg g,
+                                                                            const unsigned char* __restrict__ lut, int channel,
+                                                                            const unsigned short* __restrict__ conn, int K, int c, int n_active,
+                                                                            unsigned char* __restrict__ wt, int* __restrict__ d, int* __restrict__ err,
+                                                                            const int* __restrict__ bank_of, unsigned col0, unsigned per) {
+    extern __shared__ unsigned mb_lds[];
+    const int N = g.sh * g.sw;
+    const unsigned col = col0 + blockIdx.x;
+    const unsigned char* land = land_of_column(lands, tab, land_of, col, per, g);
+    const NoiseRow* row = rows + col / per;
+    const unsigned long long a_N = (unsigned long long)(col % per) * (unsigned)N;
+    mb_view<kMbScore>(mb_lds, [&](unsigned char* plane, int tid) { mb_fill_pose<true>(plane, tid, land, poses, g, lut, channel, N, err, row, a_N); },
+                      (int)blockIdx.x, N, conn, K, c, n_active, mb_bank(wt, K, bank_of, col0, per), d, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(kMbWaves * 64) void k_mb_pose_bank_lands_sensors_noise(const unsigned char* __restrict__ lands,
+                                                                                    const LandEntry* __restrict__ tab,
+                                                                                    const SensorEntry* __restrict__ sens,
+                                                                                    const unsigned char* __restrict__ luts,
+                                                                                    const int* __restrict__ land_of, const NoiseRow* __restrict__ rows,
+                                                                                    const Pose* __restrict__ poses, SensorCfg g, int channel,
+                                                                                    const unsigned short* __restrict__ conn, int K, int c, int n_active,
+                                                                                    unsigned char* __restrict__ wt, int* __restrict__ d,
+                                                                                    int* __restrict__ err, const int* __restrict__ bank_of,
+                                                                                    unsigned col0, unsigned per) {
+    extern __shared__ unsigned mb_lds[];
+    const int N = g.sh * g.sw;
+    const unsigned col = col0 + blockIdx.x;
+    const unsigned char* lut;
+    const unsigned char* land = land_sensor_of_column(lands, tab, sens, luts, land_of, col, per, g, lut);
+    const NoiseRow* row = rows + col / per;
+    const unsigned long long a_N = (unsigned long long)(col % per) * (unsigned)N;
+    mb_view<kMbScore>(mb_lds, [&](unsigned char* plane, int tid) { mb_fill_pose<true>(plane, tid, land, poses, g, lut, channel, N, err, row, a_N); },
                       (int)blockIdx.x, N, conn, K, c, n_active, mb_bank(wt, K, bank_of, col0, per), d, nullptr, nullptr);
 }
 
@@ -437,6 +479,8 @@ extern "C" int dv_mb_begin(dv_ctx* c, int h, int w, int channel, int n_kc, int f
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_pose_bank, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_pose_bank_lands, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_pose_bank_lands_sensors, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_pose_bank_lands_noise, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_pose_bank_lands_sensors_noise, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = mbpop_lds_cap(lds);
     if (e == hipSuccess) e = hipMemcpyAsync(c->mb_conn, ct.data(), ct.size() * sizeof(unsigned short), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->mb_wt, 1, K, c->stream);
@@ -491,6 +535,7 @@ static int mb_train_from_poses(dv_ctx* c, const char* who, const double* x, cons
     if (rc) return rc;
     if (bank_of) { rc = mbank_check(c, who, "bank_of_view", bank_of, n); if (rc) return rc; }
     if (land_of) { rc = lands_check(c, who, "land_of_view", land_of, n); if (rc) return rc; }
+    else { rc = noise_need_lands(c, who); if (rc) return rc; }
     HIP_TRY(c, hipSetDevice(c->device));
     if (bank_of) { rc = mbank_upload(c, bank_of, n); if (rc) return rc; }
     if (land_of) { rc = lands_upload(c, land_of, n); if (rc) return rc; }
@@ -619,6 +664,9 @@ static int mb_batch(dv_ctx* c, const char* who, const uint8_t* planes, const dou
     if (C > 0x7fffffffll) return fail(c, DV_ERR_INVALID, "%s: %d agents x %d headings are too many columns", who, n_agents, A);
     if (bank_of) { const int rb = mbank_check(c, who, "bank_of_member", bank_of, n_agents); if (rb) return rb; }
     if (land_of) { const int rl = lands_check(c, who, "land_of_member", land_of, n_agents); if (rl) return rl; }
+    else if (!planes) { const int rl = noise_need_lands(c, who); if (rl) return rl; }
+    if (!planes && c->nz_n && c->mbp_pops)                      // (the population table's pose kernels have no noise form)
+        return fail(c, DV_ERR_STATE, "%s: noise rows are live, and the sensed step under a population table has no noise form (dv_noise_clear first)", who);
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t N = (size_t)c->mb_N;
     long long slab = planes ? (long long)mb_slab(N) : (long long)kMbSlabViews;
@@ -645,6 +693,18 @@ static int mb_batch(dv_ctx* c, const char* who, const uint8_t* planes, const dou
         } else if (c->mbp_pops) {                               // (bank_of is there: the bank-0 calls are refused under a table)
             rc = mbpop_launch_pose(c, land_of != nullptr, c0, nc, A);
             if (rc) return rc;
+        } else if (land_of && c->nz_n && c->sn_tab) {             // (noise rows: uploaded beside the landscape table, dejavu_noise.inl)
+            hipLaunchKernelGGL(k_mb_pose_bank_lands_sensors_noise, dim3((unsigned)nc), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, c->ld_lands,
+                               c->ld_tab, c->sn_tab, c->sn_luts, c->ld_of.device<int>(), c->nz_tab.device<NoiseRow>(), c->d_poses + c0, c->sensor,
+                               c->mb_channel, c->mb_conn, c->mb_K, c->mb_c, c->mb_active, c->mb_wt, c->mb_bd + c0, c->mb_berr + c0,
+                               c->mb_bank_of.device<int>(), (unsigned)c0, (unsigned)A);
+            HIP_TRY(c, hipGetLastError());
+        } else if (land_of && c->nz_n) {
+            hipLaunchKernelGGL(k_mb_pose_bank_lands_noise, dim3((unsigned)nc), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, c->ld_lands, c->ld_tab,
+                               c->ld_of.device<int>(), c->nz_tab.device<NoiseRow>(), c->d_poses + c0, c->sensor, c->d_lut, c->mb_channel, c->mb_conn,
+                               c->mb_K, c->mb_c, c->mb_active, c->mb_wt, c->mb_bd + c0, c->mb_berr + c0, c->mb_bank_of.device<int>(), (unsigned)c0,
+                               (unsigned)A);
+            HIP_TRY(c, hipGetLastError());
         } else if (land_of && c->sn_tab) {
             hipLaunchKernelGGL(k_mb_pose_bank_lands_sensors, dim3((unsigned)nc), dim3(kMbWaves * 64), mb_lds_bytes(c), c->stream, c->ld_lands, c->ld_tab,
                                c->sn_tab, c->sn_luts, c->ld_of.device<int>(), c->d_poses + c0, c->sensor, c->mb_channel, c->mb_conn, c->mb_K, c->mb_c,

@@ -429,7 +429,7 @@ extern "C" int dv_rviews_set_from_poses(dv_ctx* c, const double* x, const double
     if (first[n_routes] != n) return fail(c, DV_ERR_INVALID, "%s: first[%d] = %lld, but n = %lld views", who, n_routes, (long long)first[n_routes], (long long)n);
     rc = rviews_check_poses(c, who, n);
     if (!rc) rc = rviews_check_shape(c, who, c->sensor.sh, c->sensor.sw);
-    if (!rc && land_of_view) rc = lands_check(c, who, "land_of_view", land_of_view, n);
+    if (!rc) rc = land_of_view ? lands_check(c, who, "land_of_view", land_of_view, n) : noise_need_lands(c, who);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)n * c->sensor.sh * c->sensor.sw * 3;
@@ -626,7 +626,7 @@ static int rviews_sense_members(dv_ctx* c, const char* who, const double* x, con
     int rc = rviews_check_tables(c, who, N, A, route_of_member, chem_weights);
     if (!rc) rc = rviews_check_poses(c, who, (long long)N * A);
     if (!rc) rc = sensor_fits(c, who, c->rv_h, c->rv_w);
-    if (!rc && land_of_member) rc = lands_check(c, who, "land_of_member", land_of_member, N);
+    if (!rc) rc = land_of_member ? lands_check(c, who, "land_of_member", land_of_member, N) : noise_need_lands(c, who);
     if (rc) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     rc = ensure_sense_buffer(c, (size_t)N * A * c->rv_h * c->rv_w * 3);

@@ -118,6 +118,7 @@ _f64p = ctypes.POINTER(ctypes.c_double)
 _i64p = ctypes.POINTER(ctypes.c_int64)
 _i32p = ctypes.POINTER(ctypes.c_int32)
 _u32p = ctypes.POINTER(ctypes.c_uint32)
+_u64p = ctypes.POINTER(ctypes.c_uint64)
 
 # name -> (restype, argtypes); every symbol include/dejavu.h declares
 PROTOTYPES = {
@@ -302,6 +303,9 @@ PROTOTYPES = {
     "dv_sensors_set": (ctypes.c_int, [_ctx_p, _i32p, _i32p, _i32p, _u8p, ctypes.c_int]),
     "dv_sensors_clear": (ctypes.c_int, [_ctx_p]),
     "dv_sensors_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), _i32p, _i32p, _i32p, _u8p]),
+    "dv_noise_rows": (ctypes.c_int, [_ctx_p, ctypes.c_uint64, _u64p, _u8p, _u8p, ctypes.c_int64]),
+    "dv_noise_clear": (ctypes.c_int, [_ctx_p]),
+    "dv_noise_info": (ctypes.c_int, [_ctx_p, _i64p, _u64p, _u64p, _u8p, _u8p]),
     "dv_rviews_set_u8": (ctypes.c_int, [_ctx_p, _u8p, _i64p, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "dv_rviews_set_from_poses": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int64, _i64p, ctypes.c_int, _i32p, _u8p]),
     "dv_rviews_step_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, _i32p, _f64p, ctypes.c_uint32, _f64p, _i64p, _i32p]),

@@ -250,6 +250,7 @@ class FamiliarityEngine(object):
         shape = (int(sensor_dimensions[1]), int(sensor_dimensions[0]))
         if getattr(self, "sensor_shape", shape) != shape:
             self.n_sensors = 0                                   # (a sensor table was checked against the old w x h: the library drops it)
+            self.n_noise_rows = 0                                # (w h enters the noise rows' counters: the library drops them)
         self.sensor_shape = shape
 
     @staticmethod
@@ -1696,6 +1697,56 @@ class FamiliarityEngine(object):
                                               N.u8ptr(lt)), "dv_sensors_info")
         self.n_sensors = n.value
         return dict(n_sensors=n.value, pixel_dimensions=np.stack([pw, ph], axis=1)[:n.value], masks=mk[:n.value], luts=lt[:n.value])
+
+    # -- noise rows: a reproducible noise draw per sensing on a landscape set (include/dejavu.h: dv_noise_*) ---------------------------
+    n_noise_rows = 0             # live noise rows (noise_rows; 0: every sensed call is the noiseless model)
+
+    @staticmethod
+    def _noise_args(seed, keys, amp_s, amp_v):
+        """(seed, keys uint64[n], amp_s uint8[n], amp_v uint8[n]) checked, or ValueError naming the argument and the entry."""
+        if isinstance(seed, (bool, float)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("seed must be an integer in [0, 2**64), got %r" % (seed,))
+        k = np.asarray(keys)
+        if k.dtype != np.uint64 or k.ndim != 1 or k.shape[0] < 1:
+            raise ValueError("keys must be uint64[n] with n >= 1, got dtype %s and shape %r" % (k.dtype, k.shape))
+        amps = []
+        for a, what in ((amp_s, "amp_s"), (amp_v, "amp_v")):
+            a = np.asarray(a)
+            if a.dtype.kind not in "iu":
+                raise ValueError("%s must hold integers, got dtype %s" % (what, a.dtype))
+            if a.shape != k.shape:
+                raise ValueError("%s must have shape %r (an amplitude per key), got %r" % (what, k.shape, a.shape))
+            for i, v in enumerate(a.tolist()):
+                if not 0 <= v <= 255:
+                    raise ValueError("%s[%d] = %d outside [0, 255]" % (what, i, v))
+            amps.append(np.ascontiguousarray(a, dtype=np.uint8))
+        return int(seed), np.ascontiguousarray(k), amps[0], amps[1]
+
+    def noise_rows(self, seed, keys, amp_s, amp_v):
+        """Noise rows of the sensed calls that take a landscape table (land_of_*): row i = (keys[i], amp_s[i], amp_v[i]) belongs to
+        member i of a step or scene call, or to view / pose i of a training, store or lands_sense call, which then add to the S and V
+        of every sensor pixel an integer in [-amp, +amp] drawn from splitmix64 at a counter of (seed, key, heading, pixel) -- after
+        the pixel block's rule, before the level tables; hue, mask and errors are the noiseless model's.  keys: uint64[n]; amplitudes:
+        integers in [0, 255], one per key; seed in [0, 2**64).  Checked before any library call.  While rows are live a call whose
+        landscape table has not n entries, or a sensed call without one, is refused; noise_clear ends that."""
+        seed, k, s, v = self._noise_args(seed, keys, amp_s, amp_v)
+        self._check(self._lib.dv_noise_rows(self._ctx, ctypes.c_uint64(seed), k.ctypes.data_as(N._u64p), N.u8ptr(s), N.u8ptr(v), len(k)),
+                    "dv_noise_rows")
+        self.n_noise_rows = len(k)
+
+    def noise_clear(self):
+        self._check(self._lib.dv_noise_clear(self._ctx), "dv_noise_clear")
+        self.n_noise_rows = 0
+
+    def noise_info(self):
+        """dict(n_rows, seed, keys uint64[n], amp_s uint8[n], amp_v uint8[n]) of the live rows (n_rows = 0: none)."""
+        n, seed = ctypes.c_int64(0), ctypes.c_uint64(0)
+        self._check(self._lib.dv_noise_info(self._ctx, ctypes.byref(n), ctypes.byref(seed), None, None, None), "dv_noise_info")
+        m = max(n.value, 1)
+        k, s, v = np.zeros(m, dtype=np.uint64), np.zeros(m, dtype=np.uint8), np.zeros(m, dtype=np.uint8)
+        self._check(self._lib.dv_noise_info(self._ctx, None, None, k.ctypes.data_as(N._u64p), N.u8ptr(s), N.u8ptr(v)), "dv_noise_info")
+        self.n_noise_rows = n.value
+        return dict(n_rows=n.value, seed=seed.value, keys=k[:n.value], amp_s=s[:n.value], amp_v=v[:n.value])
 
     # -- route view store: perfect-memory members scored on their own routes (include/dejavu.h: dv_rviews_*) ------------------------
     rviews_first = None          # int64[n_routes + 1] of the store (rviews_set_u8 / rviews_set_from_poses; None: no store)

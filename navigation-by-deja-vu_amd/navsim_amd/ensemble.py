@@ -426,7 +426,16 @@ class _RouteEnsemble(_OneValueEnsemble):
     from_landscapes(sensors=[...]) makes trials that differ in their SENSOR too: entry l of the list is the sensor landscape l is sensed
     with -- its sensor_pixel_dimensions, n_sensor_levels and mask_middle_n; w x h stays the engine's one -- kept on the engine as the
     set's sensor table (FamiliarityEngine.sensors_set).  A trial that uses two sensors on one landscape enters that landscape twice.
-    The members of a route on landscape l carry that entry's configuration, so their bounds are their own footprint's."""
+    The members of a route on landscape l carry that entry's configuration, so their bounds are their own footprint's.
+
+    from_landscapes(noise=dict(...)) puts NOISE IN THE SENSOR: every sensing adds to S and V of every sensor pixel an integer drawn
+    uniformly from [-amp, +amp] (FamiliarityEngine.noise_rows has the statement), independent at every sensing and reproducible from
+    (seed, key): training view v of route r draws under key (0x80000000 | r) << 32 | v, a member's step under stream << 32 | count,
+    count being the device steps the member has taken part in so far (fake or not).  Members carry `noise_stream`, `noise_amp`
+    (amp_s, amp_v) and `noise_count`; a member's rows are those of a one-member ensemble built with its stream, whoever else is in
+    the ensemble.  The ensemble sets the rows of exactly the members of each device call before it."""
+    NOISE_KEYS = ("seed", "amp_s", "amp_v", "train_amp_s", "train_amp_v", "streams")
+    _noise_seed = None           # from_landscapes(noise=...): the seed of the members' draws (None: no rows are ever set)
     _metrics_on_slots = False    # (NavEnsemble's slots hold ONE training path: the routed slots are made below)
     _one_route = None            # the name of the ensemble whose members share one trained route
     _info_call = None            # the engine's per-bank info
@@ -526,7 +535,7 @@ class _RouteEnsemble(_OneValueEnsemble):
         starts: iterable of (route_index, (x, y), angle), one member each (the first is `agent` itself, the others copies of it on the
         same engine).  Every route is trained into its own bank, all in one call; member i gets the training_path, training_path_length
         and familiar_scenes of routes[route_index_i], and that route's bank as its `memory_bank`.  The members' error metrics run on
-        the host; from_routes_with chooses."""
+        the host; from_routes_with chooses.  Sensor noise needs a landscape set: from_landscapes([landscape], ..., noise=...)."""
         return cls.from_routes_with(agent, routes, starts)
 
     @classmethod
@@ -534,7 +543,8 @@ class _RouteEnsemble(_OneValueEnsemble):
         """from_routes with the members' error metrics on the host ("host": every member's own NumPy pass, as from_routes) or on the
         device ("device": all members' in one call per ensemble step, each against its own route; see the class).
         populations (MushroomRouteEnsemble): None, or a list with one entry per route, the route's own model parameters -- see
-        MushroomRouteEnsemble."""
+        MushroomRouteEnsemble.  There is no `noise` here: sensor noise rides the landscape table, so use
+        from_landscapes([landscape], ..., noise=...)."""
         return cls._from_routes(agent, routes, starts, metrics, None, None, populations=populations)
 
     @classmethod
@@ -543,9 +553,10 @@ class _RouteEnsemble(_OneValueEnsemble):
         raise ValueError("%s has no populations: MushroomRouteEnsemble gives every route's bank cells and wiring of its own" % cls.__name__)
 
     @classmethod
-    def _from_routes(cls, agent, routes, starts, metrics, lands, land_of_route, sensors=None, populations=None, table=None):
+    def _from_routes(cls, agent, routes, starts, metrics, lands, land_of_route, sensors=None, populations=None, table=None, noise=None):
         """from_routes_with (lands None: every route on the agent's own landscape, the engine's one), or from_landscapes (route r on
-        lands[land_of_route[r]] of the engine's landscape set; sensors: None, or _sensor_entries' entry per landscape).
+        lands[land_of_route[r]] of the engine's landscape set; sensors: None, or _sensor_entries' entry per landscape; noise: None, or
+        _noise_arg's dict).
         populations: None, or from_routes_with's list (an entry per route).  table: None, or a subclass's own extra argument of
         _train_banks, by name (InfomaxRouteEnsemble's networks)."""
         import copy
@@ -593,7 +604,16 @@ class _RouteEnsemble(_OneValueEnsemble):
                 eng.sensors_set([e["sensor_pixel_dimensions"] for e in sensors], np.stack([e["lut"] for e in sensors]),
                                 [e["mask_middle_n"] for e in sensors])
             land_of_view = np.repeat(np.array(land_of_route, dtype=np.int32), [len(r) for r in routes])
-            views = cls._train_banks(eng, len(routes), points[:, 0], points[:, 1], np.concatenate(headings), bank_of_view, land_of_view, **table)
+            if noise is not None:                                 # the routes' views draw under their own keys, then no rows until a step
+                per_route = [len(r) for r in routes]
+                eng.noise_rows(noise["seed"], np.concatenate([cls._train_keys(r, n) for r, n in enumerate(per_route)]),
+                               np.repeat(noise["train_amp_s"], per_route), np.repeat(noise["train_amp_v"], per_route))
+            try:
+                views = cls._train_banks(eng, len(routes), points[:, 0], points[:, 1], np.concatenate(headings), bank_of_view, land_of_view,
+                                         **table)
+            finally:
+                if noise is not None:
+                    eng.noise_clear()
         func = model.from_engine(eng, views)
         members = []
         for k, (r, pos, ang) in enumerate(starts):
@@ -617,8 +637,90 @@ class _RouteEnsemble(_OneValueEnsemble):
             a.step_familiarity = np.inf
             a.position, a.angle = pos, ang
             a.reset_error()
+            a.noise_stream = None if noise is None else noise["streams"][k]
+            a.noise_amp = None if noise is None else (noise["amp_s"][k], noise["amp_v"][k])
+            a.noise_count, a._noise_key = 0, None
             members.append(a)
-        return cls(members, metrics=metrics)
+        ens = cls(members, metrics=metrics)
+        if noise is not None:
+            ens._noise_seed = noise["seed"]
+        return ens
+
+    # ---- sensor noise (from_landscapes(noise=...)) --------------------------------------------------------------------------------
+    @staticmethod
+    def _train_keys(route, n_views):
+        """uint64[n_views]: the noise keys of the views of route `route`, (0x80000000 | route) << 32 | view."""
+        return (np.uint64((0x80000000 | route) << 32) | np.arange(n_views, dtype=np.uint64)).astype(np.uint64)
+
+    @staticmethod
+    def _step_key(stream, count):
+        """The noise key of a member's device step: stream << 32 | count (count wraps at 2**32)."""
+        return (int(stream) << 32) | (int(count) & 0xFFFFFFFF)
+
+    @classmethod
+    def _noise_arg(cls, noise, n_starts, n_routes):
+        """from_landscapes' `noise` as dict(seed, amp_s / amp_v: a list per start, train_amp_s / train_amp_v: a list per route,
+        streams: a list per start), or None.  ValueError names the entry."""
+        if noise is None:
+            return None
+        if not isinstance(noise, dict):
+            raise ValueError("noise must be None or a dict with any of %r, got %r" % (cls.NOISE_KEYS, noise))
+        extra = sorted(set(noise) - set(cls.NOISE_KEYS))
+        if extra:
+            raise ValueError("noise: unknown keys %r (it holds any of %r)" % (extra, cls.NOISE_KEYS))
+
+        def whole(v):
+            return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+        seed = noise.get("seed", 0)
+        if not whole(seed) or not 0 <= seed < 2 ** 64:
+            raise ValueError("noise['seed'] must be an integer in [0, 2**64), got %r" % (seed,))
+
+        def amps(key, n, per):
+            v = noise.get(key, 0)
+            if isinstance(v, (list, tuple, np.ndarray)):
+                if len(v) != n:
+                    raise ValueError("noise[%r] holds %d values for %d %s" % (key, len(v), n, per))
+                items = [("noise[%r][%d]" % (key, i), x) for i, x in enumerate(v)]
+            else:
+                items = [("noise[%r]" % key, v)] * n
+            for what, x in items:
+                if not whole(x) or not 0 <= x <= 255:
+                    raise ValueError("%s = %r: an amplitude is an integer in [0, 255]" % (what, x))
+            return [int(x) for _, x in items]
+        out = dict(seed=int(seed), amp_s=amps("amp_s", n_starts, "starts"), amp_v=amps("amp_v", n_starts, "starts"),
+                   train_amp_s=amps("train_amp_s", n_routes, "routes"), train_amp_v=amps("train_amp_v", n_routes, "routes"))
+        streams = noise.get("streams")
+        if streams is None:
+            streams = list(range(n_starts))
+        else:
+            if isinstance(streams, (str, dict)) or not hasattr(streams, "__len__") or len(streams) != n_starts:
+                raise ValueError("noise['streams'] must be None or a list with one stream per start (%d), got %r" % (n_starts, streams))
+            streams = list(streams)
+            for i, x in enumerate(streams):
+                if not whole(x) or not 0 <= x < 2 ** 31:
+                    raise ValueError("noise['streams'][%d] = %r: a stream is an integer in [0, 2**31)" % (i, x))
+                if x in streams[:i]:
+                    raise ValueError("noise['streams'][%d] = %d duplicates noise['streams'][%d]: members of one stream would draw the same "
+                                     "noise" % (i, x, streams.index(x)))
+        out["streams"] = [int(x) for x in streams]
+        return out
+
+    def _noise_begin_step(self, idx):
+        """The members `idx` are about to take part in a device step: each gets that step's key (kept for its scene_familiarity) and
+        its count goes up.  Nothing without noise."""
+        if self._noise_seed is None:
+            return
+        for i in idx:
+            a = self.agents[i]
+            a._noise_key = self._step_key(a.noise_stream, a.noise_count)
+            a.noise_count += 1
+
+    def _noise_set_rows(self, agents):
+        """The engine's noise rows become those of `agents`, the members of the device call that follows, under their last keys."""
+        if self._noise_seed is None:
+            return
+        self.engine.noise_rows(self._noise_seed, np.array([a._noise_key for a in agents], dtype=np.uint64),
+                               [a.noise_amp[0] for a in agents], [a.noise_amp[1] for a in agents])
 
     @staticmethod
     def _on_landscape(agent, landscape, sensor=None):
@@ -679,7 +781,7 @@ class _RouteEnsemble(_OneValueEnsemble):
         return out
 
     @classmethod
-    def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host", sensors=None, populations=None):
+    def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host", sensors=None, noise=None, populations=None):
         """Trials that differ in their LANDSCAPE, their training route and their start.  `agent`: an UNTRAINED agent of the ensemble's
         model with the GPU sensor model; landscapes: a list of uint8[rows, cols, 3] of any shapes; routes: a list of
         (landscape_index, float64[n_r, 2]); starts and metrics as from_routes_with.  The landscapes become the engine's landscape set,
@@ -691,9 +793,18 @@ class _RouteEnsemble(_OneValueEnsemble):
         sensor landscape l is sensed with; sensor_dimensions is refused (w × h is the engine's one).  Two sensors on one landscape:
         enter the landscape twice.  The members of a route on landscape l carry that entry's configuration and `sensor_index`, so
         their bounds are their own footprint's and their get_sensor_mat senses under their own entry.
-        populations: as from_routes_with's, an entry per route."""
+        populations: as from_routes_with's, an entry per route.
+        noise: None (the sensor is the deterministic model, and no noise row is ever set), or a dict with any of
+            seed=0, amp_s=0, amp_v=0       recall: an integer amplitude in [0, 255], or a list with one per start
+            train_amp_s=0, train_amp_v=0   the training views: likewise, or a list per route (0: a noiseless memory)
+            streams=None                   None: a start's index; or a list of distinct ints in [0, 2**31), one per start
+        (see the class).  A scene_familiarity read after a step re-senses that step's poses under that step's keys."""
+        starts, routes = list(starts), list(routes)
+        nz = cls._noise_arg(noise, len(starts), len(routes))
+        if nz is not None and populations is not None:
+            raise ValueError("noise with populations: the sensed step under a population table has no noise form")
         lands, points, land_of_route, entries = cls._landscape_args(agent, landscapes, routes, sensors)
-        return cls._from_routes(agent, points, starts, metrics, lands, land_of_route, entries, populations=populations)
+        return cls._from_routes(agent, points, starts, metrics, lands, land_of_route, entries, populations=populations, noise=nz)
 
     @classmethod
     def _landscape_args(cls, agent, landscapes, routes, sensors):
@@ -715,6 +826,8 @@ class _RouteEnsemble(_OneValueEnsemble):
 
     def _device_step(self, idx, xs, ys, angs):
         if self._lands is not None:
+            self._noise_begin_step(idx)
+            self._noise_set_rows([self.agents[i] for i in idx])
             results = getattr(self.engine, self._batch_call)(xs, ys, angs, self._banks[idx], land_of_member=self._lands[idx])
         else:
             results = getattr(self.engine, self._batch_call)(xs, ys, angs, self._banks[idx])
@@ -878,20 +991,22 @@ class InfomaxRouteEnsemble(_RouteEnsemble):
         return cls._from_routes(agent, list(routes), starts, metrics, None, None, networks=networks)
 
     @classmethod
-    def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host", sensors=None, networks=None):
+    def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host", sensors=None, noise=None, networks=None):
         """_RouteEnsemble.from_landscapes; networks: as from_routes_with's, an entry per route."""
+        starts, routes = list(starts), list(routes)
+        nz = cls._noise_arg(noise, len(starts), len(routes))
         lands, points, land_of_route, entries = cls._landscape_args(agent, landscapes, routes, sensors)
-        return cls._from_routes(agent, points, starts, metrics, lands, land_of_route, entries, networks=networks)
+        return cls._from_routes(agent, points, starts, metrics, lands, land_of_route, entries, networks=networks, noise=nz)
 
     @classmethod
-    def _from_routes(cls, agent, routes, starts, metrics, lands, land_of_route, sensors=None, networks=None):
+    def _from_routes(cls, agent, routes, starts, metrics, lands, land_of_route, sensors=None, networks=None, noise=None):
         nets = None
         if networks is not None:
             model = getattr(agent, "familiarity_model", None)
             cls._check_model(model)
             nets = cls._network_entries(agent, model, len(routes), networks)
         ens = super(InfomaxRouteEnsemble, cls)._from_routes(agent, routes, starts, metrics, lands, land_of_route, sensors,
-                                                            table=None if nets is None else dict(networks=nets))
+                                                            table=None if nets is None else dict(networks=nets), noise=noise)
         for a in ens.agents:
             a.network_index = None if nets is None else int(nets[1][a.memory_bank])
             a.network = None if nets is None else {k: v for k, v in nets[0][a.network_index].items() if k != "w0"}
@@ -1134,15 +1249,16 @@ class SadsRouteEnsemble(_WindowedMembers, _RouteEnsemble):
 
     @classmethod
     def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host", chem_weights=None, sensors=None, window=None,
-                        window_centres=None, relocalise_below=None):
-        """_RouteEnsemble.from_landscapes, and chem_weights, window, window_centres and relocalise_below as from_routes_with takes them."""
+                        window_centres=None, relocalise_below=None, noise=None):
+        """_RouteEnsemble.from_landscapes (noise included), and chem_weights, window, window_centres and relocalise_below as
+        from_routes_with takes them.  A windowed ensemble's two calls per step each get their own members' noise rows."""
         starts = list(starts)
         w = cls._weights_arg(chem_weights, starts)
         routes = list(routes)
         lengths = [len(rt[1]) if isinstance(rt, (tuple, list)) and len(rt) == 2 else 0 for rt in routes]
         wins, centres = cls._windows_arg(window, window_centres, starts, lengths)
         thresholds = cls._thresholds_arg(relocalise_below, wins)
-        ens = super(SadsRouteEnsemble, cls).from_landscapes(agent, landscapes, routes, starts, metrics=metrics, sensors=sensors)
+        ens = super(SadsRouteEnsemble, cls).from_landscapes(agent, landscapes, routes, starts, metrics=metrics, sensors=sensors, noise=noise)
         if w is not None:
             ens._set_weights(w)
         ens._set_windows(wins, centres, thresholds)
@@ -1158,7 +1274,9 @@ class SadsRouteEnsemble(_WindowedMembers, _RouteEnsemble):
         lands = None if self._lands is None else self._lands[idx]
         self._step_windows = {id(self.agents[i]): w for i, w in zip(idx, wins)}
         ks = [k for k, w in enumerate(wins) if w is not None]
+        self._noise_begin_step(idx)
         if not ks:
+            self._noise_set_rows([self.agents[i] for i in idx])
             results = self.engine.rviews_sense_step(xs, ys, angs, self._banks[idx], self._weights[idx], land_of_member=lands)
         else:
             xs, ys, angs = np.asarray(xs, dtype=np.float64), np.asarray(ys, dtype=np.float64), np.asarray(angs, dtype=np.float64)
@@ -1166,9 +1284,11 @@ class SadsRouteEnsemble(_WindowedMembers, _RouteEnsemble):
             rest = [k for k, w in enumerate(wins) if w is None]
             taus = [getattr(self.agents[idx[k]], "relocalise_below", None) for k in ks]
             more = {} if all(t is None for t in taus) else dict(reloc_below=np.array([-np.inf if t is None else t for t in taus]))
+            self._noise_set_rows([self.agents[idx[k]] for k in ks])
             parts = [(ks, self.engine.rvwin_sense_step(xs[ks], ys[ks], angs[ks], banks[ks], weights[ks], [wins[k][0] for k in ks],
                                                        [wins[k][1] for k in ks], land_of_member=None if lands is None else lands[ks], **more))]
             if rest:
+                self._noise_set_rows([self.agents[idx[k]] for k in rest])
                 parts.append((rest, self.engine.rviews_sense_step(xs[rest], ys[rest], angs[rest], banks[rest], weights[rest],
                                                                   land_of_member=None if lands is None else lands[rest])))
             n, A = angs.shape
@@ -1186,6 +1306,7 @@ class SadsRouteEnsemble(_WindowedMembers, _RouteEnsemble):
             return
         st = [a._scene_stale for a in todo]
         lands = None if self._lands is None else [a.landscape_index for a in todo]
+        self._noise_set_rows(todo)                                # (the scene of the patches the last step scored: its keys)
         rows = self.engine.rviews_scene([t[0] for t in st], [t[1] for t in st], np.stack([t[2] for t in st]), [a.memory_bank for a in todo],
                                         [t[3] for t in st], land_of_member=lands)
         for a, row, t in zip(todo, rows, st):
@@ -1289,13 +1410,14 @@ class SsdRouteEnsemble(_WindowedMembers, _RouteEnsemble):
 
     @classmethod
     def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host", sensors=None, window=None, window_centres=None,
-                        relocalise_below=None):
-        """_RouteEnsemble.from_landscapes, and window, window_centres and relocalise_below as from_routes_with takes them."""
+                        relocalise_below=None, noise=None):
+        """_RouteEnsemble.from_landscapes (noise included), and window, window_centres and relocalise_below as from_routes_with takes
+        them."""
         starts, routes = list(starts), list(routes)
         lengths = [len(rt[1]) if isinstance(rt, (tuple, list)) and len(rt) == 2 else 0 for rt in routes]
         wins, centres = cls._windows_arg(window, window_centres, starts, lengths)
         thresholds = cls._thresholds_arg(relocalise_below, wins)
-        ens = super(SsdRouteEnsemble, cls).from_landscapes(agent, landscapes, routes, starts, metrics=metrics, sensors=sensors)
+        ens = super(SsdRouteEnsemble, cls).from_landscapes(agent, landscapes, routes, starts, metrics=metrics, sensors=sensors, noise=noise)
         ens._set_windows(wins, centres, thresholds)
         return ens
 
@@ -1309,7 +1431,9 @@ class SsdRouteEnsemble(_WindowedMembers, _RouteEnsemble):
         lands = None if self._lands is None else self._lands[idx]
         self._step_windows = {id(self.agents[i]): w for i, w in zip(idx, wins)}
         ks = [k for k, w in enumerate(wins) if w is not None]
+        self._noise_begin_step(idx)
         if not ks:
+            self._noise_set_rows([self.agents[i] for i in idx])
             results = self.engine.rvssd_sense_step(xs, ys, angs, self._banks[idx], self.channel, land_of_member=lands)
         else:
             xs, ys, angs = np.asarray(xs, dtype=np.float64), np.asarray(ys, dtype=np.float64), np.asarray(angs, dtype=np.float64)
@@ -1317,9 +1441,11 @@ class SsdRouteEnsemble(_WindowedMembers, _RouteEnsemble):
             rest = [k for k, w in enumerate(wins) if w is None]
             taus = [getattr(self.agents[idx[k]], "relocalise_below", None) for k in ks]
             more = {} if all(t is None for t in taus) else dict(reloc_below=np.array([-np.inf if t is None else t for t in taus]))
+            self._noise_set_rows([self.agents[idx[k]] for k in ks])
             parts = [(ks, self.engine.rvssdw_sense_step(xs[ks], ys[ks], angs[ks], banks[ks], [wins[k][0] for k in ks], [wins[k][1] for k in ks],
                                                         self.channel, land_of_member=None if lands is None else lands[ks], **more))]
             if rest:
+                self._noise_set_rows([self.agents[idx[k]] for k in rest])
                 parts.append((rest, self.engine.rvssd_sense_step(xs[rest], ys[rest], angs[rest], banks[rest], self.channel,
                                                                  land_of_member=None if lands is None else lands[rest])))
             n, A = angs.shape
@@ -1337,6 +1463,7 @@ class SsdRouteEnsemble(_WindowedMembers, _RouteEnsemble):
             return
         st = [a._scene_stale for a in todo]
         lands = None if self._lands is None else [a.landscape_index for a in todo]
+        self._noise_set_rows(todo)                                # (the scene of the patches the last step scored: its keys)
         rows = self.engine.rvssd_scene([t[0] for t in st], [t[1] for t in st], np.stack([t[2] for t in st]), [a.memory_bank for a in todo],
                                        self.channel, land_of_member=lands)
         for a, row, t in zip(todo, rows, st):

@@ -2,7 +2,7 @@
 """Times the Infomax familiarity model (navsim_amd.infomax_familiarity; include/dejavu.h: dv_infomax_*) on GPU 0 and writes
 profiles/infomax_time.json.
 
-    python tools/infomax_time.py [--sides 32,64] [--views 400] [--calls 200] [--reps 5] [--blocks single,ensemble[,banks][,lands][,sensors][,networks]]
+    python tools/infomax_time.py [--sides 32,64] [--views 400] [--calls 200] [--reps 5] [--blocks single,ensemble[,banks][,lands][,sensors][,networks][,noise]]
                                  [--out profiles/infomax_time.json]
 
 Per sensor side s (views of s x s, N = M = s*s): microseconds per training view (a dv_infomax_train_u8 call over --views views, the
@@ -403,7 +403,7 @@ def main():
                     help="the rule must stay finite on the tool's 5-level noise views: 0.01 overflows at 64x64 (the time does not depend on it)")
     ap.add_argument("--limit", type=int, default=240, help="seconds allowed to each GPU child")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "infomax_time.json"))
-    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and score_u8), ensemble, banks, lands, sensors (tools/sensors_block.py: dv_lands_ibank_sense_step without a sensor table, with one of equal entries and with one of four different entries), networks (tools/networks_block.py: network tables against the banked step without one)")
+    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and score_u8), ensemble, banks, lands, sensors (tools/sensors_block.py: dv_lands_ibank_sense_step without a sensor table, with one of equal entries and with one of four different entries), networks (tools/networks_block.py: network tables against the banked step without one), noise (tools/noise_block.py: dv_lands_ibank_sense_step without noise rows, under rows of zero amplitude and of amplitude 20, and with the rows set again before every step)")
     ap.add_argument("--route-views", type=int, default=200, help="sensed views of each of the banks block's 4 routes")
     ap.add_argument("--banks-child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--lands-child", type=int, default=0, help=argparse.SUPPRESS)
@@ -425,12 +425,12 @@ def main():
         return 0
     blocks = args.blocks.split(",")
     result = dict(tool="tools/infomax_time.py", timer="hipEvent pair (dv_timer_start/stop), median of %d windows after a warm-up" % args.reps,
-                  learning_rate=args.learning_rate, blocks=blocks, sizes=[], ensembles=[], banks=[], lands=[], sensors=[], networks=[])
+                  learning_rate=args.learning_rate, blocks=blocks, sizes=[], ensembles=[], banks=[], lands=[], sensors=[], networks=[], noise=[])
     if os.path.exists(args.out):                                  # a block that is not measured keeps its rows
         with open(args.out) as f:
             kept = json.load(f)
         for block, key in (("single", "sizes"), ("ensemble", "ensembles"), ("banks", "banks"), ("lands", "lands"), ("sensors", "sensors"),
-                           ("networks", "networks")):
+                           ("networks", "networks"), ("noise", "noise")):
             if block not in blocks:
                 result[key] = kept.get(key, [])
         result["blocks"] = [b for b in kept.get("blocks", []) if b not in blocks] + blocks      # (every block whose rows the file holds)
@@ -458,6 +458,12 @@ def main():
         if rc != 0:
             return rc
         result["sensors"].append(row)
+    if "noise" in blocks:
+        import noise_block
+        rc, row = noise_block.run_child(args.limit, [int(x) for x in args.sides.split(",")], args.ensemble_calls, args.reps, "infomax")
+        if rc != 0:
+            return rc
+        result["noise"].append(row)
     for side in [int(x) for x in args.sides.split(",")] if "networks" in blocks else []:
         import networks_block
         rc, row = networks_block.run_child(args.limit, side, args.route_views, args.ensemble_calls, args.reps)

@@ -2,7 +2,7 @@
 """Times the mushroom-body familiarity model (navsim_amd.mushroom_familiarity; include/dejavu.h: dv_mb_*) on GPU 0 and writes
 profiles/mushroom_time.json.
 
-    python tools/mushroom_time.py [--sides 32,64] [--views 1000] [--calls 200] [--reps 5] [--blocks single,ensemble[,banks][,metrics][,lands][,rows][,sensors][,populations]]
+    python tools/mushroom_time.py [--sides 32,64] [--views 1000] [--calls 200] [--reps 5] [--blocks single,ensemble[,banks][,metrics][,lands][,rows][,sensors][,populations][,noise]]
                                   [--out profiles/mushroom_time.json]
 
 Per sensor side s (views of s x s) with K = 20000 Kenyon cells, fan-in 10 and 200 firing cells: microseconds per agent step
@@ -44,6 +44,10 @@ dv_mb_train_from_poses calls on four engines (the sum of their timers, and wall 
 Sensors block (--blocks sensors): the lands block's 32 x 32 layouts stepped by dv_lands_mbank_sense_step on the set without a sensor
 table, with a table of four entries equal to the engine's sensor, and with a table of four different entries, in alternating windows
 of one process (tools/sensors_block.py, which states the figures).
+
+Noise block (--blocks noise): per side, the lands block's layouts stepped by dv_lands_mbank_sense_step without noise rows, under rows of
+zero amplitude, under rows of amplitude 20, and with the rows set again before every step as a route ensemble sets them, in
+alternating windows of one process (tools/noise_block.py, which states the figures).
 
 Rows block (--blocks rows): the metrics block's MushroomRouteEnsemble with metrics="device" (4 routes x 8 members, both route sizes),
 stepped --row-frames frames; then the three coverage columns of all members' result rows built two ways in alternating windows of the
@@ -546,7 +550,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--limit", type=int, default=240, help="seconds allowed to each GPU child")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mushroom_time.json"))
-    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and the agent step), ensemble, banks, metrics, lands, rows, sensors, populations")
+    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and the agent step), ensemble, banks, metrics, lands, rows, sensors, populations, noise")
     ap.add_argument("--ensemble-calls", type=int, default=30, help="ensemble steps per timed window")
     ap.add_argument("--child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--ensemble-child", type=int, default=0, help=argparse.SUPPRESS)
@@ -576,12 +580,12 @@ def main():
         return 0
     blocks = args.blocks.split(",")
     result = dict(tool="tools/mushroom_time.py", timer="hipEvent pair (dv_timer_start/stop), median of %d windows after a warm-up" % args.reps,
-                  sizes=[], ensembles=[], banks=[], metrics=[], lands=[], rows=[], sensors=[], populations=[])
+                  sizes=[], ensembles=[], banks=[], metrics=[], lands=[], rows=[], sensors=[], populations=[], noise=[])
     if os.path.exists(args.out):                                  # a block that is not measured keeps its rows
         with open(args.out) as f:
             kept = json.load(f)
         for block, key in (("single", "sizes"), ("ensemble", "ensembles"), ("banks", "banks"), ("metrics", "metrics"), ("lands", "lands"), ("rows", "rows"),
-                           ("sensors", "sensors"), ("populations", "populations")):
+                           ("sensors", "sensors"), ("populations", "populations"), ("noise", "noise")):
             if block not in blocks:
                 result[key] = kept.get(key, [])
     for side in [int(x) for x in args.sides.split(",")] if "ensemble" in blocks else []:
@@ -614,6 +618,12 @@ def main():
         if rc != 0:
             return rc
         result["sensors"].append(row)
+    if "noise" in blocks:
+        import noise_block
+        rc, row = noise_block.run_child(args.limit, [int(x) for x in args.sides.split(",")], args.ensemble_calls, args.reps, "mushroom")
+        if rc != 0:
+            return rc
+        result["noise"].append(row)
     for side in [int(x) for x in args.sides.split(",")] if "populations" in blocks else []:
         import populations_block
         rc, row = populations_block.run_child(args.limit, side, args.views, args.ensemble_calls, args.reps)

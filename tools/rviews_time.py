@@ -2,7 +2,7 @@
 """Times a step of the route view store (dv_rviews_sense_step, navsim_amd.SadsRouteEnsemble) at a slice of the reference's grid and
 writes profiles/rviews_time.json.
 
-    python tools/rviews_time.py [--sides 32,64] [--calls 30] [--reps 5] [--blocks routes[,sensors][,window][,reloc][,ssd][,ssdwin]] [--out profiles/rviews_time.json]
+    python tools/rviews_time.py [--sides 32,64] [--calls 30] [--reps 5] [--blocks routes[,sensors][,noise][,window][,reloc][,ssd][,ssdwin]] [--out profiles/rviews_time.json]
 
 Shape: 4 routes x 8 starts x 10 headings = 32 trials of 320 columns, views of side x side.  The routes have the grid's length:
 synth.sin_training_path with arclen = step_size / n_test_angles (scripts/run_experiment.py:207) on a 900 x 900 landscape, one curve
@@ -22,6 +22,10 @@ Sensors block (--blocks sensors): dv_rviews_sense_step with a landscape per memb
 with a table of four entries equal to the engine's sensor and with a table of four different entries, in alternating windows of one
 process (tools/sensors_block.py, which states the shape and the figures); its rows are the file's "sensors".  A block that is not
 measured keeps its rows.
+
+Noise block (--blocks noise): dv_rviews_sense_step on the same set without noise rows, under rows of zero amplitude, under rows of
+amplitude 20, and with the rows set again before every step as a route ensemble sets them, in alternating windows of one process
+(tools/noise_block.py, which states the shape and the figures); its rows are the file's "noise".
 
 Window block (--blocks window): the same slice with every member under a temporal window (dv_rvwin_sense_step: one fused scoring
 launch), WINDOWS = (50, 50) and (255, 256) centred on each pose's nearest route point, against the unwindowed dv_rviews_sense_step at
@@ -496,8 +500,8 @@ def main():
     ap.add_argument("--calls", type=int, default=30)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rviews_time.json"))
-    ap.add_argument("--blocks", default="routes", help="which blocks to measure: routes (the routed step against four engines), sensors, window, reloc, ssd, ssdwin")
-    ap.add_argument("--limit", type=int, default=240, help="seconds allowed to the sensors block's GPU child")
+    ap.add_argument("--blocks", default="routes", help="which blocks to measure: routes (the routed step against four engines), sensors, noise, window, reloc, ssd, ssdwin")
+    ap.add_argument("--limit", type=int, default=240, help="seconds allowed to the GPU child of the sensors block and of the noise block")
     args = ap.parse_args()
     blocks = args.blocks.split(",")
     kept = {}
@@ -511,31 +515,38 @@ def main():
         if rc != 0:
             return rc
         sensors = [row]
+    noise = kept.get("noise", [])
+    if "noise" in blocks:                                         # (a child of its own, as the sensors block's)
+        import noise_block
+        rc, row = noise_block.run_child(args.limit, [int(s) for s in args.sides.split(",")], args.calls, args.reps, "rviews")
+        if rc != 0:
+            return rc
+        noise = [row]
     rows = [measure(int(s), args.calls, args.reps) for s in args.sides.split(",")] if "routes" in blocks else kept.get("sizes", [])
     import torch                                                  # (after the windows: only to ask the device its name)
     doc = dict(tool="tools/rviews_time.py", device=torch.cuda.get_device_name(0), step_form="step_forward(fake=True)", note="medians of alternating windows in one process; wall-clock figures "
-               "include the host's share of a step", sizes=rows, sensors=sensors)
+               "include the host's share of a step", sizes=rows, sensors=sensors, noise=noise)
     if "window" in blocks:                                        # a key of its own: the keys that were there stay as they were
-        doc = dict(doc if ("routes" in blocks or "sensors" in blocks or not kept) else kept, window=dict(device=torch.cuda.get_device_name(0), windows=[list(w) for w in WINDOWS],
+        doc = dict(doc if ("routes" in blocks or "sensors" in blocks or "noise" in blocks or not kept) else kept, window=dict(device=torch.cuda.get_device_name(0), windows=[list(w) for w in WINDOWS],
                                             sizes=[measure_window(int(s), args.calls, args.reps) for s in args.sides.split(",")]))
     elif "window" in kept:
         doc["window"] = kept["window"]
     if "reloc" in blocks:                                         # a key of its own, as the window block's
-        if not ({"routes", "sensors", "window"} & set(blocks)) and kept:
+        if not ({"routes", "sensors", "noise", "window"} & set(blocks)) and kept:
             doc = dict(kept)
         doc["reloc"] = dict(device=torch.cuda.get_device_name(0), window=list(RELOC_WINDOW),
                             sizes=[measure_reloc(int(s), args.calls, args.reps) for s in args.sides.split(",")])
     elif "reloc" in kept:
         doc["reloc"] = kept["reloc"]
     if "ssd" in blocks:                                           # a key of its own, as the window block's
-        if not ({"routes", "sensors", "window", "reloc"} & set(blocks)) and kept:
+        if not ({"routes", "sensors", "noise", "window", "reloc"} & set(blocks)) and kept:
             doc = dict(kept)
         doc["ssd"] = dict(device=torch.cuda.get_device_name(0), channel=SSD_CHANNEL,
                           sizes=[measure_ssd(int(s), args.calls, args.reps) for s in args.sides.split(",")])
     elif "ssd" in kept:
         doc["ssd"] = kept["ssd"]
     if "ssdwin" in blocks:                                        # a key of its own, as the window block's
-        if not ({"routes", "sensors", "window", "reloc", "ssd"} & set(blocks)) and kept:
+        if not ({"routes", "sensors", "noise", "window", "reloc", "ssd"} & set(blocks)) and kept:
             doc = dict(kept)
         doc["ssdwin"] = dict(device=torch.cuda.get_device_name(0), channel=SSD_CHANNEL, windows=[list(w) for w in SSDWIN_WINDOWS],
                              sizes=[measure_ssdwin(int(s), args.calls, args.reps) for s in args.sides.split(",")])

@@ -765,6 +765,35 @@ int dv_mbpop_clear(dv_ctx *ctx);
 int dv_mbpop_info(dv_ctx *ctx, int *n_pops, int *n_banks, int32_t *n_kc, int32_t *fan_in, int32_t *n_active, int32_t *channel,
                   int32_t *population_of_bank, int64_t *views_trained, int64_t *n_depressed, int64_t *bytes);
 
+/* ---- mushroom-body bank sets ------------------------------------------------ */
+/*
+ * One selection of firing cells read out through several banks.  A member i of a step carries a set of set_size entries,
+ * 1 <= set_size <= DV_MBSET_MAX_BANKS: banks[i][j] in [0, n_banks) (a bank may occur twice) and an int32 coefs[i][j].  For a column
+ * (i, a) with fired set F (the model's own selection, unchanged)
+ *     d_j = #{k in F : weight of bank banks[i][j] at k is 1},   v = sum_j coefs[i][j] * d_j,   angle_fam[i][a] = (double)(-v)
+ * best_heading[i] is the first maximum of angle_fam[i] (the larger value, then the lower heading); a member with a footprint off its
+ * landscape gets best_heading -1 and DV_RES_SENSE_ERROR, as in the banked step.  bank_novelty (may be NULL) receives
+ * int32[n_agents][n_headings][set_size], the d_j.  Opponent memories are banks {attractive, repulsive} with coefs {1, -gain}; a
+ * capacity read-out is one member with eight prefix banks and bank_novelty.
+ * Checks, all before anything reaches the device: set_size; every banks entry (DV_ERR_INVALID names it); and a member with
+ * sum_j |coefs[i][j]| * n_active > 2^31 - 1 (DV_ERR_INVALID names the member: v could wrap).  One enqueue and one wait, launches as the
+ * banked step's; tables are uploaded only when the device does not hold them already.
+ *   dv_mbset_step_u8            uploaded planes uint8[n_agents][n_headings][h][w]
+ *   dv_mbset_sense_step         sensed on the context's one landscape (refused under live noise rows, as dv_mbank_sense_step)
+ *   dv_mbset_lands_sense_step   member i sensed on landscape land_of_member[i] of the set, under the set's sensor table and live noise
+ *                               rows where there are any
+ * DV_ERR_STATE without a model, and while a population table is live: banks of different populations share no selection (not built).
+ */
+#define DV_MBSET_MAX_BANKS 8
+int dv_mbset_step_u8(dv_ctx *ctx, const uint8_t *planes, int n_agents, int n_headings, int set_size, const int32_t *banks,
+                     const int32_t *coefs, double *angle_fam, int32_t *best_heading, int32_t *bank_novelty);
+int dv_mbset_sense_step(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings, int set_size,
+                        const int32_t *banks, const int32_t *coefs, double *angle_fam, int32_t *best_heading, uint32_t *flags,
+                        int32_t *bank_novelty);
+int dv_mbset_lands_sense_step(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
+                              int set_size, const int32_t *banks, const int32_t *coefs, const int32_t *land_of_member, double *angle_fam,
+                              int32_t *best_heading, uint32_t *flags, int32_t *bank_novelty);
+
 /* ---- Infomax weight banks --------------------------------------------------- */
 /*
  * Several Infomax models of one shape and one learning rate in ONE context: the weights are float64[n_banks][n_hidden][h * w], bank b

@@ -379,6 +379,10 @@ struct dv_ctx {
     int mb_banks = 1;                         // memories that share the connectivity (dv_mbank_set; 1 after dv_mb_begin)
     std::vector<int64_t> mb_views = std::vector<int64_t>(1, 0);   // [mb_banks]: views trained on since dv_mb_begin / dv_mbank_set
     MirroredTable mb_bank_of;                 // a banked call's table of ints: the bank of every view, or of every member
+    // bank sets (dejavu_mbset.inl: dv_mbset_*): a member read out through several banks from one selection
+    int* mbs_d = nullptr;                     // [C][S]: novelty per column and bank of the set
+    size_t mbs_d_cap = 0;                     // bytes
+    MirroredTable mbs_banks, mbs_coefs;       // a set call's tables of ints, [members][S] each
     // population table of the model (dejavu_mbpop.inl: dv_mbpop_*): the banks' own cells, wiring, quota and channel; mbp_pops == 0: none,
     // and mb_wt is [mb_banks][mb_K].  Live: mb_wt is ragged, bank b at mbp_wt_off[b], and mb_conn (the begin's wiring) is not read.
     int mbp_pops = 0;
@@ -3855,6 +3859,7 @@ extern "C" int dv_stream_read_gbps(dv_ctx* c, int64_t n_bytes, int iters, double
 #include "dejavu_inet.inl"      // dv_inet_*: network tables, a bank's own n_hidden, learning rate, W0 and channel (kernels and host side)
 #include "dejavu_mushroom.inl"  // dv_mb_*: the mushroom-body familiarity model (kernels and host side)
 #include "dejavu_mbpop.inl"     // dv_mbpop_*: population tables, a bank's own cells, wiring and channel (kernels and host side)
+#include "dejavu_mbset.inl"     // dv_mbset_*: bank sets, a member read out through several banks from one selection (kernels and host side)
 #include "dejavu_path_routes.inl"   // dv_path_routes_*: the error / coverage metrics against several routes (host side)
 #include "dejavu_marks.inl"     // dv_marks_*: the coverage statistics of a result row, from the marks on the device (kernel and host side)
 #include "dejavu_group.inl"     // dv_group_*: one process, several devices -- host logic above the C ABI

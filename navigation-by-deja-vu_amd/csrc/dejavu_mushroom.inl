@@ -41,11 +41,22 @@
 // wt is then ragged, and the banked host paths below (mb_launch_bank, mb_batch's sensed launch, the banks' weights and counts) hand
 // over to k_mbpop_*, which are mb_view on a per-bank descriptor.  The kernels of this file are launched only without a table, and
 // the calls that assume this file's one wiring behind bank 0 are refused while one is live (mb_need_bank0).
+//
+// Bank sets (dejavu_mbset.inl).  MODE kMbSet is mb_view's fourth read-out: a firing cell adds wt_j[k] for each of the S banks of the
+// workgroup's member (MbSetWts: S pointers, the same for every thread), and d receives S counts a view.  The selection is the code
+// above it, unchanged; k_mbset<SRC> and k_mbset_decide are in that file.
 namespace dv {
 
-static constexpr int kMbTrain = 0, kMbScore = 1, kMbMask = 2;
+static constexpr int kMbTrain = 0, kMbScore = 1, kMbMask = 2, kMbSet = 3;
 static constexpr int kMbWaves = 4;
 static constexpr int kMbMaxFanIn = 16;
+static constexpr int kMbSetMax = DV_MBSET_MAX_BANKS;
+
+// kMbSet's read-out (dejavu_mbset.inl): the weights of the S banks of the workgroup's member, the same for every thread of it.
+struct MbSetWts {
+    const unsigned char* w[kMbSetMax];                       // (entries from S on: not read)
+    int S;
+};
 
 __device__ __forceinline__ int mb_activity(const unsigned char* __restrict__ plane, const unsigned short* __restrict__ conn, int K, int c, int k) {
     // All kMbMaxFanIn index loads are issued together and then all the gathers: one global and one LDS latency per cell instead of c of
@@ -64,12 +75,12 @@ __device__ __forceinline__ int mb_activity(const unsigned char* __restrict__ pla
 
 // One view of a launch, whatever its source: `fill(plane, tid)` puts the view's N bytes into the LDS plane (no barrier needed after
 // it), then histogram, threshold, rank arithmetic and pass 2.  lds: the workgroup's dynamic LDS, [N rounded up to 4] plane bytes,
-// [kMbWaves][nb] histogram words (nb = 255 c + 1), then 16 words of hand-over.
-// d: [views] (kMbScore); fired: [views][K], thr: [views] (kMbMask; either may be nullptr).
+// [kMbWaves][nb] histogram words (nb = 255 c + 1), then 16 words of hand-over (kMbSet: and [kMbWaves][kMbSetMax] wave totals).
+// d: [views] (kMbScore), [views][set.S] (kMbSet); fired: [views][K], thr: [views] (kMbMask; either may be nullptr).
 template <int MODE, class Fill>
 __device__ __forceinline__ void mb_view(unsigned* lds, Fill fill, int view, int N, const unsigned short* __restrict__ conn, int K, int c, int n_active,
                                         unsigned char* __restrict__ wt, int* __restrict__ d, unsigned char* __restrict__ fired,
-                                        int* __restrict__ thr) {
+                                        int* __restrict__ thr, const MbSetWts& set = MbSetWts{}) {
     const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int nb = 255 * c + 1;
     unsigned char* plane = reinterpret_cast<unsigned char*>(lds);
@@ -120,6 +131,7 @@ __device__ __forceinline__ void mb_view(unsigned* lds, Fill fill, int view, int 
     const unsigned q = hand[5];
     unsigned rank0 = hand[6 + wave];                          // equals before this trip's cells
     int acc = 0;
+    int accs[kMbSetMax] = {};                                 // kMbSet: one per bank of the set, every index a constant (registers)
     for (int base = k0; base < k1; base += 64) {
         const int k = base + lane;
         const bool in = k < k1;
@@ -134,6 +146,12 @@ __device__ __forceinline__ void mb_view(unsigned* lds, Fill fill, int view, int 
             if (fire) wt[k] = 0;
         } else if (MODE == kMbScore) {
             if (fire) acc += (int)wt[k];
+        } else if (MODE == kMbSet) {
+            if (fire) {
+#pragma unroll
+                for (int j = 0; j < kMbSetMax; ++j)
+                    if (j < set.S) accs[j] += (int)set.w[j][k];   // (S is the workgroup's: no lane diverges here)
+            }
         } else if (in && fired) {
             fired[(size_t)view * (size_t)K + k] = fire ? 1 : 0;
         }
@@ -143,6 +161,20 @@ __device__ __forceinline__ void mb_view(unsigned* lds, Fill fill, int view, int 
         if (lane == 0) hand[10 + wave] = (unsigned)acc;
         __syncthreads();
         if (tid == 0) d[view] = (int)(hand[10] + hand[11] + hand[12] + hand[13]);
+    }
+    if (MODE == kMbSet) {
+        unsigned* tot = hand + 16;                            // [kMbWaves][kMbSetMax]
+#pragma unroll
+        for (int j = 0; j < kMbSetMax; ++j)
+            if (j < set.S) {
+                int a = accs[j];
+                for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off);
+                if (lane == 0) tot[wave * kMbSetMax + j] = (unsigned)a;
+            }
+        __syncthreads();
+        if (tid < set.S)
+            d[(size_t)view * (size_t)set.S + tid] =
+                (int)(tot[tid] + tot[kMbSetMax + tid] + tot[2 * kMbSetMax + tid] + tot[3 * kMbSetMax + tid]);
     }
     if (MODE == kMbMask && thr && tid == 0) thr[view] = t;
 }
@@ -223,21 +255,10 @@ __global__ __launch_bounds__(kMbWaves * 64) void k_mb_pose_bank(const unsigned c
                       (int)blockIdx.x, N, conn, K, c, n_active, mb_bank(wt, K, bank_of, col0, per), d, nullptr, nullptr);
 }
 
-// One workgroup per member i of A columns: fam[i][a] = (double)(-d[i A + a]); best[i] = the member's first maximum (the larger value,
-// the lower heading of equals, whichever thread held it).  perr (nullptr: the planes were uploaded) holds k_mb_pose's word per column:
-// a member with one set gets best -1 and kResSenseError.
-__global__ __launch_bounds__(256) void k_mb_decide_batch(const int* __restrict__ d, const int* __restrict__ perr, int A, double* __restrict__ fam,
-                                                         int* __restrict__ best, unsigned* __restrict__ flags) {
+// The member's decision from its 256 threads' own first maxima (bi < 0: the thread saw no heading) and error words.
+__device__ __forceinline__ void mb_decide_member(int bv, int bi, int bad, int* __restrict__ best, unsigned* __restrict__ flags) {
     __shared__ int sv[256], si[256], sb[256];
     const int tid = (int)threadIdx.x;
-    const size_t col0 = (size_t)blockIdx.x * (size_t)A;
-    int bv = 0, bi = -1, bad = 0;
-    for (int a = tid; a < A; a += 256) {                      // headings in rising order: a later equal does not replace
-        const int v = -d[col0 + a];
-        fam[col0 + a] = (double)v;
-        if (bi < 0 || v > bv) { bv = v; bi = a; }
-        if (perr) bad |= perr[col0 + a];
-    }
     sv[tid] = bv; si[tid] = bi; sb[tid] = bad;
     __syncthreads();
     for (int st = 128; st > 0; st >>= 1) {
@@ -252,6 +273,23 @@ __global__ __launch_bounds__(256) void k_mb_decide_batch(const int* __restrict__
         best[blockIdx.x] = sb[0] ? -1 : si[0];
         flags[blockIdx.x] = sb[0] ? kResSenseError : 0u;
     }
+}
+
+// One workgroup per member i of A columns: fam[i][a] = (double)(-d[i A + a]); best[i] = the member's first maximum (the larger value,
+// the lower heading of equals, whichever thread held it).  perr (nullptr: the planes were uploaded) holds k_mb_pose's word per column:
+// a member with one set gets best -1 and kResSenseError.
+__global__ __launch_bounds__(256) void k_mb_decide_batch(const int* __restrict__ d, const int* __restrict__ perr, int A, double* __restrict__ fam,
+                                                         int* __restrict__ best, unsigned* __restrict__ flags) {
+    const int tid = (int)threadIdx.x;
+    const size_t col0 = (size_t)blockIdx.x * (size_t)A;
+    int bv = 0, bi = -1, bad = 0;
+    for (int a = tid; a < A; a += 256) {                      // headings in rising order: a later equal does not replace
+        const int v = -d[col0 + a];
+        fam[col0 + a] = (double)v;
+        if (bi < 0 || v > bv) { bv = v; bi = a; }
+        if (perr) bad |= perr[col0 + a];
+    }
+    mb_decide_member(bv, bi, bad, best, flags);
 }
 
 // k_mb_pose_bank on a landscape set: the workgroup's column senses its member's own landscape (land_of_column).
@@ -355,12 +393,16 @@ static int mbpop_launch_bank(dv_ctx* c, int mode, const unsigned char* d_src, lo
                              const int* d_bank_of, long long col0, int per);
 static int mbpop_launch_pose(dv_ctx* c, bool on_lands, long long c0, int nc, int A);
 static int mbpop_count(dv_ctx* c);
+// Bank sets (dejavu_mbset.inl, which follows too): a member read out through several banks from one selection.
+static void mbset_free(dv_ctx* c);
+static hipError_t mbset_lds_cap();
 
 static void mb_free(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
     F(c->mb_conn); F(c->mb_wt); F(c->mb_d); F(c->mb_fired); F(c->mb_zeros); F(c->mb_bd); F(c->mb_berr); F(c->mb_res.dev);
     c->mb_d_cap = c->mb_fired_cap = c->mb_bd_cap = c->mb_berr_cap = c->mb_res.cap = 0;
     table_free(c->mb_bank_of);
+    mbset_free(c);
     mbpop_drop(c);
     c->mb_K = c->mb_N = c->mb_c = c->mb_active = c->mb_hh = c->mb_ww = 0;
     c->mb_banks = 1;
@@ -482,6 +524,7 @@ extern "C" int dv_mb_begin(dv_ctx* c, int h, int w, int channel, int n_kc, int f
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_pose_bank_lands_noise, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_mb_pose_bank_lands_sensors_noise, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e == hipSuccess) e = mbpop_lds_cap(lds);
+    if (e == hipSuccess) e = mbset_lds_cap();
     if (e == hipSuccess) e = hipMemcpyAsync(c->mb_conn, ct.data(), ct.size() * sizeof(unsigned short), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->mb_wt, 1, K, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);           // `ct` is this call's

@@ -25,6 +25,7 @@ DV_FORM_BODY_BITS = 5
 DV_FORM_BODY_NAMES = "Ring Ring2 RingA RingB Lc LcShort LcCode LcReg LcRegCode LcRegCode8 Lc2Tiles Lc2TilesCode Lc22".split()
 DV_RVIEWS_EXACT = 1
 DV_RES_RELOCALISED = 32                  # dv_rvreloc_*: the member's row is the whole-route step's (its window's best lay below its threshold)
+DV_MBSET_MAX_BANKS = 8                   # banks of a member's set in dv_mbset_* at most
 DV_RVWIN_MAX_VIEWS = 512                 # views of a window of dv_rvwin_* at most
 DV_DIFFUSE_AUTO = 0
 DV_DIFFUSE_PLAIN = 1
@@ -280,6 +281,11 @@ PROTOTYPES = {
     "dv_mbpop_clear": (ctypes.c_int, [_ctx_p]),
     "dv_mbpop_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _i32p, _i32p, _i32p, _i32p, _i32p,
                                      ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "dv_mbset_step_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _i32p, _f64p, _i32p, _i32p]),
+    "dv_mbset_sense_step": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _i32p, _f64p, _i32p,
+                                           _u32p, _i32p]),
+    "dv_mbset_lands_sense_step": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _i32p, _i32p,
+                                                 _f64p, _i32p, _u32p, _i32p]),
     "dv_inet_set": (ctypes.c_int, [_ctx_p, ctypes.c_int, _i32p, _f64p, _i32p, _f64p, ctypes.c_int, _i32p]),
     "dv_inet_clear": (ctypes.c_int, [_ctx_p]),
     "dv_inet_info": (ctypes.c_int, [_ctx_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _i32p, _f64p, _i32p, _i32p,

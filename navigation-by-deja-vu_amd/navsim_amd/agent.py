@@ -152,6 +152,7 @@ class NavBySceneFamiliarity(object):
 
     chem_weight = None              # a NavEnsemble member's own weight (NavEnsemble.from_agent(chem_weights=...)); None: the model's
     memory_bank = None              # a route ensemble's member: its own bank of the shared mushroom-body or Infomax model; None: the model's one
+    repulsive_bank = None           # ... made with MushroomRouteEnsemble's opponent=: the bank of its route's repulsive memory; None: one memory
     landscape_index = None          # ... made by from_landscapes: its landscape's place in the engine's landscape set; None: the engine's one
     sensor_index = None             # ... made by from_landscapes(sensors=...): its entry of the set's sensor table (its landscape's); None: the engine's one sensor
 

@@ -90,6 +90,15 @@ class RouteSsdResults(RouteViewResults):
         self.angle_ssd = angle_ssd
 
 
+class MbSetBatchResults(OneValueBatchResults):
+    """A bank-set step of the mushroom-body model (dv_mbset_step_u8 / dv_mbset_sense_step / dv_mbset_lands_sense_step):
+    OneValueBatchResults and bank_novelty[n, A, S] (int32), the column's novelty under each bank of its member's set."""
+
+    def __init__(self, angle_familiarity, best_idex, flags, bank_novelty):
+        OneValueBatchResults.__init__(self, angle_familiarity, best_idex, flags)
+        self.bank_novelty = bank_novelty
+
+
 InfomaxBatchResults = OneValueBatchResults    # the name it had while Infomax was the only such model
 
 # The one-value models -- no library, ONE value per heading: metric -> (prefix of the single calls' symbols, of the batch calls', the
@@ -1366,6 +1375,7 @@ class FamiliarityEngine(object):
         self.mb_shape = (int(h), int(w))
         self.mb_banks = 1
         self.mb_pops = None
+        self.mb_active = int(n_active)
 
     def mb_train_u8(self, planes):
         """Depress the cells that fire for each of uint8[n,h,w] planes: one launch for all of them, in no order."""
@@ -1429,6 +1439,7 @@ class FamiliarityEngine(object):
         self.mb_shape = None
         self.mb_banks = 1
         self.mb_pops = None
+        self.mb_active = None
 
     # -- memory banks of the mushroom-body model: several memories behind one connectivity (include/dejavu.h: dv_mbank_*) ---------
     mb_banks = 1                 # memories of the model (mbank_set; 1 after mb_begin)
@@ -1464,6 +1475,67 @@ class FamiliarityEngine(object):
     def mbank_sense_step_batch(self, x, y, angles, bank_of_member, land_of_member=None):
         """mb_sense_step_batch with member i scored under bank bank_of_member[i] -> OneValueBatchResults: one enqueue and one wait."""
         return self._bank_sense_step_batch("mushroom", x, y, angles, bank_of_member, land_of_member)
+
+    # -- bank sets: one selection of firing cells read out through several banks (include/dejavu.h: dv_mbset_*) ------------------
+    mb_active = None             # n_active of the model mb_begin made (None: no model)
+
+    @staticmethod
+    def mbset_tables(bank_sets, coefs, n, n_banks, n_active):
+        """`bank_sets` and `coefs` as int32[n, S] (1 <= S <= DV_MBSET_MAX_BANKS), or ValueError naming the entry: integers, one shape,
+        banks in [0, n_banks), coefficients in int32, and per member sum |coefs| * n_active <= 2^31 - 1 (the member's value cannot
+        wrap).  n_banks / n_active None: not known here, the library checks."""
+        banks, cf = np.asarray(bank_sets), np.asarray(coefs)
+        for arr, what in ((banks, "bank_sets"), (cf, "coefs")):
+            if arr.dtype.kind not in "iu":
+                raise ValueError("%s must hold integers, got dtype %s" % (what, arr.dtype))
+            if arr.ndim != 2 or arr.shape[0] != n or not 1 <= arr.shape[1] <= N.DV_MBSET_MAX_BANKS:
+                raise ValueError("%s must have shape (%d, S) with 1 <= S <= DV_MBSET_MAX_BANKS = %d, got %r"
+                                 % (what, n, N.DV_MBSET_MAX_BANKS, arr.shape))
+        if banks.shape != cf.shape:
+            raise ValueError("bank_sets and coefs must have one shape, got %r and %r" % (banks.shape, cf.shape))
+        if n_banks is not None and (banks.min() < 0 or banks.max() >= n_banks):
+            i, j = np.argwhere((banks < 0) | (banks >= n_banks))[0]
+            raise ValueError("bank_sets[%d][%d] = %d outside [0, n_banks = %d)" % (i, j, banks[i, j], n_banks))
+        if cf.min() < -2 ** 31 or cf.max() > 2 ** 31 - 1:
+            i, j = np.argwhere((cf < -2 ** 31) | (cf > 2 ** 31 - 1))[0]
+            raise ValueError("coefs[%d][%d] = %d does not fit an int32" % (i, j, cf[i, j]))
+        if n_active is not None:
+            mag = np.abs(cf.astype(np.int64)).sum(axis=1)          # (every entry fits an int32: at most 2^34 a member, 2^58 with n_active)
+            over = np.flatnonzero(mag * np.int64(n_active) > 2 ** 31 - 1)
+            if len(over):
+                raise ValueError("member %d: sum |coefs| = %d times n_active = %d exceeds 2^31 - 1" % (over[0], mag[over[0]], n_active))
+        return np.ascontiguousarray(banks, dtype=np.int32), np.ascontiguousarray(cf, dtype=np.int32)
+
+    def mbset_step_batch_u8(self, planes, bank_sets, coefs):
+        """An ensemble's step on uploaded uint8[n, A, h, w] planes with member i read out through the banks bank_sets[i][0..S) from ONE
+        selection of firing cells: angle_familiarity[i][a] = -(sum_j coefs[i][j] * d_j), d_j the column's novelty under bank
+        bank_sets[i][j] -> MbSetBatchResults (bank_novelty int32[n, A, S] holds the d_j)."""
+        planes = self._member_planes(planes)
+        n, A = planes.shape[:2]
+        banks, cf = self.mbset_tables(bank_sets, coefs, n, self.mb_banks if self.mb_shape else None, self.mb_active)
+        flat = self._ov_planes("mushroom", planes.reshape((n * A,) + planes.shape[2:]))
+        fam, best, flags = self._member_results(n, A)
+        nov = np.empty((n, A, banks.shape[1]), dtype=np.int32)
+        i32 = lambda a: a.ctypes.data_as(N._i32p)
+        self._check(self._lib.dv_mbset_step_u8(self._ctx, N.u8ptr(flat), n, A, banks.shape[1], i32(banks), i32(cf), N.f64ptr(fam), i32(best),
+                                               i32(nov)), "dv_mbset_step_u8")
+        return MbSetBatchResults(fam, best, flags, nov)
+
+    def mbset_sense_step_batch(self, x, y, angles, bank_sets, coefs, land_of_member=None):
+        """mbset_step_batch_u8 from poses: member i at (x[i], y[i]) looking along angles[i][0..A), on the engine's landscape or
+        (land_of_member) on its landscape of the live set, under the set's sensor table and noise rows where there are any.  One
+        enqueue and one wait; a member whose footprint leaves its landscape is flagged (flags & 16, best_idex -1)."""
+        x, y, angles = self._member_poses(x, y, angles)
+        n, A = angles.shape
+        banks, cf = self.mbset_tables(bank_sets, coefs, n, self.mb_banks if self.mb_shape else None, self.mb_active)
+        lands = () if land_of_member is None else (self._land_table(land_of_member, n, "land_of_member").ctypes.data_as(N._i32p),)
+        name = "dv_mbset_sense_step" if land_of_member is None else "dv_mbset_lands_sense_step"
+        fam, best, flags = self._member_results(n, A)
+        nov = np.empty((n, A, banks.shape[1]), dtype=np.int32)
+        i32 = lambda a: a.ctypes.data_as(N._i32p)
+        self._check(getattr(self._lib, name)(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, banks.shape[1], i32(banks), i32(cf),
+                                             *lands, N.f64ptr(fam), i32(best), flags.ctypes.data_as(N._u32p), i32(nov)), name)
+        return MbSetBatchResults(fam, best, flags, nov)
 
     def _bank_cells(self, bank):
         """n_kc of bank `bank` under the live population table."""

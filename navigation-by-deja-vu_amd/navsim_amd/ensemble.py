@@ -553,10 +553,12 @@ class _RouteEnsemble(_OneValueEnsemble):
         raise ValueError("%s has no populations: MushroomRouteEnsemble gives every route's bank cells and wiring of its own" % cls.__name__)
 
     @classmethod
-    def _from_routes(cls, agent, routes, starts, metrics, lands, land_of_route, sensors=None, populations=None, table=None, noise=None):
+    def _from_routes(cls, agent, routes, starts, metrics, lands, land_of_route, sensors=None, populations=None, table=None, noise=None,
+                     opponent=None):
         """from_routes_with (lands None: every route on the agent's own landscape, the engine's one), or from_landscapes (route r on
         lands[land_of_route[r]] of the engine's landscape set; sensors: None, or _sensor_entries' entry per landscape; noise: None, or
-        _noise_arg's dict).
+        _noise_arg's dict).  opponent: None, or MushroomRouteEnsemble._opponent_arg's dict: route r gets a second, repulsive bank R + r,
+        trained in the same call on the same points sensed at the route's headings plus its turn, behind the attractive views.
         populations: None, or from_routes_with's list (an entry per route).  table: None, or a subclass's own extra argument of
         _train_banks, by name (InfomaxRouteEnsemble's networks)."""
         import copy
@@ -593,28 +595,37 @@ class _RouteEnsemble(_OneValueEnsemble):
             h = np.arctan2(steps[:, 1], steps[:, 0])
             headings.append(h[np.minimum(np.arange(len(route)), len(route) - 2)])
         first = np.cumsum([0] + [len(r) for r in routes])
+        per_route = [len(r) for r in routes]
         points = np.concatenate(routes)
-        bank_of_view = np.repeat(np.arange(len(routes), dtype=np.int32), [len(r) for r in routes])
+        all_headings = np.concatenate(headings)
+        bank_of_view = np.repeat(np.arange(len(routes), dtype=np.int32), per_route)
+        n_banks, sides = len(routes), 1
+        if opponent is not None:                                  # the attractive views first, in the order they have without an opponent
+            points = np.concatenate([points, points])
+            all_headings = np.concatenate([all_headings] + [h + t for h, t in zip(headings, opponent["turn"])])
+            bank_of_view = np.concatenate([bank_of_view, bank_of_view + np.int32(len(routes))])
+            n_banks, sides = 2 * len(routes), 2
         cls._begin_model(model, eng, agent)
         if lands is None:
-            views = cls._train_banks(eng, len(routes), points[:, 0], points[:, 1], np.concatenate(headings), bank_of_view, **table)
+            views = cls._train_banks(eng, n_banks, points[:, 0], points[:, 1], all_headings, bank_of_view, **table)
         else:
             eng.lands_set(lands)
             if sensors is not None:
                 eng.sensors_set([e["sensor_pixel_dimensions"] for e in sensors], np.stack([e["lut"] for e in sensors]),
                                 [e["mask_middle_n"] for e in sensors])
-            land_of_view = np.repeat(np.array(land_of_route, dtype=np.int32), [len(r) for r in routes])
+            land_of_view = np.tile(np.repeat(np.array(land_of_route, dtype=np.int32), per_route), sides)
             if noise is not None:                                 # the routes' views draw under their own keys, then no rows until a step
-                per_route = [len(r) for r in routes]
-                eng.noise_rows(noise["seed"], np.concatenate([cls._train_keys(r, n) for r, n in enumerate(per_route)]),
-                               np.repeat(noise["train_amp_s"], per_route), np.repeat(noise["train_amp_v"], per_route))
+                keys = [cls._train_keys(r, n) for r, n in enumerate(per_route)]
+                if opponent is not None:
+                    keys += [cls._repulsive_keys(r, n) for r, n in enumerate(per_route)]
+                eng.noise_rows(noise["seed"], np.concatenate(keys), np.tile(np.repeat(noise["train_amp_s"], per_route), sides),
+                               np.tile(np.repeat(noise["train_amp_v"], per_route), sides))
             try:
-                views = cls._train_banks(eng, len(routes), points[:, 0], points[:, 1], np.concatenate(headings), bank_of_view, land_of_view,
-                                         **table)
+                views = cls._train_banks(eng, n_banks, points[:, 0], points[:, 1], all_headings, bank_of_view, land_of_view, **table)
             finally:
                 if noise is not None:
                     eng.noise_clear()
-        func = model.from_engine(eng, views)
+        func = model.from_engine(eng, views[:first[-1]])
         members = []
         for k, (r, pos, ang) in enumerate(starts):
             a = agent if k == 0 else copy.copy(agent)
@@ -640,6 +651,11 @@ class _RouteEnsemble(_OneValueEnsemble):
             a.noise_stream = None if noise is None else noise["streams"][k]
             a.noise_amp = None if noise is None else (noise["amp_s"][k], noise["amp_v"][k])
             a.noise_count, a._noise_key = 0, None
+            if opponent is not None:
+                a.repulsive_bank = len(routes) + int(r)
+                a.opponent_gain = opponent["gain"][k]
+                a.repulsive_scenes = views[first[-1] + first[r]:first[-1] + first[r + 1]]
+                a.bank_novelty = None
             members.append(a)
         ens = cls(members, metrics=metrics)
         if noise is not None:
@@ -651,6 +667,11 @@ class _RouteEnsemble(_OneValueEnsemble):
     def _train_keys(route, n_views):
         """uint64[n_views]: the noise keys of the views of route `route`, (0x80000000 | route) << 32 | view."""
         return (np.uint64((0x80000000 | route) << 32) | np.arange(n_views, dtype=np.uint64)).astype(np.uint64)
+
+    @staticmethod
+    def _repulsive_keys(route, n_views):
+        """... and of the views of its repulsive bank (MushroomRouteEnsemble's opponent): (0xC0000000 | route) << 32 | view."""
+        return (np.uint64((0xC0000000 | route) << 32) | np.arange(n_views, dtype=np.uint64)).astype(np.uint64)
 
     @staticmethod
     def _step_key(stream, count):
@@ -852,7 +873,17 @@ class MushroomRouteEnsemble(_RouteEnsemble):
     engine's population table (FamiliarityEngine.mbpop_set), and every route's bank has the cells, wiring, quota and channel of its
     entry; a route under two populations is entered twice, as a landscape under two sensors is.  Members carry `population_index` and
     `population` (dict(channel, n_kc, fan_in, n_active, sparsity, seed)); both are None without populations.  A member's rows are those
-    of a lone agent built with mushroom_familiarity of its population and trained on its route alone."""
+    of a lone agent built with mushroom_familiarity of its population and trained on its route alone.
+
+    from_routes_with / from_landscapes(opponent=dict(turn=np.pi, gain=1)) gives every route an OPPONENT memory (Le Moel & Wystrach
+    2020): route r keeps bank r, the attractive one, and gets bank R + r, the repulsive one, trained on the same points sensed at the
+    route's headings plus `turn`; all 2 sum n_r views go up in the one training call, the attractive ones first.  A member's step reads
+    ONE selection of firing cells out through both banks (FamiliarityEngine.mbset_sense_step_batch: banks [r, R + r], coefficients
+    [1, -gain]), so angle_familiarity[a] = -(d_att - gain d_rep), and it steers by the first maximum of that difference.  Members
+    carry `memory_bank` (r), `repulsive_bank` (R + r), `opponent_gain`, `repulsive_scenes` and, after a step, `bank_novelty`
+    (int32[A, 2]: d_att and d_rep of every heading); bank_info() has 2 R entries.  Like every banked member, an opponent member
+    steps with its ensemble only: its own step_forward is refused (a step of its own would read the attractive bank alone).  Not
+    with `populations`: banks of different populations share no selection."""
     POPULATION_KEYS = ("n_kc", "fan_in", "sparsity", "seed", "channel")
     _metric = "mushroom"
     _takes = MushroomEnsemble._takes
@@ -860,6 +891,89 @@ class MushroomRouteEnsemble(_RouteEnsemble):
     _info_call = "mbank_info"                # dict(n_banks, views_trained int64[R], n_depressed int64[R])
     _one_route = "MushroomEnsemble"
     _reject_others = MushroomEnsemble._reject_others
+    OPPONENT_KEYS = ("turn", "gain")
+    MAX_GAIN = 1024
+
+    def __init__(self, agents, metrics="host"):
+        super(MushroomRouteEnsemble, self).__init__(agents, metrics=metrics)
+        rep = [getattr(a, "repulsive_bank", None) for a in agents]
+        if any(r is not None for r in rep) and any(r is None for r in rep):
+            raise ValueError("MushroomRouteEnsemble: members with an opponent memory (a repulsive_bank) and members without one do not mix")
+        # an opponent member's set of a step: banks (attractive, repulsive) under coefficients (1, -gain)
+        self._sets = None if rep[0] is None else np.array([[a.memory_bank, a.repulsive_bank] for a in agents], dtype=np.int32)
+        self._coefs = None if rep[0] is None else np.array([[1, -a.opponent_gain] for a in agents], dtype=np.int32)
+
+    @classmethod
+    def _opponent_arg(cls, opponent, n_starts, n_routes):
+        """from_routes_with's / from_landscapes' `opponent` as dict(turn: a float per route, gain: an int per start), or None.
+        ValueError names the entry."""
+        if opponent is None:
+            return None
+        if not isinstance(opponent, dict):
+            raise ValueError("opponent must be None or a dict with any of %r, got %r" % (cls.OPPONENT_KEYS, opponent))
+        extra = sorted(set(opponent) - set(cls.OPPONENT_KEYS))
+        if extra:
+            raise ValueError("opponent: unknown keys %r (it holds any of %r)" % (extra, cls.OPPONENT_KEYS))
+
+        def per(key, default, n, of, ok, rule):
+            v = opponent.get(key, default)
+            if isinstance(v, (list, tuple, np.ndarray)):
+                if len(v) != n:
+                    raise ValueError("opponent[%r] holds %d values for %d %s" % (key, len(v), n, of))
+                items = [("opponent[%r][%d]" % (key, i), x) for i, x in enumerate(v)]
+            else:
+                items = [("opponent[%r]" % key, v)] * n
+            for what, x in items:
+                if isinstance(x, bool) or not ok(x):
+                    raise ValueError("%s = %r: %s" % (what, x, rule))
+            return [x for _, x in items]
+        turn = per("turn", np.pi, n_routes, "routes", lambda x: isinstance(x, (int, float, np.integer, np.floating)) and np.isfinite(x),
+                   "a turn is a finite angle in radians")
+        gain = per("gain", 1, n_starts, "starts", lambda x: isinstance(x, (int, np.integer)) and 0 <= x <= cls.MAX_GAIN,
+                   "a gain is an integer in [0, %d]" % cls.MAX_GAIN)
+        return dict(turn=[float(t) for t in turn], gain=[int(g) for g in gain])
+
+    @classmethod
+    def from_routes_with(cls, agent, routes, starts, metrics="host", opponent=None, populations=None):
+        """_RouteEnsemble.from_routes_with, and opponent: None (exactly the calls made without it), or a dict with any of
+            turn=np.pi     the repulsive views look along the route's headings plus this angle: a float, or a list per route
+            gain=1         an integer in [0, 1024], or a list per start
+        (see the class).  There is no `noise` here: sensor noise rides the landscape table, so use
+        from_landscapes([landscape], ..., noise=...)."""
+        starts, routes = list(starts), list(routes)
+        opp = cls._opponent_arg(opponent, len(starts), len(routes))
+        if opp is not None and populations is not None:
+            raise ValueError("opponent with populations: banks of different populations share no selection of firing cells")
+        return cls._from_routes(agent, routes, starts, metrics, None, None, populations=populations, opponent=opp)
+
+    @classmethod
+    def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host", sensors=None, noise=None, opponent=None, populations=None):
+        """_RouteEnsemble.from_landscapes, and opponent as from_routes_with's.  Under `noise` the attractive training keys are the
+        ones without an opponent, and repulsive view v of route r draws under (0xC0000000 | r) << 32 | v with the route's training
+        amplitudes."""
+        starts, routes = list(starts), list(routes)
+        opp = cls._opponent_arg(opponent, len(starts), len(routes))
+        if opp is not None and populations is not None:
+            raise ValueError("opponent with populations: banks of different populations share no selection of firing cells")
+        nz = cls._noise_arg(noise, len(starts), len(routes))
+        if nz is not None and populations is not None:
+            raise ValueError("noise with populations: the sensed step under a population table has no noise form")
+        lands, points, land_of_route, entries = cls._landscape_args(agent, landscapes, routes, sensors)
+        return cls._from_routes(agent, points, starts, metrics, lands, land_of_route, entries, populations=populations, noise=nz, opponent=opp)
+
+    def _device_step(self, idx, xs, ys, angs):
+        if self._sets is None:
+            return super(MushroomRouteEnsemble, self)._device_step(idx, xs, ys, angs)
+        lands = None
+        if self._lands is not None:
+            self._noise_begin_step(idx)
+            self._noise_set_rows([self.agents[i] for i in idx])
+            lands = self._lands[idx]
+        results = self.engine.mbset_sense_step_batch(xs, ys, angs, self._sets[idx], self._coefs[idx], land_of_member=lands)
+        self._rows = {id(self.agents[i]): results.angle_familiarity[k] for k, i in enumerate(idx)}
+        for k, i in enumerate(idx):
+            self.agents[i].bank_novelty = results.bank_novelty[k]
+        return results
 
     @staticmethod
     def _train_banks(eng, n_routes, x, y, headings, bank_of_view, land_of_view=None, populations=None):

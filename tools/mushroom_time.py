@@ -2,7 +2,7 @@
 """Times the mushroom-body familiarity model (navsim_amd.mushroom_familiarity; include/dejavu.h: dv_mb_*) on GPU 0 and writes
 profiles/mushroom_time.json.
 
-    python tools/mushroom_time.py [--sides 32,64] [--views 1000] [--calls 200] [--reps 5] [--blocks single,ensemble[,banks][,metrics][,lands][,rows][,sensors][,populations][,noise]]
+    python tools/mushroom_time.py [--sides 32,64] [--views 1000] [--calls 200] [--reps 5] [--blocks single,ensemble[,banks][,metrics][,lands][,rows][,sensors][,populations][,noise][,sets]]
                                   [--out profiles/mushroom_time.json]
 
 Per sensor side s (views of s x s) with K = 20000 Kenyon cells, fan-in 10 and 200 firing cells: microseconds per agent step
@@ -62,6 +62,10 @@ banked step without a table at the same poses -- a table equal to the model's, f
 engines stepped in turn -- and one banked training call over four populations against four engines (tools/populations_block.py).
 
 A block that is not measured keeps the rows it has in the output file.
+
+Sets block (--blocks sets, tools/sets_block.py): per side, the banks block's two layouts over 4 routes of two memories each, stepped by
+dv_mbset_sense_step at S = 1, 2 and 8 banks a member, by the banked step at the same poses, and by the banked step with every
+member entered S times -- what the same read-out costs without sets.
 
 Every GPU measurement runs in a child process of its own under a time limit, and nothing more is started on the GPU after one
 that failed."""
@@ -550,7 +554,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--limit", type=int, default=240, help="seconds allowed to each GPU child")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mushroom_time.json"))
-    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and the agent step), ensemble, banks, metrics, lands, rows, sensors, populations, noise")
+    ap.add_argument("--blocks", default="single,ensemble", help="which blocks to measure: single (training and the agent step), ensemble, banks, metrics, lands, rows, sensors, populations, noise, sets")
     ap.add_argument("--ensemble-calls", type=int, default=30, help="ensemble steps per timed window")
     ap.add_argument("--child", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--ensemble-child", type=int, default=0, help=argparse.SUPPRESS)
@@ -580,12 +584,12 @@ def main():
         return 0
     blocks = args.blocks.split(",")
     result = dict(tool="tools/mushroom_time.py", timer="hipEvent pair (dv_timer_start/stop), median of %d windows after a warm-up" % args.reps,
-                  sizes=[], ensembles=[], banks=[], metrics=[], lands=[], rows=[], sensors=[], populations=[], noise=[])
+                  sizes=[], ensembles=[], banks=[], metrics=[], lands=[], rows=[], sensors=[], populations=[], noise=[], sets=[])
     if os.path.exists(args.out):                                  # a block that is not measured keeps its rows
         with open(args.out) as f:
             kept = json.load(f)
         for block, key in (("single", "sizes"), ("ensemble", "ensembles"), ("banks", "banks"), ("metrics", "metrics"), ("lands", "lands"), ("rows", "rows"),
-                           ("sensors", "sensors"), ("populations", "populations"), ("noise", "noise")):
+                           ("sensors", "sensors"), ("populations", "populations"), ("noise", "noise"), ("sets", "sets")):
             if block not in blocks:
                 result[key] = kept.get(key, [])
     for side in [int(x) for x in args.sides.split(",")] if "ensemble" in blocks else []:
@@ -630,6 +634,12 @@ def main():
         if rc != 0:
             return rc
         result["populations"].append(row)
+    for side in [int(x) for x in args.sides.split(",")] if "sets" in blocks else []:
+        import sets_block
+        rc, row = sets_block.run_child(args.limit, side, args.views, args.ensemble_calls, args.reps)
+        if rc != 0:
+            return rc
+        result["sets"].append(row)
     if "metrics" in blocks:
         cmd = ["timeout", "-k", "10", str(args.limit), sys.executable, os.path.abspath(__file__), "--metrics-child", "1",
                "--ensemble-calls", str(args.ensemble_calls), "--reps", str(args.reps)]

@@ -1093,6 +1093,41 @@ int dv_rvssd_scene(dv_ctx *ctx, const double *x, const double *y, const double *
                    const int32_t *route_of_member, const int32_t *land_of_member, int channel,
                    int64_t n_out, double *scene_ssd, uint32_t *member_flags);
 
+/* ---- NCC on the route view store: the correlation coefficient of one channel ---- */
+/*
+ * dv_rvssd_*'s calls, argument for argument, with the correlation coefficient (zero-mean normalised cross-correlation) in place of the
+ * SSD: invariant to the gain and offset of a view.  For a patch plane a and a stored view b of channel `channel`, P = h w pixels, in
+ * exact integers
+ *     Sa = sum a   Sb = sum b   Saa = sum a^2   Sbb = sum b^2   Sab = sum a b
+ *     num = P Sab - Sa Sb      Va = P Saa - Sa^2      Vb = P Sbb - Sb^2
+ *     q = 0.0 if Va == 0 or Vb == 0 (a constant plane correlates with nothing), else
+ *     q = clip(double(num) / sqrt(double(Va) * double(Vb)), -1, 1): one IEEE double product, one square root, one quotient, in that order.
+ * The cross term is dv_rvssd_*'s int8 GEMM on a - 128 and b - 128 (num, Va and Vb do not change), the epilogue is in 64-bit integers
+ * (the three reach 2^38; their conversions to double are exact), and every pair is evaluated: the values are the statement's bits.
+ *   step_u8          angle_ncc[i * n_headings + a]: the LARGEST q over the views of member i's route, angle_view (may be NULL) the
+ *                    LEAST route-relative view index that attains it, best_heading[i] the FIRST heading with the largest angle_ncc
+ *                    (np.argmax(angle_ncc)).  Any n_headings >= 1, any n_agents.
+ *   sense_step       step_u8 with the patches sensed as dv_rviews_sense_step senses them (landscape sets, sensor tables and noise rows
+ *                    included): one enqueue, one wait.  member_flags[i] carries DV_RES_SENSE_ERROR for a member whose footprint leaves
+ *                    its own landscape (its row is unspecified, its best_heading -1); the others are scored.
+ *   scene_u8 / scene per view of member i's route the LEAST q over its headings (what the reference's loop leaves in scene_familiarity),
+ *                    the members' rows back to back as in dv_rviews_scene (n_out doubles).  A member with DV_RES_SENSE_ERROR gets a
+ *                    row of +inf.  member_flags may be NULL.
+ * Checks: dv_rvssd_*'s, all before anything reaches the device.  The view statistics (sum and sum of squares per view) are worked out at
+ * the first call on a (store, channel) and kept until the store is replaced or cleared, apart from dv_rvssd_*'s norms; nothing that
+ * dv_rvssd_* keeps is written.  No floating-point atomics and nothing that depends on the order of the workgroups.
+ */
+int dv_rvncc_step_u8(dv_ctx *ctx, const uint8_t *patches, int n_agents, int n_headings, const int32_t *route_of_member, int channel,
+                     double *angle_ncc, int64_t *angle_view, int32_t *best_heading);
+int dv_rvncc_sense_step(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
+                        const int32_t *route_of_member, const int32_t *land_of_member, int channel,
+                        double *angle_ncc, int64_t *angle_view, int32_t *best_heading, uint32_t *member_flags);
+int dv_rvncc_scene_u8(dv_ctx *ctx, const uint8_t *patches, int n_agents, int n_headings, const int32_t *route_of_member, int channel,
+                      int64_t n_out, double *scene_ncc);
+int dv_rvncc_scene(dv_ctx *ctx, const double *x, const double *y, const double *angles, int n_agents, int n_headings,
+                   const int32_t *route_of_member, const int32_t *land_of_member, int channel,
+                   int64_t n_out, double *scene_ncc, uint32_t *member_flags);
+
 /* ---- SSD on the route view store with a temporal window, and re-localisation inside the step ---- */
 /*
  * dv_rvssd_step_u8 / dv_rvssd_sense_step with member i scored against views [win_lo[i], win_hi[i]) of its own route only: what the

@@ -450,6 +450,14 @@ struct dv_ctx {
     MirroredTable rvsw_tab;                   // a windowed SSD call's tables (dejavu_rvssdw.inl: windows, thresholds, order); never rvs_tab
     unsigned char* rvs_plan = nullptr;        // what the device writes of a relocalising SSD call's plan (dejavu_rvssdw.inl)
     size_t rvs_plan_cap = 0;                  // bytes
+    // NCC on the store (dejavu_rvncc.inl: dv_rvncc_*): reads rv_planes, rv_routes and a call's rvs_tab, writes nothing of dv_rvssd_*'s
+    unsigned* rvn_stat = nullptr;             // [3][groups][64] sum (x - 128) (int), then [3][groups][64] sum (x - 128)^2
+    unsigned long long rvn_stat_gen[3] = {0, 0, 0};   // the store generation channel ch's statistics are of (0: none)
+    unsigned* rvn_op = nullptr;               // [C][Kp * 8] operand dwords of the sorted columns, then psum[C] (int), psq[C]
+    unsigned char* rvn_part = nullptr;        // a step's partials: q[C][G] doubles, then view[C][G] ints (G: groups of the longest route)
+    unsigned char* rvn_out = nullptr;         // a step's results: ncc[C], view[C], best[N], flags[N]
+    unsigned long long* rvn_rows = nullptr;   // a scene call's encoded rows, decoded in place
+    size_t rvn_stat_cap = 0, rvn_op_cap = 0, rvn_part_cap = 0, rvn_out_cap = 0, rvn_rows_cap = 0;   // bytes
 
     // measurement
     hipEvent_t t0 = nullptr, t1 = nullptr;
@@ -486,6 +494,7 @@ static void sensors_free(dv_ctx* c);
 static void noise_drop(dv_ctx* c);
 static void rviews_free(dv_ctx* c);
 static void rvssd_free(dv_ctx* c);
+static void rvncc_free(dv_ctx* c);
 static void path_routes_free(dv_ctx* c);
 static void free_library(dv_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
@@ -593,6 +602,7 @@ extern "C" void dv_destroy(dv_ctx* c) {
     noise_drop(c);
     rviews_free(c);
     rvssd_free(c);
+    rvncc_free(c);
     path_routes_free(c);
     if (c->d_land) (void)hipFree(c->d_land);
     if (c->d_lut) (void)hipFree(c->d_lut);
@@ -3855,6 +3865,7 @@ extern "C" int dv_stream_read_gbps(dv_ctx* c, int64_t n_bytes, int iters, double
 #include "dejavu_rvwin.inl"     // dv_rvwin_*: windowed perfect memory on the route view store, scored in one fused launch (kernel and host side)
 #include "dejavu_rvssd.inl"     // dv_rvssd_*: exact SSD of one channel on the route view store, on the int8 matrix cores (kernels and host side)
 #include "dejavu_rvssdw.inl"    // dv_rvssdw_*: dv_rvssd_* with a temporal window, lost members re-localised inside the step (kernels and host side)
+#include "dejavu_rvncc.inl"     // dv_rvncc_*: the correlation coefficient of one channel on the route view store, dv_rvssd_*'s GEMM and a 64-bit epilogue (kernels and host side)
 #include "dejavu_infomax.inl"  // dv_infomax_*: the Infomax familiarity model (kernels and host side)
 #include "dejavu_inet.inl"      // dv_inet_*: network tables, a bank's own n_hidden, learning rate, W0 and channel (kernels and host side)
 #include "dejavu_mushroom.inl"  // dv_mb_*: the mushroom-body familiarity model (kernels and host side)

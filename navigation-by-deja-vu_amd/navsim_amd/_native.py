@@ -329,6 +329,12 @@ PROTOTYPES = {
     "dv_rvssd_scene_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, ctypes.c_int64, _f64p]),
     "dv_rvssd_scene": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _i32p, _i32p, ctypes.c_int, ctypes.c_int64, _f64p,
                                       _u32p]),
+    "dv_rvncc_step_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, _f64p, _i64p, _i32p]),
+    "dv_rvncc_sense_step": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _i32p, _i32p, ctypes.c_int, _f64p, _i64p,
+                                           _i32p, _u32p]),
+    "dv_rvncc_scene_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, _i32p, ctypes.c_int, ctypes.c_int64, _f64p]),
+    "dv_rvncc_scene": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _i32p, _i32p, ctypes.c_int, ctypes.c_int64, _f64p,
+                                      _u32p]),
     "dv_rvssdw_step_u8": (ctypes.c_int, [_ctx_p, _u8p, ctypes.c_int, ctypes.c_int, _i32p, _i32p, _i32p, _f64p, ctypes.c_int, _f64p, _i64p, _i32p,
                                          _u32p]),
     "dv_rvssdw_sense_step": (ctypes.c_int, [_ctx_p, _f64p, _f64p, _f64p, ctypes.c_int, ctypes.c_int, _i32p, _i32p, _i32p, _i32p, _f64p,

@@ -281,6 +281,9 @@ class NavBySceneFamiliarity(object):
                 self.familiarity_model.begin(self._engine, self.sensor_dimensions[1], self.sensor_dimensions[0])
                 model = self._engine.one_value(self.familiarity_model.metric)
                 self.familiar_scenes[...] = model.train_from_poses(points[:, 0], points[:, 1], view_headings)
+            elif getattr(self.familiarity_model, "metric", "sads_hsv") == "ncc":
+                # no library: the route's views lie in a one-route view store, sensed where they are kept
+                self.familiar_scenes[...] = self._engine.rviews_set_from_poses(points[:, 0], points[:, 1], view_headings, [0, n])
             elif getattr(self.familiarity_model, "metric", "sads_hsv") == "ssd":
                 self.familiar_scenes[...] = self._engine.set_library_u8_from_poses(
                     points[:, 0], points[:, 1], view_headings, self.familiarity_model.channel)
@@ -318,6 +321,7 @@ class NavBySceneFamiliarity(object):
         next one of ITS path, the last reuses the last heading."""
         if self.training_path is None:
             raise ValueError("train_from_path first")
+        self._refuse_for_store_member("train_additional_path")
         points = np.asarray(points, dtype=np.float64)
         n = len(points)
         steps = points[1:] - points[:-1]
@@ -326,7 +330,18 @@ class NavBySceneFamiliarity(object):
         engine = getattr(self._familiarity_func, "engine", None)
         ssd = str(getattr(self._familiarity_func, "metric", "")).startswith("ssd")
         one_value = getattr(self._familiarity_func, "metric", "") in ONE_VALUE_METRICS
-        if one_value and self._engine is not None and engine is self._engine:
+        ncc = getattr(self._familiarity_func, "metric", "") == "ncc"
+        if ncc and self._engine is not None and engine is self._engine:
+            # the view store has no append: every view is sensed again, the old routes' under their own headings (the SSD plug-in's way)
+            for pt in points:
+                self._check_bounds(pt)
+            self._ncc_headings = np.concatenate([self._ncc_view_headings(), view_headings])
+            both = np.concatenate([np.asarray(self.training_path, dtype=np.float64), points])
+            new_views = engine.rviews_set_from_poses(both[:, 0], both[:, 1], self._ncc_headings, [0, len(both)])[len(self.training_path):]
+        elif ncc:
+            new_views = np.stack([self.get_sensor_mat(points[i], view_headings[i]) for i in range(n)])
+            engine.rviews_set_u8(np.concatenate([self.familiar_scenes, new_views]), [0, len(self.familiar_scenes) + n])
+        elif one_value and self._engine is not None and engine is self._engine:
             # the model keeps training on the same weights (Infomax: the new views follow the old ones in the chain; mushroom body: the
             # same weights are depressed further, in no order)
             for pt in points:
@@ -353,7 +368,7 @@ class NavBySceneFamiliarity(object):
             if engine is not None and hasattr(engine, "append_library"):
                 engine.append_library(new_views)
         self.familiar_scenes = np.concatenate([self.familiar_scenes, new_views])
-        if engine is None or (not ssd and not hasattr(engine, "append_library")):
+        if engine is None or (not ssd and not ncc and not hasattr(engine, "append_library")):
             self._familiarity_func = self.familiarity_model(self.familiar_scenes)     # any other plug-in: hand it all views again
         self.training_path_length = self.training_path_length + np.sum(np.linalg.norm(steps, axis=1))
         self.training_path = np.concatenate([self.training_path, points])
@@ -363,11 +378,21 @@ class NavBySceneFamiliarity(object):
             self._engine.set_training_path(self.training_path)
         self.reset_error()
 
+    def _refuse_for_store_member(self, what):
+        """A member of an NccRouteEnsemble shares ONE view store with the others: clearing or replacing it would take their routes too."""
+        if self.memory_bank is not None and route_ensemble_name(self) == "NccRouteEnsemble":
+            raise ValueError("this ensemble member's route is route %d of the view store it shares with the other members of its "
+                             "NccRouteEnsemble: %s would replace every member's routes" % (self.memory_bank, what))
+
     def clear_training(self):
         func = getattr(self, "_familiarity_func", None)
+        if func is not None:
+            self._refuse_for_store_member("clear_training")
         if func is not None and hasattr(func, "engine"):
             if func.engine is getattr(self, "_engine", None):
                 func.engine.clear_library()          # keep the landscape and the sensor configuration
+                if getattr(func, "metric", "") == "ncc":
+                    func.engine.rviews_clear()
                 if getattr(func, "metric", "") in ONE_VALUE_METRICS:
                     func.engine.one_value(func.metric).end()
             else:
@@ -381,6 +406,16 @@ class NavBySceneFamiliarity(object):
         self.scene_familiarity = None
         self._scene_is_inf = False
         self.training_path_length = None
+        self._ncc_headings = None
+
+    def _ncc_view_headings(self):
+        """The headings the views of the NCC model's store were sensed under: those of train_from_path, then of every additional path."""
+        if getattr(self, "_ncc_headings", None) is None:
+            pts = np.asarray(self.training_path, dtype=np.float64)
+            steps = pts[1:] - pts[:-1]
+            h = np.arctan2(steps[:, 1], steps[:, 0])
+            self._ncc_headings = h[np.minimum(np.arange(len(pts)), len(pts) - 2)]
+        return self._ncc_headings
 
     # ---- sensor (:151-192) ---------------------------------------------------------------------
     def get_sensor_mat(self, position, angle):
@@ -582,6 +617,9 @@ class NavBySceneFamiliarity(object):
             # the step was an ensemble's (NavEnsemble._note_scene): the ensemble works out what all its members have left to work
             # out, in library passes they share
             self._scene_owner._read_scene()
+        elif st is not None and isinstance(st[0], str):       # ("ncc", x, y, angle): _step_ncc's note
+            self._scene_stale = None
+            self._scene_fam[:] = self._ncc_scene(st[1], st[2], st[3])
         elif st is not None:
             self._scene_stale = None
             res = self._engine.sense_step(st[0], st[1], (st[2] + self.angle_offsets) % (2 * np.pi), want_scene=True)
@@ -600,7 +638,7 @@ class NavBySceneFamiliarity(object):
             # (a step of its own scores under bank 0 of the model: only its ensemble's batches score it under its own bank -- or, for the
             # perfect-memory model, against its own route's views of the store)
             name = route_ensemble_name(self)
-            if name in ("SadsRouteEnsemble", "SsdRouteEnsemble"):
+            if name in ("SadsRouteEnsemble", "SsdRouteEnsemble", "NccRouteEnsemble"):
                 raise ValueError("this ensemble member's route is route %d of the view store it shares: step it with its %s"
                                  % (self.memory_bank, name))
             raise ValueError("this ensemble member's route is kept in memory bank %d of a model it shares: step it with its %s"
@@ -622,7 +660,12 @@ class NavBySceneFamiliarity(object):
         self._scene_stale = None               # (whatever was left to work out belonged to the step before)
         self._scene_owner = None
         begun_next = None                      # (the next step was begun by the call that ended this one, an error answer it collected)
-        if engine is not None and str(getattr(func, "metric", "")).startswith("ssd"):
+        if engine is not None and getattr(func, "metric", "") == "ncc" and engine is not self._engine:
+            engine = None                      # (the host sensor model: the reference's loop below, one func call per heading)
+        if engine is not None and getattr(func, "metric", "") == "ncc":
+            self._step_ncc(func, engine, position)
+            best_idex = self.last_scored_idex
+        elif engine is not None and str(getattr(func, "metric", "")).startswith("ssd"):
             self._step_ssd(func, engine, position)
             best_idex = self.last_scored_idex
         elif engine is not None and getattr(func, "metric", "") in ONE_VALUE_METRICS:
@@ -758,6 +801,37 @@ class NavBySceneFamiliarity(object):
             self._scene_fam[:] = np.inf
             self._scene_is_inf = True
         self.last_scored_idex = res["best_idex"]
+
+    def _ncc_scene(self, x, y, angle):
+        """min over the headings of the per-view correlation coefficients of the step taken at (x, y, angle): one rvncc_scene call."""
+        angles = ((angle + self.angle_offsets) % (2 * np.pi))[None, :]
+        return self._engine.rvncc_scene([x], [y], angles, [0], self._familiarity_func.channel)[0]
+
+    def _step_ncc(self, func, engine, position):
+        """The heading loop (:289-315) with the NCC plug-in (util.ncc_familiarity) and the sensor model on the GPU: ONE device step --
+        sense, correlate against the one-route view store, decide (rvncc_sense_step with one member).  scene_familiarity is one
+        rvncc_scene call at the same pose, made when it is read (lazy_scene) or here: the same call, the same bits."""
+        angles = ((self.angle + self.angle_offsets) % (2 * np.pi))[None, :]
+        try:
+            self._check_bounds(position)
+            res = engine.rvncc_sense_step([position[0]], [position[1]], angles, [0], func.channel)
+            if res.flags[0] & 16:
+                raise IndexError("sensor footprint reaches past the end of the landscape (index out of bounds)")
+            self.angle_familiarity[:] = res.angle_ncc[0]
+            if self.track_scene_familiarity and not self.lazy_scene:
+                self._scene_fam[:] = self._ncc_scene(position[0], position[1], self.angle)
+        except Exception:
+            self._scene_fam[:] = np.inf
+            self._scene_is_inf = True
+            raise
+        if self.track_scene_familiarity:
+            if self.lazy_scene:
+                self._scene_stale = ("ncc", position[0], position[1], self.angle)
+            self._scene_is_inf = False
+        elif not self._scene_is_inf:
+            self._scene_fam[:] = np.inf
+            self._scene_is_inf = True
+        self.last_scored_idex = int(res.best_idex[0])
 
     def _step_one_value(self, func, engine, position):
         """The heading loop (:289-315) with a plug-in without per-view memory (util.infomax_familiarity, util.mushroom_familiarity): ONE

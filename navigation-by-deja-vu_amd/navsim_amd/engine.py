@@ -90,6 +90,16 @@ class RouteSsdResults(RouteViewResults):
         self.angle_ssd = angle_ssd
 
 
+class RouteNccResults(RouteViewResults):
+    """An NCC step on the route view store (dv_rvncc_step_u8 / dv_rvncc_sense_step): angle_ncc[n, A] (float64, the largest correlation
+    coefficient over the member's route), angle_view[n, A] the least view that attains it, best_idex[n] the first largest heading;
+    angle_familiarity IS angle_ncc (the same array)."""
+
+    def __init__(self, angle_ncc, angle_view, best_idex, flags):
+        RouteViewResults.__init__(self, angle_ncc, angle_view, best_idex, flags)
+        self.angle_ncc = angle_ncc
+
+
 class MbSetBatchResults(OneValueBatchResults):
     """A bank-set step of the mushroom-body model (dv_mbset_step_u8 / dv_mbset_sense_step / dv_mbset_lands_sense_step):
     OneValueBatchResults and bank_novelty[n, A, S] (int32), the column's novelty under each bank of its member's set."""
@@ -2155,5 +2165,59 @@ class FamiliarityEngine(object):
         self._check(self._lib.dv_rvssd_scene(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, routes.ctypes.data_as(N._i32p),
                                              None if lands is None else lands.ctypes.data_as(N._i32p), channel, len(out), N.f64ptr(out),
                                              flags.ctypes.data_as(N._u32p)), "dv_rvssd_scene")
+        rows = [out[row0[i]:row0[i + 1]] for i in range(n)]
+        return (rows, flags) if want_flags else rows
+
+    # -- NCC on the store: the correlation coefficient of one channel, SSD's GEMM and a 64-bit epilogue (include/dejavu.h: dv_rvncc_*) --
+    def rvncc_step_u8(self, patches, route_of_member, channel=2):
+        """patches: uint8[n, A, h, w, 3]; member i's channel `channel` is scored by the correlation coefficient against the views of
+        route route_of_member[i] -> RouteNccResults: angle_ncc[n, A] (in [-1, 1]; 0.0 where a plane is constant), angle_view[n, A] (the
+        least view of the route that attains it), best_idex[n] (the first largest heading), flags[n]."""
+        patches = self._rviews_patches(patches)
+        n, A = patches.shape[:2]
+        routes, channel, _ = self._rvssd_tables(n, route_of_member, channel)
+        ncc, best, flags = self._member_results(n, A)
+        view = np.empty((n, A), dtype=np.int64)
+        self._check(self._lib.dv_rvncc_step_u8(self._ctx, N.u8ptr(patches), n, A, routes.ctypes.data_as(N._i32p), channel, N.f64ptr(ncc),
+                                               N.i64ptr(view), best.ctypes.data_as(N._i32p)), "dv_rvncc_step_u8")
+        return RouteNccResults(ncc, view, best, flags)
+
+    def rvncc_sense_step(self, x, y, angles, route_of_member, channel=2, land_of_member=None):
+        """rvncc_step_u8 with member i's patches sensed at (x[i], y[i]) along angles[i] (on landscape land_of_member[i] of the live
+        set): one enqueue and one wait.  flags[i] carries DV_RES_SENSE_ERROR = 16 for a member whose footprint leaves its landscape."""
+        x, y, angles = self._member_poses(x, y, angles)
+        n, A = angles.shape
+        routes, channel, lands = self._rvssd_tables(n, route_of_member, channel, land_of_member)
+        ncc, best, flags = self._member_results(n, A)
+        view = np.empty((n, A), dtype=np.int64)
+        self._check(self._lib.dv_rvncc_sense_step(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, routes.ctypes.data_as(N._i32p),
+                                                  None if lands is None else lands.ctypes.data_as(N._i32p), channel, N.f64ptr(ncc),
+                                                  N.i64ptr(view), best.ctypes.data_as(N._i32p), flags.ctypes.data_as(N._u32p)),
+                    "dv_rvncc_sense_step")
+        return RouteNccResults(ncc, view, best, flags)
+
+    def rvncc_scene_u8(self, patches, route_of_member, channel=2):
+        """Per member a float64[len(its route)]: per view the least correlation coefficient over the headings (scene_familiarity)."""
+        patches = self._rviews_patches(patches)
+        n, A = patches.shape[:2]
+        routes, channel, _ = self._rvssd_tables(n, route_of_member, channel)
+        row0 = self._rviews_rows(routes)
+        out = np.empty(row0[-1], dtype=np.float64)
+        self._check(self._lib.dv_rvncc_scene_u8(self._ctx, N.u8ptr(patches), n, A, routes.ctypes.data_as(N._i32p), channel, len(out),
+                                                N.f64ptr(out)), "dv_rvncc_scene_u8")
+        return [out[row0[i]:row0[i + 1]] for i in range(n)]
+
+    def rvncc_scene(self, x, y, angles, route_of_member, channel=2, land_of_member=None, want_flags=False):
+        """rvncc_scene_u8 with the patches sensed as rvncc_sense_step senses them; a member whose footprint leaves its landscape gets
+        a row of +inf and DV_RES_SENSE_ERROR = 16 in its flag.  want_flags: returns (rows, flags uint32[n])."""
+        x, y, angles = self._member_poses(x, y, angles)
+        n, A = angles.shape
+        routes, channel, lands = self._rvssd_tables(n, route_of_member, channel, land_of_member)
+        row0 = self._rviews_rows(routes)
+        out = np.empty(row0[-1], dtype=np.float64)
+        flags = np.zeros(n, dtype=np.uint32)
+        self._check(self._lib.dv_rvncc_scene(self._ctx, N.f64ptr(x), N.f64ptr(y), N.f64ptr(angles), n, A, routes.ctypes.data_as(N._i32p),
+                                             None if lands is None else lands.ctypes.data_as(N._i32p), channel, len(out), N.f64ptr(out),
+                                             flags.ctypes.data_as(N._u32p)), "dv_rvncc_scene")
         rows = [out[row0[i]:row0[i + 1]] for i in range(n)]
         return (rows, flags) if want_flags else rows

@@ -19,7 +19,7 @@ single agent works its minimum out when it is read.
 import numpy as np
 
 from .agent import StopNavigationException, OutOfLandscapeBoundsException, coverage_row
-from .util import reject_infomax, reject_mushroom, reject_banked, route_ensemble_name
+from .util import reject_infomax, reject_mushroom, reject_ncc, reject_banked, route_ensemble_name
 
 
 class NavEnsemble(object):
@@ -342,6 +342,11 @@ class _OneValueEnsemble(NavEnsemble):
         """The refusals of util.py for the other model without a library."""
 
     @classmethod
+    def _reject_ncc(cls, agent):
+        """The NCC model's views lie in the route view store: only NccRouteEnsemble (which overrides this) steps it."""
+        reject_ncc(agent, cls.__name__)
+
+    @classmethod
     def _reject_banked(cls, agent):
         reject_banked(agent, cls.__name__)
 
@@ -349,6 +354,7 @@ class _OneValueEnsemble(NavEnsemble):
     def _check_member(cls, agent):
         func = getattr(agent, "_familiarity_func", None)
         cls._reject_banked(agent)
+        cls._reject_ncc(agent)
         cls._reject_others(agent)
         if getattr(getattr(agent, "familiarity_model", None), "metric", None) != cls._metric:
             raise ValueError("%s takes %s; NavEnsemble steps the library-based models" % (cls.__name__, cls._takes))
@@ -504,8 +510,10 @@ class _RouteEnsemble(_OneValueEnsemble):
 
     @classmethod
     def _reject_banked(cls, agent):
-        """(its own members are the banked ones; an SsdRouteEnsemble's carry a route of the view store, not a bank of this model)"""
-        if getattr(agent, "memory_bank", None) is not None and route_ensemble_name(agent) == "SsdRouteEnsemble" and cls.__name__ != "SsdRouteEnsemble":
+        """(its own members are the banked ones; an SsdRouteEnsemble's or NccRouteEnsemble's carry a route of the view store, not a bank
+        of this model)"""
+        name = route_ensemble_name(agent)
+        if getattr(agent, "memory_bank", None) is not None and name in ("SsdRouteEnsemble", "NccRouteEnsemble") and cls.__name__ != name:
             reject_banked(agent, cls.__name__)
 
     @classmethod
@@ -564,6 +572,7 @@ class _RouteEnsemble(_OneValueEnsemble):
         import copy
         if metrics not in cls.METRICS:
             raise ValueError("metrics must be one of %r, got %r" % (cls.METRICS, metrics))
+        cls._reject_ncc(agent)
         cls._reject_others(agent)
         model = getattr(agent, "familiarity_model", None)
         cls._check_model(model)
@@ -1293,6 +1302,8 @@ class SadsRouteEnsemble(_WindowedMembers, _RouteEnsemble):
             raise ValueError("SadsRouteEnsemble does not take an Infomax model: navsim_amd.InfomaxRouteEnsemble steps that one")
         if metric == "mushroom":
             raise ValueError("SadsRouteEnsemble does not take a mushroom-body model: navsim_amd.MushroomRouteEnsemble steps that one")
+        if metric == "ncc":
+            reject_ncc(model, "SadsRouteEnsemble")
         if metric is not None or not callable(getattr(model, "from_engine", None)) or getattr(model, "chem_weight", None) is None:
             if metric == "ssd":
                 raise ValueError("SadsRouteEnsemble takes %s; navsim_amd.SsdRouteEnsemble steps the SSD model" % cls._takes)
@@ -1471,6 +1482,8 @@ class SsdRouteEnsemble(_WindowedMembers, _RouteEnsemble):
                 raise ValueError("SsdRouteEnsemble does not take an Infomax model: navsim_amd.InfomaxRouteEnsemble steps that one")
             if metric == "mushroom":
                 raise ValueError("SsdRouteEnsemble does not take a mushroom-body model: navsim_amd.MushroomRouteEnsemble steps that one")
+            if metric == "ncc":
+                reject_ncc(obj, "SsdRouteEnsemble")
 
     @classmethod
     def _reject_banked(cls, agent):
@@ -1585,5 +1598,112 @@ class SsdRouteEnsemble(_WindowedMembers, _RouteEnsemble):
             a._scene_owner = None
             np.negative(row, out=a._scene_fam)                    # min over headings of -SSD = -(max over headings of SSD)
             self._mask_scene(a, t)
+
+    scene_familiarity = SadsRouteEnsemble.scene_familiarity
+
+
+class NccRouteEnsemble(_RouteEnsemble):
+    """The route ensemble of the correlation coefficient (util.ncc_familiarity(channel)): SsdRouteEnsemble without the window arguments,
+    for the metric that does not change with the gain and offset of a view.  The views of all routes lie in the engine's route view
+    store (FamiliarityEngine.rviews_set_from_poses: one call senses them all), and a step scores channel `channel` of every running
+    member's headings against the views of ITS OWN route in ONE device call (dv_rvncc_sense_step: SSD's int8 GEMM and a 64-bit
+    epilogue).  A member's angle_familiarity is a lone agent's row bit for bit, and ties go to the first heading as np.argmax decides
+    them.  A member's scene_familiarity is worked out when read (dv_rvncc_scene); its `memory_bank` is its route's place in the store.
+    All members share the model's one channel.  Made by from_routes / from_routes_with / from_landscapes (see _RouteEnsemble).
+    Not built: windows and re-localisation, a channel per member."""
+    _metric = "ncc"
+    _takes = "agents of the NCC model (familiarity_model=ncc_familiarity(channel))"
+    _info_call = "rviews_info"               # dict(n_routes, first int64[R + 1], shape, bytes)
+    _one_route = "a lone NavBySceneFamiliarity"
+
+    @classmethod
+    def from_agent(cls, agent, poses):
+        raise ValueError("NccRouteEnsemble is made from routes (from_routes): it takes an untrained agent and trains every route itself")
+
+    @classmethod
+    def _reject_ncc(cls, agent):
+        """(its own model)"""
+
+    @classmethod
+    def _reject_others(cls, agent):
+        for obj in (agent, getattr(agent, "familiarity_model", None), getattr(agent, "_familiarity_func", None)):
+            metric = getattr(obj, "metric", None)
+            if metric == "infomax":
+                raise ValueError("NccRouteEnsemble does not take an Infomax model: navsim_amd.InfomaxRouteEnsemble steps that one")
+            if metric == "mushroom":
+                raise ValueError("NccRouteEnsemble does not take a mushroom-body model: navsim_amd.MushroomRouteEnsemble steps that one")
+            if str(metric).startswith("ssd"):
+                raise ValueError("NccRouteEnsemble does not take an SSD model: navsim_amd.SsdRouteEnsemble steps that one")
+
+    @classmethod
+    def _reject_banked(cls, agent):
+        """Its own members are the banked ones; another route ensemble's are refused by name."""
+        if getattr(agent, "memory_bank", None) is not None and route_ensemble_name(agent) != cls.__name__:
+            reject_banked(agent, cls.__name__)
+
+    @classmethod
+    def _check_model(cls, model):
+        cls._reject_others(model)
+        if getattr(model, "metric", None) != "ncc" or getattr(model, "channel", None) not in (0, 1, 2):
+            if getattr(model, "metric", None) is None and getattr(model, "chem_weight", None) is not None:
+                raise ValueError("NccRouteEnsemble does not take a perfect-memory model: navsim_amd.SadsRouteEnsemble steps that one")
+            raise ValueError("NccRouteEnsemble takes %s" % cls._takes)
+
+    @classmethod
+    def _check_member(cls, agent):
+        func = getattr(agent, "_familiarity_func", None)
+        cls._reject_banked(agent)
+        cls._check_model(getattr(agent, "familiarity_model", None))
+        if getattr(agent, "_engine", None) is None:
+            raise ValueError("NccRouteEnsemble needs agents whose sensor model runs on the GPU (use_gpu_sensor=True)")
+        if agent.training_path is None or func is None or getattr(func, "engine", None) is not agent._engine:
+            raise ValueError("NccRouteEnsemble needs the members from_routes makes")
+
+    @staticmethod
+    def _begin_model(model, eng, agent):
+        """(nothing to begin: the store is made by the call that senses the routes)"""
+
+    _train_banks = staticmethod(SadsRouteEnsemble._train_banks)
+
+    def __init__(self, agents, metrics="host"):
+        channels = [getattr(getattr(a, "familiarity_model", None), "channel", None) for a in agents]
+        for i, ch in enumerate(channels):
+            if ch in (0, 1, 2) and ch != channels[0] and channels[0] in (0, 1, 2):
+                raise ValueError("NccRouteEnsemble: member %d compares channel %d, member 0 channel %d: the members of an ensemble share "
+                                 "one channel" % (i, ch, channels[0]))
+        super(NccRouteEnsemble, self).__init__(agents, metrics=metrics)
+        self.channel = int(channels[0])
+
+    @classmethod
+    def from_routes_with(cls, agent, routes, starts, metrics="host"):
+        """_RouteEnsemble.from_routes_with (there are no populations, and no windows)."""
+        return cls._from_routes(agent, list(routes), list(starts), metrics, None, None)
+
+    @classmethod
+    def from_landscapes(cls, agent, landscapes, routes, starts, metrics="host", sensors=None, noise=None):
+        """_RouteEnsemble.from_landscapes, sensors and noise included (there are no populations, and no windows)."""
+        return super(NccRouteEnsemble, cls).from_landscapes(agent, landscapes, routes, starts, metrics=metrics, sensors=sensors, noise=noise)
+
+    def _device_step(self, idx, xs, ys, angs):
+        lands = None if self._lands is None else self._lands[idx]
+        self._noise_begin_step(idx)
+        self._noise_set_rows([self.agents[i] for i in idx])
+        return self.engine.rvncc_sense_step(xs, ys, angs, self._banks[idx], self.channel, land_of_member=lands)
+
+    _note_scene = NavEnsemble._note_scene    # a per-view minimum to work out when read, not the one-value models' fill
+
+    def _read_scene(self):
+        todo = [a for a in self.agents if a._scene_stale is not None and a._scene_owner is self]
+        if not todo:
+            return
+        st = [a._scene_stale for a in todo]
+        lands = None if self._lands is None else [a.landscape_index for a in todo]
+        self._noise_set_rows(todo)                                # (the scene of the patches the last step scored: its keys)
+        rows = self.engine.rvncc_scene([t[0] for t in st], [t[1] for t in st], np.stack([t[2] for t in st]), [a.memory_bank for a in todo],
+                                       self.channel, land_of_member=lands)
+        for a, row in zip(todo, rows):
+            a._scene_stale = None
+            a._scene_owner = None
+            a._scene_fam[:] = row
 
     scene_familiarity = SadsRouteEnsemble.scene_familiarity

@@ -141,6 +141,65 @@ def ssd_familiarity(channel=2, device=0):
     return ssd_familiarity_internal
 
 
+def ncc_familiarity(channel=2, device=0):
+    """The correlation coefficient (zero-mean normalised cross-correlation) of one channel, the third perfect-memory metric of the
+    view-based navigation literature beside SADS and SSD, invariant to the gain and offset of a view -- as a familiarity plug-in of
+    the reference's shape (util.pyx:10-25):
+
+    stage 1  ncc_familiarity(channel)                  picks the compared channel of HSV scenes (0 H, 1 S, 2 V)
+    stage 2  model(scenes: uint8[F,h,w,3]) -> func     puts the scenes into a one-route view store (rviews_set_u8)
+    func(scene: uint8[h,w,3], fambuf: float64[F])      writes fambuf[f] = q(scene, view f) in place (rvncc_scene_u8 with one member and
+                                                       one heading): in [-1, 1], 0.0 where a plane is constant
+    func.max_familiarity = 1.0                         (an identical scene, or one that differs by a gain and an offset)
+
+    Extras carried by `func` for the agent's fused step: func.engine, func.metric ("ncc"), func.channel.
+    """
+    if channel not in (0, 1, 2):
+        raise ValueError("channel must be 0 (H), 1 (S) or 2 (V), got %r" % (channel,))
+
+    def bind(engine, scenes=None):
+        def func(scene, fambuf):
+            if not (isinstance(fambuf, np.ndarray) and fambuf.dtype == np.float64):
+                raise ValueError("Buffer dtype mismatch for fambuf, expected 'double'")
+            scene = np.asarray(scene)
+            fambuf[...] = engine.rvncc_scene_u8(scene.reshape((1, 1) + scene.shape), [0], channel)[0]
+
+        func.max_familiarity = 1.0
+        func.engine = engine
+        func.metric = "ncc"
+        func.channel = channel
+        return func
+
+    def ncc_familiarity_internal(scenes):
+        scenes = np.asarray(scenes)
+        if scenes.dtype != np.uint8:
+            raise ValueError("Buffer dtype mismatch, expected 'uint8_t' but got '%s'" % scenes.dtype)
+        engine = FamiliarityEngine(device=device)
+        try:
+            engine.rviews_set_u8(scenes, [0, len(scenes)])
+        except Exception:
+            engine.close()
+            raise
+        return bind(engine)
+
+    # hooks for navsim_amd.NavBySceneFamiliarity (landscape, sensor model and view store on the GPU: see sads_familiarity)
+    ncc_familiarity_internal.make_engine = lambda: FamiliarityEngine(device=device)
+    ncc_familiarity_internal.from_engine = bind
+    ncc_familiarity_internal.metric = "ncc"
+    ncc_familiarity_internal.channel = channel
+    return ncc_familiarity_internal
+
+
+def reject_ncc(model, what):
+    """Every ensemble but NccRouteEnsemble scores a view library, an Infomax matrix or a mushroom body: the NCC model's views lie in
+    the route view store and only navsim_amd.NccRouteEnsemble's step scores them there.  Raises ValueError for an NCC model (the
+    factory's product, its bound func, or an agent that carries one)."""
+    for obj in (model, getattr(model, "familiarity_model", None), getattr(model, "_familiarity_func", None)):
+        if getattr(obj, "metric", None) == "ncc":
+            raise ValueError("%s does not take an NCC model: ncc_familiarity scores the views of the route view store, which only "
+                             "navsim_amd.NccRouteEnsemble batches (or step each agent on its own engine)" % what)
+
+
 def reject_infomax(model, what):
     """The batched and multi-device forms score a library; the Infomax model has none.  Raises ValueError for an Infomax model (the
     factory's product, its bound func, or an agent that carries one)."""
@@ -159,6 +218,7 @@ def reject_mushroom(model, what):
             raise ValueError("%s does not take a mushroom-body model: it batches or shards a view library (or one Infomax weight "
                              "matrix), and mushroom_familiarity keeps neither (step each agent on its own engine, or use "
                              "navsim_amd.MushroomEnsemble)" % what)
+    reject_ncc(model, what)
 
 
 def route_ensemble_name(agent):
@@ -166,6 +226,8 @@ def route_ensemble_name(agent):
     metrics = [getattr(obj, "metric", None) for obj in (agent, getattr(agent, "familiarity_model", None), getattr(agent, "_familiarity_func", None))]
     if "infomax" in metrics:
         return "InfomaxRouteEnsemble"
+    if "ncc" in metrics:
+        return "NccRouteEnsemble"
     if any(str(m).startswith("ssd") for m in metrics if m is not None):
         return "SsdRouteEnsemble"                                 # (ssd_familiarity: "ssd", its bound func "ssd_u8")
     if all(m is None for m in metrics) and getattr(getattr(agent, "familiarity_model", None), "chem_weight", None) is not None:
@@ -177,7 +239,7 @@ def reject_banked(agent, what):
     """The refusal of every ensemble but the member's own route ensemble (navsim_amd.MushroomRouteEnsemble, InfomaxRouteEnsemble): the
     member's route is kept in a bank of its own (agent.memory_bank), and the other ensembles' steps score under the model's first bank."""
     if getattr(agent, "memory_bank", None) is not None:
-        if route_ensemble_name(agent) in ("SadsRouteEnsemble", "SsdRouteEnsemble"):
+        if route_ensemble_name(agent) in ("SadsRouteEnsemble", "SsdRouteEnsemble", "NccRouteEnsemble"):
             raise ValueError("%s does not take a member of a %s: its route is route %d of the engine's view store, "
                              "and only that ensemble's step scores it there" % (what, route_ensemble_name(agent), agent.memory_bank))
         raise ValueError("%s does not take a member of a %s: its route is kept in memory bank %d of the shared model, "

@@ -2,7 +2,7 @@
 """Times a step of the route view store (dv_rviews_sense_step, navsim_amd.SadsRouteEnsemble) at a slice of the reference's grid and
 writes profiles/rviews_time.json.
 
-    python tools/rviews_time.py [--sides 32,64] [--calls 30] [--reps 5] [--blocks routes[,sensors][,noise][,window][,reloc][,ssd][,ssdwin]] [--out profiles/rviews_time.json]
+    python tools/rviews_time.py [--sides 32,64] [--calls 30] [--reps 5] [--blocks routes[,sensors][,noise][,window][,reloc][,ssd][,ssdwin][,ncc]] [--out profiles/rviews_time.json]
 
 Shape: 4 routes x 8 starts x 10 headings = 32 trials of 320 columns, views of side x side.  The routes have the grid's length:
 synth.sin_training_path with arclen = step_size / n_test_angles (scripts/run_experiment.py:207) on a 900 x 900 landscape, one curve
@@ -57,7 +57,17 @@ planning launch, the cleared keys and the empty worst-case grid), reloc_4_lost_c
 reloc_all_lost_call_us -- and ensemble_step_wall_us per window (SsdRouteEnsemble(window=...).step_forward(fake=True), wall clock) beside
 the unwindowed ensemble's.  Whole-route windows on the shortest prefix, and the lost members' rows against the unwindowed call, are
 checked on their bits before anything is timed.  The block is the file's "ssdwin" key; measured alone it leaves every other key as it
-was."""
+was.
+
+NCC block (--blocks ncc): the same slice scored by the correlation coefficient (dv_rvncc_sense_step) against exact SSD
+(dv_rvssd_sense_step) at the same poses on the SAME engine and store, in alternating windows of one process, hipEvent pairs:
+ncc_call_us and ssd_call_us, their ratio, and ensemble_step_wall_us (NccRouteEnsemble.step_forward(fake=True), wall clock).  Two
+members' rows are checked on their bits against the NumPy statement on the store's own views before anything is timed.  The two scoring
+kernels' own times come from a kernel trace in a run of its own:
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/rviews_time.py --ncc-trace-run --sides 32
+    python tools/rviews_time.py --ncc-trace-stats DIR --sides 32   (the *kernel_stats.csv files under DIR -> the block's "kernel_trace" key,
+                                                                     a side at a time: a trace's rows do not tell the sizes apart)
+The block is the file's "ncc" key; measured alone it leaves every other key as it was."""
 import argparse
 import json
 import os
@@ -401,6 +411,126 @@ def measure_ssd(side, n_calls, reps):
     return out
 
 
+def ncc_statement(lib, pats):
+    """The correlation coefficient of every (patch, view) pair in NumPy: int64 sums, then one double product, one square root, one
+    quotient and the clip; 0.0 where a plane is constant.  lib int64[L, P], pats int64[A, P] -> float64[A, L]."""
+    P = lib.shape[1]
+    sa, sb = pats.sum(axis=1), lib.sum(axis=1)
+    num = P * (pats @ lib.T) - sa[:, None] * sb[None, :]
+    va, vb = P * (pats * pats).sum(axis=1) - sa * sa, P * (lib * lib).sum(axis=1) - sb * sb
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.clip(num.astype(np.float64) / np.sqrt(va.astype(np.float64)[:, None] * vb.astype(np.float64)[None, :]), -1.0, 1.0)
+    q[(va == 0)[:, None] | (vb == 0)[None, :]] = 0.0
+    return q
+
+
+def ncc_setup(side):
+    """The ncc block's ensemble of one side and its step arguments."""
+    import navsim_amd
+    from navsim_amd import synth
+    land = synth.synth_landscape(3, LAND, 4)
+    routes = [synth.sin_training_path(c, 0.2 * LAND, 0.6 * LAND, arclen=STEP_SIZE / HEADINGS) for c in CURVES]
+    starts = starts_of(routes)
+    a = navsim_amd.NavBySceneFamiliarity(land, (side, side), STEP_SIZE, n_test_angles=HEADINGS, track_scene_familiarity=False,
+                                         familiarity_model=navsim_amd.ncc_familiarity(SSD_CHANNEL))
+    ens = navsim_amd.NccRouteEnsemble.from_routes_with(a, routes, starts, metrics="device")
+    xs = np.array([p[0] for _, p, _ in starts])
+    ys = np.array([p[1] for _, p, _ in starts])
+    angs = (np.array([a for _, _, a in starts])[:, None] + ens.agents[0].angle_offsets[None, :]) % (2 * np.pi)
+    route_of = np.array([r for r, _, _ in starts], dtype=np.int32)
+    return ens, routes, xs, ys, angs, route_of
+
+
+def measure_ncc(side, n_calls, reps):
+    """The ncc block's row of one side."""
+    ens, routes, xs, ys, angs, route_of = ncc_setup(side)
+    eng = ens.engine
+    n = len(xs)
+
+    def ncc():
+        eng.timer_start()
+        for _ in range(n_calls):
+            res = eng.rvncc_sense_step(xs, ys, angs, route_of, SSD_CHANNEL)
+        return eng.timer_stop() * 1e3 / n_calls, res
+
+    def ssd():
+        eng.timer_start()
+        for _ in range(n_calls):
+            res = eng.rvssd_sense_step(xs, ys, angs, route_of, SSD_CHANNEL)
+        return eng.timer_stop() * 1e3 / n_calls, res
+
+    def wall():
+        w0 = time.perf_counter()
+        for _ in range(n_calls):
+            ens.step_forward(fake=True)
+        return (time.perf_counter() - w0) * 1e6 / n_calls
+
+    _, res = ncc()                                                # warm-up of both calls, and the NCC rows are the statement's bits
+    _, plain = ssd()
+    assert not res.flags.any() and not plain.flags.any()
+    for i in (0, n - 1):
+        lib = ens.agents[i].familiar_scenes[..., SSD_CHANNEL].reshape(len(routes[route_of[i]]), -1).astype(np.int64)
+        pats = eng.sense(np.full(HEADINGS, xs[i]), np.full(HEADINGS, ys[i]), angs[i])[..., SSD_CHANNEL].reshape(HEADINGS, -1).astype(np.int64)
+        rows = ncc_statement(lib, pats)
+        assert np.array_equal(res.angle_ncc[i].view(np.int64), rows.max(axis=1).view(np.int64)) and np.array_equal(res.angle_view[i], rows.argmax(axis=1))
+        assert res.best_idex[i] == int(np.argmax(rows.max(axis=1)))
+    wall()
+    assert len(ens.active) == n
+    t_ncc, t_ssd, w = [], [], []
+    for _ in range(reps):                                         # alternating windows
+        t_ncc.append(ncc()[0])
+        t_ssd.append(ssd()[0])
+        w.append(wall())
+    info = eng.rviews_info()
+    out = dict(side=side, routes=len(routes), route_views=[len(r) for r in routes], members=n, headings=HEADINGS, columns=n * HEADINGS,
+               channel=SSD_CHANNEL, calls_per_window=n_calls, windows=reps, store_bytes=info["bytes"], tile_columns=32,
+               view_groups_per_workgroup=4, ncc_call_us=spread(t_ncc), ssd_call_us=spread(t_ssd), ensemble_step_wall_us=spread(w),
+               ncc_over_ssd_call=round(float(np.median(t_ncc) / np.median(t_ssd)), 3))
+    eng.close()
+    return out
+
+
+def ncc_trace_run(sides, n_calls):
+    """What the kernel trace watches: n_calls of each call a side, after a warm-up call of each."""
+    for side in sides:
+        ens, _, xs, ys, angs, route_of = ncc_setup(side)
+        for _ in range(n_calls + 1):
+            ens.engine.rvncc_sense_step(xs, ys, angs, route_of, SSD_CHANNEL)
+            ens.engine.rvssd_sense_step(xs, ys, angs, route_of, SSD_CHANNEL)
+        ens.engine.close()
+    return 0
+
+
+def ncc_trace_stats(directory, out, side):
+    """The k_rvncc_* and k_rvssd_* rows of the trace's *kernel_stats.csv files under `directory`, a trace of --ncc-trace-run --sides
+    `side` -> the ncc block's "kernel_trace" key, under that side."""
+    import csv
+    import glob
+    rows = {}
+    for path in sorted(glob.glob(os.path.join(directory, "**", "*kernel_stats.csv"), recursive=True)):
+        with open(path) as f:
+            for r in csv.DictReader(f):
+                name = r["Name"].split("(")[0].replace("void ", "").replace("dv::", "")
+                if name.startswith(("k_rvncc_", "k_rvssd_")):
+                    rows[name] = dict(calls=int(r["Calls"]), average_us=round(float(r["AverageNs"]) / 1e3, 3), min_us=round(float(r["MinNs"]) / 1e3, 3),
+                                      max_us=round(float(r["MaxNs"]) / 1e3, 3))
+    if not rows:
+        print("no k_rvncc_* / k_rvssd_* rows under %s" % directory)
+        return 1
+    with open(out) as f:
+        doc = json.load(f)
+    trace = doc.setdefault("ncc", {}).setdefault("kernel_trace", dict(tool="rocprofv3 --kernel-trace --stats, a run of its own a side (--ncc-trace-run)",
+                                                                      sides={}))
+    score = {k: rows[k]["average_us"] for k in ("k_rvncc_score<0>", "k_rvssd_score<0>") if k in rows}
+    trace["sides"][str(side)] = dict(kernels=rows, ncc_over_ssd_score=round(score["k_rvncc_score<0>"] / score["k_rvssd_score<0>"], 3)
+                                     if len(score) == 2 else None)
+    with open(out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print(json.dumps(doc["ncc"]["kernel_trace"]))
+    return 0
+
+
 SSDWIN_WINDOWS = ((50, 50), (255, 256))
 
 
@@ -500,9 +630,15 @@ def main():
     ap.add_argument("--calls", type=int, default=30)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rviews_time.json"))
-    ap.add_argument("--blocks", default="routes", help="which blocks to measure: routes (the routed step against four engines), sensors, noise, window, reloc, ssd, ssdwin")
+    ap.add_argument("--blocks", default="routes", help="which blocks to measure: routes (the routed step against four engines), sensors, noise, window, reloc, ssd, ssdwin, ncc")
+    ap.add_argument("--ncc-trace-run", action="store_true", help="the ncc block's calls alone, for a kernel trace (no timing, no output file)")
+    ap.add_argument("--ncc-trace-stats", default=None, help="a kernel trace's output directory: its k_rvncc_* / k_rvssd_* rows go into the ncc block")
     ap.add_argument("--limit", type=int, default=240, help="seconds allowed to the GPU child of the sensors block and of the noise block")
     args = ap.parse_args()
+    if args.ncc_trace_run:
+        return ncc_trace_run([int(s) for s in args.sides.split(",")], args.calls)
+    if args.ncc_trace_stats:
+        return ncc_trace_stats(args.ncc_trace_stats, args.out, int(args.sides.split(",")[0]))
     blocks = args.blocks.split(",")
     kept = {}
     if os.path.exists(args.out):                                  # a block that is not measured keeps its rows
@@ -552,6 +688,13 @@ def main():
                              sizes=[measure_ssdwin(int(s), args.calls, args.reps) for s in args.sides.split(",")])
     elif "ssdwin" in kept:
         doc["ssdwin"] = kept["ssdwin"]
+    if "ncc" in blocks:                                           # a key of its own, as the window block's
+        if not ({"routes", "sensors", "noise", "window", "reloc", "ssd", "ssdwin"} & set(blocks)) and kept:
+            doc = dict(kept)
+        doc["ncc"] = dict(device=torch.cuda.get_device_name(0), channel=SSD_CHANNEL,
+                          sizes=[measure_ncc(int(s), args.calls, args.reps) for s in args.sides.split(",")])
+    elif "ncc" in kept:
+        doc["ncc"] = kept["ncc"]
     with open(args.out, "w") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")
